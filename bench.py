@@ -6,13 +6,13 @@ resolve -> extract -> CSR on the host) over one batch of synthetic collated RAD 
 resident in HBM.  The input is produced on the device itself by the Philox generator of
 csrc/afq_synth.hip (same bytes as its host twin, include/afquant_synth.h).
 
-  python bench.py --gpus N [--steps K --warmup W]
+  python bench.py --gpus N [--steps K --warmup W] [--full] [--dump-outputs DIR]
 
 With N > 1 and no torchrun environment the script spawns its own N ranks (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*), one per GPU, RCCL for the timing barrier and the scalar reductions;
 launched under torchrun it just joins as a rank.  Headline line = BASELINE.json configs[1]
 (PBMC-10k-like, cr-like), one such sample PER RANK (weak scaling: cells are independent, ranks share
-nothing on the data path).  The same JSON line carries further legs under "also":
+nothing on the data path).  With --full the same JSON line carries further legs under "also":
   configs2  configs[2]: USA, parsimony-em on the same cells (N = 1)
   configs1_tail / configs2_tail   the same two configurations under the label-length tail model (--na-model tail: E[na] ~ 3,
             labels of 5..30 refs on gene families), oracle-sampled, with the time per input byte against the plain model (N = 1)
@@ -24,6 +24,13 @@ nothing on the data path).  The same JSON line carries further legs under "also"
   cli       `afquant quant` wall on the same input written as a collated RAD directory (N = 1)
   reference the real `alevin-fry quant`, only if a binary is on the box ($ALEVIN_FRY_BIN / PATH)
 See DESIGN.md §6 for how roofline / cpu_baseline are built.
+
+A plain run (no --full) does only what the headline needs: it generates the input, warms up, times the K steps and prints the
+line (`roofline` included: it comes from the timed steps' own HIP events and the committed profiles).  --full adds everything
+else: the legs above (`--also` picks among them), the CPU baseline of every leg - the oracle on a sample of the same cells,
+which doubles as the full-size parity check - and the sanity checks of the rows.
+  --dump-outputs DIR   after the timed steps, what the last step handed its caller as DIR/<name>.npy (dump_outputs below);
+                       the input is seeded, so two builds run with the same arguments can be compared output for output
 """
 import argparse
 import importlib
@@ -72,15 +79,24 @@ def parse_args():
                     help="configs3: weak = c3-cells per GPU, strong = c3-cells in total, sharded over the ranks")
     ap.add_argument("--frags-per-cell", type=int, default=20000, help="atac")
     ap.add_argument("--atac-cells", type=int, default=10000, help="atac: cells per GPU (configs[4]: 10^4 x 2*10^4 records)")
-    ap.add_argument("--also", default="auto", help="comma list of extra legs (configs2,configs1_tail,configs2_tail,configs3,atac,e2e,cli,cli_sz,cli_pug,reference), 'auto' or 'none'")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the extra legs (--also), the CPU baseline / parity sample of every leg, the rows' sanity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 60 MB in all)")
+    ap.add_argument("--also", default="auto", help="--full: comma list of extra legs (configs2,configs1_tail,configs2_tail,configs3,atac,e2e,cli,cli_sz,cli_pug,reference), 'auto' (all) or 'none'")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline budget (rank 0, N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) by default; gloo + --share-gpu exercises the N>1 logic on a 1-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
     ap.add_argument("--plan-only", action="store_true",
                     help="no kernels: every rank prints the device bytes each leg would hold against the free memory of its GPU, the host its pinned "
                          "total against MemAvailable; exit code 0 when everything fits, 1 otherwise (the first thing to run on an 8-GPU node)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.also not in ("auto", "none") and not args.full and not args.plan_only:
+        ap.error("--also picks among the legs of --full: add --full")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -227,6 +243,52 @@ def sanity(res, rad):
     assert res.n_cells == len(rad.cell_nrec) and (np.diff(res.cell_ptr.astype(np.int64)) >= 0).all()
     assert (res.val > 0).all() and float(res.val.sum(dtype=np.float64)) <= rad.n_reads * (1 + 1e-6)
     assert np.array_equal(res.nrec, rad.cell_nrec)
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: at most this much in all (under 64 MB however a megabyte is counted)
+
+
+def dump_outputs(path, D, cell_ptr, per_cell, per_entry, value):
+    """--dump-outputs: the rows the timed path handed its caller in the last step, as DIR/<name>.npy (with N > 1 ranks:
+    DIR/rank<r>_<name>.npy).  Floats and integers of up to 16 bits become float32, wider integers float64 (exact below 2^53).
+    `cell_ptr` and the per_cell arrays (one entry per cell) are written whole.  The per_entry arrays (one entry per non-zero) are
+    too large for DUMP_BYTES at the headline's size (41 M non-zeros): `row_sum` (float64 sum of `value` over every cell's row)
+    covers every entry, and the rows of a fixed, seeded sample of cells are written whole as <name>_sample (`sample_cells`: the
+    cells, ascending; `sample_ptr`: CSR offsets into the samples)."""
+    import numpy as np
+
+    def flt(a):
+        a = np.asarray(a)
+        if a.dtype.kind == "f" or a.dtype.itemsize <= 2:
+            return a.astype(np.float32 if a.dtype.itemsize <= 4 else np.float64)
+        if a.dtype.itemsize == 8 and len(a) and int(a.max()) >= 1 << 53:
+            raise ValueError("a 64-bit output does not fit a float64 exactly")
+        return a.astype(np.float64)
+
+    cp = np.asarray(cell_ptr).astype(np.int64)
+    n = len(cp) - 1
+    lens = np.diff(cp)
+    out = {"cell_ptr": flt(cp), **{k: flt(v) for k, v in per_cell.items()}}
+    v64 = np.asarray(value, dtype=np.float64)
+    row_sum = np.zeros(n, np.float64)
+    if cp[-1]:
+        row_sum[lens > 0] = np.add.reduceat(v64, cp[:-1][lens > 0])
+    out["row_sum"] = row_sum
+    fixed = sum(a.nbytes for a in out.values()) + 16 * (n + 1) + 128 * (len(per_entry) + 8)   # (+ sample_cells / sample_ptr, .npy headers)
+    per = sum(flt(np.zeros(1, v.dtype)).itemsize for v in per_entry.values())
+    perm = np.random.default_rng(0).permutation(n)
+    k = int(np.searchsorted(np.cumsum(lens[perm]), max(0, DUMP_BYTES - fixed) // per, side="right"))
+    cells = np.sort(perm[:k])
+    take = np.concatenate([np.arange(cp[c], cp[c + 1]) for c in cells]) if k else np.zeros(0, np.int64)
+    out["sample_cells"] = cells.astype(np.float64)
+    out["sample_ptr"] = np.concatenate([[0], np.cumsum(lens[cells])]).astype(np.float64)
+    for name, a in per_entry.items():
+        out[name + "_sample"] = flt(np.asarray(a)[take])
+    assert sum(a.nbytes for a in out.values()) + 128 * len(out) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{D.rank}_" if D.world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(path, pre + name + ".npy"), a)
 
 
 # timers of the library that bracket several kernels: their bytes add up (the decode timer brackets whichever decoder ran)
@@ -537,8 +599,8 @@ def line(D, args, workload, value, elapsed, steps, warmup, cfgd, extra):
 
 
 # ---------------------------------------------------------------------------------------------------------
-def run_pbmc(D, args, pkg, sn, usa, resolution, steps, warmup, cpu_seconds, name, min_cells=0, tie_stats=False, tail=None, round_cells=None):
-    """configs[1] / configs[2]: one PBMC-10k-like sample per rank, generated in HBM."""
+def run_pbmc(D, args, pkg, sn, usa, resolution, steps, warmup, cpu_seconds, name, min_cells=0, tie_stats=False, tail=None, round_cells=None, dump=None):
+    """configs[1] / configs[2]: one PBMC-10k-like sample per rank, generated in HBM.  dump: --dump-outputs of the headline."""
     import numpy as np
 
     t0 = time.time()
@@ -550,11 +612,14 @@ def run_pbmc(D, args, pkg, sn, usa, resolution, steps, warmup, cpu_seconds, name
     q = pkg.Quantifier(cfg, rad.tid_to_gid, device=D.local_rank)
     try:
         elapsed, ktimes, res = timed_steps(D, q, rad, steps, warmup)
+        if dump:
+            dump_outputs(dump, D, res.cell_ptr, {"bc": res.bc, "nrec": res.nrec, "flags": res.flags}, {"gene": res.gene, "val": res.val}, res.val)
         total_reads, total_cells = D.reduce([rad.n_reads, args.cells], "sum")
         if D.rank != 0:
             return None, rad, q
         st = q.batch_stats()
-        sanity(res, rad)
+        if args.full:
+            sanity(res, rad)
         nnz = int(res.cell_ptr[-1])
         alg = float(st["input_bytes"]) + 8.0 * nnz
         sizes_default = (args.cells, args.median_reads, args.sigma, args.genes, args.ref_count, args.popularity, args.umi_err) == \
@@ -566,7 +631,7 @@ def run_pbmc(D, args, pkg, sn, usa, resolution, steps, warmup, cpu_seconds, name
             ttag = "configs2_tail" if tailed else "configs2"
         roof = roofline_of(ktimes, alg, steps, ttag, 1e3 * elapsed / steps)
         cpu = None
-        if D.world == 1 and not args.no_cpu_baseline and cpu_seconds > 0:
+        if D.world == 1 and args.full and not args.no_cpu_baseline and cpu_seconds > 0:
             cpu = cpu_leg(cfg, rad, res, cpu_seconds, min_cells=min_cells, tie_stats=tie_stats, round_cells=round_cells)
         cfgd = {"workload": f"{name}: PBMC-10k-like 10x-v3 collated RAD, {resolution}, per GPU: {args.cells} cells, log-normal reads/cell "
                             f"median {args.median_reads:g} sigma {args.sigma:g}, {args.genes} genes / {len(rad.tid_to_gid)} transcripts, "
@@ -594,7 +659,7 @@ def run_pbmc(D, args, pkg, sn, usa, resolution, steps, warmup, cpu_seconds, name
         raise
 
 
-def run_configs3(D, args, pkg, sn, steps, warmup):
+def run_configs3(D, args, pkg, sn, steps, warmup, dump=None):
     """configs[3]: ~10^6 cells x 2*10^4 reads, cr-like, cells range-sharded over the ranks.  The data set is one Philox
     stream over GLOBAL cell indices; every rank makes its own byte-balanced range of it directly in HBM."""
     import numpy as np
@@ -618,8 +683,11 @@ def run_configs3(D, args, pkg, sn, steps, warmup):
     q = pkg.Quantifier(cfg, rad.tid_to_gid, device=D.local_rank)
     try:
         elapsed, ktimes, res = timed_steps(D, q, rad, steps, warmup, first_cell=c0)
-        sanity(res, rad)
-        assert res.first_cell_index == c0
+        if dump:
+            dump_outputs(dump, D, res.cell_ptr, {"bc": res.bc, "nrec": res.nrec, "flags": res.flags}, {"gene": res.gene, "val": res.val}, res.val)
+        if args.full:
+            sanity(res, rad)
+            assert res.first_cell_index == c0
         st = q.batch_stats()
         nnz = int(res.cell_ptr[-1])
         tot_reads, tot_cells, tot_bytes, tot_nnz = D.reduce([rad.n_reads, c1 - c0, st["input_bytes"], nnz], "sum")
@@ -628,7 +696,7 @@ def run_configs3(D, args, pkg, sn, steps, warmup):
         # parity at the shard's size: the oracle on every k-th cell of THIS rank's shard (each rank checks its own), rows
         # compared bit for bit; rank 0's timing is the reported cpu_baseline
         cpu = None
-        if not args.no_cpu_baseline and args.cpu_seconds > 0:
+        if args.full and not args.no_cpu_baseline and args.cpu_seconds > 0:
             cpu = cpu_leg(cfg, rad, res, min(args.cpu_seconds, 8.0), min_cells=500,
                           n_threads=max(1, (os.cpu_count() or 1) // D.world))
             if D.world > 1:
@@ -908,7 +976,7 @@ def main():
     sn = importlib.import_module("alevin-fry_amd.synth_native")
     if args.workload == "atac":
         return bench_atac(args, pkg, D)
-    also = args.also.split(",") if args.also not in ("auto", "none") else \
+    also = [] if not args.full else args.also.split(",") if args.also not in ("auto", "none") else \
         ([] if args.also == "none" else (["configs2", "configs1_tail", "configs2_tail", "configs3", "atac", "e2e", "cli", "cli_sz", "cli_pug", "reference"] if D.world == 1 else ["e2e", "configs3", "atac"]))
     also = [a for a in also if a and a != args.workload]
     legs = {}
@@ -916,13 +984,13 @@ def main():
     rad = q = None
     try:
         if args.workload == "configs3":
-            out = run_configs3(D, args, pkg, sn, args.steps, args.warmup)
+            out = run_configs3(D, args, pkg, sn, args.steps, args.warmup, dump=args.dump_outputs)
         else:
             usa = args.usa or args.workload == "configs2"
             resolution = args.resolution or ("parsimony-em" if args.workload == "configs2" else "cr-like")
             name = "configs[2]" if (usa and resolution == "parsimony-em") else "configs[1]"
             out, rad, q = run_pbmc(D, args, pkg, sn, usa, resolution, args.steps, args.warmup, args.cpu_seconds, name,
-                                   min_cells=200 if name == "configs[2]" else 0, tie_stats=name == "configs[2]")
+                                   min_cells=200 if name == "configs[2]" else 0, tie_stats=name == "configs[2]", dump=args.dump_outputs)
 
         def leg(name, fn):
             try:
@@ -1050,7 +1118,7 @@ def main():
         D.close()
 
 
-def run_atac(args, pkg, D, steps, warmup):
+def run_atac(args, pkg, D, steps, warmup, dump=None):
     """BASELINE configs[4]: scATAC fragment / barcode de-duplication from collated-RAD bytes (afq_atac_dedup_rad): the record
     walk with the na == 1 && type == 4 filter, the per-cell sort and the run-length count all on the device.  The chunk
     bytes are resident in HBM when the timed region starts (uploaded once); a step ends with the distinct fragments on the
@@ -1089,6 +1157,8 @@ def run_atac(args, pkg, D, steps, warmup):
                 a[1] += nl
         torch.cuda.synchronize(D.dev)
         elapsed = time.perf_counter() - t0
+        if dump:
+            dump_outputs(dump, D, res[0], {"bc": res[1]}, {"ref": res[2], "start": res[3], "frag_len": res[4], "count": res[5]}, res[5])
         if D.dist:
             D.dist.barrier()
         elapsed = D.reduce([elapsed], "max")[0]
@@ -1098,7 +1168,7 @@ def run_atac(args, pkg, D, steps, warmup):
         distinct = int(res[0][-1])
         alg = float(len(data)) + 12.0 * distinct   # every record byte once; (ref, start, len, count) per distinct fragment out
         cpu = None
-        if D.world == 1 and not args.no_cpu_baseline:
+        if D.world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as ora
             from concurrent.futures import ThreadPoolExecutor
@@ -1146,7 +1216,7 @@ def run_atac(args, pkg, D, steps, warmup):
 
 
 def bench_atac(args, pkg, D):
-    out = run_atac(args, pkg, D, args.steps, args.warmup)
+    out = run_atac(args, pkg, D, args.steps, args.warmup, dump=args.dump_outputs)
     if D.rank == 0:
         print(json.dumps(out), flush=True)
     D.close()

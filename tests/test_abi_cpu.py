@@ -21,6 +21,8 @@ def test_library_exports_every_symbol():
         import __graft_entry__ as ge  # noqa
 
         ge.build()
+    pkg.load_library()   # (first: it brings torch's HIP runtime up before the library maps one - afquant.load_library; a bare dlopen
+    #                       first leaves the process with two runtimes, and every later test of the process finds no GPU)
     lib = ctypes.CDLL(path)
     for name in pkg._abi.EXPORTS:
         assert hasattr(lib, name), name
@@ -60,6 +62,7 @@ def test_every_declared_function_of_every_header_is_exported():
     """include/*.h (boundary, host front-end, synthetic generator): each declared function is in the library."""
     import glob
 
+    pkg.load_library()   # (torch's HIP runtime first, as above)
     lib = ctypes.CDLL(pkg.afquant.LIB_PATH)
     n = 0
     for path in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):

@@ -296,7 +296,7 @@ def test_bench_spawns_its_own_ranks():
     both on cuda:0 over gloo, tiny workloads; the driver's run uses one GPU per rank and RCCL)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--cells", "300", "--median-reads", "2000", "--c3-cells", "2000", "--c3-mean-reads", "300", "--also", "e2e,configs3"]
+           "--cells", "300", "--median-reads", "2000", "--c3-cells", "2000", "--c3-mean-reads", "300", "--full", "--also", "e2e,configs3"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -337,7 +337,7 @@ def test_bench_eight_ranks_bookkeeping_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
            "--cells", "200", "--median-reads", "1500", "--c3-cells", "4000", "--c3-mean-reads", "300", "--atac-cells", "60", "--frags-per-cell", "400",
-           "--cpu-seconds", "1", "--also", "e2e,configs3,atac"]
+           "--cpu-seconds", "1", "--full", "--also", "e2e,configs3,atac"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -350,10 +350,10 @@ def test_bench_eight_ranks_bookkeeping_on_one_gpu():
 
 
 def test_bench_single_gpu_legs_small():
-    """The default legs on a small workload: configs[2] with its tie report, configs[3], the PCIe-inclusive figure, the CLI wall."""
+    """The legs of --full on a small workload: configs[2] with its tie report, configs[3], the PCIe-inclusive figure, the CLI wall."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cells", "400", "--median-reads", "3000",
-           "--c3-cells", "3000", "--c3-mean-reads", "400", "--cpu-seconds", "2"]
+           "--c3-cells", "3000", "--c3-mean-reads", "400", "--cpu-seconds", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -363,6 +363,30 @@ def test_bench_single_gpu_legs_small():
         assert k in also and "error" not in also[k], (k, also.get(k))
     assert also["configs2"]["cpu_baseline"]["parsimony_ties"]["molecules"] > 0
     assert also["e2e"]["value"] > 0 and also["cli"]["wall_s"] > 0
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_rows(tmp_path):
+    """A plain run (no --full): the headline line alone, --steps timed steps; --dump-outputs writes the last step's rows as float
+    .npy files, and two runs with the same arguments write the same files (the input is seeded)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cells", "300", "--median-reads", "2000",
+               "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "also" not in line and line["cpu_baseline"] is None and line["config"]["workload"].startswith("configs[1]")
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert {"cell_ptr.npy", "bc.npy", "row_sum.npy", "sample_cells.npy", "gene_sample.npy", "val_sample.npy"} <= set(files)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    cp = np.load(tmp_path / "a" / "cell_ptr.npy")
+    assert len(cp) == 301 and cp[-1] == line["nnz"] and len(np.load(tmp_path / "a" / "sample_cells.npy")) == 300
 
 
 def test_reference_binary_hook(tmp_path, oracle):

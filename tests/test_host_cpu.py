@@ -331,6 +331,9 @@ int main() {
         const uint32_t G = usa ? 2 * (3 + rng() % 6) : 4 + rng() % 8;
         const uint32_t rows = usa ? (G / 2) * 3 - (it % 5 == 0 ? 2 : 0) : G - (it % 5 == 0 ? 1 : 0);   // (now and then a column out of range: the error path)
         uint32_t la[64], da[64], lb[64], db[64], ca[4] = {0, 0, 0, 0}, cb[4] = {0, 0, 0, 0};
+        // (both sides start from the same words: on the error path neither function writes all the words compared below, which
+        //  must then compare equal instead of comparing what the stack held; a word only one side writes still differs)
+        for (uint32_t* w : {la, da, lb, db}) std::fill(w, w + 64, 0xDEADBEEFu);
         PugCtx A{nullptr, 1, (uint32_t)usa, (uint32_t)em, rows, ((G / 2) * 3) / 3, 2 * (((G / 2) * 3) / 3), (uint32_t)(it % 7 == 0 ? 3 : 40), la, da, ca};
         PugCtx B = A; B.labw = lb; B.labd = db; B.s_cnt = cb;
         const uint32_t len = 5 + rng() % 4;
