@@ -156,6 +156,7 @@ struct RangeState {
     const PfDev* pf_stats_src = nullptr; uint64_t pf_stats_reads = 0, pf_stats_parts = 0;   // AFQ_TEST_PF_STATS
     uint32_t hash_try = 0;   // which salt the range's label hashes were made with (a collision re-runs the range under the next)
     uint32_t pool_try = 0;   // how often the range was run again with four times the parsimony pool (a cell's graph outgrew it)
+    uint64_t epool_words = 0;   // the parsimony pool the range's current attempt planned (words; 0: no parsimony cell)
     uint64_t att_records = 0, att_ref_words = 0, att_buckets = 0;   // what the current attempt added to the batch statistics
     bool chained = false;    // the rows' compaction was enqueued behind the range's kernels (row offsets made on the device, k_row_ptr) ...
     uint64_t chain_cap = 0;  // ... against d_gene / d_val of this many entries: finish_range compacts again, after growing them, if the range has more
@@ -229,6 +230,7 @@ struct afq_ctx {
     uint64_t n_em_resized = 0;     // ranges whose EM scratch was sized on the host after the device-side plan did not fit
     bool handback_seen = false;    // the phase kernels have handed a cell back to the one-workgroup kernel in some range of this context
     uint32_t retry_cuts = 0;       // how many times the range being finished has been cut around a failing cell (finish_range)
+    uint32_t retry_halvings = 0, retry_halving_cap = 0;   // ... halved after a range-wide failure, and how often it may be (finish_range)
     std::vector<TimedLaunch> launches;
     std::vector<hipEvent_t> event_pool;
     double k_ms[K_COUNT] = {0};
@@ -483,7 +485,7 @@ static uint64_t label_mask(uint32_t hash_try) {
     return ~0ull;
 }
 constexpr uint32_t kMaxHashTries = 4;
-constexpr uint32_t kMaxPoolTries = 3;   // 32 words per read x 4^3
+constexpr uint32_t kMaxPoolTries = 3;   // 24 words per read x 4^3
 
 // Reads that carry many alignments carry many genes: most UMIs then outgrow the three gene counters of a slot of k_resolve's
 // UMI table and their buckets end up sorted after the table has been tried.  Such ranges (two or more alignment words per
@@ -676,6 +678,9 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     //  and a first parsimony range of a PBMC-10k sample is 5 GB of hipMalloc less)
     const uint64_t pool_words_per_read = [] { const long v = test_hook_long("POOL_WORDS", 0); return v >= 12 && v <= 32 ? (uint64_t)v : 24ull; }();   // (tests: a small first pool; read per range - a test sets it for itself)
     const uint64_t epool_words = ((pool_words_per_read * n_pug_reads + (pool_words_per_read >= 24 ? (1ull << 22) : (1ull << 20))) << (2 * pool_try));
+    B.epool_words = n_pug ? epool_words : 0;
+    if (n_pug && pool_room_words() && epool_words > pool_room_words())   // (tests: a device without room for this pool - refused as hipMalloc would, before allocating)
+        return fail(c, AFQ_ERR_OOM, "no room for a parsimony pool of " + std::to_string(epool_words) + " words (AFQ_TEST_POOL_ROOM_WORDS)");
     if (n_pug) {
         HIP_TRY(c, B.d_pug_cells.ensure(4ull * n_pug));
         HIP_TRY(c, B.d_rd_off.ensure(8ull * n));
@@ -991,47 +996,70 @@ int finish_range(afq_ctx* c, int slot) {
         for (TimedLaunch& t : B.launches) recycle_events(c, t);   // (back to the pool, not into the kernel times)
         B.launches.clear();
     };
-    // A label-hash collision or a graph that outgrew the pool names its cell.  The range is cut around that cell: the cells before
-    // and behind it run again as they were, the cell itself ALONE under the next hash function / with four times the pool - a pool
-    // for one cell, not for the range (a range sized to fill the device cannot have its pool quadrupled), and the other cells keep
-    // their hashes.  Every cut costs the range a re-run, so a range that keeps failing (every cell of it dense, or - in the tests -
-    // every label colliding) goes back to the round-3 answer after three cuts: the whole range under the next setting.
+    // A label-hash collision names its cell: the range is cut around it - the cells before and behind it run again as they were,
+    // the cell itself ALONE under the next hash function, and the other cells keep their hashes.  Every cut costs the range a
+    // re-run, so a range that keeps failing (in the tests: every label colliding) goes back to the round-3 answer after three
+    // cuts: the whole range under the next hash function.
+    // A pool that ran out names no cell (kCellRangeWide): the pool is one bump allocator for the range, and the request that
+    // failed is whichever came last, not the graph that used the space.  The whole range runs again with four times the pool;
+    // when the device has no room for that (a range sized to fill the device), the range is HALVED, and each half runs again
+    // with the pool it had - a half that fails again regrows or is halved in turn, down to a single cell, which takes the four
+    // times larger pool of its own.  The same halving answers the range-wide graph build's size limit (kErrPugLimit of the
+    // whole range: 2^31 vertices with an edge), for which a larger pool is no help.
+    const bool wide = st.err_cell == kCellRangeWide;
     const bool rehash = st.err_code == kErrLabelHash && B.hash_try + 1 < kMaxHashTries;
     const bool regrow = st.err_code == kErrPugPool && B.pool_try < kMaxPoolTries;
-    if (rehash || regrow) {
-        (rehash ? c->n_label_rehash : c->n_pool_regrow) += 1;
+    const bool wide_limit = st.err_code == kErrPugLimit && wide && n > 1;
+    if (rehash || regrow || wide_limit) {
+        if (rehash) c->n_label_rehash += 1; else if (regrow) c->n_pool_regrow += 1;
         take_back_attempt();
         const Range whole = B.cur;
-        const uint32_t ht = B.hash_try, pt = B.pool_try, bad = whole.c0 + std::min(st.err_cell, whole.c1 - whole.c0 - 1);
+        const uint32_t ht = B.hash_try, pt = B.pool_try;
         int rc = 0;
-        // A label-hash collision names its cell.  A pool that ran out names the cell that asked LAST, not the one whose graph outgrew
-        // it (the pool is one bump allocator for the range): the whole range runs again with four times the pool, and only when the
-        // device has no room for that is the range cut - around the named cell for want of a better one; a hog that fails again in its
-        // part is cut again (three cuts at most, then the round-3 answer: the error).
-        bool cut = rehash;
+        bool halve = wide_limit;
         if (regrow) {
             // (a range sized to fill the device has no room for four times its pool: ask before trying - a failed hipMalloc frees the
-            //  pool, costs a full set-up and leaves hipErrorOutOfMemory as the runtime's last error, which the next range would report)
+            //  pool, costs a full set-up and leaves hipErrorOutOfMemory as the runtime's last error, which the next range would report.
+            //  Four times the pool THIS attempt planned: a half of a range holds the whole range's pool, which may already suffice)
             size_t free_b = 0, total_b = 0;
-            const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b + (double)B.d_epool.cap > 4.2 * (double)B.d_epool.cap;
-            if (room) {
+            const double need = 16.0 * (double)B.epool_words;
+            const bool room = pool_room_words() ? 4 * B.epool_words <= pool_room_words()
+                                                : need <= (double)B.d_epool.cap ||
+                                                      (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b + (double)B.d_epool.cap > 1.05 * need);
+            if (room || n == 1) {   // (a single cell has nothing left to halve: its larger pool or the error)
                 rc = run_range(c, whole, slot, nullptr, ht, pt + 1);
                 if (!rc) rc = finish_range(c, slot);
             } else rc = AFQ_ERR_OOM;
-            if (rc == AFQ_ERR_OOM) { cut = true; rc = 0; (void)hipGetLastError(); { std::lock_guard<std::mutex> g(c->err_mu); c->err.clear(); } }
+            if (rc == AFQ_ERR_OOM && n > 1) { halve = true; rc = 0; (void)hipGetLastError(); { std::lock_guard<std::mutex> g(c->err_mu); c->err.clear(); } }
         }
-        if (cut && whole.c1 - whole.c0 > 1 && c->retry_cuts < 3) {
+        if (halve) {
+            // (at most ceil(log2(cells)) + 2 nested halvings of the range that failed first: enough to reach a single cell)
+            if (c->retry_halvings == 0) { uint32_t lg = 0; while ((1ull << lg) < n) ++lg; c->retry_halving_cap = lg + 2; }
+            if (c->retry_halvings < c->retry_halving_cap) {
+                c->retry_halvings += 1;
+                const uint32_t mid = whole.c0 + n / 2;
+                const Range parts[2] = {{whole.c0, mid}, {mid, whole.c1}};
+                for (int k = 0; k < 2 && !rc; ++k) {
+                    rc = run_range(c, parts[k], slot, nullptr, ht, pt);
+                    if (!rc) rc = finish_range(c, slot);
+                }
+                c->retry_halvings -= 1;
+            } else if (regrow) {   // (not reached: the halvings reach a single cell first)
+                rc = run_range(c, whole, slot, nullptr, ht, pt + 1);
+                if (!rc) rc = finish_range(c, slot);
+            } else rc = fail(c, AFQ_ERR_UNSUPPORTED, "cells " + std::to_string(whole.c0) + ".." + std::to_string(whole.c1 - 1) + ": the range-wide graph build's limit of 2^31 vertices was exceeded");
+        } else if (rehash && n > 1 && c->retry_cuts < 3) {
+            const uint32_t bad = whole.c0 + std::min(st.err_cell, n - 1);
             c->retry_cuts += 1;
             const Range parts[3] = {{whole.c0, bad}, {bad, bad + 1}, {bad + 1, whole.c1}};
             for (int k = 0; k < 3 && !rc; ++k) {
                 if (parts[k].c1 == parts[k].c0) continue;
-                const bool the_cell = k == 1;
-                rc = run_range(c, parts[k], slot, nullptr, ht + (the_cell && rehash ? 1 : 0), pt + (the_cell && regrow ? 1 : 0));
+                rc = run_range(c, parts[k], slot, nullptr, ht + (k == 1 ? 1 : 0), pt);
                 if (!rc) rc = finish_range(c, slot);
             }
             c->retry_cuts -= 1;
-        } else if (cut) {
-            rc = run_range(c, whole, slot, nullptr, ht + (rehash ? 1 : 0), pt + (regrow ? 1 : 0));
+        } else if (rehash) {
+            rc = run_range(c, whole, slot, nullptr, ht + 1, pt);
             if (!rc) rc = finish_range(c, slot);
         }
         if (regrow) B.d_epool.release();   // the enlarged pool is that attempt's alone: the next range plans its own
@@ -1053,7 +1081,8 @@ int finish_range(afq_ctx* c, int slot) {
         return rc;
     }
     if (st.err_code) {
-        const std::string cell = "cell " + std::to_string(B.cur.c0 + st.err_cell) + ": ";
+        const std::string cell = st.err_cell == kCellRangeWide ? "cells " + std::to_string(B.cur.c0) + ".." + std::to_string(B.cur.c1 - 1) + ": "
+                                                               : "cell " + std::to_string(B.cur.c0 + st.err_cell) + ": ";
         switch (st.err_code) {
             case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, cell + "chunk nbytes does not match its records");
             case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, cell + "ref id out of range");

@@ -2,9 +2,13 @@
 //
 // AFQ_TEST_<NAME>: routing overrides and sizes that tests/ flips to reach every code path on inputs of a few thousand reads
 // (which decoder, which parsimony route, how small a slab or a pool, where a range is cut).  A hook changes WHICH path
-// computes the rows, never the rows: every one of them is exercised by a parity test against the oracle.  Rounds 1-4 had
-// grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not kept; those
-// alternatives are gone (a measurement build is `make variant DEFS=...`), and what is left besides the hooks is:
+// computes the rows, never the rows: every one of them is exercised by a parity test against the oracle.  Among them:
+//   AFQ_TEST_POOL_WORDS=n        the parsimony pool is planned at n (12..32) words per read instead of 24: graphs outgrow it
+//   AFQ_TEST_POOL_ROOM_WORDS=n   the device holds a parsimony pool of at most n words: run_range refuses a larger one with
+//                                AFQ_ERR_OOM before it allocates, and finish_range's room check answers as such a device would -
+//                                the no-room re-runs of a range whose graphs outgrew its pool, on a test box that always has room
+// Rounds 1-4 had grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not
+// kept; those alternatives are gone (a measurement build is `make variant DEFS=...`), and what is left besides the hooks is:
 //   AFQ_EM_ORDER=canonical   the sequential f32 EM of rounds 1-3, bit-identical to the reference's arithmetic
 //   AFQ_HOST_TIMING=1        where the host side of a batch spends its time, on stderr
 #pragma once
@@ -20,6 +24,8 @@ inline const char* test_hook(const char* name) {
 }
 inline long test_hook_long(const char* name, long dflt) { const char* e = test_hook(name); return e ? atol(e) : dflt; }
 inline bool test_hook_is(const char* name, const char* v) { const char* e = test_hook(name); return e && !strcmp(e, v); }
+// AFQ_TEST_POOL_ROOM_WORDS: 0 (unset) = the device's own free memory decides
+inline unsigned long long pool_room_words() { const long v = test_hook_long("POOL_ROOM_WORDS", 0); return v > 0 ? (unsigned long long)v : 0ull; }
 inline bool em_order_canonical() { const char* e = getenv("AFQ_EM_ORDER"); return e && !strcmp(e, "canonical"); }
 
 }  // namespace afq

@@ -596,7 +596,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                 pair_cap = 2 * V + 4096;
                 if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 2ull * pair_cap + 2);
                 __syncthreads();
-                if (s_ebase + 2ull * pair_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+                if (s_ebase + 2ull * pair_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
                 pairs = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
               if (!s_flag[1]) {
                 uint64_t* t_key = reinterpret_cast<uint64_t*>(s_big);
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         const uint32_t cand_cap = 4 * V + 4096;
         if (tid == 0) { s_ebase = atomicAdd(A.epool_cursor, 2ull * cand_cap + 2); s_flag[1] = 0; }
         __syncthreads();
-        if (s_ebase + 2ull * cand_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+        if (s_ebase + 2ull * cand_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
         cand = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
         auto append = [&](uint64_t c) {   // called under divergence: the active lanes share one reservation
             const uint64_t am = __ballot(true);
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
             const uint32_t cand_off = block_excl_scan<kPugNT>(ncand_mine, s_ws, NCAND);
             if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 2ull * NCAND + 2);
             __syncthreads();
-            if (s_ebase + 2ull * NCAND + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+            if (s_ebase + 2ull * NCAND + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
             cand = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
             uint32_t o = cand_off;
             for (uint32_t x = tid; x < V; x += kPugNT) {
@@ -908,7 +908,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     pair_cap = NCAND + V;
     if (tid == 0) { s_ebase = atomicAdd(A.epool_cursor, 2ull * pair_cap + 2); s_flag[0] = 0; }
     __syncthreads();
-    if (s_ebase + 2ull * pair_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+    if (s_ebase + 2ull * pair_cap + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
     pairs = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
     }
     // Two stages, each with four independent load chains per thread (a probe of the vertex table or of a
@@ -1021,7 +1021,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         s_ebase = atomicAdd(A.epool_cursor, (unsigned long long)E);
     }
     __syncthreads();
-    if (s_ebase + E > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+    if (s_ebase + E > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
     uint32_t* edges = A.epool + s_ebase;
     if (lds_deg) {
         for (uint32_t w = tid; w < (V + 1) / 2; w += kPugNT) cw[w] = 0;   // the counters again, as fill cursors
@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, (unsigned long long)E);
         for (uint32_t i = tid; i < NT; i += kPugNT) { wl[i] = i; local_idx[tl[i]] = i; }
         __syncthreads();
-        if (s_ebase + E > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+        if (s_ebase + E > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
         uint32_t* pedge = A.epool + s_ebase;   // edge targets as positions in tl
         for (uint32_t i = tid; i < NT; i += kPugNT) {
             const uint32_t x = tl[i];
@@ -1341,7 +1341,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     }
     if (tid == 0) { mid_off[n_mid] = S_mid; s_ebase = atomicAdd(A.epool_cursor, 9ull * S_mid + 4); }
     __syncthreads();
-    if (s_ebase + 9ull * S_mid + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+    if (s_ebase + 9ull * S_mid + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
     uint4* mrec = reinterpret_cast<uint4*>(A.epool + ((s_ebase + 3) & ~3ull));   // two per vertex: {vid, label length, ref0 | ptr lo, ref1 | ptr hi}, {ref2, ref3, adjacency}
     uint32_t* slot_comp = reinterpret_cast<uint32_t*>(mrec + 2 * (size_t)S_mid);
     for (uint32_t ci = tid; ci < n_mid; ci += kPugNT) {
@@ -1402,7 +1402,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
             (void)block_excl_scan<kPugNT>(cnt, s_ws, tot);
             if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 4ull * tot + 4);
             __syncthreads();
-            if (s_ebase + 4ull * tot + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+            if (s_ebase + 4ull * tot + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
             uint4* trip = reinterpret_cast<uint4*>(A.epool + ((s_ebase + 3) & ~3ull));
             if (tid == 0) s_flag[1] = 0;
             __syncthreads();
@@ -1482,7 +1482,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         const uint32_t nw = (n + 63) / 64;
         if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 2ull * n * nw + 2);
         __syncthreads();
-        if (s_ebase + 2ull * n * nw + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, cell); return; }
+        if (s_ebase + 2ull * n * nw + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
         uint64_t* rows = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
         for (uint32_t i = tid; i < n * nw; i += kPugNT) rows[i] = 0;
         for (uint32_t i = tid; i < n; i += kPugNT) local_idx[vid_at(c0 + i)] = i;

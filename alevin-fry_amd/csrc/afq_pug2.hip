@@ -364,7 +364,7 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
         unsigned long long base = 0;
         if (lane == 0) base = atomicAdd(A.pool_cur, 2ull * np + 2);
         base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-        if (base + 2ull * np + 2 > A.pool_cap) { if (lane == 0) { set_err(A.st, kErrPugPool, c.cell); A.pnp[gp] = 0; } return; }   // (the host runs the cell again with a larger pool)
+        if (base + 2ull * np + 2 > A.pool_cap) { if (lane == 0) { set_err(A.st, kErrPugPool, kCellRangeWide); A.pnp[gp] = 0; } return; }   // (the host runs the range again with a larger pool, or in halves)
         base = (base + 1) & ~1ull;
         if (lane == 0) ppair[0] = base;
         ppair = reinterpret_cast<uint64_t*>(A.pool + base);
@@ -951,7 +951,7 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
     if (2 * P > GLds) {
         if (tid == 0) s_ebase = atomicAdd(A.pool_cur, 2ull * P + 4);
         gsync();
-        if (s_ebase + 2ull * P + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, c.cell); return; }
+        if (s_ebase + 2ull * P + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
         ppre = A.pool + s_ebase;
         gsync();
     }
@@ -988,7 +988,7 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         gsync();
         if (tid == 0) s_ebase = atomicAdd(A.pool_cur, words + 4);
         gsync();
-        if (s_ebase + words + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, c.cell); return nullptr; }
+        if (s_ebase + words + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return nullptr; }
         return A.pool + ((s_ebase + 3) & ~3ull);
     };
     uint32_t* q = pool_take(2ull * n_pairs);
@@ -1475,7 +1475,7 @@ __device__ __forceinline__ bool cover_large(const P2Args& A, const PugCtx& C, co
         __syncthreads();
         if (tid == 0) { *s_base = atomicAdd(A.pool_cur, 4ull * tot + 4); *s_nt = 0; }
         __syncthreads();
-        if (*s_base + 4ull * tot + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, c.cell); return false; }
+        if (*s_base + 4ull * tot + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return false; }
         uint4* trip = reinterpret_cast<uint4*>(A.pool + ((*s_base + 3) & ~3ull));   // (umi, 0, gene, reads)
         for (uint32_t i = tid; i < n; i += CNT) {
             const uint32_t g = tl[lg_v[v0 + i]];

@@ -17,7 +17,10 @@
 //                                 slots those take; a cell with a larger component is routed to the per-cell kernel (rare).  The
 //                                 scan of the tile counts IS the layout: a cell's tiles are consecutive, so every cell's
 //                                 components become a contiguous run of the range-wide lists (pairs | 3..8 | 9..64) and every
-//                                 tile knows where its roots' entries go - no counter, no atomic, the same lists every run.
+//                                 tile knows where its roots' entries go - no counter, no atomic: every run puts the same
+//                                 components at the same list entries.  (Not the same records inside them: a vertex's place in its
+//                                 component is its turn at atomicAdd(&V.cnt[root]) in k_pf_root, which differs from run to run.
+//                                 The rows do not: ties are set aside and settled in a fixed order, and the EM sums are order-free.)
 //   k_pf_cells                    a workgroup per cell: the descriptor the cover kernels read, the lone vertices' staged classes
 //                                 into the cell's label area.
 //   k_pf_alloc / k_pf_place       roots take their list entry and record slots, vertices write their 32-byte cover records: label,
@@ -26,8 +29,8 @@
 //                                 vertices' UMIs, reads and labels (umi_edge, afq_pug_common.h) - a pass over the pair list with two
 //                                 atomics per pair into 32-byte records (0.64 ms per launch) is what that replaces.
 //
-// The covers (k_p2_cover, k_p2_tied) then read per-cell descriptors exactly as the per-cell graph kernel wrote them: records in
-// slot order, ties set aside (kCoverDefer).
+// The covers (k_p2_cover, k_p2_tied) then read per-cell descriptors exactly as the per-cell graph kernel wrote them, ties set
+// aside (kCoverDefer) - but a component's records in the order k_pf_root's atomics gave them, not in slot order.
 //
 // Coherence.  The eight XCDs' L2s are not coherent with each other, and a range-wide kernel's workgroups run on all of them:
 // every word that several workgroups change inside ONE kernel is changed with agent-scope atomics only (they execute at the
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(1024) void k_pf_scan2(P2Args A, uint32_t q0) {
     if (q0 == 0) {   // T vertices have an edge: their dense arrays
         const unsigned long long T = s_tot[0], words = 10 * T + 16;
         const unsigned long long base = atomicAdd(A.pool_cur, words);
-        if (base + words > A.pool_cap || T >= (1u << 31)) { set_err(A.st, T >= (1u << 31) ? kErrPugLimit : kErrPugPool, 0); D.T = 0; return; }
+        if (base + words > A.pool_cap || T >= (1u << 31)) { set_err(A.st, T >= (1u << 31) ? kErrPugLimit : kErrPugPool, kCellRangeWide); D.T = 0; return; }
         unsigned long long o = (base + 3) & ~3ull;
         D.lh = o; o += 2 * T;   // (8-byte entries first: o is a multiple of four words)
         D.par = o; o += T; D.cnt = o; o += T; D.rk = o; o += T; D.umi = o; o += T; D.rc = o; o += T; D.tl = o; o += T; D.loff = o; o += T; D.tcell = o;
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_pf_scan2(P2Args A, uint32_t q0) {
         const unsigned long long NP = s_tot[0], NC = (unsigned long long)s_tot[1] + s_tot[Q >= 5 ? 2 : 0], S = (unsigned long long)s_tot[Q >= 5 ? 3 : 0] + s_tot[Q >= 5 ? 4 : 0];
         const unsigned long long words = 2 * NP + 4 + (NC + 4) + 8 * S + 8 + 4 * (NC + A.n_cells) + 8 + NC / 2 + 4 + S + 4;
         const unsigned long long base = atomicAdd(A.pool_cur, words);
-        if (base + words > A.pool_cap || S >= (1ull << 32)) { set_err(A.st, kErrPugPool, 0); return; }
+        if (base + words > A.pool_cap || S >= (1ull << 32)) { set_err(A.st, kErrPugPool, kCellRangeWide); return; }
         unsigned long long o = (base + 3) & ~3ull;
         D.mrec = o; o += 8 * S + 4;            // (16-byte aligned: uint4 records)
         D.prv = o; o += 2 * NP + 2;
@@ -415,7 +418,7 @@ __global__ __launch_bounds__(256) void k_pf_union(P2Args A) {
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            if (sp[r] && (tx[r] >= V.T || ty[r] >= V.T)) { set_err(A.st, kErrInternal, 0); sp[r] = nullptr; }
+            if (sp[r] && (tx[r] >= V.T || ty[r] >= V.T)) { set_err(A.st, kErrInternal, kCellRangeWide); sp[r] = nullptr; }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) { px[r] = sp[r] ? ag_ld(&par[tx[r]]) : 0u; py[r] = sp[r] ? ag_ld(&par[ty[r]]) : 0u; }
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(256) void k_pf_cells(P2Args A) {
     d[12] = c.R; d[13] = w0; d[14] = d0;
     uint32_t* tp = A.pool + tied;
     tp[0] = 0; tp[1] = 0; tp[2] = 0; tp[3] = 0;
-    d[0] = 7u;   // the lists are there (1), in slot order (2: kCoverDefer), records with (UMI, reads) in place of adjacency masks (4)
+    d[0] = 7u;   // the lists are there (1), ties set aside (2: kCoverDefer; a component's records are in k_pf_root's atomic order, not slot order), records with (UMI, reads) in place of adjacency masks (4)
 }
 
 // ... and a thread per tile: where the tile's slices of the lists lie, gathered once (the workgroups that take a tile - k_pf_alloc, the

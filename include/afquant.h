@@ -282,10 +282,11 @@ int afq_get_batch_stats(afq_ctx* ctx, afq_batch_stats* out);
    detected on the device, and the range of cells is then decoded again with another hash function instead of being refused
    (the reference keys its map by the list itself, eq_class.rs:859-903).  How often that happened since afq_create. */
 uint64_t afq_label_rehash_count(const afq_ctx* ctx);
-/* Parsimony: the per-cell graphs are built in a pool sized by the range's reads (32 words per read).  A cell whose graph
-   outgrows it (short UMIs: hundreds of reads per UMI, so a vertex has many neighbours) makes the library run the range
-   again with four times the pool, up to three times, before AFQ_ERR_OOM (the reference allocates per graph,
-   pugutils.rs:65-267).  How often that happened since afq_create. */
+/* Parsimony: the per-cell graphs are built in a pool sized by the range's reads (24 words per read).  A range whose graphs
+   outgrow it (short UMIs: hundreds of reads per UMI, so a vertex has many neighbours) is run again with four times the pool,
+   up to three times, or - when the device has no room for that - in halves, down to a single cell with four times a pool of
+   its own, before AFQ_ERR_OOM (the reference allocates per graph, pugutils.rs:65-267).  How often a range (or a part of one)
+   failed that way since afq_create. */
 uint64_t afq_pool_regrow_count(const afq_ctx* ctx);
 /* EM resolutions: ranges whose EM did not fit the device scratch set aside for it ahead of time and was sized on the host
  * instead (one extra trip to the host for that range; results identical).  Diagnostics only. */
