@@ -143,7 +143,7 @@ struct Range { uint32_t c0, c1; };
 struct RangeState {
     hipStream_t stream = nullptr;
     DevBuf d_meta, d_keys0, d_keys1, d_cell_nkeys, d_bucket_cnt, d_bucket_cell, d_multi_cells, d_tile_desc, d_src_off, d_slab_ovf, d_ncols,
-        d_nnz, d_ovf, d_status, d_bc, d_cell_ptr, d_gene, d_val, d_chk, d_slab_prefix, d_slab_cell, d_cell_bc, d_bdesc, d_lab,
+        d_nnz, d_ovf, d_status, d_bc, d_cell_ptr, d_gene, d_val, d_chk, d_slab_prefix, d_slab_cell, d_cell_bc, d_div, d_lab,
         d_lab_cnt, d_em_off, d_em_scratch, d_em_nnz, d_pug_cells, d_rd_off, d_rd_h, d_rd_u, d_rd_o, d_pug_scr_off,
         d_pug_scratch, d_epool, d_epool_cur, d_alt, d_hist_cells, d_fix, d_em_hdr, d_em_order, d_eq_ncls, d_eq_nw, d_eq_cptr,
         d_p2_small, d_eq_wptr, d_eq_len, d_eq_cnt, d_eq_lab, d_bt_off, d_bt_scratch, d_bt_ns, d_bt_col, d_bt_mean, d_bt_var, d_bt_sptr, d_bt_ccol,
@@ -168,7 +168,7 @@ struct RangeState {
     std::vector<DevBuf*> all() {
         return {&d_meta, &d_keys0, &d_keys1, &d_cell_nkeys, &d_bucket_cnt, &d_bucket_cell, &d_multi_cells, &d_tile_desc, &d_src_off, &d_slab_ovf,
                 &d_ncols, &d_nnz, &d_ovf, &d_status, &d_bc, &d_cell_ptr, &d_gene, &d_val, &d_chk, &d_slab_prefix, &d_slab_cell,
-                &d_cell_bc, &d_bdesc, &d_lab, &d_lab_cnt, &d_em_off, &d_em_scratch, &d_em_nnz, &d_pug_cells, &d_rd_off, &d_rd_h,
+                &d_cell_bc, &d_div, &d_lab, &d_lab_cnt, &d_em_off, &d_em_scratch, &d_em_nnz, &d_pug_cells, &d_rd_off, &d_rd_h,
                 &d_rd_u, &d_rd_o, &d_pug_scr_off, &d_pug_scratch, &d_epool, &d_epool_cur, &d_p2_small, &d_alt, &d_hist_cells, &d_fix, &d_em_hdr, &d_em_order,
                 &d_eq_ncls, &d_eq_nw, &d_eq_cptr, &d_eq_wptr, &d_eq_len, &d_eq_cnt, &d_eq_lab, &d_bt_off, &d_bt_scratch, &d_bt_ns, &d_bt_col,
                 &d_bt_mean, &d_bt_var, &d_bt_sptr, &d_bt_ccol, &d_bt_cmean, &d_bt_cvar, &d_em2_off, &d_em2_scratch, &d_em2_tiers, &d_arena};
@@ -227,6 +227,7 @@ struct afq_ctx {
     uint64_t n_label_rehash = 0;   // ranges decoded again under another label-hash salt (life of the context)
     uint64_t n_pool_regrow = 0;    // ranges run again with a larger parsimony pool
     uint64_t n_mono_cells = 0;     // parsimony cells resolved by the one-workgroup kernel (sent there directly, or handed back by the phase kernels)
+    uint64_t n_divert = 0;         // buckets the hash resolve of the last batch handed to the sort path
     uint64_t n_em_resized = 0;     // ranges whose EM scratch was sized on the host after the device-side plan did not fit
     bool handback_seen = false;    // the phase kernels have handed a cell back to the one-workgroup kernel in some range of this context
     uint32_t retry_cuts = 0;       // how many times the range being finished has been cut around a failing cell (finish_range)
@@ -632,7 +633,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     HIP_TRY(c, B.d_ncols.ensure(4ull * n));
     HIP_TRY(c, B.d_nnz.ensure(4ull * n));
     HIP_TRY(c, B.d_ovf.ensure(sizeof(OverflowEnt) * std::max<uint64_t>(n_buckets, 1)));
-    HIP_TRY(c, B.d_bdesc.ensure(bucket_desc_bytes() * std::max<uint64_t>(n_buckets, 1)));
+    HIP_TRY(c, B.d_div.ensure(4 * std::max<uint64_t>(n_buckets, 1)));
     const bool em = g.resolution == AFQ_RES_CR_LIKE_EM || g.resolution == AFQ_RES_PARSIMONY_EM || g.resolution == AFQ_RES_PARSIMONY_GENE_EM;
     const uint32_t n_pug = (uint32_t)pug_cells.size();
     const uint32_t n_pug_blocks = std::min<uint32_t>(n_pug, pug_max_blocks());
@@ -820,12 +821,13 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     ResolveArgs ra{B.d_meta.as<CellMeta>(), B.d_bucket_cell.as<uint32_t>(), B.d_multi_cells.as<uint32_t>(),
                    B.d_tile_desc.as<uint2>(), B.d_cell_nkeys.as<uint32_t>(), B.d_bucket_cnt.as<uint32_t>(),
                    B.d_keys0.as<uint64_t>(), B.d_keys1.as<uint64_t>(), B.d_ncols.as<uint32_t>(),
-                   B.d_nnz.as<uint32_t>(), B.d_ovf.as<OverflowEnt>(), B.d_bdesc.p, em ? B.d_lab.as<uint32_t>() : nullptr,
+                   B.d_nnz.as<uint32_t>(), B.d_ovf.as<OverflowEnt>(), B.d_div.as<uint32_t>(), em ? B.d_lab.as<uint32_t>() : nullptr,
                    em ? B.d_lab_cnt.as<uint32_t>() : nullptr, B.d_status.as<DevStatus>(),
                    (uint32_t)n_buckets, n_multi, (uint32_t)n_tiles, B.d_hist_cells.as<uint32_t>(),
                    (uint32_t)hist_cells.size(), g.usa_mode, g.num_rows,
                    (g.usa_mode && g.sa_model == AFQ_SA_PREFER_AMBIG) ? 1u : 0u, max_lg_nb, B.d_slab_ovf.as<uint32_t>(), slabs ? 1u : 0u,
-                   resolve_sort_only(key_off - n, nrec_total)};
+                   resolve_sort_only(key_off - n, nrec_total), g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u,
+                   test_hook_is("RESOLVE_DIVERT", "all") ? 1u : 0u};
     if (n_multi) {
         if (!slabs) {
             tc.seg(K_HIST); launch_hist(s, ra);
@@ -1098,6 +1100,7 @@ int finish_range(afq_ctx* c, int slot) {
     }
     c->stats.n_keys += st.n_keys;
     c->stats.n_overflow_buckets += st.n_overflow;
+    c->n_divert += st.n_divert;
     c->stats.n_fallback_cells += st.n_fallback;
     c->n_mono_cells += B.h_pack.p[9];
     std::vector<uint32_t> nnz(n);
@@ -1395,6 +1398,7 @@ int begin_batch(afq_ctx* c, uint32_t n_cells, uint64_t first_cell_index) {
     if (c->cfg.dump_eq) { c->res->eq_cell_ptr.push_back(0); c->res->eq_label_ptr.push_back(0); }
     if (c->cfg.num_bootstraps) { c->res->bm_ptr.push_back(0); c->res->bv_ptr.push_back(0); }
     c->stats = afq_batch_stats{};
+    c->n_divert = 0;
     c->stats.input_bytes = c->n_bytes;
     for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
     c->h2d_piped = false;
@@ -1453,6 +1457,7 @@ uint64_t afq_label_rehash_count(const afq_ctx* ctx) { return ctx ? ctx->n_label_
 uint64_t afq_pool_regrow_count(const afq_ctx* ctx) { return ctx ? ctx->n_pool_regrow : 0; }
 uint64_t afq_em_resize_count(const afq_ctx* ctx) { return ctx ? ctx->n_em_resized : 0; }
 uint64_t afq_mono_cell_count(const afq_ctx* ctx) { return ctx ? ctx->n_mono_cells : 0; }
+uint64_t afq_resolve_divert_count(const afq_ctx* ctx) { return ctx ? ctx->n_divert : 0; }
 
 int afq_device_pci_bus_id(int device, char* out, size_t out_len) {
     if (!out || out_len < 13) return AFQ_ERR_INVALID_ARG;

@@ -54,8 +54,10 @@ struct DevStatus {
     uint32_t err_cell;
     uint32_t n_overflow;     // buckets larger than kBucketCap
     uint32_t n_fallback;     // cells re-decoded by the sequential walk
+    uint32_t n_divert;       // buckets the hash resolve handed to the sort path (k_resolve_sort's list)
     unsigned long long n_keys;
 };
+static_assert(sizeof(DevStatus) <= 32, "the packed status block holds 8 words (kPackHdrWords layout)");
 
 // Per-cell verification block of the walk-free decode (k_decode_par): the candidate
 // record starts it used are exactly the sequential parse iff ok==0, count==nrec and

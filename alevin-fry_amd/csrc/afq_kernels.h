@@ -44,7 +44,7 @@ struct ResolveArgs {
     uint32_t* cell_ncols;  // per-cell length of the resolved-column list (multi-bucket cells)
     uint32_t* nnz;
     OverflowEnt* ovf_list;
-    void* bucket_desc;     // [n_buckets] x bucket_desc_bytes()
+    uint32_t* div_list;    // [n_buckets] buckets the hash kernel hands to the sort path (count: DevStatus::n_divert)
     uint32_t* lab;         // EM modes: label area, 2 words per key slot (null otherwise)
     uint32_t* lab_cnt;     // EM modes: per cell (label words, ambiguous molecules)
     DevStatus* st;
@@ -60,6 +60,8 @@ struct ResolveArgs {
     uint32_t* slab_ovf;          // fixed-slab placement: per cell, set when one of its buckets outgrew its slab (the cell is then placed exactly)
     uint32_t slabs;              // the range's multi-bucket cells use fixed slabs (no k_hist / k_bucket_scan)
     uint32_t sort_only;          // reads of the range average two or more alignments: buckets are resolved by sorting, not through the UMI table
+    uint32_t trivial;            // the batch resolves `trivial`: its buckets (but those of tiny cells) are the sort path's
+    uint32_t divert_all;         // tests (AFQ_TEST_RESOLVE_DIVERT=all): every bucket through the divert list to the sort path
 };
 
 // one launch that clears / fills a range's small buffers (k_range_init): dst <- zeros (src_off == ~0) or arena[src_off ...)
@@ -85,7 +87,6 @@ void launch_hist(hipStream_t s, const ResolveArgs& a);
 void launch_bucket_scan(hipStream_t s, const ResolveArgs& a);
 void launch_fix_slabs(hipStream_t s, const ResolveArgs& a);
 void launch_scatter(hipStream_t s, const ResolveArgs& a);
-size_t bucket_desc_bytes();
 uint64_t em_scratch_words(uint32_t nU, uint32_t W, uint32_t M, bool usa);
 void launch_em(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, const uint64_t* em_off, uint32_t* scratch,
                uint32_t* out_nnz, void* em_hdr /* 16 B per cell */, const uint32_t* em_order /* cells, largest first */,

@@ -2,8 +2,9 @@
 // (replaces src/quant.rs:469-657 / src/pugutils.rs:644-850 / src/utils.rs:673-756 of the reference;
 // semantics: SURVEY.md appendix B.2):
 //   k_hist, k_bucket_scan, k_scatter   keys -> per-(cell, UMI-hash bucket) ranges (LDS histogram / multisplit)
-//   k_bucket_desc, k_resolve           one wave per bucket: LDS hash table keyed by UMI (or register bitonic
-//                                      sort), per-UMI arg-max with ties, USA slot rules, cr-like-em class staging
+//   k_resolve_hash                     one wave per bucket: LDS hash table keyed by UMI, per-UMI arg-max with ties,
+//                                      USA slot rules, cr-like-em class staging; other buckets onto a divert list
+//   k_resolve_sort                     one wave per (diverted) bucket: LDS bitonic sort + run-length resolve
 //   k_resolve_mid, k_resolve_big       the sort path for buckets beyond one wave / beyond LDS
 //   k_cell_hist                        per-cell LDS histogram of the resolved columns -> (column, count) pairs
 //   k_compact                          per-cell pairs -> final CSR
@@ -228,6 +229,7 @@ struct ResolveCfg {
     uint32_t pa;    // --sa-model prefer-ambig (USA only): reads of a UMI are tallied per gene, S and U together
     uint32_t sort_only;   // the batch's reads carry many genes each: the UMI table's three counters per slot would overflow for
                           // most UMIs (and the bucket then be sorted anyway) - every bucket takes the sort path straight away
+    uint32_t divert;      // tests (AFQ_TEST_RESOLVE_DIVERT=all): the hash kernel hands every bucket to the sort-path kernel
 };
 __device__ __forceinline__ bool mode_is_em(uint32_t mode) { return mode == kModeCrLikeEm; }
 
@@ -337,8 +339,9 @@ __device__ __forceinline__ void resolve_sorted(const uint64_t* keys, uint32_t n,
 }
 
 // ---------------------------------------------------------------------------
-// Per-bucket descriptors: everything a resolve workgroup needs in one 32-byte load
-// (instead of the dependent chain bucket -> cell -> meta -> cursor -> keys).
+// What a resolve workgroup needs to know about its bucket.  (Until round 7 a kernel of its own, k_bucket_desc, wrote these for
+// every bucket of the range - a launch and 32 bytes per bucket in front of the resolve; the chain bucket -> cell -> meta -> cursor
+// is wave-uniform, so the kernels that read a descriptor now make it themselves out of scalar loads.)
 struct BucketDesc {
     uint64_t src_off;  // first key of the bucket: slot in keys1 (multi-bucket cell) or keys0 (single)
     uint64_t out_off;  // the cell's key_off (column list / pair staging live in its keys0 slots)
@@ -348,23 +351,28 @@ struct BucketDesc {
     uint32_t n_ref;        // the cell's key capacity (locates its label area)
 };
 
-__global__ void k_bucket_desc(const CellMeta* __restrict__ meta, const uint32_t* __restrict__ bucket_cell,
-                              const uint32_t* __restrict__ cell_nkeys, const uint32_t* __restrict__ cursor,
-                              const uint32_t* __restrict__ slab_ovf, uint32_t n_buckets, BucketDesc* __restrict__ desc) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_buckets) return;
-    const uint32_t cell = bucket_cell[b];
-    const CellMeta m = meta[cell];
+// where the descriptor of a bucket comes from
+struct DescSrc {
+    const CellMeta* meta;
+    const uint32_t* bucket_cell;
+    const uint32_t* cell_nkeys;
+    const uint32_t* cursor;
+    const uint32_t* slab_ovf;
+};
+
+__device__ __forceinline__ BucketDesc bucket_desc(const DescSrc& ds, uint32_t b) {
+    const uint32_t cell = ds.bucket_cell[b];
+    const CellMeta m = ds.meta[cell];
     BucketDesc d;
     d.cell = cell; d.out_off = m.key_off; d.n_ref = m.n_ref;
-    if (m.lg_nb == 0) { d.mode_single = m.mode | 0x100u; d.src_off = m.key_off; d.n = mode_is_pug(m.mode) ? 0u : cell_nkeys[cell]; }
-    else if (m.slab_cap && !slab_ovf[cell]) {   // fixed slabs: the cursor is the bucket's count
-        d.mode_single = m.mode; d.src_off = m.k1_off + (uint64_t)(b - m.bucket_base) * m.slab_cap; d.n = mode_is_pug(m.mode) ? 0u : cursor[b];
+    if (m.lg_nb == 0) { d.mode_single = m.mode | 0x100u; d.src_off = m.key_off; d.n = mode_is_pug(m.mode) ? 0u : ds.cell_nkeys[cell]; }
+    else if (m.slab_cap && !ds.slab_ovf[cell]) {   // fixed slabs: the cursor is the bucket's count
+        d.mode_single = m.mode; d.src_off = m.k1_off + (uint64_t)(b - m.bucket_base) * m.slab_cap; d.n = mode_is_pug(m.mode) ? 0u : ds.cursor[b];
     } else {
-        const uint32_t beg = (b == m.bucket_base) ? 0u : cursor[b - 1];
-        d.mode_single = m.mode; d.src_off = (m.slab_cap ? m.k1_off : m.key_off) + beg; d.n = mode_is_pug(m.mode) ? 0u : cursor[b] - beg;
+        const uint32_t beg = (b == m.bucket_base) ? 0u : ds.cursor[b - 1];
+        d.mode_single = m.mode; d.src_off = (m.slab_cap ? m.k1_off : m.key_off) + beg; d.n = mode_is_pug(m.mode) ? 0u : ds.cursor[b] - beg;
     }
-    desc[b] = d;
+    return d;
 }
 
 // Where a cell's gene-level classes (EM modes) are collected: lab[2*key_off ...] holds the label
@@ -491,7 +499,9 @@ __device__ __forceinline__ void resolve_bucket_lds(const BucketDesc& d, uint64_t
 // of a sort.  Anything the slots cannot express (a UMI seen with more than kHtPairs genes, a UMI that does
 // not fit 32 bits) sends the whole bucket down the sort path - same result, just slower.
 constexpr uint32_t kHtKeys = 256;            // buckets up to this many keys take the table (nearly all: the planner aims at kBucketTarget)
-constexpr uint32_t kHtCap = kHtKeys + kHtKeys / 2;   // slots: load factor <= 2/3 (of distinct UMIs, usually far fewer than keys)
+// slots: load factor <= 4/5 (of distinct UMIs, usually far fewer than keys).  (1.5 n until round 7: 1.25 n probes longer, but its
+// 5.7 KiB of LDS let seven hash workgroups share a SIMD instead of six - k_resolve_hash 602 -> 557 us per launch.)
+constexpr uint32_t kHtCap = kHtKeys + kHtKeys / 4;
 constexpr uint32_t kHtPairs = 3;
 constexpr uint32_t kNoCol = 0xFFFFFFFFu;
 static_assert(kHtKeys < (1u << 12), "per-bucket read counts fit the 12-bit counter");
@@ -608,12 +618,13 @@ __device__ __forceinline__ uint32_t em_from_pairs(uint32_t p0, uint32_t p1, uint
 // One wave, n <= kHtKeys.  Slot = one 64-bit word (umi:32 | gene:20 | reads:12) holding the UMI and its first
 // gene's counter - a UMI seen with one gene, the common case, costs one CAS plus one add per further read - and
 // kHtPairs-1 more (gene | reads) counters.  The lane whose CAS claims a slot owns that UMI and resolves it.
-// On success the bucket's columns are in s_cols[0..nc) and true is returned.
+// On success col[h] holds the column of the UMI whose slot the lane claimed in round h (kNoCol: none) and true is returned.
+constexpr uint32_t kHtRounds = kHtKeys / 64;
 __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__ src, uint32_t n, const ResolveCfg& rc,
                                                     unsigned long long* s_slot, uint32_t* s_pair, uint64_t* s_ovf,
-                                                    uint32_t* s_flag, uint32_t* s_novf, uint32_t* s_cols, DevStatus* st,
-                                                    uint32_t cell, uint32_t& nc_out, bool em, const EmStage& es) {
-    constexpr uint32_t E = kHtKeys / 64;
+                                                    uint32_t* s_flag, uint32_t* s_novf, DevStatus* st,
+                                                    uint32_t cell, uint32_t (&col_out)[kHtRounds], bool em, const EmStage& es) {
+    constexpr uint32_t E = kHtRounds;
     constexpr unsigned long long kEmpty64 = ~0ull;
     const uint32_t lane = threadIdx.x;
 #ifdef AFQ_RESOLVE_TIMING
@@ -622,7 +633,7 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     uint64_t key[E];
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) key[h] = h * 64 + lane < n ? AFQ_LD_RESOLVE(&src[h * 64 + lane]) : 0ull;
-    uint32_t cap = (n + (n >> 1) + 63) & ~63u;   // multiples of 64 slots: 1.5 n rounded up
+    uint32_t cap = (n + (n >> 2) + 63) & ~63u;   // multiples of 64 slots: 1.25 n rounded up
     cap = cap < 128 ? 128 : cap;
     {
         uint4* u4 = reinterpret_cast<uint4*>(s_slot);
@@ -687,7 +698,8 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     __syncthreads();
     RT_MARK(1);
     const uint32_t novf = *s_novf;
-    uint32_t nc = 0;
+#pragma unroll
+    for (uint32_t h = 0; h < E; ++h) col_out[h] = kNoCol;
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) {
         if (h * 64 >= n) break;
@@ -745,14 +757,11 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
             }
             if (col != kNoCol && col >= rc.num_rows) { set_err(st, kErrSlotRange, cell); col = kNoCol; }
         }
-        const uint64_t m = __ballot(col != kNoCol);
-        if (col != kNoCol) s_cols[nc + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = col;
-        nc += (uint32_t)__popcll(m);
+        col_out[h] = col;
     }
     if (__any(bad)) return false;  // a UMI with more genes than the merge holds: nothing global was written yet
-    __syncthreads();
+    if (em) __syncthreads();       // (the staged labels are read back by other lanes)
     RT_MARK(2);
-    nc_out = nc;
     return true;
 }
 
@@ -767,10 +776,11 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
 constexpr uint32_t kH2Cap = kHtKeys + kHtKeys / 2;
 static_assert(kHtKeys < (1u << 10), "resolve_bucket_hash2 packs a UMI's winner count and its spliced-winner count into 10-bit fields of agg");
 static_assert(kHtKeys < (1u << 12), "... and the reads of a (UMI, gene) pair into 12 bits of the T1 / T2 words");
-constexpr uint32_t kH2Words = 2 * kH2Cap /* T1 */ + 2 * kH2Cap /* T2 key | max */ + 3 * kH2Cap /* agg, gmin, smin */ + kHtKeys /* columns */;
+constexpr uint32_t kH2Words = 2 * kH2Cap /* T1 */ + 2 * kH2Cap /* T2 key | max */ + 3 * kH2Cap /* agg, gmin, smin */;
+// On success col[h] holds the column of the UMI whose T2 slot the lane claimed in round h (kNoCol: none).
 __device__ __forceinline__ bool resolve_bucket_hash2(const uint64_t* __restrict__ src, uint32_t n, const ResolveCfg& rc, uint32_t* s_raw,
-                                                     DevStatus* st, uint32_t cell, uint32_t& nc_out, uint32_t*& s_cols_out) {
-    constexpr uint32_t E = kHtKeys / 64;
+                                                     DevStatus* st, uint32_t cell, uint32_t (&col_out)[kHtRounds]) {
+    constexpr uint32_t E = kHtRounds;
     constexpr unsigned long long kEmpty64 = ~0ull;
     const uint32_t lane = threadIdx.x;
     unsigned long long* t1 = reinterpret_cast<unsigned long long*>(s_raw);
@@ -778,7 +788,6 @@ __device__ __forceinline__ bool resolve_bucket_hash2(const uint64_t* __restrict_
     uint32_t* agg = s_raw + 4 * kH2Cap;    // winners: count | spliced ones << 10 | "a winner's spliced sibling wins too" << 31
     uint32_t* gmin = agg + kH2Cap;
     uint32_t* smin = gmin + kH2Cap;
-    uint32_t* s_cols = smin + kH2Cap;
     uint64_t key[E];
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) key[h] = h * 64 + lane < n ? src[h * 64 + lane] : 0ull;
@@ -849,10 +858,8 @@ __device__ __forceinline__ bool resolve_bucket_hash2(const uint64_t* __restrict_
         }
     }
     __syncthreads();
-    uint32_t nc = 0;
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) {
-        if (h * 64 >= n) break;
         uint32_t col = kNoCol;
         if (s2[h] != kNoCol && (s2[h] >> 31)) {   // (same rule table as col_from_candidates, on the aggregates)
             const uint32_t q = s2[h] & 0x7FFFFFFFu, a = agg[q];
@@ -864,13 +871,8 @@ __device__ __forceinline__ bool resolve_bucket_hash2(const uint64_t* __restrict_
             else if (nb <= 10 && nsp == 1) col = followed ? rc.ao + (sg >> 1) : (sg >> 1);
             if (col != kNoCol && col >= rc.num_rows) { set_err(st, kErrSlotRange, cell); col = kNoCol; }
         }
-        const uint64_t m = __ballot(col != kNoCol);
-        if (col != kNoCol) s_cols[nc + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = col;
-        nc += (uint32_t)__popcll(m);
+        col_out[h] = col;
     }
-    __syncthreads();
-    nc_out = nc;
-    s_cols_out = s_cols;
     return true;
 }
 
@@ -878,39 +880,21 @@ __device__ __forceinline__ bool resolve_bucket_hash2(const uint64_t* __restrict_
 // in flight per CU, which is what hides the load -> group -> reserve -> store latency
 // chain; blocks that run together are spread over different cells (column-major walk)
 // so their reservations do not pile onto one counter.
-// Single-bucket cells are finished here; buckets of multi-bucket cells append their
-// resolved columns to the cell's column list, counted later by k_cell_hist.
 constexpr int kResolveNT = 64;
 constexpr uint32_t kResolveCols = 8192;
 static_assert(kBucketCap <= kResolveNT * 8, "bucket cap <= 8 keys per thread");
-template <bool EM, bool MULTI>
-__global__ __launch_bounds__(kResolveNT) void k_resolve(const BucketDesc* __restrict__ desc, uint32_t n_buckets,
-                                                       uint64_t* __restrict__ keys0,
-                                                       const uint64_t* __restrict__ keys1,
-                                                       uint32_t* __restrict__ cell_ncols, uint32_t* __restrict__ nnz,
-                                                       OverflowEnt* __restrict__ ovf_list, DevStatus* st,
-                                                       ResolveCfg rc, LabArea la) {
-    // one LDS block carved two ways: the hash table (slot UMIs | counters), or the sort path's arrays
-    constexpr uint32_t kSortWords = 2 * kBucketCap + kBucketCap / 2 + kBucketCap + (EM ? 2 * kBucketCap : 0);
-    constexpr uint32_t kHashWords = kHtCap * (1 + kHtPairs) + 2 * kHtOvf + kHtCap / 32 + 2 + kHtKeys + (EM ? 2 * kHtKeys : 0);
-    constexpr uint32_t kWords01 = kSortWords > kHashWords ? kSortWords : kHashWords;
-    constexpr uint32_t kWords = MULTI && kH2Words > kWords01 ? kH2Words : kWords01;
-    __shared__ __attribute__((aligned(16))) uint32_t s_raw[kWords];
-    __shared__ uint32_t s_ws[kResolveNT / 64];
-    __shared__ uint32_t s_misc[6];
-    uint64_t* s_keys = reinterpret_cast<uint64_t*>(s_raw);
-    uint16_t* s_run = reinterpret_cast<uint16_t*>(s_raw + 2 * kBucketCap);
-    uint32_t* s_cols = s_raw + 2 * kBucketCap + kBucketCap / 2;
-    uint32_t* s_lab = EM ? s_cols + kBucketCap : nullptr;
-    uint32_t* s_ldesc = EM ? s_lab + kBucketCap : nullptr;
+__device__ __forceinline__ uint32_t resolve_block_bucket(uint32_t n_buckets) {
     const uint32_t n_cols = min(n_buckets, kResolveCols);
     const uint32_t n_rows = (n_buckets + n_cols - 1) / n_cols;
-    const uint32_t b = (blockIdx.x % n_cols) * n_rows + blockIdx.x / n_cols;
-    if (b >= n_buckets) return;
-    const BucketDesc d = desc[b];
+    return (blockIdx.x % n_cols) * n_rows + blockIdx.x / n_cols;
+}
+// What comes first on every route: an empty bucket (the whole cell's: its row is empty), and a bucket over kBucketCap, which
+// goes onto k_resolve_mid's list.  true: nothing is left to do here.
+__device__ __forceinline__ bool resolve_prelude(const BucketDesc& d, uint32_t b, uint32_t* __restrict__ nnz,
+                                                OverflowEnt* __restrict__ ovf_list, DevStatus* st) {
     if (d.n == 0) {
         if ((d.mode_single >> 8) && threadIdx.x == 0) nnz[d.cell] = 0;
-        return;
+        return true;
     }
     if (d.n > kBucketCap) {  // only multi-bucket cells can get here (planner keeps single buckets <= target)
         if (threadIdx.x == 0) {
@@ -918,45 +902,105 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve(const BucketDesc* __rest
             ovf_list[k].bucket = b;
             ovf_list[k].n = d.n;
         }
+        return true;
+    }
+    return false;
+}
+
+// The hash kernel.  A bucket of a multi-bucket cell that the UMI table serves (cr-like, or cr-like-em with a label area; at
+// most kHtKeys keys) is resolved here, and each lane stores the columns of its rounds straight from registers onto the cell's
+// column list - one reservation per bucket, no staging, no barrier (k_cell_hist counts the list).  Every other bucket goes
+// onto the divert list that k_resolve_sort drains: single-bucket cells (their columns are sorted and counted in place there),
+// other modes, prefer-ambig, 257..512 keys, and the buckets the table gives up on - a UMI over 32 bits, more than kHtMerge
+// genes or kHtOvf parked keys - before anything global is written.  (Until round 7 one kernel carried every route: 8.8 k
+// instructions, 127 SGPRs spilled to VGPR lanes, the LDS of the larger route, for a sort path that nearly no bucket takes.)
+template <bool EM, bool MULTI>
+__global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_t n_buckets, uint64_t* __restrict__ keys0,
+                                                            const uint64_t* __restrict__ keys1, uint32_t* __restrict__ cell_ncols,
+                                                            uint32_t* __restrict__ nnz, OverflowEnt* __restrict__ ovf_list,
+                                                            uint32_t* __restrict__ div_list, DevStatus* st, ResolveCfg rc, LabArea la) {
+    constexpr uint32_t kHashWords = kHtCap * (1 + kHtPairs) + 2 * kHtOvf + kHtCap / 32 + 2 + (EM ? 2 * kHtKeys : 0);
+    __shared__ __attribute__((aligned(16))) uint32_t s_raw[MULTI ? kH2Words : kHashWords];
+    __shared__ uint32_t s_misc[6];
+    const uint32_t b = resolve_block_bucket(n_buckets);
+    if (b >= n_buckets) return;
+    const BucketDesc d = bucket_desc(ds, b);
+    if (resolve_prelude(d, b, nnz, ovf_list, st)) return;
+    const uint32_t bmode = d.mode_single & 0xFFu;
+    const uint64_t* src = keys1 + d.src_off;
+    uint32_t col[kHtRounds];
+    bool ok = !(d.mode_single >> 8) && d.n <= kHtKeys && !rc.pa && !rc.divert;
+    if constexpr (MULTI) {   // a batch of many-gene reads: cr-like buckets through the two-table path
+        ok = ok && bmode == kModeCrLike && resolve_bucket_hash2(src, d.n, rc, s_raw, st, d.cell, col);
+    } else {
+        const bool em = EM && bmode == kModeCrLikeEm && la.lab;
+        ok = ok && !rc.sort_only && (bmode == kModeCrLike || em);
+        if (ok) {
+            unsigned long long* s_slot = reinterpret_cast<unsigned long long*>(s_raw);      // 2 words per slot
+            uint32_t* s_pair = s_raw + 2 * kHtCap;                                            // kHtPairs-1 words per slot
+            uint64_t* s_ovf = reinterpret_cast<uint64_t*>(s_raw + kHtCap * (1 + kHtPairs));
+            uint32_t* s_flag = s_raw + kHtCap * (1 + kHtPairs) + 2 * kHtOvf;
+            uint32_t* s_hlab = s_flag + kHtCap / 32 + 2;   // EM only: staged label words / descriptors of this bucket
+            if (EM && threadIdx.x < 6) s_misc[threadIdx.x] = 0;
+            const EmStage es{s_hlab, s_hlab + kHtKeys, &s_misc[2]};
+            ok = resolve_bucket_hash(src, d.n, rc, s_slot, s_pair, s_ovf, s_flag, s_flag + kHtCap / 32, st, d.cell, col, em, es);
+            if (EM && ok && s_misc[3]) flush_bucket_labels<kResolveNT>(d, la, es.lab, es.ldesc, s_misc);
+        }
+    }
+    if (!ok) {
+        if (threadIdx.x == 0) div_list[atomicAdd(&st->n_divert, 1u)] = b;
         return;
     }
-    const uint32_t bmode = d.mode_single & 0xFFu;
-    if constexpr (MULTI) {   // a batch of many-gene reads: cr-like buckets through the two-table path; everything else is sorted
-        if (bmode == kModeCrLike && d.n <= kHtKeys && !rc.pa) {
-            if (threadIdx.x < 6) s_misc[threadIdx.x] = 0;
-            uint32_t nc = 0;
-            uint32_t* h2cols = nullptr;
-            if (resolve_bucket_hash2(((d.mode_single >> 8) ? keys0 : keys1) + d.src_off, d.n, rc, s_raw, st, d.cell, nc, h2cols)) {
-                // the tables are dead: their space is the tail's scratch (sorted columns, run starts); the columns sit behind them
-                bucket_tail<kResolveNT>(d, keys0, cell_ncols, nnz, h2cols, nc, s_raw, reinterpret_cast<uint16_t*>(s_raw + kHtKeys), s_ws, s_misc);
-                return;
-            }
+    uint64_t m[kHtRounds];
+    uint32_t nc = 0;
+#pragma unroll
+    for (uint32_t h = 0; h < kHtRounds; ++h) { m[h] = __ballot(col[h] != kNoCol); nc += (uint32_t)__popcll(m[h]); }
+    if (nc == 0) return;
+    uint32_t at = 0;
+    if (threadIdx.x == 0) at = atomicAdd(&cell_ncols[d.cell], nc);
+    at = __builtin_amdgcn_readfirstlane(at);
+    uint32_t* out = reinterpret_cast<uint32_t*>(keys0 + d.out_off) + at;  // keys0 slots are dead after k_scatter
+    const uint64_t below = (1ull << threadIdx.x) - 1;
+#pragma unroll
+    for (uint32_t h = 0; h < kHtRounds; ++h) {
+        if (col[h] != kNoCol) out[__popcll(m[h] & below)] = col[h];
+        out += __popcll(m[h]);
+    }
+}
+
+// The sort path: a bucket held in LDS, bitonic-sorted and resolved run by run (resolve_bucket_lds).  LIST: the buckets the hash
+// kernel diverted, in a grid-bounded loop; otherwise every bucket of the range, a workgroup each - the batches whose buckets the
+// table never serves (prefer-ambig, trivial, cr-like-em of many-gene reads) have no hash kernel in front.  (Two instances: the
+// loop alone costs the one-bucket instance 30 VGPRs and a wave per SIMD.)
+constexpr uint32_t kSortGrid = 8192;   // (2048: 84 us per launch for the bench's ~0.9 % - each workgroup sorted two or three buckets in a row)
+template <bool EM, bool LIST>
+__global__ __launch_bounds__(kResolveNT) void k_resolve_sort(DescSrc ds, uint32_t n_buckets, const uint32_t* __restrict__ div_list,
+                                                            uint64_t* __restrict__ keys0, const uint64_t* __restrict__ keys1,
+                                                            uint32_t* __restrict__ cell_ncols, uint32_t* __restrict__ nnz,
+                                                            OverflowEnt* __restrict__ ovf_list, DevStatus* st, ResolveCfg rc, LabArea la) {
+    constexpr uint32_t kSortWords = 2 * kBucketCap + kBucketCap / 2 + kBucketCap + (EM ? 2 * kBucketCap : 0);
+    __shared__ __attribute__((aligned(16))) uint32_t s_raw[kSortWords];
+    __shared__ uint32_t s_ws[kResolveNT / 64];
+    __shared__ uint32_t s_misc[6];
+    uint64_t* s_keys = reinterpret_cast<uint64_t*>(s_raw);
+    uint16_t* s_run = reinterpret_cast<uint16_t*>(s_raw + 2 * kBucketCap);
+    uint32_t* s_cols = s_raw + 2 * kBucketCap + kBucketCap / 2;
+    uint32_t* s_lab = EM ? s_cols + kBucketCap : nullptr;
+    uint32_t* s_ldesc = EM ? s_lab + kBucketCap : nullptr;
+    if constexpr (!LIST) {
+        const uint32_t b = resolve_block_bucket(n_buckets);
+        if (b >= n_buckets) return;
+        const BucketDesc d = bucket_desc(ds, b);
+        if (resolve_prelude(d, b, nnz, ovf_list, st)) return;
+        resolve_bucket_lds<kResolveNT>(d, keys0, keys1, cell_ncols, nnz, st, rc, la, s_keys, s_run, s_cols, s_lab, s_ldesc, s_ws, s_misc);
+    } else {
+        const uint32_t nd = st->n_divert;
+        for (uint32_t e = blockIdx.x; e < nd; e += gridDim.x) {
+            const BucketDesc d = bucket_desc(ds, div_list[e]);
+            resolve_bucket_lds<kResolveNT>(d, keys0, keys1, cell_ncols, nnz, st, rc, la, s_keys, s_run, s_cols, s_lab, s_ldesc, s_ws, s_misc);
             __syncthreads();
         }
     }
-    if ((bmode == kModeCrLike || (EM && bmode == kModeCrLikeEm && la.lab)) && d.n <= kHtKeys && !rc.pa && !rc.sort_only) {
-        const bool single = (d.mode_single >> 8) != 0;
-        unsigned long long* s_slot = reinterpret_cast<unsigned long long*>(s_raw);      // 2 words per slot
-        uint32_t* s_pair = s_raw + 2 * kHtCap;                                            // kHtPairs-1 words per slot
-        uint64_t* s_ovf = reinterpret_cast<uint64_t*>(s_raw + kHtCap * (1 + kHtPairs));
-        uint32_t* s_flag = s_raw + kHtCap * (1 + kHtPairs) + 2 * kHtOvf;
-        uint32_t* s_hcols = s_flag + kHtCap / 32 + 2;
-        uint32_t* s_hlab = s_hcols + kHtKeys;          // EM only: staged label words / descriptors of this bucket
-        if (threadIdx.x < 6) s_misc[threadIdx.x] = 0;
-        const EmStage es{s_hlab, s_hlab + kHtKeys, &s_misc[2]};
-        uint32_t nc = 0;
-        if (resolve_bucket_hash((single ? keys0 : keys1) + d.src_off, d.n, rc, s_slot, s_pair, s_ovf, s_flag, s_flag + kHtCap / 32,
-                                s_hcols, st, d.cell, nc, EM && bmode == kModeCrLikeEm, es)) {
-            if (EM && s_misc[3]) flush_bucket_labels<kResolveNT>(d, la, es.lab, es.ldesc, s_misc);
-            // the table is dead: its space is the tail's scratch (sorted columns, run starts)
-            bucket_tail<kResolveNT>(d, keys0, cell_ncols, nnz, s_hcols, nc, s_raw, reinterpret_cast<uint16_t*>(s_raw + kHtKeys),
-                                    s_ws, s_misc);
-            return;
-        }
-        __syncthreads();
-    }
-    resolve_bucket_lds<kResolveNT>(d, keys0, keys1, cell_ncols, nnz, st, rc, la, s_keys, s_run, s_cols, s_lab, s_ldesc, s_ws,
-                                   s_misc);
 }
 
 // Buckets beyond LDS reach (one UMI carried by thousands of reads, adversarial
@@ -995,7 +1039,7 @@ static_assert(kBigNT == kMidNT, "one kernel takes both kinds of overflow bucket"
 constexpr uint32_t kMidCap = kMidNT * 8;
 // (Round 6: ONE launch for both kinds of overflow bucket - up to kMidCap keys: sorted in LDS; beyond: in place in keys1, below.  The
 //  list is nearly always empty, and a second 5 us launch with its boundary was paid per range for it.)
-__global__ __launch_bounds__(kMidNT) void k_resolve_mid(const BucketDesc* __restrict__ desc, const CellMeta* __restrict__ meta,
+__global__ __launch_bounds__(kMidNT) void k_resolve_mid(DescSrc ds, const CellMeta* __restrict__ meta,
                                                        uint64_t* __restrict__ keys0,
                                                        uint64_t* __restrict__ keys1,
                                                        uint32_t* __restrict__ cell_ncols, uint32_t* __restrict__ nnz,
@@ -1011,7 +1055,7 @@ __global__ __launch_bounds__(kMidNT) void k_resolve_mid(const BucketDesc* __rest
     uint32_t* s_ldesc = nullptr;
     const uint32_t novf = st->n_overflow;
     for (uint32_t e = blockIdx.x; e < novf; e += gridDim.x) {
-        const BucketDesc d = desc[ovf_list[e].bucket];
+        const BucketDesc d = bucket_desc(ds, ovf_list[e].bucket);
         if (ovf_list[e].n > kMidCap) { resolve_bucket_global(d, meta, keys0, keys1, cell_ncols, st, rc, la, s_ws); continue; }   // (uniform)
         __syncthreads();
         resolve_bucket_lds<kMidNT>(d, keys0, keys1, cell_ncols, nnz, st, rc, la, s_keys, s_run, s_cols, s_lab, s_ldesc, s_ws, s_misc);
@@ -1321,6 +1365,7 @@ static ResolveCfg make_rc(const ResolveArgs& a) {
     rc.usa = a.usa; rc.num_rows = a.num_rows; rc.uo = a.num_rows / 3; rc.ao = 2 * (a.num_rows / 3); rc.mode = 0;
     rc.pa = a.prefer_ambig;
     rc.sort_only = a.sort_only;
+    rc.divert = a.divert_all;
     return rc;
 }
 
@@ -1328,30 +1373,41 @@ void launch_resolve(hipStream_t s, const ResolveArgs& a) {
     if (!a.n_buckets) return;
     ResolveCfg rc = make_rc(a);
     LabArea la{a.lab, a.lab_cnt};
-    BucketDesc* desc = reinterpret_cast<BucketDesc*>(a.bucket_desc);
-    AFQ_LAUNCH(k_bucket_desc, (a.n_buckets + 255) / 256, 256, s, a.meta, a.bucket_cell, a.cell_nkeys, a.cursor, a.slab_ovf, a.n_buckets, desc);
+    const DescSrc ds{a.meta, a.bucket_cell, a.cell_nkeys, a.cursor, a.slab_ovf};
     const uint32_t n_cols = a.n_buckets < kResolveCols ? a.n_buckets : kResolveCols;
     const uint32_t grid = n_cols * ((a.n_buckets + n_cols - 1) / n_cols);
+    if (a.prefer_ambig || a.trivial || (a.sort_only && a.lab)) {   // no bucket of the batch is the table's: straight to the sort path
+        if (a.lab)
+            AFQ_LAUNCH((k_resolve_sort<true, false>), grid, kResolveNT, s, ds, a.n_buckets, nullptr, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+        else
+            AFQ_LAUNCH((k_resolve_sort<false, false>), grid, kResolveNT, s, ds, a.n_buckets, nullptr, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+        return;
+    }
     if (a.lab)
-        AFQ_LAUNCH((k_resolve<true, false>), grid, kResolveNT, s, desc, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+        AFQ_LAUNCH((k_resolve_hash<true, false>), grid, kResolveNT, s, ds, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.div_list, a.st, rc, la);
     else if (a.sort_only)
-        AFQ_LAUNCH((k_resolve<false, true>), grid, kResolveNT, s, desc, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+        AFQ_LAUNCH((k_resolve_hash<false, true>), grid, kResolveNT, s, ds, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.div_list, a.st, rc, la);
     else
-        AFQ_LAUNCH((k_resolve<false, false>), grid, kResolveNT, s, desc, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+        AFQ_LAUNCH((k_resolve_hash<false, false>), grid, kResolveNT, s, ds, a.n_buckets, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.div_list, a.st, rc, la);
+    // the diverted buckets (normally a few single-bucket cells; a grid-bounded loop, so an empty list costs one small launch)
+    const uint32_t sgrid = a.n_buckets < kSortGrid ? a.n_buckets : kSortGrid;
+    if (a.lab)
+        AFQ_LAUNCH((k_resolve_sort<true, true>), sgrid, kResolveNT, s, ds, a.n_buckets, a.div_list, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
+    else
+        AFQ_LAUNCH((k_resolve_sort<false, true>), sgrid, kResolveNT, s, ds, a.n_buckets, a.div_list, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);
 }
 
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a) {
     if (!a.n_multi) return;
     ResolveCfg rc = make_rc(a);
     LabArea la{a.lab, a.lab_cnt};
-    BucketDesc* desc = reinterpret_cast<BucketDesc*>(a.bucket_desc);
-    AFQ_LAUNCH(k_resolve_mid, 256, kMidNT, s, desc, a.meta, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);   // (the buckets beyond LDS reach too)
+    const DescSrc ds{a.meta, a.bucket_cell, a.cell_nkeys, a.cursor, a.slab_ovf};
+    AFQ_LAUNCH(k_resolve_mid, 256, kMidNT, s, ds, a.meta, a.keys0, a.keys1, a.cell_ncols, a.nnz, a.ovf_list, a.st, rc, la);   // (the buckets beyond LDS reach too)
 }
 
 
 
 
-size_t bucket_desc_bytes() { return sizeof(BucketDesc); }
 #ifdef AFQ_RESOLVE_TIMING
 extern "C" void afq_debug_dump() {
     unsigned long long h[8];
@@ -1432,7 +1488,7 @@ __global__ __launch_bounds__(1024) void k_row_ptr(const uint32_t* __restrict__ n
     }
     if (threadIdx.x == 0) cell_ptr[n] = carry;
 }
-// The two tables of a range that only restate the cells' plans - bucket -> cell (k_bucket_desc's lookup) and scatter tile ->
+// The two tables of a range that only restate the cells' plans - bucket -> cell (the resolve kernels' lookup) and scatter tile ->
 // (cell, tile of the cell) - written from the plans, a wave per cell.  They are 4 bytes per bucket and 8 per tile (2.8 + 0.5 MB
 // for the first range of a PBMC-10k batch) and used to be filled on the host and uploaded in front of the range's first kernel.
 __global__ __launch_bounds__(256) void k_fill_tables(const CellMeta* __restrict__ meta, uint32_t n_cells, uint32_t* __restrict__ bucket_cell,

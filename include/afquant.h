@@ -295,6 +295,11 @@ uint64_t afq_em_resize_count(const afq_ctx* ctx);
  * (gene-level parsimony, 8-byte UMIs) or handed back (a UMI partition of more than 256 reads; a component of more than 4096
  * vertices under a --large-graph-thresh raised beyond that).  Results identical; diagnostics only. */
 uint64_t afq_mono_cell_count(const afq_ctx* ctx);
+/* cr-like / cr-like-em: buckets of the last collected batch that the hash resolve handed to the sort path - single-bucket cells,
+ * buckets of 257..512 keys, and buckets whose UMIs the hash table cannot hold (a UMI over 32 bits, more than eight genes or 64
+ * parked keys).  Batches that the table never serves (prefer-ambig, trivial, cr-like-em of many-gene reads) are sorted without
+ * a hash pass and count 0.  Results identical; diagnostics only. */
+uint64_t afq_resolve_divert_count(const afq_ctx* ctx);
 
 /* Brings the HIP runtime up on `device` (first-call initialisation) - a host can call it from a side thread while it parses its
    inputs.  Returns 0 or AFQ_ERR_NO_DEVICE. */
