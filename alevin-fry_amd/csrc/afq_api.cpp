@@ -58,8 +58,8 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_HIST, K_BSCAN, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_hist", "k_bucket_scan", "k_scatter",
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_COUNT };
+const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph"};
 
@@ -153,7 +153,6 @@ struct RangeState {
     ResolveArgs last_ra{};
     std::vector<CellMeta> meta;
     Range cur{};
-    const PfDev* pf_stats_src = nullptr; uint64_t pf_stats_reads = 0, pf_stats_parts = 0;   // AFQ_TEST_PF_STATS
     uint32_t hash_try = 0;   // which salt the range's label hashes were made with (a collision re-runs the range under the next)
     uint32_t pool_try = 0;   // how often the range was run again with four times the parsimony pool (a cell's graph outgrew it)
     uint64_t epool_words = 0;   // the parsimony pool the range's current attempt planned (words; 0: no parsimony cell)
@@ -318,9 +317,8 @@ void harvest_timers(afq_ctx* c, std::vector<TimedLaunch>* list = nullptr) {
 
 uint32_t hdr_bytes(const afq_config& cfg) { return 4 + cfg.bc_bytes + cfg.umi_bytes; }
 
-// Multi-bucket cells are placed into fixed-capacity bucket slabs (no counting pass) unless AFQ_TEST_FIXED_SLABS=0;
-// AFQ_TEST_SLAB_CAP shrinks the slabs (tests: forces the overflow path).
-bool fixed_slabs() { return !test_hook_is("FIXED_SLABS", "0"); }
+// Multi-bucket cells are placed into fixed-capacity bucket slabs (no counting pass); AFQ_TEST_SLAB_CAP shrinks the slabs
+// (tests: forces the overflow path).
 // Default 384 slots for buckets planned at <= 256 keys (kBucketTarget): measured on the bench input, 512 costs the scatter
 // 10 % (a sparser target), 320 already sends a tenth of the cells through the exact placement (profiles/history/run_r02s.sh).
 constexpr uint32_t kSlabCap = 384;
@@ -385,7 +383,6 @@ int plan_ranges(afq_ctx* c) {
     // pass 1: validate the chunk headers, device bytes each cell needs
     std::vector<double> need(c->n_cells);
     double total_need = 0, pug_fixed = 0, wide_new = 0;
-    const bool use_slabs = fixed_slabs();            // (environment switches: read once per batch, not per cell)
     const double slab_slots = (double)std::max<uint32_t>(slab_capacity(), 512u);   // (ranges of many-gene reads take 512-slot slabs: run_range)
     c->all_aligned = true;
     for (uint32_t i = 0; i < c->n_cells; ++i) {
@@ -407,7 +404,7 @@ int plan_ranges(afq_ctx* c) {
             nd += 20.0 * nrec + 96.0 * nrec;   // rd_h/rd_u/rd_o + the edge pool (24 words per read), as run_range allocates them
             pug_fixed = std::max(pug_fixed, 4.0 * (double)pug_scratch_words(nrec, (uint32_t)n_ref, true) * pug_max_blocks() + 4.0 * (double)(1ull << 22));
         }
-        if (n_ref > bucket_target()) nd += 16.0 * (double)(n_ref / bucket_target() + 1) + (use_slabs && !pug_res ? 8.0 * 2.0 * slab_slots / bucket_target() * (double)n_ref : 0.0);   // (+ the slabs of keys1: up to 2 x slab capacity slots per kBucketTarget refs)
+        if (n_ref > bucket_target()) nd += 16.0 * (double)(n_ref / bucket_target() + 1) + (!pug_res ? 8.0 * 2.0 * slab_slots / bucket_target() * (double)n_ref : 0.0);   // (+ the slabs of keys1: up to 2 x slab capacity slots per kBucketTarget refs)
         if (nd > mem_budget) return fail(c, AFQ_ERR_OOM, "cell " + std::to_string(i) + " alone exceeds device memory");
         need[i] = nd;
         total_need += nd;
@@ -550,7 +547,6 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     const bool par = (c->widen || c->all_aligned) && decode_par_supported(g.bc_bytes, g.umi_bytes);
     uint64_t key_off = 0, n_buckets = 0, n_tiles = 0, n_slabs = 0, k1_slots = 0;
     uint32_t max_lg_nb = 0;
-    const bool slabs = fixed_slabs();
     uint32_t slab_cap = slab_capacity();
     {   // reads of many genes each (the range averages two or more alignment words per record): all keys of a UMI share a bucket, so
         // the buckets' sizes spread and 384-slot slabs overflow in a tenth of the cells (k_fix_slabs: 3.5 of 41 ms on the tail
@@ -592,12 +588,10 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         m.bucket_base = (uint32_t)n_buckets;
         n_buckets += 1ull << lg;
         m.slab_cap = 0; m.k1_off = 0; m.tile_base = 0;
-        if (lg && slabs) {
+        if (lg) {
             m.slab_cap = slab_cap;
             m.k1_off = k1_slots;
             k1_slots += std::max<uint64_t>((uint64_t)slab_cap << lg, (uint64_t)m.n_ref + 1);
-        }
-        if (lg) {
             multi.push_back(i);
             const uint32_t nt = (m.n_ref + kScatterTileHost - 1) / kScatterTileHost;
             m.tile_base = (uint32_t)n_tiles;   // (n_tiles is checked against 32 bits below)
@@ -825,16 +819,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
                    em ? B.d_lab_cnt.as<uint32_t>() : nullptr, B.d_status.as<DevStatus>(),
                    (uint32_t)n_buckets, n_multi, (uint32_t)n_tiles, B.d_hist_cells.as<uint32_t>(),
                    (uint32_t)hist_cells.size(), g.usa_mode, g.num_rows,
-                   (g.usa_mode && g.sa_model == AFQ_SA_PREFER_AMBIG) ? 1u : 0u, max_lg_nb, B.d_slab_ovf.as<uint32_t>(), slabs ? 1u : 0u,
+                   (g.usa_mode && g.sa_model == AFQ_SA_PREFER_AMBIG) ? 1u : 0u, max_lg_nb, B.d_slab_ovf.as<uint32_t>(),
                    resolve_sort_only(key_off - n, nrec_total), g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u,
                    test_hook_is("RESOLVE_DIVERT", "all") ? 1u : 0u};
     if (n_multi) {
-        if (!slabs) {
-            tc.seg(K_HIST); launch_hist(s, ra);
-            tc.seg(K_BSCAN); launch_bucket_scan(s, ra);
-        }
         tc.seg(K_SCATTER); launch_scatter(s, ra);
-        if (slabs) { tc.seg(K_FIX_SLABS); launch_fix_slabs(s, ra); }
+        tc.seg(K_FIX_SLABS); launch_fix_slabs(s, ra);
     }
     tc.seg(K_RESOLVE); launch_resolve(s, ra);
     if (n_multi) { tc.seg(K_RESOLVE_BIG); launch_resolve_big(s, ra); }
@@ -884,11 +874,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
                 while (p2.n_big < n_p2 && p2cells[p2.n_big].R >= big_reads) ++p2.n_big;   // (p2cells is largest first)
                 p2.defer_min = [] { const char* e = test_hook("P2_DEFER_MIN"); return e ? (uint32_t)std::max(0L, std::atol(e)) : 0xFFFFFFFFu; }();   // (tests: 0 = every cell takes the set-aside route)
             }
-            // k_p2_lone, labels over four refs: 0: by the vertex's lane alone, in scratch memory (rounds 3-4); 1: labels of 5..64 refs by the
-            // wave; 2: 5..8 by the lane in eight registers, 9..64 by the wave - an instance of 86 instead of 69 VGPRs, five waves per SIMD
-            // instead of seven: on the tail model k_p2_lone 25.1 -> 16.5 ms per step, on the plain one 5.6 -> 7.3 (profiles/history/run_r04ao.sh).
+            // k_pl_lone, labels over four refs: 1: labels of 5..64 refs by the wave; 2: 5..8 by the lane in eight registers, 9..64 by the
+            // wave - an instance of 86 instead of 69 VGPRs, five waves per SIMD instead of seven: on the tail model the lone-vertex kernel
+            // 25.1 -> 16.5 ms per step, on the plain one 5.6 -> 7.3 (profiles/history/run_r04ao.sh).  (Until round 4 such labels were
+            // resolved by the vertex's lane alone, in scratch memory.)
             // The range's own figure decides, the one that picks its decoder: two or more alignment words per record.
-            p2.lone_coop = [&] { const char* e = test_hook("P2_LONE_COOP"); return e && e[0] >= '0' && e[0] <= '2' ? (uint32_t)(e[0] - '0') : (key_off - n >= 2 * nrec_total ? 2u : 1u); }();
+            p2.lone_coop = [&] { const char* e = test_hook("P2_LONE_COOP"); return e && e[0] >= '1' && e[0] <= '2' ? (uint32_t)(e[0] - '0') : (key_off - n >= 2 * nrec_total ? 2u : 1u); }();
             p2.part_cap = kP2PartCap;
             if (const char* e = test_hook("P2_PART_CAP")) p2.part_cap = (uint32_t)std::max(1, std::atoi(e));   // tests: force cells back to the one-workgroup kernel
             p2.ref_count = c->ref_count; p2.num_genes = g.num_genes; p2.usa = g.usa_mode; p2.num_rows = g.num_rows; p2.em = em ? 1u : 0u;
@@ -899,7 +890,6 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
             tc.seg(K_P2_SEARCH); launch_p2_search(s, p2);
             tc.seg(K_P2_LONE); launch_p2_lone(s, p2);
             tc.seg(K_P2_GRAPH); launch_p2_graph(s, p2, n_pug_reads);
-            B.pf_stats_src = p2.graph_flat && test_hook("PF_STATS") ? p2.pfd : nullptr; B.pf_stats_reads = n_pug_reads; B.pf_stats_parts = p2_parts;
         }
         PugCellArgs pa{};
         pa.bytes = in_bytes; pa.meta = ra.meta; pa.pug_cells = sm + L.fb_list; pa.cell_nkeys = ra.cell_nkeys;
@@ -1066,14 +1056,6 @@ int finish_range(afq_ctx* c, int slot) {
         }
         if (regrow) B.d_epool.release();   // the enlarged pool is that attempt's alone: the next range plans its own
         return rc;
-    }
-    if (B.pf_stats_src) {   // AFQ_TEST_PF_STATS: the sizes of the range's flat graph build, on stderr (measurement scripts)
-        PfDev d{};
-        unsigned long long pool_used = 0;
-        if (hipMemcpy(&d, B.pf_stats_src, sizeof(d), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(&pool_used, B.d_epool_cur.p, 8, hipMemcpyDeviceToHost) == hipSuccess)
-            std::fprintf(stderr, "[afq] flat graph build: reads %llu partitions %llu vertices_with_an_edge %u two_vertex_components %u listed_components %u record_slots %u cells_routed_to_the_per_cell_kernel %u pool_words_used %llu (%.2f per read; the per-read arrays take 10.25 more)\n",
-                         (unsigned long long)B.pf_stats_reads, (unsigned long long)B.pf_stats_parts, d.T, d.NP, d.NC, d.S, d.n_old, pool_used, (double)pool_used / (double)std::max<uint64_t>(1, B.pf_stats_reads));
-        B.pf_stats_src = nullptr;
     }
     if (!st.err_code && !B.pug_cell_launched && B.h_pack.p[9]) {   // cells were handed back and the kernel that takes them was not launched
         c->handback_seen = true;

@@ -668,19 +668,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
     flush_chk();
 }
 
-#ifdef AFQ_DECODE_TIMING
-__device__ unsigned long long g_dtm[16];
-#define DT_MARK(i) do { if (lane == 0 && (blockIdx.x & 255) == 0 && wv == 0) { unsigned long long t_ = clock64(); atomicAdd(&g_dtm[i], t_ - tprev_); atomicAdd(&g_dtm[8 + i], 1ull); tprev_ = t_; } } while (0)
-extern "C" void afq_debug_dump_decode() {
-    unsigned long long h[16];
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dtm), sizeof(h));
-    fprintf(stderr, "[decode cycles/slab]");
-    for (int i = 0; i < 8; ++i) if (h[8 + i]) fprintf(stderr, " p%d=%llu", i, h[i] / h[8 + i]);
-    fprintf(stderr, " (n=%llu)\n", h[8]);
-}
-#else
-#define DT_MARK(i) do {} while (0)
-#endif
 
 // ---------------------------------------------------------------------------
 // k_decode_keys: the walk-free decode for batches without parsimony cells, with one lane per DWORD instead
@@ -775,12 +762,12 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
     auto issue_slab_loads = [&](uint32_t s0) {
         if (s0 + kStage <= nwords) {
 #pragma unroll
-            for (int r = 0; r < 5; ++r) R[r] = AFQ_LD_DECODE(&W[s0 + r * 64 + lane]);
+            for (int r = 0; r < 5; ++r) R[r] = W[s0 + r * 64 + lane];
         } else {
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 const uint32_t i = s0 + r * 64 + lane;
-                R[r] = i < nwords ? AFQ_LD_DECODE(&W[i]) : 0u;
+                R[r] = i < nwords ? W[i] : 0u;
             }
         }
     };
@@ -816,19 +803,12 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
         if (s0) find_carry(s0);
     }
     const uint64_t le_mask = lane == 63 ? ~0ull : ((2ull << lane) - 1);
-#ifdef AFQ_DECODE_TIMING
-    unsigned long long tprev_ = clock64();
-#endif
 
     // The loop body is written as unconditional LDS reads + selects: the compiler turns `c ? lds[i] : x` into
     // exec-mask branches (and once even into flat loads), which tripled the instruction count of this kernel.
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
         const uint32_t s0 = (slab - sp0) * kSlabWords;
         uint32_t own[4];
-#ifdef AFQ_DECODE_TIMING
-        if (R[0] == 0x12345677u && R[4] == 0x7654321u) fail = true;  // wait for the slab's loads
-#endif
-        DT_MARK(0);
 #pragma unroll
         for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = R[r];
 #pragma unroll
@@ -861,7 +841,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
         }
         if (s0 == 0 && (!room || !(mk[0] & 4ull))) fail = true;  // (1) the first record starts right after the chunk header
         acc_count += (uint32_t)(__popcll(mk[0]) + __popcll(mk[1]) + __popcll(mk[2]) + __popcll(mk[3]));
-        DT_MARK(1);
 
         // which record is each dword in; alignment words gather their gene
         uint32_t gid[4], ulo[4], uhi[4];
@@ -933,7 +912,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
             }
         }
         if (s0 == 0 && lane == 2 && ((mk[0] >> 2) & 1ull)) bc_out[cur_cell] = BWW == 2 ? ((uint64_t)bc_hi << 32 | bc_lo) : (uint64_t)bc_lo;
-        DT_MARK(2);
         // the record the next slab starts in: this slab's last candidate, else the one carried in
         uint32_t ncin_s = cin_s, ncin_na = cin_na, ncin_ulo = cin_ulo, ncin_uhi = cin_uhi;
         if (last_before != kNone) {
@@ -965,7 +943,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            DT_MARK(3);
             if (cin_s != kNone && cin_s + HW < s0) {   // the record the slab starts in: what its alignments in front of the slab named counts as named
                 const uint32_t cfr = cin_s + HW;
                 const uint32_t cend = min(s0, cfr + min(cin_na, nwords));
@@ -1003,7 +980,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            DT_MARK(3);
             if (__any(slow)) {
                 // one copy of the general rule; a dword that loses clears its gene (a duplicate's own first
                 // occurrence stays, so clearing never hides a gene from a later dword of the record)
@@ -1048,12 +1024,10 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
                 tot += (uint32_t)__popcll(bal[r]);
             }
         }
-        DT_MARK(4);
         if (tot) {
             uint32_t wbase = 0;
             if (lane == 0) wbase = atomicAdd(&cell_nkeys[cur_cell], tot);
             wbase = __builtin_amdgcn_readfirstlane(wbase);
-            DT_MARK(5);
             if (wbase + tot > m.n_ref) fail = true;
             else {
                 uint64_t* dst = keys0 + m.key_off + wbase;
@@ -1069,7 +1043,6 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
                 }
             }
         }
-        DT_MARK(6);
         cin_s = ncin_s; cin_na = ncin_na; cin_ulo = ncin_ulo; cin_uhi = ncin_uhi;
         // all lanes are done reading this slab's stage before the next iteration overwrites it
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1160,28 +1133,21 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
     auto issue_slab_loads = [&](uint32_t s0) {
         if (s0 + kStage <= nwords) {
 #pragma unroll
-            for (int r = 0; r < 5; ++r) R[r] = AFQ_LD_DECODE(&W[s0 + r * 64 + lane]);
+            for (int r = 0; r < 5; ++r) R[r] = W[s0 + r * 64 + lane];
         } else {
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 const uint32_t i = s0 + r * 64 + lane;
-                R[r] = i < nwords ? AFQ_LD_DECODE(&W[i]) : 0u;
+                R[r] = i < nwords ? W[i] : 0u;
             }
         }
     };
 
     load_cell(__builtin_amdgcn_readlane(my_cell, 0));
     issue_slab_loads((slab_a - sp0) * kSlabWords);
-#ifdef AFQ_DECODE_TIMING
-    unsigned long long tprev_ = clock64();
-#endif
 
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
         const uint32_t s0 = (slab - sp0) * kSlabWords;
-#ifdef AFQ_DECODE_TIMING
-        if (R[0] == 0x12345677u && R[4] == 0x7654321u) fail = true;  // wait for the slab's loads
-#endif
-        DT_MARK(0);
 #pragma unroll
         for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = R[r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1215,7 +1181,6 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        DT_MARK(1);
 
         for (uint32_t base = 0; base < ncand; base += 64) {
             const uint32_t c = base + lane;
@@ -1346,12 +1311,10 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
                 sex = tot + wave_excl_scan(scnt, stot);
                 tot += stot;
             }
-            DT_MARK(2);
             if (tot) {
                 uint32_t wbase = 0;
                 if (lane == 0) wbase = atomicAdd(&cell_nkeys[cur_cell], tot);
                 wbase = __builtin_amdgcn_readfirstlane(wbase);
-                DT_MARK(3);
                 if (wbase + tot > m.n_ref) fail = true;
                 else {
                     uint64_t* dst = keys0 + m.key_off + wbase;
@@ -1368,7 +1331,6 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
                     }
                 }
             }
-            DT_MARK(4);
         }
         // all lanes are done reading this slab's stage/list before the next iteration overwrites them
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1485,10 +1447,9 @@ int launch_decode(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw) 
     return -1;
 }
 
-// k_decode_keys finds a record's first mention of a gene through an LDS hash table (HD); AFQ_TEST_DECODE_DEDUP=scan: by the look-back
-// compares and the serial scan of rounds 2-4 (read per launch: tests run both).  Label-tail workload (configs1_tail, 9.66 GB):
-// 14.54 -> 9.01 ms per step, the step 35.0 -> 29.4 ms (profiles/history/run_r04ah.sh).
-static bool decode_keys_hash_dedup() { return !test_hook_is("DECODE_DEDUP", "scan"); }
+// k_decode_keys finds a record's first mention of a gene through an LDS hash table (HD); `trivial` keeps the look-back compares and
+// the serial scan of rounds 2-4.  Label-tail workload (configs1_tail, 9.66 GB), the table against the scan: 14.54 -> 9.01 ms per
+// step, the step 35.0 -> 29.4 ms (profiles/history/run_r04ah.sh).
 template <int BW, int UW>
 static void launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
     AFQ_LAUNCH((k_slab_setup<BW, UW>), (a.n_cells + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix,
@@ -1516,12 +1477,8 @@ static void launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
         AFQ_LAUNCH((k_decode_keys<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
                    const_cast<CellChk*>(a.chk));
-    else if (decode_keys_hash_dedup())
-        AFQ_LAUNCH((k_decode_keys<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk));
     else
-        AFQ_LAUNCH((k_decode_keys<BW, UW, false>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+        AFQ_LAUNCH((k_decode_keys<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
                    const_cast<CellChk*>(a.chk));
 }

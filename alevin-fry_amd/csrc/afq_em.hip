@@ -75,12 +75,6 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
     __shared__ uint32_t s_ws[kEmNT / 64];
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[8192];  // 32 KiB sort tile
     const uint32_t cell = em_order[blockIdx.x];  // largest cells first (the host sorts: input order is arbitrary in real data)
-#ifdef AFQ_EM_TIMING
-    __shared__ unsigned long long tmark[12];
-#define EM_MARK(i) do { __syncthreads(); if (threadIdx.x == 0 && (blockIdx.x % 1000) == 7) tmark[i] = wall_clock64(); } while (0)
-#else
-#define EM_MARK(i) do {} while (0)
-#endif
     const CellMeta m = meta[cell];
     const uint32_t nU = nnz_unique[cell];
     const uint2* U = reinterpret_cast<const uint2*>(((m.lg_nb || mode_is_pug(m.mode)) ? keys1 : keys0) + m.key_off);
@@ -110,7 +104,6 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
         return na > nb;
     };
     auto lab_ne = [&](uint32_t a, uint32_t b) { return lab_gt(a, b) || lab_gt(b, a); };
-    EM_MARK(0);
     // 1. classes = runs of equal labels in lexicographic order
     // The sort runs on 16-byte records out of LDS: a 63-bit key holding the label's first three genes (+1, a missing
     // gene is 0, so key order IS the lexicographic order with shorter labels first) and the molecule index; only labels
@@ -148,7 +141,6 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
         K += tot;
     }
     __syncthreads();
-    EM_MARK(1);
     // 2. EM label of each class: length, then contents
     auto em_label = [&](uint32_t c, uint32_t* dst) -> uint32_t {  // returns the length; writes when dst != null
         const uint32_t mol = order[cls_first[c]];
@@ -184,7 +176,6 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < K; c += kEmNT) em_label(c, cls_w + cls_woff[c]);
     __syncthreads();
-    EM_MARK(2);
     // 3. support = single-label columns + label slots (+ USA sibling statuses), sorted, distinct.
     // When one bit per output column fits the LDS tile next to its rank table (num_alphas <= 131072: every gene-level
     // matrix in practice), the support is a bitmap: mark, prefix-popcount, and "index of column x in the support" is
@@ -283,10 +274,8 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
             inv_pairs[w] = ((uint64_t)s << 32) | c;
         }
     __syncthreads();
-    EM_MARK(3);
     // 4. inverted index: for every support entry the classes containing it, ascending class
     tiled_bitonic_sort_by<kEmNT, 4096>(inv_pairs, Wc, [](uint64_t a, uint64_t b) { return a > b; }, reinterpret_cast<uint64_t*>(s_tile));
-    EM_MARK(4);
     // slot_off[s] = first pair with support idx >= s: count the memberships per entry, exclusive scan
     for (uint32_t s = threadIdx.x; s <= S; s += kEmNT) slot_off[s] = 0;
     __syncthreads();
@@ -312,7 +301,6 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
         }
     }
     __syncthreads();
-    EM_MARK(5);
     // 4b. The rounds only ever change entries that have a single-label count or sit in some class label
     // ("active"); every other support entry (the USA sibling statuses marked for em.rs:351-356) is produced
     // as 0 by each round.  Compact the active entries and express everything the rounds touch in active ids:
@@ -372,11 +360,7 @@ __global__ __launch_bounds__(kEmNT) void k_em(const CellMeta* __restrict__ meta,
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const uint32_t w = w0 + j * kEmNT; if (w < Wc) { lw3[w] = make_uint4(a0[j], y1[j], y2[j], 0u); memb[w] = mb[j]; } }
     }
-    EM_MARK(6);
     if (threadIdx.x == 0) em_hdr[cell] = make_uint4(A, K, Wc, 0u);  // the rounds run in k_em_rounds
-#ifdef AFQ_EM_TIMING
-    if (threadIdx.x == 0 && (blockIdx.x % 1000) == 7) { printf("em setup nrec=%u nU=%u M=%u K=%u S=%u Wc=%u A=%u:", m.nrec, nU, M, K, S, Wc, A); for (int i = 1; i <= 6; ++i) printf(" p%d=%.3fms", i, (double)(tmark[i] - tmark[i - 1]) / 1e5); printf("\n"); }
-#endif
 }
 
 // acc + sum over q in [q0, q1), in that order, of (iv(q) >= 0 ? ab * iv(q) : 0) - by the whole wave: the loads
@@ -423,19 +407,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
     __shared__ uint32_t s_flag[2];
     __shared__ __attribute__((aligned(16))) uint32_t s_mem[kEmLdsWords];
     const uint32_t cell = em_order[blockIdx.x];
-#ifdef AFQ_EM_TIMING
-    __shared__ unsigned long long tm2[6];
-#define EM2_MARK(i) do { __syncthreads(); if (threadIdx.x == 0 && (blockIdx.x % 1000) == 7) tm2[i] = wall_clock64(); } while (0)
-    __shared__ unsigned long long tph[5];
-    unsigned long long tph_t = 0;
-    if (threadIdx.x < 5) tph[threadIdx.x] = 0;
-#define EM2_PH0() do { tph_t = wall_clock64(); } while (0)
-#define EM2_PH(i) do { if (threadIdx.x == 0) { const unsigned long long n_ = wall_clock64(); tph[i] += n_ - tph_t; tph_t = n_; } } while (0)
-#else
-#define EM2_MARK(i) do {} while (0)
-#define EM2_PH0() do {} while (0)
-#define EM2_PH(i) do {} while (0)
-#endif
     const uint4 hdr = em_hdr[cell];
     if (hdr.w) return;  // no multi-label class: k_em already wrote the row
     const uint32_t A = hdr.x, K = hdr.y, Wc = hdr.z;
@@ -455,8 +426,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
     const uint32_t need = (A + 2) + K + (K + 1) + K + lw_words + mb_words;
     const bool fits = need <= kEmLdsWords && A <= kEmPer * kEmRNT && K <= kEmPer * kEmRNT;
     uint32_t nout = 0;
-    [[maybe_unused]] uint32_t it_dbg = 0;
-    EM2_MARK(0);
     if (fits) {
         float* vin = reinterpret_cast<float*>(s_mem);
         float* inv = vin + (A + 2);
@@ -526,10 +495,8 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
             }
             __syncthreads();
         }
-        EM2_MARK(1);
         uint32_t it = 0;
         bool conv = true, last_round = false;
-        EM2_PH0();
         while (it < kMinIter || (it < kMaxIter && !conv) || last_round) {
             // (A) per class: denominator in label order (get_abundance_for, em.rs:167-187)
 #pragma unroll
@@ -545,7 +512,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
             }
             if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; }   // [1]: next listed entry (the waves draw them as they come free)
             __syncthreads();
-            EM2_PH(0);
             // (B) per active entry: single-label count, then class contributions in class order
             bool bad = false;
 #pragma unroll
@@ -575,7 +541,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
                     if (x > kAlphaCheckCutoff && fabsf(old - x) > kRelDiffTol) bad = true;
                 }
             }
-            EM2_PH(1);
             if (hv_list)
                 for (;;) {   // the listed entries, a wave each: drawn from a counter, so a wave that met a long chain takes fewer
                     uint32_t i = 0;
@@ -589,10 +554,8 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
                     if (lane_id() == 0) hv[6 * i + 5] = __float_as_uint(x);
                     if (x > kAlphaCheckCutoff && fabsf(old - x) > kRelDiffTol) bad = true;
                 }
-            EM2_PH(2);
             if (bad) s_flag[0] = 1;
             __syncthreads();  // every read of the old abundances is done
-            EM2_PH(3);
             conv = s_flag[0] == 0;
 #pragma unroll
             for (uint32_t j = 0; j < kEmPer; ++j) {
@@ -603,7 +566,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
             if (tid == 0) vin[Z0] = 0.0f;  // inactive entries come out of every round as 0
             ++it;
             __syncthreads();
-            EM2_PH(4);
             if (cfg.usa) {
                 if (last_round) break;
                 if (it >= kMinIter && conv) {
@@ -617,15 +579,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
                 }
             }
         }
-        it_dbg = it;
-#ifdef AFQ_EM_TIMING
-        if (tid == 0 && (blockIdx.x % 1000) == 7) {
-            uint32_t mx = 0; for (uint32_t i = 0; i < (hv_list ? NH : 0u); ++i) mx = max(mx, hv[6 * i + 4] - hv[6 * i + 3]);
-            printf("em fits A=%u K=%u NH=%u list=%d maxdeg=%u it=%u: A=%.3f B=%.3f list(wave0)=%.3f wait=%.3f wb=%.3f ms\n", A, K, NH, (int)hv_list, mx, it,
-                   (double)tph[0]/1e5, (double)tph[1]/1e5, (double)tph[2]/1e5, (double)tph[3]/1e5, (double)tph[4]/1e5);
-        }
-#endif
-        EM2_MARK(2);
         // floor and emit the non-zero alphas in column order (active ids ascend with the column)
         for (uint32_t base = 0; base < A; base += kEmRNT) {
             const uint32_t a = base + tid;
@@ -672,7 +625,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
                     hv[5 * i] = a; hv[5 * i + 1] = e.x; hv[5 * i + 2] = e.y | (e.z << 16); hv[5 * i + 3] = e.w; hv[5 * i + 4] = q1;
                 }
             }
-        EM2_MARK(1);
         const float uni = 1.0f / (float)cfg.num_alphas;
         for (uint32_t a = threadIdx.x; a < A; a += kEmRNT) vin[a] = cfg.init_uniform ? uni : ((float)ent[a].x + 0.5f) * 1e-3f;
         if (threadIdx.x == 0) { vin[Z0] = cfg.init_uniform ? uni : ((float)0u + 0.5f) * 1e-3f; vin[Z1] = 0.0f; }
@@ -833,8 +785,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
                 }
             }
         }
-        it_dbg = it + (mb_lds ? 1000u : 0u) + (mid ? 10000u : 0u);
-        EM2_MARK(2);
         // 6. floor and emit the non-zero alphas in column order (active ids ascend with the column)
         for (uint32_t base = 0; base < A; base += kEmRNT) {
             const uint32_t a = base + threadIdx.x;
@@ -848,10 +798,6 @@ __global__ __launch_bounds__(kEmRNT) void k_em_rounds(const CellMeta* __restrict
         }
     }
     if (threadIdx.x == 0) out_nnz[cell] = nout;
-    EM2_MARK(3);
-#ifdef AFQ_EM_TIMING
-    if (threadIdx.x == 0 && (blockIdx.x % 1000) == 7) printf("em rounds cell nrec=%u A=%u K=%u Wc=%u need=%u fits=%d it=%u: load=%.3f rounds=%.3f out=%.3f total=%.3f ms\n", meta[cell].nrec, A, K, Wc, need, (int)fits, it_dbg, (double)(tm2[1]-tm2[0])/1e5, (double)(tm2[2]-tm2[1])/1e5, (double)(tm2[3]-tm2[2])/1e5, (double)(tm2[3]-tm2[0])/1e5);
-#endif
 }
 
 // EM output pairs -> final CSR

@@ -49,9 +49,6 @@ constexpr uint32_t kSibNone = 0xFFFFFFFFu;   // no such sibling status: adds +0.
 constexpr uint32_t kSibZero = 0xFFFFFFFEu;   // a sibling status nothing maps to: the start value in round 1, 0 afterwards
 constexpr uint32_t kSibPassive = 0x80000000u;   // | index into pas_val
 constexpr int kSetupNT = 256;
-#ifndef AFQ_EM2_PAIRS_PASS
-#define AFQ_EM2_PAIRS_PASS 1
-#endif
 #ifndef AFQ_EM2_CPT_STREAM
 #define AFQ_EM2_CPT_STREAM 4
 #endif
@@ -461,31 +458,22 @@ struct LocateByRuns {
 };
 template <int NT, int CPT, int EW, typename IdT, typename Locate, typename Load, typename Pick, typename Add>
 __device__ __forceinline__ void em2_class_pass(const IdT* __restrict__ cw, uint32_t c_begin, uint32_t c_end, float scale, Locate& locate, Load load, Pick pick,
-                                               Add add, unsigned long long* tq = nullptr) {
-#ifdef AFQ_EM_TIMING   // (thread 0's clock per level of a trip; the waits it forces are not in the product build)
-    unsigned long long tq_t = wall_clock64();
-#define EM2Q(i) do { if (tq && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long n_ = wall_clock64(); tq[i] += n_ - tq_t; tq_t = n_; } } while (0)
-#else
-#define EM2Q(i) do {} while (0)
-#endif
+                                               Add add) {
     // classes [c_begin, c_end), CPT per thread and trip, the first EW words of each label in registers
     for (uint32_t c0 = c_begin + threadIdx.x; c0 < c_end; c0 += CPT * NT) {
         uint32_t o0[CPT], n[CPT], e[CPT][EW];
         float a[CPT][EW];
 #pragma unroll
         for (int j = 0; j < CPT; ++j) { const uint32_t c = c0 + j * NT; locate(c, c < c_end, o0[j], n[j]); }
-        EM2Q(0);
 #pragma unroll
         for (int j = 0; j < CPT; ++j)
 #pragma unroll
             for (int k = 0; k < EW; ++k) e[j][k] = IdLoad<IdT>::at(cw, o0[j] + ((uint32_t)k < n[j] ? (uint32_t)k : 0u));
-        EM2Q(1);
         decltype(load(0u)) raw[CPT][EW];
 #pragma unroll
         for (int j = 0; j < CPT; ++j)
 #pragma unroll
             for (int k = 0; k < EW; ++k) raw[j][k] = load(e[j][k]);
-        EM2Q(2);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < CPT; ++j)
@@ -529,7 +517,6 @@ __device__ __forceinline__ void em2_class_pass(const IdT* __restrict__ cw, uint3
                 for (int t = 0; t < 4; ++t) if (k + t < n[j]) add(e4[t], (unsigned long long)((a4[t] * r) * scale));
             }
         }
-        EM2Q(3);
     }
 }
 // The streamed instances: the classes are laid out longest label first, so the labels beyond four words are the first c4
@@ -541,27 +528,13 @@ __device__ __forceinline__ void em2_class_pass(const IdT* __restrict__ cw, uint3
 // issued for nothing; the pass is bound by instruction issue).
 template <int NT, typename IdT, typename Load, typename Pick, typename Add>
 __device__ __forceinline__ void em2_class_pass_runs(const IdT* __restrict__ cw, const uint4* runs, const uint32_t* coff, uint32_t c4, uint32_t c2, uint32_t K,
-                                                    float scale, Load load, Pick pick, Add add, unsigned long long* tq = nullptr) {
+                                                    float scale, Load load, Pick pick, Add add) {
     LocateByRuns loc(runs, coff);
-    em2_class_pass<NT, kCptS / 2, 8, IdT>(cw, 0u, c4, scale, loc, load, pick, add, tq);
-    em2_class_pass<NT, kCptS, 4, IdT>(cw, c4, c2, scale, loc, load, pick, add, tq);
-#if AFQ_EM2_PAIRS_PASS
-    em2_class_pass<NT, 2 * kCptS, 2, IdT>(cw, c2, K, scale, loc, load, pick, add, tq);
-#else
-    em2_class_pass<NT, kCptS, 4, IdT>(cw, c2, K, scale, loc, load, pick, add, tq);
-#endif
+    em2_class_pass<NT, kCptS / 2, 8, IdT>(cw, 0u, c4, scale, loc, load, pick, add);
+    em2_class_pass<NT, kCptS, 4, IdT>(cw, c4, c2, scale, loc, load, pick, add);
+    em2_class_pass<NT, 2 * kCptS, 2, IdT>(cw, c2, K, scale, loc, load, pick, add);
 }
 
-#ifdef AFQ_EM_TIMING
-__device__ unsigned long long g_em2_dbg[32768][4];
-__device__ uint32_t g_em2_dbg_n;
-__global__ void k_em2_dbg_dump() {
-    const uint32_t n = g_em2_dbg_n < 32768 ? g_em2_dbg_n : 32768;
-    for (uint32_t i = 0; i < n; ++i) printf("em2 blk %llx %llu %llu %llu\n", g_em2_dbg[i][0], g_em2_dbg[i][1], g_em2_dbg[i][2], g_em2_dbg[i][3]);
-    printf("em2 blk end of launch\n");
-    g_em2_dbg_n = 0;
-}
-#endif
 template <int NT, int MODE, int EPT, uint32_t LDSW>
 __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ meta, const uint32_t* __restrict__ nnz_unique,
                                                    const uint32_t* __restrict__ lab_cnt, const uint64_t* __restrict__ em_off,
@@ -571,9 +544,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ 
     __shared__ uint32_t s_flag[2];
     __shared__ __attribute__((aligned(16))) uint32_t s_mem[LDSW];
     __shared__ uint4 s_run[MODE == 1 ? 64 : 1];
-#ifdef AFQ_EM_TIMING
-    const unsigned long long t_entry = wall_clock64();
-#endif
     if (blockIdx.x >= tiers[tier]) return;
     const uint32_t cell = tiers[8 + (size_t)tier * n_cells + blockIdx.x];
     const uint32_t tid = threadIdx.x;
@@ -626,17 +596,9 @@ __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ 
     for (uint32_t p = tid; p < P; p += NT) v[L + p] = init_of(sc.pas_val[p]);
     if (tid == 0) { v[Z0] = init_of(0u); v[Z1] = 0.0f; s_flag[0] = 0; s_flag[1] = 0; }
     __syncthreads();
-#ifdef AFQ_EM_TIMING
-    unsigned long long tph[4] = {0, 0, 0, 0}, tph_t = wall_clock64();
-    const unsigned long long t_begin = tph_t;
-#define EM2T(i) do { if (tid == 0) { const unsigned long long n_ = wall_clock64(); tph[i] += n_ - tph_t; tph_t = n_; } } while (0)
-#else
-#define EM2T(i) do {} while (0)
-#endif
     uint32_t it = 0;
     bool conv = true, last_round = false;
     while (it < kMinIter2 || (it < kMaxIter2 && !conv) || last_round) {
-        EM2T(3);
         if (usa) {   // (C) what a label word contributes with: own + sibling statuses
             if constexpr (MODE == 0) {
 #pragma unroll
@@ -664,9 +626,7 @@ __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ 
             if constexpr (MODE == 0) { LocateByOffsets<uint16_t> loc{coff16, K}; em2_class_pass<NT, 2, 4, uint16_t>(cw16, 0u, K, scale, loc, load, pick, add); }
             else em2_class_pass_runs<NT, uint16_t>(sc.cw16, s_run, sc.coff, sc.hdr[H_C4], sc.hdr[H_C2], K, scale, load, pick, add);
         }
-        EM2T(0);
         __syncthreads();
-        EM2T(1);
         // (E) entries: new abundance, convergence vote, accumulator back to the single-label count
         bool bad = false;
         if (tid == 0) s_flag[(it + 1) & 1u] = 0;   // the other round's flag: everyone read it before the barrier above
@@ -697,7 +657,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ 
         }
         if (bad) s_flag[it & 1u] = 1;
         __syncthreads();
-        EM2T(2);
         conv = s_flag[it & 1u] == 0;
         ++it;
         if (usa) {   // em_optimize_subset_impl: after the first converged round zero what is below the output floor, one more round (em.rs:391-451)
@@ -729,18 +688,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds(const CellMeta* __restrict__ 
     __syncthreads();
     for (uint32_t j = tid; j < nPU; j += NT) sc.out[j + pre[sc.pu_lb[j]]] = make_uint2(sc.pu_col[j], __float_as_uint((float)sc.pu_cnt[j]));
     if (tid == 0) out_nnz[cell] = nPU + nout;
-#ifdef AFQ_EM_TIMING
-    if (tid == 0 && (blockIdx.x % 100) == 3)
-        printf("em2 rounds tier=%u NT=%d L=%u P=%u K=%u Wc=%u nPU=%u it=%u: C+classes(thread 0)=%.1f wait=%.1f entries=%.1f other=%.1f total=%.1f us\n", tier, NT, L, P, K, Wc, nPU, it,
-               (double)tph[0] / 100.0, (double)tph[1] / 100.0, (double)tph[2] / 100.0, (double)tph[3] / 100.0, (double)(wall_clock64() - t_begin) / 100.0);
-    if (tid == 0) {
-        uint32_t hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        uint32_t xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        const uint32_t at = atomicAdd(&g_em2_dbg_n, 1u);
-        if (at < 32768) { g_em2_dbg[at][0] = ((unsigned long long)tier << 56) | ((unsigned long long)(xcc & 0xf) << 48) | ((unsigned long long)(hw & 0xffff) << 32) | blockIdx.x;
-                          g_em2_dbg[at][1] = t_entry; g_em2_dbg[at][2] = t_begin; g_em2_dbg[at][3] = wall_clock64(); }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -757,9 +704,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds_hybrid(const uint32_t* __rest
     __shared__ uint32_t s_flag[2];
     __shared__ __attribute__((aligned(16))) uint32_t s_mem[kT2Words];
     __shared__ uint4 s_run[64];
-#ifdef AFQ_EM_TIMING
-    const unsigned long long t_entry = wall_clock64();
-#endif
     if (blockIdx.x >= tiers[tier]) return;
     const uint32_t cell = tiers[8 + (size_t)tier * n_cells + blockIdx.x];
     const uint32_t tid = threadIdx.x;
@@ -799,17 +743,9 @@ __global__ __launch_bounds__(NT) void k_em2_rounds_hybrid(const uint32_t* __rest
     for (uint32_t p = tid; p < P; p += NT) v_g[L + p] = init_of(sc.pas_val[p]);
     if (tid == 0) { v_g[Z0] = init_of(0u); v_g[Z1] = 0.0f; s_flag[0] = 0; s_flag[1] = 0; }
     em2_gsync();
-#ifdef AFQ_EM_TIMING
-    unsigned long long hph[5] = {0, 0, 0, 0, 0}, hq[4] = {0, 0, 0, 0}, hph_t = wall_clock64();
-    const unsigned long long h_begin = hph_t;
-#define EM2H(i) do { if (tid == 0) { const unsigned long long n_ = wall_clock64(); hph[i] += n_ - hph_t; hph_t = n_; } } while (0)
-#else
-#define EM2H(i) do {} while (0)
-#endif
     uint32_t it = 0;
     bool conv = true, last_round = false;
     while (it < kMinIter2 || (it < kMaxIter2 && !conv) || last_round) {
-        EM2H(4);
         if (usa && narrow) {   // (C) by state id: one word holds both links
             for (uint32_t s0 = tid; s0 < L; s0 += 4 * NT) {   // (four states per thread and trip: their link loads, then their gathers, in flight together)
                 uint32_t sb[4];
@@ -842,17 +778,9 @@ __global__ __launch_bounds__(NT) void k_em2_rounds_hybrid(const uint32_t* __rest
             }
             em2_gsync();
         }
-        EM2H(0);
-#ifdef AFQ_EM_TIMING
-        unsigned long long* const tq = hq;
-#else
-        unsigned long long* const tq = nullptr;
-#endif
-        if (narrow) em2_class_pass_runs<NT, uint16_t>(sc.cw16, s_run, sc.coff, c4, c2, K, scale, ab_load, ab_pick, add, tq);
-        else em2_class_pass_runs<NT, uint32_t>(sc.cw, s_run, sc.coff, c4, c2, K, scale, ab_load, ab_pick, add, tq);
-        EM2H(1);
+        if (narrow) em2_class_pass_runs<NT, uint16_t>(sc.cw16, s_run, sc.coff, c4, c2, K, scale, ab_load, ab_pick, add);
+        else em2_class_pass_runs<NT, uint32_t>(sc.cw, s_run, sc.coff, c4, c2, K, scale, ab_load, ab_pick, add);
         em2_gsync();
-        EM2H(2);
         bool bad = false;
         if (tid == 0) s_flag[(it + 1) & 1u] = 0;
         for (uint32_t s0 = tid; s0 < L; s0 += 4 * NT) {   // (E) by state id
@@ -888,7 +816,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds_hybrid(const uint32_t* __rest
         }
         if (bad) s_flag[it & 1u] = 1;
         em2_gsync();
-        EM2H(3);
         conv = s_flag[it & 1u] == 0;
         ++it;
         if (usa) {
@@ -918,16 +845,6 @@ __global__ __launch_bounds__(NT) void k_em2_rounds_hybrid(const uint32_t* __rest
     em2_gsync();
     for (uint32_t j = tid; j < nPU; j += NT) sc.out[j + pre[sc.pu_lb[j]]] = make_uint2(sc.pu_col[j], __float_as_uint((float)sc.pu_cnt[j]));
     if (tid == 0) out_nnz[cell] = nPU + nout;
-#ifdef AFQ_EM_TIMING
-    if (tid == 0) {
-        const uint32_t at = atomicAdd(&g_em2_dbg_n, 1u);
-        if (at < 32768) { g_em2_dbg[at][0] = ((unsigned long long)tier << 56) | blockIdx.x; g_em2_dbg[at][1] = t_entry; g_em2_dbg[at][2] = t_entry; g_em2_dbg[at][3] = wall_clock64(); }
-        if ((blockIdx.x % 100) == 3) printf("em2 hybrid class pass, thread 0: locate=%.1f words=%.1f gathers=%.1f sums+shares=%.1f us\n", (double)hq[0] / 100.0, (double)hq[1] / 100.0, (double)hq[2] / 100.0, (double)hq[3] / 100.0);
-        if ((blockIdx.x % 100) == 3) printf("em2 hybrid L=%u H=%u P=%u K=%u Wc=%u it=%u: C=%.1f classes(thread 0)=%.1f wait=%.1f entries=%.1f other=%.1f rounds=%.1f total=%.1f us\n", L, H, P, K, sc.hdr[H_WC], it,
-                                            (double)hph[0] / 100.0, (double)hph[1] / 100.0, (double)hph[2] / 100.0, (double)hph[3] / 100.0, (double)hph[4] / 100.0,
-                                            (double)(wall_clock64() - h_begin) / 100.0, (double)(wall_clock64() - t_entry) / 100.0);
-    }
-#endif
 }
 
 // Where each cell's scratch slice starts, on the device (so that the EM follows the range's other kernels without a trip to
@@ -973,9 +890,6 @@ void launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t*
     EM2_ROUNDS(512, 0, 8, kT1Words, 1u);
     EM2_ROUNDS(256, 0, 8, kT0Words, 0u);
 #undef EM2_ROUNDS
-#ifdef AFQ_EM_TIMING
-    hipLaunchKernelGGL(k_em2_dbg_dump, dim3(1), dim3(1), 0, s);
-#endif
 }
 
 // columns the setup kernel's bitmap + rank table can hold in 64 KiB of LDS; beyond that the EM takes the canonical kernels

@@ -1,14 +1,16 @@
 // afq_hooks.h — the ONE place the library reads test hooks from the environment.
 //
 // AFQ_TEST_<NAME>: routing overrides and sizes that tests/ flips to reach every code path on inputs of a few thousand reads
-// (which decoder, which parsimony route, how small a slab or a pool, where a range is cut).  A hook changes WHICH path
-// computes the rows, never the rows: every one of them is exercised by a parity test against the oracle.  Among them:
+// (which decoder, which parsimony route, how small a slab or a pool, where a range is cut).  A hook forces a route that
+// production takes on some input of its own, never one it does not have; it changes WHICH path computes the rows, never the
+// rows: every one of them is exercised by a parity test against the oracle.  Among them:
 //   AFQ_TEST_POOL_WORDS=n        the parsimony pool is planned at n (12..32) words per read instead of 24: graphs outgrow it
 //   AFQ_TEST_POOL_ROOM_WORDS=n   the device holds a parsimony pool of at most n words: run_range refuses a larger one with
 //                                AFQ_ERR_OOM before it allocates, and finish_range's room check answers as such a device would -
 //                                the no-room re-runs of a range whose graphs outgrew its pool, on a test box that always has room
 // Rounds 1-4 had grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not
-// kept; those alternatives are gone (a measurement build is `make variant DEFS=...`), and what is left besides the hooks is:
+// kept; those alternatives are gone, as are (round 7) the last hooks that selected one and the per-phase clock builds (a
+// measurement build is `make variant DEFS=...` of a scratch copy), and what is left besides the hooks is:
 //   AFQ_EM_ORDER=canonical   the sequential f32 EM of rounds 1-3, bit-identical to the reference's arithmetic
 //   AFQ_HOST_TIMING=1        where the host side of a batch spends its time, on stderr
 #pragma once

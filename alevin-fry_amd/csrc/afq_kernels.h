@@ -58,7 +58,6 @@ struct ResolveArgs {
     uint32_t prefer_ambig;       // --sa-model prefer-ambig in USA mode (cr-like, cr-like-em)
     uint32_t max_lg_nb;          // largest lg_nb of the batch's multi-bucket cells (picks the scatter instance)
     uint32_t* slab_ovf;          // fixed-slab placement: per cell, set when one of its buckets outgrew its slab (the cell is then placed exactly)
-    uint32_t slabs;              // the range's multi-bucket cells use fixed slabs (no k_hist / k_bucket_scan)
     uint32_t sort_only;          // reads of the range average two or more alignments: buckets are resolved by sorting, not through the UMI table
     uint32_t trivial;            // the batch resolves `trivial`: its buckets (but those of tiny cells) are the sort path's
     uint32_t divert_all;         // tests (AFQ_TEST_RESOLVE_DIVERT=all): every bucket through the divert list to the sort path
@@ -83,8 +82,6 @@ void launch_widen(hipStream_t s, const uint8_t* src, size_t n_src, const uint64_
                   uint32_t bw, uint32_t uw, uint32_t ebw, uint32_t euw, uint8_t* dst, DevStatus* st, uint32_t bsplit = 0);
 bool decode_par_supported(uint32_t bw, uint32_t uw);
 int launch_decode_par(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw);
-void launch_hist(hipStream_t s, const ResolveArgs& a);
-void launch_bucket_scan(hipStream_t s, const ResolveArgs& a);
 void launch_fix_slabs(hipStream_t s, const ResolveArgs& a);
 void launch_scatter(hipStream_t s, const ResolveArgs& a);
 uint64_t em_scratch_words(uint32_t nU, uint32_t W, uint32_t M, bool usa);
@@ -237,7 +234,7 @@ struct P2Args {
     PfTile* ptile;
     uint32_t* pcpre; uint32_t* pbq; uint32_t npa;      // the scan of the lone vertices' staged class counts over the partitions (npa entries, blocks of 1024)
     uint32_t graph_flat;  // the graph phase as range-wide kernels (afq_pugflat.hip); 0: the per-cell kernel for every cell (tests: AFQ_TEST_P2_GRAPH=cell)
-    uint32_t lone_coop;   // k_p2_lone: a lone vertex whose label has 5..64 refs is resolved by its whole wave (0: by its lane alone, as until late in round 4 - tests, measurements)
+    uint32_t lone_coop;   // k_pl_lone: a lone vertex whose label has 5..64 refs is resolved by its whole wave; 2: those of 5..8 refs by their own lane (the L8 instance)
 };
 #ifndef AFQ_P2_PART_TARGET
 #define AFQ_P2_PART_TARGET 144

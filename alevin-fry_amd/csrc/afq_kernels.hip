@@ -1,7 +1,7 @@
 // afq_kernels.hip - the bucket pipeline of winner-take-all ("cr-like") resolution on gfx950 (CDNA4, wave64)
 // (replaces src/quant.rs:469-657 / src/pugutils.rs:644-850 / src/utils.rs:673-756 of the reference;
 // semantics: SURVEY.md appendix B.2):
-//   k_hist, k_bucket_scan, k_scatter   keys -> per-(cell, UMI-hash bucket) ranges (LDS histogram / multisplit)
+//   k_scatter, k_fix_slabs             keys -> per-(cell, UMI-hash bucket) slabs (LDS multisplit); overflowed cells placed exactly
 //   k_resolve_hash                     one wave per bucket: LDS hash table keyed by UMI, per-UMI arg-max with ties,
 //                                      USA slot rules, cr-like-em class staging; other buckets onto a divert list
 //   k_resolve_sort                     one wave per (diverted) bucket: LDS bitonic sort + run-length resolve
@@ -21,10 +21,9 @@
 
 namespace afq {
 // ---------------------------------------------------------------------------
-// Bucket histogram.  Device-scope atomics leave the XCD (every one is a fabric
-// transaction on this 8-XCD part: rocprof WRITE_SIZE showed 3-5x the payload when
-// they were issued per record), so counts are first combined in LDS over a tile
-// of kTileKeys keys and flushed with one atomic per non-empty bucket per tile.
+// Device-scope atomics leave the XCD (every one is a fabric transaction on this 8-XCD part: rocprof WRITE_SIZE showed
+// 3-5x the payload when they were issued per record), so the scatter combines counts in LDS over a tile of kTileKeys
+// keys first and reserves with one atomic per non-empty bucket per tile.
 constexpr uint32_t kTileKeys = kScatterTileHost;  // 2048
 #ifndef AFQ_SCATTER_RUN
 #define AFQ_SCATTER_RUN 16
@@ -32,62 +31,15 @@ constexpr uint32_t kTileKeys = kScatterTileHost;  // 2048
 constexpr uint32_t kScatterRun = AFQ_SCATTER_RUN;   // consecutive tiles one XCD takes (k_scatter)
 constexpr uint32_t kLdsBins = 2048;               // buckets per cell the LDS paths can hold
 
-// tile -> (cell, tile index inside the cell): a table the planner uploads with the batch.  (It used to be a binary
-// search over the cells' tile prefix by thread 0 - fourteen dependent L2 round trips and a barrier in front of every
-// 2048-key tile, more time than the tile's own work.)
-__global__ __launch_bounds__(256) void k_hist(const uint2* __restrict__ tile_desc,
-                                             const CellMeta* __restrict__ meta,
-                                             const uint32_t* __restrict__ cell_nkeys,
-                                             const uint64_t* __restrict__ keys0, uint32_t* __restrict__ bucket_cnt) {
-    __shared__ uint32_t s_hist[kLdsBins];
-    const uint2 td = tile_desc[blockIdx.x];
-    const uint32_t cell = td.x, lt = td.y;
-    const CellMeta m = meta[cell];
-    const uint32_t nk = mode_is_pug(m.mode) ? 0u : cell_nkeys[cell];  // PUG cells emit reads, not keys
-    const uint32_t t0 = lt * kTileKeys;
-    if (t0 >= nk) return;
-    const uint32_t t1 = min(nk, t0 + kTileKeys);
-    const uint64_t* src = keys0 + m.key_off;
-    uint32_t* gcnt = bucket_cnt + m.bucket_base;
-    const uint32_t nb = 1u << m.lg_nb;
-    if (nb > kLdsBins) {  // giant cell: straight to global
-        for (uint32_t i = t0 + threadIdx.x; i < t1; i += 256) atomicAdd(&gcnt[bucket_of(src[i] >> kGeneBits, m.lg_nb)], 1u);
-        return;
-    }
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) s_hist[b] = 0;
-    __syncthreads();
-    for (uint32_t i = t0 + threadIdx.x; i < t1; i += 256) atomicAdd(&s_hist[bucket_of(src[i] >> kGeneBits, m.lg_nb)], 1u);
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) {
-        const uint32_t c = s_hist[b];
-        if (c) atomicAdd(&gcnt[b], c);
-    }
-}
-
-// per-cell exclusive scan of bucket counts (in place): wave per multi-bucket cell
-__global__ __launch_bounds__(256) void k_bucket_scan(const uint32_t* __restrict__ multi_cells, uint32_t n_multi,
-                                                    const CellMeta* __restrict__ meta,
-                                                    uint32_t* __restrict__ bucket_cnt) {
-    const uint32_t ci = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ci >= n_multi) return;
-    const CellMeta m = meta[multi_cells[ci]];
-    const uint32_t nb = 1u << m.lg_nb;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += 64) {
-        const uint32_t i = base + lane_id();
-        uint32_t c = i < nb ? bucket_cnt[m.bucket_base + i] : 0u, tot;
-        uint32_t ex = wave_excl_scan(c, tot);
-        if (i < nb) bucket_cnt[m.bucket_base + i] = carry + ex;
-        carry += tot;
-    }
-}
-
 // ---------------------------------------------------------------------------
 // keys0 -> keys1 grouped by bucket: LDS multisplit of a kTileKeys tile.  Ranks
 // inside a bucket come from LDS atomics, one global atomic per non-empty bucket
 // reserves the tile's range, and the tile is written out bucket-major so the
-// stores of a bucket's run are contiguous.  After the kernel cursor[b] = end
-// offset of bucket b inside its cell's region (start = previous bucket's end).
+// stores of a bucket's run are contiguous.  After the kernel cursor[b] = count
+// of bucket b (k_fix_slabs turns the cursors of an overflowed cell into end offsets).
+// tile -> (cell, tile index inside the cell): a table the planner uploads with the batch.  (It used to be a binary
+// search over the cells' tile prefix by thread 0 - fourteen dependent L2 round trips and a barrier in front of every
+// 2048-key tile, more time than the tile's own work.)
 // BINS: buckets per cell the instance ranks in LDS (a cell with more goes key by key).  Nearly every batch is served
 // by the 512-bin instance, whose 20 KiB of LDS let eight workgroups share a CU instead of five.
 template <uint32_t BINS>
@@ -115,12 +67,11 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
     if (t0 >= nk) return;
     const uint32_t t1 = min(nk, t0 + kTileKeys);
     const uint64_t* src = keys0 + m.key_off;
-    // Fixed slabs (m.slab_cap != 0): bucket b owns slots [b * cap, (b + 1) * cap) of the cell's keys1 region and the cursors
-    // start at zero - no counting pass (k_hist) and no scan in front of this kernel.  A bucket that outgrows its slab
-    // (one UMI with hundreds of reads) flags the cell; k_fix_slabs then places that cell exactly, from the counts the
-    // cursors hold by then.  cap = 0: the exact layout behind k_hist + k_bucket_scan (cursors = exclusive offsets).
+    // Fixed slabs: bucket b owns slots [b * cap, (b + 1) * cap) of the cell's keys1 region and the cursors start at zero -
+    // no counting pass and no scan in front of this kernel.  A bucket that outgrows its slab (one UMI with hundreds of
+    // reads) flags the cell; k_fix_slabs then places that cell exactly, from the counts the cursors hold by then.
     const uint32_t cap = m.slab_cap;
-    uint64_t* dst = keys1 + (cap ? m.k1_off : m.key_off);
+    uint64_t* dst = keys1 + m.k1_off;
     uint32_t* gcur = cursor + m.bucket_base;
     const uint32_t nb = 1u << m.lg_nb;
     if (nb > BINS) {  // giant cell: per-key global atomics
@@ -129,8 +80,7 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
             const uint64_t key = src[i];
             const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
             const uint32_t pos = atomicAdd(&gcur[b], 1u);
-            if (!cap) dst[pos] = key;
-            else if (pos < cap) dst[(uint64_t)b * cap + pos] = key;
+            if (pos < cap) dst[(uint64_t)b * cap + pos] = key;
             else over = true;
         }
         if (over) atomicOr(&slab_ovf[cell], 1u);
@@ -146,7 +96,7 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
         key[e] = kKeySentinel;
         rank[e] = 0;
         if (i < t1) {
-            key[e] = AFQ_LD_SCATTER(&src[i]);
+            key[e] = src[i];
             const uint32_t b = bucket_of(key[e] >> kGeneBits, m.lg_nb);
             rank[e] = (b << 16) | atomicAdd(&s_cnt[b], 1u);
         }
@@ -163,7 +113,7 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
             s_cnt[b] = carry + ex;
             const uint32_t at = c ? atomicAdd(&gcur[b], c) : 0u;
             s_base[b] = at;
-            if (cap && at + c > cap) atomicOr(&slab_ovf[cell], 1u);
+            if (at + c > cap) atomicOr(&slab_ovf[cell], 1u);
         }
         carry += tot;
     }
@@ -179,14 +129,13 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
         const uint64_t kx = s_keys[i];
         const uint32_t b = bucket_of(kx >> kGeneBits, m.lg_nb);
         const uint32_t pos = s_base[b] + (i - s_cnt[b]);
-        if (!cap) dst[pos] = kx;
-        else if (pos < cap) dst[(uint64_t)b * cap + pos] = kx;
+        if (pos < cap) dst[(uint64_t)b * cap + pos] = kx;
     }
 }
 
 // Cells whose fixed slabs overflowed (normally none): the cursors hold every bucket's true count, so the exact layout is
 // one scan away - buckets back to back from the start of the cell's keys1 region, keys placed one atomic each out of
-// keys0 (still intact).  Afterwards cursor[b] = end offset of bucket b, as after the exact path.
+// keys0 (still intact).  Afterwards cursor[b] = end offset of bucket b.
 __global__ __launch_bounds__(256) void k_fix_slabs(const uint32_t* __restrict__ multi_cells, uint32_t n_multi,
                                                   const CellMeta* __restrict__ meta, const uint32_t* __restrict__ cell_nkeys,
                                                   const uint64_t* __restrict__ keys0, uint64_t* __restrict__ keys1,
@@ -196,7 +145,7 @@ __global__ __launch_bounds__(256) void k_fix_slabs(const uint32_t* __restrict__ 
         const uint32_t cell = multi_cells[ci];
         if (!slab_ovf[cell]) continue;
         const CellMeta m = meta[cell];
-        if (!m.slab_cap || mode_is_pug(m.mode)) continue;
+        if (mode_is_pug(m.mode)) continue;
         const uint32_t nb = 1u << m.lg_nb, nk = cell_nkeys[cell];
         uint32_t* gcur = cursor + m.bucket_base;
         uint32_t carry = 0;
@@ -366,11 +315,11 @@ __device__ __forceinline__ BucketDesc bucket_desc(const DescSrc& ds, uint32_t b)
     BucketDesc d;
     d.cell = cell; d.out_off = m.key_off; d.n_ref = m.n_ref;
     if (m.lg_nb == 0) { d.mode_single = m.mode | 0x100u; d.src_off = m.key_off; d.n = mode_is_pug(m.mode) ? 0u : ds.cell_nkeys[cell]; }
-    else if (m.slab_cap && !ds.slab_ovf[cell]) {   // fixed slabs: the cursor is the bucket's count
+    else if (!ds.slab_ovf[cell]) {   // fixed slabs: the cursor is the bucket's count
         d.mode_single = m.mode; d.src_off = m.k1_off + (uint64_t)(b - m.bucket_base) * m.slab_cap; d.n = mode_is_pug(m.mode) ? 0u : ds.cursor[b];
     } else {
         const uint32_t beg = (b == m.bucket_base) ? 0u : ds.cursor[b - 1];
-        d.mode_single = m.mode; d.src_off = (m.slab_cap ? m.k1_off : m.key_off) + beg; d.n = mode_is_pug(m.mode) ? 0u : ds.cursor[b] - beg;
+        d.mode_single = m.mode; d.src_off = m.k1_off + beg; d.n = mode_is_pug(m.mode) ? 0u : ds.cursor[b] - beg;
     }
     return d;
 }
@@ -391,13 +340,6 @@ __device__ __forceinline__ uint32_t* lab_alloc_global(const LabArea& la, uint32_
     return gw + off;
 }
 
-
-#ifdef AFQ_RESOLVE_TIMING
-__device__ unsigned long long g_dbg[8];
-#define RT_MARK(i) do { if (threadIdx.x == 0 && (blockIdx.x & 1023) == 0) { unsigned long long t_ = clock64(); atomicAdd(&g_dbg[i], t_ - tprev_); atomicAdd(&g_dbg[4 + (i & 3)], 1ull); tprev_ = t_; } } while (0)
-#else
-#define RT_MARK(i) do {} while (0)
-#endif
 
 // What follows the resolution of one bucket: s_cols[0..nc) are its molecules' columns.  A bucket of a
 // multi-bucket cell appends them to the cell's column list (one reservation per bucket); a single-bucket
@@ -470,9 +412,6 @@ __device__ __forceinline__ void resolve_bucket_lds(const BucketDesc& d, uint64_t
     ResolveCfg rcb = rc;
     rcb.mode = d.mode_single & 0xFFu;
     if (threadIdx.x < 6) s_misc[threadIdx.x] = 0;
-#ifdef AFQ_RESOLVE_TIMING
-    unsigned long long tprev_ = clock64();
-#endif
     block_sort_any<NT, uint64_t>(src, n, s_keys, kKeySentinel);
     resolve_sorted<NT>(s_keys, n, s_run, s_ws, rcb, [&](uint32_t col) {
         if (col >= rc.num_rows) { set_err(st, kErrSlotRange, d.cell); return; }
@@ -627,12 +566,9 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     constexpr uint32_t E = kHtRounds;
     constexpr unsigned long long kEmpty64 = ~0ull;
     const uint32_t lane = threadIdx.x;
-#ifdef AFQ_RESOLVE_TIMING
-    unsigned long long tprev_ = clock64();
-#endif
     uint64_t key[E];
 #pragma unroll
-    for (uint32_t h = 0; h < E; ++h) key[h] = h * 64 + lane < n ? AFQ_LD_RESOLVE(&src[h * 64 + lane]) : 0ull;
+    for (uint32_t h = 0; h < E; ++h) key[h] = h * 64 + lane < n ? ld_nt(&src[h * 64 + lane]) : 0ull;
     uint32_t cap = (n + (n >> 2) + 63) & ~63u;   // multiples of 64 slots: 1.25 n rounded up
     cap = cap < 128 ? 128 : cap;
     {
@@ -644,10 +580,6 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
         if (lane == 0) *s_novf = 0;
     }
     __syncthreads();
-#ifdef AFQ_RESOLVE_TIMING
-    if (key[0] == 1234567ull) return false;  // wait for the loads so that their latency lands in phase 0
-#endif
-    RT_MARK(0);
     bool bad = false;
     uint32_t own_slot[E];
 #pragma unroll
@@ -696,7 +628,6 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     }
     if (__any(bad)) return false;
     __syncthreads();
-    RT_MARK(1);
     const uint32_t novf = *s_novf;
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) col_out[h] = kNoCol;
@@ -761,7 +692,6 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     }
     if (__any(bad)) return false;  // a UMI with more genes than the merge holds: nothing global was written yet
     if (em) __syncthreads();       // (the staged labels are read back by other lanes)
-    RT_MARK(2);
     return true;
 }
 
@@ -1333,17 +1263,7 @@ __global__ __launch_bounds__(256) void k_atac_compact(const uint64_t* __restrict
 // first touch of a kernel loads the library's code object on the current device (tens of ms): afq_device_warmup does it early
 void warm_code_object() {
     hipFuncAttributes at{};
-    (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(k_hist));
-}
-
-void launch_hist(hipStream_t s, const ResolveArgs& a) {
-    if (!a.n_tiles) return;
-    AFQ_LAUNCH(k_hist, a.n_tiles, 256, s, a.tile_desc, a.meta, a.cell_nkeys, a.keys0, a.cursor);
-}
-
-void launch_bucket_scan(hipStream_t s, const ResolveArgs& a) {
-    if (!a.n_multi) return;
-    AFQ_LAUNCH(k_bucket_scan, (a.n_multi + 3) / 4, 256, s, a.multi_cells, a.n_multi, a.meta, a.cursor);
+    (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(k_scatter<512>));
 }
 
 void launch_scatter(hipStream_t s, const ResolveArgs& a) {
@@ -1355,7 +1275,7 @@ void launch_scatter(hipStream_t s, const ResolveArgs& a) {
 }
 
 void launch_fix_slabs(hipStream_t s, const ResolveArgs& a) {
-    if (!a.n_multi || !a.slabs) return;
+    if (!a.n_multi) return;
     const uint32_t grid = a.n_multi < 512u ? a.n_multi : 512u;
     AFQ_LAUNCH(k_fix_slabs, grid, 256, s, a.multi_cells, a.n_multi, a.meta, a.cell_nkeys, a.keys0, a.keys1, a.cursor, a.slab_ovf);
 }
@@ -1406,15 +1326,6 @@ void launch_resolve_big(hipStream_t s, const ResolveArgs& a) {
 }
 
 
-
-
-#ifdef AFQ_RESOLVE_TIMING
-extern "C" void afq_debug_dump() {
-    unsigned long long h[8];
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dbg), sizeof(h));
-    fprintf(stderr, "[resolve cycles/bucket] load+clear=%llu insert=%llu emit=%llu tail=%llu (n=%llu)\n", h[0] / (h[4] + 1), h[1] / (h[5] + 1), h[2] / (h[6] + 1), h[3] / (h[7] + 1), h[4]);
-}
-#endif
 
 void launch_atac_dedup(hipStream_t s, uint32_t n_cells, const uint32_t* ref, const uint32_t* start, const uint16_t* flen,
                        const uint64_t* cell_ptr, void* scratch, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,

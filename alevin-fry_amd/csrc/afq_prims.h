@@ -483,25 +483,9 @@ __device__ __forceinline__ bool same_gene(uint32_t a, uint32_t b) { return (a & 
 // Loads of data a kernel reads once.  Measured on the headline (profiles/history/run_r04ac.sh, three rounds, per step): the bucket's keys
 // in k_resolve non-temporal: 4.42 -> 4.35 ms, and k_cell_hist behind it 0.554 -> 0.529 (what the resolve leaves in L2 is the
 // column lists the histograms read) - kept; the input bytes in k_decode_recs: 4.47 -> 4.60 (the next slab's halo is this slab's
-// tail); keys0 in k_scatter: 2.61 -> 2.57 but k_resolve 4.42 -> 4.46 - neither kept (make variant DEFS=-DAFQ_NT_DECODE / _SCATTER;
-// -DAFQ_PLAIN_RESOLVE_LOADS for the resolve's old loads).
+// tail); keys0 in k_scatter: 2.61 -> 2.57 but k_resolve 4.42 -> 4.46 - neither kept, so the decode and the scatter load plainly.
 template <typename T>
 __device__ __forceinline__ T ld_nt(const T* p) { return __builtin_nontemporal_load(p); }
-#ifdef AFQ_NT_DECODE
-#define AFQ_LD_DECODE(p) ld_nt(p)
-#else
-#define AFQ_LD_DECODE(p) (*(p))
-#endif
-#ifdef AFQ_NT_SCATTER
-#define AFQ_LD_SCATTER(p) ld_nt(p)
-#else
-#define AFQ_LD_SCATTER(p) (*(p))
-#endif
-#ifdef AFQ_PLAIN_RESOLVE_LOADS
-#define AFQ_LD_RESOLVE(p) (*(p))
-#else
-#define AFQ_LD_RESOLVE(p) ld_nt(p)
-#endif
 
 #define AFQ_LAUNCH(kern, grid, block, stream, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 

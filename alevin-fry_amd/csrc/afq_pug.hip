@@ -27,13 +27,6 @@
 
 namespace afq {
 
-#ifdef AFQ_PUG_TIMING
-#define PUG_MARK(i) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < 4) tmark[i] = wall_clock64(); } while (0)
-#define PUG_ACC(i) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < 4) { const unsigned long long t_ = wall_clock64(); tacc[i] += t_ - tlast; tlast = t_; } } while (0)
-#else
-#define PUG_MARK(i) do {} while (0)
-#define PUG_ACC(i) do {} while (0)
-#endif
 
 constexpr int kPugNT = 1024;
 constexpr uint32_t kVidBits = 20;                 // vertices per cell < 2^20
@@ -66,15 +59,9 @@ __device__ __forceinline__ u128 rec_key(const SortRec& r) { return ((u128)r.h <<
 constexpr uint32_t kSortBucket = 2048, kSortWaveBucket = 96, kSortWaveMax = 384, kSortTile = 4096, kSortMaxBuckets = 1024;
 // (Not inlined: inside the cell kernel its register-resident tiles would share one allocation with everything that is
 // live across the sort there, and spill in the inner loops.)
-#ifdef AFQ_PUG_TIMING
-#define SORT_MARK(i) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < 4 && tm) tm[i] = wall_clock64(); } while (0)
-#else
-#define SORT_MARK(i) do {} while (0)
-#endif
 template <int NT>
 __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint32_t R, const uint64_t* rd_h, const uint64_t* rd_u,
-                                               const uint32_t* rd_o, bool wide_umi, SortRec* tile, uint32_t* aux, uint32_t* s_ws,
-                                               [[maybe_unused]] unsigned long long* tm = nullptr) {
+                                               const uint32_t* rd_o, bool wide_umi, SortRec* tile, uint32_t* aux, uint32_t* s_ws) {
     const uint32_t tid = threadIdx.x;
     auto load = [&](uint32_t i) {
         SortRec r;
@@ -117,11 +104,9 @@ __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint3
     for (uint32_t i = tid; i < nb; i += NT) cnt[i] = 0;
     if (tid == 0) *flag = 0;
     __syncthreads();
-    SORT_MARK(0);
     sort_tile(sr, ns);
     for (uint32_t j = tid; j + 1 < nb; j += NT) spl[j] = sr[(uint32_t)(((uint64_t)(j + 1) * ns) / nb)];
     __syncthreads();
-    SORT_MARK(1);
     for (uint32_t i0 = tid; i0 < R; i0 += 4 * NT) {   // four reads per thread and trip: their loads go out together
         SortRec r4[4];
 #pragma unroll
@@ -138,7 +123,6 @@ __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint3
         }
     }
     __syncthreads();
-    SORT_MARK(2);
     {
         const uint32_t c = tid < nb ? cnt[tid] : 0u;
         uint32_t tot;
@@ -163,7 +147,6 @@ __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint3
         for (int j = 0; j < 4; ++j) if (i0 + j * NT < R) sr[off[b4[j]] + atomicAdd(&cnt[b4[j]], 1u)] = r4[j];
     }
     __syncthreads();
-    SORT_MARK(3);
     if (wave_buckets) {
         u128* a128 = reinterpret_cast<u128*>(sr);
         const uint32_t lane = lane_id();
@@ -184,7 +167,6 @@ __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint3
             else sort_bucket(std::integral_constant<int, 8>{}, o, n);
         }
         __syncthreads();
-        SORT_MARK(4);
         for (uint32_t b = 0; b < nb; ++b) if (off[b + 1] - off[b] > 512) sort_tile(sr + off[b], off[b + 1] - off[b]);
         return;
     }
@@ -205,12 +187,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_big[1u << 15];   // 128 KiB: sort tiles first, the filter later
     uint32_t* s_bloom = s_big;
     __shared__ uint32_t s_bestv[kPugNT / 64], s_bestsz[kPugNT / 64];
-#ifdef AFQ_PUG_TIMING
-    __shared__ unsigned long long tmark[24];
-    __shared__ unsigned long long tacc[8];
-    __shared__ unsigned long long tsort[8];
-    __shared__ unsigned long long tlast;
-#endif
     __shared__ uint32_t s_next;
     __shared__ uint32_t s_poff[kMaxParts + 1];
     __shared__ uint32_t s_filt[2048];   // 2^16-bit presence filter over the UMIs of the partition in the table
@@ -271,7 +247,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     uint32_t* wlab = reinterpret_cast<uint32_t*>(comp_sorted + R);     // R  : WCC label
     uint32_t* local_idx = wlab + R;                                    // R  : vid -> index inside its component
 
-    PUG_MARK(0);
     // ---- 1. reads sorted by (label key, umi, offset) ----
     const bool wide_umi = A.umi32 == 0;
     const uint64_t rd_base = A.rd.rd_off[cell];
@@ -285,13 +260,8 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         }
         uint32_t* bid = reinterpret_cast<uint32_t*>(sr) + 4 * (size_t)R;   // slab A has 6R words, the records take 4R
         sample_sort_reads<kPugNT>(sr, bid, R, A.rd.h + rd_base, A.rd.u + rd_base, A.rd.o + rd_base, wide_umi,
-                                  reinterpret_cast<SortRec*>(s_big), s_big + 4 * kSortTile, s_ws
-#ifdef AFQ_PUG_TIMING
-                                  , tsort
-#endif
-                                  );
+                                  reinterpret_cast<SortRec*>(s_big), s_big + 4 * kSortTile, s_ws);
     }
-    PUG_MARK(1);
     // ---- 2. vertices = distinct (label, umi); classes = distinct labels ----
     // One pass over the sorted reads: vertex / class heads (two scans), the class's smallest record offset (its first
     // appearance in the file), and the check that equal non-exact keys are equal labels - each such read against the read
@@ -459,7 +429,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     };
     __syncthreads();
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], cell); return; }
-    PUG_MARK(2);
     // ---- 3. class ids by first appearance; reference vertex ids ----
     // c_order[r] = the class that appears r-th in the file.  The classes' first offsets are distinct dwords of the chunk:
     // one bit each in an LDS map, and a class's rank is the number of bits below its own (no sort); chunks over 2^19
@@ -544,7 +513,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         }
     }
     __syncthreads();
-    PUG_MARK(3);
     // ---- 4. neighbour search ----
     uint32_t NCAND = 0;
     uint64_t* cand = nullptr;
@@ -553,9 +521,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     constexpr uint64_t kPairRuled = 1ull << 62, kPairCheck = 1ull << 61;   // LDS route: count rule already applied / labels still to compare
     constexpr uint64_t kPairBwd = 1ull << 60, kPairFwd = 1ull << 59;        // which of y -> x, x -> y the pair stands for (the LDS route meets a pair once)
     bool fast = false;
-#ifdef AFQ_PUG_TIMING
-    if (tid == 0) { for (int q_ = 0; q_ < 8; ++q_) tacc[q_] = 0; tlast = wall_clock64(); }
-#endif
     {
         uint32_t lgP = 0;
         while (lgP < 20 && ((uint64_t)kPartTarget << lgP) < V) lgP += 2;
@@ -618,18 +583,8 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                 // reads(y) >= 2 * reads(x) (has_edge, pugutils.rs:76-99) - provided the labels overlap, which only classes
                 // that differ still have to show (stage 2)
                 constexpr uint64_t kUmi44 = (1ull << 44) - 1;
-#ifdef AFQ_PUG_TIMING
-                unsigned long long dbg_steps = 0, dbg_probes = 0;
-#define PUG_DBG_STEP ++dbg_steps
-#define PUG_DBG_PROBE ++dbg_probes
-#else
-#define PUG_DBG_STEP
-#define PUG_DBG_PROBE
-#endif
                 auto probe = [&](uint64_t pu, uint32_t slot, uint64_t xinfo, uint32_t xsig, bool same) {
-                    PUG_DBG_PROBE;
                     for (;; slot = (slot + 1) & (kTabSlots - 1)) {
-                        PUG_DBG_STEP;
                         const uint64_t k = t_key[slot];
                         if (k == kEmptyKey) break;
                         if ((k & kUmi44) != pu) continue;
@@ -657,7 +612,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                     }
                 };
                 const uint32_t lowb = lgP / 2;   // bases whose change moves a UMI to another partition
-                PUG_ACC(0);
                 for (uint32_t pp = 0; pp < P; ++pp) {
                     const uint32_t o0 = s_poff[pp], n = s_poff[pp + 1] - o0;
                     if (n == 0) continue;
@@ -665,7 +619,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                     for (uint32_t i = tid; i < kTabSlots; i += kPugNT) t_key[i] = kEmptyKey;
                     for (uint32_t i = tid; i < 2048; i += kPugNT) s_filt[i] = 0;
                     __syncthreads();
-                    PUG_ACC(1);
                     for (uint32_t i = tid; i < n; i += kPugNT) {
                         const uint64_t umi = pv_umi[o0 + i];
                         uint32_t slot = fold13(umi & kUmi44);
@@ -676,7 +629,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                         atomicOr(&s_filt[hb >> 5], 1u << (hb & 31u));
                     }
                     __syncthreads();
-                    PUG_ACC(2);
                     // the partition's own vertices: distance 0, and every change of a high base.  Three vertices per thread sit
                     // in registers while the (base, substitution) loop - uniform, so its constants are scalar - runs over them.
                     for (uint32_t i0 = tid; i0 < n; i0 += 3 * kPugNT) {
@@ -736,7 +688,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                             }
                         }
                     }
-                    PUG_ACC(3);
                     if (!C.exact_umi)
                         for (uint32_t b = 0; b < lowb; ++b) {   // vertices of the partitions one low-base change away: that one change.
                             // The three source partitions of a base are read together (three loads in flight per thread; the
@@ -760,14 +711,9 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
                                 }
                             }
                         }
-                    PUG_ACC(4);
                 }
                 __syncthreads();
                 fast = s_flag[0] <= pair_cap;
-#ifdef AFQ_PUG_TIMING
-                if (blockIdx.x < 4) { atomicAdd(&tacc[6], dbg_steps); atomicAdd(&tacc[7], dbg_probes); }
-                __syncthreads();
-#endif
               }   // (more matches than the list holds: a cell full of near-identical UMIs - the global route sizes its lists exactly)
             }
             __syncthreads();
@@ -800,7 +746,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         }
     }
     }
-    PUG_MARK(11);
     auto bloom_bit = [](uint64_t umi) -> uint32_t { return (uint32_t)((umi * kHashMul) >> 44); };
     auto bloom_bit2 = [](uint64_t umi) -> uint32_t { return (uint32_t)(((umi ^ (umi >> 23)) * 0xD6E8FEB86659FD93ull) >> 44); };
     if (!fast) {
@@ -811,7 +756,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     }
     }
     __syncthreads();
-    PUG_MARK(4);
     // Edge generation in two steps so that the expensive part runs with full waves: (A) every vertex tests
     // its 1 + 3L probe UMIs against the LDS filter and the survivors (probe UMI, vertex) go to a candidate
     // list; (B) one thread per candidate binary-searches the UMI-sorted vertices and applies the edge rule.
@@ -854,7 +798,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         }
         __syncthreads();
         NCAND = s_flag[1];
-        PUG_MARK(12);
         if (NCAND > cand_cap) {
             uint32_t ncand_mine = 0;
             for (uint32_t x = tid; x < V; x += kPugNT) {
@@ -878,7 +821,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
             }
         }
     }
-    PUG_MARK(13);
     uint32_t* tch = c_base;  // dead after phase 3: 1 = the vertex is the target of some edge
     for (uint32_t x = tid; x <= V; x += kPugNT) { deg[x] = 0; if (x < V) tch[x] = 0; }
     __syncthreads();
@@ -1000,7 +942,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         for (uint32_t i = tid; i < NCAND; i += kPugNT) for_each_edge_of(cand[i], [&](uint32_t x, uint32_t) { atomicAdd(&deg[x], 1u); });
     }
     __syncthreads();
-    PUG_MARK(14);
     uint32_t E = 0;
     for (uint32_t base = 0; base < V; base += 8 * kPugNT) {   // eight consecutive vertices per thread and scan
         const uint32_t x0 = base + 8 * tid;
@@ -1059,7 +1000,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
             for_each_edge_of(cand[i], [&](uint32_t x, uint32_t y) { edges[atomicAdd(&c_order[x], 1u)] = y; tch[y] = 1; });
     }
     __syncthreads();
-    PUG_MARK(5);
     // ---- 5. weakly connected components: min-label propagation + pointer jumping ----
     // Only vertices with an edge take part (~15 % of them: most molecules have no UMI neighbour); the others are
     // their own components and are resolved straight from their labels in 6a, without being listed or sorted.
@@ -1120,7 +1060,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
             }
             if (!s_flag[0]) break;
         }
-        PUG_MARK(6);
         for (uint32_t i = tid; i < NT; i += kPugNT) { uint32_t l = wl[i]; while (wl[l] != l) l = wl[l]; comp_sorted[i] = ((uint64_t)tl[l] << kVidBits) | tl[i]; }
         __syncthreads();
     } else {
@@ -1148,7 +1087,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         }
         if (!s_flag[0]) break;
     }
-    PUG_MARK(6);
     // a label may still point at a non-root after the last sweep; chase it
     for (uint32_t i = tid; i < NT; i += kPugNT) { const uint32_t v = tl[i]; uint32_t l = wlab[v]; while (wlab[l] != l) l = wlab[l]; comp_sorted[i] = ((uint64_t)l << kVidBits) | v; }
     __syncthreads();
@@ -1199,7 +1137,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     const uint32_t n_mid = n_tiny + s_flag[0], n_big = s_flag[1];
     __syncthreads();
 
-    PUG_MARK(7);
     // ---- 6a. single-vertex components: the label's genes (pugutils.rs:1262-1322) ----
     // A two-vertex component is always one molecule: it is weakly connected, so one of the two can reach the
     // other through a shared transcript and the greedy cover takes that 2-vertex arborescence first; its label
@@ -1321,7 +1258,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         append_cols(C, col);
         append_class2(C, cls, k0, k1);
     }
-    PUG_MARK(8);
     // ---- 6b. components of 3..64 vertices: one wave each, adjacency = one 64-bit mask per lane ----
     // What a wave needs of its component - per vertex the label and the adjacency mask - sits five dependent global reads deep
     // (list -> component bounds -> vertex id -> vertex record / edge range -> edge targets -> their local index), and a wave
@@ -1369,7 +1305,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     cover_tiny8<kPugNT / 64>(C, mrec, mid_off, n_tiny, wv, lane);   // 6b': components of 3..8 vertices, eight to a wave (afq_pug_common.h)
     cover_wave64<kPugNT / 64>(C, mrec, mid_off, n_tiny, n_mid, wv, lane);   // 9..64 vertices: a wave each
     __syncthreads();
-    PUG_MARK(9);
     // ---- 6c. larger components, one at a time by the whole workgroup ----
     for (uint32_t ci = 0; ci < n_big; ++ci) {
         const uint32_t c = big_list[ci];
@@ -1603,17 +1538,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         __syncthreads();
     }
     __syncthreads();
-    PUG_MARK(10);
-#ifdef AFQ_PUG_TIMING
-    if (tid == 0 && blockIdx.x < 4 && (work % 1024) < 4) {
-        auto ms = [&](int a, int b) { return (double)(tmark[b] - tmark[a]) / 1e5; };
-        printf("pug sort: sample-load=%.2f sample-sort=%.2f classify=%.2f scan+scatter=%.2f wave-sorts=%.2f ms\n", (double)(tsort[0] - tmark[0]) / 1e5, (double)(tsort[1] - tsort[0]) / 1e5, (double)(tsort[2] - tsort[1]) / 1e5, (double)(tsort[3] - tsort[2]) / 1e5, (double)(tsort[4] - tsort[3]) / 1e5);
-        printf("pug lds route: part+scatter=%.2f clear=%.2f insert=%.2f own=%.2f foreign=%.2f ms; probes=%llu run steps=%llu pairs=%u\n", tacc[0] / 1e5, tacc[1] / 1e5, tacc[2] / 1e5, tacc[3] / 1e5, tacc[4] / 1e5, tacc[7], tacc[6], n_pairs);
-        printf("pug cell R=%u V=%u K=%u NC=%u nmid=%u nbig=%u: sort=%.2f classes=%.2f umis=%.2f verts=%.2f | htab=%.2f bloom=%.2f cand=%.2f (2pass=%.2f) match+rule=%.2f fill=%.2f | wcc=%.2f comps=%.2f 6a=%.2f mid=%.2f big=%.2f out=%.2f | total=%.2f NCAND=%u E=%u\n",
-               R, V, K, NC, n_mid, n_big, ms(0, 1), ms(1, 2), ms(2, 3), 0.0, ms(3, 11), ms(11, 4), ms(4, 12), ms(12, 13), ms(13, 14), ms(14, 5),
-               ms(5, 6), ms(6, 7), ms(7, 8), ms(8, 9), 0.0, ms(9, 10), ms(0, 10), NCAND, E);
-    }
-#endif
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], cell); return; }
     if (tid == 0) {
         A.cell_ncols[cell] = s_cnt[0];

@@ -48,7 +48,7 @@ namespace afq {
 
 // The partition kernels' walk (a wave per partition, persistent workgroups): the partitions go to the XCDs - workgroups x, x + 8,
 // ... share one, they are dealt round-robin - in runs of 1024, a few cells each, 256 workgroups side by side on a run.  A cell's
-// partitions then meet in ONE L2: the search reads a partition's dozen neighbours, the partition and lone-vertex kernels read the
+// partitions then meet in ONE L2: the search reads a partition's dozen neighbours, the partition kernel reads the
 // labels of the cell's chunk.  (With a cell's partitions spread over all eight XCDs the search's FETCH_SIZE was 36 GB per
 // configs[2] step, eight times the vertices; in runs 19.9 GB.)  The grid is a multiple of 2048.
 template <typename F>
@@ -325,20 +325,6 @@ static_assert(kP2PartCap <= 256, "SearchLds::idx is a byte");
 // partition's first own slot says where (the graph kernel tells by pnp > pcnt), and the search runs again.  (Until round 4 such a
 // cell went to the one-workgroup kernel: on the label-tail workload that kernel was 40 ms of the 370 ms step.  A kernel of its
 // own, not a second trip through a loop here: the loop took the search from 79 to 127 VGPRs.)
-#ifdef AFQ_SEARCH_TIMING
-__device__ unsigned long long g_search_t[10];
-#define S_MARK(i) do { const unsigned long long n_ = clock64(); if (lane == 0) atomicAdd(&g_search_t[i], n_ - st_); st_ = n_; } while (0)
-__global__ void k_search_timing_dump() {
-    unsigned long long tot = 0;
-    for (int i = 0; i < 8; ++i) tot += g_search_t[i];
-    printf("search wave cycles: setup+build %.1f%% same-umi %.1f%% own filter %.1f%% own drain %.1f%% foreign fetch+filter %.1f%% foreign drain %.1f%% (unused) %.1f%% tail %.1f%% (partitions %llu, %.0f cycles each)\n",
-           100.0 * g_search_t[0] / tot, 100.0 * g_search_t[1] / tot, 100.0 * g_search_t[2] / tot, 100.0 * g_search_t[3] / tot, 100.0 * g_search_t[4] / tot,
-           100.0 * g_search_t[5] / tot, 100.0 * g_search_t[6] / tot, 100.0 * g_search_t[7] / tot, g_search_t[8], (double)tot / (double)g_search_t[8]);
-    for (int i = 0; i < 10; ++i) g_search_t[i] = 0;
-}
-#else
-#define S_MARK(i) do {} while (0)
-#endif
 template <bool OVER>
 __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, SearchLds& S, uint32_t* filt_all, uint32_t wv, uint32_t lane) {
     // filt_all: the four waves' presence filters, one behind the other in an array aligned to its own size - a filter word's byte
@@ -346,9 +332,6 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
     // ONE exclusive-or per probe, the array's address in the instruction's offset field
     uint32_t* t_umi = S.umi; uint32_t* t_word = S.word; uint8_t* t_idx = S.idx;
     uint32_t* s_filt = filt_all + wv * (kP2FiltBits / 32); uint32_t* s_np = &S.np;
-#ifdef AFQ_SEARCH_TIMING
-    unsigned long long st_ = clock64();
-#endif
     const uint32_t nv = A.pnv[gp];
     if (nv == 0) return;
     const uint32_t j = A.pcell[gp];
@@ -397,14 +380,13 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
         atomicOr(&s_filt[fb >> 5], 1u << (fb & 31u));
     }
     WAVE_SYNC();
-    S_MARK(0);
     auto filt = [&](uint32_t u) -> bool { const uint32_t f = fold11(u); return (s_filt[f >> 5] >> (f & 31u)) & 1u; };
     // Every vertex of the table with UMI pu against vertex x (cell slot gx, word xw).  A MATCH - x against the table's vertex y in
     // `slot`: UMIs as asked, signatures with a ref in common - is written down as a CANDIDATE pair with both directions of has_edge
     // decided (the read counts are at hand).  Whether the two labels really share a ref is a chain of dependent global loads (label
     // keys, record offsets, for hashed keys the ref lists): until late round 6 that chain ran here - first inside the table walk
     // that found the match, one or two lanes of the wave still in it (two thirds of the kernel's wave cycles), then, rounds 5-6,
-    // parked and checked a lane each at the partition's end (still 38 % of them: per-phase clocks, AFQ_SEARCH_TIMING) - and is now
+    // parked and checked a lane each at the partition's end (still 38 % of them: per-phase clocks of a measurement build) - and is now
     // k_p2_check's (afq_pugflat.hip), a thread per candidate over the whole range, which has no chain to wait for: it clears the
     // candidates that fail and flags the end points of the others.  (The search flagging the end points of its candidates itself -
     // byte stores of known values, no atomics in k_p2_check - was measured: a vertex that loses all its candidates then goes through
@@ -447,7 +429,6 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
         if ((uint32_t)r * 64 >= nv) break;   // (uniform)
         if (i < nv) probe((uint32_t)(own[r] >> 32), lo_p + i, (uint32_t)own[r], true);
     }
-    S_MARK(1);
     if (!A.exact_umi) {
         const char* fbase = reinterpret_cast<const char*>(filt_all);
         for (uint32_t b = b_lo; b < L; ++b) {   // (bases below m / 2 lie inside the low m bits: every change there leaves the partition)
@@ -471,7 +452,6 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
             ha[r] &= keep; hb[r] &= keep;
         }
     }
-    S_MARK(2);
     for (;;) {   // drain: every lane takes its next passed probe, whichever row it is in (static register indices: no scratch)
         const bool mine = (ha[0] | ha[1] | ha[2] | ha[3] | hb[0] | hb[1] | hb[2] | hb[3]) != 0;
         if (!__any(mine)) break;
@@ -491,7 +471,6 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
             probe((uint32_t)(ow >> 32) ^ (d << (pos & ~1u)), lo_p + r * 64 + lane, (uint32_t)ow, false);
         }
     }
-    S_MARK(3);
     // The vertices of the partitions one low-bit change away, FOUR partitions at a time (their places are in lanes k .. k + 3's
     // registers): the eight loads of a batch go out together and are waited for once.  A partition at a time with the next one's
     // load behind it, every load's latency was in the open - a partition takes some thirty instructions to go through the filter -
@@ -533,7 +512,6 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
             }
         }
     }
-    S_MARK(4);
     for (; __any(fhits != 0);) {
         const uint32_t ix = fhits ? (uint32_t)__builtin_ctzll(fhits) : 0u;
         const uint32_t k = ix >> 1, r = ix & 1u;
@@ -546,16 +524,10 @@ __device__ __forceinline__ void search_body(const P2Args& A, uint32_t gp, Search
         }
     }
     WAVE_SYNC();
-    S_MARK(5);
-    S_MARK(6);
     const uint32_t np = *s_np;
     if (lane == 0 && !OVER) A.pnp[gp] = np;   // (more than pcap: the second pass takes the partition)
     if (lane == 0 && OVER && np != pcap) set_err(A.st, kErrInternal, c.cell);   // (the same search twice: the same pairs)
     WAVE_SYNC();
-    S_MARK(7);
-#ifdef AFQ_SEARCH_TIMING
-    if (lane == 0) atomicAdd(&g_search_t[8], 1ull);
-#endif
 }
 __global__ __launch_bounds__(256, AFQ_P2_SEARCH_WGS) void k_p2_search(P2Args A) {
     if (A.st->err_code) return;   // an earlier kernel of the range failed (e.g. kErrLabelHash in k_p2_part, which then leaves its partition's vertices unwritten): nothing behind it may read that state - the host runs the range again or reports the error
@@ -704,44 +676,26 @@ __device__ __forceinline__ uint32_t molecule8_column(const PugCtx& c, uint32_t (
     return col;
 }
 
-#ifdef AFQ_LONE_TIMING
-__device__ unsigned long long g_lone_t[10];
-#define L_MARK(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long n_ = clock64(); if (lane == 0) atomicAdd(&g_lone_t[i], n_ - lt_); lt_ = n_; } while (0)
-__global__ void k_lone_timing_dump() {
-    unsigned long long tot = 0;
-    for (int i = 0; i < 7; ++i) tot += g_lone_t[i];
-    printf("lone wave cycles: head (scalar chain) %.1f%% keys+flags+offsets %.1f%% label words %.1f%% genes %.1f%% rules+stores %.1f%% coop labels %.1f%% classes %.1f%% (partitions %llu)\n",
-           100.0 * g_lone_t[0] / tot, 100.0 * g_lone_t[1] / tot, 100.0 * g_lone_t[2] / tot, 100.0 * g_lone_t[3] / tot, 100.0 * g_lone_t[4] / tot, 100.0 * g_lone_t[5] / tot, 100.0 * g_lone_t[6] / tot, g_lone_t[8]);
-    for (int i = 0; i < 10; ++i) g_lone_t[i] = 0;
-}
-#else
-#define L_MARK(i) do {} while (0)
-#endif
 // L8: labels of 5..8 refs by their own lane (molecule8_column; AFQ_TEST_P2_LONE_COOP=2) - an instance of its own: its eight-entry arrays
 // are registers of every lane whether or not a label needs them.
 #ifndef AFQ_LONE_ROWS
 #define AFQ_LONE_ROWS 2
 #endif
-// FLAT (late round 6): the rows are any run of a cell's slots, not a partition's - a slot past its partition's vertices holds a zero
-// key (k_p2_part), which is "no label", so a slot needs no partition to be resolved; only a staged two-gene class (em) does, and
-// the lane that has one works its partition out of the vertex's UMI and takes the next place in that partition's stage.
-template <bool L8, bool FLAT>
-__device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint32_t j, uint32_t lo_p, uint32_t n, uint32_t nv, uint32_t gp, uint32_t* s_cls, uint32_t* s_g, uint32_t lane) {
-#ifdef AFQ_LONE_TIMING
-    unsigned long long lt_ = clock64();
-#endif
+// The rows are any run of a cell's slots, not a partition's (late round 6) - a slot past its partition's vertices holds a zero key
+// (k_p2_part), which is "no label", so a slot needs no partition to be resolved; only a staged two-gene class (em) does, and the
+// lane that has one works its partition out of the vertex's UMI and takes the next place in that partition's stage.
+template <bool L8>
+__device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint32_t j, uint32_t lo_p, uint32_t n, uint32_t* s_g, uint32_t lane) {
     uint32_t* gc = A.gcnt + 4 * (size_t)j;
     const PugCtx C = make_ctx(A, c, gc);   // (the counters are the cell's global ones here: the rare class writes add to them directly)
     const uint64_t o = c.rd_base + lo_p;
-    uint32_t ncls = 0;   // wave-uniform
     // Two rows of 64 slots at a time, every level of the gather chain issued for both rows before anything waits: key / flag /
     // record offset, then (hashed keys only) the label's length and first four refs out of the chunk, then the genes of all
     // refs - five dependent trips per partition where a hashed label used to add four of its own per row it occurred in.
     const uint32_t cw = 2 + c.R * C.HW + c.n_ref;   // dwords of the chunk
     PugCtx Cg = C;
     Cg.gene_level = 1;   // (genes_of4 is handed gene ids below: the gathers are done here, for all slots together)
-    L_MARK(0);
-    constexpr int RW = FLAT ? AFQ_LONE_ROWS : 2;   // rows of 64 slots in flight per trip
+    constexpr int RW = AFQ_LONE_ROWS;   // rows of 64 slots in flight per trip
     for (uint32_t r0 = 0; r0 < n; r0 += 64 * RW) {   // (uniform)
         constexpr int NR = L8 ? 8 : 4;   // refs of a label a lane looks at itself
         uint64_t h2[RW];
@@ -749,11 +703,10 @@ __device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const uint32_t i = r0 + (uint32_t)r * 64 + lane;
-            h2[r] = i < nv ? A.s_h[o + i] : 0ull;
-            fl[r] = i < nv ? (A.v_flag[o + i] & 1u) : 1u;
-            of[r] = i < nv ? A.v_off[o + i] : 0u;
+            h2[r] = i < n ? A.s_h[o + i] : 0ull;
+            fl[r] = i < n ? (A.v_flag[o + i] & 1u) : 1u;
+            of[r] = i < n ? A.v_off[o + i] : 0u;
         }
-        L_MARK(1);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const uint32_t tag = fl[r] ? 0u : (uint32_t)(h2[r] >> 62);
@@ -772,12 +725,10 @@ __device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint
                 }
             }
         }
-        L_MARK(2);
 #pragma unroll
         for (int r = 0; r < RW; ++r)
 #pragma unroll
             for (int q = 0; q < NR; ++q) g4[r][q] = (uint32_t)q < ln[r] && ln[r] <= (uint32_t)NR ? C.t2g[t4[r][q]] : 0xFFFFFFFFu;
-        L_MARK(3);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const uint32_t i = r0 + (uint32_t)r * 64 + lane;
@@ -800,19 +751,12 @@ __device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint
                 }
             }
             if (i < n) C.cols[lo_p + i] = col;
-            if constexpr (FLAT) {
-                if (cls) {   // (one vertex in a dozen: its partition from its UMI's low bits, the next place of that partition's stage)
-                    const uint32_t gq = c.part_base + ((uint32_t)(A.s_u[o + i] >> 32) & ((1u << c.lgP) - 1u));
-                    const uint32_t k = atomicAdd(&A.pncls[gq], 1u);
-                    A.cstage[c.rd_base + A.poff[gq] + k] = ((uint64_t)k1 << 32) | k0;
-                }
-            } else {
-                const uint64_t mk = __ballot(cls);
-                if (cls) { const uint32_t q = ncls + (uint32_t)__popcll(mk & ((1ull << lane) - 1)); s_cls[2 * q] = k0; s_cls[2 * q + 1] = k1; }
-                ncls += (uint32_t)__popcll(mk);
+            if (cls) {   // (one vertex in a dozen: its partition from its UMI's low bits, the next place of that partition's stage)
+                const uint32_t gq = c.part_base + ((uint32_t)(A.s_u[o + i] >> 32) & ((1u << c.lgP) - 1u));
+                const uint32_t k = atomicAdd(&A.pncls[gq], 1u);
+                A.cstage[c.rd_base + A.poff[gq] + k] = ((uint64_t)k1 << 32) | k0;
             }
         }
-        L_MARK(4);
         // labels of more than 64 refs (without the cooperative path: of more than four): one lane after the other, its genes in the
         // wave's LDS row - 64 words of a lane's own were 272 bytes of scratch per lane of every wave, for a label in ten thousand.
         // (Behind the rows' loop, where the gathered refs and genes are dead: inside it the kernel lost its seventh wave per SIMD.)
@@ -830,41 +774,13 @@ __device__ __forceinline__ void lone_rows(const P2Args& A, const P2Cell& c, uint
             }
         }
     }
-    L_MARK(5);
-#ifdef AFQ_LONE_TIMING
-    if (lane == 0) atomicAdd(&g_lone_t[8], 1ull);
-#endif
-    if (FLAT || !ncls) return;
-    WAVE_SYNC();
-    uint64_t* stage = A.cstage + o;   // (at most one class per vertex: the partition's own slots hold them; the graph kernel moves them into the cell's label area)
-    for (uint32_t i = lane; i < ncls; i += 64) stage[i] = ((uint64_t)s_cls[2 * i + 1] << 32) | s_cls[2 * i];
-    if (lane == 0) A.pncls[gp] = ncls;
-    WAVE_SYNC();
-    L_MARK(6);
-}
-template <bool L8>
-__device__ __forceinline__ void lone_body(const P2Args& A, uint32_t gp, uint32_t* s_cls, uint32_t* s_g, uint32_t lane) {
-    const uint32_t n = A.pcnt[gp], nv = A.pnv[gp], j = A.pcell[gp], lo_p = A.poff[gp];
-    if (n == 0) return;
-    const P2Cell c = A.cells[j];
-    lone_rows<L8, false>(A, c, j, lo_p, n, nv, gp, s_cls, s_g, lane);
 }
 #ifndef AFQ_LONE_WPE
-#define AFQ_LONE_WPE 7   // waves per SIMD k_p2_lone<false> is compiled for
+#define AFQ_LONE_WPE 7   // waves per SIMD k_pl_lone<false> is compiled for
 #endif
-template <bool L8>
-__global__ __launch_bounds__(256, L8 ? 5 : AFQ_LONE_WPE) void k_p2_lone(P2Args A) {
-    if (A.st->err_code) return;   // an earlier kernel of the range failed (e.g. kErrLabelHash in k_p2_part, which then leaves its partition's vertices unwritten): nothing behind it may read that state - the host runs the range again or reports the error
-    __shared__ uint32_t s_cls4[4][512];
-    __shared__ uint32_t s_g4[4][kMaxGenesPerLabel];   // (a wave's row for the genes of a label of more than 64 refs)
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    for_each_partition_in_runs(A.n_parts, wv, [&](uint32_t gp) { lone_body<L8>(A, gp, s_cls4[wv], s_g4[wv], lane); });
-}
-// ... and over the range's tiles of 4096 slots, a wave per 256 slots of one: no partition's head (three dependent scalar loads in front
-// of everything), no half-empty rows at a partition's end, no staging of classes through LDS.
-#ifndef AFQ_LONE_FLAT
-#define AFQ_LONE_FLAT 1
-#endif
+// The lone vertices over the range's tiles of 4096 slots, a wave per 256 slots of one.  (Until late round 6 a wave per partition,
+// k_p2_lone: a partition's head cost three dependent scalar loads in front of everything, its last rows were half empty, and its
+// classes were staged through LDS.)
 template <bool L8>
 __global__ __launch_bounds__(256, L8 ? 5 : AFQ_LONE_WPE) void k_pl_lone(P2Args A) {
     if (A.st->err_code) return;
@@ -875,18 +791,13 @@ __global__ __launch_bounds__(256, L8 ? 5 : AFQ_LONE_WPE) void k_pl_lone(P2Args A
     const P2Cell c = A.cells[j];
     const uint32_t t0 = td.y * A.tile, t1 = min(c.R, t0 + A.tile);
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    for (uint32_t lo = t0 + wv * 256; lo < t1; lo += 1024) { const uint32_t n = min(256u, t1 - lo); lone_rows<L8, true>(A, c, j, lo, n, n, 0u, nullptr, s_g4[wv], lane); }
+    for (uint32_t lo = t0 + wv * 256; lo < t1; lo += 1024) { const uint32_t n = min(256u, t1 - lo); lone_rows<L8>(A, c, j, lo, n, s_g4[wv], lane); }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 5. one workgroup per cell: the vertices that have an edge (about a quarter of them) - components, the two-vertex rule,
 //    the covers.  Everything is sized by the pairs the search left; nothing here walks the cell's reads, and the one pass over
 //    the cell's vertices (class minima, below) reads eight bytes per vertex.
-#ifdef AFQ_PUG_TIMING
-#define G_MARK(i) do { __syncthreads(); if (threadIdx.x == 0) tmark[i] = wall_clock64(); } while (0)
-#else
-#define G_MARK(i) do {} while (0)
-#endif
 constexpr int kGNT = 256;
 #ifndef AFQ_GTAB
 #define AFQ_GTAB 4096
@@ -913,9 +824,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
     __shared__ uint32_t s_flag[4];
     __shared__ unsigned long long s_ebase;
     __shared__ uint32_t s_next;
-#ifdef AFQ_PUG_TIMING
-    __shared__ unsigned long long tmark[16];
-#endif
     const uint32_t tid = threadIdx.x;
   for (;;) {
     __syncthreads();
@@ -938,7 +846,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
     const uint64_t* cu = A.s_u + c.rd_base;
     const uint32_t* coff = A.v_off + c.rd_base;
     uint32_t* lidx = A.lidx + c.rd_base;
-    G_MARK(0);
     // ---- 0. what the partition kernels left per partition: pairs (search), two-gene classes (lone vertices), vertices under
     //         a hashed label key ----
     const uint32_t P = 1u << c.lgP;
@@ -994,7 +901,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
     uint32_t* q = pool_take(2ull * n_pairs);
     if (!q) return;
     uint64_t* lp = reinterpret_cast<uint64_t*>(q);   // pairs over local ids: x | y << 24 | directions << 48
-    G_MARK(1);
     // ---- 1. the touched vertices: the search flagged them; a scan over the flags counts them, a second numbers them (any
     //         numbering will do: the reference's order enters through the order keys of step 6 only) ----
     const uint64_t* psrc = A.pairs + c.rd_base;
@@ -1051,7 +957,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         }
     }
     gsync();
-    G_MARK(2);
     // ---- 2. weakly connected components over the pair list: union-find with compare-and-swap hooking (parents in LDS when they
     //         fit, else in the pool through workgroup-scope L2 atomics).  A root is only ever hooked under a SMALLER vertex, so
     //         the parent pointers cannot close a cycle; find() shortens the path it walks (a racing shortcut still points at an
@@ -1085,7 +990,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         }
     }
     gsync();
-    G_MARK(3);
     // ---- 3. the components by counting: sizes per root, then by size pairs / 3..8 / 9..64 / 65..4096 (anything else - a
     //         component of more than 4096 vertices that is still under --large-graph-thresh - is not for this kernel), every
     //         listed component's slots, every vertex into its component's next slot.  A component above --large-graph-thresh
@@ -1221,7 +1125,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         }
     }
     gsync();
-    G_MARK(4);
     // ---- 4. class minima for the classes of the listed components' vertices: their order decides ties.  The cell's vertex
     //         slots stream ONCE through a hash table keyed by label key that holds the asked-for classes (slots past a
     //         partition's last vertex hold key 0: no class) - in LDS when they are few, out of the pool otherwise.  A vertex
@@ -1349,8 +1252,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], c.cell); return; }
     }
     gsync();
-    G_MARK(5);
-    G_MARK(6);
     // ---- 6. components of 3..64 vertices: their vertices in the reference's order (class by first appearance = smallest
     //         record offset, then UMI), the edges between them as masks over those positions, gathered into the covers' records ----
     for (uint32_t s2 = S_lo + tid; s2 < S_mid; s2 += GNT) okey[s2] = ((uint64_t)cmin[s2] << 32) | (uint32_t)(cu[tl[slot_v[s2]]] >> 32);
@@ -1406,14 +1307,6 @@ __global__ __launch_bounds__(GNT) void k_p2_graph(P2Args A, const uint32_t* list
         mrec[2 * at + 1] = make_uint4(r2, r3, (uint32_t)am, (uint32_t)(am >> 32));
     }
     gsync();
-    G_MARK(7);
-#ifdef AFQ_PUG_TIMING
-    if (tid == 0 && (work % 512) < 2) {
-        auto us = [&](int a, int b) { return (double)(tmark[b] - tmark[a]) / 100.0; };
-        printf("p2 graph cell R=%u pairs=%u NT=%u n_tiny=%u n_mid=%u n_pr=%u S_mid=%u: gather=%.0f touched=%.0f wcc=%.0f comps=%.0f classes=%.0f records=%.0f total=%.0f us\n",
-               R, n_pairs, NT, n_tiny, n_mid, n_pr, S_mid, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(6, 7), us(0, 7));
-    }
-#endif
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], c.cell); return; }
     // what the cover kernel (k_p2_cover) takes over: where the cell's lists lie in the pool, how many there are, the cell's counters
     if (tid == 0) {
@@ -1647,11 +1540,6 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
     __shared__ uint32_t s_cnt[4];
     __shared__ uint32_t s_next;
     __shared__ uint32_t s_ws[CNT / 64];
-#ifdef AFQ_PUG_TIMING
-    __shared__ unsigned long long tmark[8];
-    unsigned long long t_keys = 0, t_stream = 0, t_order = 0;
-#define T_ADD(acc, code) do { __syncthreads(); const unsigned long long t0__ = wall_clock64(); code; __syncthreads(); acc += wall_clock64() - t0__; } while (0)
-#endif
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
   for (;;) {
     __syncthreads();
@@ -1696,7 +1584,6 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
     }
     gsync();
     const uint32_t n_batches = (n_keys + TKeys - 1) / TKeys;
-    G_MARK(0);
     auto mix = [](uint64_t h) -> uint32_t { uint32_t v = ((uint32_t)h ^ (uint32_t)(h >> 32)) * 0x9E3779B1u; return v ^ (v >> 15); };
     auto bloom_at = [&](uint32_t mx) -> uint32_t { return (mx >> 16) & (BloomWords * 32 - 1); };
     auto find = [&](uint64_t h, uint32_t mx, bool insert) -> uint32_t {   // slot of h, or 0xFFFFFFFF
@@ -1717,7 +1604,6 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
         for (uint32_t i = tid; i < TSlots; i += CNT) { t_key[i] = ~0ull; t_min[i] = 0xFFFFFFFFu; }
         for (uint32_t i = tid; i < BloomWords; i += CNT) s_bloom[i] = 0;
         __syncthreads();
-        G_MARK(1);
         // the classes that are asked for: the labels of the batch's uncovered vertices
         for (uint32_t e = tid; e < nE; e += CNT) {
             const uint32_t* en = entry(e);
@@ -1732,7 +1618,6 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
             }
         }
         __syncthreads();
-        G_MARK(2);
         // every vertex slot of the cell once (slots past a partition's last vertex hold key 0: no class), six per thread and trip
         for (uint32_t g0 = tid; g0 - tid < R; g0 += 6 * CNT) {
             uint64_t h6[6];
@@ -1757,7 +1642,6 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
                     !lab_equal(rec_label(C, off6[r]), rec_label(C, old6[r]))) s_cnt[3] = kErrLabelHash;
         }
         __syncthreads();
-        G_MARK(3);
         if constexpr (CMIN_ONLY) {   // the minima to where k_pc_resume reads them: beside the records
             uint32_t* cmv = A.pool + A.pfd->cmv;
             for (uint32_t e = tid; e < nE; e += CNT) {
@@ -1856,19 +1740,10 @@ __global__ __launch_bounds__(CNT) void k_p2_tied(P2Args A, const uint32_t* list,
     gsync();
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], c.cell); return; }
     if constexpr (CMIN_ONLY) continue;
-    G_MARK(4);
     uint32_t* const stage = reinterpret_cast<uint32_t*>(t_key) + (size_t)wv * 64 * kStageRefs;   // (the class table is dead: 4 KiB of it per wave stage the labels)
     cover_tiny8<CNT / 64, kCoverResume>(C, mrec, mid_off, nA, wv, lane, nullptr, listA, stage);
     cover_wave64<CNT / 64, kCoverResume>(C, mrec, mid_off, 0u, nB, wv, lane, nullptr, listB, stage);
     gsync();
-    G_MARK(5);
-#ifdef AFQ_PUG_TIMING
-    if (tid == 0 && (work % 512) < 2) {
-        auto us = [&](int a, int b) { return (double)(tmark[b] - tmark[a]) / 100.0; };
-        printf("p2 tied cell R=%u entries=%u+%u keys=%u batches=%u: init=%.0f keys=%.0f stream=%.0f order=%.0f resume=%.0f total=%.0f us (last batch's marks)\n",
-               R, nA, nB, n_keys, n_batches, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(0, 5));
-    }
-#endif
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], c.cell); return; }
     if (tid == 0) {
         A.cell_ncols[c.cell] = s_cnt[0];
@@ -1891,22 +1766,13 @@ void launch_p2_part(hipStream_t s, const P2Args& a) { if (a.n_parts) AFQ_LAUNCH(
 void launch_p2_search(hipStream_t s, const P2Args& a) {
     if (!a.n_parts) return;
     AFQ_LAUNCH(k_p2_search, p2_grid(a.n_parts), 256, s, a);
-#ifdef AFQ_SEARCH_TIMING
-    hipLaunchKernelGGL(k_search_timing_dump, dim3(1), dim3(1), 0, s);
-#endif
     AFQ_LAUNCH(k_p2_search_over, std::min((a.n_parts + 255) / 256, 2048u), 256, s, a);   // (the partitions with more pairs than slots, normally none: two counts per partition are read)
     launch_p2_check(s, a);   // (the candidates that fail the label test cleared, the end points of the others flagged: afq_pugflat.hip)
 }
 void launch_p2_lone(hipStream_t s, const P2Args& a) {
     if (!a.n_parts) return;
-    if (AFQ_LONE_FLAT) {
-        if (a.lone_coop >= 2) AFQ_LAUNCH(k_pl_lone<true>, a.n_tiles, 256, s, a);
-        else AFQ_LAUNCH(k_pl_lone<false>, a.n_tiles, 256, s, a);
-    } else if (a.lone_coop >= 2) AFQ_LAUNCH(k_p2_lone<true>, p2_grid(a.n_parts), 256, s, a);
-    else AFQ_LAUNCH(k_p2_lone<false>, p2_grid(a.n_parts), 256, s, a);
-#ifdef AFQ_LONE_TIMING
-    hipLaunchKernelGGL(k_lone_timing_dump, dim3(1), dim3(1), 0, s);
-#endif
+    if (a.lone_coop >= 2) AFQ_LAUNCH(k_pl_lone<true>, a.n_tiles, 256, s, a);
+    else AFQ_LAUNCH(k_pl_lone<false>, a.n_tiles, 256, s, a);
 }
 void launch_p2_graph(hipStream_t s, const P2Args& a, uint64_t n_reads) {
     if (!a.n_cells) return;

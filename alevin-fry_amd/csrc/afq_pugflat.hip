@@ -299,10 +299,6 @@ __device__ __forceinline__ void pf_for_each_pair4(const P2Args& A, uint32_t* s_s
 //    owns a partition waits for one after the other and a thread per candidate over the whole range does not notice.  A candidate
 //    that fails is cleared (0: no direction bit - every loop over pairs skips it); the end points of the others get bit 0 of their
 //    flag bytes.
-#ifdef AFQ_CHECK_COUNT
-__device__ unsigned long long g_check_n[2];
-__global__ void k_check_count_dump() { printf("k_p2_check: %llu candidates, %llu cleared\n", g_check_n[0], g_check_n[1]); g_check_n[0] = g_check_n[1] = 0; }
-#endif
 #ifndef AFQ_CHECK_PER
 #define AFQ_CHECK_PER 2
 #endif
@@ -365,9 +361,6 @@ __global__ __launch_bounds__(256) void k_p2_check(P2Args A) {
                     const uint32_t* W = reinterpret_cast<const uint32_t*>(A.bytes + A.cells[cj2[r]].chunk_off);
                     ok = klab_overlap(klab(W, A.hw, hx[r], ox[r]), klab(W, A.hw, hy[r], oy[r]));
                 }
-#ifdef AFQ_CHECK_COUNT
-                atomicAdd(&g_check_n[0], 1ull); if (!ok) atomicAdd(&g_check_n[1], 1ull);
-#endif
                 if (!ok) { *sp[r] = 0ull; continue; }
                 const unsigned long long ax = rb[r] + gx[r], ay = rb[r] + gy[r];
                 // (bit 0 of both end points' flag bytes.  A byte read and, if the bit is not there yet, a byte written: threads that race
@@ -383,9 +376,6 @@ __global__ __launch_bounds__(256) void k_p2_check(P2Args A) {
 }
 void launch_p2_check(hipStream_t s, const P2Args& a) {
     if (a.n_parts) AFQ_LAUNCH(k_p2_check, std::min((a.n_parts + 255) / 256, 4096u), 256, s, a);
-#ifdef AFQ_CHECK_COUNT
-    hipLaunchKernelGGL(k_check_count_dump, dim3(1), dim3(1), 0, s);
-#endif
 }
 
 // 2. components: one thread per pair.  A root is only ever hooked under a SMALLER vertex (no cycle); find() halves the path it
@@ -500,7 +490,7 @@ __global__ __launch_bounds__(256) void k_pf_cats(P2Args A) {
     if (threadIdx.x < 5) A.tq[(size_t)(kQPr + threadIdx.x) * A.nta + i] = s_c[threadIdx.x];
 }
 
-// 5. The lone vertices' two-gene classes (em only): k_p2_lone staged them at their partitions' slots, a count per partition.  The scan
+// 5. The lone vertices' two-gene classes (em only): k_pl_lone staged them at their partitions' slots, a count per partition.  The scan
 //    of the counts over the range's partitions (two levels, as for the tiles; a cell's partitions are consecutive) says where a
 //    partition's classes go in its cell's label area; a thread per partition moves them.
 __device__ __forceinline__ uint32_t pf_pc(const P2Args& A, uint32_t gp) { return A.pcpre[gp] + A.pbq[gp >> 10]; }   // staged classes in front of partition gp (gp = n_parts: all)
@@ -971,7 +961,7 @@ void launch_pf_build(hipStream_t s, const P2Args& a, uint64_t n_reads) {
     if (a.em && a.lab) {
         AFQ_LAUNCH(k_pf_pscan1, a.npa / 1024, 1024, s, a);
         AFQ_LAUNCH(k_pf_pscan2, 1, 1024, s, a);
-        AFQ_LAUNCH(k_pf_move, pf_grid(a.n_parts, 256), 256, s, a);   // (gcnt[1], [2] still hold what k_p2_lone left: k_pf_cells raises them afterwards)
+        AFQ_LAUNCH(k_pf_move, pf_grid(a.n_parts, 256), 256, s, a);   // (gcnt[1], [2] still hold what k_pl_lone left: k_pf_cells raises them afterwards)
     }
     AFQ_LAUNCH(k_pf_cells, (a.n_cells + 255) / 256, 256, s, a);
     AFQ_LAUNCH(k_pf_tiles, (a.n_tiles + 255) / 256, 256, s, a);

@@ -11,7 +11,7 @@ from util import pkg
 synth = pkg.synth
 
 POOL_HOOKS = ("AFQ_TEST_POOL_WORDS", "AFQ_TEST_POOL_ROOM_WORDS")
-HOOKS = ("AFQ_TEST_DECODE", "AFQ_TEST_DECODE_DEDUP", "AFQ_TEST_P2_LONE_COOP", "AFQ_TEST_P2_DEFER_MIN", "AFQ_TEST_P2_GRAPH") + POOL_HOOKS
+HOOKS = ("AFQ_TEST_DECODE", "AFQ_TEST_P2_LONE_COOP", "AFQ_TEST_P2_DEFER_MIN", "AFQ_TEST_P2_GRAPH") + POOL_HOOKS
 
 
 @dataclass
@@ -64,17 +64,19 @@ def with_pool_pressure(w, seed):
 def tailed(seed):
     """Third family (seeds from 2000; from 3000: parsimony with AFQ_TEST_P2_LONE_COOP=2): the bench's label-tail model out of the
     native generator - reads of up to 64 alignments on gene families - through a decoder picked per seed (the planner's choice,
-    lane per record, lane per dword with either way of finding a record's repeated genes) and every resolution."""
+    lane per record, lane per dword) and every resolution."""
     sn = importlib.import_module("alevin-fry_amd.synth_native")
     rng = np.random.default_rng(99000 + seed)
     res = ["cr-like", "cr-like-em", "trivial", "parsimony", "parsimony-em", "cr-like", "cr-like-em"][seed % 7]
     usa = bool(rng.integers(0, 2))
     dec = [None, "recs", "keys", "keys", "keys"][int(rng.integers(0, 5))]
-    dedup = ["hash", "scan"][int(rng.integers(0, 2))]
-    coop = str(int(rng.integers(0, 3)))   # k_p2_lone: labels over four refs by their lane in scratch memory (0), by the wave (1), 5..8 refs by the lane in registers and 9..64 by the wave (2)
+    # Both draws stay, so every seed builds the workload it always did: the first picked a dedup route of the lane-per-dword decoder
+    # (one is left); of the second, 0 (a lone-vertex route now gone) leaves the hook unset - the planner's pick.
+    rng.integers(0, 2)
+    coop = [None, "1", "2"][int(rng.integers(0, 3))]   # k_pl_lone: labels of 5..64 refs by the wave (1); 5..8 refs by the lane in registers, 9..64 by the wave (2)
     if seed >= 3000:   # fourth family: parsimony only, the lone-vertex kernel's per-lane route for labels of 5..8 refs
         res, coop = ["parsimony", "parsimony-em"][seed % 2], "2"
-    env = {k: v for k, v in (("AFQ_TEST_DECODE", dec), ("AFQ_TEST_DECODE_DEDUP", dedup), ("AFQ_TEST_P2_LONE_COOP", coop)) if v is not None}
+    env = {k: v for k, v in (("AFQ_TEST_DECODE", dec), ("AFQ_TEST_P2_LONE_COOP", coop)) if v is not None}
     d = sn.generate(seed=seed, n_cells=int(rng.choice([8, 40, 150])), median_reads=float(rng.choice([300.0, 2500.0, 9000.0])), sigma=float(rng.choice([0.5, 1.3])),
                     num_genes=int(rng.choice([40, 400, 3000])), txp_per_gene=int(rng.integers(1, 6)), usa=usa, umi_err=float(rng.choice([0.0, 0.02])),
                     tail=float(rng.choice([0.5, 0.65, 0.8, 0.9])), tail_max=int(rng.choice([8, 64])), family=int(rng.choice([4, 8, 16])))
@@ -83,7 +85,7 @@ def tailed(seed):
         kw["sa_model"] = "prefer-ambig"
     cfg = pkg.WorkerConfig.for_resolution(res, usa_mode=usa, num_genes=d.num_genes, num_rows=d.num_rows, umi_len=12, **kw)
     return Workload(cfg, d.tid_to_gid, d.data, d.chunk_off, env,
-                    f"seed {seed} {res} usa={usa} decoder={dec} dedup={dedup} lone_coop={coop} {kw} cells={len(d.chunk_off)}", int(d.n_reads))
+                    f"seed {seed} {res} usa={usa} decoder={dec} lone_coop={coop} {kw} cells={len(d.chunk_off)}", int(d.n_reads))
 
 
 def big_cells(seed):

@@ -521,21 +521,20 @@ def test_tie_shapes_and_wide_umis(oracle, usa, pad_reads):
 
 
 def set_decoder(monkeypatch, decoder):
-    """recs: one lane per record; keys: one lane per dword, a record's repeated genes found by look-back compares and a scan;
-    keys-hash: one lane per dword, repeated genes found through an LDS hash table (AFQ_TEST_DECODE_DEDUP=hash)."""
-    monkeypatch.setenv("AFQ_TEST_DECODE", "keys" if decoder == "keys-hash" else decoder)
-    monkeypatch.setenv("AFQ_TEST_DECODE_DEDUP", "hash" if decoder == "keys-hash" else "scan")   # (hash is the default)
+    """recs: one lane per record; keys: one lane per dword, a record's repeated genes found through an LDS hash table (`trivial`:
+    by look-back compares and a scan)."""
+    monkeypatch.setenv("AFQ_TEST_DECODE", decoder)
 
 
-@pytest.mark.parametrize("decoder", ["keys", "keys-hash"])
 @pytest.mark.parametrize("usa", [False, True])
-def test_many_gene_reads_both_dedups(oracle, monkeypatch, decoder, usa):
+def test_many_gene_reads_hash_dedup(oracle, monkeypatch, usa):
     """Reads of many alignments that repeat genes (the bench's label-length tail: geometric extra refs on gene families, up to
     64 per read): which alignment of a read is the first to name its gene decides the read's keys.  Cells from a handful of
-    reads to many buckets; the lane-per-dword decoder with both ways of finding the repeats, against the oracle."""
+    reads to many buckets; the lane-per-dword decoder, which finds the repeats through its LDS hash table, against the oracle."""
     import importlib
 
     sn = importlib.import_module("alevin-fry_amd.synth_native")
+    decoder = "keys"
     set_decoder(monkeypatch, decoder)
     d = sn.generate(seed=13 + usa, n_cells=90, median_reads=2500.0, sigma=1.4, num_genes=300, txp_per_gene=4, usa=usa, umi_err=0.02,
                     tail=0.75, tail_max=64, family=8)
@@ -546,14 +545,14 @@ def test_many_gene_reads_both_dedups(oracle, monkeypatch, decoder, usa):
         assert st["n_fallback_cells"] == 0
 
 
-@pytest.mark.parametrize("decoder", ["recs", "keys", "keys-hash"])
+@pytest.mark.parametrize("decoder", ["recs", "keys"])
 @pytest.mark.parametrize("resolution", ["cr-like", "trivial"])
 def test_long_and_straddling_records(oracle, monkeypatch, decoder, resolution):
     """Records of every awkward length for the walk-free decoders: 0 alignments, just around the inline limits
     (3, 4), around the 64-dword halo, around a whole 256-dword slab, and thousands of alignments (a record that
     spans many slabs, so later slabs start in the middle of it).  Alignments repeat genes on purpose.  Both
-    decoders (one lane per record / one lane per dword, the latter with both ways of finding a record's repeated genes) must
-    agree with the oracle bit for bit."""
+    decoders (one lane per record / one lane per dword, the latter with both ways of finding a record's repeated genes: the
+    hash table for cr-like, the look-back scan for trivial) must agree with the oracle bit for bit."""
     set_decoder(monkeypatch, decoder)
     rng = np.random.default_rng(5)
     n_txp, n_genes = 6000, 700
@@ -602,8 +601,8 @@ def test_empty_and_single_cell_batches(oracle, resolution):
 
 @pytest.mark.parametrize("usa", [False, True])
 def test_giant_cell_beyond_the_lds_histogram(oracle, usa):
-    """A 600 k-read cell gets 4096 buckets - more than the LDS histogram / multisplit hold (2048) - so its tiles
-    take the straight-to-global paths of k_hist and k_scatter; a small neighbour rides along."""
+    """A 600 k-read cell gets 4096 buckets - more than the LDS multisplit holds (2048) - so its tiles take k_scatter's
+    straight-to-global path; a small neighbour rides along."""
     s = synth.synth(21, [600000, 50], num_genes=3000, usa=usa, dup=0.4, zipf=0.8)
     b, off = s.encode()
     got, want, st = run_both(oracle, cfg_for(s), s.tid_to_gid, b, off)
@@ -611,13 +610,12 @@ def test_giant_cell_beyond_the_lds_histogram(oracle, usa):
     assert_same_result(got, want)
 
 
-@pytest.mark.parametrize("env", [{"AFQ_TEST_FIXED_SLABS": "0"}, {"AFQ_TEST_SLAB_CAP": "8"}, {"AFQ_TEST_SLAB_CAP": "200"}, {}])
+@pytest.mark.parametrize("env", [{"AFQ_TEST_SLAB_CAP": "8"}, {"AFQ_TEST_SLAB_CAP": "200"}, {}], ids=["env1", "env2", "env3"])   # (env0 was a route now gone)
 @pytest.mark.parametrize("res,usa", [("cr-like", False), ("cr-like", True), ("cr-like-em", True)])
 def test_bucket_placement_routes_agree(oracle, monkeypatch, env, res, usa):
     """Keys of a multi-bucket cell go to fixed-capacity bucket slabs without a counting pass; a bucket that outgrows its
-    slab sends its cell through the exact placement (scan of the counts the cursors already hold).  The exact route
-    alone (AFQ_TEST_FIXED_SLABS=0), slabs so small that every cell overflows (8), slabs that only the heavy-UMI cell
-    overflows (200), and the default: all against the oracle."""
+    slab sends its cell through the exact placement (scan of the counts the cursors already hold).  Slabs so small that
+    every cell overflows (8), slabs that only the heavy-UMI cell overflows (200), and the default: all against the oracle."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     sizes = [60000, 20000, 9000, 5000, 3000, 1200, 700, 300, 90, 12]

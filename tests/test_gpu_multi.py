@@ -64,8 +64,7 @@ def test_generated_workload_quantifies_like_the_oracle(oracle, monkeypatch, tail
     an ordinary collated RAD as far as both are concerned - with the label-length tail too (labels of up to dozens of refs
     on gene families: the long-record paths of the decoders, hashed label keys, molecules of more than four genes).  On the
     tailed input the parsimony resolutions also run with each way the lone-vertex kernel has of resolving a label of more than
-    four refs (AFQ_TEST_P2_LONE_COOP: by its lane in scratch memory, by the wave, 5..8 refs by the lane in registers; the default picks
-    by range)."""
+    four refs (AFQ_TEST_P2_LONE_COOP: by the wave, 5..8 refs by the lane in registers; the default picks by range)."""
     d = sn.generate_device(device=0, seed=3, n_cells=60, median_reads=3000.0, num_genes=400, txp_per_gene=4, usa=True, umi_err=0.03,
                            tail=tail, family=8)
     try:
@@ -73,7 +72,7 @@ def test_generated_workload_quantifies_like_the_oracle(oracle, monkeypatch, tail
         for res in ("cr-like", "parsimony-em", "parsimony", "cr-like-em"):
             cfg = pkg.WorkerConfig.for_resolution(res, usa_mode=True, num_genes=d.num_genes, num_rows=d.num_rows, umi_len=12)
             want = oracle.quant(cfg, d.tid_to_gid, host, d.chunk_off, n_threads=4)
-            for lone in ((None, "0", "1", "2") if tail and res.startswith("parsimony") else (None,)):
+            for lone in ((None, "1", "2") if tail and res.startswith("parsimony") else (None,)):
                 with monkeypatch.context() as mp:
                     if lone is not None:
                         mp.setenv("AFQ_TEST_P2_LONE_COOP", lone)
