@@ -270,6 +270,8 @@ def load_library(path: str = LIB_PATH):
     lib.afq_submit.restype = C.c_int
     lib.afq_submit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint64]
     lib.afq_submit_device.restype = C.c_int
+    lib.afq_set_aln_extra_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    lib.afq_set_aln_extra_bytes.restype = C.c_int
     lib.afq_collect.argtypes = [C.c_void_p, p(AfqResult)]
     lib.afq_collect.restype = C.c_int
     lib.afq_result_release.argtypes = [p(AfqResult)]
@@ -310,7 +312,9 @@ class _Held(np.ndarray):
 class Quantifier:
     """One per device: config + tid_to_gid resident on the GPU (afq_ctx)."""
 
-    def __init__(self, cfg: WorkerConfig, tid_to_gid: np.ndarray, device: int = 0):
+    def __init__(self, cfg: WorkerConfig, tid_to_gid: np.ndarray, device: int = 0, aln_extra_bytes: int = 0):
+        """aln_extra_bytes: records carry a position of this many bytes (1, 2, 4, 8) behind every alignment word (the RAD
+        alignment tag `pos`; afq_set_aln_extra_bytes); 0 = plain records."""
         self.lib = load_library()
         self.cfg = cfg
         self._t2g = np.ascontiguousarray(tid_to_gid, dtype=np.uint32)
@@ -321,6 +325,12 @@ class Quantifier:
         if rc != 0:
             raise AfqError(rc, (self.lib.afq_last_error(None) or b"").decode())
         self._h = h
+        if aln_extra_bytes:
+            self.set_aln_extra_bytes(aln_extra_bytes)
+
+    def set_aln_extra_bytes(self, e: int):
+        """Width of the position behind every alignment word of the records submitted from now on (0: none)."""
+        self._check(self.lib.afq_set_aln_extra_bytes(self._h, int(e)))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -207,6 +207,9 @@ struct afq_ctx {
     // downstream works on that copy - w_off / w_nbytes are the chunks of the copy, chunk_off / hdr stay the caller's
     bool widen = false;
     uint32_t eff_bc = 0, eff_umi = 0;
+    // afq_set_aln_extra_bytes: every alignment word of a record is followed by a position of this many bytes (0: none).  Such a
+    // batch always takes the copy: k_strip_aln writes it without the positions (and with the widened fields)
+    uint32_t aln_extra = 0;
     std::vector<uint64_t> w_off;
     std::vector<uint32_t> w_nbytes;
     uint64_t wide_bytes = 0;
@@ -371,6 +374,7 @@ uint64_t p2_small_bytes(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_p
 // Split the batch into ranges of cells that fit the memory budget, build nothing yet.
 int plan_ranges(afq_ctx* c) {
     const uint32_t H = hdr_bytes(c->cfg);
+    const uint32_t astride = 4 + c->aln_extra;   // bytes per alignment in the caller's records
     size_t free_b = 0, total_b = 0;
     HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
     // buffers already held by this context are reusable
@@ -393,9 +397,10 @@ int plan_ranges(afq_ctx* c) {
             return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk header/size out of range");
         if (nrec == 0) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk with no reads");
         const uint64_t fixed = 8ull + (uint64_t)nrec * H;
-        if (fixed > nbytes || ((nbytes - fixed) & 3))
-            return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk nbytes does not match its records");
-        const uint64_t n_ref = (nbytes - fixed) / 4;
+        if (fixed > nbytes || ((nbytes - fixed) % astride))
+            return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk nbytes does not match its records" +
+                                                  (c->aln_extra ? " (alignments of " + std::to_string(astride) + " bytes)" : std::string()));
+        const uint64_t n_ref = (nbytes - fixed) / astride;
         // (EM resolutions: the canonical kernels' scratch is 40 B per ref and output space; the fixed-point EM sets aside ~25-30 B per ref
         //  behind the range's kernels and, when that plan falls short, the host sizes it exactly - up to three times as much: the larger of
         //  the two is what a range sized to fill the device must have room for)
@@ -410,7 +415,7 @@ int plan_ranges(afq_ctx* c) {
         total_need += nd;
     }
     // (also: parsimony over 4/8-byte fields whose chunks the caller placed at offsets that are not dword aligned - same copy, nothing widened)
-    c->widen = c->cfg.bc_split != 0 || !decode_par_supported(c->cfg.bc_bytes, c->cfg.umi_bytes) || (pug_res && !c->all_aligned);
+    c->widen = c->cfg.bc_split != 0 || !decode_par_supported(c->cfg.bc_bytes, c->cfg.umi_bytes) || (pug_res && !c->all_aligned) || c->aln_extra != 0;
     c->eff_bc = c->cfg.bc_split ? 8 : (c->cfg.bc_bytes < 4 ? 4 : c->cfg.bc_bytes);
     c->eff_umi = c->cfg.umi_bytes < 4 ? 4 : c->cfg.umi_bytes;
     if (c->widen) {
@@ -419,7 +424,10 @@ int plan_ranges(afq_ctx* c) {
         c->w_nbytes.resize(c->n_cells);
         uint64_t o = 0;
         for (uint32_t i = 0; i < c->n_cells; ++i) {
-            const uint64_t nb = (uint64_t)c->hdr[2 * i] + (uint64_t)c->hdr[2 * i + 1] * delta;
+            const uint64_t nbytes = c->hdr[2 * i], nrec = c->hdr[2 * i + 1];
+            // (positions: each alignment loses its aln_extra bytes - pass 1 checked that the alignments tile the chunk)
+            const uint64_t n_aln = c->aln_extra ? (nbytes - 8ull - nrec * H) / astride : 0;
+            const uint64_t nb = nbytes + nrec * delta - (uint64_t)c->aln_extra * n_aln;
             if (nb >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "cell " + std::to_string(i) + ": chunk over 4 GiB once its fields are widened");
             c->w_off[i] = o; c->w_nbytes[i] = (uint32_t)nb;
             o += nb;   // (a multiple of 4: 8 + nrec * (4 + 4|8 + 4|8) + 4 * refs)
@@ -792,8 +800,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         HIP_TRY(c, B.d_src_off.ensure(8ull * n));
         HIP_TRY(c, hipMemcpyAsync(B.d_src_off.p, c->chunk_off.data() + r.c0, 8ull * n, hipMemcpyHostToDevice, s));   // (c->chunk_off outlives the batch)
         tc.seg(K_DECODE);
-        launch_widen(s, c->d_bytes, c->n_bytes, B.d_src_off.as<uint64_t>(), B.d_meta.as<CellMeta>(), n, c->cfg.bc_bytes, c->cfg.umi_bytes,
-                     c->eff_bc, c->eff_umi, c->d_wide.as<uint8_t>(), B.d_status.as<DevStatus>(), c->cfg.bc_split);
+        if (c->aln_extra)
+            launch_strip_aln(s, c->d_bytes, c->n_bytes, B.d_src_off.as<uint64_t>(), B.d_meta.as<CellMeta>(), n, c->cfg.bc_bytes, c->cfg.umi_bytes,
+                             c->eff_bc, c->eff_umi, c->aln_extra, c->d_wide.as<uint8_t>(), B.d_status.as<DevStatus>());
+        else
+            launch_widen(s, c->d_bytes, c->n_bytes, B.d_src_off.as<uint64_t>(), B.d_meta.as<CellMeta>(), n, c->cfg.bc_bytes, c->cfg.umi_bytes,
+                         c->eff_bc, c->eff_umi, c->d_wide.as<uint8_t>(), B.d_status.as<DevStatus>(), c->cfg.bc_split);
     }
     DecodeArgs da{in_bytes, in_n, B.d_meta.as<CellMeta>(), n, c->d_t2g.as<uint32_t>(), c->ref_count,
                   g.num_genes, B.d_keys0.as<uint64_t>(), B.d_cell_nkeys.as<uint32_t>(),
@@ -1432,6 +1444,15 @@ int afq_device_warmup(int device) {
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return AFQ_ERR_NO_DEVICE; }
     if (hipFree(nullptr) != hipSuccess) return AFQ_ERR_NO_DEVICE;
     warm_code_object();
+    return 0;
+}
+
+int afq_set_aln_extra_bytes(afq_ctx* c, uint32_t e) {
+    if (e != 0 && !valid_width(e)) return fail(c, AFQ_ERR_INVALID_ARG, "aln_extra_bytes must be 0, 1, 2, 4 or 8 (the width of the position behind each alignment word)");
+    if (!c) return fail(nullptr, AFQ_ERR_INVALID_ARG, "null context");
+    if (e && c->cfg.bc_split) return fail(c, AFQ_ERR_UNSUPPORTED, "multi-barcode records (bc_split) with alignment positions are not supported");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "aln_extra_bytes changed while a batch is pending on this context");
+    c->aln_extra = e;
     return 0;
 }
 

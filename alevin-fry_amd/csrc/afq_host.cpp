@@ -657,7 +657,7 @@ struct DevStat { double busy_s = 0; uint64_t bytes = 0, cells = 0; uint32_t batc
 // One device's host thread: its contexts, then batches of cells popped off the shared queue until it is empty - what the
 // reference's workers do with chunks (quant.rs:1553-1575, 1678-1765); the rows of batch b go to parts[b], so the gather in
 // batch order is the gather in cell order whatever device took which batch.
-static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, const std::vector<uint32_t>& t2g, int device, bool bind_numa,
+static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, uint32_t aln_extra, const std::vector<uint32_t>& t2g, int device, bool bind_numa,
                              const uint8_t* rad, int rad_fd, const std::vector<uint64_t>& chunk_off, const std::vector<uint64_t>& chunk_nb,
                              const std::vector<uint32_t>& chunk_nr, const std::vector<std::pair<size_t, size_t>>& batches, std::atomic<size_t>& next,
                              std::atomic<int>& stop, bool want_eq, bool res_is_em, std::vector<DevOut>& parts, DevStat& stat) {
@@ -672,6 +672,11 @@ static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, c
         rc = afq_create(cfg_eq, t2g.data(), (uint32_t)t2g.size(), device, &raw);
         if (rc) { stat.rc = rc; stat.err = std::string("afq_create: ") + afq_last_error(nullptr); stop = 1; return; }
         ctx_eq.reset(raw);
+    }
+    for (afq_ctx* x : {ctx.get(), ctx_eq.get()}) {   // records with positions (the pos alignment tag)
+        if (!x || !aln_extra) continue;
+        rc = afq_set_aln_extra_bytes(x, aln_extra);
+        if (rc) { stat.rc = rc; stat.err = afq_last_error(x); stop = 1; return; }
     }
     const bool single = batches.size() == 1;
     for (;;) {
@@ -942,7 +947,24 @@ int afq_quantify(const afq_quant_opts* o) {
     // reported collate key work unchanged, and the host splits the 64-bit key back into sample index and cell barcode.
     // (Field order b0, b1, u inside a record = the order of the read-tag section; libradicl's MultiBarcodeReadRecord
     // writer is not under /root/reference: parity unpinned.)
+    // Which records: the order of the reference's get_record_type_from_prelude (src/utils.rs:313-377) - multi-barcode, then
+    // long-read (alignment tags as, start, end), records with positions (pos), scATAC (type, start_pos, frag_len), plain records.
+    // Records with positions carry `compressed_ori_refid:u32, pos` per alignment; quant runs them through the same do_quantify as
+    // plain records (quant.rs:1977-1990) and the library drops the positions on the device (afq_set_aln_extra_bytes).
+    auto has_aln_tag = [&](const char* name) { for (auto& t : P.aln_tags) if (t.name == name) return true; return false; };
     const bool multi_bc = P.file_tag_vals.count("num_barcodes") && P.file_tag_vals["num_barcodes"] > 1;
+    uint32_t aln_extra = 0;
+    if (multi_bc) {
+        if (has_aln_tag("pos")) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD records with alignment positions (alignment tag pos) are not supported");
+    } else if (has_aln_tag("as") && has_aln_tag("start") && has_aln_tag("end")) {
+        return hfail(AFQ_ERR_UNSUPPORTED, "long-read RAD records (alignment tags as, start, end) are not supported");
+    } else if (has_aln_tag("pos")) {
+        aln_extra = P.aln_tags.size() == 2 ? (uint32_t)int_type_bytes(P.aln_tags[1].type) : 0u;
+        if (P.aln_tags.size() != 2 || P.aln_tags[0].name != "compressed_ori_refid" || P.aln_tags[0].type != 3 || P.aln_tags[1].name != "pos" || !aln_extra)
+            return hfail(AFQ_ERR_UNSUPPORTED, "RAD records with positions: the alignment-level tags must be compressed_ori_refid:u32 followed by pos, an integer of 1, 2, 4 or 8 bytes");
+    } else if (has_aln_tag("type") && has_aln_tag("start_pos") && has_aln_tag("frag_len")) {
+        return hfail(AFQ_ERR_UNSUPPORTED, "To process atac-seq data, you should use the \"atac\" sub-command");   // quant.rs:1973-1976
+    }
     uint32_t w_sample = 0, cblen = 0, bc_split = 0;
     if (multi_bc) {
         if (P.file_tag_vals["num_barcodes"] != 2 || P.read_tags.size() != 3 || P.read_tags[0].name != "b0" || P.read_tags[1].name != "b1" || P.read_tags[2].name != "u")
@@ -964,8 +986,8 @@ int afq_quantify(const afq_quant_opts* o) {
         if (P.file_tag_vals.count("cblen")) cblen = (uint32_t)P.file_tag_vals["cblen"];
         else return hfail(AFQ_ERR_UNSUPPORTED, "no cblen file tag");
     }
-    if (P.aln_tags.size() != 1 || P.aln_tags[0].type != 3)
-        return hfail(AFQ_ERR_UNSUPPORTED, "RAD alignment-level tags other than one u32 (compressed_ori_refid) are not supported");
+    if (!aln_extra && (P.aln_tags.size() != 1 || P.aln_tags[0].type != 3))
+        return hfail(AFQ_ERR_UNSUPPORTED, "RAD alignment-level tags other than one u32 (compressed_ori_refid), alone or followed by pos, are not supported");
     std::vector<std::string> sample_names;   // multi-barcode: name of sample i (src/quant.rs:1354-1373)
     bool have_samples = false;
     if (file_exists(in + "/collation_manifest.bin")) {
@@ -974,7 +996,8 @@ int afq_quantify(const afq_quant_opts* o) {
             return hfail(AFQ_ERR_UNSUPPORTED, "collation_manifest.bin is not in the layout this build reads (bincode of CollationManifest; see afq_host.cpp)");
         have_samples = true;
     }
-    // chunk table: hop the nbytes headers (what the producer thread does)
+    // chunk table: hop the nbytes headers (what the producer thread does; a record is at least its header, whatever its
+    // alignments hold - the library checks that they tile the chunk)
     const uint32_t rec_hdr = 4 + P.bc_bytes + P.umi_bytes;
     std::vector<uint64_t> chunk_off, chunk_nb;
     std::vector<uint32_t> chunk_nr;
@@ -1111,7 +1134,7 @@ int afq_quantify(const afq_quant_opts* o) {
         std::atomic<size_t> next{0};
         std::atomic<int> stop{0};
         auto work = [&](size_t d) {
-            run_device_worker(cfg, cfg_eq.dump_eq ? &cfg_eq : nullptr, t2g, devices[d], devices.size() > 1, rad.data(), compressed ? -1 : mf.fd, chunk_off, chunk_nb, chunk_nr,
+            run_device_worker(cfg, cfg_eq.dump_eq ? &cfg_eq : nullptr, aln_extra, t2g, devices[d], devices.size() > 1, rad.data(), compressed ? -1 : mf.fd, chunk_off, chunk_nb, chunk_nr,
                               batches, next, stop, o->dump_eq != 0, res_is_em, parts, dstat[d]);
         };
         if (devices.size() == 1) work(0);

@@ -80,6 +80,10 @@ int launch_decode(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw);
 
 void launch_widen(hipStream_t s, const uint8_t* src, size_t n_src, const uint64_t* src_off, const CellMeta* meta, uint32_t n_cells,
                   uint32_t bw, uint32_t uw, uint32_t ebw, uint32_t euw, uint8_t* dst, DevStatus* st, uint32_t bsplit = 0);
+// records with an e-byte position behind every alignment word rewritten without them (and with k_widen's 4-byte fields);
+// meta: the stripped chunks
+void launch_strip_aln(hipStream_t s, const uint8_t* src, size_t n_src, const uint64_t* src_off, const CellMeta* meta, uint32_t n_cells,
+                      uint32_t bw, uint32_t uw, uint32_t ebw, uint32_t euw, uint32_t e, uint8_t* dst, DevStatus* st);
 bool decode_par_supported(uint32_t bw, uint32_t uw);
 int launch_decode_par(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw);
 void launch_fix_slabs(hipStream_t s, const ResolveArgs& a);

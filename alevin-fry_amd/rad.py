@@ -7,6 +7,9 @@ Wire format as witnessed in the reference (paths relative to /root/reference):
   widths  = by sequence length 1-4 / 5-8 / 9-16 / 17-32 nt                 src/convert.rs:323-344
   2-bit   = A0 C1 G2 T3, first base most significant                       src/convert.rs:75-90
 In a collated file one chunk holds all records of one corrected cell barcode.
+Records with positions (alignment tags compressed_ori_refid:u32, pos:<1|2|4|8 bytes>; KnownRecordType::RnaShortPos,
+src/utils.rs:313-377) hold `na x (u32, pos)`: the alignment tags of each alignment in prelude order.  `pos_bytes` below is
+the width of that pos tag (0 = plain records); the same cells written with pos_bytes=0 are the positions' plain twin.
 """
 from __future__ import annotations
 
@@ -39,37 +42,102 @@ def int_to_seq(v: int, n_nt: int) -> str:
     return "".join(_NT[(v >> (2 * (n_nt - 1 - i))) & 3] for i in range(n_nt))
 
 
-def encode_cells(cells, bc_bytes: int = 4, umi_bytes: int = 4, fw_bit: bool = True):
-    """cells: list of (bc, [(umi, [ref, ...]), ...]).  Returns (bytes, chunk_off[u64]).
+def default_positions(refs, within, pos_bytes: int):
+    """Positions for reads that come without any: a value per alignment (ref id, index in its read) that fills the field."""
+    r = np.asarray(refs, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        v = (r * np.uint64(0x9E3779B97F4A7C15) + np.asarray(within, dtype=np.uint64) * np.uint64(0xBF58476D1CE4E5B9)) >> np.uint64(7)
+    return v & np.uint64((1 << (8 * pos_bytes)) - 1 if pos_bytes < 8 else 0xFFFFFFFFFFFFFFFF)
 
-    Generic (any field width) pure-python encoder for small hand-written cases.
+
+def encode_cells(cells, bc_bytes: int = 4, umi_bytes: int = 4, fw_bit: bool = True, pos_bytes: int = 0):
+    """cells: list of (bc, [(umi, [ref, ...]) or (umi, [ref, ...], [pos, ...]), ...]).  Returns (bytes, chunk_off[u64]).
+
+    Generic (any field width) pure-python encoder for small hand-written cases.  pos_bytes > 0: records with positions (each
+    alignment word followed by its pos, default_positions when a read has none); pos_bytes = 0: the plain records (any
+    positions given are left out - the twin).
     """
     out = bytearray()
     offs = []
     for bc, reads in cells:
         offs.append(len(out))
         body = bytearray()
-        for umi, refs in reads:
+        for read in reads:
+            umi, refs = read[0], read[1]
             body += int(len(refs)).to_bytes(4, "little")
             body += int(bc).to_bytes(bc_bytes, "little")
             body += int(umi).to_bytes(umi_bytes, "little")
-            for r in refs:
+            if pos_bytes:
+                pos = read[2] if len(read) > 2 else default_positions(refs, np.arange(len(refs)), pos_bytes)
+            for j, r in enumerate(refs):
                 w = int(r) | (0x80000000 if fw_bit else 0)
                 body += w.to_bytes(4, "little")
+                if pos_bytes:
+                    body += int(pos[j]).to_bytes(pos_bytes, "little")
         out += (len(body) + 8).to_bytes(4, "little") + len(reads).to_bytes(4, "little") + body
     return bytes(out), np.asarray(offs, dtype=np.uint64)
 
 
-def encode_cells_np(cell_nrec, cell_bc, umi, na, refs, fw_bits=None):
-    """Vectorised encoder for the 10x-v3 layout (u32 barcode, u32 UMI).
+def _put_le(out, at, vals, width):
+    """out[at + k] = byte k of vals (little endian), k < width."""
+    v = np.asarray(vals, dtype=np.uint64)
+    for k in range(width):
+        out[at + k] = ((v >> np.uint64(8 * k)) & np.uint64(0xFF)).astype(np.uint8)
+
+
+def _encode_general_np(cell_nrec, cell_bc, umi, na, refs, fw_bits, bc_bytes, umi_bytes, pos_bytes, pos):
+    """encode_cells_np for any field widths and pos width: byte-level scatter."""
+    hdr = 4 + bc_bytes + umi_bytes
+    stride = 4 + pos_bytes
+    n_reads = len(na)
+    n_cells = len(cell_nrec)
+    cell_of_read = np.repeat(np.arange(n_cells), cell_nrec)
+    rec_len = hdr + stride * na
+    first_read = np.concatenate(([0], np.cumsum(cell_nrec)[:-1])).astype(np.int64)
+    ends = np.cumsum(rec_len)
+    starts = ends - rec_len
+    cell_body = np.zeros(n_cells, np.int64)
+    nz = cell_nrec > 0
+    if n_reads:
+        cell_body[nz] = np.add.reduceat(rec_len, first_read[nz])
+    chunk_nb = cell_body + 8
+    chunk_off = np.concatenate(([0], np.cumsum(chunk_nb)[:-1])).astype(np.int64)
+    # record offset: its chunk's body start + the bytes of the cell's records in front of it
+    cell_first_start = np.zeros(n_cells, np.int64)
+    if n_reads:
+        cell_first_start[nz] = starts[first_read[nz]]
+    rec_off = chunk_off[cell_of_read] + 8 + (starts - cell_first_start[cell_of_read])
+    out = np.zeros(int(chunk_nb.sum()), np.uint8)
+    _put_le(out, chunk_off, chunk_nb, 4)
+    _put_le(out, chunk_off + 4, cell_nrec, 4)
+    _put_le(out, rec_off, na, 4)
+    _put_le(out, rec_off + 4, np.asarray(cell_bc, dtype=np.uint64)[cell_of_read], bc_bytes)
+    _put_le(out, rec_off + 4 + bc_bytes, umi, umi_bytes)
+    read_of_ref = np.repeat(np.arange(n_reads), na)
+    ref_start = np.concatenate(([0], np.cumsum(na)[:-1])).astype(np.int64)
+    within = np.arange(len(refs)) - ref_start[read_of_ref]
+    at = rec_off[read_of_ref] + hdr + stride * within
+    rw = np.asarray(refs, dtype=np.uint64) & np.uint64(0x7FFFFFFF)
+    rw |= (np.uint64(1) if fw_bits is None else np.asarray(fw_bits, dtype=np.uint64)) << np.uint64(31)
+    _put_le(out, at, rw, 4)
+    if pos_bytes:
+        _put_le(out, at + 4, default_positions(refs, within, pos_bytes) if pos is None else pos, pos_bytes)
+    return out, chunk_off.astype(np.uint64)
+
+
+def encode_cells_np(cell_nrec, cell_bc, umi, na, refs, fw_bits=None, bc_bytes=4, umi_bytes=4, pos_bytes=0, pos=None):
+    """Vectorised encoder, by default for the 10x-v3 layout (u32 barcode, u32 UMI).
 
     cell_nrec[n_cells], cell_bc[n_cells]; per read umi[], na[]; refs[] = concatenated,
-    sorted-ascending ref ids.  Returns (uint8 array, chunk_off[u64]).
+    sorted-ascending ref ids.  Returns (uint8 array, chunk_off[u64]).  Other barcode / UMI widths and records with
+    positions (pos_bytes > 0; pos[] per alignment, default_positions when None) take a byte-level path.
     """
     cell_nrec = np.asarray(cell_nrec, dtype=np.int64)
     na = np.asarray(na, dtype=np.int64)
     n_reads = int(cell_nrec.sum())
     assert n_reads == len(na) == len(umi)
+    if (bc_bytes, umi_bytes, pos_bytes) != (4, 4, 0):
+        return _encode_general_np(cell_nrec, cell_bc, umi, na, refs, fw_bits, bc_bytes, umi_bytes, pos_bytes, pos)
     n_cells = len(cell_nrec)
     cell_of_read = np.repeat(np.arange(n_cells), cell_nrec)
     rec_words = 3 + na
@@ -101,23 +169,26 @@ def encode_cells_np(cell_nrec, cell_bc, umi, na, refs, fw_bits=None):
     return w.view(np.uint8), (chunk_word_off * 4).astype(np.uint64)
 
 
-def decode_chunk(buf: bytes, off: int, bc_bytes: int, umi_bytes: int):
-    """Returns (bc, [(umi, [ref...])...]) for the chunk starting at off."""
+def decode_chunk(buf: bytes, off: int, bc_bytes: int, umi_bytes: int, pos_bytes: int = 0, with_pos: bool = False):
+    """Returns (bc, [(umi, [ref...])...]) for the chunk starting at off; pos_bytes: records with positions of that width
+    (with_pos: reads are (umi, [ref...], [pos...]))."""
     nbytes = int.from_bytes(buf[off : off + 4], "little")
     nrec = int.from_bytes(buf[off + 4 : off + 8], "little")
     p = off + 8
     reads = []
     bc0 = None
+    st = 4 + pos_bytes
     for _ in range(nrec):
         na = int.from_bytes(buf[p : p + 4], "little")
         bc = int.from_bytes(buf[p + 4 : p + 4 + bc_bytes], "little")
         umi = int.from_bytes(buf[p + 4 + bc_bytes : p + 4 + bc_bytes + umi_bytes], "little")
         p += 4 + bc_bytes + umi_bytes
-        refs = [int.from_bytes(buf[p + 4 * j : p + 4 * j + 4], "little") & 0x7FFFFFFF for j in range(na)]
-        p += 4 * na
+        refs = [int.from_bytes(buf[p + st * j : p + st * j + 4], "little") & 0x7FFFFFFF for j in range(na)]
+        pos = [int.from_bytes(buf[p + st * j + 4 : p + st * j + st], "little") for j in range(na)]
+        p += st * na
         if bc0 is None:
             bc0 = bc
-        reads.append((umi, refs))
+        reads.append((umi, refs, pos) if with_pos else (umi, refs))
     assert p == off + nbytes, "chunk nbytes does not match its records"
     return bc0, reads
 
@@ -143,9 +214,10 @@ def chunk_offsets(buf, start: int = 0):
 _INT_TYPE_ID = {1: 1, 2: 2, 4: 3, 8: 4}  # bytes -> RadType id (U8..U64)
 
 
-def rad_prelude(ref_names, num_chunks, cblen, ulen, bc_bytes=4, umi_bytes=4, is_paired=False) -> bytes:
+def rad_prelude(ref_names, num_chunks, cblen, ulen, bc_bytes=4, umi_bytes=4, is_paired=False, pos_bytes=0) -> bytes:
     """Header + the three tag sections + file-tag values of a single-barcode scRNA RAD file
-    (order of writes in src/convert.rs:254-369)."""
+    (order of writes in src/convert.rs:254-369).  pos_bytes > 0: records with positions - a second alignment tag `pos`,
+    an integer of that width."""
     out = bytearray()
     out += bytes([1 if is_paired else 0])
     out += len(ref_names).to_bytes(8, "little")
@@ -160,7 +232,10 @@ def rad_prelude(ref_names, num_chunks, cblen, ulen, bc_bytes=4, umi_bytes=4, is_
 
     out += (2).to_bytes(2, "little") + tag("cblen", 2) + tag("ulen", 2)  # file tags (u16, u16)
     out += (2).to_bytes(2, "little") + tag("b", _INT_TYPE_ID[bc_bytes]) + tag("u", _INT_TYPE_ID[umi_bytes])  # read tags
-    out += (1).to_bytes(2, "little") + tag("compressed_ori_refid", 3)  # alignment tags
+    if pos_bytes:
+        out += (2).to_bytes(2, "little") + tag("compressed_ori_refid", 3) + tag("pos", _INT_TYPE_ID[pos_bytes])  # alignment tags
+    else:
+        out += (1).to_bytes(2, "little") + tag("compressed_ori_refid", 3)  # alignment tags
     out += int(cblen).to_bytes(2, "little") + int(ulen).to_bytes(2, "little")  # file tag values
     return bytes(out)
 
@@ -317,15 +392,16 @@ def snappy_frame_encode(data: bytes, chunk: int = 60000, compress_literal: bool 
 
 
 def write_quant_input_dir(path, chunk_bytes, n_chunks, ref_names, t2g_rows, cblen=16, ulen=12, bc_bytes=4, umi_bytes=4,
-                          compressed=False, prelude=None):
+                          compressed=False, prelude=None, pos_bytes=0):
     """Lay out what `alevin-fry quant -i` expects: generate_permit_list.json, collate.json,
-    map.collated.rad[.sz], plus the tg-map next to it.  t2g_rows: list of tab-separated row tuples."""
+    map.collated.rad[.sz], plus the tg-map next to it.  t2g_rows: list of tab-separated row tuples.
+    pos_bytes: the chunks hold records with positions of that width (the prelude says so)."""
     import json
     import os
 
     os.makedirs(path, exist_ok=True)
     if prelude is None:
-        prelude = rad_prelude(ref_names, n_chunks, cblen, ulen, bc_bytes, umi_bytes)
+        prelude = rad_prelude(ref_names, n_chunks, cblen, ulen, bc_bytes, umi_bytes, pos_bytes=pos_bytes)
     with open(os.path.join(path, "generate_permit_list.json"), "w") as f:
         json.dump({"velo_mode": False, "expected_ori": "fw"}, f)
     with open(os.path.join(path, "collate.json"), "w") as f:

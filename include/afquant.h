@@ -38,7 +38,8 @@ extern "C" {
  *     any size, pair lists of any length.  Only when they have to hand it to the one-workgroup kernel (a UMI partition over 256
  *     reads: UMIs that share their low bases, e.g. a constant primer tail; gene-level labels or an 8-byte UMI field send every
  *     cell there) that kernel's 2^20-read limit applies;
- *   - parsimony: a component over 4096 vertices under a --large-graph-thresh raised beyond that. */
+ *   - parsimony: a component over 4096 vertices under a --large-graph-thresh raised beyond that;
+ *   - multi-barcode records (bc_split) that carry alignment positions (afq_set_aln_extra_bytes). */
 #define AFQ_ERR_HIP (-4)          /* a HIP runtime call failed                   */
 #define AFQ_ERR_NO_DEVICE (-5)    /* no usable gfx950 device                     */
 #define AFQ_ERR_STATE (-6)        /* call sequence error (collect before submit) */
@@ -170,6 +171,17 @@ int afq_submit_reader(afq_ctx* ctx, afq_read_fn read, void* user, size_t n_bytes
  */
 int afq_submit_device(afq_ctx* ctx, const void* d_bytes, size_t n_bytes, const uint64_t* chunk_off,
                       uint32_t n_cells, uint64_t first_cell_index);
+
+/*
+ * Records that carry a position per alignment (KnownRecordType::RnaShortPos, src/utils.rs:313-377: alignment tags
+ * compressed_ori_refid:u32 then pos of `e` bytes).  A record is then `na:u32, bc, umi, na x {u32(ori<<31|ref), pos}` and the
+ * reference quantifies it exactly as a plain record (src/quant.rs:1977-1990, BasicEqClassPayload): positions never reach a
+ * count.  The batch is rewritten on the device without them before the decode.  e = 1, 2, 4 or 8; 0 = plain records (the
+ * default).  Applies to every later submit of the context (all three forms) until changed.  Returns AFQ_ERR_INVALID_ARG for
+ * any other width, AFQ_ERR_UNSUPPORTED for a nonzero e on a context whose config has bc_split set (multi-barcode records with
+ * positions), AFQ_ERR_STATE while a batch is pending.
+ */
+int afq_set_aln_extra_bytes(afq_ctx* ctx, uint32_t e);
 
 /* Waits for the submitted batch and returns its rows (src/quant.rs:1131-1179, 1266-1268). */
 int afq_collect(afq_ctx* ctx, afq_result* out);
