@@ -439,6 +439,15 @@ class Quantifier:
         self.lib.afq_em_resize_count.argtypes = [C.c_void_p]
         return int(self.lib.afq_em_resize_count(self._h))
 
+    def em_instance_counts(self) -> list:
+        """Cells of the last collected batch per rounds instance of the order-free EM (tiers 0-4), then the tier 4 cells that ran
+        with 32-bit state ids (afq_em_instance_counts)."""
+        out = (C.c_uint64 * 6)()
+        self.lib.afq_em_instance_counts.restype = None
+        self.lib.afq_em_instance_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self.lib.afq_em_instance_counts(self._h, out)
+        return [int(x) for x in out]
+
     def batch_stats(self) -> dict:
         s = AfqBatchStats()
         self._check(self.lib.afq_get_batch_stats(self._h, C.byref(s)))

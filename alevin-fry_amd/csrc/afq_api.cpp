@@ -150,6 +150,7 @@ struct RangeState {
         d_bt_cmean, d_bt_cvar, d_em2_off, d_em2_scratch, d_em2_tiers, d_arena;
     PinnedVec<uint8_t> h_arena;   // the range's small uploads, gathered (RangeInit)
     PinnedVec<uint32_t> h_pack;   // what the host reads when the range is done: k_pack_small writes it from the device
+    PinnedVec<uint32_t> h_em2_tiers;   // the EM's eight counter words (afq_em2.hip k_em2_setup), copied back ahead of the range's wait
     ResolveArgs last_ra{};
     std::vector<CellMeta> meta;
     Range cur{};
@@ -231,6 +232,7 @@ struct afq_ctx {
     uint64_t n_mono_cells = 0;     // parsimony cells resolved by the one-workgroup kernel (sent there directly, or handed back by the phase kernels)
     uint64_t n_divert = 0;         // buckets the hash resolve of the last batch handed to the sort path
     uint64_t n_em_resized = 0;     // ranges whose EM scratch was sized on the host after the device-side plan did not fit
+    uint64_t n_em_inst[6] = {0};   // cells of the last batch per rounds instance of the order-free EM (tiers 0-4), then tier 4 cells with 32-bit ids
     bool handback_seen = false;    // the phase kernels have handed a cell back to the one-workgroup kernel in some range of this context
     uint32_t retry_cuts = 0;       // how many times the range being finished has been cut around a failing cell (finish_range)
     uint32_t retry_halvings = 0, retry_halving_cap = 0;   // ... halved after a range-wide failure, and how often it may be (finish_range)
@@ -982,6 +984,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     return 0;
 }
 
+// The order-free EM's counter words of a finished range (launch_em2): cells per rounds instance (tiers 0-4), tier 4 cells
+// with 32-bit state ids (word 5).
+void add_em_instance_counts(afq_ctx* c, const uint32_t* tiers) {
+    for (int t = 0; t < 6; ++t) c->n_em_inst[t] += tiers[t];
+}
+
 // Wait for the range in flight, compact its rows and append them to the host result.
 int finish_range(afq_ctx* c, int slot) {
     RangeState& B = c->rs[slot];
@@ -990,6 +998,10 @@ int finish_range(afq_ctx* c, int slot) {
     HostClock hc;
     const uint32_t n = B.cur.c1 - B.cur.c0;
     hipStream_t s = B.stream;
+    if (B.em_inline) {   // the EM's instance counters (afq_em_instance_counts): behind the range's kernels, read after the wait below
+        HIP_TRY(c, B.h_em2_tiers.reserve(8));
+        HIP_TRY(c, hipMemcpyAsync(B.h_em2_tiers.p, B.d_em2_tiers.p, 32, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(c, hipStreamSynchronize(s));
     hc.lap("finish: wait for kernels");
     DevStatus st{};
@@ -1110,6 +1122,7 @@ int finish_range(afq_ctx* c, int slot) {
         if (!short_of_scratch) {
             em2 = true;
             std::memcpy(nnz.data(), pk + 2ull * n, 4ull * n);
+            add_em_instance_counts(c, B.h_em2_tiers.p);
         } else c->n_em_resized += 1;
     }
     if (em && !em2) {
@@ -1151,8 +1164,11 @@ int finish_range(afq_ctx* c, int slot) {
             ScopedTimer t(c, K_EM, s, &B.launches);
             launch_em2(s, B.last_ra, n, B.d_em2_off.as<uint64_t>(), B.d_em2_scratch.as<uint32_t>(), B.d_em_nnz.as<uint32_t>(), B.d_em_order.as<uint32_t>(),
                        B.d_em2_tiers.as<uint32_t>(), na_em, c->cfg.em_init_uniform);
+            HIP_TRY(c, B.h_em2_tiers.reserve(8));
+            HIP_TRY(c, hipMemcpyAsync(B.h_em2_tiers.p, B.d_em2_tiers.p, 32, hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(c, hipStreamSynchronize(s));
+        if (em2) add_em_instance_counts(c, B.h_em2_tiers.p);
         HIP_TRY(c, hipMemcpy(nnz.data(), B.d_em_nnz.p, 4ull * n, hipMemcpyDeviceToHost));
         if (c->cfg.dump_eq || c->cfg.num_bootstraps) {
             // the cells' gene-level classes, read back off the EM set-up (k_eqc_dump): size, prefix on the host, fill
@@ -1393,6 +1409,7 @@ int begin_batch(afq_ctx* c, uint32_t n_cells, uint64_t first_cell_index) {
     if (c->cfg.num_bootstraps) { c->res->bm_ptr.push_back(0); c->res->bv_ptr.push_back(0); }
     c->stats = afq_batch_stats{};
     c->n_divert = 0;
+    for (uint64_t& x : c->n_em_inst) x = 0;
     c->stats.input_bytes = c->n_bytes;
     for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
     c->h2d_piped = false;
@@ -1461,6 +1478,10 @@ uint64_t afq_pool_regrow_count(const afq_ctx* ctx) { return ctx ? ctx->n_pool_re
 uint64_t afq_em_resize_count(const afq_ctx* ctx) { return ctx ? ctx->n_em_resized : 0; }
 uint64_t afq_mono_cell_count(const afq_ctx* ctx) { return ctx ? ctx->n_mono_cells : 0; }
 uint64_t afq_resolve_divert_count(const afq_ctx* ctx) { return ctx ? ctx->n_divert : 0; }
+void afq_em_instance_counts(const afq_ctx* ctx, uint64_t out[6]) {
+    if (!out) return;
+    for (int t = 0; t < 6; ++t) out[t] = ctx ? ctx->n_em_inst[t] : 0;
+}
 
 int afq_device_pci_bus_id(int device, char* out, size_t out_len) {
     if (!out || out_len < 13) return AFQ_ERR_INVALID_ARG;
@@ -1528,6 +1549,7 @@ void afq_destroy(afq_ctx* c) {
     for (auto& rs : c->rs) {
         if (rs.stream) (void)hipStreamSynchronize(rs.stream);
         for (DevBuf* b : rs.all()) b->release();
+        rs.h_em2_tiers.release();
         if (rs.kernels_done) (void)hipEventDestroy(rs.kernels_done);
         if (rs.stream) (void)hipStreamDestroy(rs.stream);
     }

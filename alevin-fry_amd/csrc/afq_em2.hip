@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kSetupNT) void k_em2_setup(const CellMeta* __restri
                                                         const uint32_t* __restrict__ lab, const uint32_t* __restrict__ lab_cnt,
                                                         const uint64_t* __restrict__ em_off, uint32_t* __restrict__ scratch,
                                                         uint32_t* __restrict__ out_nnz, const uint32_t* __restrict__ em_order,
-                                                        uint32_t* __restrict__ tiers /* [8] counters, then 5 lists of n_cells */, uint32_t n_cells,
+                                                        uint32_t* __restrict__ tiers /* [8] counters (cells per tier 0-4, tier 4 with 32-bit ids, -, plan overflow), then 5 lists of n_cells */, uint32_t n_cells,
                                                         Em2Cfg cfg) {
     extern __shared__ uint32_t s_bm[];   // bits[nwb], rank[nwb]
     __shared__ uint32_t s_ws[kSetupNT / 64];
@@ -406,6 +406,7 @@ __global__ __launch_bounds__(kSetupNT) void k_em2_setup(const CellMeta* __restri
         sc.hdr[H_TIER] = tier; sc.hdr[H_NHOT] = H; sc.hdr[H_NARROW] = narrow4 ? 1u : 0u;
         const uint32_t at = atomicAdd(&tiers[tier], 1u);
         tiers[8 + (size_t)tier * n_cells + at] = cell;
+        if (tier == 4 && !narrow4) atomicAdd(&tiers[5], 1u);   // (afq_em_instance_counts: tier 4 cells on the 32-bit route)
     }
 }
 

@@ -312,6 +312,11 @@ uint64_t afq_mono_cell_count(const afq_ctx* ctx);
  * parked keys).  Batches that the table never serves (prefer-ambig, trivial, cr-like-em of many-gene reads) are sorted without
  * a hash pass and count 0.  Results identical; diagnostics only. */
 uint64_t afq_resolve_divert_count(const afq_ctx* ctx);
+/* EM resolutions: cells of the last collected batch per instance of the order-free EM's rounds kernel (afq_em2.hip):
+ * out[0..2] everything in LDS at 256 / 512 / 1024 threads, out[3] class lists streamed, out[4] the hot entries in LDS and the
+ * rest in global memory; out[5] those of out[4] that ran with 32-bit state ids.  Cells without an ambiguous molecule, and
+ * batches under AFQ_EM_ORDER=canonical (the sequential kernels of afq_em.hip), count nowhere.  Diagnostics only. */
+void afq_em_instance_counts(const afq_ctx* ctx, uint64_t out[6]);
 
 /* Brings the HIP runtime up on `device` (first-call initialisation) - a host can call it from a side thread while it parses its
    inputs.  Returns 0 or AFQ_ERR_NO_DEVICE. */
