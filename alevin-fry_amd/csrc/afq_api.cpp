@@ -147,7 +147,7 @@ struct RangeState {
         d_lab_cnt, d_em_off, d_em_scratch, d_em_nnz, d_pug_cells, d_rd_off, d_rd_h, d_rd_u, d_rd_o, d_pug_scr_off,
         d_pug_scratch, d_epool, d_epool_cur, d_alt, d_hist_cells, d_fix, d_em_hdr, d_em_order, d_eq_ncls, d_eq_nw, d_eq_cptr,
         d_p2_small, d_eq_wptr, d_eq_len, d_eq_cnt, d_eq_lab, d_bt_off, d_bt_scratch, d_bt_ns, d_bt_col, d_bt_mean, d_bt_var, d_bt_sptr, d_bt_ccol,
-        d_bt_cmean, d_bt_cvar, d_em2_off, d_em2_scratch, d_em2_tiers, d_arena;
+        d_bt_cmean, d_bt_cvar, d_em2_off, d_em2_scratch, d_em2_tiers, d_arena, d_dtile, d_spill;
     PinnedVec<uint8_t> h_arena;   // the range's small uploads, gathered (RangeInit)
     PinnedVec<uint32_t> h_pack;   // what the host reads when the range is done: k_pack_small writes it from the device
     PinnedVec<uint32_t> h_em2_tiers;   // the EM's eight counter words (afq_em2.hip k_em2_setup), copied back ahead of the range's wait
@@ -171,7 +171,7 @@ struct RangeState {
                 &d_cell_bc, &d_div, &d_lab, &d_lab_cnt, &d_em_off, &d_em_scratch, &d_em_nnz, &d_pug_cells, &d_rd_off, &d_rd_h,
                 &d_rd_u, &d_rd_o, &d_pug_scr_off, &d_pug_scratch, &d_epool, &d_epool_cur, &d_p2_small, &d_alt, &d_hist_cells, &d_fix, &d_em_hdr, &d_em_order,
                 &d_eq_ncls, &d_eq_nw, &d_eq_cptr, &d_eq_wptr, &d_eq_len, &d_eq_cnt, &d_eq_lab, &d_bt_off, &d_bt_scratch, &d_bt_ns, &d_bt_col,
-                &d_bt_mean, &d_bt_var, &d_bt_sptr, &d_bt_ccol, &d_bt_cmean, &d_bt_cvar, &d_em2_off, &d_em2_scratch, &d_em2_tiers, &d_arena};
+                &d_bt_mean, &d_bt_var, &d_bt_sptr, &d_bt_ccol, &d_bt_cmean, &d_bt_cvar, &d_em2_off, &d_em2_scratch, &d_em2_tiers, &d_arena, &d_dtile, &d_spill};
     }
 };
 
@@ -556,6 +556,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     uint64_t n_pug_reads = 0, pug_words = 0;  // pug_words: scratch of the largest parsimony cell
     const bool par = (c->widen || c->all_aligned) && decode_par_supported(g.bc_bytes, g.umi_bytes);
     uint64_t key_off = 0, n_buckets = 0, n_tiles = 0, n_slabs = 0, k1_slots = 0;
+    uint64_t n_dtiles_lo = 0, n_dtiles_hi = 0;   // the scattering decoder's tiles, per instance (k_slab_setup writes the table)
     uint32_t max_lg_nb = 0;
     uint32_t slab_cap = slab_capacity();
     {   // reads of many genes each (the range averages two or more alignment words per record): all keys of a UMI share a bucket, so
@@ -597,7 +598,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         max_lg_nb = std::max(max_lg_nb, lg);
         m.bucket_base = (uint32_t)n_buckets;
         n_buckets += 1ull << lg;
-        m.slab_cap = 0; m.k1_off = 0; m.tile_base = 0;
+        m.slab_cap = 0; m.k1_off = 0; m.tile_base = 0; m.dtile_base = 0; m.pad = 0;
         if (lg) {
             m.slab_cap = slab_cap;
             m.k1_off = k1_slots;
@@ -613,8 +614,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         }
         nrec_total += m.nrec;
         if (par) {
+            const uint64_t ns = ((uint64_t)(m.nbytes >> 2) + kSlabWords - 1) / kSlabWords;
             slab_prefix.push_back((uint32_t)n_slabs);
-            n_slabs += ((uint64_t)(m.nbytes >> 2) + kSlabWords - 1) / kSlabWords;
+            n_slabs += ns;
+            uint64_t& nt = decode_tile_hi(lg) ? n_dtiles_hi : n_dtiles_lo;
+            m.dtile_base = (uint32_t)nt;
+            nt += (ns + kDecodeTileSlabsHost - 1) / kDecodeTileSlabsHost;
         }
     }
     if (n_slabs >= 0xFFFFFFF0ull) return fail(c, AFQ_ERR_UNSUPPORTED, "batch too large for 32-bit slab ids");
@@ -624,6 +629,8 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     if (n_buckets >= 0xFFFFFFF0ull || n_tiles >= 0xFFFFFFF0ull || key_off >= (1ull << 40))
         return fail(c, AFQ_ERR_UNSUPPORTED, "batch too large for 32-bit bucket/tile ids");
     const uint32_t n_multi = (uint32_t)multi.size();
+    // lane-per-record decode of a batch without parsimony cells: the decoder places the keys in their bucket slabs itself (no k_scatter)
+    const bool scat_decode = par && pug_cells.empty() && decode_short_records(key_off - n, nrec_total);
 
     HIP_TRY(c, B.d_meta.ensure(sizeof(CellMeta) * n));
     HIP_TRY(c, B.d_keys0.ensure(8 * key_off));
@@ -713,6 +720,10 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         HIP_TRY(c, B.d_slab_cell.ensure(4ull * std::max<uint64_t>(n_slabs, 1)));
         HIP_TRY(c, B.d_cell_bc.ensure(8ull * n));
     }
+    if (scat_decode) {
+        HIP_TRY(c, B.d_dtile.ensure(8ull * std::max<uint64_t>(n_dtiles_lo + n_dtiles_hi, 1)));
+        HIP_TRY(c, B.d_spill.ensure(4ull * n));
+    }
 
     hc.lap("run: plan + ensure buffers");
     hipStream_t s = B.stream;
@@ -728,6 +739,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     }
     init.zero(B.d_bucket_cnt.p, 4 * n_buckets);
     init.zero(B.d_slab_ovf.p, 4ull * n);
+    if (scat_decode) init.zero(B.d_spill.p, 4ull * n);
     init.zero(B.d_nnz.p, 4ull * n);
     init.zero(B.d_ncols.p, 4ull * n);
     if (em) init.zero(B.d_lab_cnt.p, 8ull * n);
@@ -818,6 +830,11 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
                   n_pug ? PugOut{B.d_rd_h.as<uint64_t>(), B.d_rd_u.as<uint64_t>(), B.d_rd_o.as<uint32_t>(), B.d_rd_off.as<uint64_t>(), label_salt(hash_try), label_mask(hash_try)}
                         : PugOut{nullptr, nullptr, nullptr, nullptr, 0, ~0ull},
                   g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u, decode_short_records(key_off - n, nrec_total), par ? B.d_fix.as<uint32_t>() : nullptr};
+    if (scat_decode) {
+        da.dtile = B.d_dtile.as<uint2>(); da.n_dtiles_lo = (uint32_t)n_dtiles_lo; da.n_dtiles_hi = (uint32_t)n_dtiles_hi;
+        da.keys1 = B.d_keys1.as<uint64_t>(); da.cursor = B.d_bucket_cnt.as<uint32_t>(); da.slab_ovf = B.d_slab_ovf.as<uint32_t>();
+        da.spill = B.d_spill.as<uint32_t>();
+    }
     if (par) {
         tc.seg(K_DECODE_PAR);
         if (launch_decode_par(s, da, g.bc_bytes, g.umi_bytes)) { tc.end(); return fail(c, AFQ_ERR_INVALID_ARG, "bad field widths"); }
@@ -835,9 +852,9 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
                    (uint32_t)hist_cells.size(), g.usa_mode, g.num_rows,
                    (g.usa_mode && g.sa_model == AFQ_SA_PREFER_AMBIG) ? 1u : 0u, max_lg_nb, B.d_slab_ovf.as<uint32_t>(),
                    resolve_sort_only(key_off - n, nrec_total), g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u,
-                   test_hook_is("RESOLVE_DIVERT", "all") ? 1u : 0u};
+                   test_hook_is("RESOLVE_DIVERT", "all") ? 1u : 0u, scat_decode ? 1u : 0u, scat_decode ? B.d_spill.as<uint32_t>() : nullptr};
     if (n_multi) {
-        tc.seg(K_SCATTER); launch_scatter(s, ra);
+        if (!scat_decode) { tc.seg(K_SCATTER); launch_scatter(s, ra); }
         tc.seg(K_FIX_SLABS); launch_fix_slabs(s, ra);
     }
     tc.seg(K_RESOLVE); launch_resolve(s, ra);

@@ -46,6 +46,8 @@ struct CellMeta {
     uint32_t slab_cap;     // multi-bucket cells placed without a counting pass: every bucket owns slab_cap slots of keys1 (0: single-bucket cell)
     uint32_t tile_base;    // multi-bucket cells: the cell's first scatter tile (k_fill_tables writes the range's tile table from it)
     uint64_t k1_off;       // ... starting here (the cell's region holds max(nb * slab_cap, n_ref + 1) slots)
+    uint32_t dtile_base;   // the cell's first tile of the scattering decoder, counted inside its instance's share of the table
+    uint32_t pad;
 };
 
 // device-side error / statistics block

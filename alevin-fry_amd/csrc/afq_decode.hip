@@ -16,6 +16,7 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "afq_common.h"
 #include "afq_hooks.h"
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
                                                uint32_t num_genes, uint64_t* __restrict__ keys0,
                                                uint32_t* __restrict__ cell_nkeys,
                                                uint64_t* __restrict__ bc_out, DevStatus* st,
-                                               const CellChk* __restrict__ chk, PugOut pug) {
+                                               const CellChk* __restrict__ chk, PugOut pug, uint32_t* __restrict__ slab_ovf) {
     constexpr uint32_t HDR = 4 + BW + UW;
     constexpr bool AL = (BW % 4 == 0) && (UW % 4 == 0);
     const uint32_t lane = lane_id();
@@ -65,6 +66,9 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
     // the chunk header; cells that pass add their key count to the batch total, one atomic per workgroup), and its waves then
     // re-decode the cells that failed it (normally none) right here.  (Until round 6 the proof's last step was a kernel of its own,
     // k_verify_cells, with a list in global memory between the two: one 5 us launch and one boundary more per range.)
+    // slab_ovf (after the scattering decoder, which leaves keys0 without the keys of multi-bucket cells): a multi-bucket cell that
+    // failed the proof is flagged 2 - its slabs and cursors hold keys that are not the cell's, and k_fix_slabs counts and places
+    // it afresh from the keys0 this re-decode writes.
     __shared__ unsigned long long s_sum;
     __shared__ uint32_t s_nfail;
     __shared__ uint32_t s_fail[256];
@@ -89,6 +93,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
   for (uint32_t work = chk ? (threadIdx.x >> 6) : blockIdx.x * 4 + (threadIdx.x >> 6); work < n_work; work += chk ? 4u : gridDim.x * 4) {
     const uint32_t cell = chk ? s_fail[work] : work;
     const CellMeta m = meta[cell];
+    if (slab_ovf && m.lg_nb && lane == 0) slab_ovf[cell] = 2u;
     const uint64_t abase = m.chunk_off & ~3ull;         // dword-aligned base of the walk
     const uint32_t mis = (uint32_t)(m.chunk_off - abase);
     uint64_t pos = (uint64_t)mis + 8;                    // next record start, bytes from abase
@@ -453,17 +458,26 @@ void launch_strip_aln(hipStream_t s, const uint8_t* src, size_t n_src, const uin
 
 // ---------------------------------------------------------------------------
 // k_slab_setup: per cell, record which cell every 1 KiB slab belongs to and the
-// cell's barcode words, so the decode waves start with one dependent load, not five.
+// cell's barcode words, so the decode waves start with one dependent load, not five.  For the scattering decoder (dtile != null)
+// it also writes the cell's tiles - runs of kDecodeTileSlabsHost slabs that never cross a cell - into the share of the tile
+// table of the instance the cell's bucket count picks (the kLdsBins instance's share starts at n_lo).
 template <int BW, int UW>
 __global__ __launch_bounds__(256) void k_slab_setup(const uint8_t* __restrict__ bytes,
                                                    const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                    const uint32_t* __restrict__ slab_prefix,
-                                                   uint32_t* __restrict__ slab_cell, uint64_t* __restrict__ cell_bc) {
+                                                   uint32_t* __restrict__ slab_cell, uint64_t* __restrict__ cell_bc,
+                                                   uint2* __restrict__ dtile, uint32_t n_lo) {
     constexpr uint32_t BWW = BW / 4, UWW = UW / 4, HW = 1 + BWW + UWW;
     const uint32_t cell = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (cell >= n_cells) return;
     const uint32_t a = slab_prefix[cell], b = slab_prefix[cell + 1];
-    for (uint32_t s = a + lane_id(); s < b; s += 64) slab_cell[s] = cell;
+    if (!dtile) for (uint32_t s = a + lane_id(); s < b; s += 64) slab_cell[s] = cell;   // (the scattering decoder reads its tiles instead)
+    if (dtile) {
+        const CellMeta dm = meta[cell];
+        const uint32_t nt = (b - a + kDecodeTileSlabsHost - 1) / kDecodeTileSlabsHost;
+        uint2* out = dtile + dm.dtile_base + (decode_tile_hi(dm.lg_nb) ? n_lo : 0u);
+        for (uint32_t t = lane_id(); t < nt; t += 64) out[t] = make_uint2(cell, t);
+    }
     if (lane_id() == 0) {
         const CellMeta m = meta[cell];
         const uint32_t* W = reinterpret_cast<const uint32_t*>(bytes + m.chunk_off);
@@ -1166,9 +1180,119 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
 // per-lane loop that exists once in the code.  Same proof terms as the other two decoders.
 // PUG: the batch has parsimony cells; for those a record is not turned into keys but into one read
 // (label key, UMI, record offset) for k_pug_cell - same rule as k_decode_par<.., true>.
+//
+// BINS != 0: the scattering instance (non-parsimony batches).  A workgroup takes one tile of the device-built table - up to
+// 4 * kDtileSlabs consecutive slabs of ONE cell, kDtileSlabs per wave - and each wave decodes its slabs as above.  Keys of a
+// multi-bucket cell are not reserved in keys0: a wave appends them to the workgroup's LDS stage (an LDS atomic), and after one
+// barrier the tile goes through k_scatter's tail - LDS ranks per bucket, one scan, one cursor atomic per non-empty bucket,
+// a bucket-major write into the cell's fixed slabs of keys1 (slab_ovf on overflow).  Keys beyond the stage, and the keys of
+// cells of more than BINS buckets, take one cursor atomic each.  cell_nkeys and the proof sums are added once per tile.
+// Single-bucket cells keep writing keys0 (the sort path reads them there).  A cell whose proof fails or whose slabs overflow
+// is decoded again into keys0 by the fix-up decode and placed exactly by k_fix_slabs.
+struct DecodeScatter {
+    const uint2* tile;   // tile -> (cell, tile index inside the cell)
+    uint32_t n_tiles;
+    uint64_t* keys1;
+    uint32_t* cursor;
+    uint32_t* slab_ovf;
+    uint32_t* spill;     // per cell: keys that found their bucket's slab full, kept at the front of the cell's keys0 region
+};
+struct NoScatter {};
+// A key whose bucket slab is full goes to the front of its cell's keys0 region (unused by multi-bucket cells on this route), and
+// the cell is flagged: k_fix_slabs gathers the slabs' keys behind these and places the cell exactly.  (More than n_ref of them:
+// the cell's proof fails, and the fix-up decode rewrites keys0.)
+__device__ __forceinline__ void spill_key(const DecodeScatter& so, uint64_t* __restrict__ keys0, const CellMeta& m, uint32_t cell, uint64_t key) {
+    const uint32_t q = atomicAdd(&so.spill[cell], 1u);
+    if (q < m.n_ref) keys0[m.key_off + q] = key;
+    atomicOr(&so.slab_ovf[cell], 1u);
+}
+constexpr uint32_t kDtileSlabs = AFQ_DTILE_SLABS;
+constexpr uint32_t kDtileKeys = AFQ_DTILE_KEYS;
+static_assert(kDtileKeys % 256 == 0 && kDtileKeys < 65536, "the tail keeps kDtileKeys / 256 keys per thread; ranks take 16 bits");
+#ifndef AFQ_DTILE_RUN
+#define AFQ_DTILE_RUN 16
+#endif
+constexpr uint32_t kDtileRun = AFQ_DTILE_RUN;   // consecutive tiles one XCD takes (a cell's bucket runs merge in one L2), as k_scatter
+
+// The scattering instance's end of a tile: the proof sums and the key count of the cell, then k_scatter's tail over the staged keys.
+template <uint32_t BINS>
+__device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, uint64_t* s_keys, uint32_t* s_cnt, uint32_t* s_base,
+                                             uint32_t* s_misc, uint32_t* __restrict__ cell_nkeys, CellChk* __restrict__ chk,
+                                             const DecodeScatter& so, uint64_t* __restrict__ keys0) {
+    __syncthreads();   // every wave's keys and sums are in LDS
+    const uint32_t n_all = s_misc[0], nst = min(n_all, s_misc[1]);
+    if (threadIdx.x == 0) {
+        if (s_misc[2]) atomicAdd(&chk[cell].count, s_misc[2]);
+        if (s_misc[3]) atomicAdd(&chk[cell].words, s_misc[3]);
+        if (s_misc[4]) atomicOr(&chk[cell].fail, 1u);
+        if (n_all) atomicAdd(&cell_nkeys[cell], n_all);   // (single-bucket cells counted theirs as they reserved keys0)
+    }
+    if (m.lg_nb == 0) return;
+    const uint32_t cap = m.slab_cap, nb = 1u << m.lg_nb;
+    uint64_t* dst = so.keys1 + m.k1_off;
+    uint32_t* gcur = so.cursor + m.bucket_base;
+    if (nb > BINS) {   // giant cell: per-key cursor atomics
+        for (uint32_t i = threadIdx.x; i < nst; i += 256) {
+            const uint64_t key = s_keys[i];
+            const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
+            const uint32_t pos = atomicAdd(&gcur[b], 1u);
+            if (pos < cap) dst[(uint64_t)b * cap + pos] = key;
+            else spill_key(so, keys0, m, cell, key);
+        }
+        return;
+    }
+    constexpr uint32_t E = kDtileKeys / 256;
+    uint64_t key[E];
+    uint32_t rank[E];   // bucket << 16 | rank of the key among the tile's keys of that bucket
+#pragma unroll
+    for (uint32_t e = 0; e < E; ++e) {
+        const uint32_t i = e * 256 + threadIdx.x;
+        key[e] = kKeySentinel;
+        rank[e] = 0;
+        if (i < nst) {
+            key[e] = s_keys[i];
+            const uint32_t b = bucket_of(key[e] >> kGeneBits, m.lg_nb);
+            rank[e] = (b << 16) | atomicAdd(&s_cnt[b], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += 256) {   // tile-local offsets + one reservation per non-empty bucket
+        const uint32_t b = base + threadIdx.x;
+        const uint32_t c = b < nb ? s_cnt[b] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan<256>(c, s_misc + 8, tot);
+        if (b < nb) {
+            s_cnt[b] = carry + ex;
+            const uint32_t at = c ? atomicAdd(&gcur[b], c) : 0u;
+            s_base[b] = at;
+        }
+        carry += tot;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t e = 0; e < E; ++e) {
+        const uint32_t i = e * 256 + threadIdx.x;
+        if (i < nst) s_keys[s_cnt[rank[e] >> 16] + (rank[e] & 0xFFFFu)] = key[e];
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nst; i += 256) {   // bucket-major: a bucket's run is contiguous in its slab
+        const uint64_t kx = s_keys[i];
+        const uint32_t b = bucket_of(kx >> kGeneBits, m.lg_nb);
+        const uint32_t pos = s_base[b] + (i - s_cnt[b]);
+        if (pos < cap) dst[(uint64_t)b * cap + pos] = kx;
+        else spill_key(so, keys0, m, cell, kx);
+    }
+}
+
 constexpr uint32_t kInl = 3;
-template <int BW, int UW, bool TRIVIAL, bool PUG>
-__global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restrict__ bytes,
+// waves per SIMD the instance's LDS allows (160 KiB per CU, a workgroup's four waves on four SIMDs), at most eight
+constexpr uint32_t decode_recs_occupancy(uint32_t bins) {
+    const uint32_t lds = 4 * (4 * kStage + 4 * kSlabWords) + (bins ? 8 * kDtileKeys + 8 * bins : 16) + 64;
+    return 163840 / lds < 8 ? 163840 / lds : 8;
+}
+template <int BW, int UW, bool TRIVIAL, bool PUG, uint32_t BINS = 0>
+__global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_recs(const uint8_t* __restrict__ bytes,
                                                     const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                     const uint32_t* __restrict__ slab_prefix,
                                                     const uint32_t* __restrict__ slab_cell,
@@ -1177,27 +1301,49 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
                                                     uint32_t num_genes, uint64_t* __restrict__ keys0,
                                                     uint32_t* __restrict__ cell_nkeys,
                                                     uint64_t* __restrict__ bc_out, CellChk* __restrict__ chk,
-                                                    [[maybe_unused]] PugOut pug) {
+                                                    [[maybe_unused]] PugOut pug,
+                                                    [[maybe_unused]] typename std::conditional<BINS != 0, DecodeScatter, NoScatter>::type so) {
     static_assert(BW % 4 == 0 && UW % 4 == 0, "aligned layouts only");
     static_assert(!(TRIVIAL && PUG), "trivial and parsimony are different resolutions");
+    static_assert(!(BINS && PUG), "parsimony cells emit reads, not keys");
+    constexpr bool SC = BINS != 0;
     constexpr uint32_t BWW = BW / 4, UWW = UW / 4, HW = 1 + BWW + UWW;
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     __shared__ uint32_t s_stage[4][kStage];
     __shared__ uint32_t s_list[4][kSlabWords];
+    // scattering instance: the tile's keys, per-bucket counts / offsets, and [0] keys reserved, [1] end of the staged prefix,
+    // [2..4] proof sums (count, words, fail), [8..11] the scan's wave totals
+    __shared__ uint64_t s_keys[SC ? kDtileKeys : 1];
+    __shared__ uint32_t s_cnt[SC ? BINS : 1];
+    __shared__ uint32_t s_base[SC ? BINS : 1];
+    __shared__ uint32_t s_misc[12];
     const uint32_t lane = lane_id();
     const uint32_t wv = threadIdx.x >> 6;
     uint32_t* stage = s_stage[wv];
     uint32_t* list = s_list[wv];
-    const uint32_t n_groups = (n_slabs + kSlabsPerWave - 1) / kSlabsPerWave;
-    const uint32_t n_cols = min(n_groups, kDecodeCols);
-    const uint32_t n_rows = (n_groups + n_cols - 1) / n_cols;
-    const uint32_t wid = blockIdx.x * 4 + wv;
-    const uint32_t grp = (wid % n_cols) * n_rows + wid / n_cols;
-    if (wid >= n_cols * n_rows || grp >= n_groups) return;
-    const uint32_t slab_a = grp * kSlabsPerWave;
-    const uint32_t slab_b = min(n_slabs, slab_a + kSlabsPerWave);
-    uint32_t my_cell = 0;
-    if (lane < slab_b - slab_a) my_cell = slab_cell[slab_a + lane];
+    uint32_t slab_a, slab_b, my_cell = 0;
+    if constexpr (SC) {
+        const uint32_t xr = blockIdx.x / 8, tile = ((xr / kDtileRun) * 8 + blockIdx.x % 8) * kDtileRun + xr % kDtileRun;
+        if (tile >= so.n_tiles) return;   // (the whole workgroup)
+        const uint2 td = so.tile[tile];
+        my_cell = td.x;
+        const uint32_t c1 = slab_prefix[my_cell + 1];
+        slab_a = min(c1, slab_prefix[my_cell] + td.y * (4 * kDtileSlabs) + wv * kDtileSlabs);
+        slab_b = min(c1, slab_a + kDtileSlabs);
+        for (uint32_t b = threadIdx.x; b < BINS; b += 256) s_cnt[b] = 0;
+        if (threadIdx.x < 5) s_misc[threadIdx.x] = threadIdx.x == 1 ? kDtileKeys : 0u;
+        __syncthreads();
+    } else {
+        const uint32_t n_groups = (n_slabs + kSlabsPerWave - 1) / kSlabsPerWave;
+        const uint32_t n_cols = min(n_groups, kDecodeCols);
+        const uint32_t n_rows = (n_groups + n_cols - 1) / n_cols;
+        const uint32_t wid = blockIdx.x * 4 + wv;
+        const uint32_t grp = (wid % n_cols) * n_rows + wid / n_cols;
+        if (wid >= n_cols * n_rows || grp >= n_groups) return;
+        slab_a = grp * kSlabsPerWave;
+        slab_b = min(n_slabs, slab_a + kSlabsPerWave);
+        if (lane < slab_b - slab_a) my_cell = slab_cell[slab_a + lane];
+    }
 
     uint32_t cur_cell = kNone;
     CellMeta m{};
@@ -1223,9 +1369,15 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
         for (int d = 32; d > 0; d >>= 1) ws += __shfl_xor(ws, d);
         const bool any_fail = __any(fail);
         if (lane == 0) {
-            if (acc_count) atomicAdd(&chk[cur_cell].count, acc_count);
-            if (ws) atomicAdd(&chk[cur_cell].words, ws);
-            if (any_fail) atomicOr(&chk[cur_cell].fail, 1u);
+            if (SC) {   // (the tile's sums go out once, after its barrier)
+                if (acc_count) atomicAdd(&s_misc[2], acc_count);
+                if (ws) atomicAdd(&s_misc[3], ws);
+                if (any_fail) atomicOr(&s_misc[4], 1u);
+            } else {
+                if (acc_count) atomicAdd(&chk[cur_cell].count, acc_count);
+                if (ws) atomicAdd(&chk[cur_cell].words, ws);
+                if (any_fail) atomicOr(&chk[cur_cell].fail, 1u);
+            }
         }
         acc_count = 0; acc_words = 0; fail = false;
     };
@@ -1243,7 +1395,7 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
     };
 
     load_cell(__builtin_amdgcn_readlane(my_cell, 0));
-    issue_slab_loads((slab_a - sp0) * kSlabWords);
+    if (!SC || slab_a < slab_b) issue_slab_loads((slab_a - sp0) * kSlabWords);
 
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
         const uint32_t s0 = (slab - sp0) * kSlabWords;
@@ -1411,22 +1563,38 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
                 tot += stot;
             }
             if (tot) {
+                const bool staged = SC && m.lg_nb != 0;   // (wave-uniform) the scattering instance's multi-bucket cell
                 uint32_t wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&cell_nkeys[cur_cell], tot);
+                if (lane == 0) wbase = staged ? atomicAdd(&s_misc[0], tot) : atomicAdd(&cell_nkeys[cur_cell], tot);
                 wbase = __builtin_amdgcn_readfirstlane(wbase);
-                if (wbase + tot > m.n_ref) fail = true;
+                // staged: keys that do not fit the stage go to their buckets one cursor atomic each (the staged keys are the prefix
+                // [0, s_misc[1]) - every wave after the first that did not fit finds the stage full as well)
+                const bool direct = staged && wbase + tot > kDtileKeys;
+                if (direct && lane == 0) atomicMin(&s_misc[1], wbase);
+                auto put = [&](uint32_t at, uint64_t key) {
+                    if constexpr (SC) {
+                        if (!staged) keys0[m.key_off + wbase + at] = key;
+                        else if (!direct) s_keys[wbase + at] = key;
+                        else {
+                            const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
+                            const uint32_t pos = atomicAdd(&so.cursor[m.bucket_base + b], 1u);
+                            if (pos < m.slab_cap) so.keys1[m.k1_off + (uint64_t)b * m.slab_cap + pos] = key;
+                            else spill_key(so, keys0, m, cur_cell, key);
+                        }
+                    } else keys0[m.key_off + wbase + at] = key;
+                };
+                if (!staged && wbase + tot > m.n_ref) fail = true;
                 else {
-                    uint64_t* dst = keys0 + m.key_off + wbase;
                     uint32_t o = 0;
 #pragma unroll
                     for (uint32_t j = 0; j < kInl; ++j) {
                         const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
-                        if (v[j]) dst[o + before] = (umi << kGeneBits) | g[j];
+                        if (v[j]) put(o + before, (umi << kGeneBits) | g[j]);
                         o += (uint32_t)__popcll(bal[j]);
                     }
                     if (any_slow && slowrec && scnt) {
                         uint32_t w = sex;
-                        for_each_first_gene([&](uint32_t gj) { dst[w++] = (umi << kGeneBits) | gj; });
+                        for_each_first_gene([&](uint32_t gj) { put(w++, (umi << kGeneBits) | gj); });
                     }
                 }
             }
@@ -1441,6 +1609,7 @@ __global__ __launch_bounds__(256, 8) void k_decode_recs(const uint8_t* __restric
         }
     }
     flush_chk();
+    if constexpr (SC) scatter_tail<BINS>(m, my_cell, s_keys, s_cnt, s_base, s_misc, cell_nkeys, chk, so, keys0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1532,7 +1701,7 @@ template <int BW, int UW>
 static void launch_decode_t(hipStream_t s, const DecodeArgs& a) {
     const uint32_t grid = a.chk ? (a.n_cells + 255) / 256 : (a.n_cells + 3) / 4;   // (fix-up mode: a workgroup verifies 256 cells' proofs and re-decodes the ones that failed)
     AFQ_LAUNCH((k_decode<BW, UW>), grid, 256, s, a.bytes, a.n_bytes, a.meta, a.n_cells, a.t2g,
-               a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, a.st, a.chk, a.pug);
+               a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, a.st, a.chk, a.pug, a.chk ? a.slab_ovf : nullptr);
 }
 
 int launch_decode(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw) {
@@ -1550,28 +1719,40 @@ int launch_decode(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw) 
 // the serial scan of rounds 2-4.  Label-tail workload (configs1_tail, 9.66 GB), the table against the scan: 14.54 -> 9.01 ms per
 // step, the step 35.0 -> 29.4 ms (profiles/history/run_r04ah.sh).
 template <int BW, int UW>
-static void launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
+static int launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
+    // lane-per-record decode of a batch without parsimony cells is always the scattering instance (run_range passes slab_ovf for it)
+    const bool scat = a.slab_ovf && !a.pug.h && a.short_records;
     AFQ_LAUNCH((k_slab_setup<BW, UW>), (a.n_cells + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix,
-               a.slab_cell, a.cell_bc);
+               a.slab_cell, a.cell_bc, scat ? a.dtile : nullptr, a.n_dtiles_lo);
     const uint32_t n_groups = (a.n_slabs + kSlabsPerWave - 1) / kSlabsPerWave;
     const uint32_t n_cols = n_groups < kDecodeCols ? n_groups : kDecodeCols;
     const uint32_t n_waves = n_cols * ((n_groups + n_cols - 1) / n_cols);
-    if (a.pug.h && a.short_records && !a.trivial)  // the batch has PUG cells: instances that also emit (label key, umi, offset) per read
+    if (scat) {   // a tile per workgroup; the grid is a multiple of 8 * kDtileRun (the XCD dealing)
+        const DecodeScatter lo{a.dtile, a.n_dtiles_lo, a.keys1, a.cursor, a.slab_ovf, a.spill};
+        const DecodeScatter hi{a.dtile + a.n_dtiles_lo, a.n_dtiles_hi, a.keys1, a.cursor, a.slab_ovf, a.spill};
+        const uint32_t glo = (a.n_dtiles_lo + 8 * kDtileRun - 1) / (8 * kDtileRun) * (8 * kDtileRun);
+        const uint32_t ghi = (a.n_dtiles_hi + 8 * kDtileRun - 1) / (8 * kDtileRun) * (8 * kDtileRun);
+        if (a.trivial) {
+            if (glo) AFQ_LAUNCH((k_decode_recs<BW, UW, true, false, kDecodeSplitBins>), glo, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, lo);
+            if (ghi) AFQ_LAUNCH((k_decode_recs<BW, UW, true, false, kLdsBins>), ghi, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, hi);
+        } else {
+            if (glo) AFQ_LAUNCH((k_decode_recs<BW, UW, false, false, kDecodeSplitBins>), glo, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, lo);
+            if (ghi) AFQ_LAUNCH((k_decode_recs<BW, UW, false, false, kLdsBins>), ghi, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, hi);
+        }
+    } else if (a.pug.h && a.short_records && !a.trivial)  // the batch has PUG cells: instances that also emit (label key, umi, offset) per read
         AFQ_LAUNCH((k_decode_recs<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk), a.pug);
+                   const_cast<CellChk*>(a.chk), a.pug, NoScatter{});
     else if (a.pug.h)
         AFQ_LAUNCH((k_decode_par<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
                    const_cast<CellChk*>(a.chk), a.pug);
-    else if (a.short_records && a.trivial)
-        AFQ_LAUNCH((k_decode_recs<BW, UW, true, false>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk), a.pug);
     else if (a.short_records)
-        AFQ_LAUNCH((k_decode_recs<BW, UW, false, false>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk), a.pug);
+        return -1;   // (unreachable: such a batch takes the scattering instance above)
     else if (a.trivial)
         AFQ_LAUNCH((k_decode_keys<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
@@ -1580,16 +1761,17 @@ static void launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
         AFQ_LAUNCH((k_decode_keys<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
                    a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
                    const_cast<CellChk*>(a.chk));
+    return 0;
 }
 
 bool decode_par_supported(uint32_t bw, uint32_t uw) { return (bw == 4 || bw == 8) && (uw == 4 || uw == 8); }
 
 int launch_decode_par(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw) {
     if (!a.n_slabs) return 0;
-    if (bw == 4 && uw == 4) { launch_decode_par_t<4, 4>(s, a); return 0; }
-    if (bw == 4 && uw == 8) { launch_decode_par_t<4, 8>(s, a); return 0; }
-    if (bw == 8 && uw == 4) { launch_decode_par_t<8, 4>(s, a); return 0; }
-    if (bw == 8 && uw == 8) { launch_decode_par_t<8, 8>(s, a); return 0; }
+    if (bw == 4 && uw == 4) return launch_decode_par_t<4, 4>(s, a);
+    if (bw == 4 && uw == 8) return launch_decode_par_t<4, 8>(s, a);
+    if (bw == 8 && uw == 4) return launch_decode_par_t<8, 4>(s, a);
+    if (bw == 8 && uw == 8) return launch_decode_par_t<8, 8>(s, a);
     return -1;
 }
 

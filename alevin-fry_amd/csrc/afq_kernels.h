@@ -6,6 +6,14 @@
 
 #include "afq_common.h"
 
+// the scattering decoder's tile: slabs per wave (four waves a tile) and the keys its LDS stage holds (measurement builds override them)
+#ifndef AFQ_DTILE_SLABS
+#define AFQ_DTILE_SLABS 4
+#endif
+#ifndef AFQ_DTILE_KEYS
+#define AFQ_DTILE_KEYS 1536
+#endif
+
 namespace afq {
 
 struct DecodeArgs {
@@ -30,7 +38,21 @@ struct DecodeArgs {
     uint32_t trivial;             // the batch has cells in `trivial` mode
     uint32_t short_records;       // the batch averages < 2 alignment words per record: lane-per-record decode
     uint32_t* fix_list;           // [n_cells] cells whose walk-free proof failed (filled by k_verify_cells)
+    // the scattering decoder (k_decode_recs with a bin count): a non-null slab_ovf selects it.  It places the keys of multi-bucket
+    // cells straight into their bucket slabs (keys1, cursor) - keys0 then holds single-bucket cells' keys and the keys that found
+    // their slab full - and the fix-up decode re-decodes every cell whose proof failed into keys0 for k_fix_slabs
+    uint2* dtile;                 // [n_dtiles] device-filled (k_slab_setup): tile -> (cell, tile index inside the cell)
+    uint32_t n_dtiles_lo;         // tiles of the 512-bin instance (cells of <= 512 or > kLdsBins buckets) ...
+    uint32_t n_dtiles_hi;         // ... then those of the kLdsBins instance (512 < buckets <= kLdsBins)
+    uint64_t* keys1;
+    uint32_t* cursor;
+    uint32_t* slab_ovf;
+    uint32_t* spill;              // [n_cells] keys that found their slab full (kept at the front of the cell's keys0 region)
 };
+constexpr uint32_t kDecodeTileSlabsHost = 4 * AFQ_DTILE_SLABS;   // 1 KiB slabs per scattering-decoder tile (4 waves)
+constexpr uint32_t kLdsBins = 2048;          // buckets per cell the LDS paths (k_scatter, the scattering decoder) can hold
+constexpr uint32_t kDecodeSplitBins = 512;   // cells of more buckets than this (and at most kLdsBins) take the kLdsBins instance
+__host__ __device__ inline bool decode_tile_hi(uint32_t lg_nb) { return (1u << lg_nb) > kDecodeSplitBins && (1u << lg_nb) <= kLdsBins; }
 
 struct ResolveArgs {
     const CellMeta* meta;
@@ -61,6 +83,9 @@ struct ResolveArgs {
     uint32_t sort_only;          // reads of the range average two or more alignments: buckets are resolved by sorting, not through the UMI table
     uint32_t trivial;            // the batch resolves `trivial`: its buckets (but those of tiny cells) are the sort path's
     uint32_t divert_all;         // tests (AFQ_TEST_RESOLVE_DIVERT=all): every bucket through the divert list to the sort path
+    uint32_t fix_recount;        // the scattering decoder placed the keys: k_fix_slabs gathers an overflowed cell's keys into keys0
+                                 // (flag 1) or counts a re-decoded one's buckets afresh (flag 2) before placing it
+    const uint32_t* spill;       // ... with the spilled keys' count per cell (DecodeArgs::spill)
 };
 
 // one launch that clears / fills a range's small buffers (k_range_init): dst <- zeros (src_off == ~0) or arena[src_off ...)

@@ -29,7 +29,6 @@ constexpr uint32_t kTileKeys = kScatterTileHost;  // 2048
 #define AFQ_SCATTER_RUN 16
 #endif
 constexpr uint32_t kScatterRun = AFQ_SCATTER_RUN;   // consecutive tiles one XCD takes (k_scatter)
-constexpr uint32_t kLdsBins = 2048;               // buckets per cell the LDS paths can hold
 
 // ---------------------------------------------------------------------------
 // keys0 -> keys1 grouped by bucket: LDS multisplit of a kTileKeys tile.  Ranks
@@ -136,22 +135,52 @@ __global__ __launch_bounds__(256) void k_scatter(const uint2* __restrict__ tile_
 // Cells whose fixed slabs overflowed (normally none): the cursors hold every bucket's true count, so the exact layout is
 // one scan away - buckets back to back from the start of the cell's keys1 region, keys placed one atomic each out of
 // keys0 (still intact).  Afterwards cursor[b] = end offset of bucket b.
+// recount (after the scattering decoder, which writes no keys0 for multi-bucket cells): a cell flagged 1 overflowed - keys0 holds
+// the spill[cell] keys that found their slab full, the slabs the first slab_cap keys of every bucket; those are gathered behind
+// the spill (a ballot and one LDS atomic per wave and 64 slots), and the cursors' counts stay right.  A cell flagged 2 failed its
+// proof and was decoded again into keys0 (the fix-up k_decode): its cursors are counted afresh from there.
 __global__ __launch_bounds__(256) void k_fix_slabs(const uint32_t* __restrict__ multi_cells, uint32_t n_multi,
                                                   const CellMeta* __restrict__ meta, const uint32_t* __restrict__ cell_nkeys,
-                                                  const uint64_t* __restrict__ keys0, uint64_t* __restrict__ keys1,
-                                                  uint32_t* __restrict__ cursor, const uint32_t* __restrict__ slab_ovf) {
+                                                  uint64_t* __restrict__ keys0, uint64_t* __restrict__ keys1,
+                                                  uint32_t* __restrict__ cursor, const uint32_t* __restrict__ slab_ovf, uint32_t recount,
+                                                  const uint32_t* __restrict__ spill) {
     __shared__ uint32_t s_ws[4];
+    __shared__ uint32_t s_at;
     for (uint32_t ci = blockIdx.x; ci < n_multi; ci += gridDim.x) {
         const uint32_t cell = multi_cells[ci];
-        if (!slab_ovf[cell]) continue;
+        const uint32_t flag = slab_ovf[cell];
+        if (!flag) continue;
         const CellMeta m = meta[cell];
         if (mode_is_pug(m.mode)) continue;
         const uint32_t nb = 1u << m.lg_nb, nk = cell_nkeys[cell];
         uint32_t* gcur = cursor + m.bucket_base;
+        if (recount && flag >= 2) {
+            for (uint32_t b = threadIdx.x; b < nb; b += 256) gcur[b] = 0;
+            __threadfence();
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < nk; i += 256) atomicAdd(&gcur[bucket_of(keys0[m.key_off + i] >> kGeneBits, m.lg_nb)], 1u);
+            __threadfence();
+            __syncthreads();
+        } else if (recount) {
+            if (threadIdx.x == 0) s_at = spill[cell];
+            __syncthreads();
+            const uint32_t cap = m.slab_cap, slots = nb * cap, lane = lane_id();
+            for (uint32_t s0 = (threadIdx.x & ~63u); s0 < slots; s0 += 256) {   // (whole waves: the ballot's leader is lane 0)
+                const uint32_t sl = s0 + lane, b = min(sl / cap, nb - 1u);
+                const bool v = sl < slots && sl - b * cap < gcur[b];
+                const uint64_t mk = __ballot(v);
+                uint32_t at = 0;
+                if (lane == 0 && mk) at = atomicAdd(&s_at, (uint32_t)__popcll(mk));
+                at = __shfl(at, 0);
+                if (v) keys0[m.key_off + at + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = keys1[m.k1_off + sl];
+            }
+            __threadfence();
+            __syncthreads();
+        }
         uint32_t carry = 0;
         for (uint32_t base = 0; base < nb; base += 256) {
             const uint32_t b = base + threadIdx.x;
-            const uint32_t c = b < nb ? gcur[b] : 0u;
+            const uint32_t c = b < nb ? __hip_atomic_load(&gcur[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
             uint32_t tot;
             const uint32_t ex = block_excl_scan<256>(c, s_ws, tot);
             if (b < nb) gcur[b] = carry + ex;
@@ -1277,7 +1306,7 @@ void launch_scatter(hipStream_t s, const ResolveArgs& a) {
 void launch_fix_slabs(hipStream_t s, const ResolveArgs& a) {
     if (!a.n_multi) return;
     const uint32_t grid = a.n_multi < 512u ? a.n_multi : 512u;
-    AFQ_LAUNCH(k_fix_slabs, grid, 256, s, a.multi_cells, a.n_multi, a.meta, a.cell_nkeys, a.keys0, a.keys1, a.cursor, a.slab_ovf);
+    AFQ_LAUNCH(k_fix_slabs, grid, 256, s, a.multi_cells, a.n_multi, a.meta, a.cell_nkeys, a.keys0, a.keys1, a.cursor, a.slab_ovf, a.fix_recount, a.spill);
 }
 
 static ResolveCfg make_rc(const ResolveArgs& a) {
