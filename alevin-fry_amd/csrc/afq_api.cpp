@@ -373,6 +373,9 @@ P2Small p2_small_layout(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_p
 }
 uint64_t p2_small_bytes(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_pug) { return 4 * p2_small_layout(n, parts, tiles, n_pug).words + 64; }
 
+#ifndef AFQ_TAPER_CR
+#define AFQ_TAPER_CR 0.419, 0.671, 0.822, 0.913, 0.967, 1.0, 1.0, 1.0   // (measurement builds override the cr-like taper: eight cumulative shares)
+#endif
 // Split the batch into ranges of cells that fit the memory budget, build nothing yet.
 int plan_ranges(afq_ctx* c) {
     const uint32_t H = hdr_bytes(c->cfg);
@@ -447,7 +450,7 @@ int plan_ranges(afq_ctx* c) {
     // (late round 4, cr-like: a range's rows take about half as long to cross PCIe as its kernels run - more for ranges of small
     //  cells, whose rows are longer per read - so every range is 0.6 of the one before it: six ranges, the last 3.3 % of the work;
     //  28/28/22/14/8 % left 0.65 ms of the last range's rows in the open.  12.96-13.26 -> 12.48-12.68 ms, profiles/history/run_r04ad.sh)
-    static const double kTaperCr[] = {0.419, 0.671, 0.822, 0.913, 0.967, 1.0, 1.0, 1.0}, kTaperPug[] = {0.40, 0.76, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
+    static const double kTaperCr[] = {AFQ_TAPER_CR}, kTaperPug[] = {0.40, 0.76, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
     const double* kTaper = pug_res ? kTaperPug : kTaperCr;
     const size_t kTaperN = 8;
     if (pug_fixed > 0.5 * mem_budget) return fail(c, AFQ_ERR_OOM, "the largest parsimony cell's scratch does not fit device memory");

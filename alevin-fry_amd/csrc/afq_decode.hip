@@ -1215,6 +1215,12 @@ static_assert(kDtileKeys % 256 == 0 && kDtileKeys < 65536, "the tail keeps kDtil
 constexpr uint32_t kDtileRun = AFQ_DTILE_RUN;   // consecutive tiles one XCD takes (a cell's bucket runs merge in one L2), as k_scatter
 
 // The scattering instance's end of a tile: the proof sums and the key count of the cell, then k_scatter's tail over the staged keys.
+// The per-bucket words are 16 bits each (s_cnt, s_base: two buckets a word), which is what lets the six-workgroups-per-CU instance
+// hold 1024 buckets in the LDS that held 512 of 32-bit words (and the kLdsBins instance run five workgroups per CU, not four): a
+// tile has fewer than 2^16 keys, so its counts and tile-local offsets fit, and a bucket's position in its slab is kept exactly
+// below kBase16Max and as kBase16Max from there on - beyond any slab capacity this path takes (a cell with larger slabs goes the
+// per-key way), so a key at such a position is seen to be past its slab all the same.
+constexpr uint32_t kBase16Max = 0xFFFFu - kDtileKeys;
 template <uint32_t BINS>
 __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, uint64_t* s_keys, uint32_t* s_cnt, uint32_t* s_base,
                                              uint32_t* s_misc, uint32_t* __restrict__ cell_nkeys, CellChk* __restrict__ chk,
@@ -1231,7 +1237,9 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
     const uint32_t cap = m.slab_cap, nb = 1u << m.lg_nb;
     uint64_t* dst = so.keys1 + m.k1_off;
     uint32_t* gcur = so.cursor + m.bucket_base;
-    if (nb > BINS) {   // giant cell: per-key cursor atomics
+    uint16_t* c16 = reinterpret_cast<uint16_t*>(s_cnt);
+    uint16_t* b16 = reinterpret_cast<uint16_t*>(s_base);
+    if (nb > BINS || cap > kBase16Max) {   // giant cell (or slabs beyond the 16-bit positions): per-key cursor atomics
         for (uint32_t i = threadIdx.x; i < nst; i += 256) {
             const uint64_t key = s_keys[i];
             const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
@@ -1251,21 +1259,21 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
         rank[e] = 0;
         if (i < nst) {
             key[e] = s_keys[i];
-            const uint32_t b = bucket_of(key[e] >> kGeneBits, m.lg_nb);
-            rank[e] = (b << 16) | atomicAdd(&s_cnt[b], 1u);
+            const uint32_t b = bucket_of(key[e] >> kGeneBits, m.lg_nb), sh = (b & 1u) << 4;
+            rank[e] = (b << 16) | ((atomicAdd(&s_cnt[b >> 1], 1u << sh) >> sh) & 0xFFFFu);   // (a half never carries into its neighbour: < 2^16 keys a tile)
         }
     }
     __syncthreads();
     uint32_t carry = 0;
     for (uint32_t base = 0; base < nb; base += 256) {   // tile-local offsets + one reservation per non-empty bucket
         const uint32_t b = base + threadIdx.x;
-        const uint32_t c = b < nb ? s_cnt[b] : 0u;
+        const uint32_t c = b < nb ? c16[b] : 0u;
         uint32_t tot;
         const uint32_t ex = block_excl_scan<256>(c, s_misc + 8, tot);
         if (b < nb) {
-            s_cnt[b] = carry + ex;
+            c16[b] = (uint16_t)(carry + ex);
             const uint32_t at = c ? atomicAdd(&gcur[b], c) : 0u;
-            s_base[b] = at;
+            b16[b] = (uint16_t)min(at, kBase16Max);
         }
         carry += tot;
     }
@@ -1273,13 +1281,13 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
 #pragma unroll
     for (uint32_t e = 0; e < E; ++e) {
         const uint32_t i = e * 256 + threadIdx.x;
-        if (i < nst) s_keys[s_cnt[rank[e] >> 16] + (rank[e] & 0xFFFFu)] = key[e];
+        if (i < nst) s_keys[c16[rank[e] >> 16] + (rank[e] & 0xFFFFu)] = key[e];
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < nst; i += 256) {   // bucket-major: a bucket's run is contiguous in its slab
         const uint64_t kx = s_keys[i];
         const uint32_t b = bucket_of(kx >> kGeneBits, m.lg_nb);
-        const uint32_t pos = s_base[b] + (i - s_cnt[b]);
+        const uint32_t pos = (uint32_t)b16[b] + (i - c16[b]);
         if (pos < cap) dst[(uint64_t)b * cap + pos] = kx;
         else spill_key(so, keys0, m, cell, kx);
     }
@@ -1288,7 +1296,7 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
 constexpr uint32_t kInl = 3;
 // waves per SIMD the instance's LDS allows (160 KiB per CU, a workgroup's four waves on four SIMDs), at most eight
 constexpr uint32_t decode_recs_occupancy(uint32_t bins) {
-    const uint32_t lds = 4 * (4 * kStage + 4 * kSlabWords) + (bins ? 8 * kDtileKeys + 8 * bins : 16) + 64;
+    const uint32_t lds = 4 * (4 * kStage + 4 * kSlabWords) + (bins ? 8 * kDtileKeys + 4 * bins : 16) + 64;
     return 163840 / lds < 8 ? 163840 / lds : 8;
 }
 template <int BW, int UW, bool TRIVIAL, bool PUG, uint32_t BINS = 0>
@@ -1314,8 +1322,8 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
     // scattering instance: the tile's keys, per-bucket counts / offsets, and [0] keys reserved, [1] end of the staged prefix,
     // [2..4] proof sums (count, words, fail), [8..11] the scan's wave totals
     __shared__ uint64_t s_keys[SC ? kDtileKeys : 1];
-    __shared__ uint32_t s_cnt[SC ? BINS : 1];
-    __shared__ uint32_t s_base[SC ? BINS : 1];
+    __shared__ uint32_t s_cnt[SC ? BINS / 2 : 1];    // (16 bits per bucket, two buckets a word: scatter_tail)
+    __shared__ uint32_t s_base[SC ? BINS / 2 : 1];
     __shared__ uint32_t s_misc[12];
     const uint32_t lane = lane_id();
     const uint32_t wv = threadIdx.x >> 6;
@@ -1330,7 +1338,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         const uint32_t c1 = slab_prefix[my_cell + 1];
         slab_a = min(c1, slab_prefix[my_cell] + td.y * (4 * kDtileSlabs) + wv * kDtileSlabs);
         slab_b = min(c1, slab_a + kDtileSlabs);
-        for (uint32_t b = threadIdx.x; b < BINS; b += 256) s_cnt[b] = 0;
+        for (uint32_t b = threadIdx.x; b < BINS / 2; b += 256) s_cnt[b] = 0;
         if (threadIdx.x < 5) s_misc[threadIdx.x] = threadIdx.x == 1 ? kDtileKeys : 0u;
         __syncthreads();
     } else {

@@ -42,8 +42,8 @@ struct DecodeArgs {
     // cells straight into their bucket slabs (keys1, cursor) - keys0 then holds single-bucket cells' keys and the keys that found
     // their slab full - and the fix-up decode re-decodes every cell whose proof failed into keys0 for k_fix_slabs
     uint2* dtile;                 // [n_dtiles] device-filled (k_slab_setup): tile -> (cell, tile index inside the cell)
-    uint32_t n_dtiles_lo;         // tiles of the 512-bin instance (cells of <= 512 or > kLdsBins buckets) ...
-    uint32_t n_dtiles_hi;         // ... then those of the kLdsBins instance (512 < buckets <= kLdsBins)
+    uint32_t n_dtiles_lo;         // tiles of the kDecodeSplitBins instance (cells of <= kDecodeSplitBins or > kLdsBins buckets) ...
+    uint32_t n_dtiles_hi;         // ... then those of the kLdsBins instance (kDecodeSplitBins < buckets <= kLdsBins)
     uint64_t* keys1;
     uint32_t* cursor;
     uint32_t* slab_ovf;
@@ -51,7 +51,10 @@ struct DecodeArgs {
 };
 constexpr uint32_t kDecodeTileSlabsHost = 4 * AFQ_DTILE_SLABS;   // 1 KiB slabs per scattering-decoder tile (4 waves)
 constexpr uint32_t kLdsBins = 2048;          // buckets per cell the LDS paths (k_scatter, the scattering decoder) can hold
-constexpr uint32_t kDecodeSplitBins = 512;   // cells of more buckets than this (and at most kLdsBins) take the kLdsBins instance
+#ifndef AFQ_DECODE_SPLIT_BINS
+#define AFQ_DECODE_SPLIT_BINS 1024
+#endif
+constexpr uint32_t kDecodeSplitBins = AFQ_DECODE_SPLIT_BINS;   // cells of more buckets than this (and at most kLdsBins) take the kLdsBins instance (measurement builds: 512)
 __host__ __device__ inline bool decode_tile_hi(uint32_t lg_nb) { return (1u << lg_nb) > kDecodeSplitBins && (1u << lg_nb) <= kLdsBins; }
 
 struct ResolveArgs {

@@ -467,9 +467,16 @@ __device__ __forceinline__ void resolve_bucket_lds(const BucketDesc& d, uint64_t
 // of a sort.  Anything the slots cannot express (a UMI seen with more than kHtPairs genes, a UMI that does
 // not fit 32 bits) sends the whole bucket down the sort path - same result, just slower.
 constexpr uint32_t kHtKeys = 256;            // buckets up to this many keys take the table (nearly all: the planner aims at kBucketTarget)
-// slots: load factor <= 4/5 (of distinct UMIs, usually far fewer than keys).  (1.5 n until round 7: 1.25 n probes longer, but its
-// 5.7 KiB of LDS let seven hash workgroups share a SIMD instead of six - k_resolve_hash 602 -> 557 us per launch.)
-constexpr uint32_t kHtCap = kHtKeys + kHtKeys / 4;
+// slots: load factor <= 8/9 (of distinct UMIs, usually far fewer than keys).  (1.5 n until round 7: 1.25 n probes longer, but its
+// 5.7 KiB of LDS let seven hash workgroups share a SIMD instead of six - k_resolve_hash 602 -> 557 us per launch.  Round 9: n + n / 8
+// slots in multiples of 32 - 288 for 256 keys - and the parked keys as 32-bit words: 4.8 KiB, EIGHT workgroups per SIMD, 551 -> 509 us;
+// the 32-bit parked list with n + n / 4 slots, seven workgroups: no gain.  profiles/r09_bench.txt; measurement builds: -DAFQ_HT_SLOT_SHIFT=2.)
+#ifndef AFQ_HT_SLOT_SHIFT
+#define AFQ_HT_SLOT_SHIFT 3
+#endif
+constexpr uint32_t ht_slots(uint32_t n) { return AFQ_HT_SLOT_SHIFT == 2 ? ((n + (n >> 2) + 63) & ~63u) : ((n + (n >> AFQ_HT_SLOT_SHIFT) + 31) & ~31u); }
+constexpr uint32_t kHtCap = ht_slots(kHtKeys);
+static_assert(kHtCap > kHtKeys && kHtCap < (1u << 12), "a probe always meets an empty slot; a parked key's slot takes 12 bits beside its 20-bit gene");
 constexpr uint32_t kHtPairs = 3;
 constexpr uint32_t kNoCol = 0xFFFFFFFFu;
 static_assert(kHtKeys < (1u << 12), "per-bucket read counts fit the 12-bit counter");
@@ -510,7 +517,7 @@ __device__ __forceinline__ uint32_t col_from_pairs(uint32_t p0, uint32_t p1, uin
 // aggregates of the winner set W: |W|, its two smallest genes, its spliced members, and whether the sibling
 // (g+1) of its smallest spliced gene is in W - which is what "the next winner in gene order is the same
 // gene" means for ascending ids 2g, 2g+1.
-constexpr uint32_t kHtOvf = 64;
+constexpr uint32_t kHtOvf = 64;   // parked keys a bucket's list holds, each one word: the UMI's slot << 20 | gene (the slot stands for the UMI)
 constexpr uint32_t kHtMerge = 8;   // genes of one UMI the in-register merge holds (more: the bucket takes the sort path)
 // (gene, reads) candidates in registers, a count of 0 = no candidate.  Plain unrolled loops over the two arrays: as a callback
 // that walked them (a lambda handed a lambda) the aggregates below were captured by reference twice over, stayed in memory -
@@ -589,7 +596,7 @@ __device__ __forceinline__ uint32_t em_from_pairs(uint32_t p0, uint32_t p1, uint
 // On success col[h] holds the column of the UMI whose slot the lane claimed in round h (kNoCol: none) and true is returned.
 constexpr uint32_t kHtRounds = kHtKeys / 64;
 __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__ src, uint32_t n, const ResolveCfg& rc,
-                                                    unsigned long long* s_slot, uint32_t* s_pair, uint64_t* s_ovf,
+                                                    unsigned long long* s_slot, uint32_t* s_pair, uint32_t* s_ovf,
                                                     uint32_t* s_flag, uint32_t* s_novf, DevStatus* st,
                                                     uint32_t cell, uint32_t (&col_out)[kHtRounds], bool em, const EmStage& es) {
     constexpr uint32_t E = kHtRounds;
@@ -598,7 +605,7 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
     uint64_t key[E];
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) key[h] = h * 64 + lane < n ? ld_nt(&src[h * 64 + lane]) : 0ull;
-    uint32_t cap = (n + (n >> 2) + 63) & ~63u;   // multiples of 64 slots: 1.25 n rounded up
+    uint32_t cap = ht_slots(n);
     cap = cap < 128 ? 128 : cap;
     {
         uint4* u4 = reinterpret_cast<uint4*>(s_slot);
@@ -649,7 +656,7 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
                 }
                 if (!done) {  // the UMI's counters are taken by other genes (and this gene can never get one)
                     const uint32_t k = atomicAdd(s_novf, 1u);
-                    if (k < kHtOvf) { s_ovf[k] = key[h]; atomicOr(&s_flag[slot >> 5], 1u << (slot & 31)); }
+                    if (k < kHtOvf) { s_ovf[k] = (slot << kGeneBits) | gene; atomicOr(&s_flag[slot >> 5], 1u << (slot & 31)); }   // (the UMI is the slot's)
                     else bad = true;
                 }
             }
@@ -666,7 +673,7 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
         uint32_t col = kNoCol;
         const uint32_t slot = own_slot[h];
         if (slot != kNoCol) {
-            const uint32_t p0 = (uint32_t)s_slot[slot], umi = (uint32_t)(key[h] >> kGeneBits);
+            const uint32_t p0 = (uint32_t)s_slot[slot];
             const uint32_t p1 = s_pair[slot * (kHtPairs - 1)], p2 = s_pair[slot * (kHtPairs - 1) + 1];
             if (!novf || !((s_flag[slot >> 5] >> (slot & 31)) & 1u)) col = em ? em_from_pairs(p0, p1, p2, rc, es) : col_from_pairs(p0, p1, p2, rc);
             else {
@@ -678,9 +685,9 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
                 cg[0] = p0 >> 12; cc[0] = p0 & 0xFFFu; cg[1] = p1 >> 12; cc[1] = p1 & 0xFFFu; cg[2] = p2 >> 12; cc[2] = p2 & 0xFFFu;
                 uint32_t k = 3;
                 for (uint32_t i = 0; i < novf; ++i) {
-                    const uint64_t ki = s_ovf[i];
-                    if ((uint32_t)(ki >> kGeneBits) != umi) continue;
-                    const uint32_t g = (uint32_t)ki & kGeneMask;
+                    const uint32_t ki = s_ovf[i];
+                    if ((ki >> kGeneBits) != slot) continue;
+                    const uint32_t g = ki & kGeneMask;
                     bool found = false;
 #pragma unroll
                     for (uint32_t q = 3; q < kHtMerge; ++q) if (q < k && cg[q] == g) { ++cc[q]; found = true; }
@@ -878,7 +885,7 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
                                                             const uint64_t* __restrict__ keys1, uint32_t* __restrict__ cell_ncols,
                                                             uint32_t* __restrict__ nnz, OverflowEnt* __restrict__ ovf_list,
                                                             uint32_t* __restrict__ div_list, DevStatus* st, ResolveCfg rc, LabArea la) {
-    constexpr uint32_t kHashWords = kHtCap * (1 + kHtPairs) + 2 * kHtOvf + kHtCap / 32 + 2 + (EM ? 2 * kHtKeys : 0);
+    constexpr uint32_t kHashWords = kHtCap * (1 + kHtPairs) + kHtOvf + kHtCap / 32 + 2 + (EM ? 2 * kHtKeys : 0);
     __shared__ __attribute__((aligned(16))) uint32_t s_raw[MULTI ? kH2Words : kHashWords];
     __shared__ uint32_t s_misc[6];
     const uint32_t b = resolve_block_bucket(n_buckets);
@@ -897,8 +904,8 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
         if (ok) {
             unsigned long long* s_slot = reinterpret_cast<unsigned long long*>(s_raw);      // 2 words per slot
             uint32_t* s_pair = s_raw + 2 * kHtCap;                                            // kHtPairs-1 words per slot
-            uint64_t* s_ovf = reinterpret_cast<uint64_t*>(s_raw + kHtCap * (1 + kHtPairs));
-            uint32_t* s_flag = s_raw + kHtCap * (1 + kHtPairs) + 2 * kHtOvf;
+            uint32_t* s_ovf = s_raw + kHtCap * (1 + kHtPairs);
+            uint32_t* s_flag = s_raw + kHtCap * (1 + kHtPairs) + kHtOvf;
             uint32_t* s_hlab = s_flag + kHtCap / 32 + 2;   // EM only: staged label words / descriptors of this bucket
             if (EM && threadIdx.x < 6) s_misc[threadIdx.x] = 0;
             const EmStage es{s_hlab, s_hlab + kHtKeys, &s_misc[2]};
