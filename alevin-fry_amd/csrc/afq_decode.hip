@@ -1215,8 +1215,8 @@ static_assert(kDtileKeys % 256 == 0 && kDtileKeys < 65536, "the tail keeps kDtil
 constexpr uint32_t kDtileRun = AFQ_DTILE_RUN;   // consecutive tiles one XCD takes (a cell's bucket runs merge in one L2), as k_scatter
 
 // The scattering instance's end of a tile: the proof sums and the key count of the cell, then k_scatter's tail over the staged keys.
-// The per-bucket words are 16 bits each (s_cnt, s_base: two buckets a word), which is what lets the six-workgroups-per-CU instance
-// hold 1024 buckets in the LDS that held 512 of 32-bit words (and the kLdsBins instance run five workgroups per CU, not four): a
+// The per-bucket words are 16 bits each (s_cnt, s_base: two buckets a word), so that 1024 buckets' words fit the 5 KiB of the
+// waves' slab stages, where k_decode_recs puts them (2048 buckets: s_cnt there, s_base apart), and are cleared here: a
 // tile has fewer than 2^16 keys, so its counts and tile-local offsets fit, and a bucket's position in its slab is kept exactly
 // below kBase16Max and as kBase16Max from there on - beyond any slab capacity this path takes (a cell with larger slabs goes the
 // per-key way), so a key at such a position is seen to be past its slab all the same.
@@ -1225,7 +1225,7 @@ template <uint32_t BINS>
 __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, uint64_t* s_keys, uint32_t* s_cnt, uint32_t* s_base,
                                              uint32_t* s_misc, uint32_t* __restrict__ cell_nkeys, CellChk* __restrict__ chk,
                                              const DecodeScatter& so, uint64_t* __restrict__ keys0) {
-    __syncthreads();   // every wave's keys and sums are in LDS
+    __syncthreads();   // every wave's keys and sums are in LDS, and no wave reads its slab stage any more
     const uint32_t n_all = s_misc[0], nst = min(n_all, s_misc[1]);
     if (threadIdx.x == 0) {
         if (s_misc[2]) atomicAdd(&chk[cell].count, s_misc[2]);
@@ -1249,6 +1249,10 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
         }
         return;
     }
+    // s_cnt (and s_base, where it fits) lie on the waves' slab stages, which are dead from the barrier above on: cleared here, not in
+    // the kernel's prologue
+    for (uint32_t b = threadIdx.x; b < BINS / 2; b += 256) s_cnt[b] = 0;
+    __syncthreads();
     constexpr uint32_t E = kDtileKeys / 256;
     uint64_t key[E];
     uint32_t rank[E];   // bucket << 16 | rank of the key among the tile's keys of that bucket
@@ -1294,13 +1298,27 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
 }
 
 constexpr uint32_t kInl = 3;
-// waves per SIMD the instance's LDS allows (160 KiB per CU, a workgroup's four waves on four SIMDs), at most eight
-constexpr uint32_t decode_recs_occupancy(uint32_t bins) {
-    const uint32_t lds = 4 * (4 * kStage + 4 * kSlabWords) + (bins ? 8 * kDtileKeys + 4 * bins : 16) + 64;
-    return 163840 / lds < 8 ? 163840 / lds : 8;
+// LDS of an instance, as k_decode_recs declares it: the four waves' slab stages, their candidate lists (one byte an entry: a
+// candidate is a staged position below kSlabWords), s_misc, and for the scattering instance the tile's keys.  Its per-bucket words
+// s_cnt and s_base (2 * BINS bytes each) are laid over the stages, which are dead when the tail starts; only where the two do not
+// fit the stages together (the kLdsBins instance) s_base has words of its own.
+constexpr uint32_t kStageBytes = 4 * 4 * kStage;
+static_assert(kSlabWords <= 256, "a candidate's staged position is kept in a byte");
+constexpr bool decode_recs_own_base(uint32_t bins) { return 4 * bins > kStageBytes; }
+constexpr uint32_t decode_recs_lds(uint32_t bins) {
+    return kStageBytes + 4 * kSlabWords + 12 * 4 + (bins ? 8 * kDtileKeys + (decode_recs_own_base(bins) ? 2 * bins : 0) : 0);
+}
+// waves per SIMD of an instance (a workgroup's four waves sit on four SIMDs): what its LDS allows of the CU's 160 KiB, at most
+// eight; at most seven for the scattering instance, whose record loop needs 72 VGPRs of the 512 a SIMD's lane has (at 64 it spills);
+// six for its trivial instance and for barcodes or UMIs of two words, which need up to 80 (at 72 they spill six).
+constexpr uint32_t kCuLdsBytes = 163840, kLaneVgprs = 512;
+constexpr uint32_t decode_recs_occupancy(uint32_t bins, bool trivial, bool wide) {
+    const uint32_t by_lds = kCuLdsBytes / decode_recs_lds(bins);
+    const uint32_t by_regs = !bins ? 8u : kLaneVgprs / (trivial || wide ? 80u : 72u);
+    return by_lds < by_regs ? by_lds : by_regs;
 }
 template <int BW, int UW, bool TRIVIAL, bool PUG, uint32_t BINS = 0>
-__global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_recs(const uint8_t* __restrict__ bytes,
+__global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW > 8))) void k_decode_recs(const uint8_t* __restrict__ bytes,
                                                     const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                     const uint32_t* __restrict__ slab_prefix,
                                                     const uint32_t* __restrict__ slab_cell,
@@ -1318,17 +1336,22 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
     constexpr uint32_t BWW = BW / 4, UWW = UW / 4, HW = 1 + BWW + UWW;
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     __shared__ uint32_t s_stage[4][kStage];
-    __shared__ uint32_t s_list[4][kSlabWords];
-    // scattering instance: the tile's keys, per-bucket counts / offsets, and [0] keys reserved, [1] end of the staged prefix,
-    // [2..4] proof sums (count, words, fail), [8..11] the scan's wave totals
+    __shared__ uint8_t s_list[4][kSlabWords];   // staged positions of the slab's candidates (< kSlabWords)
+    // scattering instance: the tile's keys, and [0] keys reserved, [1] end of the staged prefix, [2..4] proof sums (count, words,
+    // fail), [8..11] the scan's wave totals.  The tail's per-bucket counts / offsets (16 bits per bucket, two buckets a word:
+    // scatter_tail) take the stages' place once every wave is through its slabs.
     __shared__ uint64_t s_keys[SC ? kDtileKeys : 1];
-    __shared__ uint32_t s_cnt[SC ? BINS / 2 : 1];    // (16 bits per bucket, two buckets a word: scatter_tail)
-    __shared__ uint32_t s_base[SC ? BINS / 2 : 1];
+    constexpr bool kOwnBase = SC && decode_recs_own_base(BINS);
+    __shared__ uint32_t s_base_own[kOwnBase ? BINS / 2 : 1];
     __shared__ uint32_t s_misc[12];
+    static_assert(sizeof(s_stage) == kStageBytes && 2 * BINS <= kStageBytes, "s_cnt lies on the stages");
+    static_assert(kOwnBase || 4 * BINS <= kStageBytes, "s_cnt and s_base lie on the stages");
+    static_assert(sizeof(s_stage) + sizeof(s_list) + sizeof(s_misc) + (SC ? sizeof(s_keys) + (kOwnBase ? sizeof(s_base_own) : 0) : 0) ==
+                      decode_recs_lds(BINS), "decode_recs_occupancy counts this layout");
     const uint32_t lane = lane_id();
     const uint32_t wv = threadIdx.x >> 6;
     uint32_t* stage = s_stage[wv];
-    uint32_t* list = s_list[wv];
+    uint8_t* list = s_list[wv];
     uint32_t slab_a, slab_b, my_cell = 0;
     if constexpr (SC) {
         const uint32_t xr = blockIdx.x / 8, tile = ((xr / kDtileRun) * 8 + blockIdx.x % 8) * kDtileRun + xr % kDtileRun;
@@ -1338,7 +1361,6 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         const uint32_t c1 = slab_prefix[my_cell + 1];
         slab_a = min(c1, slab_prefix[my_cell] + td.y * (4 * kDtileSlabs) + wv * kDtileSlabs);
         slab_b = min(c1, slab_a + kDtileSlabs);
-        for (uint32_t b = threadIdx.x; b < BINS / 2; b += 256) s_cnt[b] = 0;
         if (threadIdx.x < 5) s_misc[threadIdx.x] = threadIdx.x == 1 ? kDtileKeys : 0u;
         __syncthreads();
     } else {
@@ -1389,15 +1411,16 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         }
         acc_count = 0; acc_words = 0; fail = false;
     };
-    auto issue_slab_loads = [&](uint32_t s0) {
+    // rows [r0, 5) of the slab at s0; r0 = 1 where the first row is already staged as the halo of the slab before
+    auto issue_slab_loads = [&](uint32_t s0, int r0 = 0) {
         if (s0 + kStage <= nwords) {
 #pragma unroll
-            for (int r = 0; r < 5; ++r) R[r] = W[s0 + r * 64 + lane];
+            for (int r = 0; r < 5; ++r) if (r >= r0) R[r] = W[s0 + r * 64 + lane];
         } else {
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 const uint32_t i = s0 + r * 64 + lane;
-                R[r] = i < nwords ? W[i] : 0u;
+                if (r >= r0) R[r] = i < nwords ? W[i] : 0u;
             }
         }
     };
@@ -1405,8 +1428,12 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
     load_cell(__builtin_amdgcn_readlane(my_cell, 0));
     if (!SC || slab_a < slab_b) issue_slab_loads((slab_a - sp0) * kSlabWords);
 
+    bool halo_is_row0 = false;
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
         const uint32_t s0 = (slab - sp0) * kSlabWords;
+        // a slab that follows one of its own cell finds its first row staged as that slab's halo (the same word, or the same zero
+        // fill past nwords): it was not loaded again, and is not kept in a register over the records either
+        if (halo_is_row0) R[0] = stage[kSlabWords + lane];
 #pragma unroll
         for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = R[r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1415,7 +1442,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         const bool has_next = slab + 1 < slab_b;
         const uint32_t next_cell = has_next ? __builtin_amdgcn_readlane(my_cell, (int)(slab + 1 - slab_a)) : cur_cell;
         const bool same_next = has_next && next_cell == cur_cell;
-        if (same_next) issue_slab_loads(s0 + kSlabWords);
+        if (same_next) issue_slab_loads(s0 + kSlabWords, 1);
 
         const bool triv = TRIVIAL && m.mode == kModeTrivial;  // tiny cells of a trivial run are cr-like (quant.rs:794-938)
         const bool room = nwords >= 2 + HW;
@@ -1615,9 +1642,10 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
             load_cell(next_cell);
             issue_slab_loads((slab + 1 - sp0) * kSlabWords);
         }
+        halo_is_row0 = same_next;
     }
     flush_chk();
-    if constexpr (SC) scatter_tail<BINS>(m, my_cell, s_keys, s_cnt, s_base, s_misc, cell_nkeys, chk, so, keys0);
+    if constexpr (SC) scatter_tail<BINS>(m, my_cell, s_keys, &s_stage[0][0], kOwnBase ? s_base_own : &s_stage[0][0] + BINS / 2, s_misc, cell_nkeys, chk, so, keys0);
 }
 
 // ---------------------------------------------------------------------------
