@@ -448,6 +448,16 @@ class Quantifier:
         self.lib.afq_em_instance_counts(self._h, out)
         return [int(x) for x in out]
 
+    def range_pipeline_counts(self) -> list:
+        """The last batch's ranges, those whose rows crossed on the copy stream without the host waiting, those that fell back
+        to the waiting path after draining it, and the result-array growths that had to wait for rows in flight
+        (afq_range_pipeline_counts)."""
+        out = (C.c_uint64 * 4)()
+        self.lib.afq_range_pipeline_counts.restype = None
+        self.lib.afq_range_pipeline_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self.lib.afq_range_pipeline_counts(self._h, out)
+        return [int(x) for x in out]
+
     def batch_stats(self) -> dict:
         s = AfqBatchStats()
         self._check(self.lib.afq_get_batch_stats(self._h, C.byref(s)))

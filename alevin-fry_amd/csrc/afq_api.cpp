@@ -164,6 +164,8 @@ struct RangeState {
     bool in_flight = false;
     bool pug_cell_launched = true;   // the range's k_pug_cell launch was made (else a handed-back cell means: run the range again)
     hipEvent_t kernels_done = nullptr;
+    hipEvent_t rows_done = nullptr;   // the copy stream has read this slot's d_gene / d_val (the rows of the range that last took the non-waiting path)
+    bool rows_pending = false;        // ... recorded, and the copy stream not drained since
     std::vector<TimedLaunch> launches;  // HIP-event brackets of this range's kernels (cfg.profile)
     std::vector<DevBuf*> all() {
         return {&d_meta, &d_keys0, &d_keys1, &d_cell_nkeys, &d_bucket_cnt, &d_bucket_cell, &d_multi_cells, &d_tile_desc, &d_src_off, &d_slab_ovf,
@@ -203,6 +205,15 @@ struct afq_ctx {
     std::string up_err;
     // Two sets of per-range device state: while the rows of range i cross PCIe, the kernels of range i+1 run.
     RangeState rs[2];
+    // The rows cross on a stream of their own, range behind range, and the host does not wait for them until afq_collect
+    // (finish_range; DESIGN.md 3.1 "Round 11").  It never holds a kernel.
+    hipStream_t copy_stream = nullptr;
+    DevBuf d_kick;                   // a few bytes that go up in front of every range's rows (finish_range says why)
+    void* h_kick = nullptr;          // ... out of pinned memory that never changes
+    bool copies_in_flight = false;   // row copies enqueued since the copy stream was last drained
+    bool in_retry = false;           // finish_range is running a range again: the nested ranges take the waiting path
+    uint64_t n_pipe[4] = {0};        // afq_range_pipeline_counts
+    uint64_t last_total = 0;         // rows of the batch collected last: begin_batch sizes the result arrays from it
     bool all_aligned = true;  // every chunk offset is a multiple of 4
     // 1/2-byte barcode or UMI fields: the batch is rewritten on the device with 4-byte fields (k_widen) and everything
     // downstream works on that copy - w_off / w_nbytes are the chunks of the copy, chunk_off / hdr stay the caller's
@@ -374,7 +385,7 @@ P2Small p2_small_layout(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_p
 uint64_t p2_small_bytes(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_pug) { return 4 * p2_small_layout(n, parts, tiles, n_pug).words + 64; }
 
 #ifndef AFQ_TAPER_CR
-#define AFQ_TAPER_CR 0.419, 0.671, 0.822, 0.913, 0.967, 1.0, 1.0, 1.0   // (measurement builds override the cr-like taper: eight cumulative shares)
+#define AFQ_TAPER_CR 0.363, 0.606, 0.769, 0.878, 0.951, 1.0, 1.0, 1.0   // (measurement builds override the cr-like taper: eight cumulative shares)
 #endif
 // Split the batch into ranges of cells that fit the memory budget, build nothing yet.
 int plan_ranges(afq_ctx* c) {
@@ -450,6 +461,9 @@ int plan_ranges(afq_ctx* c) {
     // (late round 4, cr-like: a range's rows take about half as long to cross PCIe as its kernels run - more for ranges of small
     //  cells, whose rows are longer per read - so every range is 0.6 of the one before it: six ranges, the last 3.3 % of the work;
     //  28/28/22/14/8 % left 0.65 ms of the last range's rows in the open.  12.96-13.26 -> 12.48-12.68 ms, profiles/history/run_r04ad.sh)
+    // (round 11, cr-like: the rows cross on the copy stream back to back from the end of the first range's kernels on, so the step is
+    //  the longer of front + kernels(0) + all rows and front + all kernels + the last range's rows; the two meet at a first range of
+    //  0.36 of the work: ratio 0.67, six ranges.  10.29-10.33 -> 10.12-10.17 ms against the ratio-0.6 table, profiles/r11_bench.txt)
     static const double kTaperCr[] = {AFQ_TAPER_CR}, kTaperPug[] = {0.40, 0.76, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
     const double* kTaper = pug_res ? kTaperPug : kTaperCr;
     const size_t kTaperN = 8;
@@ -540,6 +554,34 @@ int RangeInit::flush(afq_ctx* c, RangeState& B, hipStream_t s) {
     launch();
     HIP_TRY(c, hipGetLastError());
     ops.clear();
+    return 0;
+}
+
+// The copy stream: of the device's highest priority, which is a hardware queue of another pool than the context's other streams
+// share with the rest of the process (inferred from one trace, profiles/r11_timeline_nokick.txt against r11_timeline.txt: the stream of default
+// priority ran on the second range stream's queue, this one does not) - its rows_done markers wait for copies, and behind such a marker on a shared queue a
+// range's kernels would wait as well.  Made by the first range that sends rows down it, not by afq_create: the first such
+// stream of a process is a new hardware queue - tens of milliseconds, one context after the other - which a context that
+// never uses it (EM resolutions) should not pay, and which `afquant quant --devices` counts as a device's busy time only
+// from its first batch on (tests/test_gpu_multi.py: the devices' busy times within 1.35x).
+void rows_delay_cb(void* us) { std::this_thread::sleep_for(std::chrono::microseconds((long)(intptr_t)us)); }   // AFQ_TEST_ROWS_DELAY_US
+int ensure_copy_stream(afq_ctx* c) {
+    if (c->copy_stream) return 0;
+    int least = 0, greatest = 0;   // (the greatest priority is the numerically lowest value)
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); greatest = 0; }
+    HIP_TRY(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, greatest));
+    HIP_TRY(c, c->d_kick.ensure(64));
+    HIP_TRY(c, hipHostMalloc(&c->h_kick, 64, hipHostMallocDefault));
+    std::memset(c->h_kick, 0, 64);
+    return 0;
+}
+
+// Wait until every row copy enqueued so far has landed: in front of everything that frees, rewrites or hands out what the
+// copy stream reads or writes (a slot's d_gene / d_val, the result arrays).
+int drain_copies(afq_ctx* c) {
+    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    c->copies_in_flight = false;
+    for (auto& rs : c->rs) rs.rows_pending = false;
     return 0;
 }
 
@@ -984,6 +1026,9 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     if (!em) {
         HIP_TRY(c, B.d_cell_ptr.ensure(8ull * (n + 1)));
         B.chain_cap = std::min(B.d_gene.cap, B.d_val.cap) / 4;
+        // (the rows of the range that had this slot before may still be crossing out of d_gene / d_val: the compaction - and nothing
+        //  in front of it - waits for them on the device, ahead of its bracket's first event)
+        if (B.rows_pending) HIP_TRY(c, hipStreamWaitEvent(s, B.rows_done, 0));
         tc.seg(K_COMPACT);
         launch_row_ptr(s, B.d_nnz.as<uint32_t>(), n, B.d_cell_ptr.as<uint64_t>(), pack);
         launch_compact(s, B.d_meta.as<CellMeta>(), n, B.d_keys0.as<uint64_t>(), B.d_keys1.as<uint64_t>(), B.d_nnz.as<uint32_t>(),
@@ -1046,6 +1091,16 @@ int finish_range(afq_ctx* c, int slot) {
     const bool rehash = st.err_code == kErrLabelHash && B.hash_try + 1 < kMaxHashTries;
     const bool regrow = st.err_code == kErrPugPool && B.pool_try < kMaxPoolTries;
     const bool wide_limit = st.err_code == kErrPugLimit && wide && n > 1;
+    const bool handback = !st.err_code && !B.pug_cell_launched && B.h_pack.p[9];
+    // Whatever is not the plain end of a range - a re-run, an error - first lets the rows in flight land, then goes on as it
+    // did when finish_range waited for every range's rows itself.  The ranges a re-run enqueues take that path as well.
+    const bool nested = c->in_retry;
+    struct RetryScope { afq_ctx* c; bool was; ~RetryScope() { c->in_retry = was; } } retry_scope{c, nested};
+    if (rehash || regrow || wide_limit || handback || st.err_code) {
+        if (const int rc = drain_copies(c)) return rc;
+        if (!nested) c->n_pipe[2] += 1;
+        c->in_retry = true;
+    }
     if (rehash || regrow || wide_limit) {
         if (rehash) c->n_label_rehash += 1; else if (regrow) c->n_pool_regrow += 1;
         take_back_attempt();
@@ -1101,7 +1156,7 @@ int finish_range(afq_ctx* c, int slot) {
         if (regrow) B.d_epool.release();   // the enlarged pool is that attempt's alone: the next range plans its own
         return rc;
     }
-    if (!st.err_code && !B.pug_cell_launched && B.h_pack.p[9]) {   // cells were handed back and the kernel that takes them was not launched
+    if (handback) {   // cells were handed back and the kernel that takes them was not launched
         c->handback_seen = true;
         take_back_attempt();
         int rc = run_range(c, B.cur, slot, nullptr, B.hash_try, B.pool_try);
@@ -1282,6 +1337,19 @@ int finish_range(afq_ctx* c, int slot) {
     const uint64_t tot = ptr[n];
     hc.lap("finish: small D2H + prefix");
     const bool compacted = B.chained && !em && tot <= B.chain_cap;   // the compaction behind the range's kernels had room for every row
+    HostResult& R = *c->res;
+    const size_t g0 = R.gene.n;
+    const bool fast = compacted && !nested;   // the rows need nothing more from the host: they cross on the copy stream, unwaited for
+    if (!fast) {   // (d_gene / d_val are grown, i.e. freed, or written again; the rows then cross on the range's stream)
+        if (const int rc = drain_copies(c)) return rc;
+        if (!nested) c->n_pipe[2] += 1;
+    } else {
+        c->n_pipe[1] += 1;
+        if (c->copies_in_flight && g0 + tot > std::min(R.gene.cap, R.val.cap)) {   // (reserve moves the arrays: not under a copy into them)
+            if (const int rc = drain_copies(c)) return rc;
+            c->n_pipe[3] += 1;
+        }
+    }
     if (!compacted) {
         HIP_TRY(c, B.d_cell_ptr.ensure(8ull * (n + 1)));
         HIP_TRY(c, B.d_gene.ensure(std::max<uint64_t>(4 * tot, 16)));
@@ -1298,20 +1366,40 @@ int finish_range(afq_ctx* c, int slot) {
     // (the row offsets still go up, although the device has made its own: under rocprofv3 the runtime moved the rows' two copies
     //  with __amd_rocclr_copyBuffer kernels - 27 % of the GPU time of a profiled step, next to the following range's decoder -
     //  whenever the command in front of them on the stream was a kernel; behind a small upload they stay on the DMA engines, as
-    //  they did while the compaction was enqueued from here.  profiles/history/run_r04ak.sh, run_r04al.sh, run_r04am.sh)
-    if (compacted) HIP_TRY(c, hipMemcpyAsync(B.d_cell_ptr.p, ptr.data(), 8ull * (n + 1), hipMemcpyHostToDevice, s));
-    HostResult& R = *c->res;
-    const size_t g0 = R.gene.n;
+    //  they did while the compaction was enqueued from here.  profiles/history/run_r04ak.sh, run_r04al.sh, run_r04am.sh.
+    //  The copy stream never holds a kernel, yet without such an upload the runtime moved every range's rows but the first with
+    //  blit kernels all the same - the command in front of them is then the rows_done marker of the range before, a packet on the
+    //  compute queue like a kernel: profiles/r11_timeline_nokick.txt.  There the upload is a few constant bytes, d_kick.)
+    if (compacted && !fast) HIP_TRY(c, hipMemcpyAsync(B.d_cell_ptr.p, ptr.data(), 8ull * (n + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(c, R.gene.reserve(g0 + tot));
     HIP_TRY(c, R.val.reserve(g0 + tot));
     R.gene.n = R.val.n = g0 + tot;
-    if (tot) {
-        HIP_TRY(c, hipMemcpyAsync(R.gene.p + g0, B.d_gene.p, 4 * tot, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(R.val.p + g0, B.d_val.p, 4 * tot, hipMemcpyDeviceToHost, s));
+    if (fast) {
+        // (the range's stream has been waited for above, so the rows are in d_gene / d_val; the copies of consecutive ranges queue
+        //  back to back, and the next range of this slot compacts behind rows_done.  afq_collect waits for them.)
+        if (tot) {
+            if (const int rc = ensure_copy_stream(c)) return rc;
+            if (!B.rows_done) HIP_TRY(c, hipEventCreateWithFlags(&B.rows_done, hipEventDisableTiming));
+            // (tests: the rows start across that much later, as on a slow link - the next range of the slot has long been compacted by
+            //  then unless it waits for rows_done)
+            if (const long us = test_hook_long("ROWS_DELAY_US", 0); us > 0) HIP_TRY(c, hipLaunchHostFunc(c->copy_stream, rows_delay_cb, (void*)(intptr_t)us));
+            HIP_TRY(c, hipMemcpyAsync(c->d_kick.p, c->h_kick, 64, hipMemcpyHostToDevice, c->copy_stream));
+            HIP_TRY(c, hipMemcpyAsync(R.gene.p + g0, B.d_gene.p, 4 * tot, hipMemcpyDeviceToHost, c->copy_stream));
+            HIP_TRY(c, hipMemcpyAsync(R.val.p + g0, B.d_val.p, 4 * tot, hipMemcpyDeviceToHost, c->copy_stream));
+            HIP_TRY(c, hipEventRecord(B.rows_done, c->copy_stream));
+            B.rows_pending = true;
+            c->copies_in_flight = true;
+        }
+        hc.lap("finish: rows enqueued");
+    } else {
+        if (tot) {
+            HIP_TRY(c, hipMemcpyAsync(R.gene.p + g0, B.d_gene.p, 4 * tot, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(R.val.p + g0, B.d_val.p, 4 * tot, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipGetLastError());
+        hc.lap("finish: compact + D2H of CSR");
     }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    hc.lap("finish: compact + D2H of CSR");
     const afq_config& g = c->cfg;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t nrec = c->hdr[2 * (B.cur.c0 + i) + 1];
@@ -1433,32 +1521,49 @@ int begin_batch(afq_ctx* c, uint32_t n_cells, uint64_t first_cell_index) {
     c->stats.input_bytes = c->n_bytes;
     for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
     c->h2d_piped = false;
-    return plan_ranges(c);
+    for (uint64_t& x : c->n_pipe) x = 0;
+    // (the result arrays as large as the last batch's rows: a reserve that grows them has to wait for the row copies in flight)
+    if (c->last_total) {
+        HIP_TRY(c, c->res->gene.reserve(c->last_total));
+        HIP_TRY(c, c->res->val.reserve(c->last_total));
+    }
+    const int rc = plan_ranges(c);
+    c->n_pipe[0] = rc ? 0 : c->ranges.size();
+    return rc;
 }
 
-// Software pipeline over the ranges with two buffer sets: range i is enqueued before range i-1 is
-// finished (sync + compaction + D2H of its rows), so that copy overlaps range i's kernels.  The last range
-// stays in flight until afq_collect.  With h2d_piped, range i's kernels also wait for its input bytes, which an
-// upload thread (or the DMA engine alone, for pinned sources) is still bringing over while earlier ranges run.
+// Software pipeline over the ranges with two buffer sets, three deep: ranges 0 and 1 are enqueued, then range i is
+// finished (wait for its kernels, enqueue its rows on the copy stream) and range i+2 enqueued straight after, into the
+// slot range i has left - the device always has the next range queued, the host plans under kernels, and the rows of
+// consecutive ranges cross back to back.  The last range stays in flight until afq_collect, which also waits for the
+// rows.  With h2d_piped, range i's kernels also wait for its input bytes, which an upload thread (or the DMA engine
+// alone, for pinned sources) is still bringing over while earlier ranges run.
 int run_batch(afq_ctx* c) {
     c->next_range = 0;
     c->pending = true;
     const size_t k = c->ranges.size();
     int rc = 0;
-    for (size_t i = 0; i < k && !rc; ++i) {
+    auto enqueue = [&](size_t i) -> int {
         hipEvent_t ev = nullptr;
         if (c->h2d_piped) {
             std::unique_lock<std::mutex> lk(c->up_mu);
             c->up_cv.wait(lk, [&]() { return c->up_enqueued > i || c->up_rc != 0; });
-            if (c->up_rc) { rc = c->up_rc; std::lock_guard<std::mutex> g(c->err_mu); c->err = c->up_err; break; }
+            if (c->up_rc) { std::lock_guard<std::mutex> g(c->err_mu); c->err = c->up_err; return c->up_rc; }
             ev = c->h2d_ev[i];
         }
-        rc = run_range(c, c->ranges[i], (int)(i & 1), ev);
-        if (!rc && i > 0) rc = finish_range(c, (int)((i - 1) & 1));
+        return run_range(c, c->ranges[i], (int)(i & 1), ev);
+    };
+    for (size_t i = 0; i < std::min<size_t>(k, 2) && !rc; ++i) rc = enqueue(i);
+    for (size_t i = 0; i + 1 < k && !rc; ++i) {
+        rc = finish_range(c, (int)(i & 1));
+        if (!rc && i + 2 < k) rc = enqueue(i + 2);
     }
     if (rc) {
         c->pending = false;
         for (auto& rs : c->rs) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
+        if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+        c->copies_in_flight = false;
+        for (auto& rs : c->rs) rs.rows_pending = false;
         return rc;
     }
     c->next_range = k;
@@ -1498,6 +1603,10 @@ uint64_t afq_pool_regrow_count(const afq_ctx* ctx) { return ctx ? ctx->n_pool_re
 uint64_t afq_em_resize_count(const afq_ctx* ctx) { return ctx ? ctx->n_em_resized : 0; }
 uint64_t afq_mono_cell_count(const afq_ctx* ctx) { return ctx ? ctx->n_mono_cells : 0; }
 uint64_t afq_resolve_divert_count(const afq_ctx* ctx) { return ctx ? ctx->n_divert : 0; }
+void afq_range_pipeline_counts(const afq_ctx* ctx, uint64_t out[4]) {
+    if (!out) return;
+    for (int t = 0; t < 4; ++t) out[t] = ctx ? ctx->n_pipe[t] : 0;
+}
 void afq_em_instance_counts(const afq_ctx* ctx, uint64_t out[6]) {
     if (!out) return;
     for (int t = 0; t < 6; ++t) out[t] = ctx ? ctx->n_em_inst[t] : 0;
@@ -1564,6 +1673,7 @@ void afq_destroy(afq_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);   // (before the slots' buffers and the result arrays go)
     harvest_timers(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     for (auto& rs : c->rs) {
@@ -1571,9 +1681,12 @@ void afq_destroy(afq_ctx* c) {
         for (DevBuf* b : rs.all()) b->release();
         rs.h_em2_tiers.release();
         if (rs.kernels_done) (void)hipEventDestroy(rs.kernels_done);
+        if (rs.rows_done) (void)hipEventDestroy(rs.rows_done);
         if (rs.stream) (void)hipStreamDestroy(rs.stream);
     }
-    DevBuf* bufs[] = {&c->d_t2g, &c->d_bytes_own, &c->d_chunk_off, &c->d_hdr, &c->d_wide};
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    if (c->h_kick) (void)hipHostFree(c->h_kick);
+    DevBuf* bufs[] = {&c->d_t2g, &c->d_bytes_own, &c->d_chunk_off, &c->d_hdr, &c->d_wide, &c->d_kick};
     for (auto b : bufs) b->release();
     for (auto& b : c->atac) b.release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
@@ -1728,8 +1841,17 @@ int afq_collect(afq_ctx* c, afq_result* out) {
     HIP_TRY(c, hipSetDevice(c->device));
     c->pending = false;
     int rc = c->ranges.empty() ? 0 : finish_range(c, (int)((c->ranges.size() - 1) & 1));
+    if (!rc) {   // the late half of every range that did not wait for its rows
+        HostClock hc;
+        rc = drain_copies(c);
+        hc.lap("collect: wait for rows");
+    } else {
+        for (auto& rs : c->rs) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
+        (void)drain_copies(c);
+    }
     if (rc) return rc;
     HostResult* R = c->res;
+    c->last_total = R->gene.n;
     c->res = nullptr;
     std::memset(out, 0, sizeof(*out));
     out->n_cells = c->n_cells;

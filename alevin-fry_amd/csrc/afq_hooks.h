@@ -8,6 +8,9 @@
 //   AFQ_TEST_POOL_ROOM_WORDS=n   the device holds a parsimony pool of at most n words: run_range refuses a larger one with
 //                                AFQ_ERR_OOM before it allocates, and finish_range's room check answers as such a device would -
 //                                the no-room re-runs of a range whose graphs outgrew its pool, on a test box that always has room
+//   AFQ_TEST_ROWS_DELAY_US=n     a range's rows start across the link n microseconds after they were enqueued on the copy stream (a
+//                                host function in front of them): the stand-in for a slow link, under which the next range of the
+//                                slot would compact into row buffers still being read unless it waits for rows_done
 // Rounds 1-4 had grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not
 // kept; those alternatives are gone, as are (round 7) the last hooks that selected one and the per-phase clock builds (a
 // measurement build is `make variant DEFS=...` of a scratch copy), and what is left besides the hooks is:

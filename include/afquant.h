@@ -317,6 +317,12 @@ uint64_t afq_resolve_divert_count(const afq_ctx* ctx);
  * rest in global memory; out[5] those of out[4] that ran with 32-bit state ids.  Cells without an ambiguous molecule, and
  * batches under AFQ_EM_ORDER=canonical (the sequential kernels of afq_em.hip), count nowhere.  Diagnostics only. */
 void afq_em_instance_counts(const afq_ctx* ctx, uint64_t out[6]);
+/* The range pipeline of the last submitted batch: out[0] its ranges, out[1] those whose rows went onto the copy stream without
+ * the host waiting for them (waited for in afq_collect), out[2] those that first let the copy stream drain and then waited for
+ * their own rows (a range run again, rows beyond the slot's row buffers, EM resolutions, an error), out[3] how often the
+ * result arrays had to grow while rows were crossing into them, which waits for those rows.  out[1] + out[2] counts the
+ * ranges finished so far (all of them after afq_collect).  Diagnostics only. */
+void afq_range_pipeline_counts(const afq_ctx* ctx, uint64_t out[4]);
 
 /* Brings the HIP runtime up on `device` (first-call initialisation) - a host can call it from a side thread while it parses its
    inputs.  Returns 0 or AFQ_ERR_NO_DEVICE. */
