@@ -592,13 +592,15 @@ __device__ __forceinline__ uint32_t em_from_pairs(uint32_t p0, uint32_t p1, uint
 
 // One wave, n <= kHtKeys.  Slot = one 64-bit word (umi:32 | gene:20 | reads:12) holding the UMI and its first
 // gene's counter - a UMI seen with one gene, the common case, costs one CAS plus one add per further read - and
-// kHtPairs-1 more (gene | reads) counters.  The lane whose CAS claims a slot owns that UMI and resolves it.
-// On success col[h] holds the column of the UMI whose slot the lane claimed in round h (kNoCol: none) and true is returned.
+// kHtPairs-1 more (gene | reads) counters.  The lane whose CAS claims a slot owns that UMI; the owners are then numbered
+// 0 .. n_own-1 and resolved 64 to a round.
+// On success n_own is the bucket's number of UMIs (wave-uniform), col[r] holds the column of owner 64 r + lane (kNoCol: none,
+// and in every round from ceil(n_own / 64) on) and true is returned.
 constexpr uint32_t kHtRounds = kHtKeys / 64;
 __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__ src, uint32_t n, const ResolveCfg& rc,
                                                     unsigned long long* s_slot, uint32_t* s_pair, uint32_t* s_ovf,
                                                     uint32_t* s_flag, uint32_t* s_novf, DevStatus* st,
-                                                    uint32_t cell, uint32_t (&col_out)[kHtRounds], bool em, const EmStage& es) {
+                                                    uint32_t cell, uint32_t (&col_out)[kHtRounds], uint32_t& n_own, bool em, const EmStage& es) {
     constexpr uint32_t E = kHtRounds;
     constexpr unsigned long long kEmpty64 = ~0ull;
     const uint32_t lane = threadIdx.x;
@@ -616,63 +618,81 @@ __device__ __forceinline__ bool resolve_bucket_hash(const uint64_t* __restrict__
         if (lane == 0) *s_novf = 0;
     }
     __syncthreads();
+    // What makes the table give up is kept out of the insert's branches (a flag carried through them costs scalar mask
+    // arithmetic at every join): a UMI that does not fit the slot word (or would read as "empty") is looked for first, the
+    // parked keys are counted past kHtOvf and looked at afterwards.
     bool bad = false;
+#pragma unroll
+    for (uint32_t h = 0; h < E; ++h) bad = bad || (key[h] >> kGeneBits) >= 0xFFFFFFFFull;   // (a key past n is 0)
+    if (__any(bad)) return false;
+    static_assert(kHtPairs == 3, "the insert below spells out the two counters beside the slot word");
     uint32_t own_slot[E];
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) {
         own_slot[h] = kNoCol;
         if (h * 64 >= n) break;
         if (h * 64 + lane < n) {
-            const uint64_t u64 = key[h] >> kGeneBits;
-            const uint32_t gene = (uint32_t)key[h] & kGeneMask;
-            if (u64 >= 0xFFFFFFFFull) bad = true;  // does not fit the slot word (or would read as "empty")
+            const uint32_t umi = (uint32_t)(key[h] >> kGeneBits), gene = (uint32_t)key[h] & kGeneMask;
+            const uint32_t mine32 = (gene << 12) | 1u;
+            const unsigned long long mine = ((unsigned long long)umi << 32) | mine32;
+            uint32_t slot = ht_slot(umi, cap);
+            // the probe loop only finds the UMI's slot (one exit: the slot was empty - now claimed - or holds this UMI;
+            // an occupied slot's UMI word is never 0xFFFFFFFF); what the hit means is sorted out after it
+            unsigned long long old;
+            for (;;) {
+                old = atomicCAS(&s_slot[slot], kEmpty64, mine);
+                const uint32_t ou = (uint32_t)(old >> 32);
+                if (ou == umi || ou == 0xFFFFFFFFu) break;
+                slot = slot + 1 == cap ? 0u : slot + 1;
+            }
+            uint32_t ou = (uint32_t)(old >> 32);
+            asm volatile("" : "+v"(ou));   // (nothing is emitted: without it "claimed" is worked out in every trip of the loop and carried out of it as a mask, four instructions a trip)
+            if (ou == 0xFFFFFFFFu) own_slot[h] = slot;
+            else if ((((uint32_t)old) >> 12) == gene) atomicAdd(&s_slot[slot], 1ull);
             else {
-                const uint32_t umi = (uint32_t)u64;
-                const unsigned long long mine = ((unsigned long long)umi << 32) | (gene << 12) | 1u;
-                uint32_t slot = ht_slot(umi, cap);
-                // the probe loop only finds the UMI's slot (one exit: the slot was empty - now claimed - or holds this UMI;
-                // an occupied slot's UMI word is never 0xFFFFFFFF); what the hit means is sorted out after it
-                unsigned long long old;
-                for (;;) {
-                    old = atomicCAS(&s_slot[slot], kEmpty64, mine);
-                    const uint32_t ou = (uint32_t)(old >> 32);
-                    if (ou == umi || ou == 0xFFFFFFFFu) break;
-                    slot = slot + 1 == cap ? 0u : slot + 1;
-                }
-                bool done = true;
-                if ((uint32_t)(old >> 32) == 0xFFFFFFFFu) own_slot[h] = slot;
-                else if ((((uint32_t)old) >> 12) == gene) atomicAdd(&s_slot[slot], 1ull);
-                else done = false;
-                if (!done) {
-                    uint32_t* pr = s_pair + slot * (kHtPairs - 1);
-#pragma unroll
-                    for (uint32_t q = 0; q < kHtPairs - 1; ++q) {
-                        if (!done) {
-                            const uint32_t old = atomicCAS(&pr[q], 0u, (gene << 12) | 1u);
-                            if (old == 0u) done = true;
-                            else if ((old >> 12) == gene) { atomicAdd(&pr[q], 1u); done = true; }
+                uint32_t* pr = s_pair + slot * (kHtPairs - 1);
+                const uint32_t o1 = atomicCAS(&pr[0], 0u, mine32);
+                if (o1 != 0u) {
+                    if ((o1 >> 12) == gene) atomicAdd(&pr[0], 1u);
+                    else {
+                        const uint32_t o2 = atomicCAS(&pr[1], 0u, mine32);
+                        if (o2 != 0u) {
+                            if ((o2 >> 12) == gene) atomicAdd(&pr[1], 1u);
+                            else {  // the UMI's counters are taken by other genes (and this gene can never get one)
+                                const uint32_t k = atomicAdd(s_novf, 1u);
+                                if (k < kHtOvf) { s_ovf[k] = (slot << kGeneBits) | gene; atomicOr(&s_flag[slot >> 5], 1u << (slot & 31)); }   // (the UMI is the slot's)
+                            }
                         }
                     }
-                }
-                if (!done) {  // the UMI's counters are taken by other genes (and this gene can never get one)
-                    const uint32_t k = atomicAdd(s_novf, 1u);
-                    if (k < kHtOvf) { s_ovf[k] = (slot << kGeneBits) | gene; atomicOr(&s_flag[slot >> 5], 1u << (slot & 31)); }   // (the UMI is the slot's)
-                    else bad = true;
                 }
             }
         }
     }
-    if (__any(bad)) return false;
     __syncthreads();
     const uint32_t novf = *s_novf;
+    if (novf > kHtOvf) return false;   // more parked keys than the list holds
+    // The owners are spread thinly over the key rounds (a bucket has about 0.4 UMIs per key), so the rule rounds run over the
+    // owners instead: owner k - counted over the key rounds, lane order within one - leaves its slot number in the UMI half of
+    // slot word k, which nobody reads once every key is inserted (k < n_own <= n < cap), and lane l of rule round r takes owner
+    // 64 r + l from there.  No LDS of its own: the headline instance keeps its eight workgroups per SIMD.
+    uint32_t* s_own = reinterpret_cast<uint32_t*>(s_slot) + 1;
+    n_own = 0;
+#pragma unroll
+    for (uint32_t h = 0; h < E; ++h) {
+        if (h * 64 >= n) break;
+        const uint64_t mo = __ballot(own_slot[h] != kNoCol);
+        if (own_slot[h] != kNoCol) s_own[2 * (n_own + __builtin_amdgcn_mbcnt_hi((uint32_t)(mo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mo, 0u)))] = own_slot[h];
+        n_own += (uint32_t)__popcll(mo);
+    }
+    __syncthreads();
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) col_out[h] = kNoCol;
 #pragma unroll
     for (uint32_t h = 0; h < E; ++h) {
-        if (h * 64 >= n) break;
+        if (h * 64 >= n_own) break;
         uint32_t col = kNoCol;
-        const uint32_t slot = own_slot[h];
-        if (slot != kNoCol) {
+        if (h * 64 + lane < n_own) {
+            const uint32_t slot = s_own[2 * (h * 64 + lane)];
             const uint32_t p0 = (uint32_t)s_slot[slot];
             const uint32_t p1 = s_pair[slot * (kHtPairs - 1)], p2 = s_pair[slot * (kHtPairs - 1) + 1];
             if (!novf || !((s_flag[slot >> 5] >> (slot & 31)) & 1u)) col = em ? em_from_pairs(p0, p1, p2, rc, es) : col_from_pairs(p0, p1, p2, rc);
@@ -895,6 +915,7 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
     const uint32_t bmode = d.mode_single & 0xFFu;
     const uint64_t* src = keys1 + d.src_off;
     uint32_t col[kHtRounds];
+    uint32_t n_emit = d.n;   // the rounds that can hold a column cover 0 .. n_emit-1: the keys (two tables), the UMIs (one)
     bool ok = !(d.mode_single >> 8) && d.n <= kHtKeys && !rc.pa && !rc.divert;
     if constexpr (MULTI) {   // a batch of many-gene reads: cr-like buckets through the two-table path
         ok = ok && bmode == kModeCrLike && resolve_bucket_hash2(src, d.n, rc, s_raw, st, d.cell, col);
@@ -909,7 +930,7 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
             uint32_t* s_hlab = s_flag + kHtCap / 32 + 2;   // EM only: staged label words / descriptors of this bucket
             if (EM && threadIdx.x < 6) s_misc[threadIdx.x] = 0;
             const EmStage es{s_hlab, s_hlab + kHtKeys, &s_misc[2]};
-            ok = resolve_bucket_hash(src, d.n, rc, s_slot, s_pair, s_ovf, s_flag, s_flag + kHtCap / 32, st, d.cell, col, em, es);
+            ok = resolve_bucket_hash(src, d.n, rc, s_slot, s_pair, s_ovf, s_flag, s_flag + kHtCap / 32, st, d.cell, col, n_emit, em, es);
             if (EM && ok && s_misc[3]) flush_bucket_labels<kResolveNT>(d, la, es.lab, es.ldesc, s_misc);
         }
     }
@@ -920,7 +941,10 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
     uint64_t m[kHtRounds];
     uint32_t nc = 0;
 #pragma unroll
-    for (uint32_t h = 0; h < kHtRounds; ++h) { m[h] = __ballot(col[h] != kNoCol); nc += (uint32_t)__popcll(m[h]); }
+    for (uint32_t h = 0; h < kHtRounds; ++h) {
+        if (!MULTI && h * 64 >= n_emit) break;
+        m[h] = __ballot(col[h] != kNoCol); nc += (uint32_t)__popcll(m[h]);
+    }
     if (nc == 0) return;
     uint32_t at = 0;
     if (threadIdx.x == 0) at = atomicAdd(&cell_ncols[d.cell], nc);
@@ -929,6 +953,7 @@ __global__ __launch_bounds__(kResolveNT) void k_resolve_hash(DescSrc ds, uint32_
     const uint64_t below = (1ull << threadIdx.x) - 1;
 #pragma unroll
     for (uint32_t h = 0; h < kHtRounds; ++h) {
+        if (!MULTI && h * 64 >= n_emit) break;
         if (col[h] != kNoCol) out[__popcll(m[h] & below)] = col[h];
         out += __popcll(m[h]);
     }
