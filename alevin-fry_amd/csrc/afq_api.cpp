@@ -599,25 +599,29 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     std::vector<uint32_t> multi, slab_prefix, pug_cells, hist_cells;
     std::vector<uint64_t> rd_off(n, 0);
     uint64_t n_pug_reads = 0, pug_words = 0;  // pug_words: scratch of the largest parsimony cell
-    const bool par = (c->widen || c->all_aligned) && decode_par_supported(g.bc_bytes, g.umi_bytes);
+    const bool em = g.resolution == AFQ_RES_CR_LIKE_EM || g.resolution == AFQ_RES_PARSIMONY_EM || g.resolution == AFQ_RES_PARSIMONY_GENE_EM;
+    const bool gene_level = g.resolution == AFQ_RES_PARSIMONY_GENE || g.resolution == AFQ_RES_PARSIMONY_GENE_EM;
+    // walk-free decode wants dword-aligned chunks (the fields are 4 or 8 bytes here: narrower ones are widened): the widened copy
+    // is, the caller's chunks may not be
+    const bool par = c->widen || c->all_aligned;
     uint64_t key_off = 0, n_buckets = 0, n_tiles = 0, n_slabs = 0, k1_slots = 0;
     uint64_t n_dtiles_lo = 0, n_dtiles_hi = 0;   // the scattering decoder's tiles, per instance (k_slab_setup writes the table)
     uint32_t max_lg_nb = 0;
     uint32_t slab_cap = slab_capacity();
-    {   // reads of many genes each (the range averages two or more alignment words per record): all keys of a UMI share a bucket, so
-        // the buckets' sizes spread and 384-slot slabs overflow in a tenth of the cells (k_fix_slabs: 3.5 of 41 ms on the tail
-        // model); such ranges get 512-slot slabs (AFQ_TEST_SLAB_CAP still overrides)
-        uint64_t words = 0, recs = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t ci = r.c0 + i;
-            const uint64_t nb = c->widen ? c->w_nbytes[ci] : c->hdr[2 * ci], nr = c->hdr[2 * ci + 1];
-            words += (nb - 8ull - nr * H) / 4; recs += nr;
-        }
-        if (!test_hook("SLAB_CAP") && resolve_sort_only(words, recs)) slab_cap = std::max<uint32_t>(slab_cap, 512u);
+    uint64_t ref_words = 0, nrec_total = 0;   // the range's alignment words and records: their ratio picks the decoder and the resolve path
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t ci = r.c0 + i;
+        const uint64_t nb = c->widen ? c->w_nbytes[ci] : c->hdr[2 * ci], nr = c->hdr[2 * ci + 1];
+        ref_words += (nb - 8ull - nr * H) / 4; nrec_total += nr;
     }
+    const bool sort_only = resolve_sort_only(ref_words, nrec_total);
+    const bool short_records = decode_short_records(ref_words, nrec_total);   // (reads AFQ_TEST_DECODE: once per range)
+    // reads of many genes each (the range averages two or more alignment words per record): all keys of a UMI share a bucket, so
+    // the buckets' sizes spread and 384-slot slabs overflow in a tenth of the cells (k_fix_slabs: 3.5 of 41 ms on the tail
+    // model); such ranges get 512-slot slabs (AFQ_TEST_SLAB_CAP still overrides)
+    if (!test_hook("SLAB_CAP") && sort_only) slab_cap = std::max<uint32_t>(slab_cap, 512u);
     if (par) slab_prefix.reserve(n + 1);
     // bucket -> cell and scatter tile -> (cell, tile) are written on the device from the cells' plans (k_fill_tables)
-    uint64_t nrec_total = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t ci = r.c0 + i;
         CellMeta& m = B.meta[i];
@@ -657,7 +661,6 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
             pug_cells.push_back(i); rd_off[i] = n_pug_reads; n_pug_reads += m.nrec;
             pug_words = std::max<uint64_t>(pug_words, pug_scratch_words(m.nrec, m.n_ref, mode_pug_gene(m.mode)));
         }
-        nrec_total += m.nrec;
         if (par) {
             const uint64_t ns = ((uint64_t)(m.nbytes >> 2) + kSlabWords - 1) / kSlabWords;
             slab_prefix.push_back((uint32_t)n_slabs);
@@ -674,8 +677,9 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     if (n_buckets >= 0xFFFFFFF0ull || n_tiles >= 0xFFFFFFF0ull || key_off >= (1ull << 40))
         return fail(c, AFQ_ERR_UNSUPPORTED, "batch too large for 32-bit bucket/tile ids");
     const uint32_t n_multi = (uint32_t)multi.size();
-    // lane-per-record decode of a batch without parsimony cells: the decoder places the keys in their bucket slabs itself (no k_scatter)
-    const bool scat_decode = par && pug_cells.empty() && decode_short_records(key_off - n, nrec_total);
+    const DecodeRoute route = decode_route(par, !pug_cells.empty(), short_records);
+    // the scattering decoder places the keys in their bucket slabs itself: no k_scatter, its spill counts, k_fix_slabs' recount
+    const bool scat_decode = route == DecodeRoute::RecsScatter;
 
     HIP_TRY(c, B.d_meta.ensure(sizeof(CellMeta) * n));
     HIP_TRY(c, B.d_keys0.ensure(8 * key_off));
@@ -690,12 +694,11 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     HIP_TRY(c, B.d_nnz.ensure(4ull * n));
     HIP_TRY(c, B.d_ovf.ensure(sizeof(OverflowEnt) * std::max<uint64_t>(n_buckets, 1)));
     HIP_TRY(c, B.d_div.ensure(4 * std::max<uint64_t>(n_buckets, 1)));
-    const bool em = g.resolution == AFQ_RES_CR_LIKE_EM || g.resolution == AFQ_RES_PARSIMONY_EM || g.resolution == AFQ_RES_PARSIMONY_GENE_EM;
     const uint32_t n_pug = (uint32_t)pug_cells.size();
     const uint32_t n_pug_blocks = std::min<uint32_t>(n_pug, pug_max_blocks());
     // largest cells first: the persistent workgroups take them in list order, so the long ones do not end up as the tail
     std::stable_sort(pug_cells.begin(), pug_cells.end(), [&](uint32_t a, uint32_t b) { return B.meta[a].nrec > B.meta[b].nrec; });
-    if (n_pug && !par) return fail(c, AFQ_ERR_UNSUPPORTED, "device parsimony needs dword-aligned chunk offsets");
+    // (a parsimony batch is walk-free: plan_ranges widens one whose chunks sit at odd offsets)
     // Parsimony cells go through the phase kernels of afq_pug2.hip (partition-parallel) unless their labels are
     // gene-level, their UMI field is wider than 4 bytes or they hold 2^22 reads or more: those - and the cells the phase kernels
     // hand back - are resolved by the one-workgroup kernel of afq_pug.hip.  AFQ_TEST_PUG_ROUTE=mono sends every cell there (tests).
@@ -707,7 +710,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     const uint32_t p2_tile = kP2TileHost;
     {
         const char* route = test_hook("PUG_ROUTE");
-        const bool p2_ok = n_pug && g.umi_bytes == 4 && !(g.resolution == AFQ_RES_PARSIMONY_GENE || g.resolution == AFQ_RES_PARSIMONY_GENE_EM) &&
+        const bool p2_ok = n_pug && g.umi_bytes == 4 && !gene_level &&
                            !(route && !std::strcmp(route, "mono"));
         for (uint32_t ci : pug_cells) {   // (largest first)
             const CellMeta& m = B.meta[ci];
@@ -869,12 +872,12 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     DecodeArgs da{in_bytes, in_n, B.d_meta.as<CellMeta>(), n, c->d_t2g.as<uint32_t>(), c->ref_count,
                   g.num_genes, B.d_keys0.as<uint64_t>(), B.d_cell_nkeys.as<uint32_t>(),
                   B.d_bc.as<uint64_t>(), B.d_status.as<DevStatus>(),
-                  par ? B.d_chk.as<CellChk>() : nullptr, B.d_slab_prefix.as<uint32_t>(), B.d_slab_cell.as<uint32_t>(),
+                  route, par ? B.d_chk.as<CellChk>() : nullptr, B.d_slab_prefix.as<uint32_t>(), B.d_slab_cell.as<uint32_t>(),
                   B.d_cell_bc.as<uint64_t>(),
                   (uint32_t)n_slabs,
                   n_pug ? PugOut{B.d_rd_h.as<uint64_t>(), B.d_rd_u.as<uint64_t>(), B.d_rd_o.as<uint32_t>(), B.d_rd_off.as<uint64_t>(), label_salt(hash_try), label_mask(hash_try)}
                         : PugOut{nullptr, nullptr, nullptr, nullptr, 0, ~0ull},
-                  g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u, decode_short_records(key_off - n, nrec_total), par ? B.d_fix.as<uint32_t>() : nullptr};
+                  g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u, par ? B.d_fix.as<uint32_t>() : nullptr};
     if (scat_decode) {
         da.dtile = B.d_dtile.as<uint2>(); da.n_dtiles_lo = (uint32_t)n_dtiles_lo; da.n_dtiles_hi = (uint32_t)n_dtiles_hi;
         da.keys1 = B.d_keys1.as<uint64_t>(); da.cursor = B.d_bucket_cnt.as<uint32_t>(); da.slab_ovf = B.d_slab_ovf.as<uint32_t>();
@@ -884,7 +887,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         tc.seg(K_DECODE_PAR);
         if (launch_decode_par(s, da, g.bc_bytes, g.umi_bytes)) { tc.end(); return fail(c, AFQ_ERR_INVALID_ARG, "bad field widths"); }
     }
-    {   // sequential walk: the whole decode for unaligned layouts, the verified fix-up otherwise
+    {   // sequential walk: the whole decode on DecodeRoute::Walk, the verified fix-up otherwise
         tc.seg(K_DECODE);
         if (launch_decode(s, da, g.bc_bytes, g.umi_bytes)) { tc.end(); return fail(c, AFQ_ERR_INVALID_ARG, "bad field widths"); }
     }
@@ -896,7 +899,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
                    (uint32_t)n_buckets, n_multi, (uint32_t)n_tiles, B.d_hist_cells.as<uint32_t>(),
                    (uint32_t)hist_cells.size(), g.usa_mode, g.num_rows,
                    (g.usa_mode && g.sa_model == AFQ_SA_PREFER_AMBIG) ? 1u : 0u, max_lg_nb, B.d_slab_ovf.as<uint32_t>(),
-                   resolve_sort_only(key_off - n, nrec_total), g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u,
+                   sort_only ? 1u : 0u, g.resolution == AFQ_RES_TRIVIAL ? 1u : 0u,
                    test_hook_is("RESOLVE_DIVERT", "all") ? 1u : 0u, scat_decode ? 1u : 0u, scat_decode ? B.d_spill.as<uint32_t>() : nullptr};
     if (n_multi) {
         if (!scat_decode) { tc.seg(K_SCATTER); launch_scatter(s, ra); }
@@ -955,7 +958,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
             // 25.1 -> 16.5 ms per step, on the plain one 5.6 -> 7.3 (profiles/history/run_r04ao.sh).  (Until round 4 such labels were
             // resolved by the vertex's lane alone, in scratch memory.)
             // The range's own figure decides, the one that picks its decoder: two or more alignment words per record.
-            p2.lone_coop = [&] { const char* e = test_hook("P2_LONE_COOP"); return e && e[0] >= '1' && e[0] <= '2' ? (uint32_t)(e[0] - '0') : (key_off - n >= 2 * nrec_total ? 2u : 1u); }();
+            p2.lone_coop = [&] { const char* e = test_hook("P2_LONE_COOP"); return e && e[0] >= '1' && e[0] <= '2' ? (uint32_t)(e[0] - '0') : (sort_only ? 2u : 1u); }();
             p2.part_cap = kP2PartCap;
             if (const char* e = test_hook("P2_PART_CAP")) p2.part_cap = (uint32_t)std::max(1, std::atoi(e));   // tests: force cells back to the one-workgroup kernel
             p2.ref_count = c->ref_count; p2.num_genes = g.num_genes; p2.usa = g.usa_mode; p2.num_rows = g.num_rows; p2.em = em ? 1u : 0u;
@@ -976,7 +979,7 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
         pa.alt = B.d_alt.as<uint32_t>(); pa.st = ra.st; pa.ref_count = c->ref_count; pa.num_genes = g.num_genes; pa.usa = g.usa_mode;
         pa.num_rows = g.num_rows; pa.em = em ? 1u : 0u; pa.exact_umi = g.pug_exact_umi; pa.large_thresh = g.large_graph_thresh; pa.umi32 = g.umi_bytes == 4 ? 1u : 0u;
         pa.hw = 1 + g.bc_bytes / 4 + g.umi_bytes / 4; pa.umi_pairs = std::min<uint32_t>(g.umi_len ? g.umi_len : g.umi_bytes * 4, 22);
-        pa.gene_level = (g.resolution == AFQ_RES_PARSIMONY_GENE || g.resolution == AFQ_RES_PARSIMONY_GENE_EM) ? 1u : 0u;
+        pa.gene_level = gene_level ? 1u : 0u;
         pa.force_global_route = test_hook("PUG_GLOBAL_ROUTE") ? 1u : 0u;
         // The one-workgroup kernel is 0.36 ms of a range even when its list is empty and whatever its grid (its private segment -
         // 138 spilled registers per lane - is set up per dispatch: 1.1 ms of a configs[2] step that hands no cell back).  It is

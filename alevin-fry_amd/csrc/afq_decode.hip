@@ -3,7 +3,8 @@
 // (libradicl's Chunk<R> reader as used at src/quant.rs:733-757, the per-read gene projection of
 // src/pugutils.rs:774-781 / src/quant.rs:469-530):
 //   k_gather_headers  chunk headers of a device-resident input
-//   k_decode          sequential walk, any field width / alignment; also the re-decode of cells whose proof failed
+//   k_decode          sequential walk, 4/8-byte fields at any chunk alignment; also the re-decode of cells whose proof failed
+//   k_widen / k_strip_aln  chunks of 1/2-byte fields (or with alignment positions) rewritten with 4/8-byte fields, ahead of every decoder
 //   k_slab_setup      slab -> cell table, barcode of every cell
 //   k_decode_par      walk-free decode, one lane per record (general; emits the parsimony per-read records)
 //   k_decode_keys     walk-free decode, one lane per dword (flat in record length)
@@ -43,6 +44,47 @@ __global__ void k_gather_headers(const uint8_t* __restrict__ bytes, size_t n_byt
 }
 
 // ---------------------------------------------------------------------------
+// What every decoder computes per record, written once.
+// A record's distinct genes in first-occurrence order, one pass of O(na^2): the decoders keep eight genes in registers and come
+// here for the rare record that names more.  ref(j): the record's j-th alignment word (orientation bit off); bad(code): called
+// for every word that names no reference (kErrRefRange) or no gene (kErrGeneRange); f(gene): called per distinct gene.
+template <class Ref, class Bad, class F>
+__device__ __forceinline__ void for_each_first_gene(uint32_t na, Ref&& ref, const uint32_t* __restrict__ t2g, uint32_t ref_count,
+                                                    uint32_t num_genes, Bad&& bad, F&& f) {
+    for (uint32_t j = 0; j < na; ++j) {
+        const uint32_t tj = ref(j);
+        if (tj >= ref_count) { bad(kErrRefRange); continue; }
+        const uint32_t gj = t2g[tj];
+        if (gj >= num_genes) { bad(kErrGeneRange); continue; }
+        bool first = true;
+        for (uint32_t q = 0; q < j && first; ++q) {
+            const uint32_t tq = ref(q);
+            if (tq < ref_count && t2g[tq] == gj) first = false;
+        }
+        if (first) f(gj);
+    }
+}
+// Label key of a parsimony read at transcript level: the hash of its ref list (afq_common.h label_key: one or two refs sit in the key).
+template <class Ref, class Bad>
+__device__ __forceinline__ uint64_t txp_label_key(uint32_t na, Ref&& ref, uint32_t ref_count, const PugOut& pug, Bad&& bad) {
+    uint64_t h = label_hash_init(na) ^ pug.salt;
+    uint32_t t0 = 0, t1 = 0;
+    for (uint32_t j = 0; j < na; ++j) {
+        const uint32_t t = ref(j);
+        if (t >= ref_count) bad(kErrRefRange);
+        h = label_hash_step(h, t);
+        if (j == 0) t0 = t;
+        if (j == 1) t1 = t;
+    }
+    return label_key(h & pug.mask, na, t0, t1);
+}
+// ... and at gene level: sum = the gene_set_hash_term(gene ^ salt) of the read's n distinct genes, added up (order-independent);
+// g0, g1: its first two genes (read only when n <= 2).
+__device__ __forceinline__ uint64_t gene_set_label_key(uint64_t sum, uint32_t n, uint32_t g0, uint32_t g1, const PugOut& pug) {
+    return label_key((sum ^ (uint64_t)n * kHashMul) & pug.mask, n, g0, g1);
+}
+
+// ---------------------------------------------------------------------------
 // k_decode: one wave per chunk.  The record stream has no self-synchronisation
 // (a record's length is its own na field), so the wave walks it: each 256-byte
 // window is loaded coalesced (one dword per lane), a scalar loop follows
@@ -59,7 +101,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
                                                uint64_t* __restrict__ bc_out, DevStatus* st,
                                                const CellChk* __restrict__ chk, PugOut pug, uint32_t* __restrict__ slab_ovf) {
     constexpr uint32_t HDR = 4 + BW + UW;
-    constexpr bool AL = (BW % 4 == 0) && (UW % 4 == 0);
+    static_assert(BW % 4 == 0 && UW % 4 == 0, "narrower fields are widened first (k_widen)");
     const uint32_t lane = lane_id();
     // plain mode: wave w takes cell w.  Fix-up mode (chk: after a walk-free decoder): the workgroup first takes the last step of
     // the walk-free proof for its 256 cells, a thread each (the accumulated candidate count and sizes against
@@ -98,7 +140,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
     const uint32_t mis = (uint32_t)(m.chunk_off - abase);
     uint64_t pos = (uint64_t)mis + 8;                    // next record start, bytes from abase
     const uint64_t end = (uint64_t)mis + m.nbytes;       // chunk end, bytes from abase
-    const bool al_chunk = AL && mis == 0;
+    const bool al_chunk = mis == 0;
     uint32_t nk_total = 0, rec_seen = 0;
     bool bad = false;
 
@@ -143,6 +185,10 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
         bool ovf = false, pug_rec = false;
         uint64_t umi = 0, lhash = 0;
         const uint8_t* rp = nullptr;
+        auto refw = [&](uint32_t j) -> uint32_t {  // j-th alignment word of this lane's record
+            return ld_u32(rp + 4 * j, (((uintptr_t)rp) & 3) == 0) & 0x7FFFFFFFu;
+        };
+        auto report = [&](uint32_t code) { set_err(st, code, cell); };
         if (is_start && !bad) {
             const uint32_t sub = al_chunk ? 0u : (uint32_t)((sub0 >> lane) & 1ull) | ((uint32_t)((sub1 >> lane) & 1ull) << 1);
             const uint64_t roff = abase + (w << 8) + lane * 4 + sub;
@@ -152,22 +198,13 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
             if (roff == m.chunk_off + 8) bc_out[cell] = ld_le<BW>(rec + 4);
             if (UW == 8 && (umi >> kUmiBits)) { set_err(st, kErrUmiWide, cell); na = 0; }
             rp = rec + HDR;
-            const bool ral = ((((uintptr_t)rp) & 3) == 0);
             if (mode_is_pug(m.mode)) { rec_dw = (uint32_t)((roff - m.chunk_off) >> 2); pug_rec = true; }
             if (mode_is_pug(m.mode) && !mode_pug_gene(m.mode)) {  // txp-level PUG: hash of the ref list
-                lhash = label_hash_init(na) ^ pug.salt;
-                uint32_t t01[2] = {0, 0};
-                for (uint32_t j = 0; j < na; ++j) {
-                    const uint32_t t = ld_u32(rp + 4 * j, ral) & 0x7FFFFFFFu;
-                    if (t >= ref_count) set_err(st, kErrRefRange, cell);
-                    lhash = label_hash_step(lhash, t);
-                    if (j < 2) t01[j] = t;
-                }
-                lhash = label_key(lhash & pug.mask, na, t01[0], t01[1]);
+                lhash = txp_label_key(na, refw, ref_count, pug, report);
                 na = 0;
             }
             for (uint32_t j = 0; j < na; ++j) {
-                uint32_t t = ld_u32(rp + 4 * j, ral) & 0x7FFFFFFFu;
+                uint32_t t = refw(j);
                 if (t >= ref_count) { set_err(st, kErrRefRange, cell); continue; }
                 uint32_t gid = t2g[t];
                 if (gid >= num_genes) { set_err(st, kErrGeneRange, cell); continue; }
@@ -185,27 +222,17 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
             kcnt = k;
             if (ovf) {  // > 8 distinct genes: count by first occurrence, O(na^2), rare
                 kcnt = 0;
-                for (uint32_t j = 0; j < na; ++j) {
-                    uint32_t tj = ld_u32(rp + 4 * j, ral) & 0x7FFFFFFFu;
-                    if (tj >= ref_count) continue;
-                    uint32_t gj = t2g[tj];
-                    if (gj >= num_genes) continue;
-                    bool first = true;
-                    for (uint32_t i = 0; i < j && first; ++i) {
-                        uint32_t ti = ld_u32(rp + 4 * i, ral) & 0x7FFFFFFFu;
-                        if (ti < ref_count && t2g[ti] == gj) first = false;
-                    }
-                    kcnt += first;
-                    if (first && mode_pug_gene(m.mode)) lhash += gene_set_hash_term(gj ^ (uint32_t)pug.salt);
-                }
+                for_each_first_gene(na, refw, t2g, ref_count, num_genes, report, [&](uint32_t gj) {
+                    ++kcnt;
+                    if (mode_pug_gene(m.mode)) lhash += gene_set_hash_term(gj ^ (uint32_t)pug.salt);
+                });
             }
             if (mode_pug_gene(m.mode)) {  // gene-level PUG: order-independent hash of the read's gene set
                 if (!ovf) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i) if ((uint32_t)i < k) lhash += gene_set_hash_term(g[i] ^ (uint32_t)pug.salt);
                 }
-                lhash ^= (uint64_t)kcnt * kHashMul;
-                lhash = label_key(lhash & pug.mask, kcnt, g[0], g[1]);  // (kcnt <= 2 implies !ovf: g[0], g[1] are the read's genes)
+                lhash = gene_set_label_key(lhash, kcnt, g[0], g[1], pug);  // (kcnt <= 2 implies !ovf: g[0], g[1] are the read's genes)
             }
         }
         if (m.mode == kModeTrivial && kcnt != 1) kcnt = 0;  // multi-gene reads are discarded (pugutils.rs:870-891)
@@ -229,20 +256,8 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t* __restrict__ byte
                     for (int i = 0; i < 8; ++i)
                         if ((uint32_t)i < k) dst[o0 + i] = (umi << kGeneBits) | g[i];
                 } else {
-                    const bool ral = ((((uintptr_t)rp) & 3) == 0);
-                    uint32_t o = o0;
-                    for (uint32_t j = 0; j < na; ++j) {
-                        uint32_t tj = ld_u32(rp + 4 * j, ral) & 0x7FFFFFFFu;
-                        if (tj >= ref_count) continue;
-                        uint32_t gj = t2g[tj];
-                        if (gj >= num_genes) continue;
-                        bool first = true;
-                        for (uint32_t i = 0; i < j && first; ++i) {
-                            uint32_t ti = ld_u32(rp + 4 * i, ral) & 0x7FFFFFFFu;
-                            if (ti < ref_count && t2g[ti] == gj) first = false;
-                        }
-                        if (first) dst[o++] = (umi << kGeneBits) | gj;
-                    }
+                    uint32_t o = o0;   // (the count above has reported the words that name nothing)
+                    for_each_first_gene(na, refw, t2g, ref_count, num_genes, [](uint32_t) {}, [&](uint32_t gj) { dst[o++] = (umi << kGeneBits) | gj; });
                 }
             } else bad = true;
         }
@@ -515,7 +530,7 @@ constexpr uint32_t kHalo = 64;
 constexpr uint32_t kDecodeCols = AFQ_DECODE_COLS;
 constexpr uint32_t kStage = kSlabWords + kHalo;  // 320 dwords = 5 per lane
 
-template <int BW, int UW, bool PUG>
+template <int BW, int UW>
 __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict__ bytes,
                                                    const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                    const uint32_t* __restrict__ slab_prefix,
@@ -668,20 +683,11 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
             }
             // request the next slab's dwords while the gathers above are in flight
             if (!prefetched && same_next) { issue_slab_loads(s0 + kSlabWords); prefetched = true; }
-            const bool pug_rec = PUG && act && mode_is_pug(m.mode);
+            const bool pug_rec = act && mode_is_pug(m.mode);
             uint64_t lhash = 0;
             const bool pug_gene = pug_rec && mode_pug_gene(m.mode);
             if (pug_rec && !pug_gene) {  // txp-level PUG: hash of the ref list
-                lhash = label_hash_init(na) ^ pug.salt;
-                uint32_t t0 = 0, t1 = 0;
-                for (uint32_t j = 0; j < na; ++j) {
-                    const uint32_t t = refw(j);
-                    if (t >= ref_count) fail = true;
-                    lhash = label_hash_step(lhash, t);
-                    if (j == 0) t0 = t;
-                    if (j == 1) t1 = t;
-                }
-                lhash = label_key(lhash & pug.mask, na, t0, t1);
+                lhash = txp_label_key(na, refw, ref_count, pug, [&](uint32_t) { fail = true; });
             }
             if (act && na && (!pug_rec || pug_gene)) {
                 if (ok0) {
@@ -706,27 +712,17 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
                 kcnt = k;
                 if (ovf) {  // > 8 distinct genes: first-occurrence count, O(na^2), rare
                     kcnt = 0;
-                    for (uint32_t j = 0; j < na; ++j) {
-                        const uint32_t tj = refw(j);
-                        if (tj >= ref_count) continue;
-                        const uint32_t gj = t2g[tj];
-                        if (gj >= num_genes) continue;
-                        bool first = true;
-                        for (uint32_t q = 0; q < j && first; ++q) {
-                            const uint32_t tq = refw(q);
-                            if (tq < ref_count && t2g[tq] == gj) first = false;
-                        }
-                        kcnt += first;
-                        if (first && pug_gene) lhash += gene_set_hash_term(gj ^ (uint32_t)pug.salt);
-                    }
+                    for_each_first_gene(na, refw, t2g, ref_count, num_genes, [&](uint32_t) { fail = true; }, [&](uint32_t gj) {
+                        ++kcnt;
+                        if (pug_gene) lhash += gene_set_hash_term(gj ^ (uint32_t)pug.salt);
+                    });
                 }
                 if (pug_gene) {  // gene-level PUG: order-independent hash of the read's gene set
                     if (!ovf) {
 #pragma unroll
                         for (int q = 0; q < 8; ++q) if ((uint32_t)q < k) lhash += gene_set_hash_term(g[q] ^ (uint32_t)pug.salt);
                     }
-                    lhash ^= (uint64_t)kcnt * kHashMul;
-                    lhash = label_key(lhash & pug.mask, kcnt, g[0], g[1]);  // (kcnt <= 2 implies !ovf: g[0], g[1] are the read's genes)
+                    lhash = gene_set_label_key(lhash, kcnt, g[0], g[1], pug);  // (kcnt <= 2 implies !ovf: g[0], g[1] are the read's genes)
                 }
             }
             if (m.mode == kModeTrivial && kcnt != 1) kcnt = 0;  // multi-gene reads are discarded (pugutils.rs:870-891)
@@ -737,7 +733,7 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
             if (tot) {
                 if (lane == 0) wbase = atomicAdd(&cell_nkeys[cur_cell], tot);
                 wbase = __builtin_amdgcn_readfirstlane(wbase);
-                if (wbase + tot > ((PUG && mode_is_pug(m.mode)) ? m.nrec : m.n_ref)) { fail = true; kcnt = 0; }
+                if (wbase + tot > (mode_is_pug(m.mode) ? m.nrec : m.n_ref)) { fail = true; kcnt = 0; }
             }
             if (pug_rec) {
                 if (kcnt) {
@@ -752,18 +748,7 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
                     for (int q = 0; q < 8; ++q) if ((uint32_t)q < k) dst[q] = (umi << kGeneBits) | g[q];
                 } else {
                     uint32_t o = 0;
-                    for (uint32_t j = 0; j < na; ++j) {
-                        const uint32_t tj = refw(j);
-                        if (tj >= ref_count) continue;
-                        const uint32_t gj = t2g[tj];
-                        if (gj >= num_genes) continue;
-                        bool first = true;
-                        for (uint32_t q = 0; q < j && first; ++q) {
-                            const uint32_t tq = refw(q);
-                            if (tq < ref_count && t2g[tq] == gj) first = false;
-                        }
-                        if (first) dst[o++] = (umi << kGeneBits) | gj;
-                    }
+                    for_each_first_gene(na, refw, t2g, ref_count, num_genes, [](uint32_t) {}, [&](uint32_t gj) { dst[o++] = (umi << kGeneBits) | gj; });
                 }
             }
         }
@@ -803,7 +788,7 @@ __global__ __launch_bounds__(256, 6) void k_decode_par(const uint8_t* __restrict
 // slots).  The table's cost does not depend on the records' lengths.  The words a record that started before the slab has in
 // front of it are looked up in the table (not inserted: any number of them), and a hit means "named before this slab".
 constexpr uint32_t kHdLg = 9, kHdSlots = 1u << kHdLg;   // 256 alignment words per slab at most: the table is at most half full
-template <int BW, int UW, bool TRIVIAL, bool HD = false>
+template <int BW, int UW, bool TRIVIAL>
 __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restrict__ bytes,
                                                     const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                     const uint32_t* __restrict__ slab_prefix,
@@ -817,7 +802,7 @@ __global__ __launch_bounds__(256, 6) void k_decode_keys(const uint8_t* __restric
     constexpr uint32_t BWW = BW / 4, UWW = UW / 4, HW = 1 + BWW + UWW;
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     __shared__ uint32_t s_stage[4][kStage];
-    static_assert(!(TRIVIAL && HD), "the trivial rule keeps the scan");
+    constexpr bool HD = !TRIVIAL;   // the trivial rule keeps the scan
     __shared__ uint32_t s_gene[4][HD ? 1 : 4 + kSlabWords];   // [4 pad] + gene of every alignment word of the slab (kNone elsewhere)
     __shared__ uint32_t s_first[4][HD ? 1 : kSlabWords];  // dword index of the first alignment word of the dword's record
     __shared__ uint32_t s_tkey[4][HD ? kHdSlots : 1];     // HD: record-of-the-slab << 20 | gene (kNone: free) ...
@@ -1530,6 +1515,8 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
                 const uint32_t pj = il + HW + j;
                 return (pj < kStage ? stage[pj] : W[i + HW + j]) & 0x7FFFFFFFu;
             };
+            // (the shared for_each_first_gene / txp_label_key / gene_set_label_key above say the same; this kernel keeps its own text
+            //  because its instances do not compile to the same instructions through them, and it is the headline's decoder)
             auto for_each_first_gene = [&](auto&& f) {  // distinct genes of the record in first-occurrence order
                 for (uint32_t j = 0; j < na_eff; ++j) {
                     const uint32_t tj = ref_at(j);
@@ -1733,70 +1720,75 @@ void launch_gather_headers(hipStream_t s, const uint8_t* bytes, size_t n_bytes, 
     AFQ_LAUNCH(k_gather_headers, (n_cells + 255) / 256, 256, s, bytes, n_bytes, chunk_off, n_cells, hdr);
 }
 
+// k_decode: the whole decode on DecodeRoute::Walk; after a walk-free decoder its fix-up mode (a workgroup verifies 256 cells' proofs
+// and re-decodes the ones that failed).  Fields of 1 or 2 bytes never get here: run_range widens them first (k_widen).
 template <int BW, int UW>
 static void launch_decode_t(hipStream_t s, const DecodeArgs& a) {
-    const uint32_t grid = a.chk ? (a.n_cells + 255) / 256 : (a.n_cells + 3) / 4;   // (fix-up mode: a workgroup verifies 256 cells' proofs and re-decodes the ones that failed)
-    AFQ_LAUNCH((k_decode<BW, UW>), grid, 256, s, a.bytes, a.n_bytes, a.meta, a.n_cells, a.t2g,
-               a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, a.st, a.chk, a.pug, a.chk ? a.slab_ovf : nullptr);
+    const bool fixup = a.route != DecodeRoute::Walk;
+    AFQ_LAUNCH((k_decode<BW, UW>), fixup ? (a.n_cells + 255) / 256 : (a.n_cells + 3) / 4, 256, s, a.bytes, a.n_bytes, a.meta, a.n_cells, a.t2g,
+               a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, a.st, fixup ? a.chk : nullptr, a.pug,
+               a.route == DecodeRoute::RecsScatter ? a.slab_ovf : nullptr);
 }
 
 int launch_decode(hipStream_t s, const DecodeArgs& a, uint32_t bw, uint32_t uw) {
     if (!a.n_cells) return 0;
 #define AFQ_CASE(B, U) if (bw == B && uw == U) { launch_decode_t<B, U>(s, a); return 0; }
     AFQ_CASE(4, 4) AFQ_CASE(4, 8) AFQ_CASE(8, 4) AFQ_CASE(8, 8)
-    AFQ_CASE(1, 1) AFQ_CASE(1, 2) AFQ_CASE(1, 4) AFQ_CASE(1, 8)
-    AFQ_CASE(2, 1) AFQ_CASE(2, 2) AFQ_CASE(2, 4) AFQ_CASE(2, 8)
-    AFQ_CASE(4, 1) AFQ_CASE(4, 2) AFQ_CASE(8, 1) AFQ_CASE(8, 2)
 #undef AFQ_CASE
     return -1;
 }
 
+// The walk-free decoder of the range's route, after k_slab_setup.
 // k_decode_keys finds a record's first mention of a gene through an LDS hash table (HD); `trivial` keeps the look-back compares and
 // the serial scan of rounds 2-4.  Label-tail workload (configs1_tail, 9.66 GB), the table against the scan: 14.54 -> 9.01 ms per
 // step, the step 35.0 -> 29.4 ms (profiles/history/run_r04ah.sh).
 template <int BW, int UW>
 static int launch_decode_par_t(hipStream_t s, const DecodeArgs& a) {
-    // lane-per-record decode of a batch without parsimony cells is always the scattering instance (run_range passes slab_ovf for it)
-    const bool scat = a.slab_ovf && !a.pug.h && a.short_records;
+    if (a.route == DecodeRoute::Walk) return -1;   // (no walk-free decoder, no slab tables: run_range does not come here)
+    const bool scat = a.route == DecodeRoute::RecsScatter;
     AFQ_LAUNCH((k_slab_setup<BW, UW>), (a.n_cells + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix,
                a.slab_cell, a.cell_bc, scat ? a.dtile : nullptr, a.n_dtiles_lo);
     const uint32_t n_groups = (a.n_slabs + kSlabsPerWave - 1) / kSlabsPerWave;
     const uint32_t n_cols = n_groups < kDecodeCols ? n_groups : kDecodeCols;
     const uint32_t n_waves = n_cols * ((n_groups + n_cols - 1) / n_cols);
-    if (scat) {   // a tile per workgroup; the grid is a multiple of 8 * kDtileRun (the XCD dealing)
+    CellChk* const chk = const_cast<CellChk*>(a.chk);
+    switch (a.route) {
+    case DecodeRoute::Walk: break;   // (returned above)
+    case DecodeRoute::RecsScatter: {   // a tile per workgroup; the grid is a multiple of 8 * kDtileRun (the XCD dealing)
         const DecodeScatter lo{a.dtile, a.n_dtiles_lo, a.keys1, a.cursor, a.slab_ovf, a.spill};
         const DecodeScatter hi{a.dtile + a.n_dtiles_lo, a.n_dtiles_hi, a.keys1, a.cursor, a.slab_ovf, a.spill};
         const uint32_t glo = (a.n_dtiles_lo + 8 * kDtileRun - 1) / (8 * kDtileRun) * (8 * kDtileRun);
         const uint32_t ghi = (a.n_dtiles_hi + 8 * kDtileRun - 1) / (8 * kDtileRun) * (8 * kDtileRun);
         if (a.trivial) {
             if (glo) AFQ_LAUNCH((k_decode_recs<BW, UW, true, false, kDecodeSplitBins>), glo, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, lo);
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug, lo);
             if (ghi) AFQ_LAUNCH((k_decode_recs<BW, UW, true, false, kLdsBins>), ghi, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, hi);
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug, hi);
         } else {
             if (glo) AFQ_LAUNCH((k_decode_recs<BW, UW, false, false, kDecodeSplitBins>), glo, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, lo);
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug, lo);
             if (ghi) AFQ_LAUNCH((k_decode_recs<BW, UW, false, false, kLdsBins>), ghi, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, const_cast<CellChk*>(a.chk), a.pug, hi);
+                                a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug, hi);
         }
-    } else if (a.pug.h && a.short_records && !a.trivial)  // the batch has PUG cells: instances that also emit (label key, umi, offset) per read
+        break;
+    }
+    case DecodeRoute::RecsPug:   // short records, parsimony cells: the instance that also emits (label key, umi, offset) per read
         AFQ_LAUNCH((k_decode_recs<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk), a.pug, NoScatter{});
-    else if (a.pug.h)
-        AFQ_LAUNCH((k_decode_par<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk), a.pug);
-    else if (a.short_records)
-        return -1;   // (unreachable: such a batch takes the scattering instance above)
-    else if (a.trivial)
-        AFQ_LAUNCH((k_decode_keys<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk));
-    else
-        AFQ_LAUNCH((k_decode_keys<BW, UW, false, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
-                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out,
-                   const_cast<CellChk*>(a.chk));
+                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug, NoScatter{});
+        break;
+    case DecodeRoute::Par:
+        AFQ_LAUNCH((k_decode_par<BW, UW>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                   a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk, a.pug);
+        break;
+    case DecodeRoute::Keys:
+        if (a.trivial)
+            AFQ_LAUNCH((k_decode_keys<BW, UW, true>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                       a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk);
+        else
+            AFQ_LAUNCH((k_decode_keys<BW, UW, false>), (n_waves + 3) / 4, 256, s, a.bytes, a.meta, a.n_cells, a.slab_prefix, a.slab_cell,
+                       a.cell_bc, a.n_slabs, a.t2g, a.ref_count, a.num_genes, a.keys0, a.cell_nkeys, a.bc_out, chk);
+        break;
+    }
     return 0;
 }
 

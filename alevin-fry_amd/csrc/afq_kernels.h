@@ -16,6 +16,23 @@
 
 namespace afq {
 
+// The decoder a range takes.  run_range picks it once per range; the launchers switch on it, and who places the keys in their
+// bucket slabs (k_scatter, or the scattering decoder with its spill counts and k_fix_slabs' recount) follows from it.
+enum class DecodeRoute : uint32_t {
+    Walk,          // k_decode alone, the sequential walk: chunks the caller placed at offsets that are no multiple of 4
+    Keys,          // k_decode_keys: walk-free, a lane per dword (records of two or more alignments on average)
+    Par,           // k_decode_par: walk-free, a lane per record; the general decoder of ranges with parsimony cells
+    RecsPug,       // k_decode_recs, the instance that also emits the parsimony reads (short records)
+    RecsScatter,   // k_decode_recs, the scattering instances (short records, no parsimony cell)
+};
+// walk_free: the (widened) chunks are dword aligned; has_pug: the range has parsimony cells; short_records: it averages fewer than two
+// alignment words per record (or AFQ_TEST_DECODE says so).  Every walk-free route ends in k_decode's fix-up mode.
+__host__ inline DecodeRoute decode_route(bool walk_free, bool has_pug, bool short_records) {
+    if (!walk_free) return DecodeRoute::Walk;
+    if (has_pug) return short_records ? DecodeRoute::RecsPug : DecodeRoute::Par;
+    return short_records ? DecodeRoute::RecsScatter : DecodeRoute::Keys;
+}
+
 struct DecodeArgs {
     const uint8_t* bytes;
     size_t n_bytes;
@@ -28,7 +45,8 @@ struct DecodeArgs {
     uint32_t* cell_nkeys;
     uint64_t* bc_out;
     DevStatus* st;
-    // walk-free decode (k_decode_par) + fix-up mode of k_decode; null chk = plain sequential decode
+    DecodeRoute route;
+    // the walk-free routes: per-cell proof terms (k_decode's fix-up mode checks them) and the slab tables; unused on DecodeRoute::Walk
     const CellChk* chk;
     const uint32_t* slab_prefix;  // [n_cells+1] 1 KiB slabs per cell, prefix
     uint32_t* slab_cell;          // [n_slabs] device-filled: cell of each slab
@@ -36,9 +54,8 @@ struct DecodeArgs {
     uint32_t n_slabs;
     PugOut pug;                   // PUG cells: per-read outputs (null pointers when the batch has none)
     uint32_t trivial;             // the batch has cells in `trivial` mode
-    uint32_t short_records;       // the batch averages < 2 alignment words per record: lane-per-record decode
     uint32_t* fix_list;           // [n_cells] cells whose walk-free proof failed (filled by k_verify_cells)
-    // the scattering decoder (k_decode_recs with a bin count): a non-null slab_ovf selects it.  It places the keys of multi-bucket
+    // DecodeRoute::RecsScatter only (k_decode_recs with a bin count).  It places the keys of multi-bucket
     // cells straight into their bucket slabs (keys1, cursor) - keys0 then holds single-bucket cells' keys and the keys that found
     // their slab full - and the fix-up decode re-decodes every cell whose proof failed into keys0 for k_fix_slabs
     uint2* dtile;                 // [n_dtiles] device-filled (k_slab_setup): tile -> (cell, tile index inside the cell)

@@ -207,7 +207,8 @@ def test_bootstraps_large_cell(oracle):
 
 @pytest.mark.parametrize("bw,uw", [(1, 1), (2, 2), (8, 8), (2, 4), (4, 2), (8, 4), (1, 8)])
 def test_field_widths(oracle, bw, uw):
-    """Unaligned record layouts take the byte-granular walk."""
+    """Record layouts with 1- or 2-byte fields (nothing in them is dword aligned) are widened to 4-byte fields on the device
+    (k_widen) and then decoded like any other batch; 8-byte fields are decoded as they are."""
     case = load_golden("crlike_hand_cases.json")["cases"][0]
     cells = [(c["bc"], [(u, r) for u, r in c["reads"]]) for c in case["cells"]]
     b, off = rad.encode_cells(cells, bw, uw)
@@ -627,3 +628,55 @@ def test_bucket_placement_routes_agree(oracle, monkeypatch, env, res, usa):
     got, want, st = run_both(oracle, cfg_for(s, res), s.tid_to_gid, b, off)
     assert_same_result(got, want, what=str(env))
     assert got.val.sum() > 0
+
+
+def _ninth_gene_batch(tenth_ref):
+    """Two cells: three ordinary records, then one record of ten alignments whose first nine name nine distinct genes -
+    the decoders keep eight genes in registers, so its tenth word is seen only by their many-gene fallback."""
+    cells = [(11, [(1, [0]), (2, [1, 10]), (3, [2])]),
+             (12, [(5, list(range(9)) + [tenth_ref])])]
+    return rad.encode_cells(cells, 4, 4)
+
+
+_NINTH_GENE_T2G = np.asarray(list(range(10)) + [0, 1], np.uint32)   # twelve refs, ten genes
+NINTH_GENE_ROUTES = {   # name: (resolution, small_thresh, AFQ_TEST_DECODE, chunk shift)
+    "recs": ("cr-like", 0, "recs", 0),             # k_decode_recs, then the fix-up k_decode
+    "keys": ("cr-like", 0, "keys", 0),             # k_decode_keys, then the fix-up k_decode
+    "walk": ("cr-like", 0, None, 1),               # chunks at offsets 1 mod 4: k_decode alone
+    "par-keys": ("parsimony", 2, "keys", 0),       # cell 1 is below small_thresh: k_decode_par emits its keys
+    "par-gene-set": ("parsimony-gene", 0, None, 0),   # k_decode_par's gene-set label key
+}
+
+
+@pytest.mark.parametrize("route", list(NINTH_GENE_ROUTES))
+def test_bad_ref_behind_the_ninth_gene_is_an_error_on_every_route(oracle, monkeypatch, route):
+    """A ref id >= ref_count behind a record's ninth distinct gene is refused on every decode route, as the oracle refuses it
+    (oracle/afq_oracle.cpp quant_cell, "ref id out of range"); with the tenth ref in range the routes agree with the oracle.
+    (Until the decoders shared one gene projection, the many-gene fallback of k_decode and k_decode_par stepped over such
+    a word and all five cases returned rows for the batch.)"""
+    resolution, small_thresh, decoder, shift = NINTH_GENE_ROUTES[route]
+    if decoder:
+        monkeypatch.setenv("AFQ_TEST_DECODE", decoder)
+    else:
+        monkeypatch.delenv("AFQ_TEST_DECODE", raising=False)
+    t2g = _NINTH_GENE_T2G
+    cfg = pkg.WorkerConfig.for_resolution(resolution, num_genes=10, num_rows=10, small_thresh=small_thresh)
+
+    def shifted(b, off):
+        return np.concatenate((np.zeros(shift, np.uint8), np.frombuffer(b, np.uint8))), off + np.uint64(shift)
+
+    b, off = shifted(*_ninth_gene_batch(9))   # control: ten distinct genes, all in range
+    got, want, _ = run_both(oracle, cfg, t2g, b, off)
+    assert_same_result(got, want, what=route)
+
+    b, off = shifted(*_ninth_gene_batch(len(t2g)))
+    with pytest.raises(oracle.OracleError) as e:
+        oracle.quant(cfg, t2g, b, off)
+    assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "cell 1: ref id out of range" in str(e.value), e.value
+    q = pkg.Quantifier(cfg, t2g)
+    try:
+        with pytest.raises(pkg.AfqError) as e:
+            q.quant_chunks(b, off)
+        assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "cell 1" in str(e.value), e.value
+    finally:
+        q.close()

@@ -945,3 +945,43 @@ int main() {
     r = subprocess.run([str(tmp_path / "t")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 mismatches" in r.stdout
+
+
+def test_decode_route_is_stated_for_every_kind_of_range(tmp_path):
+    """csrc/afq_kernels.h decode_route: the decoder of a range from (walk-free decode possible, the range has parsimony cells, short
+    records).  The function's own source text on the host, over all eight combinations: the sequential walk exactly when walk-free
+    decode is impossible; otherwise parsimony cells pick between k_decode_par and the parsimony instance of k_decode_recs, their
+    absence between k_decode_keys and the scattering instance - short records take k_decode_recs.  No GPU."""
+    import itertools
+    import re
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    src = open(os.path.join(ROOT, "alevin-fry_amd", "csrc", "afq_kernels.h")).read()
+    a = src.index("enum class DecodeRoute")
+    enum = src[a:src.index("};\n", a) + 3]
+    a = src.index("__host__ inline DecodeRoute decode_route(")
+    fn = src[a:src.index("\n}\n", a) + 3]
+    names = re.findall(r"^\s*(\w+),", enum, re.M)
+    assert names == ["Walk", "Keys", "Par", "RecsPug", "RecsScatter"], names
+    host = r'''#include <cstdint>
+#include <cstdio>
+#define __host__
+''' + enum + fn + r'''
+int main() {
+    for (int w = 0; w < 2; ++w) for (int p = 0; p < 2; ++p) for (int s = 0; s < 2; ++s)
+        printf("%d %d %d %u\n", w, p, s, (unsigned)decode_route(w != 0, p != 0, s != 0));
+    return 0;
+}
+'''
+    (tmp_path / "t.cpp").write_text(host)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(tmp_path / "t"), str(tmp_path / "t.cpp")], check=True, capture_output=True)
+    out = subprocess.run([str(tmp_path / "t")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    got = {tuple(int(x) for x in ln.split()[:3]): names[int(ln.split()[3])] for ln in out.stdout.splitlines()}
+    want = {(1, 0, 0): "Keys", (1, 0, 1): "RecsScatter", (1, 1, 0): "Par", (1, 1, 1): "RecsPug"}
+    for w, p, s in itertools.product((0, 1), repeat=3):
+        assert got[(w, p, s)] == (want[(w, p, s)] if w else "Walk"), (w, p, s, got[(w, p, s)])
+    assert len(got) == 8 and [k for k, v in got.items() if v == "Walk"] == [k for k in got if k[0] == 0]
