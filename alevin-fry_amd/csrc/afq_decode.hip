@@ -1183,13 +1183,29 @@ struct DecodeScatter {
     uint32_t* spill;     // per cell: keys that found their bucket's slab full, kept at the front of the cell's keys0 region
 };
 struct NoScatter {};
+// Where the keys of a tile's cell go when they leave the workgroup: the cell's slabs of keys1, its buckets' cursors, its spill words, its
+// sums.  Wave-uniform, but read on the rare exits of the record loop and in the tail only, so the scattering decoder keeps them in vector
+// registers on purpose (in_vgpr: nothing is emitted): as scalars they were spilled to lanes and read back inside the record loop, and a
+// store or an atomic wants its address in vector registers anyway.
+template <class T>
+__device__ __forceinline__ T in_vgpr(T x) { asm volatile("" : "+v"(x)); return x; }
+struct TileOut {
+    uint64_t* k1;           // so.keys1 + m.k1_off
+    uint32_t* cur;          // so.cursor + m.bucket_base
+    uint32_t* spill;        // &so.spill[cell]
+    uint32_t* ovf;          // &so.slab_ovf[cell]
+    uint64_t* k0;           // keys0 + m.key_off
+    uint32_t* nkeys;        // &cell_nkeys[cell]
+    CellChk* chk;           // &chk[cell]
+    uint64_t* bc;           // &bc_out[cell]
+};
 // A key whose bucket slab is full goes to the front of its cell's keys0 region (unused by multi-bucket cells on this route), and
 // the cell is flagged: k_fix_slabs gathers the slabs' keys behind these and places the cell exactly.  (More than n_ref of them:
 // the cell's proof fails, and the fix-up decode rewrites keys0.)
-__device__ __forceinline__ void spill_key(const DecodeScatter& so, uint64_t* __restrict__ keys0, const CellMeta& m, uint32_t cell, uint64_t key) {
-    const uint32_t q = atomicAdd(&so.spill[cell], 1u);
-    if (q < m.n_ref) keys0[m.key_off + q] = key;
-    atomicOr(&so.slab_ovf[cell], 1u);
+__device__ __forceinline__ void spill_key(const TileOut& to, uint32_t n_ref, uint64_t key) {
+    const uint32_t q = atomicAdd(to.spill, 1u);
+    if (q < n_ref) to.k0[q] = key;
+    atomicOr(to.ovf, 1u);
 }
 constexpr uint32_t kDtileSlabs = AFQ_DTILE_SLABS;
 constexpr uint32_t kDtileKeys = AFQ_DTILE_KEYS;
@@ -1207,21 +1223,20 @@ constexpr uint32_t kDtileRun = AFQ_DTILE_RUN;   // consecutive tiles one XCD tak
 // per-key way), so a key at such a position is seen to be past its slab all the same.
 constexpr uint32_t kBase16Max = 0xFFFFu - kDtileKeys;
 template <uint32_t BINS>
-__device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, uint64_t* s_keys, uint32_t* s_cnt, uint32_t* s_base,
-                                             uint32_t* s_misc, uint32_t* __restrict__ cell_nkeys, CellChk* __restrict__ chk,
-                                             const DecodeScatter& so, uint64_t* __restrict__ keys0) {
+__device__ __forceinline__ void scatter_tail(const CellMeta& m, uint64_t* s_keys, uint32_t* s_cnt, uint32_t* s_base,
+                                             uint32_t* s_misc, const TileOut& to) {
     __syncthreads();   // every wave's keys and sums are in LDS, and no wave reads its slab stage any more
     const uint32_t n_all = s_misc[0], nst = min(n_all, s_misc[1]);
     if (threadIdx.x == 0) {
-        if (s_misc[2]) atomicAdd(&chk[cell].count, s_misc[2]);
-        if (s_misc[3]) atomicAdd(&chk[cell].words, s_misc[3]);
-        if (s_misc[4]) atomicOr(&chk[cell].fail, 1u);
-        if (n_all) atomicAdd(&cell_nkeys[cell], n_all);   // (single-bucket cells counted theirs as they reserved keys0)
+        if (s_misc[2]) atomicAdd(&to.chk->count, s_misc[2]);
+        if (s_misc[3]) atomicAdd(&to.chk->words, s_misc[3]);
+        if (s_misc[4]) atomicOr(&to.chk->fail, 1u);
+        if (n_all) atomicAdd(to.nkeys, n_all);   // (single-bucket cells counted theirs as they reserved keys0)
     }
     if (m.lg_nb == 0) return;
     const uint32_t cap = m.slab_cap, nb = 1u << m.lg_nb;
-    uint64_t* dst = so.keys1 + m.k1_off;
-    uint32_t* gcur = so.cursor + m.bucket_base;
+    uint64_t* dst = to.k1;
+    uint32_t* gcur = to.cur;
     uint16_t* c16 = reinterpret_cast<uint16_t*>(s_cnt);
     uint16_t* b16 = reinterpret_cast<uint16_t*>(s_base);
     if (nb > BINS || cap > kBase16Max) {   // giant cell (or slabs beyond the 16-bit positions): per-key cursor atomics
@@ -1230,7 +1245,7 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
             const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
             const uint32_t pos = atomicAdd(&gcur[b], 1u);
             if (pos < cap) dst[(uint64_t)b * cap + pos] = key;
-            else spill_key(so, keys0, m, cell, key);
+            else spill_key(to, m.n_ref, key);
         }
         return;
     }
@@ -1278,7 +1293,7 @@ __device__ __forceinline__ void scatter_tail(const CellMeta& m, uint32_t cell, u
         const uint32_t b = bucket_of(kx >> kGeneBits, m.lg_nb);
         const uint32_t pos = (uint32_t)b16[b] + (i - c16[b]);
         if (pos < cap) dst[(uint64_t)b * cap + pos] = kx;
-        else spill_key(so, keys0, m, cell, kx);
+        else spill_key(to, m.n_ref, kx);
     }
 }
 
@@ -1293,17 +1308,23 @@ constexpr bool decode_recs_own_base(uint32_t bins) { return 4 * bins > kStageByt
 constexpr uint32_t decode_recs_lds(uint32_t bins) {
     return kStageBytes + 4 * kSlabWords + 12 * 4 + (bins ? 8 * kDtileKeys + (decode_recs_own_base(bins) ? 2 * bins : 0) : 0);
 }
-// waves per SIMD of an instance (a workgroup's four waves sit on four SIMDs): what its LDS allows of the CU's 160 KiB, at most
-// eight; at most seven for the scattering instance, whose record loop needs 72 VGPRs of the 512 a SIMD's lane has (at 64 it spills);
-// six for its trivial instance and for barcodes or UMIs of two words, which need up to 80 (at 72 they spill six).
-constexpr uint32_t kCuLdsBytes = 163840, kLaneVgprs = 512;
-constexpr uint32_t decode_recs_occupancy(uint32_t bins, bool trivial, bool wide) {
+// Workgroups per CU an instance is compiled for (a workgroup's four waves sit on four SIMDs): what its LDS allows of the CU's 160 KiB,
+// at most eight - and at most seven for the scattering instances.  Their vector registers would allow eight: with the tile's uniform
+// state in scalar registers every one of them needs at most 60 VGPRs of the 64 that eight waves leave a lane.  But a bound of eight
+// cuts the compiler's scalar budget from 96 to 80 registers, the state that now lives there is then spilled to lanes and read back
+// inside the record loop (21 SGPRs against none: profiles/r14_resource_usage.txt), and the two builds measure the same
+// (profiles/r14_bench.txt; -DAFQ_DECODE_RECS_WAVES=8 builds the other).  The static_assert in the kernel holds the layout this counts.
+#ifndef AFQ_DECODE_RECS_WAVES
+#define AFQ_DECODE_RECS_WAVES 7
+#endif
+constexpr uint32_t kCuLdsBytes = 163840;
+constexpr uint32_t decode_recs_occupancy(uint32_t bins) {
     const uint32_t by_lds = kCuLdsBytes / decode_recs_lds(bins);
-    const uint32_t by_regs = !bins ? 8u : kLaneVgprs / (trivial || wide ? 80u : 72u);
+    const uint32_t by_regs = !bins ? 8u : AFQ_DECODE_RECS_WAVES;
     return by_lds < by_regs ? by_lds : by_regs;
 }
 template <int BW, int UW, bool TRIVIAL, bool PUG, uint32_t BINS = 0>
-__global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW > 8))) void k_decode_recs(const uint8_t* __restrict__ bytes,
+__global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_recs(const uint8_t* __restrict__ bytes,
                                                     const CellMeta* __restrict__ meta, uint32_t n_cells,
                                                     const uint32_t* __restrict__ slab_prefix,
                                                     const uint32_t* __restrict__ slab_cell,
@@ -1334,7 +1355,9 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
     static_assert(sizeof(s_stage) + sizeof(s_list) + sizeof(s_misc) + (SC ? sizeof(s_keys) + (kOwnBase ? sizeof(s_base_own) : 0) : 0) ==
                       decode_recs_lds(BINS), "decode_recs_occupancy counts this layout");
     const uint32_t lane = lane_id();
-    const uint32_t wv = threadIdx.x >> 6;
+    // the scattering instance says that the wave's number is uniform: its slab range, its cell and everything read per cell are then
+    // scalar, and the slab loop is a scalar loop
+    const uint32_t wv = SC ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     uint32_t* stage = s_stage[wv];
     uint8_t* list = s_list[wv];
     uint32_t slab_a, slab_b, my_cell = 0;
@@ -1410,8 +1433,19 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
         }
     };
 
-    load_cell(__builtin_amdgcn_readlane(my_cell, 0));
+    load_cell(SC ? my_cell : __builtin_amdgcn_readlane(my_cell, 0));
     if (!SC || slab_a < slab_b) issue_slab_loads((slab_a - sp0) * kSlabWords);
+    [[maybe_unused]] TileOut to{};
+    if constexpr (SC) {
+        to.k1 = in_vgpr(so.keys1 + m.k1_off);
+        to.cur = in_vgpr(so.cursor + m.bucket_base);
+        to.spill = in_vgpr(so.spill + my_cell);
+        to.ovf = in_vgpr(so.slab_ovf + my_cell);
+        to.k0 = in_vgpr(keys0 + m.key_off);
+        to.nkeys = in_vgpr(cell_nkeys + my_cell);
+        to.chk = in_vgpr(chk + my_cell);
+        to.bc = in_vgpr(bc_out + my_cell);
+    }
 
     bool halo_is_row0 = false;
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
@@ -1425,7 +1459,8 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const bool has_next = slab + 1 < slab_b;
-        const uint32_t next_cell = has_next ? __builtin_amdgcn_readlane(my_cell, (int)(slab + 1 - slab_a)) : cur_cell;
+        // (a scattering tile is slabs of one cell: the next slab, where there is one, is the cell's own)
+        const uint32_t next_cell = !SC && has_next ? __builtin_amdgcn_readlane(my_cell, (int)(slab + 1 - slab_a)) : cur_cell;
         const bool same_next = has_next && next_cell == cur_cell;
         if (same_next) issue_slab_loads(s0 + kSlabWords, 1);
 
@@ -1447,7 +1482,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
             ncand += (uint32_t)__popcll(mk);
         }
         if (s0 == 0 && (!room || !(mk0 & 4ull))) fail = true;  // (1) the first record starts right after the chunk header
-        if (s0 == 0 && lane == 2 && ((mk0 >> 2) & 1ull)) bc_out[cur_cell] = BWW == 2 ? ((uint64_t)bc_hi << 32 | bc_lo) : (uint64_t)bc_lo;
+        if (s0 == 0 && lane == 2 && ((mk0 >> 2) & 1ull)) *(SC ? to.bc : &bc_out[cur_cell]) = BWW == 2 ? ((uint64_t)bc_hi << 32 | bc_lo) : (uint64_t)bc_lo;
         acc_count += ncand;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1482,33 +1517,34 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
             const bool pugc = PUG && mode_is_pug(m.mode);
             const bool pug_txp = pugc && !mode_pug_gene(m.mode);
             uint32_t t[kInl], g[kInl];
-            bool v[kInl];
+            bool v0 = false, v1 = false, v2 = false;
+            auto v = [&](uint32_t j) -> bool& { return j == 0 ? v0 : j == 1 ? v1 : v2; };
 #pragma unroll
             for (uint32_t j = 0; j < kInl; ++j) {
                 const uint32_t pj = il + HW + j;
                 t[j] = stage[pj < kStage ? pj : kStage - 1] & 0x7FFFFFFFu;
-                v[j] = !slowrec && j < na_eff;
-                if (v[j] && t[j] >= ref_count) { fail = true; v[j] = false; }
-                g[j] = pug_txp ? 0u : t2g[v[j] ? t[j] : 0u];
+                v(j) = !slowrec && j < na_eff;
+                if (v(j) && t[j] >= ref_count) { fail = true; v(j) = false; }
+                g[j] = pug_txp ? 0u : t2g[v(j) ? t[j] : 0u];
             }
             if (!pug_txp) {
 #pragma unroll
                 for (uint32_t j = 0; j < kInl; ++j) {
-                    if (v[j] && g[j] >= num_genes) { fail = true; v[j] = false; }
+                    if (v(j) && g[j] >= num_genes) { fail = true; v(j) = false; }
 #pragma unroll
-                    for (uint32_t q = 0; q < j; ++q) v[j] = v[j] && !(v[q] && g[q] == g[j]);
+                    for (uint32_t q = 0; q < j; ++q) v(j) = v(j) && !(v(q) && g[q] == g[j]);
                 }
             }
             if (triv) {  // only reads whose alignments name one gene count (pugutils.rs:870-891)
                 bool multi = false;
 #pragma unroll
-                for (uint32_t j = 1; j < kInl; ++j) { multi = multi || v[j]; v[j] = false; }
-                v[0] = v[0] && !multi;
+                for (uint32_t j = 1; j < kInl; ++j) { multi = multi || v(j); v(j) = false; }
+                v(0) = v(0) && !multi;
             }
             uint64_t bal[kInl];
             uint32_t tot = 0;
 #pragma unroll
-            for (uint32_t j = 0; j < kInl; ++j) { bal[j] = __ballot(v[j]); tot += (uint32_t)__popcll(bal[j]); }
+            for (uint32_t j = 0; j < kInl; ++j) { bal[j] = __ballot(v(j)); tot += (uint32_t)__popcll(bal[j]); }
             // long records: serial count now, serial emission after the reservation
             uint32_t scnt = 0, sex = 0;
             auto ref_at = [&](uint32_t j) -> uint32_t {
@@ -1556,7 +1592,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
                     auto add = [&](uint32_t gj) { if (kc == 0) ga = gj; else if (kc == 1) gb = gj; ++kc; hs += gene_set_hash_term(gj ^ (uint32_t)pug.salt); };
                     if (!slowrec) {
 #pragma unroll
-                        for (uint32_t j = 0; j < kInl; ++j) if (v[j]) add(g[j]);
+                        for (uint32_t j = 0; j < kInl; ++j) if (v(j)) add(g[j]);
                     } else for_each_first_gene(add);
                     hs ^= (uint64_t)kc * kHashMul;
                     lkey = label_key(hs & pug.mask, kc, ga, gb);
@@ -1584,10 +1620,11 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
                 sex = tot + wave_excl_scan(scnt, stot);
                 tot += stot;
             }
+            if constexpr (SC) tot = __builtin_amdgcn_readfirstlane(tot);   // (a sum of ballot counts and a wave total)
             if (tot) {
                 const bool staged = SC && m.lg_nb != 0;   // (wave-uniform) the scattering instance's multi-bucket cell
                 uint32_t wbase = 0;
-                if (lane == 0) wbase = staged ? atomicAdd(&s_misc[0], tot) : atomicAdd(&cell_nkeys[cur_cell], tot);
+                if (lane == 0) wbase = staged ? atomicAdd(&s_misc[0], tot) : atomicAdd(SC ? to.nkeys : &cell_nkeys[cur_cell], tot);
                 wbase = __builtin_amdgcn_readfirstlane(wbase);
                 // staged: keys that do not fit the stage go to their buckets one cursor atomic each (the staged keys are the prefix
                 // [0, s_misc[1]) - every wave after the first that did not fit finds the stage full as well)
@@ -1595,13 +1632,13 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
                 if (direct && lane == 0) atomicMin(&s_misc[1], wbase);
                 auto put = [&](uint32_t at, uint64_t key) {
                     if constexpr (SC) {
-                        if (!staged) keys0[m.key_off + wbase + at] = key;
+                        if (!staged) to.k0[wbase + at] = key;
                         else if (!direct) s_keys[wbase + at] = key;
                         else {
                             const uint32_t b = bucket_of(key >> kGeneBits, m.lg_nb);
-                            const uint32_t pos = atomicAdd(&so.cursor[m.bucket_base + b], 1u);
-                            if (pos < m.slab_cap) so.keys1[m.k1_off + (uint64_t)b * m.slab_cap + pos] = key;
-                            else spill_key(so, keys0, m, cur_cell, key);
+                            const uint32_t pos = atomicAdd(&to.cur[b], 1u);
+                            if (pos < m.slab_cap) to.k1[(uint64_t)b * m.slab_cap + pos] = key;
+                            else spill_key(to, m.n_ref, key);
                         }
                     } else keys0[m.key_off + wbase + at] = key;
                 };
@@ -1611,7 +1648,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
 #pragma unroll
                     for (uint32_t j = 0; j < kInl; ++j) {
                         const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
-                        if (v[j]) put(o + before, (umi << kGeneBits) | g[j]);
+                        if (v(j)) put(o + before, (umi << kGeneBits) | g[j]);
                         o += (uint32_t)__popcll(bal[j]);
                     }
                     if (any_slow && slowrec && scnt) {
@@ -1624,15 +1661,17 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS, TRIVIAL, (BW + UW 
         // all lanes are done reading this slab's stage/list before the next iteration overwrites them
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (has_next && !same_next) {
-            flush_chk();
-            load_cell(next_cell);
-            issue_slab_loads((slab + 1 - sp0) * kSlabWords);
+        if constexpr (!SC) {
+            if (has_next && !same_next) {
+                flush_chk();
+                load_cell(next_cell);
+                issue_slab_loads((slab + 1 - sp0) * kSlabWords);
+            }
         }
         halo_is_row0 = same_next;
     }
     flush_chk();
-    if constexpr (SC) scatter_tail<BINS>(m, my_cell, s_keys, &s_stage[0][0], kOwnBase ? s_base_own : &s_stage[0][0] + BINS / 2, s_misc, cell_nkeys, chk, so, keys0);
+    if constexpr (SC) scatter_tail<BINS>(m, s_keys, &s_stage[0][0], kOwnBase ? s_base_own : &s_stage[0][0] + BINS / 2, s_misc, to);
 }
 
 // ---------------------------------------------------------------------------
