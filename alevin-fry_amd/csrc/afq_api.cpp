@@ -999,8 +999,8 @@ int run_range(afq_ctx* c, Range r, int slot, hipEvent_t h2d_done = nullptr, uint
     if (!hist_cells.empty()) { tc.seg(K_CELL_HIST); launch_cell_hist(s, ra); }
     if (B.em_inline) {
         tc.seg(K_EM);
-        launch_em2(s, ra, n, B.d_em2_off.as<uint64_t>(), B.d_em2_scratch.as<uint32_t>(), B.d_em_nnz.as<uint32_t>(), B.d_em_order.as<uint32_t>(),
-                   B.d_em2_tiers.as<uint32_t>(), na_em, g.em_init_uniform, em2_cap);
+        HIP_TRY(c, launch_em2(s, ra, n, B.d_em2_off.as<uint64_t>(), B.d_em2_scratch.as<uint32_t>(), B.d_em_nnz.as<uint32_t>(), B.d_em_order.as<uint32_t>(),
+                              B.d_em2_tiers.as<uint32_t>(), na_em, g.em_init_uniform, em2_cap));
     }
     tc.end();
     HIP_TRY(c, hipGetLastError());
@@ -1240,8 +1240,8 @@ int finish_range(afq_ctx* c, int slot) {
             HIP_TRY(c, B.d_em2_tiers.ensure(4ull * (8 + 5ull * n)));
             HIP_TRY(c, hipMemcpyAsync(B.d_em2_off.p, eoff2.data(), 8ull * (n + 1), hipMemcpyHostToDevice, s));
             ScopedTimer t(c, K_EM, s, &B.launches);
-            launch_em2(s, B.last_ra, n, B.d_em2_off.as<uint64_t>(), B.d_em2_scratch.as<uint32_t>(), B.d_em_nnz.as<uint32_t>(), B.d_em_order.as<uint32_t>(),
-                       B.d_em2_tiers.as<uint32_t>(), na_em, c->cfg.em_init_uniform);
+            HIP_TRY(c, launch_em2(s, B.last_ra, n, B.d_em2_off.as<uint64_t>(), B.d_em2_scratch.as<uint32_t>(), B.d_em_nnz.as<uint32_t>(), B.d_em_order.as<uint32_t>(),
+                                  B.d_em2_tiers.as<uint32_t>(), na_em, c->cfg.em_init_uniform));
             HIP_TRY(c, B.h_em2_tiers.reserve(8));
             HIP_TRY(c, hipMemcpyAsync(B.h_em2_tiers.p, B.d_em2_tiers.p, 32, hipMemcpyDeviceToHost, s));
         }

@@ -873,16 +873,25 @@ __global__ __launch_bounds__(1024) void k_em2_plan(const uint32_t* __restrict__ 
     for (uint32_t i = i0; i < i1; ++i) { em_off[i] = off; off += em2_words(nnz_unique[i], lab_cnt[2 * i], lab_cnt[2 * i + 1], usa != 0); }
 }
 
-void launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t* em_off, uint32_t* scratch, uint32_t* out_nnz,
-                const uint32_t* em_order, uint32_t* tiers, uint32_t num_alphas, uint32_t init_uniform, uint64_t plan_cap_words) {
-    if (!n_cells) return;
+hipError_t launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t* em_off, uint32_t* scratch, uint32_t* out_nnz,
+                      const uint32_t* em_order, uint32_t* tiers, uint32_t num_alphas, uint32_t init_uniform, uint64_t plan_cap_words) {
+    if (!n_cells) return hipSuccess;
     uint32_t min_tier = 0;
     if (const char* e = test_hook("EM2_MIN_TIER")) min_tier = (uint32_t)std::min(4, std::max(0, std::atoi(e)));   // (tests; read per range)
     Em2Cfg cfg{a.usa, num_alphas, a.num_rows / 3, 2 * (a.num_rows / 3), init_uniform, (num_alphas + 31) / 32, min_tier, test_hook_is("EM2_WIDE_IDS", "1") ? 1u : 0u};
     if (!plan_cap_words) (void)hipMemsetAsync(tiers, 0, 32, s);   // (with a device-side plan the range's init kernel has cleared the counters)
     if (plan_cap_words) hipLaunchKernelGGL(k_em2_plan, dim3(1), dim3(1024), 0, s, a.nnz, a.lab_cnt, n_cells, a.usa, (unsigned long long)plan_cap_words, em_off, tiers, a.st);
-    hipLaunchKernelGGL(k_em2_setup, dim3(n_cells), dim3(kSetupNT), 8 * cfg.nwb, s, a.meta, a.nnz, a.keys0, a.keys1, a.lab, a.lab_cnt, em_off,
+    // bitmap + ranks: 8 bytes per 32 columns, 64 KiB at em2_supported's bound on top of the kernel's 1.3 KiB of static LDS - more
+    // than a workgroup gets without asking (as launch_cell_hist asks); the launch's status goes back to the caller
+    const uint32_t setup_lds = 8 * cfg.nwb;
+    if (setup_lds > 48u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_em2_setup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)setup_lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_em2_setup, dim3(n_cells), dim3(kSetupNT), setup_lds, s, a.meta, a.nnz, a.keys0, a.keys1, a.lab, a.lab_cnt, em_off,
                        scratch, out_nnz, em_order, tiers, n_cells, cfg);
+    const hipError_t setup_status = hipGetLastError();
+    if (setup_status != hipSuccess) return setup_status;
 #define EM2_ROUNDS(NT, MODE, EPT, LDSW, TIER) \
     hipLaunchKernelGGL((k_em2_rounds<NT, MODE, EPT, LDSW>), dim3(n_cells), dim3(NT), 0, s, a.meta, a.nnz, a.lab_cnt, em_off, scratch, out_nnz, tiers, n_cells, TIER, cfg)
     hipLaunchKernelGGL(k_em2_rounds_hybrid<1024>, dim3(n_cells), dim3(1024), 0, s, a.nnz, a.lab_cnt, em_off, scratch, out_nnz, tiers, n_cells, 4u, cfg);   // largest first
@@ -891,6 +900,7 @@ void launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t*
     EM2_ROUNDS(512, 0, 8, kT1Words, 1u);
     EM2_ROUNDS(256, 0, 8, kT0Words, 0u);
 #undef EM2_ROUNDS
+    return hipSuccess;
 }
 
 // columns the setup kernel's bitmap + rank table can hold in 64 KiB of LDS; beyond that the EM takes the canonical kernels

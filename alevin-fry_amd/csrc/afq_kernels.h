@@ -142,8 +142,9 @@ void launch_em(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, const uint
 uint64_t em2_scratch_words(uint32_t nU, uint32_t W, uint32_t M, bool usa);
 bool em2_supported(uint32_t num_alphas);
 // plan_cap_words != 0: the per-cell offsets are made on the device (k_em2_plan) from the counts the range's kernels left, packed
-// into a scratch buffer of that many words; tiers[7] != 0 afterwards = it did not fit and nothing ran
-void launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t* em_off, uint32_t* scratch, uint32_t* out_nnz,
+// into a scratch buffer of that many words; tiers[7] != 0 afterwards = it did not fit and nothing ran.  Returns the status of
+// the set-up kernel's launch, the one whose LDS grows with num_alphas (64 KiB of bitmap and ranks at em2_supported's bound)
+hipError_t launch_em2(hipStream_t s, const ResolveArgs& a, uint32_t n_cells, uint64_t* em_off, uint32_t* scratch, uint32_t* out_nnz,
                 const uint32_t* em_order, uint32_t* tiers /* 8 + 5 * n_cells words */, uint32_t num_alphas, uint32_t init_uniform,
                 uint64_t plan_cap_words = 0);
 // -d: sizes (cls_ptr == null) or fills the per-cell gene-level classes; see k_eqc_dump

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from pug_routes import PUG_ROUTES, set_pug_route
 from util import assert_same_result, cfg_for, load_golden, pkg, rows_of
 
 pytestmark = pytest.mark.gpu
@@ -9,7 +10,7 @@ rad = pkg.rad
 synth = pkg.synth
 
 
-@pytest.fixture(autouse=True, params=["phase-kernels", "one-workgroup", "handed-back", "cover-1024", "graph-per-cell", "graph-per-cell-1024", "graph-per-cell-ties-set-aside"])
+@pytest.fixture(autouse=True, params=list(PUG_ROUTES))
 def pug_route(request, monkeypatch):
     """Every test of this module runs seven times: through the partition-parallel phase kernels with the range-wide flat graph
     build (csrc/afq_pug2.hip + csrc/afq_pugflat.hip, the default; a cell with a component of more than 64 vertices is routed to
@@ -19,22 +20,7 @@ def pug_route(request, monkeypatch):
     of 15 000 reads), and three times with the per-cell graph kernel of rounds 3-5 for EVERY cell (AFQ_TEST_P2_GRAPH=cell): as
     it decides itself, with its 1024-thread instance from 300 reads, and with every cell covering its components in slot order
     and setting the tied ones aside for k_p2_tied (what the flat build always does)."""
-    if request.param == "one-workgroup":
-        monkeypatch.setenv("AFQ_TEST_PUG_ROUTE", "mono")
-    elif request.param == "handed-back":
-        monkeypatch.setenv("AFQ_TEST_P2_PART_CAP", "24")
-    elif request.param == "cover-1024":
-        monkeypatch.setenv("AFQ_TEST_P2_BIG_READS", "300")
-    elif request.param == "graph-per-cell":
-        monkeypatch.setenv("AFQ_TEST_P2_GRAPH", "cell")
-    elif request.param == "graph-per-cell-1024":
-        monkeypatch.setenv("AFQ_TEST_P2_GRAPH", "cell")
-        monkeypatch.setenv("AFQ_TEST_P2_BIG_READS", "300")
-        monkeypatch.setenv("AFQ_TEST_P2_DEFER_MIN", "0")
-    elif request.param == "graph-per-cell-ties-set-aside":
-        monkeypatch.setenv("AFQ_TEST_P2_GRAPH", "cell")
-        monkeypatch.setenv("AFQ_TEST_P2_DEFER_MIN", "0")
-    return request.param
+    return set_pug_route(monkeypatch, request.param)
 
 
 def run_both(oracle, cfg, t2g, b, off):
