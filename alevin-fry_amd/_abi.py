@@ -122,6 +122,8 @@ EXPORTS = [
     "afq_infer",
     "afq_atac_dedup",
     "afq_atac_dedup_rad",
+    "afq_atac_sort_rad",
+    "afq_atac_sort_limits",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -136,3 +138,8 @@ EXPORTS = [
 class AfqAtacStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_not_mapped_pair", C.c_uint64), ("n_distinct", C.c_uint64),
                 ("n_deduplicated", C.c_uint64), ("n_long_fragments", C.c_uint64), ("n_fallback_cells", C.c_uint64)]
+
+
+class AfqAtacSortStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_uncorrected", C.c_uint64),
+                ("n_kept", C.c_uint64), ("n_distinct", C.c_uint64), ("n_long_fragments", C.c_uint64), ("n_repartitioned_bins", C.c_uint64)]

@@ -289,6 +289,12 @@ def load_library(path: str = LIB_PATH):
     lib.afq_atac_dedup_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(p(C.c_uint64)),
                                        p(p(C.c_uint64)), p(p(C.c_uint32)), p(p(C.c_uint32)), p(p(C.c_uint16)), p(p(C.c_uint16)), p(_abi.AfqAtacStats)]
     lib.afq_atac_dedup_rad.restype = C.c_int
+    lib.afq_atac_sort_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), p(C.c_uint64),
+                                      C.c_uint64, p(C.c_uint32), C.c_uint32, p(C.c_uint64), p(p(C.c_uint32)), p(p(C.c_uint32)), p(p(C.c_uint16)),
+                                      p(p(C.c_uint64)), p(p(C.c_uint32)), p(_abi.AfqAtacSortStats)]
+    lib.afq_atac_sort_rad.restype = C.c_int
+    lib.afq_atac_sort_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_atac_sort_limits.restype = None
     lib.afq_free.argtypes = [C.c_void_p]
     lib.afq_free.restype = None
     lib.afq_get_kernel_times.argtypes = [C.c_void_p, p(AfqKernelTime), C.c_uint32]
@@ -303,6 +309,13 @@ def load_library(path: str = LIB_PATH):
         raise RuntimeError("libafquant.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def atac_sort_limits():
+    """afq_atac_sort_limits: {"bin_shift", "leaf_cap", "repartition_above", "parse_tile"} of the `atac sort` kernels."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_atac_sort_limits(out)
+    return {"bin_shift": int(out[0]), "leaf_cap": int(out[1]), "repartition_above": int(out[2]), "parse_tile": int(out[3])}
 
 
 class _Held(np.ndarray):
@@ -482,6 +495,42 @@ class Quantifier:
             return ptr, mk(o_ref, np.uint32), mk(o_start, np.uint32), mk(o_len, np.uint16), mk(o_cnt, np.uint16)
         finally:
             for q in (o_ptr, o_ref, o_start, o_len, o_cnt):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def atac_sort_limits():
+        """The `atac sort` kernels' limits (module-level atac_sort_limits)."""
+        return atac_sort_limits()
+
+    def atac_sort_rad(self, chunk_bytes, chunk_off, observed, corrected, ref_lengths, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0):
+        """afq_atac_sort_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the
+        device) with the correction map (observed -> corrected) and the references' lengths; a dict out: the distinct
+        (ref, start, frag_len, bc) rows in that order with their count, and "stats"."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        obs = np.ascontiguousarray(observed, dtype=np.uint64)
+        cor = np.ascontiguousarray(corrected, dtype=np.uint64)
+        rl = np.ascontiguousarray(ref_lengths, dtype=np.uint32)
+        if len(obs) != len(cor):
+            raise ValueError("observed and corrected must have one length")
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        o_n = C.c_uint64()
+        o_ref, o_start, o_len, o_bc, o_cnt = u32p(), u32p(), C.POINTER(C.c_uint16)(), u64p(), u32p()
+        st = _abi.AfqAtacSortStats()
+        self._check(self.lib.afq_atac_sort_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), bc_bytes, on_dev, obs.ctypes.data_as(u64p),
+                                               cor.ctypes.data_as(u64p), len(obs), rl.ctypes.data_as(u32p), len(rl), C.byref(o_n), C.byref(o_ref),
+                                               C.byref(o_start), C.byref(o_len), C.byref(o_bc), C.byref(o_cnt), C.byref(st)))
+        n = int(o_n.value)
+        try:
+            mk = lambda p_, dt: (np.ctypeslib.as_array(p_, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt))
+            return {"ref": mk(o_ref, np.uint32), "start": mk(o_start, np.uint32), "frag_len": mk(o_len, np.uint16), "bc": mk(o_bc, np.uint64),
+                    "count": mk(o_cnt, np.uint32), "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_ref, o_start, o_len, o_bc, o_cnt):
                 self.lib.afq_free(q)
 
     def atac_dedup_rad(self, chunk_bytes, chunk_off, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0, copy: bool = True):

@@ -58,10 +58,11 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
-                                           "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph"};
+                                           "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
+                                           "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -193,6 +194,7 @@ struct afq_ctx {
     size_t n_bytes = 0;
     DevBuf d_chunk_off, d_hdr;
     DevBuf atac[27];  // afq_atac_dedup[_rad]'s device buffers, kept between calls
+    DevBuf asort[24]; // afq_atac_sort_rad's
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
@@ -1692,6 +1694,7 @@ void afq_destroy(afq_ctx* c) {
     DevBuf* bufs[] = {&c->d_t2g, &c->d_bytes_own, &c->d_chunk_off, &c->d_hdr, &c->d_wide, &c->d_kick};
     for (auto b : bufs) b->release();
     for (auto& b : c->atac) b.release();
+    for (auto& b : c->asort) b.release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);
@@ -2394,6 +2397,318 @@ int afq_atac_dedup_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const u
         stats->n_deduplicated = tally[0]; stats->n_long_fragments = tally[1];   // (tallied by the compaction kernel)
         stats->n_fallback_cells = st.n_fallback;
     }
+    return 0;
+}
+
+// `atac sort` on the device (afq_atac_sort.hip): table, parse + correct, partition into position bins, re-partition of the
+// oversize ones, leaves, dense arrays.  The host's part is what needs the whole picture and is small: the ranks of the corrected
+// barcodes, the bins' first ids, and - from the bins' counts - which segments are leaves and which are split again.
+void afq_atac_sort_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSortBinShift; out[1] = kSortLeafCap; out[2] = kSortRepartAbove; out[3] = kSortParseTile;
+}
+
+int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                      int bytes_on_device, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint32_t* ref_lengths,
+                      uint32_t ref_count, uint64_t* out_n, uint32_t** out_ref, uint32_t** out_start, uint16_t** out_frag_len, uint64_t** out_bc,
+                      uint32_t** out_count, afq_atac_sort_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || ((!observed || !corrected) && n_corr) || (!ref_lengths && ref_count) || !out_n || !out_ref ||
+        !out_start || !out_frag_len || !out_bc || !out_count)
+        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    if (n_corr >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^30 or more correction entries");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    // ---- host: ranks of the corrected barcodes, the all-ones key, the bins' first ids
+    std::vector<uint64_t> uniq(corrected, corrected + n_corr);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    if (uniq.size() >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^31 or more distinct corrected barcodes");
+    std::vector<uint32_t> rank(n_corr);
+    uint32_t ones_rank = kSortNoRank;
+    for (uint64_t i = 0; i < n_corr; ++i) {
+        rank[i] = (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), corrected[i]) - uniq.begin());
+        if (observed[i] == kSortEmptyKey) {
+            if (ones_rank != kSortNoRank && ones_rank != rank[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
+            ones_rank = rank[i];
+        }
+    }
+    std::vector<uint2> ref_info(std::max<uint32_t>(ref_count, 1));
+    std::vector<uint32_t> bin_base((size_t)ref_count + 1, 0);
+    uint64_t n_bins64 = 0;
+    for (uint32_t r = 0; r < ref_count; ++r) {
+        bin_base[r] = (uint32_t)n_bins64;
+        ref_info[r] = make_uint2(ref_lengths[r], (uint32_t)n_bins64);
+        n_bins64 += ((uint64_t)ref_lengths[r] + (1u << kSortBinShift) - 1) >> kSortBinShift;
+        if (n_bins64 >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^31 or more position bins");
+    }
+    bin_base[ref_count] = (uint32_t)n_bins64;
+    const uint32_t n_bins = (uint32_t)n_bins64;
+    // ---- chunk table
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (!bytes_on_device) {
+        for (uint32_t i = 0; i < n_chunks; ++i) {
+            if (chunk_off[i] + 8 > n_bytes || chunk_off[i] + 8 < chunk_off[i]) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk offset out of range");
+            std::memcpy(&hdr[2 * i], bytes + chunk_off[i], 8);
+        }
+    } else if (n_chunks) {
+        HIP_TRY(c, c->d_chunk_off.ensure(8ull * n_chunks));
+        HIP_TRY(c, c->d_hdr.ensure(8ull * n_chunks));
+        HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n_chunks, hipMemcpyHostToDevice, s));
+        launch_gather_headers(s, bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n_chunks, c->d_hdr.as<uint32_t>());
+        HIP_TRY(c, hipMemcpyAsync(hdr.data(), c->d_hdr.p, 8ull * n_chunks, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    std::vector<SortChunk> chunks(n_chunks);
+    uint64_t n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (chunk_off[i] + 8 > n_bytes || chunk_off[i] + 8 < chunk_off[i] || nb < 8 || chunk_off[i] + nb > n_bytes)
+            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk header/size out of range");
+        if ((uint64_t)nr * (4 + bc_bytes) + 8 > nb) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk nbytes does not match its records");
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + ")");
+    uint64_t cap = 2;
+    while (cap < 2 * n_corr) cap <<= 1;
+    const uint32_t tab_mask = (uint32_t)(cap - 1);
+    // ---- does it fit?  (input + staging, 12 bytes a record of parse output, two key buffers, 22 bytes a row of output, the tables)
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);
+    {
+        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * (12 + 16 + 22), need_tab = cap * 12 + n_corr * 12 + uniq.size() * 8,
+                       need_misc = nc1 * (sizeof(SortChunk) + 16) + (uint64_t)nb1 * 8 + (uint64_t)ref_count * 12;
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
+                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables > " +
+                        std::to_string(tot) + " bytes of device memory");
+    }
+    DevBuf &d_chunks = c->asort[0], &d_obs = c->asort[1], &d_rank = c->asort[2], &d_tkey = c->asort[3], &d_tval = c->asort[4], &d_rinfo = c->asort[5],
+           &d_bbase = c->asort[6], &d_rbc = c->asort[7], &d_bin = c->asort[8], &d_key0 = c->asort[9], &d_cstat = c->asort[10], &d_status = c->asort[11],
+           &d_hist = c->asort[12], &d_cur = c->asort[13], &d_segs = c->asort[14], &d_ka = c->asort[15], &d_kb = c->asort[16], &d_andor = c->asort[17],
+           &d_leaves = c->asort[18], &d_ids = c->asort[19], &d_on = c->asort[20], &d_lout = c->asort[21], &d_out = c->asort[22], &d_tally = c->asort[23];
+    hipError_t e = hipSuccess;
+    auto T = [&](hipError_t x) { if (e == hipSuccess) e = x; };
+    auto hip_fail = [&]() {
+        (void)hipGetLastError();
+        return fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_sort_rad: ") + hipGetErrorString(e) + " (" + std::to_string(n_bytes) +
+                    " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_corr) + " corrections)");
+    };
+    T(d_chunks.ensure(sizeof(SortChunk) * nc1)); T(d_obs.ensure(8 * std::max<uint64_t>(n_corr, 1))); T(d_rank.ensure(4 * std::max<uint64_t>(n_corr, 1)));
+    T(d_tkey.ensure(8 * cap)); T(d_tval.ensure(4 * cap)); T(d_rinfo.ensure(8ull * ref_info.size())); T(d_bbase.ensure(4ull * bin_base.size()));
+    T(d_rbc.ensure(8 * std::max<uint64_t>(uniq.size(), 1))); T(d_bin.ensure(4 * s1)); T(d_key0.ensure(8 * s1)); T(d_cstat.ensure(16ull * nc1));
+    T(d_status.ensure(sizeof(DevStatus))); T(d_hist.ensure(4ull * nb1)); T(d_cur.ensure(4ull * nb1)); T(d_segs.ensure(sizeof(SortSeg))); T(d_tally.ensure(8));
+    if (e != hipSuccess) return hip_fail();
+    const uint8_t* d_bytes = bytes;
+    if (!bytes_on_device) {
+        T(c->d_bytes_own.ensure(n_bytes + 16));
+        if (e != hipSuccess) return hip_fail();
+        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
+        d_bytes = c->d_bytes_own.as<uint8_t>();
+    }
+    if (n_chunks) T(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_corr) { T(hipMemcpyAsync(d_obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(d_rank.p, rank.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
+    if (ref_count) T(hipMemcpyAsync(d_rinfo.p, ref_info.data(), 8ull * ref_count, hipMemcpyHostToDevice, s));
+    T(hipMemcpyAsync(d_bbase.p, bin_base.data(), 4ull * bin_base.size(), hipMemcpyHostToDevice, s));
+    if (!uniq.empty()) T(hipMemcpyAsync(d_rbc.p, uniq.data(), 8 * uniq.size(), hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(d_tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(d_status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(d_hist.p, 0, 4ull * nb1, s));
+    T(hipMemsetAsync(d_tally.p, 0, 8, s));
+    if (hc.on) { T(hipStreamSynchronize(s)); hc.lap("atac sort: alloc + H2D"); }
+    if (e != hipSuccess) return hip_fail();
+    for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
+    // ---- table, parse
+    {
+        ScopedTimer t(c, K_ASORT_TABLE, s);
+        launch_sort_table(s, d_obs.as<uint64_t>(), d_rank.as<uint32_t>(), n_corr, d_tkey.as<uint64_t>(), d_tval.as<uint32_t>(), tab_mask, d_status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_ASORT_PARSE, s);
+        launch_sort_parse(s, SortParseArgs{d_bytes, (uint64_t)n_bytes, d_chunks.as<SortChunk>(), n_chunks, bc_bytes, d_tkey.as<uint64_t>(), d_tval.as<uint32_t>(), tab_mask,
+                                           ones_rank, d_rinfo.as<uint2>(), ref_count, d_bin.as<uint32_t>(), d_key0.as<uint64_t>(), d_cstat.as<uint32_t>(),
+                                           d_status.as<DevStatus>()});
+    }
+    T(hipGetLastError());
+    DevStatus st{};
+    std::vector<uint32_t> cstat(4ull * n_chunks);
+    T(hipMemcpyAsync(&st, d_status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), d_cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
+    hc.lap("atac sort: table + parse");
+    if (e != hipSuccess) return hip_fail();
+    if (st.err_code) {
+        harvest_timers(c);
+        const std::string who = std::to_string(st.err_cell);
+        switch (st.err_code) {
+            case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + who + ": an observed barcode with two different corrected barcodes");
+            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+            case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a reference id is not below ref_count");
+            case kErrStartRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a start position is not below its reference's length");
+            default: return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: device status " + std::to_string(st.err_code));
+        }
+    }
+    afq_atac_sort_stats S{};
+    S.n_records = n_slots;
+    for (uint32_t i = 0; i < n_chunks; ++i) { S.n_unmapped += cstat[4 * i]; S.n_multimapped += cstat[4 * i + 1]; S.n_uncorrected += cstat[4 * i + 2]; S.n_kept += cstat[4 * i + 3]; }
+    const uint32_t n_kept = (uint32_t)S.n_kept;   // (< 2^32: n_slots is)
+    // ---- level 0: the position bins
+    std::vector<SortLeaf> leaves;
+    struct Big { uint32_t off, cnt, bin; };
+    std::vector<Big> big;
+    if (n_kept) {
+        T(d_ka.ensure(8ull * n_kept));
+        if (e != hipSuccess) return hip_fail();
+        const SortSeg seg0{0, (uint32_t)n_slots, 0, 0};
+        T(hipMemcpyAsync(d_segs.p, &seg0, sizeof(seg0), hipMemcpyHostToDevice, s));
+        {
+            ScopedTimer t(c, K_ASORT_PART, s);
+            launch_sort_partition(s, d_segs.as<SortSeg>(), 1, (uint32_t)n_slots, d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), n_bins, d_hist.as<uint32_t>(),
+                                  d_cur.as<uint32_t>(), d_ka.as<uint64_t>());
+        }
+        T(hipGetLastError());
+        std::vector<uint32_t> hist(n_bins);
+        T(hipMemcpyAsync(hist.data(), d_hist.p, 4ull * n_bins, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (e != hipSuccess) return hip_fail();
+        uint32_t off = 0;
+        for (uint32_t b = 0; b < n_bins; ++b) {
+            const uint32_t n = hist[b];
+            if (!n) continue;
+            if (n > kSortRepartAbove) { big.push_back(Big{off, n, b}); ++S.n_repartitioned_bins; }
+            else leaves.push_back(SortLeaf{off, n, b, 0});
+            off += n;
+        }
+        if (off != n_kept) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: the bins hold " + std::to_string(off) + " of " + std::to_string(n_kept) + " fragments");
+    }
+    hc.lap("atac sort: partition");
+    // ---- oversize segments: split by the eight highest bits in which their keys differ, until they fit a leaf or are one run
+    uint32_t src_is_b = 0;
+    for (uint32_t level = 0; !big.empty(); ++level) {
+        if (level > 64 / kSortRadixBits) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: a segment survived every key bit");
+        const uint32_t nb_ = (uint32_t)big.size();
+        std::vector<SortSeg> segs(nb_);
+        std::vector<uint64_t> ao(2ull * nb_);
+        uint32_t max_cnt = 0;
+        for (uint32_t i = 0; i < nb_; ++i) { segs[i] = SortSeg{big[i].off, big[i].cnt, i * 256u, 0}; ao[2 * i] = ~0ull; ao[2 * i + 1] = 0; max_cnt = std::max(max_cnt, big[i].cnt); }
+        T(d_segs.ensure(sizeof(SortSeg) * nb_)); T(d_andor.ensure(16ull * nb_)); T(d_hist.ensure(1024ull * nb_)); T(d_cur.ensure(1024ull * nb_)); T(d_kb.ensure(8ull * n_kept));
+        if (e != hipSuccess) return hip_fail();
+        uint64_t* src = src_is_b ? d_kb.as<uint64_t>() : d_ka.as<uint64_t>();
+        uint64_t* dst = src_is_b ? d_ka.as<uint64_t>() : d_kb.as<uint64_t>();
+        T(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(SortSeg) * nb_, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(d_andor.p, ao.data(), 16ull * nb_, hipMemcpyHostToDevice, s));
+        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_bits(s, d_segs.as<SortSeg>(), nb_, max_cnt, src, d_andor.as<uint64_t>()); }
+        T(hipGetLastError());
+        T(hipMemcpyAsync(ao.data(), d_andor.p, 16ull * nb_, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (e != hipSuccess) return hip_fail();
+        std::vector<Big> split;
+        std::vector<SortSeg> ssegs;
+        max_cnt = 0;
+        for (uint32_t i = 0; i < nb_; ++i) {
+            const uint64_t diff = ao[2 * i] ^ ao[2 * i + 1];
+            if (!diff) { leaves.push_back(SortLeaf{big[i].off, big[i].cnt, big[i].bin, src_is_b | 2u}); continue; }   // one run: no sort
+            const uint32_t top = 63u - (uint32_t)__builtin_clzll(diff);
+            const uint32_t shift = top >= kSortRadixBits - 1 ? top - (kSortRadixBits - 1) : 0u;
+            ssegs.push_back(SortSeg{big[i].off, big[i].cnt, (uint32_t)split.size() * 256u, shift});
+            split.push_back(big[i]);
+            max_cnt = std::max(max_cnt, big[i].cnt);
+        }
+        big.clear();
+        if (split.empty()) break;
+        const uint32_t ns = (uint32_t)split.size();
+        std::vector<uint32_t> hist(256ull * ns);
+        T(hipMemcpyAsync(d_segs.p, ssegs.data(), sizeof(SortSeg) * ns, hipMemcpyHostToDevice, s));
+        T(hipMemsetAsync(d_hist.p, 0, 1024ull * ns, s));
+        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_partition(s, d_segs.as<SortSeg>(), ns, max_cnt, src, nullptr, 256, d_hist.as<uint32_t>(), d_cur.as<uint32_t>(), dst); }
+        T(hipGetLastError());
+        T(hipMemcpyAsync(hist.data(), d_hist.p, 1024ull * ns, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (e != hipSuccess) return hip_fail();
+        src_is_b ^= 1u;
+        for (uint32_t i = 0; i < ns; ++i) {
+            uint32_t off = split[i].off;
+            for (uint32_t d = 0; d < 256; ++d) {
+                const uint32_t n = hist[256ull * i + d];
+                if (!n) continue;
+                if (n == split[i].cnt) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: a re-partition level did not split its segment");
+                if (n > kSortRepartAbove) big.push_back(Big{off, n, split[i].bin});
+                else leaves.push_back(SortLeaf{off, n, split[i].bin, src_is_b});
+                off += n;
+            }
+        }
+    }
+    hc.lap("atac sort: re-partition");
+    // ---- leaves, in position order
+    std::sort(leaves.begin(), leaves.end(), [](const SortLeaf& a, const SortLeaf& b) { return a.off < b.off; });
+    const uint32_t n_leaves = (uint32_t)leaves.size();
+    std::vector<uint32_t> ids_small, ids_big, on(n_leaves), lout((size_t)n_leaves + 1, 0);
+    for (uint32_t i = 0; i < n_leaves; ++i) ((leaves[i].flags & 2u) || leaves[i].cnt <= kSortSmallLeaf ? ids_small : ids_big).push_back(i);
+    uint64_t n_out = 0;
+    if (n_leaves) {
+        T(d_leaves.ensure(sizeof(SortLeaf) * n_leaves)); T(d_ids.ensure(4ull * n_leaves)); T(d_on.ensure(4ull * n_leaves)); T(d_lout.ensure(4ull * (n_leaves + 1)));
+        if (e != hipSuccess) return hip_fail();
+        std::vector<uint32_t> ids(ids_small);
+        ids.insert(ids.end(), ids_big.begin(), ids_big.end());
+        T(hipMemcpyAsync(d_leaves.p, leaves.data(), sizeof(SortLeaf) * n_leaves, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(d_ids.p, ids.data(), 4ull * n_leaves, hipMemcpyHostToDevice, s));
+        {   // (the parse's outputs are dead after level 0: the runs' keys and lengths go where they were)
+            ScopedTimer t(c, K_ASORT_LEAF, s);
+            launch_sort_leaves(s, d_leaves.as<SortLeaf>(), d_ids.as<uint32_t>(), (uint32_t)ids_small.size(), d_ids.as<uint32_t>() + ids_small.size(), (uint32_t)ids_big.size(),
+                               d_ka.as<uint64_t>(), d_kb.as<uint64_t>(), d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), d_on.as<uint32_t>());
+        }
+        T(hipGetLastError());
+        T(hipMemcpyAsync(on.data(), d_on.p, 4ull * n_leaves, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (e != hipSuccess) return hip_fail();
+        for (uint32_t i = 0; i < n_leaves; ++i) { n_out += on[i]; lout[i + 1] = (uint32_t)n_out; }
+    }
+    hc.lap("atac sort: leaves");
+    const uint64_t o1 = std::max<uint64_t>(n_out, 1);
+    uint32_t* oref = (uint32_t*)pinned_pool()->get(4 * o1);
+    uint32_t* ostart = (uint32_t*)pinned_pool()->get(4 * o1);
+    uint16_t* oflen = (uint16_t*)pinned_pool()->get(2 * o1);
+    uint64_t* obc = (uint64_t*)pinned_pool()->get(8 * o1);
+    uint32_t* ocnt = (uint32_t*)pinned_pool()->get(4 * o1);
+    auto drop = [&]() { afq_free(oref); afq_free(ostart); afq_free(oflen); afq_free(obc); afq_free(ocnt); };
+    if (!oref || !ostart || !oflen || !obc || !ocnt) { drop(); return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: host allocation failed (" + std::to_string(22 * o1) + " bytes of rows)"); }
+    unsigned long long n_long = 0;
+    if (n_out) {
+        // one allocation, the columns behind one another (8-byte column first)
+        T(d_out.ensure(22 * o1 + 64));
+        if (e != hipSuccess) { drop(); return hip_fail(); }
+        uint8_t* b = d_out.as<uint8_t>();
+        uint64_t* dbc = reinterpret_cast<uint64_t*>(b);
+        uint32_t* dref = reinterpret_cast<uint32_t*>(b + 8 * o1);
+        uint32_t* dstart = reinterpret_cast<uint32_t*>(b + 12 * o1);
+        uint32_t* dcnt = reinterpret_cast<uint32_t*>(b + 16 * o1);
+        uint16_t* dflen = reinterpret_cast<uint16_t*>(b + 20 * o1);
+        T(hipMemcpyAsync(d_lout.p, lout.data(), 4ull * (n_leaves + 1), hipMemcpyHostToDevice, s));
+        {
+            ScopedTimer t(c, K_ASORT_EMIT, s);
+            launch_sort_emit(s, d_leaves.as<SortLeaf>(), n_leaves, d_lout.as<uint32_t>(), d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), d_bbase.as<uint32_t>(), ref_count,
+                             d_rbc.as<uint64_t>(), dref, dstart, dflen, dbc, dcnt, d_tally.as<unsigned long long>());
+        }
+        T(hipGetLastError());
+        T(hipMemcpyAsync(oref, dref, 4 * n_out, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(ostart, dstart, 4 * n_out, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(oflen, dflen, 2 * n_out, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(obc, dbc, 8 * n_out, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(ocnt, dcnt, 4 * n_out, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(&n_long, d_tally.p, 8, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+    }
+    hc.lap("atac sort: emit + D2H");
+    harvest_timers(c);
+    if (e != hipSuccess) { drop(); return hip_fail(); }
+    S.n_distinct = n_out; S.n_long_fragments = n_long;
+    if (stats) *stats = S;
+    *out_n = n_out; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_bc = obc; *out_count = ocnt;
     return 0;
 }
 

@@ -20,6 +20,7 @@ static void usage() {
                  "       [--summary-stat] [--boot-seed S] [--sa-model winner-take-all|prefer-ambig]\n"
                  "resolutions: trivial cr-like cr-like-em parsimony parsimony-em parsimony-gene parsimony-gene-em\n"
                  "       afquant atac deduplicate -i <input-dir> [-t N] [-d fw|rc] [--device N]\n"
+                 "       afquant atac sort -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]\n"
                  "       afquant infer -c <geqc_counts.mtx> -e <gene_eqclass.txt.gz> -o <output-dir> [--usa] [--quant-subset FILE] [-t N]\n");
 }
 
@@ -74,6 +75,32 @@ int main(int argc, char** argv) {
         if (!ao.input_dir) { usage(); return 2; }
         const int rc = afq_atac_deduplicate(&ao);
         if (rc) { std::fprintf(stderr, "afquant atac deduplicate failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        return 0;
+    }
+    if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "sort") == 0) {   // src/main.rs:924-938
+        afq_atac_sort_opts so{};
+        so.num_threads = 0; so.max_records = 30000000;   // -t: min(16, cores), at least 2
+        std::string cmdline;
+        for (int i = 0; i < argc; ++i) { if (i) cmdline += ' '; cmdline += argv[i]; }
+        so.cmdline = cmdline.c_str();
+        auto need3 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        for (int i = 3; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-i" || a == "--input-dir") so.input_dir = need3(i);
+            else if (a == "-r" || a == "--rad-dir") so.rad_dir = need3(i);
+            else if (a == "-t" || a == "--threads") so.num_threads = (uint32_t)std::atoi(need3(i));
+            else if (a == "-c" || a == "--compress") so.compress = 1;
+            else if (a == "-m" || a == "--max-records") so.max_records = (uint32_t)std::strtoul(need3(i), nullptr, 10);
+            else if (a == "--device") so.device = (uint32_t)std::atoi(need3(i));
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!so.input_dir || !so.rad_dir) {
+            std::fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", so.input_dir ? "" : "  --input-dir <INPUTDIR>\n", so.rad_dir ? "" : "  --rad-dir <RADDIR>\n");
+            usage();
+            return 2;
+        }
+        const int rc = afq_atac_sort(&so);
+        if (rc) { std::fprintf(stderr, "afquant atac sort failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         return 0;
     }
     if (argc < 2 || std::strcmp(argv[1], "quant") != 0) { usage(); return 2; }

@@ -226,6 +226,8 @@ struct RadPrelude {
     std::unordered_map<std::string, uint64_t> file_tag_vals;
     size_t first_chunk = 0;
     uint32_t bc_bytes = 0, umi_bytes = 0;
+    std::vector<uint32_t> ref_lengths;   // the ref_lengths file tag (an array of u32), when there is one
+    bool have_ref_lengths = false;
 };
 
 bool read_tag_section(Cursor& c, std::vector<TagDesc>& tags) {
@@ -267,7 +269,11 @@ int parse_prelude(const uint8_t* bytes, size_t n, RadPrelude& P, bool want_names
                 uint64_t len = 0;
                 switch (t.len_type) { case 1: len = c.get<uint8_t>(); break; case 2: len = c.get<uint16_t>(); break; case 3: len = c.get<uint32_t>(); break; case 4: len = c.get<uint64_t>(); break; default: c.ok = false; }
                 const size_t eb = t.elem_type == 5 ? 4 : t.elem_type == 6 ? 8 : t.elem_type == 0 ? 1 : int_type_bytes(t.elem_type);
-                if (!eb || c.p + len * eb > c.n) c.ok = false; else c.p += len * eb;
+                if (!eb || c.p + len * eb > c.n) c.ok = false;
+                else {
+                    if (t.name == "ref_lengths" && t.elem_type == 3) { P.ref_lengths.resize((size_t)len); if (len) std::memcpy(P.ref_lengths.data(), c.b + c.p, (size_t)len * 4); P.have_ref_lengths = true; }
+                    c.p += len * eb;
+                }
                 break;
             }
             case 8: { const uint16_t sl = c.get<uint16_t>(); c.str(sl); break; }
@@ -863,6 +869,282 @@ int afq_atac_deduplicate(const afq_atac_dedup_opts* o) {
     std::fprintf(stderr, "Number of records that are deduplicated %llu\n", (unsigned long long)st.n_deduplicated);
     std::fprintf(stderr, "Number of records that are not mapped pairs %llu\n", (unsigned long long)st.n_not_mapped_pair);
     std::fprintf(stderr, "Number of records that have frag length > 2000 %llu\n", (unsigned long long)st.n_long_fragments);
+    if (o->stats_out) *o->stats_out = st;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// `alevin-fry atac sort` (src/atac/sort.rs:170-895): the mapper's map.rad in, <input_dir>/map.bed[.gz] out.
+//
+// correction_plan.bin (src/correction_plan.rs:20-45, 157-160): magic, u16 version, then bincode (default options: fixed-width
+// little-endian integers, u64 lengths, u8 Option tags, u32 enum variants) of
+//   CorrectionPlan { sample_barcode_len: Option<u8>, cell_barcode_len: u8, sample_spec: Option<CorrectionSpec>,
+//                    sample_corrections: Vec<(u64, u64)>, cell_scopes: Vec<{ sample_barcode: Option<u64>, spec, corrections }> }
+//   CorrectionSpec { barcode_len: u8, neighborhood: enum {HammingOne, SubstitutionOrShiftOne},
+//                    resolution: enum { Unique, Frequency { confidence: {u64, u64}, pseudocount: u64 } } }   (barcode_correction.rs:28-37, 64-67, 209-227)
+// A restatement of serde's derive under bincode, not a reading of bincode's source: parity unpinned.
+namespace {
+bool skip_correction_spec(Cursor& c) {
+    c.get<uint8_t>();
+    if (c.get<uint32_t>() > 1) return false;
+    const uint32_t res = c.get<uint32_t>();
+    if (res == 1) { c.get<uint64_t>(); c.get<uint64_t>(); c.get<uint64_t>(); }
+    else if (res != 0) return false;
+    return c.ok;
+}
+// n corrections at the cursor: counted, and the first `cap` of them written
+bool take_corrections(Cursor& c, uint64_t& n, uint64_t* obs, uint64_t* cor, size_t cap, bool keep) {
+    n = c.get<uint64_t>();
+    if (!c.ok || n > (c.n - c.p) / 16) return false;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t o = c.get<uint64_t>(), k = c.get<uint64_t>();
+        if (keep && obs && cor && i < cap) { obs[i] = o; cor[i] = k; }
+    }
+    return c.ok;
+}
+}  // namespace
+
+int64_t afq_parse_correction_plan(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap, uint32_t* cell_barcode_len) {
+    if (!in && n) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+    static const uint8_t kMagic[8] = {'A', 'F', 'C', 'O', 'R', 'R', 0, 0};
+    if (n < 8) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has a truncated header");
+    if (std::memcmp(in, kMagic, 8) != 0) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has invalid magic");
+    Cursor c{in, n};
+    c.p = 8;
+    const uint16_t ver = c.get<uint16_t>();
+    if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has a truncated header");
+    if (ver != 1) return hfail(AFQ_ERR_BAD_INPUT, "correction plan uses unsupported format version " + std::to_string(ver) + " (expected 1)");
+    const char* trunc = "could not deserialize correction plan: the file is truncated or malformed";
+    const uint8_t has_sample = c.get<uint8_t>();
+    if (!c.ok || has_sample > 1) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    if (has_sample) c.get<uint8_t>();
+    const uint8_t cell_len = c.get<uint8_t>();
+    const uint8_t has_sspec = c.get<uint8_t>();
+    if (!c.ok || has_sspec > 1 || (has_sspec && !skip_correction_spec(c))) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    uint64_t n_sample = 0, n_scopes = 0, n_global = 0;
+    if (!take_corrections(c, n_sample, nullptr, nullptr, 0, false)) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    n_scopes = c.get<uint64_t>();
+    if (!c.ok || n_scopes > c.n) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    bool have_global = false;
+    for (uint64_t i = 0; i < n_scopes; ++i) {
+        const uint8_t has_bc = c.get<uint8_t>();
+        if (!c.ok || has_bc > 1) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+        if (has_bc) c.get<uint64_t>();
+        if (!skip_correction_spec(c)) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+        uint64_t cnt = 0;
+        const bool global = !has_bc && !have_global;
+        if (!take_corrections(c, cnt, observed, corrected, cap, global)) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+        if (global) { have_global = true; n_global = cnt; }
+    }
+    if (c.p != c.n) return hfail(AFQ_ERR_BAD_INPUT, "correction plan contains trailing data");
+    if (has_sample) return hfail(AFQ_ERR_BAD_INPUT, "correction plan does not match this ATAC input: it is sample-scoped");   // sort.rs:453-455
+    if (!have_global) return hfail(AFQ_ERR_BAD_INPUT, "ATAC correction plan has no global cell scope");                         // sort.rs:456-460
+    if (cell_barcode_len) *cell_barcode_len = cell_len;
+    return (int64_t)n_global;
+}
+
+int64_t afq_parse_permit_map(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap) {
+    if (!in && n) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+    Cursor c{in, n};
+    uint64_t cnt = 0;
+    if (n < 8) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize legacy permit_map.bin: truncated length");
+    if (!take_corrections(c, cnt, observed, corrected, cap, true)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize legacy permit_map.bin: truncated entries");
+    if (c.p != c.n) return hfail(AFQ_ERR_BAD_INPUT, "legacy permit_map.bin contains trailing data");
+    return (int64_t)cnt;
+}
+
+int afq_atac_sort(const afq_atac_sort_opts* o) {
+    if (!o || !o->input_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (!o->rad_dir) return hfail(AFQ_ERR_INVALID_ARG, "the RAD directory (-r) is required");
+    const std::string in = o->input_dir, rd = o->rad_dir;
+    // ---- generate_permit_list.json (sort.rs:189-216, atac/collate.rs:235-245)
+    std::vector<uint8_t> gj;
+    if (!read_file(in + "/generate_permit_list.json", gj)) return hfail(AFQ_ERR_BAD_INPUT, "Could not open the file \"" + in + "/generate_permit_list.json\".");
+    const std::string gjs(gj.begin(), gj.end());
+    auto value_at = [&](const char* key, size_t from) -> size_t {   // offset of the value of "key", or npos
+        const std::string k = std::string("\"") + key + "\"";
+        const size_t at = gjs.find(k, from);
+        if (at == std::string::npos) return at;
+        return gjs.find_first_not_of(" \t\r\n:", at + k.size());
+    };
+    if (value_at("version_str", 0) == std::string::npos)
+        return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
+    bool rc_flag = false;
+    {
+        const size_t g = gjs.find("\"gpl_options\"");
+        const size_t v = g == std::string::npos ? g : value_at("rc", g);
+        if (v == std::string::npos || (gjs.compare(v, 4, "true") != 0 && gjs.compare(v, 5, "false") != 0)) return hfail(AFQ_ERR_BAD_INPUT, "generate_permit_list.json: gpl_options.rc must be a boolean");
+        rc_flag = gjs.compare(v, 4, "true") == 0;
+    }
+    if (!file_exists(in + "/bin_recs.bin") || !file_exists(in + "/bin_lens.bin")) return hfail(AFQ_ERR_BAD_INPUT, "bin file containing records does not exist");
+    // ---- permit_freq.bin: version, barcode length (sort.rs:234-262)
+    std::vector<uint8_t> pf;
+    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 16) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
+    uint64_t pf_ver, bc_len;
+    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8);
+    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
+    uint64_t num_chunks = 0;
+    {
+        const size_t v = value_at("num-chunks", 0);
+        if (v == std::string::npos) return hfail(AFQ_ERR_BAD_INPUT, "num-chunks key not present");
+        char* e = nullptr;
+        num_chunks = std::strtoull(gjs.c_str() + v, &e, 10);
+        if (e == gjs.c_str() + v) return hfail(AFQ_ERR_BAD_INPUT, "Error parsing num-chunks");
+    }
+    // ---- sort.json (sort.rs:342-357)
+    {
+        FilePtr f(std::fopen((in + "/sort.json").c_str(), "w"));
+        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": %s\n}", json_escape(o->cmdline ? o->cmdline : "").c_str(), o->compress ? "true" : "false");
+    }
+    if (!file_exists(rd)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + rd + "\" does not exist");
+    PhaseClock pc;
+    std::thread warm([dev = (int)o->device]() { afq_device_warmup(dev); });
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } warm_join{warm};
+    MappedFile mf;
+    if (!mf.open(rd + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open input RAD file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, true);
+    if (rc) return rc;
+    if (P.read_tags.size() != 1 || P.read_tags[0].name != "b" || !P.bc_bytes) return hfail(AFQ_ERR_UNSUPPORTED, "scATAC RAD: the read-level tags must be exactly one integer 'b'");
+    static const struct { const char* name; uint8_t type; } kAln[4] = {{"ref", 3}, {"type", 1}, {"start_pos", 3}, {"frag_len", 2}};
+    bool aln_ok = P.aln_tags.size() == 4;
+    for (size_t i = 0; aln_ok && i < 4; ++i) aln_ok = P.aln_tags[i].name == kAln[i].name && P.aln_tags[i].type == kAln[i].type;
+    if (!aln_ok) return hfail(AFQ_ERR_UNSUPPORTED, "scATAC RAD: the alignment-level tags must be ref:u32, type:u8, start_pos:u32, frag_len:u16");
+    if (!P.file_tag_vals.count("cblen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain cblen");
+    const uint32_t cblen = (uint32_t)P.file_tag_vals["cblen"];
+    if (!P.have_ref_lengths || P.ref_lengths.size() != P.ref_count) return hfail(AFQ_ERR_BAD_INPUT, "scATAC RAD: the ref_lengths file tag must be an array of u32 with one entry per reference");
+    // ---- the correction map: the plan if there is one, else the legacy map (sort.rs:450-479)
+    std::vector<uint64_t> obs, cor;
+    {
+        std::vector<uint8_t> cm;
+        const bool plan = file_exists(in + "/correction_plan.bin");
+        if (plan) {
+            if (!read_file(in + "/correction_plan.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "could not open correction plan " + in + "/correction_plan.bin");
+            uint32_t cell_len = 0;
+            const int64_t n = afq_parse_correction_plan(cm.data(), cm.size(), nullptr, nullptr, 0, &cell_len);
+            if (n < 0) return (int)n;
+            if (cell_len != bc_len) return hfail(AFQ_ERR_BAD_INPUT, "correction plan does not match this ATAC input");
+            obs.resize((size_t)n); cor.resize((size_t)n);
+            afq_parse_correction_plan(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n, nullptr);
+        } else {
+            std::fprintf(stderr, "No correction_plan.bin was found; loading legacy permit_map.bin for ATAC sorting\n");
+            if (!read_file(in + "/permit_map.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open legacy permit_map.bin file");
+            const int64_t n = afq_parse_permit_map(cm.data(), cm.size(), nullptr, nullptr, 0);
+            if (n < 0) return (int)n;
+            obs.resize((size_t)n); cor.resize((size_t)n);
+            afq_parse_permit_map(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n);
+        }
+    }
+    // ---- unmapped_bc_count.bin -> unmapped_bc_count_collated.bin (atac/collate.rs:247-283)
+    {
+        std::vector<uint8_t> ub;
+        if (!read_file(rd + "/unmapped_bc_count.bin", ub)) return hfail(AFQ_ERR_BAD_INPUT, "could not open " + rd + "/unmapped_bc_count.bin");
+        std::unordered_map<uint64_t, uint64_t> cmap;
+        cmap.reserve(obs.size() * 2);
+        for (size_t i = 0; i < obs.size(); ++i) cmap.emplace(obs[i], cor[i]);
+        std::unordered_map<uint64_t, uint32_t> cnt;
+        for (size_t p = 0; p + 12 <= ub.size(); p += 12) {
+            uint64_t k; uint32_t v;
+            std::memcpy(&k, ub.data() + p, 8); std::memcpy(&v, ub.data() + p + 8, 4);
+            auto it = cmap.find(k);
+            if (it != cmap.end()) cnt[it->second] += v;
+        }
+        FilePtr f(std::fopen((in + "/unmapped_bc_count_collated.bin").c_str(), "wb"));
+        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create serialization file.");
+        const uint64_t n = cnt.size();
+        std::fwrite(&n, 8, 1, f.get());
+        for (auto& kv : cnt) { std::fwrite(&kv.first, 8, 1, f.get()); std::fwrite(&kv.second, 4, 1, f.get()); }
+    }
+    // ---- exactly num-chunks chunk headers (sort.rs:670)
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || p + nb > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
+    pc.lap("map + prelude + maps + chunk table");
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    warm.join();
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    const uint64_t span0 = chunk_off.empty() ? 0 : chunk_off[0];
+    std::vector<uint64_t> rel(chunk_off.size());
+    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    uint64_t n_rows = 0, *obc = nullptr; uint32_t *oref = nullptr, *ostart = nullptr, *ocnt = nullptr; uint16_t* oflen = nullptr;
+    afq_atac_sort_stats st{};
+    rc = afq_atac_sort_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, 0, obs.data(), cor.data(), obs.size(),
+                           P.ref_lengths.data(), (uint32_t)P.ref_count, &n_rows, &oref, &ostart, &oflen, &obc, &ocnt, &st);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer { void *a, *b, *c2, *d, *e; ~Freer() { afq_free(a); afq_free(b); afq_free(c2); afq_free(d); afq_free(e); } } fr{oref, ostart, oflen, obc, ocnt};
+    pc.lap("device: parse + sort");
+    // ---- write_bed_string (sort.rs:66-88), the rows cut over the threads
+    const unsigned nthreads = std::max(2u, o->num_threads ? o->num_threads : std::min(16u, std::thread::hardware_concurrency()));   // main.rs:856, 934
+    const unsigned nth = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)nthreads, 64, n_rows / 65536 + 1}));
+    std::vector<std::string> txt(nth);
+    std::vector<int> bad(nth, 0);
+    {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nth; ++t)
+            th.emplace_back([&, t]() {
+                std::string& out = txt[t];
+                char num[32];
+                for (uint64_t k = n_rows * t / nth; k < n_rows * (t + 1) / nth; ++k) {
+                    if (oflen[k] >= 2000) continue;
+                    if (oref[k] >= P.ref_names.size()) { bad[t] = 1; return; }
+                    uint64_t bc = obc[k];
+                    if (rc_flag) {   // needletail::bitkmer::reverse_complement
+                        uint64_t r = 0;
+                        for (uint32_t q = 0; q < cblen; ++q) { r = (r << 2) | (3 - (bc & 3)); bc >>= 2; }
+                        bc = r;
+                    }
+                    out += P.ref_names[oref[k]]; out += '\t';
+                    *put_u64(num, ostart[k]) = 0; out += num; out += '\t';
+                    *put_u64(num, (unsigned long long)(uint32_t)(ostart[k] + (uint32_t)oflen[k])) = 0; out += num; out += '\t';
+                    out += bc_to_string(bc, cblen); out += '\t';
+                    *put_u64(num, ocnt[k]) = 0; out += num; out += '\n';
+                }
+            });
+        for (auto& x : th) x.join();
+    }
+    for (int b2 : bad) if (b2) return hfail(AFQ_ERR_BAD_INPUT, "a fragment's reference id is beyond the RAD header's reference names");
+    if (o->compress) {   // sort.rs:852-854
+        gzFile gz = gzopen((in + "/map.bed.gz").c_str(), "wb");
+        if (!gz) return hfail(AFQ_ERR_BAD_INPUT, "could not create map.bed.gz");
+        for (auto& tx : txt)
+            for (size_t off = 0; off < tx.size();) {
+                const unsigned len = (unsigned)std::min<size_t>(tx.size() - off, 1u << 30);
+                if (gzwrite(gz, tx.data() + off, len) <= 0) { gzclose(gz); return hfail(AFQ_ERR_BAD_INPUT, "could not write map.bed.gz"); }
+                off += len;
+            }
+        if (gzclose(gz) != Z_OK) return hfail(AFQ_ERR_BAD_INPUT, "could not write map.bed.gz");
+    } else {
+        FilePtr bed(std::fopen((in + "/map.bed").c_str(), "w"));
+        if (!bed) return hfail(AFQ_ERR_BAD_INPUT, "could not create map.bed");
+        for (auto& tx : txt) if (!tx.empty() && std::fwrite(tx.data(), 1, tx.size(), bed.get()) != tx.size()) return hfail(AFQ_ERR_BAD_INPUT, "could not write map.bed");
+    }
+    pc.lap("map.bed");
+    std::fprintf(stderr, "deserialized correction map of length : %llu\n", (unsigned long long)obs.size());
+    std::fprintf(stderr, "finished parsing RAD file; processed %llu total records\n", (unsigned long long)st.n_records);
+    std::fprintf(stderr, "Number of records without a mapping %llu\n", (unsigned long long)st.n_unmapped);
+    std::fprintf(stderr, "Number of records with greater than 1 mapping %llu\n", (unsigned long long)st.n_multimapped);
+    std::fprintf(stderr, "Number of records whose barcode is not in the correction map %llu\n", (unsigned long long)st.n_uncorrected);
+    std::fprintf(stderr, "Number of fragments sorted %llu\n", (unsigned long long)st.n_kept);
+    std::fprintf(stderr, "Number of rows (distinct fragments) %llu\n", (unsigned long long)st.n_distinct);
+    std::fprintf(stderr, "Number of distinct fragments that have frag length >= 2000 %llu\n", (unsigned long long)st.n_long_fragments);
+    std::fprintf(stderr, "Number of position bins that were partitioned again %llu\n", (unsigned long long)st.n_repartitioned_bins);
     if (o->stats_out) *o->stats_out = st;
     return 0;
 }

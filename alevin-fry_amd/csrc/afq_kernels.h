@@ -186,6 +186,39 @@ void launch_atac_compact(hipStream_t s, uint32_t n_cells, const uint64_t* cell_p
                          const uint32_t* i_start, const uint16_t* i_flen, const uint16_t* i_cnt, uint32_t* o_ref, uint32_t* o_start,
                          uint16_t* o_flen, uint16_t* o_cnt, unsigned long long* tally = nullptr, uint4* runs = nullptr, uint32_t* run_ctr = nullptr,
                          uint32_t run_cap = 0);
+// `atac sort`: the fragments of an UNCOLLATED scATAC RAD in one global (ref, start, frag_len, barcode) order (afq_atac_sort.hip)
+constexpr uint32_t kSortBinShift = 17;        // a position bin is 2^17 bases of one reference
+constexpr uint32_t kSortLeafCap = 16384;      // keys one workgroup sorts in a single LDS tile
+constexpr uint32_t kSortRepartAbove = kSortLeafCap;   // a segment with more keys is partitioned again by its next key bits
+constexpr uint32_t kSortParseTile = 4096;     // bytes of a chunk a wave stages in LDS per trip
+constexpr uint32_t kSortRadixBits = 8;        // digit width of a re-partition level
+constexpr uint32_t kSortSmallLeaf = 2048;     // leaves up to this size are sorted by a 256-thread workgroup
+constexpr uint32_t kSortNoBin = 0xFFFFFFFFu;  // an output slot of the parse that holds no fragment
+constexpr uint32_t kSortNoRank = 0xFFFFFFFFu;
+constexpr uint64_t kSortEmptyKey = ~0ull;     // free slot of the correction table (the all-ones barcode travels as SortParseArgs::ones_rank)
+struct SortChunk { uint64_t chunk_off; uint64_t out_off; uint32_t nbytes; uint32_t nrec; };
+struct SortParseArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks; uint32_t bc_bytes;
+    const uint64_t* tab_key; const uint32_t* tab_val; uint32_t tab_mask; uint32_t ones_rank;
+    const uint2* ref_info;   // [ref_count] (length, first bin)
+    uint32_t ref_count;
+    uint32_t* o_bin; uint64_t* o_key;   // a slot per record of the chunk table: the kept ones first, kSortNoBin behind them
+    uint32_t* chunk_stat;    // [n_chunks][4]: na == 0, na > 1, barcode not in the map, kept
+    DevStatus* st;
+};
+struct SortSeg { uint32_t off, cnt, hist_base, shift; };    // a run of keys to partition: digit = (key >> shift) & 255, counted at hist[hist_base + digit]
+struct SortLeaf { uint32_t off, cnt, bin, flags; };         // flags: bit 0 = the keys sit in the second buffer, bit 1 = all keys are equal
+void launch_sort_table(hipStream_t s, const uint64_t* observed, const uint32_t* rank, uint64_t n, uint64_t* tab_key, uint32_t* tab_val, uint32_t tab_mask, DevStatus* st);
+void launch_sort_parse(hipStream_t s, const SortParseArgs& a);
+// level 0 (bins != nullptr): one segment, the digit of slot i is bins[i] (n_sub bins); above: 256 digits of the keys
+void launch_sort_partition(hipStream_t s, const SortSeg* segs, uint32_t n_seg, uint32_t max_cnt, const uint64_t* keys, const uint32_t* bins, uint32_t n_sub,
+                           uint32_t* hist, uint32_t* cursor, uint64_t* dst);
+void launch_sort_bits(hipStream_t s, const SortSeg* segs, uint32_t n_seg, uint32_t max_cnt, const uint64_t* keys, uint64_t* and_or);
+void launch_sort_leaves(hipStream_t s, const SortLeaf* leaves, const uint32_t* ids_small, uint32_t n_small, const uint32_t* ids_big, uint32_t n_big,
+                        uint64_t* buf_a, uint64_t* buf_b, uint64_t* o_key, uint32_t* o_cnt, uint32_t* o_n);
+void launch_sort_emit(hipStream_t s, const SortLeaf* leaves, uint32_t n_leaves, const uint32_t* leaf_out, const uint64_t* i_key, const uint32_t* i_cnt,
+                      const uint32_t* bin_base, uint32_t ref_count, const uint64_t* rank_bc, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,
+                      uint64_t* o_bc, uint32_t* o_cnt, unsigned long long* n_long);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

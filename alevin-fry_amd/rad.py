@@ -305,6 +305,64 @@ def encode_atac_cells(cells, bc_bytes: int = 4):
     return bytes(out), np.asarray(offs, dtype=np.uint64)
 
 
+def encode_atac_chunks(chunks, bc_bytes: int = 4):
+    """chunks of an UNCOLLATED scATAC RAD: a list of chunks, each a list of records (bc, [(ref, type, start, frag_len), ...]) -
+    a barcode per record.  Returns (bytes, chunk_off[u64])."""
+    out = bytearray()
+    offs = []
+    for recs in chunks:
+        offs.append(len(out))
+        body = bytearray()
+        for bc, alns in recs:
+            body += len(alns).to_bytes(4, "little") + int(bc).to_bytes(bc_bytes, "little")
+            for ref, ty, start, fl in alns:
+                body += int(ref).to_bytes(4, "little") + bytes([ty]) + int(start).to_bytes(4, "little") + int(fl).to_bytes(2, "little")
+        out += (len(body) + 8).to_bytes(4, "little") + len(recs).to_bytes(4, "little") + body
+    return bytes(out), np.asarray(offs, dtype=np.uint64)
+
+
+def _correction_spec_bytes(barcode_len, spec) -> bytes:
+    """bincode of CorrectionSpec (src/barcode_correction.rs:28-37, 209-227).  spec: "unique" or
+    ("frequency", (numerator, denominator), pseudocount); the neighbourhood is HammingOne."""
+    out = bytes([barcode_len]) + (0).to_bytes(4, "little")
+    if spec == "unique":
+        return out + (0).to_bytes(4, "little")
+    _, (num, den), pseudo = spec
+    return out + (1).to_bytes(4, "little") + int(num).to_bytes(8, "little") + int(den).to_bytes(8, "little") + int(pseudo).to_bytes(8, "little")
+
+
+def _corrections_bytes(pairs) -> bytes:
+    a = np.asarray(pairs, dtype=np.uint64).reshape(-1, 2)
+    return len(a).to_bytes(8, "little") + a.astype("<u8").tobytes()
+
+
+def correction_plan_bytes(pairs, barcode_len: int = 16, spec="unique", sample_barcode_len=None, sample_scopes=(), version: int = 1,
+                          magic: bytes = b"AFCORR\0\0") -> bytes:
+    """correction_plan.bin (src/correction_plan.rs:20-45, 157-160): magic, u16 version, bincode of CorrectionPlan with one
+    global cell scope holding `pairs` ((observed, corrected), written in observed order as write_to does).  sample_barcode_len /
+    sample_scopes ((sample barcode, pairs), ...) make the sample-scoped shapes the ATAC reader refuses."""
+    pairs = sorted((int(o), int(c)) for o, c in pairs)
+    out = bytearray(magic) + int(version).to_bytes(2, "little")
+    out += b"\x00" if sample_barcode_len is None else bytes([1, sample_barcode_len])
+    out += bytes([barcode_len]) + b"\x00" + (0).to_bytes(8, "little")   # no sample spec, no sample corrections
+    scopes = [(None, pairs)] + [(int(sb), sorted((int(o), int(c)) for o, c in pp)) for sb, pp in sample_scopes]
+    out += len(scopes).to_bytes(8, "little")
+    for sb, pp in scopes:
+        out += b"\x00" if sb is None else b"\x01" + sb.to_bytes(8, "little")
+        out += _correction_spec_bytes(barcode_len, spec) + _corrections_bytes(pp)
+    return bytes(out)
+
+
+def permit_map_bytes(pairs) -> bytes:
+    """The legacy permit_map.bin: bincode HashMap<u64, u64> - a u64 count, then (observed, corrected) pairs."""
+    return _corrections_bytes([(int(o), int(c)) for o, c in pairs])
+
+
+def permit_freq_header(barcode_len: int, version: int = 1) -> bytes:
+    """permit_freq.bin as far as `atac sort` reads it: u64 version, u64 barcode length, an empty bincode HashMap behind them."""
+    return int(version).to_bytes(8, "little") + int(barcode_len).to_bytes(8, "little") + (0).to_bytes(8, "little")
+
+
 def collation_manifest(groups, level_names=("sample", "cell")) -> bytes:
     """collation_manifest.bin in the layout csrc/afq_host.cpp reads (bincode of libradicl's CollationManifest - a
     restatement, libradicl's source is not in the reference tree).  groups: (key, name or None, chunk_start, num_chunks,

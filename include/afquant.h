@@ -267,6 +267,42 @@ int afq_atac_dedup_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const
                        uint32_t** out_start, uint16_t** out_frag_len, uint16_t** out_count, afq_atac_stats* stats);
 
 /*
+ * `alevin-fry atac sort` (src/atac/sort.rs) on the device: every record of an UNCOLLATED scATAC RAD - the mapper's chunks, whose
+ * records carry a barcode each - is walked, a record is kept iff it has exactly one alignment (sort.rs:121-123; no map_type
+ * filter, unlike deduplicate) and its barcode is one of `observed`, and the kept fragments come back as the distinct
+ * (ref, start, frag_len, corrected barcode) tuples in that order (barcode as an integer, sort.rs:47-59) with their multiplicity
+ * (u32: the reference counts in a usize, sort.rs:74).  Fragments of 2000 bases and more are INCLUDED (the cut at sort.rs:75
+ * belongs to the writer) and counted in n_long_fragments.
+ *   observed / corrected : the correction map, n_corrections pairs in any order; the same pair twice is fine, one observed
+ *                          barcode with two corrected ones is AFQ_ERR_BAD_INPUT
+ *   ref_lengths          : the prelude's ref_lengths tag; ref >= ref_count or start_pos >= ref_lengths[ref] in a record with one
+ *                          alignment is AFQ_ERR_BAD_INPUT, as are records that do not tile their chunk or do not number its
+ *                          nrec - the message names the chunk, nothing outside `bytes` is read, the context stays usable
+ * Limits (AFQ_ERR_UNSUPPORTED): 2^32 records, 2^31 distinct corrected barcodes, 2^31 position bins, 2^30 map entries per call.
+ * An input that does not fit the device with its staging is AFQ_ERR_OOM (sizes in the message); one call is one device fill.
+ * `bytes` / `chunk_off` / bytes_on_device as for afq_atac_dedup_rad.  Free each output array with afq_free().
+ */
+typedef struct afq_atac_sort_stats {
+    uint64_t n_records;             /* records read                                                        */
+    uint64_t n_unmapped;            /* records without an alignment                                        */
+    uint64_t n_multimapped;         /* records with more than one                                          */
+    uint64_t n_uncorrected;         /* one alignment, barcode not in the map                               */
+    uint64_t n_kept;                /* fragments sorted                                                    */
+    uint64_t n_distinct;            /* rows returned                                                       */
+    uint64_t n_long_fragments;      /* rows with frag_len >= 2000                                          */
+    uint64_t n_repartitioned_bins;  /* position bins above the leaf cap, split again by their key bits     */
+} afq_atac_sort_stats;
+int afq_atac_sort_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks,
+                      uint32_t bc_bytes, int bytes_on_device, const uint64_t* observed, const uint64_t* corrected,
+                      uint64_t n_corrections, const uint32_t* ref_lengths, uint32_t ref_count, uint64_t* out_n, uint32_t** out_ref,
+                      uint32_t** out_start, uint16_t** out_frag_len, uint64_t** out_bc, uint32_t** out_count,
+                      afq_atac_sort_stats* stats);
+/* out[0] = bin shift S (a position bin is 2^S bases), out[1] = leaf cap (keys one workgroup sorts in LDS), out[2] = a segment
+ * with MORE keys than this is partitioned again, out[3] = bytes of a chunk the parse stages per trip.  For tests, which derive
+ * their boundary shapes from these. */
+void afq_atac_sort_limits(uint32_t out[4]);
+
+/*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the
  * number of kernels, or a negative error.  `name[i]` points to static storage.

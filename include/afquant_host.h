@@ -71,6 +71,22 @@ typedef struct afq_atac_dedup_opts {
 /* Runs the whole `atac deduplicate` sub-command (src/atac/deduplicate.rs:68-309) on the device: <input_dir>/map.bed. */
 int afq_atac_deduplicate(const afq_atac_dedup_opts* opts);
 
+/* The options of `alevin-fry atac sort` (src/main.rs:924-938). */
+struct afq_atac_sort_stats;
+typedef struct afq_atac_sort_opts {
+    const char* input_dir;      /* -i : output directory of `atac generate-permit-list`; map.bed[.gz], sort.json and
+                                        unmapped_bc_count_collated.bin are written here                                    */
+    const char* rad_dir;        /* -r : the mapper's directory: map.rad, unmapped_bc_count.bin                             */
+    uint32_t num_threads;       /* -t : BED formatting threads (0 = all cores)                                            */
+    uint32_t compress;          /* -c : map.bed.gz instead of map.bed                                                     */
+    uint32_t max_records;       /* -m : accepted and ignored (it sizes the reference's host buffers)                      */
+    uint32_t device;
+    const char* cmdline;        /* optional: goes into sort.json                                                          */
+    struct afq_atac_sort_stats* stats_out;   /* optional */
+} afq_atac_sort_opts;
+/* Runs the whole `atac sort` sub-command (src/atac/sort.rs:170-895): the coordinate-sorted, de-duplicated BED of an uncollated RAD. */
+int afq_atac_sort(const afq_atac_sort_opts* opts);
+
 /* Runs the whole `quant` sub-command.  Returns 0 or a negative AFQ_ERR_* code; message via afq_host_last_error(). */
 int afq_quantify(const afq_quant_opts* opts);
 const char* afq_host_last_error(void);
@@ -80,6 +96,13 @@ const char* afq_host_last_error(void);
 int afq_format_f32(float v, char* buf, size_t cap);
 /* Snappy *frame format* decode (what `snap::read::FrameDecoder` undoes, src/quant.rs:376). out may be NULL to size. */
 int64_t afq_snappy_frame_decode(const uint8_t* in, size_t n, uint8_t* out, size_t cap);
+/* correction_plan.bin (src/correction_plan.rs: magic "AFCORR\0\0", u16 version 1, bincode of CorrectionPlan) and the legacy
+ * permit_map.bin (bincode HashMap<u64, u64>).  Each returns the number of corrections of the global cell scope, or a negative
+ * error with its reason in afq_host_last_error(): truncated file, bad magic, wrong version, trailing data, a sample-scoped
+ * plan.  observed / corrected may both be NULL to size; otherwise they hold `cap` entries and at most `cap` are written.
+ * cell_barcode_len (may be NULL) receives the plan's barcode length. */
+int64_t afq_parse_correction_plan(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap, uint32_t* cell_barcode_len);
+int64_t afq_parse_permit_map(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap);
 /* Parse a RAD prelude; fills the scalars, returns the byte offset of the first chunk or a negative error. */
 typedef struct afq_rad_info {
     uint64_t ref_count, num_chunks, first_chunk_off;
