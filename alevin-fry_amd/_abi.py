@@ -124,6 +124,8 @@ EXPORTS = [
     "afq_atac_dedup_rad",
     "afq_atac_sort_rad",
     "afq_atac_sort_limits",
+    "afq_atac_sort_leaf_limits",
+    "afq_atac_sort_table_slot",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",

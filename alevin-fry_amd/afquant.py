@@ -295,6 +295,10 @@ def load_library(path: str = LIB_PATH):
     lib.afq_atac_sort_rad.restype = C.c_int
     lib.afq_atac_sort_limits.argtypes = [p(C.c_uint32)]
     lib.afq_atac_sort_limits.restype = None
+    lib.afq_atac_sort_leaf_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_atac_sort_leaf_limits.restype = None
+    lib.afq_atac_sort_table_slot.argtypes = [C.c_uint64, C.c_uint64, p(C.c_uint32), p(C.c_uint32)]
+    lib.afq_atac_sort_table_slot.restype = None
     lib.afq_free.argtypes = [C.c_void_p]
     lib.afq_free.restype = None
     lib.afq_get_kernel_times.argtypes = [C.c_void_p, p(AfqKernelTime), C.c_uint32]
@@ -312,10 +316,20 @@ def load_library(path: str = LIB_PATH):
 
 
 def atac_sort_limits():
-    """afq_atac_sort_limits: {"bin_shift", "leaf_cap", "repartition_above", "parse_tile"} of the `atac sort` kernels."""
-    out = (C.c_uint32 * 4)()
+    """afq_atac_sort_limits and afq_atac_sort_leaf_limits: {"bin_shift", "leaf_cap", "repartition_above", "parse_tile", "small_leaf",
+    "small_leaf_threads", "leaf_threads", "parse_halo"} of the `atac sort` kernels."""
+    out, leaf = (C.c_uint32 * 4)(), (C.c_uint32 * 4)()
     load_library().afq_atac_sort_limits(out)
-    return {"bin_shift": int(out[0]), "leaf_cap": int(out[1]), "repartition_above": int(out[2]), "parse_tile": int(out[3])}
+    load_library().afq_atac_sort_leaf_limits(leaf)
+    return {"bin_shift": int(out[0]), "leaf_cap": int(out[1]), "repartition_above": int(out[2]), "parse_tile": int(out[3]),
+            "small_leaf": int(leaf[0]), "small_leaf_threads": int(leaf[1]), "leaf_threads": int(leaf[2]), "parse_halo": int(leaf[3])}
+
+
+def atac_sort_table_slot(barcode, n_corr):
+    """afq_atac_sort_table_slot: (home slot of `barcode`, capacity) of the correction table afq_atac_sort_rad builds for n_corr entries."""
+    slot, cap = C.c_uint32(), C.c_uint32()
+    load_library().afq_atac_sort_table_slot(int(barcode), int(n_corr), C.byref(slot), C.byref(cap))
+    return int(slot.value), int(cap.value)
 
 
 class _Held(np.ndarray):
@@ -501,6 +515,11 @@ class Quantifier:
     def atac_sort_limits():
         """The `atac sort` kernels' limits (module-level atac_sort_limits)."""
         return atac_sort_limits()
+
+    @staticmethod
+    def atac_sort_table_slot(barcode, n_corr):
+        """Home slot and capacity of the `atac sort` correction table (module-level atac_sort_table_slot)."""
+        return atac_sort_table_slot(barcode, n_corr)
 
     def atac_sort_rad(self, chunk_bytes, chunk_off, observed, corrected, ref_lengths, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0):
         """afq_atac_sort_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the

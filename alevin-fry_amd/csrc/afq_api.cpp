@@ -2408,6 +2408,17 @@ void afq_atac_sort_limits(uint32_t out[4]) {
     out[0] = kSortBinShift; out[1] = kSortLeafCap; out[2] = kSortRepartAbove; out[3] = kSortParseTile;
 }
 
+void afq_atac_sort_leaf_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSortSmallLeaf; out[1] = (uint32_t)kSortSmallLeafNT; out[2] = (uint32_t)kSortLeafNT; out[3] = kSortParseHalo;
+}
+
+void afq_atac_sort_table_slot(uint64_t barcode, uint64_t n_corr, uint32_t* home_slot, uint32_t* capacity) {
+    const uint64_t cap = sort_table_capacity(n_corr < (1ull << 30) ? n_corr : (1ull << 30) - 1);   // (afq_atac_sort_rad refuses 2^30 entries and more)
+    if (home_slot) *home_slot = sort_hash_bc(barcode) & (uint32_t)(cap - 1);
+    if (capacity) *capacity = (uint32_t)cap;
+}
+
 int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
                       int bytes_on_device, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint32_t* ref_lengths,
                       uint32_t ref_count, uint64_t* out_n, uint32_t** out_ref, uint32_t** out_start, uint16_t** out_frag_len, uint64_t** out_bc,
@@ -2473,8 +2484,7 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
         n_slots += nr;
     }
     if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + ")");
-    uint64_t cap = 2;
-    while (cap < 2 * n_corr) cap <<= 1;
+    const uint64_t cap = sort_table_capacity(n_corr);
     const uint32_t tab_mask = (uint32_t)(cap - 1);
     // ---- does it fit?  (input + staging, 12 bytes a record of parse output, two key buffers, 22 bytes a row of output, the tables)
     const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);

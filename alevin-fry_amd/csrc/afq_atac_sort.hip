@@ -25,11 +25,6 @@ namespace afq {
 
 namespace {
 
-__device__ __forceinline__ uint32_t hash_bc(uint64_t x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-    return (uint32_t)x;
-}
-
 // ---- correction table: open addressing, 64-bit keys claimed by CAS (several workgroups share a slot word: agent scope)
 __global__ __launch_bounds__(256) void k_sort_table_insert(const uint64_t* __restrict__ observed, const uint32_t* __restrict__ rank, uint64_t n,
                                                           uint64_t* __restrict__ tab_key, uint32_t* __restrict__ tab_val, uint32_t mask) {
@@ -37,7 +32,7 @@ __global__ __launch_bounds__(256) void k_sort_table_insert(const uint64_t* __res
     if (i >= n) return;
     const uint64_t k = observed[i];
     if (k == kSortEmptyKey) return;   // (the host carries this one)
-    uint32_t slot = hash_bc(k) & mask;
+    uint32_t slot = sort_hash_bc(k) & mask;
     for (uint32_t probe = 0; probe <= mask; ++probe) {
         const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(tab_key + slot), (unsigned long long)kSortEmptyKey, (unsigned long long)k);
         if (prev == kSortEmptyKey) { tab_val[slot] = rank[i]; return; }
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void k_sort_table_verify(const uint64_t* __res
     if (i >= n) return;
     const uint64_t k = observed[i];
     if (k == kSortEmptyKey) return;
-    uint32_t slot = hash_bc(k) & mask;
+    uint32_t slot = sort_hash_bc(k) & mask;
     for (uint32_t probe = 0; probe <= mask; ++probe) {
         const uint64_t kk = tab_key[slot];
         if (kk == k) { if (tab_val[slot] != rank[i]) set_err(st, kErrCorrection, (uint32_t)i); return; }
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(256) void k_sort_table_verify(const uint64_t* __res
 
 __device__ __forceinline__ uint32_t table_find(const SortParseArgs& a, uint64_t k) {
     if (k == kSortEmptyKey) return a.ones_rank;
-    uint32_t slot = hash_bc(k) & a.tab_mask;
+    uint32_t slot = sort_hash_bc(k) & a.tab_mask;
     for (uint32_t probe = 0; probe <= a.tab_mask; ++probe) {   // (at most half the slots are taken: an empty one ends the probe)
         const uint64_t kk = a.tab_key[slot];
         if (kk == k) return a.tab_val[slot];
@@ -78,7 +73,7 @@ __device__ __forceinline__ uint32_t table_find(const SortParseArgs& a, uint64_t 
 // ---- parse + correct
 constexpr int kSortParseNT = 256;
 constexpr uint32_t kParseWaves = kSortParseNT / 64;
-constexpr uint32_t kHalo = 24;   // a record that starts inside the tile: its head (4 + 8) and ONE alignment (11) are staged with it
+constexpr uint32_t kHalo = kSortParseHalo;
 constexpr uint32_t kTileWords = (3 + kSortParseTile + kHalo + 3) / 4 + 1;   // (+ the dword an unaligned 4-byte read of the last bytes also touches)
 constexpr uint32_t kTileRecs = kSortParseTile / 5 + 1;   // the shortest record is na = 0 with a 1-byte barcode
 
@@ -363,8 +358,8 @@ void launch_sort_bits(hipStream_t s, const SortSeg* segs, uint32_t n_seg, uint32
 
 void launch_sort_leaves(hipStream_t s, const SortLeaf* leaves, const uint32_t* ids_small, uint32_t n_small, const uint32_t* ids_big, uint32_t n_big,
                         uint64_t* buf_a, uint64_t* buf_b, uint64_t* o_key, uint32_t* o_cnt, uint32_t* o_n) {
-    if (n_small) AFQ_LAUNCH((k_sort_leaf<256, kSortSmallLeaf>), n_small, 256, s, leaves, ids_small, buf_a, buf_b, o_key, o_cnt, o_n);
-    if (n_big) AFQ_LAUNCH((k_sort_leaf<1024, kSortLeafCap>), n_big, 1024, s, leaves, ids_big, buf_a, buf_b, o_key, o_cnt, o_n);
+    if (n_small) AFQ_LAUNCH((k_sort_leaf<kSortSmallLeafNT, kSortSmallLeaf>), n_small, kSortSmallLeafNT, s, leaves, ids_small, buf_a, buf_b, o_key, o_cnt, o_n);
+    if (n_big) AFQ_LAUNCH((k_sort_leaf<kSortLeafNT, kSortLeafCap>), n_big, kSortLeafNT, s, leaves, ids_big, buf_a, buf_b, o_key, o_cnt, o_n);
 }
 
 void launch_sort_emit(hipStream_t s, const SortLeaf* leaves, uint32_t n_leaves, const uint32_t* leaf_out, const uint64_t* i_key, const uint32_t* i_cnt,

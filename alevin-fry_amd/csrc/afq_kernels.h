@@ -192,10 +192,28 @@ constexpr uint32_t kSortLeafCap = 16384;      // keys one workgroup sorts in a s
 constexpr uint32_t kSortRepartAbove = kSortLeafCap;   // a segment with more keys is partitioned again by its next key bits
 constexpr uint32_t kSortParseTile = 4096;     // bytes of a chunk a wave stages in LDS per trip
 constexpr uint32_t kSortRadixBits = 8;        // digit width of a re-partition level
-constexpr uint32_t kSortSmallLeaf = 2048;     // leaves up to this size are sorted by a 256-thread workgroup
+constexpr uint32_t kSortSmallLeaf = 2048;     // leaves up to this size are sorted by a workgroup of kSortSmallLeafNT threads
+constexpr int kSortSmallLeafNT = 256, kSortLeafNT = 1024;   // threads of the two leaf instances: a leaf's run heads are compacted a slice of that many at a time
+constexpr uint32_t kSortParseHalo = 24;       // bytes staged behind a parse tile: a record that starts inside the tile has its head (4 + 8) and ONE alignment (11) staged with it
 constexpr uint32_t kSortNoBin = 0xFFFFFFFFu;  // an output slot of the parse that holds no fragment
 constexpr uint32_t kSortNoRank = 0xFFFFFFFFu;
 constexpr uint64_t kSortEmptyKey = ~0ull;     // free slot of the correction table (the all-ones barcode travels as SortParseArgs::ones_rank)
+// the correction table: home slot = sort_hash_bc(barcode) & (capacity - 1), capacity = sort_table_capacity(entries): at most half the slots are taken
+#if defined(__HIPCC__)
+#define AFQ_SORT_HD __host__ __device__
+#else
+#define AFQ_SORT_HD
+#endif
+AFQ_SORT_HD inline uint32_t sort_hash_bc(uint64_t x) {
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
+    return (uint32_t)x;
+}
+#undef AFQ_SORT_HD
+inline uint64_t sort_table_capacity(uint64_t n_corr) {   // the smallest power of two >= max(2, 2 n_corr)
+    uint64_t cap = 2;
+    while (cap < 2 * n_corr) cap <<= 1;
+    return cap;
+}
 struct SortChunk { uint64_t chunk_off; uint64_t out_off; uint32_t nbytes; uint32_t nrec; };
 struct SortParseArgs {
     const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks; uint32_t bc_bytes;

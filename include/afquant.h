@@ -301,6 +301,14 @@ int afq_atac_sort_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const 
  * with MORE keys than this is partitioned again, out[3] = bytes of a chunk the parse stages per trip.  For tests, which derive
  * their boundary shapes from these. */
 void afq_atac_sort_limits(uint32_t out[4]);
+/* out[0] = leaves of at most this many keys are sorted by the smaller workgroup, out[1] / out[2] = threads of the smaller / the
+ * larger leaf workgroup (a leaf's run heads are compacted a slice of that many at a time), out[3] = bytes the parse stages
+ * behind a tile (the head and one alignment of a record that starts on the tile's last byte).  For tests, as above. */
+void afq_atac_sort_leaf_limits(uint32_t out[4]);
+/* The correction table afq_atac_sort_rad builds for n_corrections entries: its capacity (the smallest power of two
+ * >= max(2, 2 * n_corrections); open addressing, the next slot modulo the capacity on a collision) and the home slot of
+ * `barcode` in it.  For tests, which build probe chains of a stated length from these.  Either pointer may be NULL. */
+void afq_atac_sort_table_slot(uint64_t barcode, uint64_t n_corrections, uint32_t* home_slot, uint32_t* capacity);
 
 /*
  * Kernel timing of the last collected batch (HIP events on the context's own

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from atac_sort_cases import distinct, expected, flat, na1_chunks, same
 from util import ROOT, pkg
 
 pytestmark = pytest.mark.gpu
@@ -36,67 +37,7 @@ def lim():
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
-def expected(bc, ref, start, fl, obs, cor):
-    """the rows `atac sort` owes for the single-alignment records (bc, ref, start, fl) under the map obs -> cor"""
-    bc, ref, start, fl = (np.asarray(x, dt) for x, dt in ((bc, np.uint64), (ref, np.uint32), (start, np.uint32), (fl, np.uint16)))
-    obs, cor = np.asarray(obs, np.uint64), np.asarray(cor, np.uint64)
-    o = np.argsort(obs)
-    so, sc = obs[o], cor[o]
-    i = np.minimum(np.searchsorted(so, bc), max(len(so) - 1, 0))
-    hit = so[i] == bc if len(so) else np.zeros(len(bc), bool)
-    cbc, ref, start, fl = sc[i][hit] if len(so) else bc[:0], ref[hit], start[hit], fl[hit]
-    k = np.lexsort((cbc, fl, start, ref))
-    cbc, ref, start, fl = cbc[k], ref[k], start[k], fl[k]
-    head = np.ones(len(k), bool)
-    if len(k):
-        head[1:] = (ref[1:] != ref[:-1]) | (start[1:] != start[:-1]) | (fl[1:] != fl[:-1]) | (cbc[1:] != cbc[:-1])
-    pos = np.flatnonzero(head)
-    cnt = np.diff(np.append(pos, len(k))).astype(np.uint32)
-    return {"ref": ref[pos], "start": start[pos], "frag_len": fl[pos], "bc": cbc[pos], "count": cnt,
-            "n_uncorrected": int((~hit).sum()), "n_kept": int(hit.sum())}
-
-
-def same(got, want, what=""):
-    for k in ("ref", "start", "frag_len", "bc", "count"):
-        assert got[k].dtype == want[k].dtype, (what, k)
-        assert np.array_equal(got[k], want[k]), (what, k, len(got[k]), len(want[k]))
-    st = got["stats"]
-    assert st["n_distinct"] == len(want["ref"]) and st["n_kept"] == want["n_kept"] and st["n_uncorrected"] == want["n_uncorrected"], (what, st)
-    assert st["n_long_fragments"] == int((want["frag_len"] >= 2000).sum()), (what, st)
-
-
-def flat(chunks):
-    """(bc, ref, start, fl) of the single-alignment records of python-level chunks, plus (#records, #na == 0, #na > 1)"""
-    one = [(bc, a[0]) for recs in chunks for bc, a in recs if len(a) == 1]
-    n = sum(len(r) for r in chunks)
-    n0 = sum(1 for recs in chunks for _, a in recs if len(a) == 0)
-    cols = ([b for b, _ in one], [a[0] for _, a in one], [a[2] for _, a in one], [a[3] for _, a in one])
-    return cols, (n, n0, n - n0 - len(one))
-
-
-def na1_chunks(bc, ref, start, fl, per_chunk, ty=4, bc_bytes=8):
-    """chunks of single-alignment records, encoded with numpy (the large shapes): bytes, chunk_off"""
-    dt = np.dtype([("na", "<u4"), ("bc", "<u%d" % bc_bytes), ("ref", "<u4"), ("ty", "u1"), ("start", "<u4"), ("fl", "<u2")])
-    assert dt.itemsize == 15 + bc_bytes
-    r = np.zeros(len(bc), dt)
-    r["na"], r["bc"], r["ref"], r["ty"], r["start"], r["fl"] = 1, bc, ref, ty, start, fl
-    out, offs = bytearray(), []
-    for a in range(0, max(len(r), 1), per_chunk):
-        body = r[a:a + per_chunk].tobytes()
-        offs.append(len(out))
-        out += (len(body) + 8).to_bytes(4, "little") + len(r[a:a + per_chunk]).to_bytes(4, "little") + body
-    return bytes(out), np.asarray(offs, np.uint64)
-
-
-def distinct(rng, n, bits):
-    """n distinct integers below 2^bits, in random order"""
-    if bits <= 20:
-        return rng.permutation(1 << bits)[:n].astype(np.uint64)
-    v = np.unique(rng.integers(0, 1 << bits, size=2 * n + 16, dtype=np.uint64))
-    assert len(v) >= n
-    return rng.permutation(v)[:n]
-
-
+# (expected - the judge of every result -, same, flat, na1_chunks and distinct live in tests/atac_sort_cases.py)
 def rand_alns(rng, na, ref_lengths):
     out = []
     for _ in range(na):
