@@ -89,8 +89,8 @@ __device__ __forceinline__ PugCtx make_ctx(const P2Args& A, const P2Cell& c, uin
 // The two-vertex components of one cell: one molecule each, the refs both labels share (pugutils.rs:1161-1188).  The NT threads of
 // the workgroup take the n_pr components of pr_v (two vertices each; tl: touched-vertex number -> slot, or nullptr when the list
 // holds slots); stage_wave: this wave's 64 x kStageRefs words of LDS.  Workgroup-wide call.
-// (GL: as in cover_tiny8 - a first label of more refs than the stage holds has its shared refs' genes sorted in the first gene row
-//  behind the wave's stage, its lanes one after the other, not in a private array.)
+// A first label of more refs than the stage holds goes through emit_label_molecule (afq_pug_common.h), its gene set in a private
+// array - or (GL, as in cover_tiny8) in the first gene row behind the wave's stage, the lanes that hold one taking turns.
 template <int NT, bool GL = false>
 __device__ __forceinline__ void p2_cover_pairs(const PugCtx& C, const uint64_t* ch, const uint32_t* coff, const uint32_t* tl, const uint32_t* pr_v, uint32_t n_pr, uint32_t* stage_wave) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -118,6 +118,7 @@ __device__ __forceinline__ void p2_cover_pairs(const PugCtx& C, const uint64_t* 
             WAVE_SYNC();
         }
         auto in_l2 = [&](uint32_t t) -> bool { return lds2 ? stage_contains(row, l2.n, t) : klab_contains(l2, t); };
+        auto shared_ref = [&](uint32_t j) -> uint32_t { const uint32_t t = l.p[j] & 0x7FFFFFFFu; return in_l2(t) ? t : 0xFFFFFFFFu; };   // (of a first label in the chunk)
         if (k < n_pr) {
             if (l.n <= 4) {
                 uint32_t g4[4];
@@ -151,44 +152,14 @@ __device__ __forceinline__ void p2_cover_pairs(const PugCtx& C, const uint64_t* 
                 emit_molecule(C, row, ng);
             } else if (!GL) {
                 uint32_t g[kMaxGenesPerLabel];
-                uint32_t ng = 0;
-                for (uint32_t jj = 0; jj < l.n && ng != 0xFFFFFFFFu; ++jj) {
-                    const uint32_t t = l.p[jj] & 0x7FFFFFFFu;
-                    if (!in_l2(t)) continue;
-                    const uint32_t gid = C.t2g[t];
-                    uint32_t qq = 0;
-                    while (qq < ng && g[qq] < gid) ++qq;
-                    if (qq < ng && g[qq] == gid) continue;
-                    if (ng == kMaxGenesPerLabel) { ng = 0xFFFFFFFFu; break; }
-                    for (uint32_t r = ng; r > qq; --r) g[r] = g[r - 1];
-                    g[qq] = gid;
-                    ++ng;
-                }
-                if (ng == 0xFFFFFFFFu && C.em)
-                    emit_wide_class(C, l.n, [&](uint32_t jj) -> uint32_t { const uint32_t t = l.p[jj] & 0x7FFFFFFFu; return in_l2(t) ? t : 0xFFFFFFFFu; });
-                else emit_molecule(C, g, ng);
+                emit_label_molecule(C, l.n, shared_ref, g);
             }
         }
         if constexpr (GL) {   // first labels of more than kStageRefs refs (rare): the lanes that hold one, one after the other, through one LDS gene row
+            WAVE_SYNC();
             for (uint64_t lm = __ballot(k < n_pr && l.n > kStageRefs); lm; lm &= lm - 1) {
-                if (lane != (uint32_t)__builtin_ctzll(lm)) continue;
-                uint32_t* const g = stage_wave + 64 * kStageRefs;
-                uint32_t ng = 0;
-                for (uint32_t jj = 0; jj < l.n && ng != 0xFFFFFFFFu; ++jj) {
-                    const uint32_t t = l.p[jj] & 0x7FFFFFFFu;
-                    if (!in_l2(t)) continue;
-                    const uint32_t gid = C.t2g[t];
-                    uint32_t qq = 0;
-                    while (qq < ng && g[qq] < gid) ++qq;
-                    if (qq < ng && g[qq] == gid) continue;
-                    if (ng == kMaxGenesPerLabel) { ng = 0xFFFFFFFFu; break; }
-                    for (uint32_t r = ng; r > qq; --r) g[r] = g[r - 1];
-                    g[qq] = gid;
-                    ++ng;
-                }
-                if (ng == 0xFFFFFFFFu && C.em)
-                    emit_wide_class(C, l.n, [&](uint32_t jj) -> uint32_t { const uint32_t t = l.p[jj] & 0x7FFFFFFFu; return in_l2(t) ? t : 0xFFFFFFFFu; });
-                else emit_molecule(C, g, ng);
+                if (lane == (uint32_t)__builtin_ctzll(lm)) emit_label_molecule(C, l.n, shared_ref, stage_wave + 64 * kStageRefs);
+                WAVE_SYNC();
             }
         }
         append_cols(C, col);

@@ -13,9 +13,12 @@
 //
 // One 1024-thread workgroup owns one cell and runs every phase out of a per-cell slice of global
 // scratch (L2 resident), so nothing here needs a device-scope atomic except the edge-pool bump.
-// Most components are singletons (lane-parallel), small ones (<= 64 vertices) are covered by one
-// wave with the adjacency as one 64-bit mask per lane, larger ones (<= 4096) by the workgroup with
-// multi-word masks (one mask word per lane, candidate vertices spread over the waves).
+// Phases 1-5 (sort, vertices and classes, vertex ids, neighbour search, components) are the kernel's
+// own text; phase 6, the molecules, is three functions in front of it: resolve_lone_and_pairs (6a:
+// single vertices and pairs, lane-parallel), cover_small_components (6b: 3..64 vertices, gathered
+// into records for cover_tiny8 / cover_wave64) and cover_big_components (6c: up to 4096 vertices
+// through cover_big, the winner-take-all rule above --large-graph-thresh).  The covers and the
+// molecule rules themselves are afq_pug_common.h's, shared with the phase kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -175,6 +178,269 @@ __device__ __noinline__ void sample_sort_reads(SortRec* sr, uint32_t* bid, uint3
 
 
 
+// A vertex's label: its class's ref list, or gene list at gene level.
+struct CellLabels {
+    const PugCtx& C;
+    const uint4* vv;          // per vertex: .x reads | label code << 20, .y class, .z/.w the refs of a short label or a record carrying the label
+    const uint32_t* c_glab;   // gene level: the classes' sorted distinct gene lists, class k at c_goff[k]
+    const uint32_t* c_goff;
+    __device__ __forceinline__ Lab operator()(uint32_t v) const {
+        if (!C.gene_level) {
+            const uint4 q = vv[v];
+            const uint32_t code = q.x >> 20;   // 1 / 2: the refs sit in .z / .w of the vertex record; 0: empty; 3: in the chunk
+            if (code == 3) return rec_label(C, q.z);
+            return Lab{reinterpret_cast<const uint32_t*>(vv + v) + 2, code};
+        }
+        const uint32_t k = vv[v].y;
+        return Lab{c_glab + c_goff[k], c_goff[k + 1] - c_goff[k]};
+    }
+};
+// What phases 1-5 leave of a cell in its scratch slice for phase 6.
+struct CellGraph {
+    CellLabels vlab;
+    const uint64_t* vv_umi;          // UMI by vertex id
+    const uint32_t* deg;             // out-edges of v: edges[deg[v] .. deg[v + 1])
+    const uint32_t* edges;
+    const uint32_t* tch;             // 1 = the vertex is the target of some edge
+    const uint32_t* comp_start;      // component c of the NC with two or more vertices: comp_sorted[comp_start[c] .. comp_start[c + 1])
+    const uint64_t* comp_sorted;
+    uint32_t* local_idx;             // vid -> index inside its component
+    uint32_t V, NC;
+    __device__ __forceinline__ uint32_t vid_at(uint32_t i) const { return (uint32_t)comp_sorted[i] & ((1u << kVidBits) - 1); }
+};
+// The labels of the component whose vertices start at comp_sorted[c0], for cover_big.
+struct ComponentLabels {
+    const CellGraph& G;
+    uint32_t c0;
+    __device__ __forceinline__ Lab label(uint32_t i) const { return G.vlab(G.vid_at(c0 + i)); }
+    __device__ __forceinline__ bool contains(uint32_t i, uint32_t t) const { return lab_contains(label(i), t); }
+};
+// The kernel's LDS words phase 6 works with.
+struct CellLds {
+    uint32_t* s_ws;                  // block_excl_scan's
+    uint32_t* s_flag;                // two counters
+    unsigned long long* s_ebase;     // where the last reservation in the edge pool begins
+    uint64_t (*s_mask)[64];          // cover_big's
+    uint32_t* s_bestv;
+    uint32_t* s_bestsz;
+};
+
+// ---- 6a. single-vertex components: the label's genes (pugutils.rs:1262-1322); two-vertex components ----
+// Vertices without an edge: one molecule each, the label's genes.  Four vertices per thread and trip, their loads issued
+// together; labels of one or two refs (in the vertex record) never touch the chunk or a gene array.
+// Lone vertices whose label has more than two refs (one in ten) need the chunk and a gene lookup per ref - three dependent
+// reads deep; they are listed here (long_list: V words) and taken afterwards, a lane each, instead of holding up the wave that met them.
+// A two-vertex component is always one molecule: it is weakly connected, so one of the two can reach the
+// other through a shared transcript and the greedy cover takes that 2-vertex arborescence first; its label
+// is the transcripts the two labels share (pugutils.rs:1161-1188) - never empty, an edge needs an overlap.
+__device__ __forceinline__ void resolve_lone_and_pairs(const PugCtx& C, const CellGraph& G, const CellLds& S, uint32_t* long_list) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid == 0) S.s_flag[0] = 0;
+    __syncthreads();
+    for (uint32_t v0 = tid; v0 - lane < G.V; v0 += 4 * kPugNT) {   // wave-uniform trip count (append_cols is a wave-wide call)
+        uint4 q4[4];
+        bool lone[4], shrt[4];
+        uint32_t ga[4], gb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t v = v0 + j * kPugNT;
+            lone[j] = v < G.V && !(G.deg[v + 1] > G.deg[v] || G.tch[v]);
+            q4[j] = v < G.V ? G.vlab.vv[v] : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t code = q4[j].x >> 20;
+            shrt[j] = lone[j] && !C.gene_level && (code == 1 || code == 2);
+            ga[j] = shrt[j] ? C.t2g[q4[j].z] : 0u;
+            gb[j] = shrt[j] && code == 2 ? C.t2g[q4[j].w] : ga[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
+            bool cls = false;
+            if (lone[j] && shrt[j]) {
+                const uint32_t lo = ga[j] < gb[j] ? ga[j] : gb[j], hi = ga[j] < gb[j] ? gb[j] : ga[j];
+                col = molecule2_column(C, lo, hi, lo == hi ? 1u : 2u, cls);
+                k0 = lo; k1 = hi;
+            }
+            const bool later = lone[j] && !shrt[j];
+            const uint64_t lm = __ballot(later);
+            if (lm) {
+                const uint32_t leader = (uint32_t)__builtin_ctzll(lm);
+                uint32_t at = 0;
+                if (lane == leader) at = atomicAdd(&S.s_flag[0], (uint32_t)__popcll(lm));
+                at = __builtin_amdgcn_readlane(at, (int)leader);
+                if (later) long_list[at + (uint32_t)__popcll(lm & ((1ull << lane) - 1))] = v0 + j * kPugNT;
+            }
+            append_cols(C, col);   // (v0 - lane is wave-uniform: every lane of the wave gets here)
+            append_class2(C, cls, k0, k1);
+        }
+    }
+    __syncthreads();
+    const uint32_t n_long = S.s_flag[0];
+    // One molecule from a first label l: its refs that `keep` lets through.  Up to four refs in registers, more through a gene array.
+    auto label_molecule = [&](const Lab& l, auto&& keep, uint32_t& col, bool& cls, uint32_t& k0, uint32_t& k1) {
+        if (l.n <= 4) {
+            uint32_t g4[4];
+            uint32_t k = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                g4[q] = 0xFFFFFFFFu;
+                if ((uint32_t)q < l.n && keep(l.ref(q))) {
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) if ((uint32_t)w == k) g4[w] = l.ref(q);
+                    ++k;
+                }
+            }
+            const uint32_t ng = genes_of4(C, g4, k);
+            col = molecule4_column(C, g4, ng, cls);
+            k0 = g4[0]; k1 = g4[1];
+        } else {
+            uint32_t g[kMaxGenesPerLabel];
+            emit_label_molecule(C, l.n, [&](uint32_t j) -> uint32_t { const uint32_t t = l.ref(j); return keep(t) ? t : 0xFFFFFFFFu; }, g);
+        }
+    };
+    for (uint32_t i = tid; i - lane < n_long; i += kPugNT) {
+        uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
+        bool cls = false;
+        if (i < n_long) label_molecule(G.vlab(long_list[i]), [](uint32_t) { return true; }, col, cls, k0, k1);
+        append_cols(C, col);
+        append_class2(C, cls, k0, k1);
+    }
+    for (uint32_t c = tid; c - lane < G.NC; c += kPugNT) {   // (wave-uniform trip count: append_cols is a wave-wide call)
+        uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
+        bool cls = false;
+        const uint32_t n = c < G.NC ? G.comp_start[c + 1] - G.comp_start[c] : 0u;
+        if (n == 2 && n <= C.large_thresh) {   // the transcripts the two labels share
+            const Lab l2 = G.vlab(G.vid_at(G.comp_start[c] + 1));
+            label_molecule(G.vlab(G.vid_at(G.comp_start[c])), [&](uint32_t t) { return lab_contains(l2, t); }, col, cls, k0, k1);
+        }
+        append_cols(C, col);
+        append_class2(C, cls, k0, k1);
+    }
+}
+
+// ---- 6b. components of 3..64 vertices: one wave each, adjacency = one 64-bit mask per lane ----
+// What a wave needs of its component - per vertex the label and the adjacency mask - sits five dependent global reads deep
+// (list -> component bounds -> vertex id -> vertex record / edge range -> edge targets -> their local index), and a wave
+// working alone on one component pays that chain in full, a thousand times per cell.  So the gathering is done first,
+// by all threads over all such components at once (thread per vertex: the chains of a thousand vertices overlap), into
+// 32-byte records laid out component by component; the cover then reads its records with one access, the next
+// component's already on their way.
+// mid_list: the n_mid components, those of 3..8 vertices (n_tiny) first, with room for n_mid + 1 offsets behind it.  false: the
+// pool is exhausted.
+__device__ __forceinline__ bool cover_small_components(const PugCellArgs& A, const PugCtx& C, const CellGraph& G, const CellLds& S,
+                                                       uint32_t* mid_list, uint32_t n_tiny, uint32_t n_mid) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t* mid_off = mid_list + n_mid;   // [n_mid + 1] first record of each listed component
+    uint32_t S_mid = 0;
+    for (uint32_t base = 0; base < n_mid; base += kPugNT) {
+        const uint32_t ci = base + tid;
+        const uint32_t n = ci < n_mid ? G.comp_start[mid_list[ci] + 1] - G.comp_start[mid_list[ci]] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan<kPugNT>(n, S.s_ws, tot);
+        if (ci < n_mid) mid_off[ci] = S_mid + ex;
+        S_mid += tot;
+    }
+    if (tid == 0) { mid_off[n_mid] = S_mid; *S.s_ebase = atomicAdd(A.epool_cursor, 9ull * S_mid + 4); }
+    __syncthreads();
+    if (*S.s_ebase + 9ull * S_mid + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return false; }
+    uint4* mrec = reinterpret_cast<uint4*>(A.epool + ((*S.s_ebase + 3) & ~3ull));   // two per vertex: {vid, label length, ref0 | ptr lo, ref1 | ptr hi}, {ref2, ref3, adjacency}
+    uint32_t* slot_comp = reinterpret_cast<uint32_t*>(mrec + 2 * (size_t)S_mid);
+    for (uint32_t ci = tid; ci < n_mid; ci += kPugNT) {
+        const uint32_t b0 = mid_off[ci], n = mid_off[ci + 1] - b0;
+        for (uint32_t i = 0; i < n; ++i) slot_comp[b0 + i] = ci;
+    }
+    __syncthreads();
+    for (uint32_t sl = tid; sl < S_mid; sl += kPugNT) {
+        const uint32_t ci = slot_comp[sl];
+        const uint32_t v = G.vid_at(G.comp_start[mid_list[ci]] + (sl - mid_off[ci]));
+        const Lab l = G.vlab(v);
+        uint32_t r0 = 0xFFFFFFFFu, r1 = 0xFFFFFFFFu, r2 = 0xFFFFFFFFu, r3 = 0xFFFFFFFFu;
+        if (l.n <= 4) {   // labels are short: up to four refs travel in the record
+            if (l.n > 0) r0 = l.ref(0);
+            if (l.n > 1) r1 = l.ref(1);
+            if (l.n > 2) r2 = l.ref(2);
+            if (l.n > 3) r3 = l.ref(3);
+        } else { const uint64_t pa = (uint64_t)(uintptr_t)l.p; r0 = (uint32_t)pa; r1 = (uint32_t)(pa >> 32); }
+        uint64_t adj = 0;
+        for (uint32_t e = G.deg[v]; e < G.deg[v + 1]; ++e) adj |= 1ull << G.local_idx[G.edges[e]];
+        mrec[2 * (size_t)sl] = make_uint4(v, l.n, r0, r1);
+        mrec[2 * (size_t)sl + 1] = make_uint4(r2, r3, (uint32_t)adj, (uint32_t)(adj >> 32));
+    }
+    __syncthreads();
+    cover_tiny8<kPugNT / 64>(C, mrec, mid_off, n_tiny, wv, lane);   // 6b': components of 3..8 vertices, eight to a wave
+    cover_wave64<kPugNT / 64>(C, mrec, mid_off, n_tiny, n_mid, wv, lane);   // 9..64 vertices: a wave each
+    __syncthreads();
+    return true;
+}
+
+// ---- 6c. larger components, one at a time by the whole workgroup ----
+// Up to kMaxBigComp vertices: cover_big over the labels where they lie (no records are gathered) and the adjacency as rows of
+// mask words in the pool.  Above --large-graph-thresh: get_num_molecules_large_component (pugutils.rs:916-982), winner-take-all
+// over the component's (umi, gene, count) triplets.  Both rare.  false: the pool is exhausted, or a component is too large.
+__device__ __forceinline__ bool cover_big_components(const PugCellArgs& A, const PugCtx& C, const CellGraph& G, const CellLds& S,
+                                                  const uint32_t* big_list, uint32_t n_big) {
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));   // (nothing is emitted: what this rare phase derives from the thread id is worked out here, not held in registers from before the kernel's loop over cells)
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    for (uint32_t ci = 0; ci < n_big; ++ci) {
+        const uint32_t c = big_list[ci];
+        const uint32_t c0 = G.comp_start[c], n = G.comp_start[c + 1] - c0;
+        if (n > C.large_thresh) {
+            uint32_t cnt = 0;
+            for (uint32_t i = tid; i < n; i += kPugNT) {
+                const Lab l = G.vlab(G.vid_at(c0 + i));
+                auto ref = [&](uint32_t j) { return l.ref(j); };
+                uint32_t g[kMaxGenesPerLabel];
+                each_gene_of(C, l.n, ref, g, genes_of(C, l.n, ref, g), [&](uint32_t) { ++cnt; });
+            }
+            uint32_t tot;
+            (void)block_excl_scan<kPugNT>(cnt, S.s_ws, tot);
+            if (tid == 0) *S.s_ebase = atomicAdd(A.epool_cursor, 4ull * tot + 4);
+            __syncthreads();
+            if (*S.s_ebase + 4ull * tot + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return false; }
+            uint4* trip = reinterpret_cast<uint4*>(A.epool + ((*S.s_ebase + 3) & ~3ull));   // (umi lo, umi hi, gene, count)
+            if (tid == 0) S.s_flag[1] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < n; i += kPugNT) {
+                const uint32_t v = G.vid_at(c0 + i);
+                const uint64_t umi = G.vv_umi[v];
+                const uint32_t reads = G.vlab.vv[v].x & 0xFFFFFu;
+                const Lab l = G.vlab(v);
+                auto ref = [&](uint32_t j) { return l.ref(j); };
+                uint32_t g[kMaxGenesPerLabel];
+                const uint32_t ng = genes_of(C, l.n, ref, g);
+                uint32_t k = 0;
+                each_gene_of(C, l.n, ref, g, ng, [&](uint32_t) { ++k; });
+                uint32_t o = atomicAdd(&S.s_flag[1], k);
+                each_gene_of(C, l.n, ref, g, ng, [&](uint32_t gid) { trip[o++] = make_uint4((uint32_t)umi, (uint32_t)(umi >> 32), gid, reads); });
+            }
+            __syncthreads();
+            large_component_from_triplets<kPugNT>(C, trip, S.s_flag[1]);
+            if (tid == 0) A.alt[C.cell] = 1;  // used_alternative_strategy, pugutils.rs:1070
+            __syncthreads();
+            continue;
+        }
+        if (n > kMaxBigComp) { if (tid == 0) set_err(A.st, kErrPugLimit, C.cell); return false; }
+        const uint32_t nw = (n + 63) / 64;   // mask words of a row
+        if (tid == 0) *S.s_ebase = atomicAdd(A.epool_cursor, 2ull * n * nw + 2);
+        __syncthreads();
+        if (*S.s_ebase + 2ull * n * nw + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return false; }
+        uint64_t* rows = reinterpret_cast<uint64_t*>(A.epool + ((*S.s_ebase + 1) & ~1ull));
+        for (uint32_t i = tid; i < n * nw; i += kPugNT) rows[i] = 0;
+        for (uint32_t i = tid; i < n; i += kPugNT) G.local_idx[G.vid_at(c0 + i)] = i;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += kPugNT) {
+            const uint32_t v = G.vid_at(c0 + i);
+            for (uint32_t e = G.deg[v]; e < G.deg[v + 1]; ++e) { const uint32_t y = G.local_idx[G.edges[e]]; rows[(size_t)i * nw + (y >> 6)] |= 1ull << (y & 63); }
+        }
+        cover_big<kPugNT / 64>(C, n, ComponentLabels{G, c0}, rows, S.s_mask, S.s_bestv, S.s_bestsz, wv, lane);
+    }
+    return true;
+}
+
+
 __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     __shared__ uint32_t s_ws[kPugNT / 64];
     __shared__ uint32_t s_cnt[4];
@@ -190,7 +456,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     __shared__ uint32_t s_next;
     __shared__ uint32_t s_poff[kMaxParts + 1];
     __shared__ uint32_t s_filt[2048];   // 2^16-bit presence filter over the UMIs of the partition in the table
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
   // Persistent workgroup: takes the next cell of the (largest-first) list until the list is empty.  Its scratch
   // slice is reused cell after cell, so the working set of a CU stays the size of ONE cell instead of wandering
   // over a slice per cell (the random probes of the edge phase were paying a TLB miss each).
@@ -266,31 +532,16 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     // One pass over the sorted reads: vertex / class heads (two scans), the class's smallest record offset (its first
     // appearance in the file), and the check that equal non-exact keys are equal labels - each such read against the read
     // before it, equality chaining through the class.  A vertex's multiplicity is the distance to the next vertex head.
+    // (through t2g also at gene level: these lists ARE the gene-level labels)
     auto gene_list = [&](uint32_t rec_dw, uint32_t* g) -> uint32_t {
         const Lab l = rec_label(C, rec_dw);
-        uint32_t k = 0;
-        for (uint32_t j = 0; j < l.n; ++j) {
-            const uint32_t gid = C.t2g[l.p[j] & 0x7FFFFFFFu];
-            uint32_t q = 0;
-            while (q < k && g[q] < gid) ++q;
-            if (q < k && g[q] == gid) continue;
-            if (k == kMaxGenesPerLabel) return 0xFFFFFFFFu;
-            for (uint32_t r = k; r > q; --r) g[r] = g[r - 1];
-            g[q] = gid;
-            ++k;
-        }
-        return k;
+        return genes_of(C, l.n, [&](uint32_t j) { return l.ref(j); }, g, true);
     };
     // the same for a read with more distinct genes than kMaxGenesPerLabel (a large gene family; rare): counted, compared and
     // written by looking back over the refs instead of through a register array
     auto gene_first_occurrences = [&](uint32_t rec_dw, auto&& f) {
         const Lab l = rec_label(C, rec_dw);
-        for (uint32_t j = 0; j < l.n; ++j) {
-            const uint32_t gj = C.t2g[l.p[j] & 0x7FFFFFFFu];
-            bool first = true;
-            for (uint32_t q = 0; q < j && first; ++q) first = C.t2g[l.p[q] & 0x7FFFFFFFu] != gj;
-            if (first) f(gj);
-        }
+        each_distinct_gene(C, l.n, [&](uint32_t j) { return l.ref(j); }, true, f);
     };
     auto gene_subset_slow = [&](uint32_t a_dw, uint32_t b_dw) -> bool {   // every gene of read a is a gene of read b
         const Lab la = rec_label(C, a_dw), lb = rec_label(C, b_dw);
@@ -417,16 +668,7 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         if (tid == 0) c_goff[K] = carry;
         __syncthreads();
     }
-    auto vlab = [&](uint32_t v) -> Lab {  // label of a vertex: its class's ref list, or gene list at gene level
-        if (!C.gene_level) {
-            const uint4 q = vv[v];
-            const uint32_t code = q.x >> 20;   // 1 / 2: the refs sit in .z / .w of the vertex record; 0: empty; 3: in the chunk
-            if (code == 3) return rec_label(C, q.z);
-            return Lab{reinterpret_cast<const uint32_t*>(vv + v) + 2, code};
-        }
-        const uint32_t k = vv[v].y;
-        return Lab{c_glab + c_goff[k], c_goff[k + 1] - c_goff[k]};
-    };
+    const CellLabels vlab{C, vv, c_glab, c_goff};
     __syncthreads();
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], cell); return; }
     // ---- 3. class ids by first appearance; reference vertex ids ----
@@ -1107,7 +1349,6 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
         if (comp_start[c + 1] - comp_start[c] <= 64)
             for (uint32_t i = comp_start[c]; i < comp_start[c + 1]; ++i) local_idx[(uint32_t)comp_sorted[i] & ((1u << kVidBits) - 1)] = i - comp_start[c];
     __syncthreads();
-    auto vid_at = [&](uint32_t i) { return (uint32_t)comp_sorted[i] & ((1u << kVidBits) - 1); };
     // work lists: almost every component is a single vertex; list the others once instead of rescanning
     uint32_t* mid_list = reinterpret_cast<uint32_t*>(v_umi);  // slab B is dead: 2..64-vertex components
     uint32_t* big_list = v_cnt;                               // > 64 vertices or over the large-graph threshold
@@ -1136,407 +1377,12 @@ __global__ __launch_bounds__(kPugNT) void k_pug_cell(PugCellArgs A) {
     __syncthreads();
     const uint32_t n_mid = n_tiny + s_flag[0], n_big = s_flag[1];
     __syncthreads();
-
-    // ---- 6a. single-vertex components: the label's genes (pugutils.rs:1262-1322) ----
-    // A two-vertex component is always one molecule: it is weakly connected, so one of the two can reach the
-    // other through a shared transcript and the greedy cover takes that 2-vertex arborescence first; its label
-    // is the transcripts the two labels share (pugutils.rs:1161-1188) - never empty, an edge needs an overlap.
-    // vertices without an edge: one molecule each, the label's genes.  Four vertices per thread and trip, their loads issued
-    // together; labels of one or two refs (in the vertex record) never touch the chunk or a gene array.
-    // Lone vertices whose label has more than two refs (one in ten) need the chunk and a gene lookup per ref - three dependent
-    // reads deep; they are listed here and taken afterwards, a lane each, instead of holding up the wave that met them.
-    uint32_t* long_list = c_minoff;   // (dead since phase 3)
-    if (tid == 0) s_flag[0] = 0;
-    __syncthreads();
-    for (uint32_t v0 = tid; v0 - lane < V; v0 += 4 * kPugNT) {   // wave-uniform trip count (append_cols is a wave-wide call)
-        uint4 q4[4];
-        bool lone[4], shrt[4];
-        uint32_t ga[4], gb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t v = v0 + j * kPugNT;
-            lone[j] = v < V && !(deg[v + 1] > deg[v] || tch[v]);
-            q4[j] = v < V ? vv[v] : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t code = q4[j].x >> 20;
-            shrt[j] = lone[j] && !C.gene_level && (code == 1 || code == 2);
-            ga[j] = shrt[j] ? C.t2g[q4[j].z] : 0u;
-            gb[j] = shrt[j] && code == 2 ? C.t2g[q4[j].w] : ga[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
-            bool cls = false;
-            if (lone[j] && shrt[j]) {
-                const uint32_t lo = ga[j] < gb[j] ? ga[j] : gb[j], hi = ga[j] < gb[j] ? gb[j] : ga[j];
-                col = molecule2_column(C, lo, hi, lo == hi ? 1u : 2u, cls);
-                k0 = lo; k1 = hi;
-            }
-            const bool later = lone[j] && !shrt[j];
-            const uint64_t lm = __ballot(later);
-            if (lm) {
-                const uint32_t leader = (uint32_t)__builtin_ctzll(lm);
-                uint32_t at = 0;
-                if (lane == leader) at = atomicAdd(&s_flag[0], (uint32_t)__popcll(lm));
-                at = __builtin_amdgcn_readlane(at, (int)leader);
-                if (later) long_list[at + (uint32_t)__popcll(lm & ((1ull << lane) - 1))] = v0 + j * kPugNT;
-            }
-            append_cols(C, col);   // (v0 - lane is wave-uniform: every lane of the wave gets here)
-            append_class2(C, cls, k0, k1);
-        }
-    }
-    __syncthreads();
-    const uint32_t n_long = s_flag[0];
-    for (uint32_t i = tid; i - lane < n_long; i += kPugNT) {
-        uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
-        bool cls = false;
-        if (i < n_long) {
-            const Lab l = vlab(long_list[i]);
-            if (l.n <= 4) {
-                uint32_t g4[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g4[q] = (uint32_t)q < l.n ? l.p[q] & 0x7FFFFFFFu : 0xFFFFFFFFu;
-                const uint32_t ng = genes_of4(C, g4, l.n);
-                col = molecule4_column(C, g4, ng, cls);
-                k0 = g4[0]; k1 = g4[1];
-            } else {
-                uint32_t g[kMaxGenesPerLabel];
-                const uint32_t ng = genes_of(C, l.n, [&](uint32_t j2) { return l.p[j2] & 0x7FFFFFFFu; }, g);
-                if (ng == 0xFFFFFFFFu && C.em) emit_wide_class(C, l.n, [&](uint32_t j2) { return l.p[j2] & 0x7FFFFFFFu; });
-                else emit_molecule(C, g, ng);
-            }
-        }
-        append_cols(C, col);
-        append_class2(C, cls, k0, k1);
-    }
-    for (uint32_t c = tid; c - lane < NC; c += kPugNT) {   // (wave-uniform trip count: append_cols is a wave-wide call)
-        uint32_t col = 0xFFFFFFFFu, k0 = 0, k1 = 0;
-        bool cls = false;
-        const uint32_t n = c < NC ? comp_start[c + 1] - comp_start[c] : 0u;
-        if (n == 2 && n <= C.large_thresh) {
-            const Lab l = vlab(vid_at(comp_start[c])), l2 = vlab(vid_at(comp_start[c] + 1));
-            if (l.n <= 4) {   // the shared transcripts of two short labels, in registers
-                uint32_t g4[4];
-                uint32_t k = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    g4[q] = 0xFFFFFFFFu;
-                    if ((uint32_t)q < l.n) {
-                        const uint32_t t = l.p[q] & 0x7FFFFFFFu;
-                        if (lab_contains(l2, t)) {
-#pragma unroll
-                            for (int w = 0; w < 4; ++w) if ((uint32_t)w == k) g4[w] = t;
-                            ++k;
-                        }
-                    }
-                }
-                const uint32_t ng = genes_of4(C, g4, k);
-                col = molecule4_column(C, g4, ng, cls);
-                k0 = g4[0]; k1 = g4[1];
-            } else {
-                uint32_t g[kMaxGenesPerLabel];
-                uint32_t ng = 0;
-                for (uint32_t j = 0; j < l.n && ng != 0xFFFFFFFFu; ++j) {
-                    const uint32_t t = l.p[j] & 0x7FFFFFFFu;
-                    if (!lab_contains(l2, t)) continue;
-                    const uint32_t gid = C.gene_level ? t : C.t2g[t];
-                    uint32_t q = 0;
-                    while (q < ng && g[q] < gid) ++q;
-                    if (q < ng && g[q] == gid) continue;
-                    if (ng == kMaxGenesPerLabel) { ng = 0xFFFFFFFFu; break; }
-                    for (uint32_t r = ng; r > q; --r) g[r] = g[r - 1];
-                    g[q] = gid;
-                    ++ng;
-                }
-                if (ng == 0xFFFFFFFFu && C.em)
-                    emit_wide_class(C, l.n, [&](uint32_t j) -> uint32_t { const uint32_t t = l.p[j] & 0x7FFFFFFFu; return lab_contains(l2, t) ? t : 0xFFFFFFFFu; });
-                else emit_molecule(C, g, ng);
-            }
-        }
-        append_cols(C, col);
-        append_class2(C, cls, k0, k1);
-    }
-    // ---- 6b. components of 3..64 vertices: one wave each, adjacency = one 64-bit mask per lane ----
-    // What a wave needs of its component - per vertex the label and the adjacency mask - sits five dependent global reads deep
-    // (list -> component bounds -> vertex id -> vertex record / edge range -> edge targets -> their local index), and a wave
-    // working alone on one component pays that chain in full, a thousand times per cell.  So the gathering is done first,
-    // by all threads over all such components at once (thread per vertex: the chains of a thousand vertices overlap), into
-    // 32-byte records laid out component by component; the cover then reads its records with one access, the next
-    // component's already on their way.
-    uint32_t* mid_off = mid_list + n_mid;   // [n_mid + 1] first record of each listed component (slab B has the room)
-    uint32_t S_mid = 0;
-    for (uint32_t base = 0; base < n_mid; base += kPugNT) {
-        const uint32_t ci = base + tid;
-        const uint32_t n = ci < n_mid ? comp_start[mid_list[ci] + 1] - comp_start[mid_list[ci]] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_excl_scan<kPugNT>(n, s_ws, tot);
-        if (ci < n_mid) mid_off[ci] = S_mid + ex;
-        S_mid += tot;
-    }
-    if (tid == 0) { mid_off[n_mid] = S_mid; s_ebase = atomicAdd(A.epool_cursor, 9ull * S_mid + 4); }
-    __syncthreads();
-    if (s_ebase + 9ull * S_mid + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
-    uint4* mrec = reinterpret_cast<uint4*>(A.epool + ((s_ebase + 3) & ~3ull));   // two per vertex: {vid, label length, ref0 | ptr lo, ref1 | ptr hi}, {ref2, ref3, adjacency}
-    uint32_t* slot_comp = reinterpret_cast<uint32_t*>(mrec + 2 * (size_t)S_mid);
-    for (uint32_t ci = tid; ci < n_mid; ci += kPugNT) {
-        const uint32_t b0 = mid_off[ci], n = mid_off[ci + 1] - b0;
-        for (uint32_t i = 0; i < n; ++i) slot_comp[b0 + i] = ci;
-    }
-    __syncthreads();
-    for (uint32_t sl = tid; sl < S_mid; sl += kPugNT) {
-        const uint32_t ci = slot_comp[sl];
-        const uint32_t v = vid_at(comp_start[mid_list[ci]] + (sl - mid_off[ci]));
-        const Lab l = vlab(v);
-        uint32_t r0 = 0xFFFFFFFFu, r1 = 0xFFFFFFFFu, r2 = 0xFFFFFFFFu, r3 = 0xFFFFFFFFu;
-        if (l.n <= 4) {   // labels are short: up to four refs travel in the record
-            if (l.n > 0) r0 = l.p[0] & 0x7FFFFFFFu;
-            if (l.n > 1) r1 = l.p[1] & 0x7FFFFFFFu;
-            if (l.n > 2) r2 = l.p[2] & 0x7FFFFFFFu;
-            if (l.n > 3) r3 = l.p[3] & 0x7FFFFFFFu;
-        } else { const uint64_t pa = (uint64_t)(uintptr_t)l.p; r0 = (uint32_t)pa; r1 = (uint32_t)(pa >> 32); }
-        uint64_t adj = 0;
-        for (uint32_t e = deg[v]; e < deg[v + 1]; ++e) adj |= 1ull << local_idx[edges[e]];
-        mrec[2 * (size_t)sl] = make_uint4(v, l.n, r0, r1);
-        mrec[2 * (size_t)sl + 1] = make_uint4(r2, r3, (uint32_t)adj, (uint32_t)(adj >> 32));
-    }
-    __syncthreads();
-    cover_tiny8<kPugNT / 64>(C, mrec, mid_off, n_tiny, wv, lane);   // 6b': components of 3..8 vertices, eight to a wave (afq_pug_common.h)
-    cover_wave64<kPugNT / 64>(C, mrec, mid_off, n_tiny, n_mid, wv, lane);   // 9..64 vertices: a wave each
-    __syncthreads();
-    // ---- 6c. larger components, one at a time by the whole workgroup ----
-    for (uint32_t ci = 0; ci < n_big; ++ci) {
-        const uint32_t c = big_list[ci];
-        const uint32_t c0 = comp_start[c], n = comp_start[c + 1] - c0;
-        if (n > C.large_thresh) {
-            // get_num_molecules_large_component (pugutils.rs:916-982): winner-take-all over the component's
-            // (umi, gene, count) triplets.  Rare; thread 0 walks the triplets sorted by the workgroup.
-            // triplets live in the edge pool: 4 words each (umi lo, umi hi, gene, count)
-            if (tid == 0) { s_flag[1] = 0; }
-            __syncthreads();
-            // distinct genes of a label that has more of them than kMaxGenesPerLabel: first occurrences, found by looking back
-            auto wide_genes = [&](const Lab& l, auto&& f) {
-                for (uint32_t j = 0; j < l.n; ++j) {
-                    const uint32_t tj = l.p[j] & 0x7FFFFFFFu;
-                    const uint32_t gj = C.gene_level ? tj : C.t2g[tj];
-                    bool first = true;
-                    for (uint32_t q = 0; q < j && first; ++q) { const uint32_t tq = l.p[q] & 0x7FFFFFFFu; first = (C.gene_level ? tq : C.t2g[tq]) != gj; }
-                    if (first) f(gj);
-                }
-            };
-            // count triplets
-            uint32_t cnt = 0;
-            for (uint32_t i = tid; i < n; i += kPugNT) {
-                const Lab l = vlab(vid_at(c0 + i));
-                uint32_t g[kMaxGenesPerLabel];
-                const uint32_t ng = genes_of(C, l.n, [&](uint32_t j) { return l.p[j] & 0x7FFFFFFFu; }, g);
-                if (ng == 0xFFFFFFFFu) wide_genes(l, [&](uint32_t) { ++cnt; }); else cnt += ng;
-            }
-            uint32_t tot;
-            (void)block_excl_scan<kPugNT>(cnt, s_ws, tot);
-            if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 4ull * tot + 4);
-            __syncthreads();
-            if (s_ebase + 4ull * tot + 4 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
-            uint4* trip = reinterpret_cast<uint4*>(A.epool + ((s_ebase + 3) & ~3ull));
-            if (tid == 0) s_flag[1] = 0;
-            __syncthreads();
-            for (uint32_t i = tid; i < n; i += kPugNT) {
-                const uint32_t v = vid_at(c0 + i);
-                const Lab l = vlab(v);
-                uint32_t g[kMaxGenesPerLabel];
-                const uint32_t ng = genes_of(C, l.n, [&](uint32_t j) { return l.p[j] & 0x7FFFFFFFu; }, g);
-                if (ng == 0xFFFFFFFFu) {   // more genes than g[] holds: the distinct ones, found by looking back (rare)
-                    uint32_t k = 0;
-                    wide_genes(l, [&](uint32_t) { ++k; });
-                    uint32_t o = atomicAdd(&s_flag[1], k);
-                    wide_genes(l, [&](uint32_t gid) { trip[o++] = make_uint4((uint32_t)vv_umi[v], (uint32_t)(vv_umi[v] >> 32), gid, vv[v].x & 0xFFFFFu); });
-                    continue;
-                }
-                const uint32_t o = atomicAdd(&s_flag[1], ng);
-                for (uint32_t q = 0; q < ng; ++q) trip[o + q] = make_uint4((uint32_t)vv_umi[v], (uint32_t)(vv_umi[v] >> 32), g[q], vv[v].x & 0xFFFFFu);
-            }
-            __syncthreads();
-            const uint32_t nt = s_flag[1];
-            bitonic_sort_by<kPugNT>(trip, nt, [](const uint4& a, const uint4& b) {
-                if (a.y != b.y) return a.y > b.y;
-                if (a.x != b.x) return a.x > b.x;
-                if (a.z != b.z) return a.z > b.z;
-                return a.w > b.w;
-            });
-            if (tid == 0 && nt) {  // resolve_num_molecules_crlike_from_vec, pugutils.rs:644-749
-                uint32_t best[kMaxGenesPerLabel];
-                uint32_t nbest = 0, maxc = 0, aggr = 0;
-                uint32_t cu_lo = trip[0].x, cu_hi = trip[0].y, cg = trip[0].z;
-                bool wide = false;
-                uint32_t run0 = 0;   // first triplet of the current UMI
-                // a UMI whose tie set has more genes than best[] holds is a class of its own for the EM: the genes whose
-                // summed count is the maximum, ascending as the triplets are, written straight into the label area
-                auto emit_ties = [&](uint32_t i0, uint32_t i1, uint32_t maxc_) {
-                    auto each_tied = [&](auto&& f) {
-                        for (uint32_t i = i0; i < i1;) {
-                            uint32_t j = i, sum = 0;
-                            for (; j < i1 && trip[j].z == trip[i].z; ++j) sum += trip[j].w;
-                            if (sum == maxc_) f(trip[i].z);
-                            i = j;
-                        }
-                    };
-                    uint32_t k = 0;
-                    each_tied([&](uint32_t) { ++k; });
-                    const uint32_t off = atomicAdd(&C.s_cnt[1], k), di = atomicAdd(&C.s_cnt[2], 1u);
-                    if (off + k > C.lab_cap || 2 * (di + 1) > C.lab_cap) { C.s_cnt[3] = kErrPugLimit; return; }
-                    uint32_t w = off;
-                    each_tied([&](uint32_t gid) { C.labw[w++] = gid; });
-                    C.labd[2 * di] = off; C.labd[2 * di + 1] = k;
-                };
-                for (uint32_t i = 0; i < nt; ++i) {
-                    const uint4 t = trip[i];
-                    if (t.x != cu_lo || t.y != cu_hi) {
-                        if (wide && C.em) emit_ties(run0, i, maxc); else emit_molecule(C, best, wide ? 0xFFFFFFFFu : nbest);
-                        run0 = i;
-                        cu_lo = t.x; cu_hi = t.y; cg = t.z;
-                        nbest = 1; best[0] = t.z; aggr = t.w; maxc = t.w; wide = false;
-                    } else {
-                        if (t.z == cg) aggr += t.w; else { aggr = t.w; cg = t.z; }
-                        if (aggr > maxc) {
-                            maxc = aggr;
-                            if (!(nbest == 1 && best[0] == t.z)) { nbest = 1; best[0] = t.z; wide = false; }
-                        } else if (aggr == maxc) {
-                            if (nbest == kMaxGenesPerLabel) wide = true; else best[nbest++] = t.z;
-                        }
-                    }
-                }
-                if (wide && C.em) emit_ties(run0, nt, maxc); else emit_molecule(C, best, wide ? 0xFFFFFFFFu : nbest);
-            }
-            if (tid == 0) A.alt[cell] = 1;  // used_alternative_strategy, pugutils.rs:1070
-            __syncthreads();
-            continue;
-        }
-        if (n > kMaxBigComp) { if (tid == 0) set_err(A.st, kErrPugLimit, cell); return; }
-        // multi-word cover: nw mask words, lane l of a wave holds word l; rows of the adjacency in the pool
-        const uint32_t nw = (n + 63) / 64;
-        if (tid == 0) s_ebase = atomicAdd(A.epool_cursor, 2ull * n * nw + 2);
-        __syncthreads();
-        if (s_ebase + 2ull * n * nw + 2 > A.epool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return; }
-        uint64_t* rows = reinterpret_cast<uint64_t*>(A.epool + ((s_ebase + 1) & ~1ull));
-        for (uint32_t i = tid; i < n * nw; i += kPugNT) rows[i] = 0;
-        for (uint32_t i = tid; i < n; i += kPugNT) local_idx[vid_at(c0 + i)] = i;
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += kPugNT) {
-            const uint32_t v = vid_at(c0 + i);
-            for (uint32_t e = deg[v]; e < deg[v + 1]; ++e) { const uint32_t y = local_idx[edges[e]]; rows[(size_t)i * nw + (y >> 6)] |= 1ull << (y & 63); }
-        }
-        if (tid < nw) s_mask[0][tid] = (tid + 1 < nw || (n & 63) == 0) ? ~0ull : ((1ull << (n & 63)) - 1);
-        __syncthreads();
-        for (;;) {
-            // uncovered count
-            uint32_t rem = 0;
-            for (uint32_t w = 0; w < nw; ++w) rem += (uint32_t)__popcll(s_mask[0][w]);
-            if (rem == 0) break;
-            // every wave evaluates candidates v = k-th uncovered vertex for k = wv, wv+16, ...
-            uint32_t my_best_sz = 0, my_best_v = 0xFFFFFFFFu;
-            uint64_t my_best_word = 0;  // lane l: word l of this wave's best arborescence
-            const uint64_t ucw = lane < nw ? s_mask[0][lane] : 0ull;
-            uint32_t seen = 0;
-            for (uint32_t w = 0; w < nw; ++w) {
-                uint64_t bits = s_mask[0][w];
-                for (; bits; bits &= bits - 1, ++seen) {
-                    if (seen % (kPugNT / 64) != wv) continue;
-                    const uint32_t v = w * 64 + (uint32_t)__builtin_ctzll(bits);
-                    const Lab lv = vlab(vid_at(c0 + v));
-                    uint64_t mvw = 0; uint32_t mv_sz = 0;
-                    for (uint32_t j = 0; j < lv.n; ++j) {
-                        const uint32_t t = lv.p[j] & 0x7FFFFFFFu;
-                        // A_t: uncovered vertices whose label contains t (chunks of 64 vertices, lane = vertex)
-                        uint64_t Aw = 0;
-                        for (uint32_t cw = 0; cw < nw; ++cw) {
-                            const uint32_t i = cw * 64 + lane;
-                            const uint64_t ucb = __shfl((uint32_t)(ucw >> 32), (int)cw);
-                            const uint64_t uca = __shfl((uint32_t)ucw, (int)cw);
-                            const uint64_t ucword = (ucb << 32) | uca;
-                            const bool in = i < n && ((ucword >> lane) & 1ull) && lab_contains(vlab(vid_at(c0 + i)), t);
-                            const uint64_t word = __ballot(in);
-                            if (lane == cw) Aw = word;
-                        }
-                        uint64_t Rw = (lane == (v >> 6)) ? (1ull << (v & 63)) : 0ull, Fw = Rw;
-                        for (;;) {
-                            // N = OR of the rows of the frontier vertices
-                            uint64_t Nw = 0;
-                            for (uint32_t fw = 0; fw < nw; ++fw) {
-                                const uint32_t flo = __shfl((uint32_t)Fw, (int)fw), fhi = __shfl((uint32_t)(Fw >> 32), (int)fw);
-                                uint64_t fb = ((uint64_t)fhi << 32) | flo;
-                                for (; fb; fb &= fb - 1) {
-                                    const uint32_t x = fw * 64 + (uint32_t)__builtin_ctzll(fb);
-                                    if (lane < nw) Nw |= rows[(size_t)x * nw + lane];
-                                }
-                            }
-                            Fw = Nw & Aw & ~Rw;
-                            Rw |= Fw;
-                            if (!__any(Fw != 0)) break;
-                        }
-                        uint32_t sz = (uint32_t)__popcll(Rw);
-#pragma unroll
-                        for (int d = 32; d > 0; d >>= 1) sz += __shfl_xor(sz, d);
-                        if (sz > mv_sz) { mv_sz = sz; mvw = Rw; }
-                    }
-                    if (mv_sz > my_best_sz) { my_best_sz = mv_sz; my_best_v = v; my_best_word = mvw; }
-                }
-            }
-            if (lane == 0) { s_bestv[wv] = my_best_v; s_bestsz[wv] = my_best_sz; }
-            __syncthreads();
-            // winner: largest size, then smallest vertex (= first in ascending scan order)
-            uint32_t win = 0;
-            for (uint32_t w = 1; w < kPugNT / 64; ++w)
-                if (s_bestsz[w] > s_bestsz[win] || (s_bestsz[w] == s_bestsz[win] && s_bestv[w] < s_bestv[win])) win = w;
-            if (s_bestsz[win] == 0) { if (tid == 0) s_cnt[3] = kErrPugLimit; break; }
-            if (wv == win && lane < nw) s_mask[1][lane] = my_best_word;
-            __syncthreads();
-            if (wv == 0) {
-                // common transcripts of the arborescence -> genes
-                uint32_t fv = 0xFFFFFFFFu;
-                for (uint32_t w = 0; w < nw && fv == 0xFFFFFFFFu; ++w) if (s_mask[1][w]) fv = w * 64 + (uint32_t)__builtin_ctzll(s_mask[1][w]);
-                const Lab lf = vlab(vid_at(c0 + fv));
-                uint32_t g[kMaxGenesPerLabel];
-                uint32_t ng = 0;
-                bool wide = false;
-                for (uint32_t j = 0; j < lf.n; ++j) {
-                    const uint32_t t = lf.p[j] & 0x7FFFFFFFu;
-                    bool all = true;
-                    for (uint32_t cw = 0; cw < nw; ++cw) {
-                        const uint32_t i = cw * 64 + lane;
-                        const bool inb = i < n && ((s_mask[1][cw] >> lane) & 1ull);
-                        const bool miss = inb && !lab_contains(vlab(vid_at(c0 + i)), t);
-                        if (__any(miss)) { all = false; break; }
-                    }
-                    if (!all) continue;
-                    if (lane == 0) {
-                        const uint32_t gid = C.gene_level ? t : C.t2g[t];
-                        uint32_t q = 0;
-                        while (q < ng && g[q] < gid) ++q;
-                        if (!(q < ng && g[q] == gid)) {
-                            if (ng == kMaxGenesPerLabel) wide = true;
-                            else { for (uint32_t r = ng; r > q; --r) g[r] = g[r - 1]; g[q] = gid; ++ng; }
-                        }
-                    }
-                }
-                if (lane == 0) {
-                    if (wide && C.em)
-                        emit_wide_class(C, lf.n, [&](uint32_t j) -> uint32_t {
-                            const uint32_t t = lf.p[j] & 0x7FFFFFFFu;
-                            for (uint32_t cw = 0; cw < nw; ++cw)
-                                for (uint64_t m = s_mask[1][cw]; m; m &= m - 1)
-                                    if (!lab_contains(vlab(vid_at(c0 + cw * 64 + (uint32_t)__builtin_ctzll(m))), t)) return 0xFFFFFFFFu;
-                            return t;
-                        });
-                    else emit_molecule(C, g, wide ? 0xFFFFFFFFu : ng);
-                }
-            }
-            __syncthreads();
-            if (tid < nw) s_mask[0][tid] &= ~s_mask[1][tid];
-            __syncthreads();
-        }
-        __syncthreads();
-    }
+    // ---- 6. the molecules: lone vertices and pairs, components of 3..64 vertices, larger ones ----
+    const CellGraph G{vlab, vv_umi, deg, edges, tch, comp_start, comp_sorted, local_idx, V, NC};
+    const CellLds S{s_ws, s_flag, &s_ebase, s_mask, s_bestv, s_bestsz};
+    resolve_lone_and_pairs(C, G, S, c_minoff);   // (c_minoff: dead since phase 3)
+    if (!cover_small_components(A, C, G, S, mid_list, n_tiny, n_mid)) return;   // (slab B has the room behind the list)
+    if (!cover_big_components(A, C, G, S, big_list, n_big)) return;
     __syncthreads();
     if (s_cnt[3]) { if (tid == 0) set_err(A.st, s_cnt[3], cell); return; }
     if (tid == 0) {

@@ -1344,24 +1344,15 @@ __device__ __forceinline__ bool cover_large(const P2Args& A, const PugCtx& C, co
     const uint64_t* ch = A.s_h + c.rd_base;
     const uint64_t* cu = A.s_u + c.rd_base;
     const uint32_t* coff = A.v_off + c.rd_base;
-    // distinct genes of a label that has more of them than kMaxGenesPerLabel: first occurrences, found by looking back
-    auto wide_genes = [&](const KLab& l, auto&& f) {
-        for (uint32_t j = 0; j < l.n; ++j) {
-            const uint32_t gj = C.t2g[klab_ref(l, j)];
-            bool first = true;
-            for (uint32_t q = 0; q < j && first; ++q) first = C.t2g[klab_ref(l, q)] != gj;
-            if (first) f(gj);
-        }
-    };
     for (uint32_t b = 0; b < n_large; ++b) {
         const uint32_t v0 = lg_off[b], n = lg_off[b + 1] - v0;
         uint32_t cnt = 0;
         for (uint32_t i = tid; i < n; i += CNT) {
             const uint32_t g = tl[lg_v[v0 + i]];
             const KLab l = klab(C.W, C.HW, ch[g], coff[g]);
+            auto ref = [&](uint32_t j) { return klab_ref(l, j); };
             uint32_t gg[kMaxGenesPerLabel];
-            const uint32_t ng = genes_of(C, l.n, [&](uint32_t j) { return klab_ref(l, j); }, gg);
-            if (ng == 0xFFFFFFFFu) wide_genes(l, [&](uint32_t) { ++cnt; }); else cnt += ng;
+            each_gene_of(C, l.n, ref, gg, genes_of(C, l.n, ref, gg), [&](uint32_t) { ++cnt; });
         }
         uint32_t tot;
         (void)block_excl_scan<CNT>(cnt, s_ws, tot);
@@ -1369,74 +1360,21 @@ __device__ __forceinline__ bool cover_large(const P2Args& A, const PugCtx& C, co
         if (tid == 0) { *s_base = atomicAdd(A.pool_cur, 4ull * tot + 4); *s_nt = 0; }
         __syncthreads();
         if (*s_base + 4ull * tot + 4 > A.pool_cap) { if (tid == 0) set_err(A.st, kErrPugPool, kCellRangeWide); return false; }
-        uint4* trip = reinterpret_cast<uint4*>(A.pool + ((*s_base + 3) & ~3ull));   // (umi, 0, gene, reads)
+        uint4* trip = reinterpret_cast<uint4*>(A.pool + ((*s_base + 3) & ~3ull));   // (umi, 0, gene, reads): a UMI of the phase kernels has 32 bits
         for (uint32_t i = tid; i < n; i += CNT) {
             const uint32_t g = tl[lg_v[v0 + i]];
             const uint64_t uw = cu[g];
             const KLab l = klab(C.W, C.HW, ch[g], coff[g]);
+            auto ref = [&](uint32_t j) { return klab_ref(l, j); };
             uint32_t gg[kMaxGenesPerLabel];
-            const uint32_t ng = genes_of(C, l.n, [&](uint32_t j) { return klab_ref(l, j); }, gg);
-            if (ng == 0xFFFFFFFFu) {
-                uint32_t k = 0;
-                wide_genes(l, [&](uint32_t) { ++k; });
-                uint32_t o = atomicAdd(s_nt, k);
-                wide_genes(l, [&](uint32_t gid) { trip[o++] = make_uint4((uint32_t)(uw >> 32), 0u, gid, (uint32_t)uw & kVCntMask); });
-                continue;
-            }
-            const uint32_t o = atomicAdd(s_nt, ng);
-            for (uint32_t q = 0; q < ng; ++q) trip[o + q] = make_uint4((uint32_t)(uw >> 32), 0u, gg[q], (uint32_t)uw & kVCntMask);
+            const uint32_t ng = genes_of(C, l.n, ref, gg);
+            uint32_t k = 0;
+            each_gene_of(C, l.n, ref, gg, ng, [&](uint32_t) { ++k; });
+            uint32_t o = atomicAdd(s_nt, k);
+            each_gene_of(C, l.n, ref, gg, ng, [&](uint32_t gid) { trip[o++] = make_uint4((uint32_t)(uw >> 32), 0u, gid, (uint32_t)uw & kVCntMask); });
         }
         __syncthreads();
-        const uint32_t nt = *s_nt;
-        bitonic_sort_by<CNT>(trip, nt, [](const uint4& x, const uint4& y) {
-            if (x.x != y.x) return x.x > y.x;
-            if (x.z != y.z) return x.z > y.z;
-            return x.w > y.w;
-        });
-        if (tid == 0 && nt) {
-            uint32_t best[kMaxGenesPerLabel];
-            uint32_t nbest = 0, maxc = 0, aggr = 0;
-            uint32_t cur_umi = trip[0].x, cg = trip[0].z;
-            bool wide = false;
-            uint32_t run0 = 0;   // first triplet of the current UMI
-            // a UMI whose tie set has more genes than best[] holds is a class of its own for the EM: the genes whose summed count
-            // is the maximum, ascending as the triplets are, written straight into the label area
-            auto emit_ties = [&](uint32_t i0, uint32_t i1, uint32_t maxc_) {
-                auto each_tied = [&](auto&& f) {
-                    for (uint32_t i = i0; i < i1;) {
-                        uint32_t j = i, sum = 0;
-                        for (; j < i1 && trip[j].z == trip[i].z; ++j) sum += trip[j].w;
-                        if (sum == maxc_) f(trip[i].z);
-                        i = j;
-                    }
-                };
-                uint32_t k = 0;
-                each_tied([&](uint32_t) { ++k; });
-                const uint32_t off = atomicAdd(&C.s_cnt[1], k), di = atomicAdd(&C.s_cnt[2], 1u);
-                if (off + k > C.lab_cap || 2 * (di + 1) > C.lab_cap) { C.s_cnt[3] = kErrPugLimit; return; }
-                uint32_t w = off;
-                each_tied([&](uint32_t gid) { C.labw[w++] = gid; });
-                C.labd[2 * di] = off; C.labd[2 * di + 1] = k;
-            };
-            for (uint32_t i = 0; i < nt; ++i) {
-                const uint4 t = trip[i];
-                if (i == 0 || t.x != cur_umi) {
-                    if (i) { if (wide && C.em) emit_ties(run0, i, maxc); else emit_molecule(C, best, wide ? 0xFFFFFFFFu : nbest); }
-                    run0 = i;
-                    cur_umi = t.x; cg = t.z;
-                    nbest = 1; best[0] = t.z; aggr = t.w; maxc = t.w; wide = false;
-                } else {
-                    if (t.z == cg) aggr += t.w; else { aggr = t.w; cg = t.z; }
-                    if (aggr > maxc) {
-                        maxc = aggr;
-                        if (!(nbest == 1 && best[0] == t.z)) { nbest = 1; best[0] = t.z; wide = false; }
-                    } else if (aggr == maxc) {
-                        if (nbest == kMaxGenesPerLabel) wide = true; else best[nbest++] = t.z;
-                    }
-                }
-            }
-            if (wide && C.em) emit_ties(run0, nt, maxc); else emit_molecule(C, best, wide ? 0xFFFFFFFFu : nbest);
-        }
+        large_component_from_triplets<CNT>(C, trip, *s_nt);
         if (tid == 0) A.alt[c.cell] = 1;   // used_alternative_strategy, pugutils.rs:1070
         __syncthreads();
     }
@@ -1495,7 +1433,10 @@ __global__ __launch_bounds__(CNT, CNT == 256 ? 4 : 1) void k_p2_cover(P2Args A, 
     if (n_bigc) {   // 65..4096 vertices: the graph kernel left their adjacency as rows of mask words
         const uint64_t* rows = reinterpret_cast<const uint64_t*>(A.pool + (((unsigned long long)x[1] << 32) | x[0]));
         const uint32_t* rowoff = A.pool + (((unsigned long long)x[3] << 32) | x[2]);
-        cover_big<CNT / 64>(C, mrec, mid_off, n_mid, n_bigc, rowoff, rows, s_mask, s_bestv, s_bestsz, wv, lane);
+        for (uint32_t b = 0; b < n_bigc; ++b) {
+            const uint32_t c0 = mid_off[n_mid + b];
+            cover_big<CNT / 64>(C, mid_off[n_mid + b + 1] - c0, RecordLabels{mrec, c0}, rows + rowoff[b], s_mask, s_bestv, s_bestsz, wv, lane);
+        }
     }
     if (d[15] >> 31) {   // components above --large-graph-thresh
         const uint32_t n_large = x[4];

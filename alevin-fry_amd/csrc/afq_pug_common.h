@@ -1,7 +1,8 @@
 // afq_pug_common.h — pieces shared by the two parsimony paths (afq_pug.hip: one workgroup per cell, every phase in
 // one kernel; afq_pug2.hip: phase kernels over UMI partitions): labels as they sit in the chunk, a resolved molecule's
-// way into the cell's column list / gene-level classes, and the monochromatic-arborescence covers of small components
-// (collapse_vertices / get_num_molecules, src/pugutils.rs:308-391, 1048-1261).  Device code only.
+// way into the cell's column list / gene-level classes, the monochromatic-arborescence covers of components of every size
+// (cover_lane4, cover_tiny8, cover_wave64, cover_big; collapse_vertices / get_num_molecules, src/pugutils.rs:308-391,
+// 1048-1261) and the winner-take-all rule above --large-graph-thresh (large_component_from_triplets).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +49,7 @@ __device__ __forceinline__ bool umi_edge(uint32_t ux, uint32_t cx, uint32_t uy, 
 struct Lab {
     const uint32_t* p;
     uint32_t n;
+    __device__ __forceinline__ uint32_t ref(uint32_t j) const { return p[j] & 0x7FFFFFFFu; }
 };
 __device__ __forceinline__ Lab rec_label(const PugCtx& c, uint32_t rec_dw) {
     Lab l;
@@ -79,22 +81,54 @@ __device__ __forceinline__ bool lab_equal(const Lab& a, const Lab& b) {
     return true;
 }
 
+// g[0 .. ng): distinct gene ids, ascending.  Puts gid among them and returns how many there are now, or 0xFFFFFFFF when gid is
+// new and the set already holds kMaxGenesPerLabel (nothing is changed then).
+__device__ __forceinline__ uint32_t gene_set_insert(uint32_t* g, uint32_t ng, uint32_t gid) {
+    uint32_t p = 0;
+    while (p < ng && g[p] < gid) ++p;
+    if (p < ng && g[p] == gid) return ng;
+    if (ng == kMaxGenesPerLabel) return 0xFFFFFFFFu;
+    for (uint32_t q = ng; q > p; --q) g[q] = g[q - 1];
+    g[p] = gid;
+    return ng + 1;
+}
 // sorted distinct gene ids of a list of refs (pugutils.rs:1213-1225, 1296-1298); returns the count
-// or 0xFFFFFFFF when more than kMaxGenesPerLabel distinct genes turn up.
+// or 0xFFFFFFFF when more than kMaxGenesPerLabel distinct genes turn up.  ref(j) = 0xFFFFFFFF: no ref, skipped.
+// through_t2g: the refs are transcripts; else they already are gene ids (gene-level labels).
 template <typename GetRef>
-__device__ __forceinline__ uint32_t genes_of(const PugCtx& c, uint32_t n, GetRef&& ref, uint32_t* g) {
+__device__ __forceinline__ uint32_t genes_of(const PugCtx& c, uint32_t n, GetRef&& ref, uint32_t* g, bool through_t2g) {
     uint32_t k = 0;
     for (uint32_t j = 0; j < n; ++j) {
-        const uint32_t gid = c.gene_level ? ref(j) : c.t2g[ref(j)];  // gene-level labels already hold gene ids
-        uint32_t p = 0;
-        while (p < k && g[p] < gid) ++p;
-        if (p < k && g[p] == gid) continue;
-        if (k == kMaxGenesPerLabel) return 0xFFFFFFFFu;
-        for (uint32_t q = k; q > p; --q) g[q] = g[q - 1];
-        g[p] = gid;
-        ++k;
+        const uint32_t t = ref(j);
+        if (t == 0xFFFFFFFFu) continue;
+        k = gene_set_insert(g, k, through_t2g ? c.t2g[t] : t);
+        if (k == 0xFFFFFFFFu) break;
     }
     return k;
+}
+template <typename GetRef>
+__device__ __forceinline__ uint32_t genes_of(const PugCtx& c, uint32_t n, GetRef&& ref, uint32_t* g) {
+    return genes_of(c, n, ref, g, !c.gene_level);
+}
+// The distinct genes of a list of refs in order of first appearance, found by looking back over the refs - for a label with more
+// of them than kMaxGenesPerLabel (a large gene family; rare), which no register array holds.  Every ref(j) is a real ref here:
+// unlike genes_of this skips none.
+template <typename GetRef, typename F>
+__device__ __forceinline__ void each_distinct_gene(const PugCtx& c, uint32_t n, GetRef&& ref, bool through_t2g, F&& f) {
+    auto gene = [&](uint32_t j) -> uint32_t { const uint32_t t = ref(j); return through_t2g ? c.t2g[t] : t; };
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t gj = gene(j);
+        bool first = true;
+        for (uint32_t q = 0; q < j && first; ++q) first = gene(q) != gj;
+        if (first) f(gj);
+    }
+}
+// Every gene of a label once, given what genes_of made of it: out of g[0 .. ng), or - it overflowed - by looking back.
+// For whole labels: every ref(j) is a real ref (each_distinct_gene).
+template <typename GetRef, typename F>
+__device__ __forceinline__ void each_gene_of(const PugCtx& c, uint32_t n, GetRef&& ref, const uint32_t* g, uint32_t ng, F&& f) {
+    if (ng == 0xFFFFFFFFu) each_distinct_gene(c, n, ref, !c.gene_level, f);
+    else for (uint32_t q = 0; q < ng; ++q) f(g[q]);
 }
 
 // One resolved molecule with gene label g[0..ng): a column, a gene-level class for the EM, or nothing.
@@ -268,6 +302,12 @@ __device__ __forceinline__ void append_class2(const PugCtx& c, bool want, uint32
     }
 }
 
+// Room in the cell's label area for one EM class of up to n genes: its first word, its descriptor.  false: full (the error is set).
+__device__ __forceinline__ bool reserve_class(const PugCtx& c, uint32_t n, uint32_t& off, uint32_t& di) {
+    off = atomicAdd(&c.s_cnt[1], n); di = atomicAdd(&c.s_cnt[2], 1u);
+    if (off + n > c.lab_cap || 2 * (di + 1) > c.lab_cap) { c.s_cnt[3] = kErrPugLimit; return false; }
+    return true;
+}
 // A class of more than kMaxGenesPerLabel genes for the EM (a read that hits a large gene family: rare, but real data has
 // them), written straight into the cell's label area by ONE lane: cand(j) is the j-th ref of the arborescence's first
 // label - a gene id at gene level - or 0xFFFFFFFF when it is not shared by every vertex; n, the first label's length,
@@ -275,8 +315,8 @@ __device__ __forceinline__ void append_class2(const PugCtx& c, bool want, uint32
 // molecule's first vertex is a different one).  Distinct genes are kept ascending by insertion, in global memory.
 template <typename Cand>
 __device__ __forceinline__ void emit_wide_class(const PugCtx& c, uint32_t n, Cand&& cand) {
-    const uint32_t off = atomicAdd(&c.s_cnt[1], n), di = atomicAdd(&c.s_cnt[2], 1u);
-    if (off + n > c.lab_cap || 2 * (di + 1) > c.lab_cap) { c.s_cnt[3] = kErrPugLimit; return; }
+    uint32_t off, di;
+    if (!reserve_class(c, n, off, di)) return;
     uint32_t* w = c.labw + off;
     uint32_t k = 0;
     for (uint32_t j = 0; j < n; ++j) {
@@ -292,22 +332,95 @@ __device__ __forceinline__ void emit_wide_class(const PugCtx& c, uint32_t n, Can
     }
     c.labd[2 * di] = off; c.labd[2 * di + 1] = k;
 }
-// the label of the vertex in slot `slot` of the gathered component records (6b): short labels travel in the record
-struct RecLab { Lab l; uint32_t r[4]; };
-__device__ __forceinline__ void rec_lab(const uint4* mrec, size_t slot, RecLab& o) {
-    const uint4 qa = mrec[2 * slot], qb = mrec[2 * slot + 1];
-    o.l.n = qa.y;
-    if (qa.y <= 4) { o.r[0] = qa.z; o.r[1] = qa.w; o.r[2] = qb.x; o.r[3] = qb.y; o.l.p = o.r; }
-    else o.l.p = reinterpret_cast<const uint32_t*>((uintptr_t)(((uint64_t)qa.w << 32) | qa.z));
+// One molecule whose label is the refs cand(j), j < n (0xFFFFFFFF: none): its genes gathered in g (kMaxGenesPerLabel words,
+// ONE lane's), then a column, a class for the EM - a wide one when g cannot hold it - or nothing.
+template <typename Cand>
+__device__ __forceinline__ void emit_label_molecule(const PugCtx& c, uint32_t n, Cand&& cand, uint32_t* g) {
+    const uint32_t ng = genes_of(c, n, cand, g);
+    if (ng == 0xFFFFFFFFu && c.em) emit_wide_class(c, n, cand); else emit_molecule(c, g, ng);
 }
+
+// get_num_molecules_large_component (pugutils.rs:916-982) behind its sort: trip[0 .. nt) are the (UMI lo, UMI hi, gene, reads)
+// triplets of a component above --large-graph-thresh, ascending by UMI (hi, lo), gene, reads; per UMI one molecule, the gene(s)
+// with the most reads (resolve_num_molecules_crlike_from_vec, pugutils.rs:644-749).  ONE thread.
+__device__ __forceinline__ void molecules_of_sorted_triplets(const PugCtx& c, const uint4* trip, uint32_t nt) {
+    uint32_t best[kMaxGenesPerLabel];
+    uint32_t nbest = 0, maxc = 0, aggr = 0, cg = 0;
+    bool wide = false;
+    uint32_t run0 = 0;   // first triplet of the current UMI
+    // a UMI whose tie set has more genes than best[] holds is a class of its own for the EM: the genes whose summed count
+    // is the maximum, ascending as the triplets are, written straight into the label area
+    auto emit_ties = [&](uint32_t i0, uint32_t i1) {
+        auto each_tied = [&](auto&& f) {
+            for (uint32_t i = i0; i < i1;) {
+                uint32_t j = i, sum = 0;
+                for (; j < i1 && trip[j].z == trip[i].z; ++j) sum += trip[j].w;
+                if (sum == maxc) f(trip[i].z);
+                i = j;
+            }
+        };
+        uint32_t k = 0, off, di;
+        each_tied([&](uint32_t) { ++k; });
+        if (!reserve_class(c, k, off, di)) return;
+        uint32_t w = off;
+        each_tied([&](uint32_t gid) { c.labw[w++] = gid; });
+        c.labd[2 * di] = off; c.labd[2 * di + 1] = k;
+    };
+    auto emit_umi = [&](uint32_t i1) { if (wide && c.em) emit_ties(run0, i1); else emit_molecule(c, best, wide ? 0xFFFFFFFFu : nbest); };
+    for (uint32_t i = 0; i < nt; ++i) {
+        const uint4 t = trip[i];
+        if (i == 0 || t.x != trip[run0].x || t.y != trip[run0].y) {
+            if (i) emit_umi(i);
+            run0 = i;
+            cg = t.z;
+            nbest = 1; best[0] = t.z; aggr = t.w; maxc = t.w; wide = false;
+        } else {
+            if (t.z == cg) aggr += t.w; else { aggr = t.w; cg = t.z; }
+            if (aggr > maxc) {
+                maxc = aggr;
+                if (!(nbest == 1 && best[0] == t.z)) { nbest = 1; best[0] = t.z; wide = false; }
+            } else if (aggr == maxc) {
+                if (nbest == kMaxGenesPerLabel) wide = true; else best[nbest++] = t.z;
+            }
+        }
+    }
+    if (nt) emit_umi(nt);
+}
+// The molecules of one component above --large-graph-thresh from its nt triplets (any order).  Workgroup-wide call.
+template <int NT>
+__device__ __forceinline__ void large_component_from_triplets(const PugCtx& c, uint4* trip, uint32_t nt) {
+    bitonic_sort_by<NT>(trip, nt, [](const uint4& a, const uint4& b) {
+        if (a.y != b.y) return a.y > b.y;
+        if (a.x != b.x) return a.x > b.x;
+        if (a.z != b.z) return a.z > b.z;
+        return a.w > b.w;
+    });
+    if (threadIdx.x == 0) molecules_of_sorted_triplets(c, trip, nt);
+}
+// the label of a vertex as it travels in its two gathered component records (6b): short labels in the record itself
+struct RecLab {
+    uint4 qa, qb;
+    uint32_t n;
+    __device__ __forceinline__ uint32_t ref(uint32_t j) const {
+        if (n <= 4) return j == 0 ? qa.z : j == 1 ? qa.w : j == 2 ? qb.x : qb.y;
+        return reinterpret_cast<const uint32_t*>((uintptr_t)(((uint64_t)qa.w << 32) | qa.z))[j] & 0x7FFFFFFFu;
+    }
+};
 __device__ __forceinline__ bool rec_contains(const uint4& qa, const uint4& qb, uint32_t t) {
     if (qa.y <= 4) return t == qa.z || t == qa.w || t == qb.x || t == qb.y;   // (unused places hold 0xFFFFFFFF: no ref)
     const Lab l{reinterpret_cast<const uint32_t*>((uintptr_t)(((uint64_t)qa.w << 32) | qa.z)), qa.y};
     return lab_contains(l, t);
 }
+// The labels of a component for cover_big: vertex i of it is the record pair in slot c0 + i.
+struct RecordLabels {
+    const uint4* mrec;
+    size_t c0;
+    __device__ __forceinline__ RecLab label(uint32_t i) const { const uint4 qa = mrec[2 * (c0 + i)]; return RecLab{qa, mrec[2 * (c0 + i) + 1], qa.y}; }
+    __device__ __forceinline__ bool contains(uint32_t i, uint32_t t) const { return rec_contains(mrec[2 * (c0 + i)], mrec[2 * (c0 + i) + 1], t); }
+};
 // cand() of emit_wide_class for a component held in those records: ref j of the vertex in slot b0 + fv if every vertex
-// of `mask` (bit i = slot b0 + i) has it.  (Everything out of the records' own words: a RecLab points into a private array, which
-// puts it - and 72 bytes of every lane of the calling kernel - into scratch memory.)
+// of `mask` (bit i = slot b0 + i) has it.  (Everything out of the records' own words, by selects: an array of the refs indexed at run time
+// would put it - and 72 bytes of every lane of the calling kernel - into scratch memory.)
 __device__ __forceinline__ void emit_wide_from_records(const PugCtx& c, const uint4* mrec, size_t b0, uint32_t fv, uint64_t mask) {
     const uint4 fa = mrec[2 * (b0 + fv)], fb = mrec[2 * (b0 + fv) + 1];
     const uint32_t* fp = fa.y > 4 ? reinterpret_cast<const uint32_t*>((uintptr_t)(((uint64_t)fa.w << 32) | fa.z)) : nullptr;
@@ -336,7 +449,8 @@ __device__ __forceinline__ uint64_t wave_or64(uint64_t v) {
     // four in five of all that reach the cover; a wave to each left 59 of its 64 lanes without a vertex.
 // The covers run in one of three ways (MODE):
 //   kCoverOrdered  the records of a component lie in the reference's vertex order (class by first appearance, then UMI): ties
-//                  between equal-size arborescences go to the first one met, as in the reference (afq_pug.hip; cover_big).
+//                  between equal-size arborescences go to the first one met, as in the reference (afq_pug.hip; cover_big, whatever
+//                  its labels are read from, always runs this way).
 //   kCoverDefer    the records lie in NO particular order (afq_pug2.hip's k_p2_cover).  A round whose largest arborescence is
 //                  unique does not depend on the order - same winner, same molecule, same vertices left; at the first round that
 //                  meets two different vertex sets of the largest size the component is SET ASIDE: its list index and the mask
@@ -495,13 +609,7 @@ __device__ __forceinline__ void cover_tiny8(const PugCtx& C, const uint4* mrec, 
                             for (int w = 0; w < 4; ++w) if ((uint32_t)w == k4) c4[w] = t;
                             ++k4;
                         } else {
-                            const uint32_t gid = C.gene_level ? t : C.t2g[t];
-                            uint32_t q = 0;
-                            while (q < ng && g[q] < gid) ++q;
-                            if (!(q < ng && g[q] == gid)) {
-                                if (ng == kMaxGenesPerLabel) wide = true;
-                                else { for (uint32_t r = ng; r > q; --r) g[r] = g[r - 1]; g[q] = gid; ++ng; }
-                            }
+                            { const uint32_t k = gene_set_insert(g, ng, C.gene_level ? t : C.t2g[t]); if (k == 0xFFFFFFFFu) wide = true; else ng = k; }
                         }
                     }
                 }
@@ -816,13 +924,7 @@ __device__ __forceinline__ void cover_wave64(const PugCtx& C, const uint4* mrec,
                         for (int w = 0; w < 4; ++w) if ((uint32_t)w == k4) c4[w] = t;
                         ++k4;
                     } else {
-                        const uint32_t gid = C.gene_level ? t : C.t2g[t];
-                        uint32_t q = 0;
-                        while (q < ng && g[q] < gid) ++q;
-                        if (!(q < ng && g[q] == gid)) {
-                            if (ng == kMaxGenesPerLabel) wide = true;
-                            else { for (uint32_t r = ng; r > q; --r) g[r] = g[r - 1]; g[q] = gid; ++ng; }
-                        }
+                        { const uint32_t k = gene_set_insert(g, ng, C.gene_level ? t : C.t2g[t]); if (k == 0xFFFFFFFFu) wide = true; else ng = k; }
                     }
                 }
             }
@@ -852,132 +954,115 @@ __device__ __forceinline__ void cover_wave64(const PugCtx& C, const uint4* mrec,
     }
     }
 
-    // ---- 6c'. components of 65..4096 vertices, one at a time by the whole workgroup ----
-    // The same greedy cover over multi-word masks: lane l of a wave holds mask word l, the component's adjacency is n rows of
-    // nw = ceil(n / 64) words (`rows`), the uncovered set and the round's best arborescence sit in LDS (s_mask[0], s_mask[1]).
-    // The candidates of a round - the uncovered vertices, ascending - are dealt to the waves; the winner is the largest
-    // arborescence, the smallest vertex among equals (the reference takes the first it meets in ascending order: pugutils.rs:1090-1160).
-template <int NWAVES>
-__device__ __forceinline__ void cover_big(const PugCtx& C, const uint4* mrec, const uint32_t* mid_off, uint32_t first, uint32_t count,
-                                          const uint32_t* rowoff, const uint64_t* rows_base, uint64_t (*s_mask)[64], uint32_t* s_bestv, uint32_t* s_bestsz,
-                                          uint32_t wv, uint32_t lane)
+// ---- one component of 65..4096 vertices, by the whole workgroup ----
+// The same greedy cover over multi-word masks: lane l of a wave holds mask word l, the component's adjacency is n rows of
+// nw = ceil(n / 64) words (`rows`), the uncovered set and the round's best arborescence sit in LDS (s_mask[0], s_mask[1]).
+// The candidates of a round - the uncovered vertices, ascending - are dealt to the waves; the winner is the largest
+// arborescence, the smallest vertex among equals (the reference takes the first it meets in ascending order: pugutils.rs:1090-1160).
+// L: where the labels are - L.label(i) is the label of vertex i of the component (its length .n, its refs .ref(j)),
+// L.contains(i, t) whether it holds ref t.  Workgroup-wide call.
+template <int NWAVES, typename Labels>
+__device__ __forceinline__ void cover_big(const PugCtx& C, uint32_t n, const Labels& L, const uint64_t* rows, uint64_t (*s_mask)[64],
+                                          uint32_t* s_bestv, uint32_t* s_bestsz, uint32_t wv, uint32_t lane)
 {
-    const uint32_t tid = wv * 64 + lane;
-    for (uint32_t b = 0; b < count; ++b) {
-        const uint32_t c0 = mid_off[first + b], n = mid_off[first + b + 1] - c0, nw = (n + 63) / 64;
-        const uint64_t* rows = rows_base + rowoff[b];
-        __syncthreads();
-        if (tid < nw) s_mask[0][tid] = (tid + 1 < nw || (n & 63) == 0) ? ~0ull : ((1ull << (n & 63)) - 1);
-        __syncthreads();
-        for (;;) {
-            uint32_t rem = 0;
-            for (uint32_t w = 0; w < nw; ++w) rem += (uint32_t)__popcll(s_mask[0][w]);
-            if (rem == 0) break;
-            uint32_t my_best_sz = 0, my_best_v = 0xFFFFFFFFu;
-            uint64_t my_best_word = 0;   // lane l: word l of this wave's best arborescence
-            const uint64_t ucw = lane < nw ? s_mask[0][lane] : 0ull;
-            uint32_t seen = 0;
-            for (uint32_t w = 0; w < nw && my_best_sz != rem; ++w) {
-                uint64_t bits = s_mask[0][w];
-                for (; bits; bits &= bits - 1, ++seen) {
-                    if (seen % (NWAVES) != wv) continue;
-                    const uint32_t v = w * 64 + (uint32_t)__builtin_ctzll(bits);
-                    RecLab lv;
-                    rec_lab(mrec, (size_t)c0 + v, lv);
-                    uint64_t mvw = 0;
-                    uint32_t mv_sz = 0;
-                    for (uint32_t j = 0; j < lv.l.n; ++j) {
-                        const uint32_t t = lv.l.p[j] & 0x7FFFFFFFu;
-                        uint64_t Aw = 0;   // uncovered vertices whose label has t: 64 vertices per step, a lane each
-                        for (uint32_t cw = 0; cw < nw; ++cw) {
-                            const uint32_t i = cw * 64 + lane;
-                            const uint64_t ucword = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ucw >> 32), (int)cw) << 32) | (uint32_t)__shfl((int)(uint32_t)ucw, (int)cw);
-                            bool in = i < n && ((ucword >> lane) & 1ull);
-                            if (in) { const uint4 qa = mrec[2 * ((size_t)c0 + i)], qb = mrec[2 * ((size_t)c0 + i) + 1]; in = rec_contains(qa, qb, t); }
-                            const uint64_t word = __ballot(in);
-                            if (lane == cw) Aw = word;
-                        }
-                        uint64_t Rw = (lane == (v >> 6)) ? (1ull << (v & 63)) : 0ull, Fw = Rw;
-                        for (;;) {
-                            uint64_t Nw = 0;   // OR of the rows of the frontier's vertices
-                            for (uint32_t fw = 0; fw < nw; ++fw) {
-                                uint64_t fb = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(Fw >> 32), (int)fw) << 32) | (uint32_t)__shfl((int)(uint32_t)Fw, (int)fw);
-                                for (; fb; fb &= fb - 1) {
-                                    const uint32_t x = fw * 64 + (uint32_t)__builtin_ctzll(fb);
-                                    if (lane < nw) Nw |= rows[(size_t)x * nw + lane];
-                                }
-                            }
-                            Fw = Nw & Aw & ~Rw;
-                            Rw |= Fw;
-                            if (!__any(Fw != 0)) break;
-                        }
-                        uint32_t sz = (uint32_t)__popcll(Rw);
-#pragma unroll
-                        for (int dd = 32; dd > 0; dd >>= 1) sz += __shfl_xor(sz, dd);
-                        if (sz > mv_sz) { mv_sz = sz; mvw = Rw; }
-                    }
-                    if (mv_sz > my_best_sz) { my_best_sz = mv_sz; my_best_v = v; my_best_word = mvw; }
-                    if (my_best_sz == rem) break;   // (everything that is left: no later candidate is larger, none of this wave's is earlier)
-                }
-            }
-            if (lane == 0) { s_bestv[wv] = my_best_v; s_bestsz[wv] = my_best_sz; }
-            __syncthreads();
-            uint32_t win = 0;
-            for (uint32_t w = 1; w < (uint32_t)(NWAVES); ++w)
-                if (s_bestsz[w] > s_bestsz[win] || (s_bestsz[w] == s_bestsz[win] && s_bestv[w] < s_bestv[win])) win = w;
-            if (s_bestsz[win] == 0) { if (tid == 0) C.s_cnt[3] = kErrPugLimit; break; }   // a vertex with an empty label
-            if (wv == win && lane < nw) s_mask[1][lane] = my_best_word;
-            __syncthreads();
-            if (wv == 0) {   // the refs every vertex of the arborescence has (pugutils.rs:1161-1188) -> genes
-                uint32_t fv = 0xFFFFFFFFu;
-                for (uint32_t w = 0; w < nw && fv == 0xFFFFFFFFu; ++w) if (s_mask[1][w]) fv = w * 64 + (uint32_t)__builtin_ctzll(s_mask[1][w]);
-                RecLab lf;
-                rec_lab(mrec, (size_t)c0 + fv, lf);
-                auto all_have = [&](uint32_t t) -> bool {   // wave-wide
+    const uint32_t tid = wv * 64 + lane, nw = (n + 63) / 64;
+    __syncthreads();
+    if (tid < nw) s_mask[0][tid] = (tid + 1 < nw || (n & 63) == 0) ? ~0ull : ((1ull << (n & 63)) - 1);
+    __syncthreads();
+    for (;;) {
+        uint32_t rem = 0;
+        for (uint32_t w = 0; w < nw; ++w) rem += (uint32_t)__popcll(s_mask[0][w]);
+        if (rem == 0) break;
+        uint32_t my_best_sz = 0, my_best_v = 0xFFFFFFFFu;
+        uint64_t my_best_word = 0;   // lane l: word l of this wave's best arborescence
+        const uint64_t ucw = lane < nw ? s_mask[0][lane] : 0ull;
+        uint32_t seen = 0;
+        for (uint32_t w = 0; w < nw && my_best_sz != rem; ++w) {
+            uint64_t bits = s_mask[0][w];
+            for (; bits; bits &= bits - 1, ++seen) {
+                if (seen % (NWAVES) != wv) continue;
+                const uint32_t v = w * 64 + (uint32_t)__builtin_ctzll(bits);
+                const auto lv = L.label(v);
+                uint64_t mvw = 0;
+                uint32_t mv_sz = 0;
+                for (uint32_t j = 0; j < lv.n; ++j) {
+                    const uint32_t t = lv.ref(j);
+                    uint64_t Aw = 0;   // uncovered vertices whose label has t: 64 vertices per step, a lane each
                     for (uint32_t cw = 0; cw < nw; ++cw) {
                         const uint32_t i = cw * 64 + lane;
-                        bool miss = i < n && ((s_mask[1][cw] >> lane) & 1ull);
-                        if (miss) { const uint4 qa = mrec[2 * ((size_t)c0 + i)], qb = mrec[2 * ((size_t)c0 + i) + 1]; miss = !rec_contains(qa, qb, t); }
-                        if (__any(miss)) return false;
+                        const uint64_t ucword = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ucw >> 32), (int)cw) << 32) | (uint32_t)__shfl((int)(uint32_t)ucw, (int)cw);
+                        const bool in = i < n && ((ucword >> lane) & 1ull) && L.contains(i, t);
+                        const uint64_t word = __ballot(in);
+                        if (lane == cw) Aw = word;
                     }
-                    return true;
-                };
-                uint32_t g[kMaxGenesPerLabel];
-                uint32_t ng = 0;
-                bool wide = false;
-                for (uint32_t j = 0; j < lf.l.n; ++j) {
-                    const uint32_t t = lf.l.p[j] & 0x7FFFFFFFu;
-                    if (!all_have(t)) continue;
-                    if (lane == 0) {
-                        const uint32_t gid = C.gene_level ? t : C.t2g[t];
-                        uint32_t q = 0;
-                        while (q < ng && g[q] < gid) ++q;
-                        if (!(q < ng && g[q] == gid)) {
-                            if (ng == kMaxGenesPerLabel) wide = true;
-                            else { for (uint32_t r = ng; r > q; --r) g[r] = g[r - 1]; g[q] = gid; ++ng; }
+                    uint64_t Rw = (lane == (v >> 6)) ? (1ull << (v & 63)) : 0ull, Fw = Rw;
+                    for (;;) {
+                        uint64_t Nw = 0;   // OR of the rows of the frontier's vertices
+                        for (uint32_t fw = 0; fw < nw; ++fw) {
+                            uint64_t fb = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(Fw >> 32), (int)fw) << 32) | (uint32_t)__shfl((int)(uint32_t)Fw, (int)fw);
+                            for (; fb; fb &= fb - 1) {
+                                const uint32_t x = fw * 64 + (uint32_t)__builtin_ctzll(fb);
+                                if (lane < nw) Nw |= rows[(size_t)x * nw + lane];
+                            }
                         }
+                        Fw = Nw & Aw & ~Rw;
+                        Rw |= Fw;
+                        if (!__any(Fw != 0)) break;
                     }
+                    uint32_t sz = (uint32_t)__popcll(Rw);
+#pragma unroll
+                    for (int dd = 32; dd > 0; dd >>= 1) sz += __shfl_xor(sz, dd);
+                    if (sz > mv_sz) { mv_sz = sz; mvw = Rw; }
                 }
-                if (lane == 0) {
-                    if (wide && C.em)
-                        emit_wide_class(C, lf.l.n, [&](uint32_t j) -> uint32_t {
-                            const uint32_t t = lf.l.p[j] & 0x7FFFFFFFu;
-                            for (uint32_t cw = 0; cw < nw; ++cw)
-                                for (uint64_t m = s_mask[1][cw]; m; m &= m - 1) {
-                                    const size_t sl = (size_t)c0 + cw * 64 + (uint32_t)__builtin_ctzll(m);
-                                    if (!rec_contains(mrec[2 * sl], mrec[2 * sl + 1], t)) return 0xFFFFFFFFu;
-                                }
-                            return t;
-                        });
-                    else emit_molecule(C, g, wide ? 0xFFFFFFFFu : ng);
-                }
+                if (mv_sz > my_best_sz) { my_best_sz = mv_sz; my_best_v = v; my_best_word = mvw; }
+                if (my_best_sz == rem) break;   // (everything that is left: no later candidate is larger, none of this wave's is earlier)
             }
-            __syncthreads();
-            if (tid < nw) s_mask[0][tid] &= ~s_mask[1][tid];
-            __syncthreads();
+        }
+        if (lane == 0) { s_bestv[wv] = my_best_v; s_bestsz[wv] = my_best_sz; }
+        __syncthreads();
+        uint32_t win = 0;
+        for (uint32_t w = 1; w < (uint32_t)(NWAVES); ++w)
+            if (s_bestsz[w] > s_bestsz[win] || (s_bestsz[w] == s_bestsz[win] && s_bestv[w] < s_bestv[win])) win = w;
+        if (s_bestsz[win] == 0) { if (tid == 0) C.s_cnt[3] = kErrPugLimit; break; }   // a vertex with an empty label
+        if (wv == win && lane < nw) s_mask[1][lane] = my_best_word;
+        __syncthreads();
+        if (wv == 0) {   // the refs every vertex of the arborescence has (pugutils.rs:1161-1188) -> genes
+            uint32_t fv = 0xFFFFFFFFu;
+            for (uint32_t w = 0; w < nw && fv == 0xFFFFFFFFu; ++w) if (s_mask[1][w]) fv = w * 64 + (uint32_t)__builtin_ctzll(s_mask[1][w]);
+            const auto lf = L.label(fv);
+            auto all_have = [&](uint32_t t) -> bool {   // wave-wide
+                for (uint32_t cw = 0; cw < nw; ++cw) {
+                    const uint32_t i = cw * 64 + lane;
+                    const bool miss = i < n && ((s_mask[1][cw] >> lane) & 1ull) && !L.contains(i, t);
+                    if (__any(miss)) return false;
+                }
+                return true;
+            };
+            uint32_t g[kMaxGenesPerLabel];
+            uint32_t ng = 0;
+            bool wide = false;
+            for (uint32_t j = 0; j < lf.n; ++j) {
+                const uint32_t t = lf.ref(j);
+                if (!all_have(t)) continue;
+                if (lane == 0) { const uint32_t k = gene_set_insert(g, ng, C.gene_level ? t : C.t2g[t]); if (k == 0xFFFFFFFFu) wide = true; else ng = k; }
+            }
+            if (lane == 0) {
+                if (wide && C.em)
+                    emit_wide_class(C, lf.n, [&](uint32_t j) -> uint32_t {
+                        const uint32_t t = lf.ref(j);
+                        for (uint32_t cw = 0; cw < nw; ++cw)
+                            for (uint64_t m = s_mask[1][cw]; m; m &= m - 1)
+                                if (!L.contains(cw * 64 + (uint32_t)__builtin_ctzll(m), t)) return 0xFFFFFFFFu;
+                        return t;
+                    });
+                else emit_molecule(C, g, wide ? 0xFFFFFFFFu : ng);
+            }
         }
         __syncthreads();
+        if (tid < nw) s_mask[0][tid] &= ~s_mask[1][tid];
+        __syncthreads();
     }
+    __syncthreads();
 }
 
 }  // namespace afq

@@ -80,6 +80,24 @@ def test_large_component_fallback_sets_alt_flag(oracle):
     assert_same_result(got, want)
 
 
+def test_large_component_fallback_keeps_umis_apart_beyond_32_bits(oracle):
+    """Above --large-graph-thresh a component is resolved per UMI, and with 8-byte UMI fields (the one-workgroup kernel's) a
+    UMI has more than 32 bits: A and B below are one base apart, in bit 34, and equal in their low words.  The component of
+    their four vertices (4 > 3) gives two molecules - A: gene 0 (3 reads against 1), B: gene 2 (4 against 1); a walk that
+    told UMIs apart by the low word alone would see one UMI and count ONE molecule, for gene 2 (4 reads against 3 and 2), and the row would begin (0, 1.0)."""
+    A = (5 << 36) | 0x0ABCDEF1
+    B = A ^ (1 << 34)
+    reads = [(A, [0, 2])] + [(A, [0])] * 2 + [(B, [2, 4])] + [(B, [4])] * 3 + [((7 << 36) | 0x11111111, [0]), ((9 << 36) | 0x22222222, [2])]
+    b, off = rad.encode_cells([(21, reads)], 4, 8)
+    t2g = np.asarray([0, 0, 1, 1, 2, 2], np.uint32)
+    for res in ("parsimony", "parsimony-em", "parsimony-gene"):
+        cfg = pkg.WorkerConfig.for_resolution(res, num_genes=3, num_rows=3, umi_bytes=8, umi_len=22, small_thresh=0, large_graph_thresh=3)
+        got, want = run_both(oracle, cfg, t2g, b, off)
+        assert [(int(g), float(v)) for g, v in rows_of(got)[0]] == [(0, 2.0), (1, 1.0), (2, 1.0)], res
+        assert got.flags[0] & pkg._abi.CELL_ALT_RES, res
+        assert_same_result(got, want, what=res)
+
+
 def test_components_beyond_one_wave(oracle):
     """All 256 UMIs over 4 positions on one transcript form one 256-vertex component (each vertex has 12
     neighbours); a second, overlapping class splits the cover.  Exercises the multi-word cover."""

@@ -309,7 +309,7 @@ def test_molecule8_column_is_the_general_rule_on_host(tmp_path):
         a = text.index(start)
         return text[a:text.index(end, a)]
 
-    parts = [grab(com, "template <typename GetRef>\n__device__ __forceinline__ uint32_t genes_of(", "// One resolved molecule with gene label"),
+    parts = [grab(com, "__device__ __forceinline__ uint32_t gene_set_insert(", "// One resolved molecule with gene label"),
              grab(com, "__device__ __forceinline__ uint32_t molecule_column_n(", "__device__ __forceinline__ void emit_molecule("),
              grab(src, "__device__ __forceinline__ void sort8", "__device__ __forceinline__ uint32_t molecule8_column"),
              grab(src, "__device__ __forceinline__ uint32_t molecule8_column", "// L8: labels of 5..8 refs by their own lane")]
@@ -486,7 +486,7 @@ def test_parsimony_molecule_rules_are_the_oracles_on_host(tmp_path):
 constexpr uint32_t kMaxGenesPerLabel = 64, kErrPugLimit = 7, kErrSlotRange = 9;
 struct PugCtx { const uint32_t* t2g; uint32_t gene_level, usa, em, num_rows, uo, ao, lab_cap; uint32_t* labw; uint32_t* labd; uint32_t* s_cnt; };
 static uint32_t atomicAdd(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v; return o; }
-''' + grab("template <typename GetRef>\n__device__ __forceinline__ uint32_t genes_of(", "// One resolved molecule with gene label") + \
+''' + grab("__device__ __forceinline__ uint32_t gene_set_insert(", "// One resolved molecule with gene label") + \
         grab("__device__ __forceinline__ uint32_t molecule_column_n(", "__device__ __forceinline__ void emit_molecule(") + \
         grab("__device__ __forceinline__ uint32_t molecule2_column(", "// Up to four refs -> their distinct gene ids") + \
         grab("__device__ __forceinline__ uint32_t genes_of4(", "// Append one column per lane that has one.") + r'''
@@ -650,6 +650,165 @@ int main() {
     for r, g in zip(rows, got):
         want = sorted(set(x for x in r if x != 0xFFFFFFFF))
         assert g[0] == len(want) and g[1:] == want, (r, g, want)
+
+
+def test_gene_sets_with_skipped_refs_on_host(tmp_path):
+    """csrc/afq_pug_common.h: `gene_set_insert` / `genes_of` - the sorted distinct gene ids of a list of refs, where a ref of
+    0xFFFFFFFF is none ("not shared by every vertex") and is skipped.  The functions' own source text on the host: every list of
+    up to six refs over nine transcripts, each with a random skip mask, through t2g or as gene ids, against sorted(set());
+    and a list of 65 distinct genes for the overflow return (64 of them still fit).  No GPU."""
+    import itertools
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    src = open(os.path.join(ROOT, "alevin-fry_amd", "csrc", "afq_pug_common.h")).read()
+    a = src.index("__device__ __forceinline__ uint32_t gene_set_insert(")
+    fns = src[a:src.index("// One resolved molecule with gene label", a)]
+    host = r'''#include <cstdint>
+#include <cstdio>
+#define __device__
+#define __forceinline__ inline
+constexpr uint32_t kMaxGenesPerLabel = 64;
+struct PugCtx { const uint32_t* t2g; uint32_t gene_level; };
+''' + fns + r'''
+int main() {
+    static const uint32_t T2G[9] = {0, 0, 1, 1, 2, 2, 3, 4, 5};
+    unsigned through, n;
+    while (scanf("%u %u", &through, &n) == 2) {
+        uint32_t r[80], g[kMaxGenesPerLabel + 1];
+        for (unsigned i = 0; i < n; ++i) if (scanf("%u", &r[i]) != 1) return 2;
+        g[kMaxGenesPerLabel] = 0xDEADBEEFu;
+        PugCtx C{T2G, 7u};   // (gene_level is not what decides: the argument is)
+        const uint32_t k = genes_of(C, n, [&](uint32_t j) { return r[j]; }, g, through != 0);
+        if (g[kMaxGenesPerLabel] != 0xDEADBEEFu) return 3;   // wrote past the set
+        printf("%u", k);
+        for (unsigned i = 0; k != 0xFFFFFFFFu && i < k; ++i) printf(" %u", g[i]);
+        printf("\n");
+    }
+    return 0;
+}
+'''
+    (tmp_path / "t.cpp").write_text(host)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(tmp_path / "t"), str(tmp_path / "t.cpp")], check=True, capture_output=True)
+    NO = 0xFFFFFFFF
+    t2g = [0, 0, 1, 1, 2, 2, 3, 4, 5]
+    rng = np.random.default_rng(8)
+    cases = [(1, [])]
+    for k in range(1, 7):
+        lists = np.array(list(itertools.product(range(9), repeat=k)), dtype=np.int64).reshape(-1, k)
+        skip = rng.random(lists.shape) < 0.3
+        through = rng.integers(0, 2, len(lists))
+        for row, sk, th in zip(lists.tolist(), skip.tolist(), through.tolist()):
+            cases.append((th, [NO if s_ else t for t, s_ in zip(row, sk)]))
+    wide = [int(x) for x in 100 + rng.permutation(65)]
+    cases += [(0, wide), (0, wide[:64]), (0, wide[:64] + [NO, wide[3], wide[63]]), (0, wide[:64] + [NO, wide[64]])]
+    text = "".join(f"{th} {len(r)} " + " ".join(map(str, r)) + "\n" for th, r in cases)
+    out = subprocess.run([str(tmp_path / "t")], input=text, capture_output=True, text=True)
+    assert out.returncode == 0, (out.returncode, out.stderr)
+    got = out.stdout.splitlines()
+    assert len(got) == len(cases)
+    for (th, r), line in zip(cases, got):
+        want = sorted(set((t2g[t] if th else t) for t in r if t != NO))
+        exp = str(NO) if len(want) > 64 else " ".join(map(str, [len(want)] + want))
+        assert line == exp, (th, r, line, exp)
+    assert got[-4] == str(NO) and got[-1] == str(NO) and got[-3].startswith("64 ") and got[-2] == got[-3]
+
+
+def test_winner_take_all_walk_is_the_plain_rule_on_host(tmp_path):
+    """csrc/afq_pug_common.h, `molecules_of_sorted_triplets`: a component above --large-graph-thresh is resolved per UMI from its
+    sorted (UMI lo, UMI hi, gene, reads) triplets - the gene(s) with the most reads (pugutils.rs:916-982, 644-749).  The walk's own
+    source text on the host against a plain restatement: per UMI sum the reads per gene, keep the genes at the maximum.  A few
+    thousand random lists of up to 40 triplets over 6 genes - few UMIs, some equal in the low word and different in the high one,
+    small read counts so that ties are common - and one UMI whose 70 genes tie: a class of all 70 for the EM, and without an EM
+    no class (the molecule is dropped like any of more genes than the device carries).  No GPU."""
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    src = open(os.path.join(ROOT, "alevin-fry_amd", "csrc", "afq_pug_common.h")).read()
+
+    def grab(start, end):
+        a = src.index(start)
+        return src[a:src.index(end, a)]
+
+    host = r'''#include <cstdint>
+#include <cstdio>
+#include <algorithm>
+#include <tuple>
+#include <vector>
+#define __device__
+#define __forceinline__ inline
+constexpr uint32_t kMaxGenesPerLabel = 64, kErrPugLimit = 7;
+struct uint4 { uint32_t x, y, z, w; };
+struct PugCtx { uint32_t em, lab_cap; uint32_t* labw; uint32_t* labd; uint32_t* s_cnt; };
+static uint32_t atomicAdd(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v; return o; }
+// a molecule whose genes fit the device's array: printed as it comes; 0xFFFFFFFF: more genes than that, no class
+static void emit_molecule(const PugCtx&, const uint32_t* g, uint32_t ng) {
+    if (ng == 0xFFFFFFFFu) { printf("M wide\n"); return; }
+    printf("M");
+    for (uint32_t i = 0; i < ng; ++i) printf(" %u", g[i]);
+    printf("\n");
+}
+''' + grab("__device__ __forceinline__ bool reserve_class(", "template <typename Cand>\n__device__ __forceinline__ void emit_wide_class(") + \
+        grab("__device__ __forceinline__ void molecules_of_sorted_triplets(", "// The molecules of one component above --large-graph-thresh from its nt triplets") + r'''
+int main() {
+    unsigned em, nt;
+    while (scanf("%u %u", &em, &nt) == 2) {
+        std::vector<uint4> t(nt);
+        for (auto& q : t) if (scanf("%u %u %u %u", &q.x, &q.y, &q.z, &q.w) != 4) return 2;
+        std::sort(t.begin(), t.end(), [](const uint4& a, const uint4& b) { return std::tie(a.y, a.x, a.z, a.w) < std::tie(b.y, b.x, b.z, b.w); });
+        uint32_t cnt[4] = {0, 0, 0, 0}, lw[256], ld[64];
+        PugCtx C{em, 256, lw, ld, cnt};
+        printf("case\n");
+        molecules_of_sorted_triplets(C, t.data(), nt);
+        if (cnt[3]) return 3;
+        for (uint32_t d = 0; d < cnt[2]; ++d) {
+            printf("C");
+            for (uint32_t i = 0; i < ld[2 * d + 1]; ++i) printf(" %u", lw[ld[2 * d] + i]);
+            printf("\n");
+        }
+    }
+    return 0;
+}
+'''
+    (tmp_path / "t.cpp").write_text(host)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(tmp_path / "t"), str(tmp_path / "t.cpp")], check=True, capture_output=True)
+    rng = np.random.default_rng(9)
+    umis = [(5, 0), (5, 1), (9, 0), (9, 2), (0x0ABCDEF1, 5 << 4), (0x0ABCDEF1, (5 << 4) ^ 4)]   # (lo, hi)
+    cases = []
+    for it in range(4000):
+        nt = int(rng.integers(0, 41))
+        pool = [umis[i] for i in rng.choice(len(umis), size=int(rng.integers(1, len(umis) + 1)), replace=False)]
+        trips = [(*pool[int(rng.integers(0, len(pool)))], int(rng.integers(0, 6)), int(rng.integers(1, 4))) for _ in range(nt)]
+        cases.append((it & 1, trips))
+    tie70 = [(7, 3, 1000 + g, 2) for g in range(70)] + [(7, 3, 1000 + g, 1) for g in range(70)] + [(7, 4, 11, 1), (6, 3, 12, 5), (6, 3, 13, 5)]
+    order = rng.permutation(len(tie70))
+    for em in (0, 1):
+        cases.append((em, [tie70[i] for i in order]))
+    text = "".join(f"{em} {len(t)}\n" + "".join(f"{x} {y} {z} {w}\n" for x, y, z, w in t) for em, t in cases)
+    out = subprocess.run([str(tmp_path / "t")], input=text, capture_output=True, text=True)
+    assert out.returncode == 0, (out.returncode, out.stderr)
+    got = out.stdout.split("case\n")[1:]
+    assert len(got) == len(cases)
+    for (em, trips), g in zip(cases, got):
+        mol, cls = [], []
+        for lo, hi in sorted({(x, y) for x, y, _, _ in trips}, key=lambda u: (u[1], u[0])):
+            reads = {}
+            for x, y, z, w in trips:
+                if (x, y) == (lo, hi):
+                    reads[z] = reads.get(z, 0) + w
+            top = sorted(z for z, w in reads.items() if w == max(reads.values()))
+            if len(top) <= 64:
+                mol.append("M " + " ".join(map(str, top)))
+            elif em:
+                cls.append("C " + " ".join(map(str, top)))
+            else:
+                mol.append("M wide")
+        assert g.splitlines() == mol + cls, (em, trips, g)
+    assert got[-1].splitlines()[-1] == "C " + " ".join(str(1000 + g) for g in range(70)) and "C" not in got[-2]
 
 
 def test_atac_ref_runs_rebuild_the_column_on_host(tmp_path):
