@@ -15,11 +15,13 @@
 #include <cstring>
 #include <condition_variable>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/afquant.h"
+#include "afq_chunk_table.h"
 #include "afq_common.h"
 #include "afq_hooks.h"
 #include "afq_kernels.h"
@@ -178,6 +180,24 @@ struct RangeState {
     }
 };
 
+// afq_atac_dedup[_rad]'s device buffers, kept between calls (hipMalloc / hipFree of gigabytes is not free)
+struct AtacBufs {
+    DevBuf ref, start, flen, ptr, scr, oref, ostart, oflen, ocnt, on, optr, cref, cstart, cflen, ccnt, flag, cells, bm, cnt, bc, stat, walk, nwalk, status, tally, rstat, runctr;
+    std::vector<DevBuf*> all() {
+        return {&ref, &start, &flen, &ptr, &scr, &oref, &ostart, &oflen, &ocnt, &on, &optr, &cref, &cstart, &cflen, &ccnt, &flag, &cells, &bm, &cnt,
+                &bc, &stat, &walk, &nwalk, &status, &tally, &rstat, &runctr};
+    }
+};
+
+// afq_atac_sort_rad's
+struct AtacSortBufs {
+    DevBuf chunks, obs, rank, tkey, tval, rinfo, bbase, rbc, bin, key0, cstat, status, hist, cur, segs, ka, kb, andor, leaves, ids, on, lout, out, tally;
+    std::vector<DevBuf*> all() {
+        return {&chunks, &obs, &rank, &tkey, &tval, &rinfo, &bbase, &rbc, &bin, &key0, &cstat, &status, &hist, &cur, &segs, &ka, &kb, &andor,
+                &leaves, &ids, &on, &lout, &out, &tally};
+    }
+};
+
 }  // namespace
 
 struct afq_ctx {
@@ -193,8 +213,8 @@ struct afq_ctx {
     const uint8_t* d_bytes = nullptr;
     size_t n_bytes = 0;
     DevBuf d_chunk_off, d_hdr;
-    DevBuf atac[27];  // afq_atac_dedup[_rad]'s device buffers, kept between calls
-    DevBuf asort[24]; // afq_atac_sort_rad's
+    AtacBufs atac;
+    AtacSortBufs asort;
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
@@ -268,6 +288,19 @@ int fail(afq_ctx* c, int code, const std::string& msg) {
             return fail((c), e__ == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP,              \
                         std::string(#expr) + ": " + hipGetErrorString(e__));                      \
     } while (0)
+
+// The first error of a run of HIP calls; the calls behind it are skipped (`if (T.ok())`) or made and ignored.
+struct HipLatch {
+    hipError_t e = hipSuccess;
+    void operator()(hipError_t x) { if (e == hipSuccess) e = x; }
+    bool ok() const { return e == hipSuccess; }
+    int fail(afq_ctx* c, const char* who, const std::string& detail = "") const {
+        (void)hipGetLastError();   // (the runtime keeps the error until it is read)
+        return ::fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e) + detail);
+    }
+};
+
+void reset_kernel_times(afq_ctx* c) { for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; } }
 
 hipEvent_t get_event(afq_ctx* c) {
     if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
@@ -1524,7 +1557,7 @@ int begin_batch(afq_ctx* c, uint32_t n_cells, uint64_t first_cell_index) {
     c->n_divert = 0;
     for (uint64_t& x : c->n_em_inst) x = 0;
     c->stats.input_bytes = c->n_bytes;
-    for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
+    reset_kernel_times(c);
     c->h2d_piped = false;
     for (uint64_t& x : c->n_pipe) x = 0;
     // (the result arrays as large as the last batch's rows: a reserve that grows them has to wait for the row copies in flight)
@@ -1693,8 +1726,8 @@ void afq_destroy(afq_ctx* c) {
     if (c->h_kick) (void)hipHostFree(c->h_kick);
     DevBuf* bufs[] = {&c->d_t2g, &c->d_bytes_own, &c->d_chunk_off, &c->d_hdr, &c->d_wide, &c->d_kick};
     for (auto b : bufs) b->release();
-    for (auto& b : c->atac) b.release();
-    for (auto& b : c->asort) b.release();
+    for (DevBuf* b : c->atac.all()) b->release();
+    for (DevBuf* b : c->asort.all()) b->release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);
@@ -1714,6 +1747,35 @@ void afq_destroy(afq_ctx* c) {
     delete c;
 }
 
+// The checks of afq_chunk_table.h with the entry points' error texts (`noun`: what the caller's API calls a chunk).
+static int chunk_fault(afq_ctx* c, const char* noun, uint32_t i, ChunkFault f) {
+    static const char* const kWhat[] = {"", ": chunk offset out of range", ": chunk header/size out of range", ": chunk nbytes does not match its records"};
+    return fail(c, AFQ_ERR_BAD_INPUT, std::string(noun) + " " + std::to_string(i) + kWhat[f]);
+}
+static int check_chunk_offsets(afq_ctx* c, const uint64_t* chunk_off, uint32_t n, size_t n_bytes, const char* noun) {
+    const uint32_t bad = first_chunk_outside(chunk_off, n, n_bytes);
+    return bad < n ? chunk_fault(c, noun, bad, kChunkOffset) : 0;
+}
+
+// The `nbytes, nrec` headers of n chunks into hdr[2 * n], from host bytes or gathered off the device (k_gather_headers; `timed`:
+// under a K_GATHER bracket).  No byte is read and nothing is launched before every offset has passed stage A.
+static int fetch_chunk_headers(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n, bool on_device,
+                               uint32_t* hdr, const char* noun = "cell", bool timed = false) {
+    if (int rc = check_chunk_offsets(c, chunk_off, n, n_bytes, noun)) return rc;
+    for (uint32_t i = 0; i < n && !on_device; ++i) std::memcpy(hdr + 2ull * i, bytes + chunk_off[i], 8);
+    if (!on_device || !n) return 0;
+    HIP_TRY(c, c->d_chunk_off.ensure(8ull * n));
+    HIP_TRY(c, c->d_hdr.ensure(8ull * n));
+    HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n, hipMemcpyHostToDevice, c->stream));
+    std::optional<ScopedTimer> t;
+    if (timed) t.emplace(c, K_GATHER);
+    launch_gather_headers(c->stream, bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n, c->d_hdr.as<uint32_t>());
+    t.reset();
+    HIP_TRY(c, hipMemcpyAsync(hdr, c->d_hdr.p, 8ull * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 static int submit_host(afq_ctx* c, const ByteSource& src, size_t n_bytes, const uint64_t* chunk_off, const uint32_t* chunk_hdr,
                        uint32_t n_cells, uint64_t first_cell_index) {
     const uint8_t* bytes = src.bytes;
@@ -1723,14 +1785,9 @@ static int submit_host(afq_ctx* c, const ByteSource& src, size_t n_bytes, const 
     if (rc) return rc;
     c->chunk_off.assign(chunk_off, chunk_off + n_cells);
     c->hdr.assign(2ull * n_cells, 0);
-    for (uint32_t i = 0; i < n_cells; ++i) {
-        if (chunk_off[i] + 8 > n_bytes) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk offset out of range");
-        uint32_t h[2];
-        if (chunk_hdr) { h[0] = chunk_hdr[2 * i]; h[1] = chunk_hdr[2 * i + 1]; }
-        else std::memcpy(h, bytes + chunk_off[i], 8);
-        c->hdr[2 * i] = h[0];
-        c->hdr[2 * i + 1] = h[1];
-    }
+    rc = chunk_hdr ? check_chunk_offsets(c, chunk_off, n_cells, n_bytes, "cell") : fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_cells, false, c->hdr.data());
+    if (rc) return rc;
+    if (chunk_hdr) std::copy(chunk_hdr, chunk_hdr + 2ull * n_cells, c->hdr.begin());
     // A RAD file's prelude has an arbitrary length, so chunk offsets inside the caller's buffer are usually not
     // dword-aligned although every chunk size is a multiple of 4.  The bytes are copied anyway: land them shifted so
     // that the chunks start on dword boundaries on the device (that is what the walk-free decode and the PUG path need).
@@ -1824,17 +1881,8 @@ int afq_submit_device(afq_ctx* c, const void* d_bytes, size_t n_bytes, const uin
     c->hdr.assign(2ull * n_cells, 0);
     c->d_bytes = (const uint8_t*)d_bytes;
     c->n_bytes = n_bytes;
-    if (n_cells) {
-        HIP_TRY(c, c->d_chunk_off.ensure(8ull * n_cells));
-        HIP_TRY(c, c->d_hdr.ensure(8ull * n_cells));
-        HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n_cells, hipMemcpyHostToDevice, c->stream));
-        {
-            ScopedTimer t(c, K_GATHER);
-            launch_gather_headers(c->stream, c->d_bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n_cells, c->d_hdr.as<uint32_t>());
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->hdr.data(), c->d_hdr.p, 8ull * n_cells, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    rc = fetch_chunk_headers(c, c->d_bytes, n_bytes, chunk_off, n_cells, true, c->hdr.data(), "cell", true);
+    if (rc) return rc;
     hc.lap("submit: chunk headers");
     int rc2 = begin_batch(c, n_cells, first_cell_index);
     hc.lap("submit: plan ranges");
@@ -2017,85 +2065,91 @@ struct PinnedPool {
     }
 };
 PinnedPool* pinned_pool() { static PinnedPool* P = new PinnedPool(); return P; }
+// What an ATAC call hands out: arrays from pinned_pool() or malloc, given back (afq_free takes either) unless release()d into the
+// caller's out-parameters on success.  Copies and threads may still be writing into a block when an exit is taken, so before one
+// of these is destroyed or free_all()ed after work was started on its blocks: the filler threads are joined and both streams are
+// synchronised (atac_dedup_piped does that ahead of its first exit), and the pipeline's `runs` and `pin` go back to the pool
+// before a redo falls through to the plain route, which draws on the same pool.
+struct HostOuts {
+    void* p[6] = {};
+    int n = 0;
+    void* keep(void* q) { if (q) p[n++] = q; return q; }
+    void* pinned(size_t bytes) { return keep(pinned_pool()->get(bytes)); }
+    void* mallocd(size_t bytes) { return keep(std::malloc(bytes)); }
+    void free_all() { while (n) afq_free(p[--n]); }
+    void release() { n = 0; }
+    ~HostOuts() { free_all(); }
+};
 }  // namespace
 
-// Shared back half of the two ATAC entry points: de-duplicate the fragments sitting in d_ref/d_start/d_flen (cell i at
-// d_ptr[i], cell_cnt[i] of them when d_cnt is given, else up to d_ptr[i+1]) and hand the distinct ones out as malloc'd arrays.
+// Shared back half of the two ATAC entry points: de-duplicate the fragments sitting in A.ref/A.start/A.flen (cell i at
+// A.ptr[i], cell_cnt[i] of them when d_cnt is given, else up to A.ptr[i+1]) and hand the distinct ones out as malloc'd arrays.
 static int atac_dedup_device(afq_ctx* c, uint64_t n, uint32_t n_cells, const uint32_t* d_cnt, uint64_t** out_cell_ptr, uint32_t** out_ref,
                              uint32_t** out_start, uint16_t** out_frag_len, uint16_t** out_count, HostClock& hc, unsigned long long* tally_out = nullptr) {
-    DevBuf &d_ref = c->atac[0], &d_start = c->atac[1], &d_flen = c->atac[2], &d_ptr = c->atac[3], &d_scr = c->atac[4],
-           &d_oref = c->atac[5], &d_ostart = c->atac[6], &d_oflen = c->atac[7], &d_ocnt = c->atac[8], &d_on = c->atac[9],
-           &d_optr = c->atac[10], &d_cref = c->atac[11], &d_cstart = c->atac[12], &d_cflen = c->atac[13], &d_ccnt = c->atac[14],
-           &d_flag = c->atac[15];
+    auto& A = c->atac;
     hipStream_t s = c->stream;
     const uint64_t n1 = std::max<uint64_t>(n, 1);
-    hipError_t e = hipSuccess;
-    auto T = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    T(d_scr.ensure(16 * n1)); T(d_oref.ensure(4 * n1)); T(d_ostart.ensure(4 * n1)); T(d_oflen.ensure(2 * n1));
-    T(d_ocnt.ensure(2 * n1)); T(d_on.ensure(4ull * std::max<uint32_t>(n_cells, 1))); T(d_optr.ensure(8ull * (n_cells + 1)));
-    T(d_flag.ensure(4));
-    if (e == hipSuccess) T(hipMemsetAsync(d_flag.p, 0, 4, s));
+    HipLatch T;
+    T(A.scr.ensure(16 * n1)); T(A.oref.ensure(4 * n1)); T(A.ostart.ensure(4 * n1)); T(A.oflen.ensure(2 * n1));
+    T(A.ocnt.ensure(2 * n1)); T(A.on.ensure(4ull * std::max<uint32_t>(n_cells, 1))); T(A.optr.ensure(8ull * (n_cells + 1)));
+    T(A.flag.ensure(4));
+    if (T.ok()) T(hipMemsetAsync(A.flag.p, 0, 4, s));
     std::vector<uint32_t> on(n_cells);
     uint32_t wide = 0;
-    if (e == hipSuccess) {
+    if (T.ok()) {
         ScopedTimer t(c, K_ATAC, s);
-        launch_atac_dedup64(s, n_cells, d_ref.as<uint32_t>(), d_start.as<uint32_t>(), d_flen.as<uint16_t>(), d_ptr.as<uint64_t>(),
-                            d_scr.p, d_oref.as<uint32_t>(), d_ostart.as<uint32_t>(), d_oflen.as<uint16_t>(),
-                            d_ocnt.as<uint16_t>(), d_on.as<uint32_t>(), d_flag.as<uint32_t>(), d_cnt);
+        launch_atac_dedup64(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
+                            A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
+                            A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), A.flag.as<uint32_t>(), d_cnt);
         T(hipGetLastError());
     }
-    if (e == hipSuccess) {
-        T(hipMemcpyAsync(&wide, d_flag.p, 4, hipMemcpyDeviceToHost, s));
+    if (T.ok()) {
+        T(hipMemcpyAsync(&wide, A.flag.p, 4, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
     }
-    if (e == hipSuccess && wide) {  // a reference id >= 65536: the 16-byte-record kernel
+    if (T.ok() && wide) {  // a reference id >= 65536: the 16-byte-record kernel
         ScopedTimer t(c, K_ATAC, s);
-        launch_atac_dedup(s, n_cells, d_ref.as<uint32_t>(), d_start.as<uint32_t>(), d_flen.as<uint16_t>(), d_ptr.as<uint64_t>(),
-                          d_scr.p, d_oref.as<uint32_t>(), d_ostart.as<uint32_t>(), d_oflen.as<uint16_t>(),
-                          d_ocnt.as<uint16_t>(), d_on.as<uint32_t>(), d_cnt);
+        launch_atac_dedup(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
+                          A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
+                          A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), d_cnt);
         T(hipGetLastError());
     }
-    if (e == hipSuccess && n_cells) T(hipMemcpyAsync(on.data(), d_on.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
-    if (e == hipSuccess) T(hipStreamSynchronize(s));
+    if (T.ok() && n_cells) T(hipMemcpyAsync(on.data(), A.on.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
+    if (T.ok()) T(hipStreamSynchronize(s));
     hc.lap("atac: kernel");
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_dedup: ") + hipGetErrorString(e));
-    uint64_t* optr = (uint64_t*)std::malloc(8ull * (n_cells + 1));
+    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
+    HostOuts H;
+    uint64_t* optr = (uint64_t*)H.mallocd(8ull * (n_cells + 1));
     if (!optr) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup: host allocation failed");
     optr[0] = 0;
     for (uint32_t i = 0; i < n_cells; ++i) optr[i + 1] = optr[i] + on[i];
     const uint64_t tot = optr[n_cells], tot1 = std::max<uint64_t>(tot, 1);
-    uint32_t* oref = (uint32_t*)pinned_pool()->get(4 * tot1);
-    uint32_t* ostart = (uint32_t*)pinned_pool()->get(4 * tot1);
-    uint16_t* oflen = (uint16_t*)pinned_pool()->get(2 * tot1);
-    uint16_t* ocnt = (uint16_t*)pinned_pool()->get(2 * tot1);
-    if (!oref || !ostart || !oflen || !ocnt) {
-        std::free(optr); afq_free(oref); afq_free(ostart); afq_free(oflen); afq_free(ocnt);
-        return fail(c, AFQ_ERR_OOM, "afq_atac_dedup: host allocation failed");
-    }
+    uint32_t* oref = (uint32_t*)H.pinned(4 * tot1);
+    uint32_t* ostart = (uint32_t*)H.pinned(4 * tot1);
+    uint16_t* oflen = (uint16_t*)H.pinned(2 * tot1);
+    uint16_t* ocnt = (uint16_t*)H.pinned(2 * tot1);
+    if (!oref || !ostart || !oflen || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup: host allocation failed");
     // dense runs on the device, then straight into the caller's arrays
-    T(d_cref.ensure(4 * tot1)); T(d_cstart.ensure(4 * tot1)); T(d_cflen.ensure(2 * tot1)); T(d_ccnt.ensure(2 * tot1));
-    if (e == hipSuccess) T(hipMemcpyAsync(d_optr.p, optr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    DevBuf& d_tally = c->atac[24];
-    T(d_tally.ensure(16));
-    if (e == hipSuccess) T(hipMemsetAsync(d_tally.p, 0, 16, s));
-    if (e == hipSuccess && tot) {
-        launch_atac_compact(s, n_cells, d_ptr.as<uint64_t>(), d_optr.as<uint64_t>(), d_oref.as<uint32_t>(), d_ostart.as<uint32_t>(),
-                            d_oflen.as<uint16_t>(), d_ocnt.as<uint16_t>(), d_cref.as<uint32_t>(), d_cstart.as<uint32_t>(),
-                            d_cflen.as<uint16_t>(), d_ccnt.as<uint16_t>(), tally_out ? d_tally.as<unsigned long long>() : nullptr);
+    T(A.cref.ensure(4 * tot1)); T(A.cstart.ensure(4 * tot1)); T(A.cflen.ensure(2 * tot1)); T(A.ccnt.ensure(2 * tot1));
+    if (T.ok()) T(hipMemcpyAsync(A.optr.p, optr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
+    T(A.tally.ensure(16));
+    if (T.ok()) T(hipMemsetAsync(A.tally.p, 0, 16, s));
+    if (T.ok() && tot) {
+        launch_atac_compact(s, n_cells, A.ptr.as<uint64_t>(), A.optr.as<uint64_t>(), A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(),
+                            A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.cref.as<uint32_t>(), A.cstart.as<uint32_t>(),
+                            A.cflen.as<uint16_t>(), A.ccnt.as<uint16_t>(), tally_out ? A.tally.as<unsigned long long>() : nullptr);
         T(hipGetLastError());
-        T(hipMemcpyAsync(oref, d_cref.p, 4 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ostart, d_cstart.p, 4 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(oflen, d_cflen.p, 2 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ocnt, d_ccnt.p, 2 * tot, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(oref, A.cref.p, 4 * tot, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(ostart, A.cstart.p, 4 * tot, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(oflen, A.cflen.p, 2 * tot, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(ocnt, A.ccnt.p, 2 * tot, hipMemcpyDeviceToHost, s));
     }
-    if (e == hipSuccess && tally_out) T(hipMemcpyAsync(tally_out, d_tally.p, 16, hipMemcpyDeviceToHost, s));
-    if (e == hipSuccess) T(hipStreamSynchronize(s));
+    if (T.ok() && tally_out) T(hipMemcpyAsync(tally_out, A.tally.p, 16, hipMemcpyDeviceToHost, s));
+    if (T.ok()) T(hipStreamSynchronize(s));
     hc.lap("atac: compact + D2H");
     harvest_timers(c);
-    if (e != hipSuccess) {
-        std::free(optr); afq_free(oref); afq_free(ostart); afq_free(oflen); afq_free(ocnt);
-        return fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_dedup: ") + hipGetErrorString(e));
-    }
+    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
+    H.release();
     *out_cell_ptr = optr; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_count = ocnt;
     return 0;
 }
@@ -2114,23 +2168,210 @@ int afq_atac_dedup(afq_ctx* c, const uint32_t* ref, const uint32_t* start, const
         if (cell_ptr[i + 1] < cell_ptr[i] || cell_ptr[i + 1] - cell_ptr[i] > 0x7FFFFFFFull)
             return fail(c, AFQ_ERR_INVALID_ARG, "cell_ptr must be non-decreasing");
     HostClock hc;
-    // device buffers live in the context and are reused by the next call (hipMalloc/hipFree of GBs is not free)
-    DevBuf &d_ref = c->atac[0], &d_start = c->atac[1], &d_flen = c->atac[2], &d_ptr = c->atac[3];
+    auto& A = c->atac;
     hipStream_t s = c->stream;
     const uint64_t n1 = std::max<uint64_t>(n, 1);
-    hipError_t e = hipSuccess;
-    auto T = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    T(d_ref.ensure(4 * n1)); T(d_start.ensure(4 * n1)); T(d_flen.ensure(2 * n1)); T(d_ptr.ensure(8ull * (n_cells + 1)));
-    if (e == hipSuccess && n) {   // (the pinned staging path of afq_submit was measured here too: no faster for these arrays)
-        T(hipMemcpyAsync(d_ref.p, ref, 4 * n, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(d_start.p, start, 4 * n, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(d_flen.p, frag_len, 2 * n, hipMemcpyHostToDevice, s));
+    HipLatch T;
+    T(A.ref.ensure(4 * n1)); T(A.start.ensure(4 * n1)); T(A.flen.ensure(2 * n1)); T(A.ptr.ensure(8ull * (n_cells + 1)));
+    if (T.ok() && n) {   // (the pinned staging path of afq_submit was measured here too: no faster for these arrays)
+        T(hipMemcpyAsync(A.ref.p, ref, 4 * n, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(A.start.p, start, 4 * n, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(A.flen.p, frag_len, 2 * n, hipMemcpyHostToDevice, s));
     }
-    if (e == hipSuccess) T(hipMemcpyAsync(d_ptr.p, cell_ptr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
+    if (T.ok()) T(hipMemcpyAsync(A.ptr.p, cell_ptr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
     if (hc.on) { T(hipStreamSynchronize(s)); hc.lap("atac: alloc + H2D"); }
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_dedup: ") + hipGetErrorString(e));
-    for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
+    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
+    reset_kernel_times(c);
     return atac_dedup_device(c, n, n_cells, nullptr, out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc);
+}
+
+namespace {
+// What the two routes of afq_atac_dedup_rad (the eight-range pipeline and the plain one) work on.
+struct AtacRadJob {
+    const uint8_t* d_bytes;
+    size_t n_bytes;
+    uint32_t n_cells, bc_bytes;
+    uint64_t n_rec = 0;
+    std::vector<uint64_t> cap_ptr;   // capacity offsets of the cells' fragments = prefix of nrec
+    DevStatus st{};
+    std::vector<uint32_t> stat;      // per cell: multi-mapped, not a mapped pair
+    unsigned long long tally[2] = {0, 0};
+    uint64_t* obc = nullptr;         // the cells' barcodes (the caller's; owned by afq_atac_dedup_rad until it returns 0)
+    AtacParseArgs parse_args(AtacBufs& A, uint32_t c0, uint32_t c1, uint32_t* nwalk, DevStatus* dst) const {
+        return AtacParseArgs{d_bytes, A.cells.as<AtacCell>() + c0, c1 - c0, bc_bytes, A.bm.as<uint64_t>(), A.ref.as<uint32_t>(), A.start.as<uint32_t>(),
+                             A.flen.as<uint16_t>(), A.cnt.as<uint32_t>() + c0, A.bc.as<uint64_t>() + c0, A.stat.as<uint32_t>() + 2ull * c0,
+                             A.walk.as<uint32_t>() + c0, nwalk, dst, (uint64_t)n_bytes};
+    }
+};
+constexpr int kPipedDone = 0, kPipedRedo = 1;   // (or an AFQ_ERR_ code, all negative)
+}  // namespace
+
+// Big batches go through in eight ranges of cells: the distinct fragments of range r cross PCIe on a second stream while the
+// later ranges are still parsed and sorted.  The rows are the long pole - 12 bytes a row, 1.8 GB for 2*10^8 records, 34 ms at
+// the 52 GB/s the link gives (the e2e leg), against 20 ms for all the kernels - so (round 5) the ref column stays on the device
+// (8 bytes a row cross, 23 ms; the host writes the column from a list of runs, below), and what matters then is how soon the
+// FIRST rows can leave and how few are left when the last kernel ends: the ranges GROW (4, 8, 12, 14, 15, 16, 16, 15 % of the
+// records; four equal ranges kept the link idle for the first quarter of the kernels), the opposite of the cr-like taper,
+// whose rows are short.  Measured and not kept: the parse of range r+1 on a stream of its own next to the sort of range r
+// (the sort's workgroups wait for CUs behind the parse's: 12.7 -> 18.3 ms of sort, 28.6 -> 30.9 ms a step).
+// Returns kPipedDone (the outputs, J.obc, J.stat, J.tally and J.st.n_fallback are filled), kPipedRedo (a reference id >= 65536:
+// nothing is handed out or left allocated, the plain route runs the 16-byte-record kernel) or an error code.
+static int atac_dedup_piped(afq_ctx* c, AtacRadJob& J, uint64_t** out_cell_ptr, uint32_t** out_ref, uint32_t** out_start, uint16_t** out_frag_len,
+                            uint16_t** out_count, HostClock& hc) {
+    auto& A = c->atac;
+    hipStream_t s = c->stream;
+    const uint32_t n_cells = J.n_cells;
+    const uint64_t n1 = std::max<uint64_t>(J.n_rec, 1), nc1 = std::max<uint32_t>(n_cells, 1);
+    constexpr uint32_t kR = 8;
+    static const double kGrow[kR] = {0.04, 0.12, 0.24, 0.38, 0.53, 0.69, 0.85, 1.0};
+    uint32_t cut[kR + 1];
+    cut[0] = 0;
+    for (uint32_t r = 1; r < kR; ++r) {
+        const uint64_t target = (uint64_t)((double)J.n_rec * kGrow[r - 1]);
+        cut[r] = (uint32_t)(std::lower_bound(J.cap_ptr.begin(), J.cap_ptr.begin() + n_cells, target) - J.cap_ptr.begin());
+        if (cut[r] < cut[r - 1]) cut[r] = cut[r - 1];
+    }
+    cut[kR] = n_cells;
+    HipLatch T;
+    T(A.scr.ensure(16 * n1)); T(A.oref.ensure(4 * n1)); T(A.ostart.ensure(4 * n1)); T(A.oflen.ensure(2 * n1)); T(A.ocnt.ensure(2 * n1));
+    T(A.on.ensure(4ull * nc1)); T(A.optr.ensure(8ull * (n_cells + 1))); T(A.flag.ensure(4)); T(A.tally.ensure(16));
+    T(A.cref.ensure(4 * n1)); T(A.cstart.ensure(4 * n1)); T(A.cflen.ensure(2 * n1)); T(A.ccnt.ensure(2 * n1));   // (sized for "nothing is a duplicate")
+    T(A.rstat.ensure(kR * (sizeof(DevStatus) + 16))); T(A.runctr.ensure(4));
+    // The ref column does not cross PCIe: a cell's rows are sorted by ref first, so the column is a few runs per cell - the
+    // compaction kernel lists them (first row, length, ref: 16 bytes a run, written straight into pinned host memory) and
+    // host threads write the column from the list while the other three columns (8 of the 12 bytes of a row) are on the link.
+    // A list that overflows (more than 64 runs per cell on average: thousands of contigs) sends the column itself, as before.
+    const long cap_hook = test_hook_long("ATAC_RUN_CAP", -1);   // (tests: force the overflow)
+    // (at most 2^22 runs = 64 MiB of pinned memory whatever the number of barcodes - an unfiltered sample has a million of them; a
+    //  list that does not fit, or that the host has no pinned memory for, is the overflow case: the column crosses as a copy)
+    uint32_t run_cap = cap_hook >= 0 ? (uint32_t)cap_hook : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1u << 20, 64ull * n_cells), 1u << 22);
+    HostOuts out, tmp;   // the caller's columns; the run list and the pinned block, this function's own
+    uint4* runs = (uint4*)tmp.pinned(16ull * std::max<uint32_t>(run_cap, 1));
+    if (!runs) { run_cap = 0; runs = (uint4*)tmp.pinned(16); }
+    uint32_t* oref = (uint32_t*)out.pinned(4 * n1);
+    uint32_t* ostart = (uint32_t*)out.pinned(4 * n1);
+    uint16_t* oflen = (uint16_t*)out.pinned(2 * n1);
+    uint16_t* ocnt = (uint16_t*)out.pinned(2 * n1);
+    uint64_t* optr = (uint64_t*)out.mallocd(8ull * (n_cells + 1));
+    // (the per-range counts and flags land in PINNED memory: an async copy into pageable memory holds the host until the
+    // stream gets there, and the ranges would be enqueued one at a time)
+    uint8_t* pin = (uint8_t*)tmp.pinned(4ull * nc1 + kR * (sizeof(DevStatus) + 16));
+    if (!oref || !ostart || !oflen || !ocnt || !optr || !runs || !pin) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed");
+    hipStream_t s2 = c->rs[0].stream;
+    DevStatus* d_rst = reinterpret_cast<DevStatus*>(A.rstat.p);
+    uint32_t* d_rnw = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.rstat.p) + kR * sizeof(DevStatus));
+    uint32_t* on = reinterpret_cast<uint32_t*>(pin);
+    DevStatus* rst = reinterpret_cast<DevStatus*>(pin + 4ull * nc1);
+    uint32_t* wide = reinterpret_cast<uint32_t*>(pin + 4ull * nc1 + kR * sizeof(DevStatus));
+    volatile uint32_t* snap = wide + kR;   // the run counter as it stood after each range's compaction (the block has four words per range)
+    uint32_t* pin_dev = nullptr;   // the same block as the device sees it
+    T(hipHostGetDevicePointer(reinterpret_cast<void**>(&pin_dev), pin, 0));
+    uint4* runs_dev = nullptr;
+    T(hipHostGetDevicePointer(reinterpret_cast<void**>(&runs_dev), runs, 0));
+    hipEvent_t ev[2 * kR], *const ev2 = ev + kR;   // a range's kernels are done; its run list is complete
+    for (auto& x : ev) x = get_event(c);
+    T(hipMemsetAsync(A.runctr.p, 0, 4, s));
+    // the threads that write the ref column: thread 0 waits for a range's list (the event after its compaction), all fill
+    std::atomic<int> recorded{0}, listed{0}, stop{0};
+    const unsigned nfill = stage_threads();
+    std::vector<std::thread> fillers;
+    if (T.ok()) {
+        for (unsigned t = 0; t < nfill; ++t)
+            fillers.emplace_back([&, t]() {
+                if (t == 0) (void)hipSetDevice(c->device);
+                uint32_t lo = 0;
+                for (uint32_t r = 0; r < kR; ++r) {
+                    if (t == 0) {
+                        while (recorded.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
+                        if (hipEventSynchronize(ev2[r]) != hipSuccess) { (void)hipGetLastError(); stop.store(1); return; }
+                        listed.store((int)r + 1, std::memory_order_release);
+                    } else {
+                        while (listed.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
+                    }
+                    const uint32_t hi = snap[r];
+                    if (hi > run_cap) return;   // this range's column and every later one come as copies
+                    for (uint32_t i = lo + t; i < hi; i += nfill) {
+                        const uint4 q = runs[i];
+                        std::fill_n(oref + (((uint64_t)q.y << 32) | q.x), (size_t)q.z, q.w);
+                    }
+                    lo = hi;
+                }
+            });
+    }
+    T(hipMemsetAsync(A.flag.p, 0, 4, s));
+    T(hipMemsetAsync(A.tally.p, 0, 16, s));
+    T(hipMemsetAsync(A.rstat.p, 0, kR * (sizeof(DevStatus) + 16), s));
+    for (uint32_t r = 0; r < kR && T.ok(); ++r) {
+        const uint32_t c0 = cut[r], nr = cut[r + 1] - c0;
+        { ScopedTimer t(c, K_ATAC_PARSE, s); launch_atac_parse(s, J.parse_args(A, c0, cut[r + 1], d_rnw + r, d_rst + r)); }
+        { ScopedTimer t(c, K_ATAC, s);
+          launch_atac_dedup64(s, nr, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>() + c0, A.scr.p,
+                              A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.on.as<uint32_t>() + c0,
+                              A.flag.as<uint32_t>(), A.cnt.as<uint32_t>() + c0); }
+        T(hipGetLastError());
+        // (the range's counts, flag and status go to the pinned block by a kernel, not as copies: see k_copy_words3)
+        launch_copy_words3(s, A.on.as<uint32_t>() + c0, nr, pin_dev + c0, A.flag.as<uint32_t>(), 1, pin_dev + (wide - on) + r,
+                           reinterpret_cast<const uint32_t*>(d_rst + r), (uint32_t)(sizeof(DevStatus) / 4), pin_dev + (reinterpret_cast<uint32_t*>(rst + r) - on));
+        T(hipGetLastError());
+        T(hipEventRecord(ev[r], s));
+    }
+    optr[0] = 0;
+    bool redo = false;
+    int bad_rc = 0;
+    uint64_t n_fallback = 0;
+    for (uint32_t r = 0; r < kR && T.ok() && !redo && !bad_rc; ++r) {
+        const uint32_t c0 = cut[r], c1 = cut[r + 1];
+        T(hipEventSynchronize(ev[r]));
+        if (!T.ok()) break;
+        if (wide[r]) { redo = true; break; }
+        if (rst[r].err_code) { bad_rc = fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(c0 + rst[r].err_cell) + ": chunk nbytes does not match its records"); break; }
+        n_fallback += rst[r].n_fallback;
+        for (uint32_t i = c0; i < c1; ++i) optr[i + 1] = optr[i] + on[i];
+        const uint64_t o0 = optr[c0], tot_r = optr[c1] - o0;
+        T(hipMemcpyAsync(A.optr.as<uint64_t>() + c0, optr + c0, 8ull * (c1 - c0 + 1), hipMemcpyHostToDevice, s2));
+        if (tot_r) {
+            launch_atac_compact(s2, c1 - c0, A.ptr.as<uint64_t>() + c0, A.optr.as<uint64_t>() + c0, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(),
+                                A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.cref.as<uint32_t>(), A.cstart.as<uint32_t>(),
+                                A.cflen.as<uint16_t>(), A.ccnt.as<uint16_t>(), A.tally.as<unsigned long long>(), runs_dev, A.runctr.as<uint32_t>(), run_cap);
+            T(hipGetLastError());
+        }
+        launch_copy_words3(s2, A.runctr.as<uint32_t>(), 1, pin_dev + (const_cast<uint32_t*>(snap) - on) + r, nullptr, 0, nullptr, nullptr, 0, nullptr);
+        T(hipGetLastError());
+        T(hipEventRecord(ev2[r], s2));
+        if (T.ok()) recorded.store((int)r + 1, std::memory_order_release);
+        if (tot_r) {
+            T(hipMemcpyAsync(ostart + o0, A.cstart.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
+            T(hipMemcpyAsync(oflen + o0, A.cflen.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
+            T(hipMemcpyAsync(ocnt + o0, A.ccnt.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
+        }
+    }
+    const bool done = T.ok() && !redo && !bad_rc;
+    if (!done) stop.store(1);
+    for (auto& th : fillers) th.join();
+    if (done) {
+        T(hipEventSynchronize(ev2[kR - 1]));   // (every range's count is on the host; the fillers stop at the first list that overflowed)
+        for (uint32_t r = 0; r < kR && T.ok(); ++r)
+            if (snap[r] > run_cap) {
+                const uint64_t o0 = optr[cut[r]], tot_r = optr[cut[r + 1]] - o0;
+                if (tot_r) T(hipMemcpyAsync(oref + o0, A.cref.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
+            }
+        T(hipMemcpyAsync(J.tally, A.tally.p, 16, hipMemcpyDeviceToHost, s2));
+        if (n_cells) T(hipMemcpyAsync(J.stat.data(), A.stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
+        if (n_cells) T(hipMemcpyAsync(J.obc, A.bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamSynchronize(s2);
+    for (auto x : ev) c->event_pool.push_back(x);
+    tmp.free_all();
+    harvest_timers(c);
+    hc.lap("atac: ranges (parse, sort, compact, D2H)");
+    if (bad_rc) return bad_rc;
+    if (!T.ok()) return T.fail(c, "afq_atac_dedup_rad");
+    if (redo) return kPipedRedo;
+    J.st.n_fallback += n_fallback;
+    out.release();
+    *out_cell_ptr = optr; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_count = ocnt;
+    return kPipedDone;
 }
 
 int afq_atac_dedup_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_cells, uint32_t bc_bytes,
@@ -2144,258 +2385,80 @@ int afq_atac_dedup_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const u
     HIP_TRY(c, hipSetDevice(c->device));
     HostClock hc;
     hipStream_t s = c->stream;
-    // chunk headers (from the host copy, or gathered off the device), capacity offsets = prefix of nrec
+    // ---- validate: chunk headers (from the host copy, or gathered off the device), capacity offsets = prefix of nrec
     std::vector<uint32_t> hdr(2ull * n_cells);
-    if (!bytes_on_device) {
-        for (uint32_t i = 0; i < n_cells; ++i) {
-            if (chunk_off[i] + 8 > n_bytes) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk offset out of range");
-            std::memcpy(&hdr[2 * i], bytes + chunk_off[i], 8);
-        }
-    } else if (n_cells) {
-        HIP_TRY(c, c->d_chunk_off.ensure(8ull * n_cells));
-        HIP_TRY(c, c->d_hdr.ensure(8ull * n_cells));
-        HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n_cells, hipMemcpyHostToDevice, s));
-        launch_gather_headers(s, bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n_cells, c->d_hdr.as<uint32_t>());
-        HIP_TRY(c, hipMemcpyAsync(hdr.data(), c->d_hdr.p, 8ull * n_cells, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_cells, bytes_on_device != 0, hdr.data())) return rc;
+    AtacRadJob J{bytes, n_bytes, n_cells, bc_bytes};
     std::vector<AtacCell> cells(n_cells);
-    std::vector<uint64_t> cap_ptr(n_cells + 1, 0);
-    uint64_t bm_words = 0, n_rec = 0;
+    J.cap_ptr.assign((size_t)n_cells + 1, 0);
+    uint64_t bm_words = 0;
     for (uint32_t i = 0; i < n_cells; ++i) {
         const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (chunk_off[i] + 8 > n_bytes || nb < 8 || chunk_off[i] + nb > n_bytes) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk header/size out of range");
-        if ((uint64_t)nr * (4 + bc_bytes) + 8 > nb) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(i) + ": chunk nbytes does not match its records");
-        cells[i] = AtacCell{chunk_off[i], n_rec, bm_words, nb, nr};
-        cap_ptr[i] = n_rec;
-        n_rec += nr;
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "cell", i, f);
+        cells[i] = AtacCell{chunk_off[i], J.n_rec, bm_words, nb, nr};
+        J.cap_ptr[i] = J.n_rec;
+        J.n_rec += nr;
         bm_words += 4ull * (((uint64_t)nb + 3 + 255) / 256);   // four ballots per group of 256 positions (counted from the dword boundary below the chunk)
     }
-    cap_ptr[n_cells] = n_rec;
-    DevBuf &d_ref = c->atac[0], &d_start = c->atac[1], &d_flen = c->atac[2], &d_ptr = c->atac[3];
-    DevBuf &d_cells = c->atac[16], &d_bm = c->atac[17], &d_cnt = c->atac[18], &d_bc = c->atac[19], &d_stat = c->atac[20], &d_walk = c->atac[21],
-           &d_nwalk = c->atac[22], &d_status = c->atac[23];
-    const uint64_t n1 = std::max<uint64_t>(n_rec, 1), nc1 = std::max<uint32_t>(n_cells, 1);
-    HIP_TRY(c, d_ref.ensure(4 * n1)); HIP_TRY(c, d_start.ensure(4 * n1)); HIP_TRY(c, d_flen.ensure(2 * n1)); HIP_TRY(c, d_ptr.ensure(8ull * (n_cells + 1)));
-    HIP_TRY(c, d_cells.ensure(sizeof(AtacCell) * nc1)); HIP_TRY(c, d_bm.ensure(8 * std::max<uint64_t>(bm_words, 1))); HIP_TRY(c, d_cnt.ensure(4ull * nc1));
-    HIP_TRY(c, d_bc.ensure(8ull * nc1)); HIP_TRY(c, d_stat.ensure(8ull * nc1)); HIP_TRY(c, d_walk.ensure(4ull * nc1)); HIP_TRY(c, d_nwalk.ensure(4));
-    HIP_TRY(c, d_status.ensure(sizeof(DevStatus)));
-    const uint8_t* d_bytes = bytes;
+    J.cap_ptr[n_cells] = J.n_rec;
+    // ---- upload
+    auto& A = c->atac;
+    const uint64_t n1 = std::max<uint64_t>(J.n_rec, 1), nc1 = std::max<uint32_t>(n_cells, 1);
+    HIP_TRY(c, A.ref.ensure(4 * n1)); HIP_TRY(c, A.start.ensure(4 * n1)); HIP_TRY(c, A.flen.ensure(2 * n1)); HIP_TRY(c, A.ptr.ensure(8ull * (n_cells + 1)));
+    HIP_TRY(c, A.cells.ensure(sizeof(AtacCell) * nc1)); HIP_TRY(c, A.bm.ensure(8 * std::max<uint64_t>(bm_words, 1))); HIP_TRY(c, A.cnt.ensure(4ull * nc1));
+    HIP_TRY(c, A.bc.ensure(8ull * nc1)); HIP_TRY(c, A.stat.ensure(8ull * nc1)); HIP_TRY(c, A.walk.ensure(4ull * nc1)); HIP_TRY(c, A.nwalk.ensure(4));
+    HIP_TRY(c, A.status.ensure(sizeof(DevStatus)));
     if (!bytes_on_device) {
         HIP_TRY(c, c->d_bytes_own.ensure(n_bytes + 16));
         if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
+        J.d_bytes = c->d_bytes_own.as<uint8_t>();
     }
-    if (n_cells) HIP_TRY(c, hipMemcpyAsync(d_cells.p, cells.data(), sizeof(AtacCell) * n_cells, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_ptr.p, cap_ptr.data(), 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(d_nwalk.p, 0, 4, s));
-    HIP_TRY(c, hipMemsetAsync(d_status.p, 0, sizeof(DevStatus), s));
+    if (n_cells) HIP_TRY(c, hipMemcpyAsync(A.cells.p, cells.data(), sizeof(AtacCell) * n_cells, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(A.ptr.p, J.cap_ptr.data(), 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(A.nwalk.p, 0, 4, s));
+    HIP_TRY(c, hipMemsetAsync(A.status.p, 0, sizeof(DevStatus), s));
     if (hc.on) { HIP_TRY(c, hipStreamSynchronize(s)); hc.lap("atac: alloc + H2D"); }
-    for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
-    DevStatus st{};
-    std::vector<uint32_t> stat(2ull * n_cells);
-    uint64_t* obc = (uint64_t*)std::malloc(8ull * nc1);
-    if (!obc) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed");
-    unsigned long long tally[2] = {0, 0};
-    auto parse_args = [&](uint32_t c0, uint32_t c1, uint32_t* nwalk, DevStatus* dst) {
-        return AtacParseArgs{d_bytes, d_cells.as<AtacCell>() + c0, c1 - c0, bc_bytes, d_bm.as<uint64_t>(), d_ref.as<uint32_t>(), d_start.as<uint32_t>(),
-                             d_flen.as<uint16_t>(), d_cnt.as<uint32_t>() + c0, d_bc.as<uint64_t>() + c0, d_stat.as<uint32_t>() + 2ull * c0,
-                             d_walk.as<uint32_t>() + c0, nwalk, dst, (uint64_t)n_bytes};
-    };
-    // Big batches go through in eight ranges of cells: the distinct fragments of range r cross PCIe on a second stream while the
-    // later ranges are still parsed and sorted.  The rows are the long pole - 12 bytes a row, 1.8 GB for 2*10^8 records, 34 ms at
-    // the 52 GB/s the link gives (the e2e leg), against 20 ms for all the kernels - so (round 5) the ref column stays on the device
-    // (8 bytes a row cross, 23 ms; the host writes the column from a list of runs, below), and what matters then is how soon the
-    // FIRST rows can leave and how few are left when the last kernel ends: the ranges GROW (4, 8, 12, 14, 15, 16, 16, 15 % of the
-    // records; four equal ranges kept the link idle for the first quarter of the kernels), the opposite of the cr-like taper,
-    // whose rows are short.  Measured and not kept: the parse of range r+1 on a stream of its own next to the sort of range r
-    // (the sort's workgroups wait for CUs behind the parse's: 12.7 -> 18.3 ms of sort, 28.6 -> 30.9 ms a step).
-    const char* pipe_env = test_hook("ATAC_PIPE_BYTES");   // (tests: pipeline small inputs too)
-    const size_t pipe_min = pipe_env ? (size_t)std::atoll(pipe_env) : ((size_t)128 << 20);
-    const bool piped = n_cells >= 8 && n_bytes >= pipe_min;
-    bool piped_done = false;
-    if (piped) {
-        constexpr uint32_t kR = 8;
-        static const double kGrow[kR] = {0.04, 0.12, 0.24, 0.38, 0.53, 0.69, 0.85, 1.0};
-        uint32_t cut[kR + 1];
-        cut[0] = 0;
-        for (uint32_t r = 1; r < kR; ++r) {
-            const uint64_t target = (uint64_t)((double)n_rec * kGrow[r - 1]);
-            cut[r] = (uint32_t)(std::lower_bound(cap_ptr.begin(), cap_ptr.begin() + n_cells, target) - cap_ptr.begin());
-            if (cut[r] < cut[r - 1]) cut[r] = cut[r - 1];
-        }
-        cut[kR] = n_cells;
-        DevBuf &d_scr = c->atac[4], &d_oref = c->atac[5], &d_ostart = c->atac[6], &d_oflen = c->atac[7], &d_ocnt = c->atac[8], &d_on = c->atac[9],
-               &d_optr = c->atac[10], &d_cref = c->atac[11], &d_cstart = c->atac[12], &d_cflen = c->atac[13], &d_ccnt = c->atac[14],
-               &d_flag = c->atac[15], &d_tally = c->atac[24], &d_rstat = c->atac[25], &d_runctr = c->atac[26];
-        hipError_t e = hipSuccess;
-        auto T = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        T(d_scr.ensure(16 * n1)); T(d_oref.ensure(4 * n1)); T(d_ostart.ensure(4 * n1)); T(d_oflen.ensure(2 * n1)); T(d_ocnt.ensure(2 * n1));
-        T(d_on.ensure(4ull * nc1)); T(d_optr.ensure(8ull * (n_cells + 1))); T(d_flag.ensure(4)); T(d_tally.ensure(16));
-        T(d_cref.ensure(4 * n1)); T(d_cstart.ensure(4 * n1)); T(d_cflen.ensure(2 * n1)); T(d_ccnt.ensure(2 * n1));   // (sized for "nothing is a duplicate")
-        T(d_rstat.ensure(kR * (sizeof(DevStatus) + 16))); T(d_runctr.ensure(4));
-        // The ref column does not cross PCIe: a cell's rows are sorted by ref first, so the column is a few runs per cell - the
-        // compaction kernel lists them (first row, length, ref: 16 bytes a run, written straight into pinned host memory) and
-        // host threads write the column from the list while the other three columns (8 of the 12 bytes of a row) are on the link.
-        // A list that overflows (more than 64 runs per cell on average: thousands of contigs) sends the column itself, as before.
-        const long cap_hook = test_hook_long("ATAC_RUN_CAP", -1);   // (tests: force the overflow)
-        // (at most 2^22 runs = 64 MiB of pinned memory whatever the number of barcodes - an unfiltered sample has a million of them; a
-        //  list that does not fit, or that the host has no pinned memory for, is the overflow case: the column crosses as a copy)
-        uint32_t run_cap = cap_hook >= 0 ? (uint32_t)cap_hook : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1u << 20, 64ull * n_cells), 1u << 22);
-        uint4* runs = (uint4*)pinned_pool()->get(16ull * std::max<uint32_t>(run_cap, 1));
-        if (!runs) { run_cap = 0; runs = (uint4*)pinned_pool()->get(16); }
-        uint32_t* oref = (uint32_t*)pinned_pool()->get(4 * n1);
-        uint32_t* ostart = (uint32_t*)pinned_pool()->get(4 * n1);
-        uint16_t* oflen = (uint16_t*)pinned_pool()->get(2 * n1);
-        uint16_t* ocnt = (uint16_t*)pinned_pool()->get(2 * n1);
-        uint64_t* optr = (uint64_t*)std::malloc(8ull * (n_cells + 1));
-        auto drop = [&]() { std::free(optr); afq_free(oref); afq_free(ostart); afq_free(oflen); afq_free(ocnt); afq_free(runs); };
-        if (!oref || !ostart || !oflen || !ocnt || !optr || !runs) { drop(); std::free(obc); return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed"); }
-        hipStream_t s2 = c->rs[0].stream;
-        DevStatus* d_rst = reinterpret_cast<DevStatus*>(d_rstat.p);
-        uint32_t* d_rnw = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(d_rstat.p) + kR * sizeof(DevStatus));
-        // (the per-range counts and flags land in PINNED memory: an async copy into pageable memory holds the host until the
-        // stream gets there, and the ranges would be enqueued one at a time)
-        uint8_t* pin = (uint8_t*)pinned_pool()->get(4ull * nc1 + kR * (sizeof(DevStatus) + 16));
-        if (!pin) { drop(); std::free(obc); return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed"); }
-        uint32_t* on = reinterpret_cast<uint32_t*>(pin);
-        DevStatus* rst = reinterpret_cast<DevStatus*>(pin + 4ull * nc1);
-        uint32_t* wide = reinterpret_cast<uint32_t*>(pin + 4ull * nc1 + kR * sizeof(DevStatus));
-        volatile uint32_t* snap = wide + kR;   // the run counter as it stood after each range's compaction (the block has four words per range)
-        uint32_t* pin_dev = nullptr;   // the same block as the device sees it
-        T(hipHostGetDevicePointer(reinterpret_cast<void**>(&pin_dev), pin, 0));
-        uint4* runs_dev = nullptr;
-        T(hipHostGetDevicePointer(reinterpret_cast<void**>(&runs_dev), runs, 0));
-        hipEvent_t ev[kR], ev2[kR];
-        for (auto& x : ev) x = get_event(c);
-        for (auto& x : ev2) x = get_event(c);
-        T(hipMemsetAsync(d_runctr.p, 0, 4, s));
-        // the threads that write the ref column: thread 0 waits for a range's list (the event after its compaction), all fill
-        std::atomic<int> recorded{0}, listed{0}, stop{0};
-        const unsigned nfill = stage_threads();
-        std::vector<std::thread> fillers;
-        if (e == hipSuccess) {
-            for (unsigned t = 0; t < nfill; ++t)
-                fillers.emplace_back([&, t]() {
-                    if (t == 0) (void)hipSetDevice(c->device);
-                    uint32_t lo = 0;
-                    for (uint32_t r = 0; r < kR; ++r) {
-                        if (t == 0) {
-                            while (recorded.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-                            if (hipEventSynchronize(ev2[r]) != hipSuccess) { (void)hipGetLastError(); stop.store(1); return; }
-                            listed.store((int)r + 1, std::memory_order_release);
-                        } else {
-                            while (listed.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-                        }
-                        const uint32_t hi = snap[r];
-                        if (hi > run_cap) return;   // this range's column and every later one come as copies
-                        for (uint32_t i = lo + t; i < hi; i += nfill) {
-                            const uint4 q = runs[i];
-                            std::fill_n(oref + (((uint64_t)q.y << 32) | q.x), (size_t)q.z, q.w);
-                        }
-                        lo = hi;
-                    }
-                });
-        }
-        T(hipMemsetAsync(d_flag.p, 0, 4, s));
-        T(hipMemsetAsync(d_tally.p, 0, 16, s));
-        T(hipMemsetAsync(d_rstat.p, 0, kR * (sizeof(DevStatus) + 16), s));
-        for (uint32_t r = 0; r < kR && e == hipSuccess; ++r) {
-            const uint32_t c0 = cut[r], nr = cut[r + 1] - c0;
-            { ScopedTimer t(c, K_ATAC_PARSE, s); launch_atac_parse(s, parse_args(c0, cut[r + 1], d_rnw + r, d_rst + r)); }
-            { ScopedTimer t(c, K_ATAC, s);
-              launch_atac_dedup64(s, nr, d_ref.as<uint32_t>(), d_start.as<uint32_t>(), d_flen.as<uint16_t>(), d_ptr.as<uint64_t>() + c0, d_scr.p,
-                                  d_oref.as<uint32_t>(), d_ostart.as<uint32_t>(), d_oflen.as<uint16_t>(), d_ocnt.as<uint16_t>(), d_on.as<uint32_t>() + c0,
-                                  d_flag.as<uint32_t>(), d_cnt.as<uint32_t>() + c0); }
-            T(hipGetLastError());
-            // (the range's counts, flag and status go to the pinned block by a kernel, not as copies: see k_copy_words3)
-            launch_copy_words3(s, d_on.as<uint32_t>() + c0, nr, pin_dev + c0, d_flag.as<uint32_t>(), 1, pin_dev + (wide - on) + r,
-                               reinterpret_cast<const uint32_t*>(d_rst + r), (uint32_t)(sizeof(DevStatus) / 4), pin_dev + (reinterpret_cast<uint32_t*>(rst + r) - on));
-            T(hipGetLastError());
-            T(hipEventRecord(ev[r], s));
-        }
-        optr[0] = 0;
-        bool redo = false;
-        int bad_rc = 0;
-        for (uint32_t r = 0; r < kR && e == hipSuccess && !redo && !bad_rc; ++r) {
-            const uint32_t c0 = cut[r], c1 = cut[r + 1];
-            T(hipEventSynchronize(ev[r]));
-            if (e != hipSuccess) break;
-            if (wide[r]) { redo = true; break; }   // a reference id >= 65536: the plain route below runs the 16-byte-record kernel
-            if (rst[r].err_code) { bad_rc = fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(c0 + rst[r].err_cell) + ": chunk nbytes does not match its records"); break; }
-            st.n_fallback += rst[r].n_fallback;
-            for (uint32_t i = c0; i < c1; ++i) optr[i + 1] = optr[i] + on[i];
-            const uint64_t o0 = optr[c0], tot_r = optr[c1] - o0;
-            T(hipMemcpyAsync(d_optr.as<uint64_t>() + c0, optr + c0, 8ull * (c1 - c0 + 1), hipMemcpyHostToDevice, s2));
-            if (tot_r) {
-                launch_atac_compact(s2, c1 - c0, d_ptr.as<uint64_t>() + c0, d_optr.as<uint64_t>() + c0, d_oref.as<uint32_t>(), d_ostart.as<uint32_t>(),
-                                    d_oflen.as<uint16_t>(), d_ocnt.as<uint16_t>(), d_cref.as<uint32_t>(), d_cstart.as<uint32_t>(),
-                                    d_cflen.as<uint16_t>(), d_ccnt.as<uint16_t>(), d_tally.as<unsigned long long>(), runs_dev, d_runctr.as<uint32_t>(), run_cap);
-                T(hipGetLastError());
-            }
-            launch_copy_words3(s2, d_runctr.as<uint32_t>(), 1, pin_dev + (const_cast<uint32_t*>(snap) - on) + r, nullptr, 0, nullptr, nullptr, 0, nullptr);
-            T(hipGetLastError());
-            T(hipEventRecord(ev2[r], s2));
-            if (e == hipSuccess) recorded.store((int)r + 1, std::memory_order_release);
-            if (tot_r) {
-                T(hipMemcpyAsync(ostart + o0, d_cstart.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
-                T(hipMemcpyAsync(oflen + o0, d_cflen.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
-                T(hipMemcpyAsync(ocnt + o0, d_ccnt.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
-            }
-        }
-        if (e != hipSuccess || redo || bad_rc) stop.store(1);
-        for (auto& th : fillers) th.join();
-        if (e == hipSuccess && !redo && !bad_rc) {
-            T(hipEventSynchronize(ev2[kR - 1]));   // (every range's count is on the host; the fillers stop at the first list that overflowed)
-            for (uint32_t r = 0; r < kR && e == hipSuccess; ++r)
-                if (snap[r] > run_cap) {
-                    const uint64_t o0 = optr[cut[r]], tot_r = optr[cut[r + 1]] - o0;
-                    if (tot_r) T(hipMemcpyAsync(oref + o0, d_cref.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
-                }
-            T(hipMemcpyAsync(tally, d_tally.p, 16, hipMemcpyDeviceToHost, s2));
-            if (n_cells) T(hipMemcpyAsync(stat.data(), d_stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
-            if (n_cells) T(hipMemcpyAsync(obc, d_bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
-        }
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamSynchronize(s2);
-        for (auto x : ev) c->event_pool.push_back(x);
-        for (auto x : ev2) c->event_pool.push_back(x);
-        afq_free(pin); afq_free(runs); runs = nullptr;
-        harvest_timers(c);
-        hc.lap("atac: ranges (parse, sort, compact, D2H)");
-        if (e != hipSuccess || bad_rc) {
-            drop(); std::free(obc);
-            return bad_rc ? bad_rc : fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_dedup_rad: ") + hipGetErrorString(e));
-        }
-        if (redo) { drop(); st = DevStatus{}; for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; } }
-        else { *out_cell_ptr = optr; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_count = ocnt; piped_done = true; }
+    reset_kernel_times(c);
+    J.stat.assign(2ull * n_cells, 0);
+    HostOuts H;
+    J.obc = (uint64_t*)H.mallocd(8ull * nc1);
+    if (!J.obc) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed");
+    // ---- piped (big batches) or plain
+    const size_t pipe_min = (size_t)test_hook_long("ATAC_PIPE_BYTES", 128L << 20);   // (tests: pipeline small inputs too)
+    int route = kPipedRedo;
+    if (n_cells >= 8 && n_bytes >= pipe_min) {
+        route = atac_dedup_piped(c, J, out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc);
+        if (route < 0) return route;
+        if (route == kPipedRedo) reset_kernel_times(c);
     }
-    if (!piped_done) {
-        HIP_TRY(c, hipMemsetAsync(d_nwalk.p, 0, 4, s));
-        HIP_TRY(c, hipMemsetAsync(d_status.p, 0, sizeof(DevStatus), s));
+    if (route == kPipedRedo) {
+        HIP_TRY(c, hipMemsetAsync(A.nwalk.p, 0, 4, s));
+        HIP_TRY(c, hipMemsetAsync(A.status.p, 0, sizeof(DevStatus), s));
         {
             ScopedTimer t(c, K_ATAC_PARSE, s);
-            launch_atac_parse(s, parse_args(0, n_cells, d_nwalk.as<uint32_t>(), d_status.as<DevStatus>()));
+            launch_atac_parse(s, J.parse_args(A, 0, n_cells, A.nwalk.as<uint32_t>(), A.status.as<DevStatus>()));
             HIP_TRY(c, hipGetLastError());
         }
-        hipError_t e = hipMemcpyAsync(&st, d_status.p, sizeof(st), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && n_cells) e = hipMemcpyAsync(stat.data(), d_stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && n_cells) e = hipMemcpyAsync(obc, d_bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller keeps ownership of `bytes`: the copy out of them is done by now, too
-        if (e != hipSuccess) { std::free(obc); return fail(c, AFQ_ERR_HIP, std::string("afq_atac_dedup_rad: ") + hipGetErrorString(e)); }
-        if (st.err_code) { std::free(obc); return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(st.err_cell) + ": chunk nbytes does not match its records"); }
-        int rc = atac_dedup_device(c, n_rec, n_cells, d_cnt.as<uint32_t>(), out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc, tally);
-        if (rc) { std::free(obc); return rc; }
+        HipLatch T;
+        T(hipMemcpyAsync(&J.st, A.status.p, sizeof(J.st), hipMemcpyDeviceToHost, s));
+        if (T.ok() && n_cells) T(hipMemcpyAsync(J.stat.data(), A.stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s));
+        if (T.ok() && n_cells) T(hipMemcpyAsync(J.obc, A.bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s));
+        if (T.ok()) T(hipStreamSynchronize(s));   // the caller keeps ownership of `bytes`: the copy out of them is done by now, too
+        if (!T.ok()) return T.fail(c, "afq_atac_dedup_rad");
+        if (J.st.err_code) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(J.st.err_cell) + ": chunk nbytes does not match its records");
+        int rc = atac_dedup_device(c, J.n_rec, n_cells, A.cnt.as<uint32_t>(), out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc, J.tally);
+        if (rc) return rc;
     }
-    *out_bc = obc;
+    // ---- stats
+    H.release();
+    *out_bc = J.obc;
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
-        stats->n_records = n_rec;
-        for (uint32_t i = 0; i < n_cells; ++i) { stats->n_multimapped += stat[2 * i]; stats->n_not_mapped_pair += stat[2 * i + 1]; }
-        const uint64_t tot = (*out_cell_ptr)[n_cells];
-        stats->n_distinct = tot;
-        stats->n_deduplicated = tally[0]; stats->n_long_fragments = tally[1];   // (tallied by the compaction kernel)
-        stats->n_fallback_cells = st.n_fallback;
+        stats->n_records = J.n_rec;
+        for (uint32_t i = 0; i < n_cells; ++i) { stats->n_multimapped += J.stat[2 * i]; stats->n_not_mapped_pair += J.stat[2 * i + 1]; }
+        stats->n_distinct = (*out_cell_ptr)[n_cells];
+        stats->n_deduplicated = J.tally[0]; stats->n_long_fragments = J.tally[1];   // (tallied by the compaction kernel)
+        stats->n_fallback_cells = J.st.n_fallback;
     }
     return 0;
 }
@@ -2460,26 +2523,12 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     const uint32_t n_bins = (uint32_t)n_bins64;
     // ---- chunk table
     std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (!bytes_on_device) {
-        for (uint32_t i = 0; i < n_chunks; ++i) {
-            if (chunk_off[i] + 8 > n_bytes || chunk_off[i] + 8 < chunk_off[i]) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk offset out of range");
-            std::memcpy(&hdr[2 * i], bytes + chunk_off[i], 8);
-        }
-    } else if (n_chunks) {
-        HIP_TRY(c, c->d_chunk_off.ensure(8ull * n_chunks));
-        HIP_TRY(c, c->d_hdr.ensure(8ull * n_chunks));
-        HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n_chunks, hipMemcpyHostToDevice, s));
-        launch_gather_headers(s, bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n_chunks, c->d_hdr.as<uint32_t>());
-        HIP_TRY(c, hipMemcpyAsync(hdr.data(), c->d_hdr.p, 8ull * n_chunks, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
     std::vector<SortChunk> chunks(n_chunks);
     uint64_t n_slots = 0;
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (chunk_off[i] + 8 > n_bytes || chunk_off[i] + 8 < chunk_off[i] || nb < 8 || chunk_off[i] + nb > n_bytes)
-            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk header/size out of range");
-        if ((uint64_t)nr * (4 + bc_bytes) + 8 > nb) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(i) + ": chunk nbytes does not match its records");
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
         chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
         n_slots += nr;
     }
@@ -2498,60 +2547,54 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
                         std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables > " +
                         std::to_string(tot) + " bytes of device memory");
     }
-    DevBuf &d_chunks = c->asort[0], &d_obs = c->asort[1], &d_rank = c->asort[2], &d_tkey = c->asort[3], &d_tval = c->asort[4], &d_rinfo = c->asort[5],
-           &d_bbase = c->asort[6], &d_rbc = c->asort[7], &d_bin = c->asort[8], &d_key0 = c->asort[9], &d_cstat = c->asort[10], &d_status = c->asort[11],
-           &d_hist = c->asort[12], &d_cur = c->asort[13], &d_segs = c->asort[14], &d_ka = c->asort[15], &d_kb = c->asort[16], &d_andor = c->asort[17],
-           &d_leaves = c->asort[18], &d_ids = c->asort[19], &d_on = c->asort[20], &d_lout = c->asort[21], &d_out = c->asort[22], &d_tally = c->asort[23];
-    hipError_t e = hipSuccess;
-    auto T = [&](hipError_t x) { if (e == hipSuccess) e = x; };
+    auto& B = c->asort;
+    HipLatch T;
     auto hip_fail = [&]() {
-        (void)hipGetLastError();
-        return fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string("afq_atac_sort_rad: ") + hipGetErrorString(e) + " (" + std::to_string(n_bytes) +
-                    " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_corr) + " corrections)");
+        return T.fail(c, "afq_atac_sort_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_corr) + " corrections)");
     };
-    T(d_chunks.ensure(sizeof(SortChunk) * nc1)); T(d_obs.ensure(8 * std::max<uint64_t>(n_corr, 1))); T(d_rank.ensure(4 * std::max<uint64_t>(n_corr, 1)));
-    T(d_tkey.ensure(8 * cap)); T(d_tval.ensure(4 * cap)); T(d_rinfo.ensure(8ull * ref_info.size())); T(d_bbase.ensure(4ull * bin_base.size()));
-    T(d_rbc.ensure(8 * std::max<uint64_t>(uniq.size(), 1))); T(d_bin.ensure(4 * s1)); T(d_key0.ensure(8 * s1)); T(d_cstat.ensure(16ull * nc1));
-    T(d_status.ensure(sizeof(DevStatus))); T(d_hist.ensure(4ull * nb1)); T(d_cur.ensure(4ull * nb1)); T(d_segs.ensure(sizeof(SortSeg))); T(d_tally.ensure(8));
-    if (e != hipSuccess) return hip_fail();
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * std::max<uint64_t>(n_corr, 1))); T(B.rank.ensure(4 * std::max<uint64_t>(n_corr, 1)));
+    T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap)); T(B.rinfo.ensure(8ull * ref_info.size())); T(B.bbase.ensure(4ull * bin_base.size()));
+    T(B.rbc.ensure(8 * std::max<uint64_t>(uniq.size(), 1))); T(B.bin.ensure(4 * s1)); T(B.key0.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1));
+    T(B.status.ensure(sizeof(DevStatus))); T(B.hist.ensure(4ull * nb1)); T(B.cur.ensure(4ull * nb1)); T(B.segs.ensure(sizeof(SortSeg))); T(B.tally.ensure(8));
+    if (!T.ok()) return hip_fail();
     const uint8_t* d_bytes = bytes;
     if (!bytes_on_device) {
         T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (e != hipSuccess) return hip_fail();
+        if (!T.ok()) return hip_fail();
         if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
         d_bytes = c->d_bytes_own.as<uint8_t>();
     }
-    if (n_chunks) T(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_corr) { T(hipMemcpyAsync(d_obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(d_rank.p, rank.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
-    if (ref_count) T(hipMemcpyAsync(d_rinfo.p, ref_info.data(), 8ull * ref_count, hipMemcpyHostToDevice, s));
-    T(hipMemcpyAsync(d_bbase.p, bin_base.data(), 4ull * bin_base.size(), hipMemcpyHostToDevice, s));
-    if (!uniq.empty()) T(hipMemcpyAsync(d_rbc.p, uniq.data(), 8 * uniq.size(), hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(d_tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(d_status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(d_hist.p, 0, 4ull * nb1, s));
-    T(hipMemsetAsync(d_tally.p, 0, 8, s));
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.rank.p, rank.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
+    if (ref_count) T(hipMemcpyAsync(B.rinfo.p, ref_info.data(), 8ull * ref_count, hipMemcpyHostToDevice, s));
+    T(hipMemcpyAsync(B.bbase.p, bin_base.data(), 4ull * bin_base.size(), hipMemcpyHostToDevice, s));
+    if (!uniq.empty()) T(hipMemcpyAsync(B.rbc.p, uniq.data(), 8 * uniq.size(), hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.hist.p, 0, 4ull * nb1, s));
+    T(hipMemsetAsync(B.tally.p, 0, 8, s));
     if (hc.on) { T(hipStreamSynchronize(s)); hc.lap("atac sort: alloc + H2D"); }
-    if (e != hipSuccess) return hip_fail();
-    for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; }
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
     // ---- table, parse
     {
         ScopedTimer t(c, K_ASORT_TABLE, s);
-        launch_sort_table(s, d_obs.as<uint64_t>(), d_rank.as<uint32_t>(), n_corr, d_tkey.as<uint64_t>(), d_tval.as<uint32_t>(), tab_mask, d_status.as<DevStatus>());
+        launch_sort_table(s, B.obs.as<uint64_t>(), B.rank.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
     }
     {
         ScopedTimer t(c, K_ASORT_PARSE, s);
-        launch_sort_parse(s, SortParseArgs{d_bytes, (uint64_t)n_bytes, d_chunks.as<SortChunk>(), n_chunks, bc_bytes, d_tkey.as<uint64_t>(), d_tval.as<uint32_t>(), tab_mask,
-                                           ones_rank, d_rinfo.as<uint2>(), ref_count, d_bin.as<uint32_t>(), d_key0.as<uint64_t>(), d_cstat.as<uint32_t>(),
-                                           d_status.as<DevStatus>()});
+        launch_sort_parse(s, SortParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask,
+                                           ones_rank, B.rinfo.as<uint2>(), ref_count, B.bin.as<uint32_t>(), B.key0.as<uint64_t>(), B.cstat.as<uint32_t>(),
+                                           B.status.as<DevStatus>()});
     }
     T(hipGetLastError());
     DevStatus st{};
     std::vector<uint32_t> cstat(4ull * n_chunks);
-    T(hipMemcpyAsync(&st, d_status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), d_cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("atac sort: table + parse");
-    if (e != hipSuccess) return hip_fail();
+    if (!T.ok()) return hip_fail();
     if (st.err_code) {
         harvest_timers(c);
         const std::string who = std::to_string(st.err_cell);
@@ -2572,20 +2615,20 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     struct Big { uint32_t off, cnt, bin; };
     std::vector<Big> big;
     if (n_kept) {
-        T(d_ka.ensure(8ull * n_kept));
-        if (e != hipSuccess) return hip_fail();
+        T(B.ka.ensure(8ull * n_kept));
+        if (!T.ok()) return hip_fail();
         const SortSeg seg0{0, (uint32_t)n_slots, 0, 0};
-        T(hipMemcpyAsync(d_segs.p, &seg0, sizeof(seg0), hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.segs.p, &seg0, sizeof(seg0), hipMemcpyHostToDevice, s));
         {
             ScopedTimer t(c, K_ASORT_PART, s);
-            launch_sort_partition(s, d_segs.as<SortSeg>(), 1, (uint32_t)n_slots, d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), n_bins, d_hist.as<uint32_t>(),
-                                  d_cur.as<uint32_t>(), d_ka.as<uint64_t>());
+            launch_sort_partition(s, B.segs.as<SortSeg>(), 1, (uint32_t)n_slots, B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), n_bins, B.hist.as<uint32_t>(),
+                                  B.cur.as<uint32_t>(), B.ka.as<uint64_t>());
         }
         T(hipGetLastError());
         std::vector<uint32_t> hist(n_bins);
-        T(hipMemcpyAsync(hist.data(), d_hist.p, 4ull * n_bins, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(hist.data(), B.hist.p, 4ull * n_bins, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
-        if (e != hipSuccess) return hip_fail();
+        if (!T.ok()) return hip_fail();
         uint32_t off = 0;
         for (uint32_t b = 0; b < n_bins; ++b) {
             const uint32_t n = hist[b];
@@ -2606,17 +2649,17 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
         std::vector<uint64_t> ao(2ull * nb_);
         uint32_t max_cnt = 0;
         for (uint32_t i = 0; i < nb_; ++i) { segs[i] = SortSeg{big[i].off, big[i].cnt, i * 256u, 0}; ao[2 * i] = ~0ull; ao[2 * i + 1] = 0; max_cnt = std::max(max_cnt, big[i].cnt); }
-        T(d_segs.ensure(sizeof(SortSeg) * nb_)); T(d_andor.ensure(16ull * nb_)); T(d_hist.ensure(1024ull * nb_)); T(d_cur.ensure(1024ull * nb_)); T(d_kb.ensure(8ull * n_kept));
-        if (e != hipSuccess) return hip_fail();
-        uint64_t* src = src_is_b ? d_kb.as<uint64_t>() : d_ka.as<uint64_t>();
-        uint64_t* dst = src_is_b ? d_ka.as<uint64_t>() : d_kb.as<uint64_t>();
-        T(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(SortSeg) * nb_, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(d_andor.p, ao.data(), 16ull * nb_, hipMemcpyHostToDevice, s));
-        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_bits(s, d_segs.as<SortSeg>(), nb_, max_cnt, src, d_andor.as<uint64_t>()); }
+        T(B.segs.ensure(sizeof(SortSeg) * nb_)); T(B.andor.ensure(16ull * nb_)); T(B.hist.ensure(1024ull * nb_)); T(B.cur.ensure(1024ull * nb_)); T(B.kb.ensure(8ull * n_kept));
+        if (!T.ok()) return hip_fail();
+        uint64_t* src = src_is_b ? B.kb.as<uint64_t>() : B.ka.as<uint64_t>();
+        uint64_t* dst = src_is_b ? B.ka.as<uint64_t>() : B.kb.as<uint64_t>();
+        T(hipMemcpyAsync(B.segs.p, segs.data(), sizeof(SortSeg) * nb_, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.andor.p, ao.data(), 16ull * nb_, hipMemcpyHostToDevice, s));
+        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_bits(s, B.segs.as<SortSeg>(), nb_, max_cnt, src, B.andor.as<uint64_t>()); }
         T(hipGetLastError());
-        T(hipMemcpyAsync(ao.data(), d_andor.p, 16ull * nb_, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(ao.data(), B.andor.p, 16ull * nb_, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
-        if (e != hipSuccess) return hip_fail();
+        if (!T.ok()) return hip_fail();
         std::vector<Big> split;
         std::vector<SortSeg> ssegs;
         max_cnt = 0;
@@ -2633,13 +2676,13 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
         if (split.empty()) break;
         const uint32_t ns = (uint32_t)split.size();
         std::vector<uint32_t> hist(256ull * ns);
-        T(hipMemcpyAsync(d_segs.p, ssegs.data(), sizeof(SortSeg) * ns, hipMemcpyHostToDevice, s));
-        T(hipMemsetAsync(d_hist.p, 0, 1024ull * ns, s));
-        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_partition(s, d_segs.as<SortSeg>(), ns, max_cnt, src, nullptr, 256, d_hist.as<uint32_t>(), d_cur.as<uint32_t>(), dst); }
+        T(hipMemcpyAsync(B.segs.p, ssegs.data(), sizeof(SortSeg) * ns, hipMemcpyHostToDevice, s));
+        T(hipMemsetAsync(B.hist.p, 0, 1024ull * ns, s));
+        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_partition(s, B.segs.as<SortSeg>(), ns, max_cnt, src, nullptr, 256, B.hist.as<uint32_t>(), B.cur.as<uint32_t>(), dst); }
         T(hipGetLastError());
-        T(hipMemcpyAsync(hist.data(), d_hist.p, 1024ull * ns, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(hist.data(), B.hist.p, 1024ull * ns, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
-        if (e != hipSuccess) return hip_fail();
+        if (!T.ok()) return hip_fail();
         src_is_b ^= 1u;
         for (uint32_t i = 0; i < ns; ++i) {
             uint32_t off = split[i].off;
@@ -2661,48 +2704,48 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     for (uint32_t i = 0; i < n_leaves; ++i) ((leaves[i].flags & 2u) || leaves[i].cnt <= kSortSmallLeaf ? ids_small : ids_big).push_back(i);
     uint64_t n_out = 0;
     if (n_leaves) {
-        T(d_leaves.ensure(sizeof(SortLeaf) * n_leaves)); T(d_ids.ensure(4ull * n_leaves)); T(d_on.ensure(4ull * n_leaves)); T(d_lout.ensure(4ull * (n_leaves + 1)));
-        if (e != hipSuccess) return hip_fail();
+        T(B.leaves.ensure(sizeof(SortLeaf) * n_leaves)); T(B.ids.ensure(4ull * n_leaves)); T(B.on.ensure(4ull * n_leaves)); T(B.lout.ensure(4ull * (n_leaves + 1)));
+        if (!T.ok()) return hip_fail();
         std::vector<uint32_t> ids(ids_small);
         ids.insert(ids.end(), ids_big.begin(), ids_big.end());
-        T(hipMemcpyAsync(d_leaves.p, leaves.data(), sizeof(SortLeaf) * n_leaves, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(d_ids.p, ids.data(), 4ull * n_leaves, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.leaves.p, leaves.data(), sizeof(SortLeaf) * n_leaves, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.ids.p, ids.data(), 4ull * n_leaves, hipMemcpyHostToDevice, s));
         {   // (the parse's outputs are dead after level 0: the runs' keys and lengths go where they were)
             ScopedTimer t(c, K_ASORT_LEAF, s);
-            launch_sort_leaves(s, d_leaves.as<SortLeaf>(), d_ids.as<uint32_t>(), (uint32_t)ids_small.size(), d_ids.as<uint32_t>() + ids_small.size(), (uint32_t)ids_big.size(),
-                               d_ka.as<uint64_t>(), d_kb.as<uint64_t>(), d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), d_on.as<uint32_t>());
+            launch_sort_leaves(s, B.leaves.as<SortLeaf>(), B.ids.as<uint32_t>(), (uint32_t)ids_small.size(), B.ids.as<uint32_t>() + ids_small.size(), (uint32_t)ids_big.size(),
+                               B.ka.as<uint64_t>(), B.kb.as<uint64_t>(), B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), B.on.as<uint32_t>());
         }
         T(hipGetLastError());
-        T(hipMemcpyAsync(on.data(), d_on.p, 4ull * n_leaves, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(on.data(), B.on.p, 4ull * n_leaves, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
-        if (e != hipSuccess) return hip_fail();
+        if (!T.ok()) return hip_fail();
         for (uint32_t i = 0; i < n_leaves; ++i) { n_out += on[i]; lout[i + 1] = (uint32_t)n_out; }
     }
     hc.lap("atac sort: leaves");
     const uint64_t o1 = std::max<uint64_t>(n_out, 1);
-    uint32_t* oref = (uint32_t*)pinned_pool()->get(4 * o1);
-    uint32_t* ostart = (uint32_t*)pinned_pool()->get(4 * o1);
-    uint16_t* oflen = (uint16_t*)pinned_pool()->get(2 * o1);
-    uint64_t* obc = (uint64_t*)pinned_pool()->get(8 * o1);
-    uint32_t* ocnt = (uint32_t*)pinned_pool()->get(4 * o1);
-    auto drop = [&]() { afq_free(oref); afq_free(ostart); afq_free(oflen); afq_free(obc); afq_free(ocnt); };
-    if (!oref || !ostart || !oflen || !obc || !ocnt) { drop(); return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: host allocation failed (" + std::to_string(22 * o1) + " bytes of rows)"); }
+    HostOuts H;
+    uint32_t* oref = (uint32_t*)H.pinned(4 * o1);
+    uint32_t* ostart = (uint32_t*)H.pinned(4 * o1);
+    uint16_t* oflen = (uint16_t*)H.pinned(2 * o1);
+    uint64_t* obc = (uint64_t*)H.pinned(8 * o1);
+    uint32_t* ocnt = (uint32_t*)H.pinned(4 * o1);
+    if (!oref || !ostart || !oflen || !obc || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: host allocation failed (" + std::to_string(22 * o1) + " bytes of rows)");
     unsigned long long n_long = 0;
     if (n_out) {
         // one allocation, the columns behind one another (8-byte column first)
-        T(d_out.ensure(22 * o1 + 64));
-        if (e != hipSuccess) { drop(); return hip_fail(); }
-        uint8_t* b = d_out.as<uint8_t>();
+        T(B.out.ensure(22 * o1 + 64));
+        if (!T.ok()) return hip_fail();
+        uint8_t* b = B.out.as<uint8_t>();
         uint64_t* dbc = reinterpret_cast<uint64_t*>(b);
         uint32_t* dref = reinterpret_cast<uint32_t*>(b + 8 * o1);
         uint32_t* dstart = reinterpret_cast<uint32_t*>(b + 12 * o1);
         uint32_t* dcnt = reinterpret_cast<uint32_t*>(b + 16 * o1);
         uint16_t* dflen = reinterpret_cast<uint16_t*>(b + 20 * o1);
-        T(hipMemcpyAsync(d_lout.p, lout.data(), 4ull * (n_leaves + 1), hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.lout.p, lout.data(), 4ull * (n_leaves + 1), hipMemcpyHostToDevice, s));
         {
             ScopedTimer t(c, K_ASORT_EMIT, s);
-            launch_sort_emit(s, d_leaves.as<SortLeaf>(), n_leaves, d_lout.as<uint32_t>(), d_key0.as<uint64_t>(), d_bin.as<uint32_t>(), d_bbase.as<uint32_t>(), ref_count,
-                             d_rbc.as<uint64_t>(), dref, dstart, dflen, dbc, dcnt, d_tally.as<unsigned long long>());
+            launch_sort_emit(s, B.leaves.as<SortLeaf>(), n_leaves, B.lout.as<uint32_t>(), B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), B.bbase.as<uint32_t>(), ref_count,
+                             B.rbc.as<uint64_t>(), dref, dstart, dflen, dbc, dcnt, B.tally.as<unsigned long long>());
         }
         T(hipGetLastError());
         T(hipMemcpyAsync(oref, dref, 4 * n_out, hipMemcpyDeviceToHost, s));
@@ -2710,14 +2753,15 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
         T(hipMemcpyAsync(oflen, dflen, 2 * n_out, hipMemcpyDeviceToHost, s));
         T(hipMemcpyAsync(obc, dbc, 8 * n_out, hipMemcpyDeviceToHost, s));
         T(hipMemcpyAsync(ocnt, dcnt, 4 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(&n_long, d_tally.p, 8, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(&n_long, B.tally.p, 8, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
     }
     hc.lap("atac sort: emit + D2H");
     harvest_timers(c);
-    if (e != hipSuccess) { drop(); return hip_fail(); }
+    if (!T.ok()) return hip_fail();
     S.n_distinct = n_out; S.n_long_fragments = n_long;
     if (stats) *stats = S;
+    H.release();
     *out_n = n_out; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_bc = obc; *out_count = ocnt;
     return 0;
 }

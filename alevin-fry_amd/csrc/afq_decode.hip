@@ -35,7 +35,7 @@ __global__ void k_gather_headers(const uint8_t* __restrict__ bytes, size_t n_byt
     if (i >= n_cells) return;
     uint64_t off = chunk_off[i];
     uint32_t a = 0, b = 0;
-    if (off + 8 <= n_bytes) {
+    if (n_bytes >= 8 && off <= n_bytes - 8) {   // (off + 8 may wrap)
         a = (uint32_t)ld_le<4>(bytes + off);
         b = (uint32_t)ld_le<4>(bytes + off + 4);
     }

@@ -16,8 +16,8 @@ sn = importlib.import_module("alevin-fry_amd.synth_native")
 CLI = os.path.join(ROOT, "alevin-fry_amd", "csrc", "afquant")
 
 
-def _q():
-    cfg = pkg.WorkerConfig.for_resolution("cr-like", num_genes=1, num_rows=1)
+def _q(profile=False):
+    cfg = pkg.WorkerConfig.for_resolution("cr-like", num_genes=1, num_rows=1, profile=profile)
     return pkg.Quantifier(cfg, np.zeros(1, np.uint32), device=0)
 
 
@@ -185,3 +185,135 @@ def test_atac_last_record_in_a_partial_dword_needs_no_fallback(oracle, bcb):
         _same(got, oracle.atac_dedup_rad(data, np.asarray(off, np.uint64), bc_bytes=bcb))
         assert got[6]["n_fallback_cells"] == 0
     assert hits >= 2
+
+
+# ------------------------------------------------------------------------------------- the exits of the eight-range pipeline
+# Twelve cells of 3-20 one-alignment records (19 bytes each), 113 records.  Under AFQ_TEST_ATAC_PIPE_BYTES=1 they go through the
+# pipeline, whose ranges end at 4, 12, 24, 38, 53, 69 and 85 % of the records: cell 0 (records 0-19) is all of range 0 - some
+# ranges are empty - and cells 10 and 11 (records 104-112, behind 85 % = 96) are range 7.
+_SIZES = [20, 3, 7, 12, 5, 18, 9, 4, 15, 11, 6, 3]
+
+
+def _small_cells(seed, wide_cell=None):
+    rng = np.random.default_rng(seed)
+    cells = []
+    for ci, n in enumerate(_SIZES):
+        recs = [[(int(rng.integers(0, 3)), 4, int(rng.integers(0, 4)), int(rng.integers(50, 52)))] for _ in range(n)]   # (24 distinct fragments)
+        if ci == wide_cell:
+            recs[1] = [(70000, 4, 10, 100)]
+        cells.append((100 + ci, recs))
+    b, off = rad.encode_atac_cells(cells)
+    return np.frombuffer(b, np.uint8).copy(), np.asarray(off, np.uint64)
+
+
+def _dedup(q, data, off, on_device):
+    if not on_device:
+        return q.atac_dedup_rad(data, off)
+    import torch
+
+    t = torch.from_numpy(data).cuda()
+    return q.atac_dedup_rad(None, off, d_ptr=t.data_ptr(), n_bytes=len(data))
+
+
+@pytest.mark.parametrize("on_device", [False, True])
+@pytest.mark.parametrize("wide_cell", [0, 11])
+def test_atac_pipeline_redoes_a_batch_with_a_wide_reference_id(oracle, monkeypatch, wide_cell, on_device):
+    """A reference id of 70000 in the first range, or in the last, sends the whole batch round the plain route (one parse, the
+    64-bit-key kernel and then the 16-byte-record one, seen in the launch counts); the rows are the oracle's, and the next
+    batch on the context - every id below 65536 - goes through the pipeline (a parse per range) and is the oracle's too."""
+    monkeypatch.setenv("AFQ_TEST_ATAC_PIPE_BYTES", "1")
+    data, off = _small_cells(1, wide_cell)
+    good, goff = _small_cells(2)
+    q = _q(profile=True)
+    try:
+        got = _dedup(q, data, off, on_device)
+        kt = q.kernel_times()
+        again = _dedup(q, good, goff, on_device)
+        kt2 = q.kernel_times()
+    finally:
+        q.close()
+    want = oracle.atac_dedup_rad(data, off)
+    _same(got, want)
+    assert 70000 in want[2] and int(want[5].max()) > 1
+    assert kt["k_atac_parse"][1] == 1 and kt["k_atac_dedup"][1] == 2, kt
+    _same(again, oracle.atac_dedup_rad(good, goff))
+    assert kt2["k_atac_parse"][1] == 8 and kt2["k_atac_dedup"][1] == 8, kt2
+
+
+@pytest.mark.parametrize("on_device", [False, True])
+def test_atac_pipeline_reports_a_corrupt_cell_of_a_late_range(oracle, monkeypatch, on_device):
+    """The corrupt header of the plain-route test under the pipeline: cell 10 (the last range) claims 8 records where its bytes
+    hold 6 - few enough to pass the host's size check, so the device's parse finds it while the filler threads run.  The call
+    names the cell; the same context then computes the uncorrupted batch."""
+    monkeypatch.setenv("AFQ_TEST_ATAC_PIPE_BYTES", "1")
+    data, off = _small_cells(3)
+    bad = data.copy()
+    bad[int(off[10]) + 4:int(off[10]) + 8] = np.frombuffer((8).to_bytes(4, "little"), np.uint8)
+    q = _q()
+    try:
+        with pytest.raises(pkg.AfqError) as e:
+            _dedup(q, bad, off, on_device)
+        assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "cell 10: chunk nbytes does not match its records" in str(e.value), e.value
+        got = _dedup(q, data, off, on_device)
+    finally:
+        q.close()
+    _same(got, oracle.atac_dedup_rad(data, off))
+
+
+@pytest.mark.parametrize("on_device", [False, True])
+def test_atac_chunk_offset_outside_the_buffer_is_refused_before_any_read(oracle, on_device):
+    """A chunk offset of n_bytes - 4: its 8-byte header does not lie inside the buffer.  atac_dedup_rad and atac_sort_rad both
+    refuse it on the host - for device bytes too, where nothing is launched before the offsets are checked - and the context
+    then computes a good batch.  (Offsets that wrap 64 bits are tested on the CPU only: tests/test_host_cpu.py.)"""
+    from atac_sort_cases import expected, flat, same
+
+    data, off = _small_cells(4)
+    bad_off = np.append(off, np.uint64(len(data) - 4))
+    chunks = [[(7, [(0, 4, 10, 50)]), (8, [(0, 4, 10, 50)]), (3, [(0, 4, 99, 20)])], [(3, [(0, 4, 5, 30)])]]
+    sdata, soff = rad.encode_atac_chunks(chunks)
+    sdata = np.frombuffer(sdata, np.uint8).copy()
+    sbad = soff.copy()
+    sbad[1] = len(sdata) - 4
+
+    def sort(o):
+        if not on_device:
+            return q.atac_sort_rad(sdata, o, [7, 8, 3], [7, 7, 3], [1000])
+        import torch
+
+        t = torch.from_numpy(sdata).cuda()
+        return q.atac_sort_rad(None, o, [7, 8, 3], [7, 7, 3], [1000], d_ptr=t.data_ptr(), n_bytes=len(sdata))
+
+    q = _q()
+    try:
+        with pytest.raises(pkg.AfqError) as e:
+            _dedup(q, data, bad_off, on_device)
+        assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "cell 12: chunk offset out of range" in str(e.value), e.value
+        got = _dedup(q, data, off, on_device)
+        with pytest.raises(pkg.AfqError) as e:
+            sort(sbad)
+        assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "chunk 1: chunk offset out of range" in str(e.value), e.value
+        sgot = sort(soff)
+    finally:
+        q.close()
+    _same(got, oracle.atac_dedup_rad(data, off))
+    same(sgot, expected(*flat(chunks)[0], [7, 8, 3], [7, 7, 3]), "after a refused table")
+
+
+def test_atac_plain_route_error_after_the_barcode_array_exists(oracle):
+    """The corrupt header of test_atac_walk_free_parse_falls_back..., fifty times on one context: the exit is taken with the
+    call's barcode array already allocated (it is given back on every exit; a test cannot see that, it pins the exit), and the
+    context still computes a good batch."""
+    recs = [[(1, 4, 1000 + i, 100)] for i in range(50)]
+    b, off = rad.encode_atac_cells([(0x00ABCDEF, recs), (5, [[(0, 4, 3, 3)]] * 4)])
+    bad = bytearray(b)
+    bad[4:8] = (60).to_bytes(4, "little")   # the header claims 60 records
+    q = _q()
+    try:
+        for _ in range(50):
+            with pytest.raises(pkg.AfqError) as e:
+                q.atac_dedup_rad(bytes(bad), off)
+            assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and "cell 0: chunk nbytes does not match its records" in str(e.value)
+        got = q.atac_dedup_rad(b, off)
+    finally:
+        q.close()
+    _same(got, oracle.atac_dedup_rad(b, off))

@@ -1144,3 +1144,77 @@ int main() {
     for w, p, s in itertools.product((0, 1), repeat=3):
         assert got[(w, p, s)] == (want[(w, p, s)] if w else "Walk"), (w, p, s, got[(w, p, s)])
     assert len(got) == 8 and [k for k, v in got.items() if v == "Walk"] == [k for k in got if k[0] == 0]
+
+
+def test_chunk_table_checks_do_not_wrap(tmp_path):
+    """csrc/afq_chunk_table.h: stage A (does every chunk's 8-byte header lie inside the buffer?) and stage B (does the chunk its
+    header describes lie inside, and can it hold its records?) against the same questions asked in Python's unbounded integers,
+    at the sizes where a sum in 64 or 32 bits would wrap.  A stand-alone program under AddressSanitizer and UBSan; no GPU."""
+    import itertools
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    (tmp_path / "probe.cpp").write_text("int main() { return 0; }\n")
+    if subprocess.run(["g++", *san, "-o", str(tmp_path / "probe"), str(tmp_path / "probe.cpp")], capture_output=True).returncode != 0 or \
+            subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
+        pytest.skip("no sanitizer runtime")
+    host = r'''#include <cstdio>
+#include <vector>
+#include "afq_chunk_table.h"
+int main() {
+    char what;
+    while (scanf(" %c", &what) == 1) {
+        unsigned long long nb, n, a, b, c, m;
+        if (what == 'A') {
+            if (scanf("%llu %llu", &nb, &n) != 2) return 2;
+            std::vector<uint64_t> off(n);
+            for (auto& x : off) { if (scanf("%llu", &a) != 1) return 2; x = a; }
+            printf("%u\n", afq::first_chunk_outside(off.data(), (uint32_t)n, nb));
+        } else {
+            if (scanf("%llu %llu %llu %llu %llu", &a, &b, &c, &nb, &m) != 5) return 2;
+            printf("%d\n", (int)afq::check_chunk_header(a, (uint32_t)b, (uint32_t)c, nb, (uint32_t)m));
+        }
+    }
+    return 0;
+}
+'''
+    (tmp_path / "t.cpp").write_text(host)
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", *san, "-I", os.path.join(ROOT, "alevin-fry_amd", "csrc"), "-o", str(tmp_path / "t"),
+                    str(tmp_path / "t.cpp")], check=True, capture_output=True)
+    M64, M32 = 1 << 64, (1 << 32) - 1
+
+    def stage_a(offs, nb):
+        return next((i for i, o in enumerate(offs) if o + 8 > nb), len(offs))
+
+    def stage_b(off, nbytes, nrec, nb, min_rec):   # 0 fine, 2 the chunk is not inside the buffer, 3 it cannot hold its records
+        if off + 8 > nb or nbytes < 8 or off + nbytes > nb:
+            return 2
+        return 3 if nrec * min_rec + 8 > nbytes else 0
+
+    lines, want = [], []
+    sizes = [0, 7, 8, 9, 64, 1000, (1 << 32) + 64]   # (the issue's four, and buffers that chunks of 8 bytes and more fit into)
+    for nb in sizes:
+        offs = sorted({0, (nb - 8) % M64, (nb - 7) % M64, nb // 2, M64 - 8, M64 - 4, M64 - 1})
+        inside = [o for o in offs if o + 8 <= nb]
+        tables = [[o] for o in offs] + [[]] + [inside + [o] + inside for o in offs]
+        for t in tables:
+            lines.append(f"A {nb} {len(t)} " + " ".join(map(str, t)))
+            want.append(stage_a(t, nb))
+        for off in offs:
+            to_end = nb - off
+            sizes_b = {0, 7, 8, M32} | {x for x in (to_end, to_end + 1) if 0 <= x <= M32}
+            for nbytes, min_rec in itertools.product(sorted(sizes_b), (5, 6, 8, 12)):
+                fits = max(nbytes - 8, 0) // min_rec
+                for nrec in sorted({0, fits, min(fits + 1, M32), M32}):
+                    lines.append(f"B {off} {nbytes} {nrec} {nb} {min_rec}")
+                    want.append(stage_b(off, nbytes, nrec, nb, min_rec))
+    assert {0, 2, 3} <= set(want) and len(want) > 2000
+    out = subprocess.run([str(tmp_path / "t")], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    got = [int(x) for x in out.stdout.split()]
+    assert len(got) == len(want)
+    for ln, g, w in zip(lines, got, want):
+        assert g == w, (ln, g, w)
