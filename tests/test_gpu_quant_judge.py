@@ -138,7 +138,7 @@ def test_parsimony_switches(judged, name, case):
 @pytest.mark.parametrize("name", qc.BATCHES)
 def test_class_tables_of_the_em_resolutions_are_admitted(judged, name, case):
     """cr-like-em, parsimony-em, parsimony-gene-em with dump_eq: the gene-level classes the EM is given (what -d dumps).  The EM's
-    values are not judged here."""
+    values are judged from these tables on in tests/test_gpu_em_judge.py."""
     b = qc.batch(name)
     res, ckw, _ = ALL_CASES[case]
     got = _device(b.cfg(qc.EM_OF[res], dump_eq=True, **ckw), b.t2g, b.data, b.off)
