@@ -21,9 +21,12 @@ side; it returns every admissible outcome, as the parsimony judge does for cover
   * an entry within the margin of the output floor: the row may hold it or not.
 
     judge_em(classes, num_rows, usa, loop, init="informative") -> (outcomes, undecided)
+    run_loop(classes, offsets, loop, alphas, support) -> (outcomes, undecided): the rounds alone, from an explicit start vector
     admits(outcomes, row, tight=True) -> True, or a message naming the first difference
 
-Random initialisation (em.rs:379-381) is left out: its draws are not the reference's.  So are bootstraps.
+Random initialisation (em.rs:379-381) is not judge_em's: its draws are not the reference's.  It occurs in bootstrap replicates
+only, whose draws are the project's own streams; tests/boot_judge.py judges those, and runs this file's rounds from the random
+start through run_loop.
 """
 import struct
 from collections import namedtuple
@@ -240,7 +243,12 @@ def judge_em(classes, num_rows, usa, loop, init="informative"):
     # em.rs:370-383 over the support; em.rs:519-531 over every alpha, of which only those of some label are ever read or written
     support = support_of(classes, offsets)
     prior = _f32(1.0 / _f32(num_rows))
-    alphas = {x: prior if init == "uniform" else (unique.get(x, 0.0) + 0.5) * 1e-3 for x in support}
+    return run_loop(classes, offsets, loop, {x: prior if init == "uniform" else (unique.get(x, 0.0) + 0.5) * 1e-3 for x in support}, support)
+
+
+def run_loop(classes, offsets, loop, alphas, support):
+    """The rounds of either loop (em.rs:391-451, 538-572) from an explicit start vector over the support, whatever filled it: an
+    initialisation of judge_em, or a bootstrap replicate's random start (tests/boot_judge.py).  Returns (outcomes, undecided)."""
     outcomes = []
     rounds = 0
     try:

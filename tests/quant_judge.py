@@ -7,8 +7,8 @@ labels - so that a rule misread there is not repeated here.  Only ints, tuples, 
 
 What it covers: the tiny-cell path, cr-like (winner-take-all and prefer-ambig), trivial, parsimony and parsimony-gene with the
 large-component fall-back, the step from a cell's gene-level classes to its row (non-USA and USA), and the class table that the
--em resolutions hand to their EM (what -d dumps).  The EM's numbers are judged from that table on by tests/em_judge.py.  What is
-left out: bootstraps, the decoding of bytes.
+-em resolutions hand to their EM (what -d dumps).  The EM's numbers are judged from that table on by tests/em_judge.py, the
+bootstrap means and variances by tests/boot_judge.py.  What is left out: the decoding of bytes.
 
 The parsimony cover's tie-break.  The reference walks a HashSet of the uncovered vertices and keeps the first largest
 arborescence (pugutils.rs:1110-1146); which one is first depends on the hash order.  The judge therefore does not replay a scan:
