@@ -2092,26 +2092,30 @@ static int atac_dedup_device(afq_ctx* c, uint64_t n, uint32_t n_cells, const uin
     HipLatch T;
     T(A.scr.ensure(16 * n1)); T(A.oref.ensure(4 * n1)); T(A.ostart.ensure(4 * n1)); T(A.oflen.ensure(2 * n1));
     T(A.ocnt.ensure(2 * n1)); T(A.on.ensure(4ull * std::max<uint32_t>(n_cells, 1))); T(A.optr.ensure(8ull * (n_cells + 1)));
-    T(A.flag.ensure(4));
+    T(A.flag.ensure(4)); T(A.tally.ensure(16));
     if (T.ok()) T(hipMemsetAsync(A.flag.p, 0, 4, s));
+    if (T.ok()) T(hipMemsetAsync(A.tally.p, 0, 16, s));
+    // (the tally starts here, not at the compaction: the dedup kernels add the runs whose 16-bit count wrapped to 0 or 1)
+    unsigned long long* const d_tally = tally_out ? A.tally.as<unsigned long long>() : nullptr;
     std::vector<uint32_t> on(n_cells);
     uint32_t wide = 0;
     if (T.ok()) {
         ScopedTimer t(c, K_ATAC, s);
         launch_atac_dedup64(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
                             A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
-                            A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), A.flag.as<uint32_t>(), d_cnt);
+                            A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), A.flag.as<uint32_t>(), d_cnt, d_tally);
         T(hipGetLastError());
     }
     if (T.ok()) {
         T(hipMemcpyAsync(&wide, A.flag.p, 4, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
     }
-    if (T.ok() && wide) {  // a reference id >= 65536: the 16-byte-record kernel
+    if (T.ok() && wide) {  // a reference id >= 65536: the 16-byte-record kernel (and its tally, not that of the cut keys' runs)
+        T(hipMemsetAsync(A.tally.p, 0, 16, s));
         ScopedTimer t(c, K_ATAC, s);
         launch_atac_dedup(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
                           A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
-                          A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), d_cnt);
+                          A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), d_cnt, d_tally);
         T(hipGetLastError());
     }
     if (T.ok() && n_cells) T(hipMemcpyAsync(on.data(), A.on.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
@@ -2132,8 +2136,6 @@ static int atac_dedup_device(afq_ctx* c, uint64_t n, uint32_t n_cells, const uin
     // dense runs on the device, then straight into the caller's arrays
     T(A.cref.ensure(4 * tot1)); T(A.cstart.ensure(4 * tot1)); T(A.cflen.ensure(2 * tot1)); T(A.ccnt.ensure(2 * tot1));
     if (T.ok()) T(hipMemcpyAsync(A.optr.p, optr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    T(A.tally.ensure(16));
-    if (T.ok()) T(hipMemsetAsync(A.tally.p, 0, 16, s));
     if (T.ok() && tot) {
         launch_atac_compact(s, n_cells, A.ptr.as<uint64_t>(), A.optr.as<uint64_t>(), A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(),
                             A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.cref.as<uint32_t>(), A.cstart.as<uint32_t>(),
@@ -2307,7 +2309,7 @@ static int atac_dedup_piped(afq_ctx* c, AtacRadJob& J, uint64_t** out_cell_ptr, 
         { ScopedTimer t(c, K_ATAC, s);
           launch_atac_dedup64(s, nr, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>() + c0, A.scr.p,
                               A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.on.as<uint32_t>() + c0,
-                              A.flag.as<uint32_t>(), A.cnt.as<uint32_t>() + c0); }
+                              A.flag.as<uint32_t>(), A.cnt.as<uint32_t>() + c0, A.tally.as<unsigned long long>()); }
         T(hipGetLastError());
         // (the range's counts, flag and status go to the pinned block by a kernel, not as copies: see k_copy_words3)
         launch_copy_words3(s, A.on.as<uint32_t>() + c0, nr, pin_dev + c0, A.flag.as<uint32_t>(), 1, pin_dev + (wide - on) + r,

@@ -168,10 +168,14 @@ void launch_compact_em(hipStream_t s, uint32_t n_cells, const uint64_t* em_off, 
                        const uint64_t* cell_ptr, uint32_t* gene, float* val);
 void launch_atac_dedup(hipStream_t s, uint32_t n_cells, const uint32_t* ref, const uint32_t* start, const uint16_t* flen,
                        const uint64_t* cell_ptr, void* scratch /* 16 B per fragment */, uint32_t* o_ref, uint32_t* o_start,
-                       uint16_t* o_flen, uint16_t* o_cnt, uint32_t* o_n, const uint32_t* cell_cnt = nullptr);
+                       uint16_t* o_flen, uint16_t* o_cnt, uint32_t* o_n, const uint32_t* cell_cnt = nullptr,
+                       unsigned long long* tally = nullptr);
 void launch_atac_dedup64(hipStream_t s, uint32_t n_cells, const uint32_t* ref, const uint32_t* start, const uint16_t* flen,
                          const uint64_t* cell_ptr, void* scratch, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,
-                         uint16_t* o_cnt, uint32_t* o_n, uint32_t* flag, const uint32_t* cell_cnt = nullptr);
+                         uint16_t* o_cnt, uint32_t* o_n, uint32_t* flag, const uint32_t* cell_cnt = nullptr,
+                         unsigned long long* tally = nullptr);
+// (tally: tally[0] += the runs of 65536 and more records whose 16-bit count reads 0 or 1 - launch_atac_compact, which tallies
+//  "seen more than once" from the stored counts, cannot see them; zeroed by the caller before the dedup kernel it keeps)
 // ATAC records straight from collated-RAD chunks (afq_atac.hip)
 struct AtacCell { uint64_t chunk_off; uint64_t out_off; uint64_t bm_off; uint32_t nbytes; uint32_t nrec; };
 struct AtacParseArgs {

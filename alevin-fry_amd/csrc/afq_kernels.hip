@@ -1187,13 +1187,21 @@ struct Frag {
 __device__ __forceinline__ bool operator>(const Frag& a, const Frag& b) { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
 __device__ __forceinline__ bool operator!=(const Frag& a, const Frag& b) { return a.hi != b.hi || a.lo != b.lo; }
 
+// The reference counts a fragment as deduplicated from the run length BEFORE it is cut to 16 bits (`if count > 1` on the usize,
+// deduplicate.rs:224) while k_atac_compact sees the stored u16 only: a run of 65536 k or 65536 k + 1 records (k >= 1), whose
+// stored count is 0 or 1, is tallied here, at the run head, where e - i is known.  (Runs stored as 2 and more are the compaction's.)
+__device__ __forceinline__ void tally_wrapped_run(unsigned long long* tally, uint32_t len) {
+    if (len > 0xFFFFu && (len & 0xFFFFu) <= 1u && tally) atomicAdd(&tally[0], 1ull);
+}
+
 constexpr int kAtacNT = 1024;
 __global__ __launch_bounds__(kAtacNT) void k_atac_dedup(const uint32_t* __restrict__ ref, const uint32_t* __restrict__ start,
                                                        const uint16_t* __restrict__ flen,
                                                        const uint64_t* __restrict__ cell_ptr, Frag* __restrict__ scratch,
                                                        uint32_t* __restrict__ o_ref, uint32_t* __restrict__ o_start,
                                                        uint16_t* __restrict__ o_flen, uint16_t* __restrict__ o_cnt,
-                                                       uint32_t* __restrict__ o_n, const uint32_t* __restrict__ cell_cnt) {
+                                                       uint32_t* __restrict__ o_n, const uint32_t* __restrict__ cell_cnt,
+                                                       unsigned long long* __restrict__ tally) {
     __shared__ uint32_t s_ws[kAtacNT / 64];
     const uint32_t cell = blockIdx.x;
     const uint64_t b0 = cell_ptr[cell];
@@ -1221,7 +1229,8 @@ __global__ __launch_bounds__(kAtacNT) void k_atac_dedup(const uint32_t* __restri
             o_ref[o] = (uint32_t)(f[i].hi >> 32);
             o_start[o] = (uint32_t)f[i].hi;
             o_flen[o] = (uint16_t)f[i].lo;
-            o_cnt[o] = (uint16_t)(e - i);  // `count as u16`, deduplicate.rs:220
+            o_cnt[o] = (uint16_t)(e - i);  // `count as u16`, deduplicate.rs:222
+            tally_wrapped_run(tally, e - i);
         }
         carry += tot;
     }
@@ -1237,7 +1246,8 @@ __global__ __launch_bounds__(kAtacNT) void k_atac_dedup64(const uint32_t* __rest
                                                          const uint64_t* __restrict__ cell_ptr, uint64_t* __restrict__ scratch,
                                                          uint32_t* __restrict__ o_ref, uint32_t* __restrict__ o_start,
                                                          uint16_t* __restrict__ o_flen, uint16_t* __restrict__ o_cnt,
-                                                         uint32_t* __restrict__ o_n, uint32_t* __restrict__ flag, const uint32_t* __restrict__ cell_cnt) {
+                                                         uint32_t* __restrict__ o_n, uint32_t* __restrict__ flag, const uint32_t* __restrict__ cell_cnt,
+                                                         unsigned long long* __restrict__ tally) {
     __shared__ uint32_t s_ws[kAtacNT / 64];
     __shared__ __attribute__((aligned(16))) uint64_t s_tile[16384];
     const uint32_t cell = blockIdx.x;
@@ -1267,7 +1277,8 @@ __global__ __launch_bounds__(kAtacNT) void k_atac_dedup64(const uint32_t* __rest
             o_ref[o] = (uint32_t)(k >> 48);
             o_start[o] = (uint32_t)(k >> 16);
             o_flen[o] = (uint16_t)k;
-            o_cnt[o] = (uint16_t)(e - i);  // `count as u16`, deduplicate.rs:220
+            o_cnt[o] = (uint16_t)(e - i);  // `count as u16`, deduplicate.rs:222
+            tally_wrapped_run(tally, e - i);
         }
         carry += tot;
     }
@@ -1285,13 +1296,13 @@ __global__ __launch_bounds__(256) void k_atac_compact(const uint64_t* __restrict
     const uint32_t cell = blockIdx.x;
     const uint64_t src = cell_ptr[cell], dst = out_ptr[cell];
     const uint32_t n = (uint32_t)(out_ptr[cell + 1] - dst);
-    uint32_t dup = 0, lng = 0;   // fragments seen more than once / of 2000 bases and more (deduplicate.rs:222-224, 47-63)
+    uint32_t dup = 0, lng = 0;   // fragments seen more than once / of 2000 bases and more (deduplicate.rs:224-226, 47-63)
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
         const uint16_t fl = i_flen[src + i], ct = i_cnt[src + i];
         const uint32_t r = i_ref[src + i];
         o_ref[dst + i] = r; o_start[dst + i] = i_start[src + i];
         o_flen[dst + i] = fl; o_cnt[dst + i] = ct;
-        dup += ct > 1; lng += fl >= 2000;
+        dup += ct > 1; lng += fl >= 2000;   // (a run whose count wrapped to 0 or 1: tally_wrapped_run)
         // A cell's rows are in (ref, start, frag_len) order, so its ref column is a few runs: (first row, length, ref) of each
         // goes to the host's list - `runs` is host memory as the device sees it - and the column itself stays here (the host
         // writes it from the list while the other three columns cross PCIe; afq_api.cpp).  The row that starts a run finds its end
@@ -1390,18 +1401,18 @@ void launch_resolve_big(hipStream_t s, const ResolveArgs& a) {
 
 void launch_atac_dedup(hipStream_t s, uint32_t n_cells, const uint32_t* ref, const uint32_t* start, const uint16_t* flen,
                        const uint64_t* cell_ptr, void* scratch, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,
-                       uint16_t* o_cnt, uint32_t* o_n, const uint32_t* cell_cnt) {
+                       uint16_t* o_cnt, uint32_t* o_n, const uint32_t* cell_cnt, unsigned long long* tally) {
     if (!n_cells) return;
     AFQ_LAUNCH(k_atac_dedup, n_cells, kAtacNT, s, ref, start, flen, cell_ptr, reinterpret_cast<Frag*>(scratch), o_ref, o_start,
-               o_flen, o_cnt, o_n, cell_cnt);
+               o_flen, o_cnt, o_n, cell_cnt, tally);
 }
 
 void launch_atac_dedup64(hipStream_t s, uint32_t n_cells, const uint32_t* ref, const uint32_t* start, const uint16_t* flen,
                          const uint64_t* cell_ptr, void* scratch, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,
-                         uint16_t* o_cnt, uint32_t* o_n, uint32_t* flag, const uint32_t* cell_cnt) {
+                         uint16_t* o_cnt, uint32_t* o_n, uint32_t* flag, const uint32_t* cell_cnt, unsigned long long* tally) {
     if (!n_cells) return;
     AFQ_LAUNCH(k_atac_dedup64, n_cells, kAtacNT, s, ref, start, flen, cell_ptr, reinterpret_cast<uint64_t*>(scratch), o_ref, o_start,
-               o_flen, o_cnt, o_n, flag, cell_cnt);
+               o_flen, o_cnt, o_n, flag, cell_cnt, tally);
 }
 
 void launch_atac_compact(hipStream_t s, uint32_t n_cells, const uint64_t* cell_ptr, const uint64_t* out_ptr, const uint32_t* i_ref,

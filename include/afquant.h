@@ -258,7 +258,7 @@ typedef struct afq_atac_stats {
     uint64_t n_multimapped;      /* "records with greater than 1 mapping", deduplicate.rs:210-212                 */
     uint64_t n_not_mapped_pair;  /* neither kept nor multi-mapped (no alignment, or one that is not type 4), :213-215 */
     uint64_t n_distinct;         /* distinct fragments over all cells                                             */
-    uint64_t n_deduplicated;     /* distinct fragments seen more than once, :222-224                              */
+    uint64_t n_deduplicated;     /* distinct fragments seen more than once (the run length before `as u16`), :224 */
     uint64_t n_long_fragments;   /* distinct fragments with frag_len >= 2000 (left out of the BED, :47-63)        */
     uint64_t n_fallback_cells;   /* cells the walk-free parse could not prove and walked record by record         */
 } afq_atac_stats;

@@ -1180,9 +1180,11 @@ int ora_has_edge(uint64_t xu, uint32_t xc, uint64_t yu, uint32_t yc, int exact) 
 // (chr, start, frag_len, barcode) from src/atac/sort.rs:37-64.  The barcode is
 // constant within a cell so it does not affect the order.  Counts are u16 and
 // (like Vec::dedup_by_key accumulation in the reference) are not saturated.
-int ora_atac_dedup(const uint32_t* ref, const uint32_t* start, const uint16_t* flen, const uint64_t* cell_ptr,
-                   uint32_t n_cells, uint64_t* out_cell_ptr, uint32_t* out_ref, uint32_t* out_start,
-                   uint16_t* out_flen, uint16_t* out_count) {
+// n_dup (may be null): += the runs of more than one record - from the run length before `count as u16` cuts it, as
+// deduplicate.rs:224 tests it (a run of 65536 records is stored as 0 and is deduplicated all the same)
+static void atac_dedup_cells(const uint32_t* ref, const uint32_t* start, const uint16_t* flen, const uint64_t* cell_ptr,
+                             uint32_t n_cells, uint64_t* out_cell_ptr, uint32_t* out_ref, uint32_t* out_start,
+                             uint16_t* out_flen, uint16_t* out_count, uint64_t* n_dup) {
     struct H { u32 r, s; u16 f; };
     uint64_t w = 0;
     out_cell_ptr[0] = 0;
@@ -1199,10 +1201,17 @@ int ora_atac_dedup(const uint32_t* ref, const uint32_t* start, const uint16_t* f
             size_t j = i;
             while (j < v.size() && v[j].r == v[i].r && v[j].s == v[i].s && v[j].f == v[i].f) ++j;
             out_ref[w] = v[i].r; out_start[w] = v[i].s; out_flen[w] = v[i].f; out_count[w] = (u16)(j - i);
+            if (n_dup && j - i > 1) ++*n_dup;
             ++w; i = j;
         }
         out_cell_ptr[c + 1] = w;
     }
+}
+
+int ora_atac_dedup(const uint32_t* ref, const uint32_t* start, const uint16_t* flen, const uint64_t* cell_ptr,
+                   uint32_t n_cells, uint64_t* out_cell_ptr, uint32_t* out_ref, uint32_t* out_start,
+                   uint16_t* out_flen, uint16_t* out_count) {
+    atac_dedup_cells(ref, start, flen, cell_ptr, n_cells, out_cell_ptr, out_ref, out_start, out_flen, out_count, nullptr);
     return 0;
 }
 
@@ -1244,8 +1253,8 @@ int ora_atac_dedup_rad(const uint8_t* bytes, size_t n_bytes, const uint64_t* chu
         out_bc[c] = bc;
         ptr.push_back(ref.size());
     }
-    ora_atac_dedup(ref.data(), start.data(), flen.data(), ptr.data(), n_cells, out_cell_ptr, out_ref, out_start, out_flen, out_count);
-    for (uint64_t k = 0; k < out_cell_ptr[n_cells]; ++k) { if (out_count[k] > 1) stats[3]++; if (out_flen[k] >= 2000) stats[4]++; }
+    atac_dedup_cells(ref.data(), start.data(), flen.data(), ptr.data(), n_cells, out_cell_ptr, out_ref, out_start, out_flen, out_count, &stats[3]);
+    for (uint64_t k = 0; k < out_cell_ptr[n_cells]; ++k) if (out_flen[k] >= 2000) stats[4]++;
     return 0;
 }
 
