@@ -126,6 +126,10 @@ EXPORTS = [
     "afq_atac_sort_limits",
     "afq_atac_sort_leaf_limits",
     "afq_atac_sort_table_slot",
+    "afq_gpl_hist_rad",
+    "afq_gpl_correct",
+    "afq_gpl_limits",
+    "afq_gpl_table_slot",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -145,3 +149,20 @@ class AfqAtacStats(C.Structure):
 class AfqAtacSortStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_uncorrected", C.c_uint64),
                 ("n_kept", C.c_uint64), ("n_distinct", C.c_uint64), ("n_long_fragments", C.c_uint64), ("n_repartitioned_bins", C.c_uint64)]
+
+
+class AfqGplHistStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("max_ambig", C.c_uint64), ("n_long_records", C.c_uint64)]
+
+
+class AfqGplCorrectionStats(C.Structure):
+    _fields_ = [("exact_distinct", C.c_uint64), ("exact_reads", C.c_uint64), ("corrected_distinct", C.c_uint64), ("corrected_reads", C.c_uint64),
+                ("ambiguous_distinct", C.c_uint64), ("ambiguous_reads", C.c_uint64), ("not_found_distinct", C.c_uint64), ("not_found_reads", C.c_uint64)]
+
+
+# afq_gpl_hist_rad's expected_ori, afq_gpl_correct's neighborhood / resolution / decisions
+GPL_ORI = {"both": 0, "either": 0, "fw": 1, "rc": 2}
+GPL_NEIGHBORHOODS = {"hamming-1": 0, "substitution-or-shift-1": 1, "edit-1": 1}
+GPL_RESOLUTIONS = {"unique": 0, "frequency": 1}
+GPL_EXACT, GPL_CORRECTED, GPL_AMBIGUOUS, GPL_NOT_FOUND = 0, 1, 2, 3
+GPL_NO_TARGET = 0xFFFFFFFF

@@ -299,6 +299,17 @@ def load_library(path: str = LIB_PATH):
     lib.afq_atac_sort_leaf_limits.restype = None
     lib.afq_atac_sort_table_slot.argtypes = [C.c_uint64, C.c_uint64, p(C.c_uint32), p(C.c_uint32)]
     lib.afq_atac_sort_table_slot.restype = None
+    lib.afq_gpl_hist_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                     p(C.c_uint64), p(p(C.c_uint64)), p(p(C.c_uint64)), p(_abi.AfqGplHistStats)]
+    lib.afq_gpl_hist_rad.restype = C.c_int
+    lib.afq_gpl_correct.argtypes = [C.c_void_p, p(C.c_uint64), p(C.c_uint64), C.c_uint64, p(C.c_uint64), p(C.c_uint64), C.c_uint64, C.c_uint32, C.c_uint32,
+                                    C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, p(p(C.c_uint8)), p(p(C.c_uint32)), p(p(C.c_uint64)),
+                                    p(_abi.AfqGplCorrectionStats)]
+    lib.afq_gpl_correct.restype = C.c_int
+    lib.afq_gpl_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_gpl_limits.restype = None
+    lib.afq_gpl_table_slot.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, p(C.c_uint32), p(C.c_uint32)]
+    lib.afq_gpl_table_slot.restype = None
     lib.afq_free.argtypes = [C.c_void_p]
     lib.afq_free.restype = None
     lib.afq_get_kernel_times.argtypes = [C.c_void_p, p(AfqKernelTime), C.c_uint32]
@@ -329,6 +340,21 @@ def atac_sort_table_slot(barcode, n_corr):
     """afq_atac_sort_table_slot: (home slot of `barcode`, capacity) of the correction table afq_atac_sort_rad builds for n_corr entries."""
     slot, cap = C.c_uint32(), C.c_uint32()
     load_library().afq_atac_sort_table_slot(int(barcode), int(n_corr), C.byref(slot), C.byref(cap))
+    return int(slot.value), int(cap.value)
+
+
+def gpl_limits():
+    """afq_gpl_limits: {"parse_tile", "parse_halo", "lane_alns"} of the generate-permit-list parse - bytes staged per trip, bytes
+    staged behind them, and the alignment count above which a record is a long record."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_gpl_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2])}
+
+
+def gpl_table_slot(barcode, n_kept, bc_bytes: int = 8):
+    """afq_gpl_table_slot: (home slot of `barcode`, capacity) of the counting table afq_gpl_hist_rad builds for n_kept compatible records."""
+    slot, cap = C.c_uint32(), C.c_uint32()
+    load_library().afq_gpl_table_slot(int(barcode), int(n_kept), int(bc_bytes), C.byref(slot), C.byref(cap))
     return int(slot.value), int(cap.value)
 
 
@@ -551,6 +577,60 @@ class Quantifier:
         finally:
             for q in (o_ref, o_start, o_len, o_bc, o_cnt):
                 self.lib.afq_free(q)
+
+    def gpl_hist_rad(self, chunk_bytes, chunk_off, bc_bytes: int = 4, umi_bytes: int = 4, expected_ori="both", d_ptr: int = 0, n_bytes: int = 0):
+        """afq_gpl_hist_rad: the chunks of an uncollated RNA RAD in (host bytes, or d_ptr/n_bytes for bytes already on the device);
+        a dict out: "bc" (the distinct barcodes of the records compatible with expected_ori - "both" / "either", "fw", "rc" - ascending),
+        "count" (u64) and "stats" (n_records, n_compatible, max_ambig, n_long_records).  Position bytes: set_aln_extra_bytes."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        ori = _abi.GPL_ORI[expected_ori.lower()] if isinstance(expected_ori, str) else int(expected_ori)
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p = C.POINTER(C.c_uint64)
+        o_n, o_bc, o_cnt, st = C.c_uint64(), u64p(), u64p(), _abi.AfqGplHistStats()
+        self._check(self.lib.afq_gpl_hist_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), bc_bytes, umi_bytes, ori, on_dev, C.byref(o_n),
+                                              C.byref(o_bc), C.byref(o_cnt), C.byref(st)))
+        n = int(o_n.value)
+        try:
+            mk = lambda p_: (np.ctypeslib.as_array(p_, shape=(n,)).astype(np.uint64, copy=True) if n else np.zeros(0, np.uint64))
+            return {"bc": mk(o_bc), "count": mk(o_cnt), "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_bc, o_cnt):
+                self.lib.afq_free(q)
+
+    def gpl_correct(self, observed, observed_count, retained, retained_count, barcode_len: int, neighborhood="substitution-or-shift-1",
+                    resolution="unique", confidence=(39, 40), pseudocount: int = 1):
+        """afq_gpl_correct: the correction decision of every observed barcode against the retained ones (both ascending, distinct);
+        a dict out: "decision" (u8: _abi.GPL_EXACT ...), "target" (u32 index into retained, GPL_NO_TARGET without one),
+        "target_count" (u64 per retained barcode) and "stats" (the eight CorrectionStats counters)."""
+        obs = np.ascontiguousarray(observed, dtype=np.uint64)
+        oc = np.ascontiguousarray(observed_count, dtype=np.uint64)
+        ret = np.ascontiguousarray(retained, dtype=np.uint64)
+        rc_ = np.ascontiguousarray(retained_count, dtype=np.uint64)
+        if len(obs) != len(oc) or len(ret) != len(rc_):
+            raise ValueError("a barcode list and its counts must have one length")
+        nbh = _abi.GPL_NEIGHBORHOODS[neighborhood] if isinstance(neighborhood, str) else int(neighborhood)
+        res = _abi.GPL_RESOLUTIONS[resolution] if isinstance(resolution, str) else int(resolution)
+        u64p = C.POINTER(C.c_uint64)
+        o_dec, o_tgt, o_tc, st = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)(), u64p(), _abi.AfqGplCorrectionStats()
+        self._check(self.lib.afq_gpl_correct(self._h, obs.ctypes.data_as(u64p), oc.ctypes.data_as(u64p), len(obs), ret.ctypes.data_as(u64p),
+                                             rc_.ctypes.data_as(u64p), len(ret), int(barcode_len), nbh, res, int(confidence[0]), int(confidence[1]),
+                                             int(pseudocount), C.byref(o_dec), C.byref(o_tgt), C.byref(o_tc), C.byref(st)))
+        try:
+            mk = lambda p_, n, dt: (np.ctypeslib.as_array(p_, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt))
+            return {"decision": mk(o_dec, len(obs), np.uint8), "target": mk(o_tgt, len(obs), np.uint32), "target_count": mk(o_tc, len(ret), np.uint64),
+                    "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_dec, o_tgt, o_tc):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def gpl_limits():
+        """The generate-permit-list parse's limits (module-level gpl_limits)."""
+        return gpl_limits()
 
     def atac_dedup_rad(self, chunk_bytes, chunk_off, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0, copy: bool = True):
         """afq_atac_dedup_rad: collated scATAC chunks in (host bytes, or d_ptr/n_bytes for bytes already on the device),

@@ -60,11 +60,12 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
-                                           "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit"};
+                                           "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit",
+                                           "k_gpl_parse", "k_gpl_count", "k_gpl_compact", "k_gpl_table", "k_gpl_correct"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -198,6 +199,16 @@ struct AtacSortBufs {
     }
 };
 
+// afq_gpl_hist_rad's and afq_gpl_correct's
+struct GplBufs {
+    DevBuf chunks, bc, cstat, status, tkey, tcnt, ones, okey, ocnt, nout;            // histogram
+    DevBuf obs, obscnt, ret, retcnt, idx, rkey, rval, dec, tgt, stats, tcount, cstatus;   // correction
+    std::vector<DevBuf*> all() {
+        return {&chunks, &bc, &cstat, &status, &tkey, &tcnt, &ones, &okey, &ocnt, &nout, &obs, &obscnt, &ret, &retcnt, &idx, &rkey, &rval, &dec, &tgt,
+                &stats, &tcount, &cstatus};
+    }
+};
+
 }  // namespace
 
 struct afq_ctx {
@@ -215,6 +226,7 @@ struct afq_ctx {
     DevBuf d_chunk_off, d_hdr;
     AtacBufs atac;
     AtacSortBufs asort;
+    GplBufs gpl;
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
@@ -1728,6 +1740,7 @@ void afq_destroy(afq_ctx* c) {
     for (auto b : bufs) b->release();
     for (DevBuf* b : c->atac.all()) b->release();
     for (DevBuf* b : c->asort.all()) b->release();
+    for (DevBuf* b : c->gpl.all()) b->release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);
@@ -2765,6 +2778,249 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     if (stats) *stats = S;
     H.release();
     *out_n = n_out; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_bc = obc; *out_count = ocnt;
+    return 0;
+}
+
+// `generate-permit-list` on the device (afq_gpl.hip): parse + orientation filter, counting table, compaction; the host sorts the
+// distinct barcodes.  And the correction decisions of distinct observed barcodes against a retained set.
+void afq_gpl_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = 0;
+}
+
+void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity) {
+    const uint64_t cap = gpl_table_capacity(n_kept < (1ull << 30) ? n_kept : (1ull << 30) - 1, valid_width(bc_bytes) ? bc_bytes : 8);   // (afq_gpl_hist_rad refuses 2^30 records and more)
+    if (home_slot) *home_slot = sort_hash_bc(barcode) & (uint32_t)(cap - 1);
+    if (capacity) *capacity = (uint32_t)cap;
+}
+
+int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                     uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, uint64_t* out_n, uint64_t** out_bc, uint64_t** out_count,
+                     afq_gpl_hist_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !out_n || !out_bc || !out_count) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
+    if (!valid_width(umi_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "umi_bytes must be 1, 2, 4 or 8");
+    if (expected_ori > kGplOriRc) return fail(c, AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    // ---- chunk table
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
+    std::vector<SortChunk> chunks(n_chunks);
+    uint64_t n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes + umi_bytes)) return chunk_fault(c, "chunk", i, f);
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    if (n_slots >= (1ull << 30))
+        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1);
+    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 16 a slot of the largest table, 16 a distinct barcode)
+        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, bc_bytes) * 24,
+                       need_misc = nc1 * (sizeof(SortChunk) + 16);
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_gpl_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
+                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables > " +
+                        std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->gpl;
+    HipLatch T;
+    auto hip_fail = [&]() { return T.fail(c, "afq_gpl_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records)"); };
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
+    T(B.ones.ensure(8)); T(B.nout.ensure(4));
+    if (!T.ok()) return hip_fail();
+    const uint8_t* d_bytes = bytes;
+    if (!bytes_on_device) {
+        T(c->d_bytes_own.ensure(n_bytes + 16));
+        if (!T.ok()) return hip_fail();
+        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
+        d_bytes = c->d_bytes_own.as<uint8_t>();
+    }
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.ones.p, 0, 8, s));
+    T(hipMemsetAsync(B.nout.p, 0, 4, s));
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    {
+        ScopedTimer t(c, K_GPL_PARSE, s);
+        launch_gpl_parse(s, GplParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, umi_bytes, c->aln_extra, expected_ori,
+                                         B.bc.as<uint64_t>(), B.cstat.as<uint32_t>(), B.status.as<DevStatus>()});
+    }
+    T(hipGetLastError());
+    DevStatus st{};
+    std::vector<uint32_t> cstat(4ull * n_chunks);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
+    hc.lap("gpl: parse");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) {
+        harvest_timers(c);
+        if (st.err_code == kErrRecordWalk)
+            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(st.err_cell) + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+        return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: device status " + std::to_string(st.err_code));
+    }
+    afq_gpl_hist_stats S{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        S.n_records += cstat[4 * i]; S.n_compatible += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_long_records += cstat[4 * i + 3];
+    }
+    // ---- count, compact
+    const uint64_t cap = gpl_table_capacity(S.n_compatible, bc_bytes);
+    T(B.tkey.ensure(8 * cap)); T(B.tcnt.ensure(8 * cap)); T(B.okey.ensure(4 * cap)); T(B.ocnt.ensure(4 * cap));   // (at most cap / 2 distinct barcodes)
+    if (!T.ok()) return hip_fail();
+    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.tcnt.p, 0, 8 * cap, s));
+    {
+        ScopedTimer t(c, K_GPL_COUNT, s);
+        launch_gpl_count(s, B.chunks.as<SortChunk>(), n_chunks, B.cstat.as<uint32_t>(), B.bc.as<uint64_t>(), B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(),
+                         (uint32_t)(cap - 1), B.ones.as<unsigned long long>(), B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_GPL_COMPACT, s);
+        launch_gpl_compact(s, B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(), cap, B.okey.as<uint64_t>(), B.ocnt.as<uint64_t>(), B.nout.as<uint32_t>());
+    }
+    T(hipGetLastError());
+    uint32_t n_tab = 0;
+    unsigned long long n_ones = 0;
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&n_tab, B.nout.p, 4, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&n_ones, B.ones.p, 8, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: the counting table of " + std::to_string(cap) + " slots ran full (device status " + std::to_string(st.err_code) + ")"); }
+    if (n_tab > cap / 2) return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: " + std::to_string(n_tab) + " keys in a table of " + std::to_string(cap) + " slots");
+    std::vector<std::pair<uint64_t, uint64_t>> pairs((size_t)n_tab + (n_ones ? 1 : 0));
+    {
+        std::vector<uint64_t> k(n_tab), n(n_tab);
+        if (n_tab) {
+            T(hipMemcpyAsync(k.data(), B.okey.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
+            T(hipMemcpyAsync(n.data(), B.ocnt.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
+            T(hipStreamSynchronize(s));
+        }
+        harvest_timers(c);
+        if (!T.ok()) return hip_fail();
+        for (uint32_t i = 0; i < n_tab; ++i) pairs[i] = {k[i], n[i]};
+        if (n_ones) pairs[n_tab] = {kSortEmptyKey, (uint64_t)n_ones};
+    }
+    std::sort(pairs.begin(), pairs.end());
+    hc.lap("gpl: count + compact + sort");
+    uint64_t total = 0;
+    for (const auto& pr : pairs) total += pr.second;
+    if (total != S.n_compatible)
+        return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_compatible) + " compatible records");
+    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    HostOuts H;
+    uint64_t* obc = (uint64_t*)H.mallocd(8 * o1);
+    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
+    if (!obc || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_gpl_hist_rad: host allocation failed (" + std::to_string(16 * o1) + " bytes of histogram)");
+    for (uint64_t i = 0; i < n_out; ++i) { obc[i] = pairs[i].first; ocnt[i] = pairs[i].second; }
+    if (stats) *stats = S;
+    H.release();
+    *out_n = n_out; *out_bc = obc; *out_count = ocnt;
+    return 0;
+}
+
+int afq_gpl_correct(afq_ctx* c, const uint64_t* observed, const uint64_t* obs_count, uint64_t n_obs, const uint64_t* retained, const uint64_t* ret_count,
+                    uint64_t n_ret, uint32_t barcode_len, uint32_t neighborhood, uint32_t resolution, uint64_t conf_num, uint64_t conf_den,
+                    uint64_t pseudocount, uint8_t** out_decision, uint32_t** out_target, uint64_t** out_target_count, afq_gpl_correction_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if (((!observed || !obs_count) && n_obs) || ((!retained || !ret_count) && n_ret) || !out_decision || !out_target || !out_target_count)
+        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (barcode_len < 1 || barcode_len > 32) return fail(c, AFQ_ERR_INVALID_ARG, "barcode length must be between 1 and 32 (got " + std::to_string(barcode_len) + ")");
+    if (neighborhood > kGplShift) return fail(c, AFQ_ERR_INVALID_ARG, "neighborhood must be 0 (hamming-1) or 1 (substitution-or-shift-1)");
+    if (resolution > kGplFrequency) return fail(c, AFQ_ERR_INVALID_ARG, "resolution must be 0 (unique) or 1 (frequency)");
+    if (resolution == kGplFrequency) {
+        if (conf_den == 0 || conf_num > conf_den)
+            return fail(c, AFQ_ERR_INVALID_ARG, "barcode-correction confidence must be between zero and one (got " + std::to_string(conf_num) + "/" + std::to_string(conf_den) + ")");
+        if (pseudocount == 0) return fail(c, AFQ_ERR_INVALID_ARG, "frequency correction requires a non-zero pseudocount");
+        if (pseudocount >= kGplMaxWeight) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: a pseudocount of 2^55 or more");
+    } else { conf_num = 0; conf_den = 1; pseudocount = 0; }
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    if (n_ret >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: 2^30 or more retained barcodes (" + std::to_string(n_ret) + ")");
+    if (n_obs >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: 2^32 or more observed barcodes in one call (" + std::to_string(n_obs) + ")");
+    const uint64_t fit = barcode_len < 32 ? (1ull << (2 * barcode_len)) : 0;   // (0: every u64 fits)
+    for (uint64_t i = 0; i < n_ret; ++i) {
+        if (i && retained[i] <= retained[i - 1]) return fail(c, AFQ_ERR_INVALID_ARG, "retained barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
+        if (fit && retained[i] >= fit) return fail(c, AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(retained[i]) + " does not fit declared length " + std::to_string(barcode_len));
+        if (resolution == kGplFrequency && ret_count[i] >= kGplMaxWeight - pseudocount)
+            return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: retained barcode " + std::to_string(retained[i]) + " has an exact count + pseudocount of 2^55 or more");
+    }
+    for (uint64_t i = 0; i < n_obs; ++i) {
+        if (i && observed[i] <= observed[i - 1]) return fail(c, AFQ_ERR_INVALID_ARG, "observed barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
+        if (fit && observed[i] >= fit) return fail(c, AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(observed[i]) + " does not fit declared length " + std::to_string(barcode_len));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const uint64_t cap = sort_table_capacity(n_ret), no1 = std::max<uint64_t>(n_obs, 1), nr1 = std::max<uint64_t>(n_ret, 1);
+    {
+        const uint64_t need = no1 * 21 + nr1 * 28 + cap * 12;
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_gpl_correct: " + std::to_string(need) + " bytes for " + std::to_string(n_obs) + " observed and " + std::to_string(n_ret) +
+                        " retained barcodes > " + std::to_string(tot) + " bytes of device memory");
+    }
+    std::vector<uint32_t> idx(n_ret);
+    uint32_t ones_idx = kGplNoTarget;
+    for (uint64_t i = 0; i < n_ret; ++i) { idx[i] = (uint32_t)i; if (retained[i] == kSortEmptyKey) ones_idx = (uint32_t)i; }
+    auto& B = c->gpl;
+    HipLatch T;
+    auto hip_fail = [&]() { return T.fail(c, "afq_gpl_correct", " (" + std::to_string(n_obs) + " observed, " + std::to_string(n_ret) + " retained barcodes)"); };
+    T(B.obs.ensure(8 * no1)); T(B.obscnt.ensure(8 * no1)); T(B.ret.ensure(8 * nr1)); T(B.retcnt.ensure(8 * nr1)); T(B.idx.ensure(4 * nr1));
+    T(B.rkey.ensure(8 * cap)); T(B.rval.ensure(4 * cap)); T(B.dec.ensure(no1)); T(B.tgt.ensure(4 * no1)); T(B.stats.ensure(64)); T(B.tcount.ensure(8 * nr1));
+    T(B.cstatus.ensure(sizeof(DevStatus)));
+    if (!T.ok()) return hip_fail();
+    if (n_obs) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_obs, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.obscnt.p, obs_count, 8 * n_obs, hipMemcpyHostToDevice, s)); }
+    if (n_ret) {
+        T(hipMemcpyAsync(B.ret.p, retained, 8 * n_ret, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.retcnt.p, ret_count, 8 * n_ret, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.idx.p, idx.data(), 4 * n_ret, hipMemcpyHostToDevice, s));
+    }
+    T(hipMemsetAsync(B.rkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.stats.p, 0, 64, s));
+    T(hipMemsetAsync(B.tcount.p, 0, 8 * nr1, s));
+    T(hipMemsetAsync(B.cstatus.p, 0, sizeof(DevStatus), s));
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    {
+        ScopedTimer t(c, K_GPL_TABLE, s);
+        launch_sort_table(s, B.ret.as<uint64_t>(), B.idx.as<uint32_t>(), n_ret, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(cap - 1), B.cstatus.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_GPL_CORRECT, s);
+        launch_gpl_correct(s, GplCorrectArgs{B.obs.as<uint64_t>(), B.obscnt.as<uint64_t>(), n_obs, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(cap - 1), ones_idx,
+                                             B.retcnt.as<uint64_t>(), barcode_len, neighborhood, resolution, conf_num, conf_den, pseudocount, B.dec.as<uint8_t>(),
+                                             B.tgt.as<uint32_t>(), B.stats.as<unsigned long long>(), B.tcount.as<unsigned long long>()});
+    }
+    T(hipGetLastError());
+    HostOuts H;
+    uint8_t* odec = (uint8_t*)H.mallocd(no1);
+    uint32_t* otgt = (uint32_t*)H.mallocd(4 * no1);
+    uint64_t* otc = (uint64_t*)H.mallocd(8 * nr1);
+    if (!odec || !otgt || !otc) { (void)hipStreamSynchronize(s); return fail(c, AFQ_ERR_OOM, "afq_gpl_correct: host allocation failed (" + std::to_string(5 * no1 + 8 * nr1) + " bytes of decisions)"); }
+    DevStatus st{};
+    uint64_t cs[8] = {};
+    T(hipMemcpyAsync(&st, B.cstatus.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(cs, B.stats.p, 64, hipMemcpyDeviceToHost, s));
+    if (n_obs) { T(hipMemcpyAsync(odec, B.dec.p, n_obs, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(otgt, B.tgt.p, 4 * n_obs, hipMemcpyDeviceToHost, s)); }
+    T(hipMemcpyAsync(otc, B.tcount.p, 8 * nr1, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
+    harvest_timers(c);
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_gpl_correct: device status " + std::to_string(st.err_code) + " at retained entry " + std::to_string(st.err_cell));
+    if (stats) {
+        stats->exact_distinct = cs[0]; stats->exact_reads = cs[1]; stats->corrected_distinct = cs[2]; stats->corrected_reads = cs[3];
+        stats->ambiguous_distinct = cs[4]; stats->ambiguous_reads = cs[5]; stats->not_found_distinct = cs[6]; stats->not_found_reads = cs[7];
+    }
+    H.release();
+    *out_decision = odec; *out_target = otgt; *out_target_count = otc;
     return 0;
 }
 

@@ -1,8 +1,9 @@
-// afq_cli.cpp — `afquant quant …` and `afquant infer …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
+// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
 // reference) and `alevin-fry infer` (src/main.rs:350-365) in front of afq_quantify() / afq_infer_files()
 // (include/afquant_host.h).  Same spellings and defaults; what the reference refuses (--use-eds, -b with a plain
 // resolution, -d with trivial, --summary-stat without -b) is refused here too, with its message.
 #include <cctype>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,9 @@ static void usage() {
                  "resolutions: trivial cr-like cr-like-em parsimony parsimony-em parsimony-gene parsimony-gene-em\n"
                  "       afquant atac deduplicate -i <input-dir> [-t N] [-d fw|rc] [--device N]\n"
                  "       afquant atac sort -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]\n"
+                 "       afquant generate-permit-list -i <input-dir> -d fw|rc|both|either -o <output-dir> (-k | -e N | -f N | -b FILE | -u FILE [-m MINREADS])\n"
+                 "       [-t N] [--cell-bc-correction unique|frequency] [--cell-bc-neighborhood hamming-1|substitution-or-shift-1|edit-1]\n"
+                 "       [--cell-bc-confidence 0.975|a/b] [--device N] [--fill-bytes BYTES]\n"
                  "       afquant infer -c <geqc_counts.mtx> -e <gene_eqclass.txt.gz> -o <output-dir> [--usa] [--quant-subset FILE] [-t N]\n");
 }
 
@@ -53,6 +57,89 @@ int main(int argc, char** argv) {
         if (!io.count_mat || !io.eq_labels || !io.output_dir) { usage(); return 2; }
         const int rc = afq_infer_files(&io);
         if (rc) { std::fprintf(stderr, "afquant infer failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        return 0;
+    }
+    if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "generate-permit-list") == 0) {
+        std::fprintf(stderr, "afquant: `atac generate-permit-list` is not supported; only `generate-permit-list` for single-barcode RNA RAD files is\n");
+        return 1;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "generate-permit-list") == 0) {   // src/main.rs:170-269, 392-577
+        afq_gpl_opts go{};
+        go.min_reads = 10; go.neighborhood = -1; go.conf_num = 39; go.conf_den = 40;
+        std::string cmdline;
+        for (int i = 0; i < argc; ++i) { if (i) cmdline += ' '; cmdline += argv[i]; }
+        go.cmdline = cmdline.c_str();
+        int n_methods = 0;
+        bool have_ori = false;
+        auto need2 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        auto count_arg = [&](int& i, const char* flag, uint64_t& v) -> bool {
+            const char* t = need2(i);
+            char* e = nullptr;
+            errno = 0;
+            v = std::strtoull(t, &e, 10);
+            if (e == t || *e || errno || t[0] == '-') { std::fprintf(stderr, "error: invalid value '%s' for '%s': invalid digit found in string\n", t, flag); return false; }
+            return true;
+        };
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-i" || a == "--input") go.input_dir = need2(i);
+            else if (a == "-o" || a == "--output-dir") go.output_dir = need2(i);
+            else if (a == "-d" || a == "--expected-ori") {
+                std::string v = need2(i);
+                for (auto& ch : v) ch = (char)std::toupper((unsigned char)ch);
+                if (v == "FW") go.expected_ori = 1; else if (v == "RC") go.expected_ori = 2; else if (v == "BOTH" || v == "EITHER") go.expected_ori = 0;
+                else { std::fprintf(stderr, "error: invalid value '%s' for '--expected-ori <EXPECTEDORI>'\n  [possible values: fw, rc, both, either]\n", argv[i]); return 2; }
+                have_ori = true;
+            }
+            else if (a == "-k" || a == "--knee-distance") { go.method = AFQ_GPL_KNEE; ++n_methods; }
+            else if (a == "-e" || a == "--expect-cells") { go.method = AFQ_GPL_EXPECT; ++n_methods; if (!count_arg(i, "--expect-cells <EXPECTCELLS>", go.method_count)) return 2; }
+            else if (a == "-f" || a == "--force-cells") { go.method = AFQ_GPL_FORCE; ++n_methods; if (!count_arg(i, "--force-cells <FORCECELLS>", go.method_count)) return 2; }
+            else if (a == "-b" || a == "--valid-bc") { go.method = AFQ_GPL_VALID_BC; ++n_methods; go.list_file = need2(i); }
+            else if (a == "-u" || a == "--unfiltered-pl") { go.method = AFQ_GPL_UNFILTERED; ++n_methods; go.list_file = need2(i); }
+            else if (a == "-m" || a == "--min-reads") { if (!count_arg(i, "--min-reads <MINREADS>", go.min_reads)) return 2; }
+            else if (a == "-t" || a == "--threads") go.num_threads = (uint32_t)std::atoi(need2(i));
+            else if (a == "--cell-bc-correction") {
+                const std::string v = need2(i);
+                if (v == "unique") go.frequency = 0; else if (v == "frequency") go.frequency = 1;
+                else { std::fprintf(stderr, "error: invalid value '%s' for '--cell-bc-correction <STRATEGY>'\n  [possible values: unique, frequency]\n", v.c_str()); return 2; }
+            }
+            else if (a == "--cell-bc-neighborhood") {
+                const std::string v = need2(i);
+                if (v == "hamming-1") go.neighborhood = 0; else if (v == "substitution-or-shift-1" || v == "edit-1") go.neighborhood = 1;
+                else { std::fprintf(stderr, "error: invalid value '%s' for '--cell-bc-neighborhood <NEIGHBORHOOD>'\n  [possible values: hamming-1, substitution-or-shift-1, edit-1]\n", v.c_str()); return 2; }
+            }
+            else if (a == "--cell-bc-confidence") {
+                const char* v = need2(i);
+                if (afq_gpl_parse_confidence(v, &go.conf_num, &go.conf_den)) { std::fprintf(stderr, "error: invalid value '%s' for '--cell-bc-confidence <CONFIDENCE>': %s\n", v, afq_host_last_error()); return 2; }
+            }
+            else if (a == "--memory-limit" || a == "--tmp-dir") (void)need2(i);   // accepted and ignored: they size the reference's deferred sample buffers
+            else if (a.rfind("--sample-", 0) == 0) {
+                std::fprintf(stderr, "afquant generate-permit-list: %s is not supported: multi-barcode (--sample-bc-list) input is not supported\n", a.c_str());
+                return 1;
+            }
+            else if (a == "--device") go.device = (uint32_t)std::atoi(need2(i));
+            else if (a == "--fill-bytes") { if (!count_arg(i, "--fill-bytes <BYTES>", go.fill_bytes)) return 2; }   // chunk bytes per device fill (default 8 GiB)
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!go.input_dir || !go.output_dir || !have_ori) {
+            std::fprintf(stderr, "error: the following required arguments were not provided:\n%s%s%s", go.input_dir ? "" : "  --input <INPUT>\n", have_ori ? "" : "  --expected-ori <EXPECTEDORI>\n",
+                         go.output_dir ? "" : "  --output-dir <OUTPUTDIR>\n");
+            usage();
+            return 2;
+        }
+        if (n_methods != 1) {
+            std::fprintf(stderr, n_methods ? "error: the filter methods --knee-distance, --expect-cells, --force-cells, --valid-bc and --unfiltered-pl cannot be used with one another\n"
+                                           : "error: the following required arguments were not provided:\n  <--knee-distance|--expect-cells <EXPECTCELLS>|--force-cells <FORCECELLS>|--valid-bc <VALIDBC>|--unfiltered-pl <UNFILTEREDPL>>\n");
+            usage();
+            return 2;
+        }
+        if (go.method == AFQ_GPL_UNFILTERED && go.min_reads < 1) { std::fprintf(stderr, "min-reads < 1 is not supported, the value %llu was provided\n", (unsigned long long)go.min_reads); return 1; }
+        if (go.num_threads < 2) go.num_threads = 2;   // (minimum: 2; lower values use 2)
+        uint64_t corrected = 0;
+        go.corrected_out = &corrected;
+        const int rc = afq_generate_permit_list(&go);
+        if (rc) { std::fprintf(stderr, "afquant generate-permit-list failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        if (corrected == 0) std::fprintf(stderr, "found 0 corrected barcodes; please check the input.\n");
         return 0;
     }
     if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "deduplicate") == 0) {   // src/main.rs:942-956, atac/run.rs:128-169

@@ -41,6 +41,7 @@
 
 #include "../../include/afquant.h"
 #include "../../include/afquant_host.h"
+#include "afq_gpl_host.h"
 #include "afq_hooks.h"
 
 namespace {
@@ -1628,6 +1629,252 @@ int afq_quantify(const afq_quant_opts* o) {
                      json_escape(o->cmdline ? o->cmdline : "").c_str());
         std::fclose(j);
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// `alevin-fry generate-permit-list` (src/cellfilter.rs:369-780, 1686-1830, 2044-2335; src/barcode_correction.rs; src/knee_finding.rs)
+// for single-barcode RNA RAD files: the record pass and the correction decisions run on the device (afq_gpl_hist_rad,
+// afq_gpl_correct); the retained set, the neighbourhood list and the files are the host's.  All maps are written in ascending
+// key order (the reference writes its hasher's order; readers take the files as maps).
+int afq_gpl_parse_confidence(const char* text, uint64_t* num, uint64_t* den) {
+    std::string e;
+    const int r = afq::gplhost::parse_confidence(text, num, den, e);
+    return r ? hfail(r, e) : 0;
+}
+int64_t afq_gpl_parse_barcode_list(const uint8_t* text, size_t n, int unfiltered, uint32_t barcode_len, uint64_t* out, size_t cap, uint32_t* first_len) {
+    std::string e;
+    const int64_t r = afq::gplhost::parse_barcode_list(text, n, unfiltered, barcode_len, out, cap, first_len, e);
+    return r < 0 ? hfail((int)r, e) : r;
+}
+int64_t afq_gpl_knee(const uint64_t* freq, size_t n) {
+    std::string e;
+    const int64_t r = afq::gplhost::knee(freq, n, e);
+    return r < 0 ? hfail((int)r, e) : r;
+}
+int64_t afq_gpl_select_retained(const uint64_t* bc, const uint64_t* count, size_t n, uint32_t method, uint64_t arg, uint64_t* out, size_t cap) {
+    std::string e;
+    const int64_t r = afq::gplhost::select_retained(bc, count, n, method, arg, out, cap, e);
+    return r < 0 ? hfail((int)r, e) : r;
+}
+int afq_gpl_write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t) {
+    std::string e;
+    const int r = afq::gplhost::write_outputs(o, t, e);
+    return r ? hfail(r, e) : 0;
+}
+
+int afq_generate_permit_list(const afq_gpl_opts* o) {
+    if (!o || !o->input_dir || !o->output_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (o->expected_ori > 2) return hfail(AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
+    if (o->method > AFQ_GPL_UNFILTERED) return hfail(AFQ_ERR_INVALID_ARG, "unknown filter method");
+    if ((o->method == AFQ_GPL_VALID_BC || o->method == AFQ_GPL_UNFILTERED) && !o->list_file) return hfail(AFQ_ERR_INVALID_ARG, "the filter method needs a barcode list file");
+    if (o->method == AFQ_GPL_UNFILTERED && o->min_reads < 1) return hfail(AFQ_ERR_INVALID_ARG, "min-reads < 1 is not supported, the value " + std::to_string(o->min_reads) + " was provided");
+    if (o->neighborhood > 1) return hfail(AFQ_ERR_INVALID_ARG, "unknown barcode neighbourhood; expected hamming-1 or substitution-or-shift-1");
+    uint64_t conf_num = 39, conf_den = 40;
+    if (o->conf_den || o->conf_num) { std::string e; if (int rc = afq::gplhost::confidence_new(o->conf_num, o->conf_den, &conf_num, &conf_den, e)) return hfail(rc, e); }
+    const std::string in = o->input_dir;
+    if (!file_exists(in)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + in + "\" does not exist");
+    MappedFile mf;
+    if (!mf.open(in + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "could not open input rad file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    auto has_tag = [](const std::vector<TagDesc>& v, const char* name) { for (auto& t : v) if (t.name == name) return true; return false; };
+    if (P.file_tag_vals.count("num_barcodes") && P.file_tag_vals["num_barcodes"] > 1)
+        return hfail(AFQ_ERR_UNSUPPORTED, "generate-permit-list: multi-barcode RAD files (--sample-bc-list input, num_barcodes > 1) are not supported");
+    if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len"))
+        return hfail(AFQ_ERR_UNSUPPORTED, "generate-permit-list: this is a scATAC RAD file; `atac generate-permit-list` is not supported");
+    if (P.read_tags.size() != 2 || P.read_tags[0].name != "b" || P.read_tags[1].name != "u" || !P.bc_bytes || !P.umi_bytes)
+        return hfail(AFQ_ERR_UNSUPPORTED, "generate-permit-list: the read-level tags must be the integers (b, u)");
+    uint32_t aln_extra = 0;
+    if (P.aln_tags.size() == 2 && P.aln_tags[1].name == "pos") aln_extra = (uint32_t)int_type_bytes(P.aln_tags[1].type);
+    if (P.aln_tags.empty() || P.aln_tags[0].type != 3 || (P.aln_tags.size() == 2 && !aln_extra) || P.aln_tags.size() > 2)
+        return hfail(AFQ_ERR_UNSUPPORTED, "generate-permit-list: the alignment-level tags must be one u32 (ref | orientation), optionally followed by an integer pos");
+    if (!P.file_tag_vals.count("cblen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain cblen");
+    const uint32_t cblen = (uint32_t)P.file_tag_vals["cblen"];
+    if (cblen < 1 || cblen > 32) return hfail(AFQ_ERR_BAD_INPUT, "barcode length must be between 1 and 32 (got " + std::to_string(cblen) + ")");
+    // ---- the barcode list of -b / -u (plain text or gzip: zlib reads both)
+    std::vector<uint64_t> listed;
+    if (o->method == AFQ_GPL_VALID_BC || o->method == AFQ_GPL_UNFILTERED) {
+        gzFile gz = gzopen(o->list_file, "rb");
+        if (!gz) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't open input barcode file. (") + o->list_file + ")");
+        std::string txt;
+        char buf[1 << 16];
+        int got;
+        while ((got = gzread(gz, buf, sizeof buf)) > 0) txt.append(buf, (size_t)got);
+        gzclose(gz);
+        if (got < 0) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't read line from barcode file. (") + o->list_file + ")");
+        uint32_t first_len = 0;
+        const int unf = o->method == AFQ_GPL_UNFILTERED;
+        const int64_t n = afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), unf, cblen, nullptr, 0, &first_len);
+        if (n < 0) return (int)n;
+        listed.resize((size_t)n);
+        afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), unf, cblen, listed.data(), listed.size(), nullptr);
+        std::sort(listed.begin(), listed.end());
+        listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
+        if (unf && first_len != cblen)
+            std::fprintf(stderr, "The provided permit list had barcodes of length %u, but the mapped reads have barcodes of length %u\n", first_len, cblen);
+        if (unf) for (uint64_t b : listed) if (cblen < 32 && b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    }
+    // ---- the chunk table
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < P.num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    // ---- the record pass: one device fill per run of chunks of at most fill_bytes, the sorted histograms merged
+    const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
+    std::vector<uint64_t> hbc, hcnt;
+    uint64_t n_records = 0, n_compat = 0, max_ambig = 0;
+    for (size_t c0 = 0; c0 < chunk_off.size();) {
+        size_t c1 = c0;
+        uint64_t nrec_sum = 0;
+        auto chunk_end = [&](size_t i) { uint32_t nb; std::memcpy(&nb, rad + chunk_off[i], 4); return chunk_off[i] + nb; };
+        while (c1 < chunk_off.size()) {
+            uint32_t nr; std::memcpy(&nr, rad + chunk_off[c1] + 4, 4);
+            if (c1 > c0 && (chunk_end(c1) - chunk_off[c0] > fill_bytes || nrec_sum + nr >= (1ull << 30))) break;
+            nrec_sum += nr; ++c1;
+        }
+        const uint64_t base = chunk_off[c0];
+        std::vector<uint64_t> rel(c1 - c0);
+        for (size_t i = c0; i < c1; ++i) rel[i - c0] = chunk_off[i] - base;
+        uint64_t n = 0, *bc = nullptr, *cnt = nullptr;
+        afq_gpl_hist_stats st{};
+        rc = afq_gpl_hist_rad(ctx.get(), rad + base, (size_t)(chunk_end(c1 - 1) - base), rel.data(), (uint32_t)rel.size(), P.bc_bytes, P.umi_bytes, o->expected_ori, 0, &n, &bc, &cnt, &st);
+        if (rc) {
+            std::string m = afq_last_error(ctx.get());
+            if (c0 && m.compare(0, 6, "chunk ") == 0) m += " (chunks of this fill are numbered from chunk " + std::to_string(c0) + " of the file)";
+            return hfail(rc, m);
+        }
+        struct Freer { void *a, *b; ~Freer() { afq_free(a); afq_free(b); } } fr{bc, cnt};
+        n_records += st.n_records; n_compat += st.n_compatible; max_ambig = std::max(max_ambig, st.max_ambig);
+        if (hbc.empty()) { hbc.assign(bc, bc + n); hcnt.assign(cnt, cnt + n); }
+        else {   // merge two ascending lists, summing a barcode present in both
+            std::vector<uint64_t> mb, mc;
+            mb.reserve(hbc.size() + n); mc.reserve(hbc.size() + n);
+            size_t i = 0, j = 0;
+            while (i < hbc.size() || j < n) {
+                if (j >= n || (i < hbc.size() && hbc[i] < bc[j])) { mb.push_back(hbc[i]); mc.push_back(hcnt[i]); ++i; }
+                else if (i >= hbc.size() || bc[j] < hbc[i]) { mb.push_back(bc[j]); mc.push_back(cnt[j]); ++j; }
+                else { mb.push_back(hbc[i]); mc.push_back(hcnt[i] + cnt[j]); ++i; ++j; }
+            }
+            hbc.swap(mb); hcnt.swap(mc);
+        }
+        c0 = c1;
+    }
+    std::fprintf(stderr, "observed %llu reads (%llu orientation consistent) in %llu chunks --- max ambiguity read occurs in %llu refs\n", (unsigned long long)n_records,
+                 (unsigned long long)n_compat, (unsigned long long)P.num_chunks, (unsigned long long)max_ambig);
+    if (cblen < 32) for (uint64_t b : hbc) if (b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    auto count_of = [&](uint64_t b) -> uint64_t { auto it = std::lower_bound(hbc.begin(), hbc.end(), b); return it != hbc.end() && *it == b ? hcnt[it - hbc.begin()] : 0; };
+    // ---- the retained set
+    const bool filtered = o->method != AFQ_GPL_UNFILTERED;
+    std::vector<uint64_t> retained;
+    if (o->method == AFQ_GPL_VALID_BC) {
+        retained = listed;
+        for (uint64_t b : retained) if (cblen < 32 && b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    } else if (o->method == AFQ_GPL_UNFILTERED) {
+        uint64_t unmatched_reads = 0;
+        for (size_t i = 0; i < hbc.size(); ++i) if (!std::binary_search(listed.begin(), listed.end(), hbc[i])) unmatched_reads += hcnt[i];
+        if (n_records > 0) {   // check_permit_list_validity (cellfilter.rs:2314-2335; note: over all reads, as the reference)
+            const double f = (double)unmatched_reads / (double)n_records;
+            if (f < 0.3) std::fprintf(stderr, "The percentage of mapped reads not matching a known barcode exactly is %.3f%%, which is < the warning threshold %.3f%%\n", f * 100.0, 30.0);
+            else std::fprintf(stderr, "Percentage of mapped reads not matching a known barcode exaclty (%g%%) is > the suggested fraction (%g%%)\n", f * 100.0, 30.0);
+        } else std::fprintf(stderr, "Cannot determine (likely) valid permit list if not reads are mapped\n");
+        std::fprintf(stderr, "minimum num reads for barcode pass = %llu\n", (unsigned long long)o->min_reads);
+        for (uint64_t b : listed) if (count_of(b) >= o->min_reads) retained.push_back(b);
+        std::fprintf(stderr, "found %zu cells with non-trivial number of reads by exact barcode match\n", retained.size());
+    } else {
+        const int64_t n = afq_gpl_select_retained(hbc.data(), hcnt.data(), hbc.size(), o->method, o->method_count, nullptr, 0);
+        if (n < 0) return (int)n;
+        retained.resize((size_t)n);
+        afq_gpl_select_retained(hbc.data(), hcnt.data(), hbc.size(), o->method, o->method_count, retained.data(), retained.size());
+    }
+    if (filtered) std::fprintf(stderr, "filtering selected %zu retained barcode targets\n", retained.size());
+    std::vector<uint64_t> ret_cnt(retained.size());
+    for (size_t i = 0; i < retained.size(); ++i) ret_cnt[i] = count_of(retained[i]);
+    const uint32_t nbh = o->neighborhood >= 0 ? (uint32_t)o->neighborhood : (filtered ? 1u : 0u);   // prog_opts.rs:135-144
+    if (o->frequency && nbh == 1)
+        std::fprintf(stderr, "cell-barcode Frequency correction is using substitution-or-shift-1. RAD stores no barcode base qualities or indel-error model, so this is an abundance heuristic rather than a calibrated indel posterior.\n");
+    // ---- compile_distinct_observed_with_target_counts (barcode_correction.rs:539-603)
+    uint8_t* dec = nullptr; uint32_t* tgt = nullptr; uint64_t* tcount = nullptr;
+    afq_gpl_correction_stats cs{};
+    rc = afq_gpl_correct(ctx.get(), hbc.data(), hcnt.data(), hbc.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, 1,
+                         &dec, &tgt, &tcount, &cs);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer3 { void *a, *b, *c; ~Freer3() { afq_free(a); afq_free(b); afq_free(c); } } fr3{dec, tgt, tcount};
+    std::vector<uint8_t> has_obs(retained.size(), 0), permitted(retained.size(), 0);
+    std::vector<uint64_t> plan_obs, plan_cor;
+    for (size_t i = 0; i < hbc.size(); ++i) {
+        if (tgt[i] == 0xFFFFFFFFu) continue;
+        permitted[tgt[i]] = 1;   // (the target has an accepted observation: it is in permit_freq)
+        if (dec[i] == 0) has_obs[tgt[i]] = 1;
+    }
+    {   // the observed entries and the identities of never-observed sources, merged in barcode order, restricted to permitted targets
+        size_t r = 0;
+        auto flush_sources = [&](uint64_t below, bool all) {
+            for (; r < retained.size() && (all || retained[r] < below); ++r)
+                if (!has_obs[r]) { ++cs.exact_distinct; if (permitted[r]) { plan_obs.push_back(retained[r]); plan_cor.push_back(retained[r]); } }
+        };
+        for (size_t i = 0; i < hbc.size(); ++i) {
+            flush_sources(hbc[i], false);
+            if (tgt[i] != 0xFFFFFFFFu && permitted[tgt[i]]) { plan_obs.push_back(hbc[i]); plan_cor.push_back(retained[tgt[i]]); }
+        }
+        flush_sources(0, true);
+    }
+    std::vector<uint64_t> freq_bc, freq_cnt;
+    for (size_t r = 0; r < retained.size(); ++r) if (permitted[r]) { freq_bc.push_back(retained[r]); freq_cnt.push_back(tcount[r]); }
+    std::fprintf(stderr, "Cell correction: %llu exact reads, %llu corrected, %llu ambiguous, %llu without a candidate\n", (unsigned long long)cs.exact_reads,
+                 (unsigned long long)cs.corrected_reads, (unsigned long long)cs.ambiguous_reads, (unsigned long long)cs.not_found_reads);
+    // ---- permit_map.bin: the full theoretical neighbourhood (filtered methods), or the observed entries
+    std::vector<uint64_t> map_obs, map_cor;
+    if (filtered) {
+        std::vector<uint64_t> theo;
+        theo.reserve(retained.size() * (1 + 3ull * cblen + 8));
+        for (uint64_t s : retained) { theo.push_back(s); afq::gplhost::gpl_push_neighbors(s, cblen, nbh == 1, theo); }
+        std::sort(theo.begin(), theo.end());
+        theo.erase(std::unique(theo.begin(), theo.end()), theo.end());
+        const std::vector<uint64_t> zeros(theo.size(), 0);
+        uint8_t* d2 = nullptr; uint32_t* t2 = nullptr; uint64_t* c2 = nullptr;
+        rc = afq_gpl_correct(ctx.get(), theo.data(), zeros.data(), theo.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, 1,
+                             &d2, &t2, &c2, nullptr);
+        if (rc) return hfail(rc, afq_last_error(ctx.get()));
+        Freer3 fr4{d2, t2, c2};
+        for (size_t i = 0; i < theo.size(); ++i)
+            if (t2[i] != 0xFFFFFFFFu && permitted[t2[i]]) { map_obs.push_back(theo[i]); map_cor.push_back(retained[t2[i]]); }
+    } else { map_obs = plan_obs; map_cor = plan_cor; }
+    afq_gpl_tables T{};
+    T.barcode_len = cblen; T.neighborhood = nbh; T.frequency = o->frequency ? 1 : 0; T.filtered = filtered ? 1 : 0;
+    T.conf_num = conf_num; T.conf_den = conf_den; T.pseudocount = 1;
+    T.freq_bc = freq_bc.data(); T.freq_count = freq_cnt.data(); T.n_freq = freq_bc.size();
+    static const uint64_t kNone = 0;
+    if (filtered) { T.all_bc = hbc.empty() ? &kNone : hbc.data(); T.all_count = hcnt.empty() ? &kNone : hcnt.data(); T.n_all = hbc.size(); }
+    T.map_obs = map_obs.data(); T.map_cor = map_cor.data(); T.n_map = map_obs.size();
+    T.plan_obs = plan_obs.data(); T.plan_cor = plan_cor.data(); T.n_plan = plan_obs.size();
+    const uint64_t sv[8] = {cs.exact_distinct, cs.exact_reads, cs.corrected_distinct, cs.corrected_reads, cs.ambiguous_distinct, cs.ambiguous_reads, cs.not_found_distinct, cs.not_found_reads};
+    std::memcpy(T.stats, sv, sizeof sv);
+    T.max_ambig = max_ambig;
+    afq_gpl_opts oo = *o;
+    oo.conf_num = conf_num; oo.conf_den = conf_den;
+    rc = afq_gpl_write_outputs(&oo, &T);
+    if (rc) return rc;
+    std::fprintf(stderr, "total number of distinct corrected barcodes : %llu\n", (unsigned long long)cs.corrected_distinct);
+    if (o->corrected_out) *o->corrected_out = cs.corrected_distinct;
     return 0;
 }
 

@@ -241,6 +241,44 @@ void launch_sort_leaves(hipStream_t s, const SortLeaf* leaves, const uint32_t* i
 void launch_sort_emit(hipStream_t s, const SortLeaf* leaves, uint32_t n_leaves, const uint32_t* leaf_out, const uint64_t* i_key, const uint32_t* i_cnt,
                       const uint32_t* bin_base, uint32_t ref_count, const uint64_t* rank_bc, uint32_t* o_ref, uint32_t* o_start, uint16_t* o_flen,
                       uint64_t* o_bc, uint32_t* o_cnt, unsigned long long* n_long);
+// `generate-permit-list`: the barcode histogram of an uncollated RNA RAD and the correction decisions (afq_gpl.hip)
+constexpr uint32_t kGplParseTile = 4096;      // bytes of a chunk a wave stages in LDS per trip
+constexpr uint32_t kGplParseHalo = 256;       // bytes staged behind a tile: the head (at most 4 + 8 + 8) of a record that starts on the tile's last byte, and its first alignments
+constexpr uint32_t kGplLaneAlns = 16;         // a record with more alignments than this has them tested by the whole wave, out of global memory
+constexpr uint32_t kGplOriBoth = 0, kGplOriFw = 1, kGplOriRc = 2;                                   // afq_gpl_hist_rad's expected_ori
+constexpr uint32_t kGplHamming = 0, kGplShift = 1;                                                  // afq_gpl_correct's neighborhood
+constexpr uint32_t kGplUnique = 0, kGplFrequency = 1;                                               // ... resolution
+constexpr uint32_t kGplExact = 0, kGplCorrected = 1, kGplAmbiguous = 2, kGplNotFound = 3;           // ... decisions
+constexpr uint32_t kGplNoTarget = 0xFFFFFFFFu;
+constexpr uint64_t kGplMaxWeight = 1ull << 55;   // exact count + pseudocount stays below this: 499 candidates' weights then sum below 2^64
+// the counting table: home slot = sort_hash_bc(barcode) & (capacity - 1); at most half the slots are taken
+inline uint64_t gpl_table_capacity(uint64_t n_kept, uint32_t bc_bytes) {   // the smallest power of two >= max(2, 2 min(n_kept, 2^(8 bc_bytes)))
+    const uint64_t n = bc_bytes < 8 && n_kept > (1ull << (8 * bc_bytes)) ? (1ull << (8 * bc_bytes)) : n_kept;
+    return sort_table_capacity(n);
+}
+struct GplParseArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks;
+    uint32_t bc_bytes, umi_bytes, aln_extra, expected_ori;
+    uint64_t* o_bc;          // a slot per record of the chunk table: a chunk's compatible records first (chunk_stat[1] of them)
+    uint32_t* chunk_stat;    // [n_chunks][4]: records seen, compatible, largest na among the compatible, long records
+    DevStatus* st;
+};
+struct GplCorrectArgs {
+    const uint64_t* observed; const uint64_t* obs_count; uint64_t n_obs;
+    const uint64_t* tab_key; const uint32_t* tab_val; uint32_t tab_mask; uint32_t ones_idx;   // retained barcode -> its index
+    const uint64_t* ret_count;   // [n_retained] exact counts
+    uint32_t barcode_len, neighborhood, resolution;
+    uint64_t conf_num, conf_den, pseudocount;
+    uint8_t* o_decision; uint32_t* o_target;
+    unsigned long long* stats;          // [8]: (distinct, reads) of exact, corrected, ambiguous, not found
+    unsigned long long* target_count;   // [n_retained]
+};
+void launch_gpl_parse(hipStream_t s, const GplParseArgs& a);
+void launch_gpl_count(hipStream_t s, const SortChunk* chunks, uint32_t n_chunks, const uint32_t* chunk_stat, const uint64_t* bcs, uint64_t* tab_key,
+                      unsigned long long* tab_cnt, uint32_t mask, unsigned long long* ones, DevStatus* st);
+void launch_gpl_compact(hipStream_t s, const uint64_t* tab_key, const unsigned long long* tab_cnt, uint64_t cap, uint64_t* o_key, uint64_t* o_cnt,
+                        uint32_t* n_out);
+void launch_gpl_correct(hipStream_t s, const GplCorrectArgs& a);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

@@ -321,10 +321,35 @@ def encode_atac_chunks(chunks, bc_bytes: int = 4):
     return bytes(out), np.asarray(offs, dtype=np.uint64)
 
 
-def _correction_spec_bytes(barcode_len, spec) -> bytes:
+def encode_chunks(chunks, bc_bytes: int = 4, umi_bytes: int = 4, pos_bytes: int = 0, pad: int = 0):
+    """chunks of an UNCOLLATED single-barcode RNA RAD, as the mapper writes them and generate-permit-list reads them: a list of
+    chunks, each a list of records (bc, umi, [(ref, fw), ...]) - a barcode per record, the orientation in bit 31 of every
+    alignment word (set = forward), pos_bytes zero bytes of position behind each.  `pad` bytes go in front of the first chunk
+    (to place chunks at a chosen byte alignment).  Returns (bytes, chunk_off[u64])."""
+    out = bytearray(pad)
+    offs = []
+    for recs in chunks:
+        offs.append(len(out))
+        body = bytearray()
+        for bc, umi, alns in recs:
+            body += len(alns).to_bytes(4, "little") + int(bc).to_bytes(bc_bytes, "little") + int(umi).to_bytes(umi_bytes, "little")
+            if pos_bytes == 0 and len(alns) > 64:
+                a = np.asarray(alns, dtype=np.int64).reshape(-1, 2)
+                body += ((a[:, 0] & 0x7FFFFFFF) | (a[:, 1].astype(bool).astype(np.int64) << 31)).astype("<u4").tobytes()
+                continue
+            for ref, fw in alns:
+                body += ((int(ref) & 0x7FFFFFFF) | (0x80000000 if fw else 0)).to_bytes(4, "little") + bytes(pos_bytes)
+        out += (len(body) + 8).to_bytes(4, "little") + len(recs).to_bytes(4, "little") + body
+    return bytes(out), np.asarray(offs, dtype=np.uint64)
+
+
+NEIGHBORHOOD_TAGS = {"hamming-1": 0, "substitution-or-shift-1": 1}   # BarcodeNeighborhood's variants in declaration order
+
+
+def _correction_spec_bytes(barcode_len, spec, neighborhood="hamming-1") -> bytes:
     """bincode of CorrectionSpec (src/barcode_correction.rs:28-37, 209-227).  spec: "unique" or
-    ("frequency", (numerator, denominator), pseudocount); the neighbourhood is HammingOne."""
-    out = bytes([barcode_len]) + (0).to_bytes(4, "little")
+    ("frequency", (numerator, denominator), pseudocount); neighborhood: HammingOne (tag 0) or SubstitutionOrShiftOne (tag 1)."""
+    out = bytes([barcode_len]) + NEIGHBORHOOD_TAGS[neighborhood].to_bytes(4, "little")
     if spec == "unique":
         return out + (0).to_bytes(4, "little")
     _, (num, den), pseudo = spec
@@ -337,7 +362,7 @@ def _corrections_bytes(pairs) -> bytes:
 
 
 def correction_plan_bytes(pairs, barcode_len: int = 16, spec="unique", sample_barcode_len=None, sample_scopes=(), version: int = 1,
-                          magic: bytes = b"AFCORR\0\0") -> bytes:
+                          magic: bytes = b"AFCORR\0\0", neighborhood="hamming-1") -> bytes:
     """correction_plan.bin (src/correction_plan.rs:20-45, 157-160): magic, u16 version, bincode of CorrectionPlan with one
     global cell scope holding `pairs` ((observed, corrected), written in observed order as write_to does).  sample_barcode_len /
     sample_scopes ((sample barcode, pairs), ...) make the sample-scoped shapes the ATAC reader refuses."""
@@ -349,7 +374,7 @@ def correction_plan_bytes(pairs, barcode_len: int = 16, spec="unique", sample_ba
     out += len(scopes).to_bytes(8, "little")
     for sb, pp in scopes:
         out += b"\x00" if sb is None else b"\x01" + sb.to_bytes(8, "little")
-        out += _correction_spec_bytes(barcode_len, spec) + _corrections_bytes(pp)
+        out += _correction_spec_bytes(barcode_len, spec, neighborhood) + _corrections_bytes(pp)
     return bytes(out)
 
 
@@ -361,6 +386,67 @@ def permit_map_bytes(pairs) -> bytes:
 def permit_freq_header(barcode_len: int, version: int = 1) -> bytes:
     """permit_freq.bin as far as `atac sort` reads it: u64 version, u64 barcode length, an empty bincode HashMap behind them."""
     return int(version).to_bytes(8, "little") + int(barcode_len).to_bytes(8, "little") + (0).to_bytes(8, "little")
+
+
+def permit_freq_bytes(barcode_len: int, pairs, version: int = 1) -> bytes:
+    """permit_freq.bin / all_freq.bin (write_permit_list_freq, src/utils.rs:431-452): u64 version, u64 barcode length, then the
+    bincode HashMap<u64, u64> barcode -> count (a u64 length and the pairs, here in ascending key order)."""
+    return int(version).to_bytes(8, "little") + int(barcode_len).to_bytes(8, "little") + _corrections_bytes(sorted((int(b), int(n)) for b, n in pairs))
+
+
+def _read_pairs(buf, at):
+    n = int.from_bytes(buf[at:at + 8], "little")
+    at += 8
+    if at + 16 * n > len(buf):
+        raise ValueError("truncated pair list")
+    a = np.frombuffer(buf, dtype="<u8", count=2 * n, offset=at).reshape(-1, 2)
+    return [(int(o), int(c)) for o, c in a], at + 16 * n
+
+
+def read_permit_freq(buf: bytes):
+    """permit_freq.bin / all_freq.bin -> (version, barcode_len, {barcode: count}); the file must tile exactly."""
+    pairs, end = _read_pairs(buf, 16)
+    if end != len(buf) or len(dict(pairs)) != len(pairs):
+        raise ValueError("permit frequency file: trailing data or a repeated key")
+    return int.from_bytes(buf[0:8], "little"), int.from_bytes(buf[8:16], "little"), dict(pairs)
+
+
+def read_permit_map(buf: bytes):
+    """permit_map.bin -> {observed: corrected}; the file must tile exactly."""
+    pairs, end = _read_pairs(buf, 0)
+    if end != len(buf) or len(dict(pairs)) != len(pairs):
+        raise ValueError("permit map: trailing data or a repeated key")
+    return dict(pairs)
+
+
+def read_correction_plan(buf: bytes):
+    """correction_plan.bin with one global cell scope (what generate-permit-list writes for a single-barcode experiment) ->
+    {"barcode_len", "neighborhood", "resolution" ("unique" or ("frequency", (num, den), pseudocount)), "corrections" [(observed,
+    corrected), ...] in file order}; anything else raises."""
+    if buf[:8] != b"AFCORR\0\0" or int.from_bytes(buf[8:10], "little") != 1:
+        raise ValueError("correction plan: bad magic or version")
+    at = 10
+    if buf[at] != 0:
+        raise ValueError("correction plan: sample-scoped")
+    cell_len, has_sspec = buf[at + 1], buf[at + 2]
+    at += 3
+    if has_sspec or int.from_bytes(buf[at:at + 8], "little") != 0 or int.from_bytes(buf[at + 8:at + 16], "little") != 1 or buf[at + 16] != 0:
+        raise ValueError("correction plan: not one global cell scope")
+    at += 17
+    spec_len, nbh, res = buf[at], int.from_bytes(buf[at + 1:at + 5], "little"), int.from_bytes(buf[at + 5:at + 9], "little")
+    at += 9
+    resolution = "unique"
+    if res == 1:
+        num, den, pseudo = (int.from_bytes(buf[at + 8 * k:at + 8 * k + 8], "little") for k in range(3))
+        resolution = ("frequency", (num, den), pseudo)
+        at += 24
+    elif res != 0:
+        raise ValueError("correction plan: unknown resolution")
+    pairs, end = _read_pairs(buf, at)
+    if end != len(buf) or spec_len != cell_len:
+        raise ValueError("correction plan: trailing data or two barcode lengths")
+    names = {v: k for k, v in NEIGHBORHOOD_TAGS.items()}
+    return {"barcode_len": cell_len, "neighborhood": names[nbh], "resolution": resolution, "corrections": pairs}
 
 
 def collation_manifest(groups, level_names=("sample", "cell")) -> bytes:

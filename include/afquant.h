@@ -311,6 +311,61 @@ void afq_atac_sort_leaf_limits(uint32_t out[4]);
 void afq_atac_sort_table_slot(uint64_t barcode, uint64_t n_corrections, uint32_t* home_slot, uint32_t* capacity);
 
 /*
+ * `generate-permit-list`, the device half: the barcode histogram of an UNCOLLATED single-barcode RNA RAD.
+ *
+ * `bytes` / `chunk_off` are the mapper's chunks as for afq_atac_sort_rad; a record is `na u32, barcode (bc_bytes), umi
+ * (umi_bytes), na x (u32 ref | orientation bit 31, + the position bytes of afq_set_aln_extra_bytes)`.  A record counts if it
+ * is compatible with expected_ori (cellfilter.rs:1698-1771 of the reference): 0 = both: always; 1 = fw: some alignment word
+ * has bit 31 set; 2 = rc: some alignment word has bit 31 clear; a record with na == 0 counts only under `both`.
+ *
+ * Out: the distinct barcodes of the compatible records, ascending, with their u64 counts (malloc'd; afq_free), and `stats`.
+ * One call is one fill of the device: a host with a file larger than the device calls once per part and merges the sorted
+ * histograms, summing n_records / n_compatible and taking the largest max_ambig.
+ * Errors: AFQ_ERR_BAD_INPUT "chunk <i>: ..." for a chunk outside the buffer, a record head or an alignment list that runs
+ * past its chunk's end, records that do not tile nbytes or do not number nrec; AFQ_ERR_UNSUPPORTED for 2^30 records or more
+ * in one call; AFQ_ERR_OOM (with the sizes) when input and tables do not fit the device.
+ */
+typedef struct afq_gpl_hist_stats {
+    uint64_t n_records;      /* records of the chunks                                                            */
+    uint64_t n_compatible;   /* ... compatible with expected_ori (= the sum of the counts)                       */
+    uint64_t max_ambig;      /* the largest na among the COMPATIBLE records (`max-ambig-record`)                 */
+    uint64_t n_long_records; /* records whose alignment words the whole wave tested out of global memory: more than
+                                afq_gpl_limits()[2] alignments, under fw / rc                                       */
+} afq_gpl_hist_stats;
+int afq_gpl_hist_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                     uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, uint64_t* out_n, uint64_t** out_bc, uint64_t** out_count,
+                     afq_gpl_hist_stats* stats);
+/*
+ * `generate-permit-list`, the correction decisions (CorrectionIndex::resolve, barcode_correction.rs:427-474, 659-704, for
+ * retained sources that are their own canonical target): for every observed barcode, against the retained barcodes with their
+ * exact counts.  Both lists ascend without duplicates (else AFQ_ERR_INVALID_ARG); every barcode fits 2 * barcode_len bits
+ * (else AFQ_ERR_BAD_INPUT); barcode_len is 1..32.  neighborhood: 0 = hamming-1, 1 = substitution-or-shift-1.  resolution:
+ * 0 = unique (confidence and pseudocount are ignored), 1 = frequency: a candidate's weight is exact count + pseudocount
+ * (pseudocount >= 1), the winner is the greatest (weight, target), accepted iff winner / total >= conf_num / conf_den exactly.
+ * That test is winner * conf_den >= conf_num * total in 128 bits: both products of two u64 fit, and winner and total fit a u64
+ * because every weight is kept below 2^55 (a larger exact count + pseudocount is AFQ_ERR_UNSUPPORTED) and an observed barcode
+ * has at most 3 * 32 + 31 * 13 = 499 candidates.  So every conf_den != 0 with conf_num <= conf_den serves; others are
+ * AFQ_ERR_INVALID_ARG.
+ * Out (malloc'd; afq_free): decision[n_observed] (0 exact, 1 corrected, 2 ambiguous, 3 not found), target[n_observed] (index
+ * into `retained`, 0xFFFFFFFF without one), target_count[n_retained] (the sum of the accepted observations' counts), `stats`.
+ * The full theoretical neighbourhood of permit_map.bin is the same call with the neighbours as `observed` and counts of 0.
+ */
+typedef struct afq_gpl_correction_stats {
+    uint64_t exact_distinct, exact_reads, corrected_distinct, corrected_reads, ambiguous_distinct, ambiguous_reads, not_found_distinct, not_found_reads;
+} afq_gpl_correction_stats;
+int afq_gpl_correct(afq_ctx* ctx, const uint64_t* observed, const uint64_t* observed_count, uint64_t n_observed, const uint64_t* retained,
+                    const uint64_t* retained_count, uint64_t n_retained, uint32_t barcode_len, uint32_t neighborhood, uint32_t resolution,
+                    uint64_t conf_num, uint64_t conf_den, uint64_t pseudocount, uint8_t** out_decision, uint32_t** out_target,
+                    uint64_t** out_target_count, afq_gpl_correction_stats* stats);
+/* out[0] = bytes of a chunk the GPL parse stages per trip, out[1] = bytes staged behind them (they hold the widest head and
+ * out[2] of the widest alignments), out[2] = a record with more alignments than this is a long record, out[3] = 0.  For tests. */
+void afq_gpl_limits(uint32_t out[4]);
+/* The counting table afq_gpl_hist_rad builds for n_kept compatible records of bc_bytes-wide barcodes: its capacity (the smallest
+ * power of two >= max(2, 2 * min(n_kept, 2^(8 bc_bytes))); open addressing, the next slot modulo the capacity on a collision)
+ * and the home slot of `barcode` in it.  For tests.  Either pointer may be NULL. */
+void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity);
+
+/*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the
  * number of kernels, or a negative error.  `name[i]` points to static storage.

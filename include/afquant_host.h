@@ -87,6 +87,59 @@ typedef struct afq_atac_sort_opts {
 /* Runs the whole `atac sort` sub-command (src/atac/sort.rs:170-895): the coordinate-sorted, de-duplicated BED of an uncollated RAD. */
 int afq_atac_sort(const afq_atac_sort_opts* opts);
 
+/* The options of `alevin-fry generate-permit-list` (src/main.rs:170-269, 392-577; GenPermitListOpts, src/prog_opts.rs:86-160) for
+ * single-barcode RNA RAD files.  Exactly one filter method is given. */
+enum { AFQ_GPL_KNEE = 0, AFQ_GPL_EXPECT = 1, AFQ_GPL_FORCE = 2, AFQ_GPL_VALID_BC = 3, AFQ_GPL_UNFILTERED = 4 };
+typedef struct afq_gpl_opts {
+    const char* input_dir;      /* -i : directory holding the mapper's map.rad                                             */
+    const char* output_dir;     /* -o                                                                                      */
+    uint32_t expected_ori;      /* -d : 0 both / either, 1 fw, 2 rc                                                        */
+    uint32_t method;            /* AFQ_GPL_*: -k, -e N, -f N, -b FILE, -u FILE                                             */
+    uint64_t method_count;      /* N of -e / -f                                                                            */
+    const char* list_file;      /* FILE of -b / -u                                                                         */
+    uint64_t min_reads;         /* -m (with -u; at least 1)                                                                */
+    uint32_t frequency;         /* --cell-bc-correction frequency (else unique)                                            */
+    int32_t neighborhood;       /* --cell-bc-neighborhood: -1 = by method (prog_opts.rs:135-144), 0 hamming-1, 1 substitution-or-shift-1 */
+    uint64_t conf_num, conf_den;/* --cell-bc-confidence, reduced (afq_gpl_parse_confidence); 0/0 = 39/40                   */
+    uint32_t num_threads;       /* -t : recorded in generate_permit_list.json; the device reads the records                */
+    uint32_t device;
+    const char* cmdline;        /* recorded in generate_permit_list.json                                                   */
+    uint64_t fill_bytes;        /* chunk bytes per device fill (0 = 8 GiB); a larger map.rad is read in several fills whose
+                                   sorted histograms are merged                                                            */
+    uint64_t* corrected_out;    /* optional: the number of distinct corrected barcodes                                     */
+} afq_gpl_opts;
+/* Runs the whole sub-command: permit_freq.bin, all_freq.bin (filtered methods), permit_map.bin, correction_plan.bin and
+ * generate_permit_list.json in output_dir.  ATAC and multi-barcode preludes are AFQ_ERR_UNSUPPORTED, named in the message. */
+int afq_generate_permit_list(const afq_gpl_opts* opts);
+
+/* ---- generate-permit-list pieces for the CPU tests (no GPU needed) ---- */
+/* Confidence::from_str (barcode_correction.rs:166-197): a decimal of at most 18 fractional digits or `a/b`, reduced exactly. */
+int afq_gpl_parse_confidence(const char* text, uint64_t* num, uint64_t* den);
+/* A barcode list file's text.  unfiltered != 0 (-u, cellfilter.rs:77-106): every line has one length (else an error), a line that is
+ * not a full valid k-mer contributes nothing, *first_len receives the length of the first line.  unfiltered == 0 (-b,
+ * cellfilter.rs:1832-1847): the first valid barcode_len-mer of every line; a line without one is an error.  Returns the number of
+ * barcodes (file order, duplicates kept) or a negative error; out may be NULL to size, else at most cap are written. */
+int64_t afq_gpl_parse_barcode_list(const uint8_t* text, size_t n, int unfiltered, uint32_t barcode_len, uint64_t* out, size_t cap, uint32_t* first_len);
+/* get_knee (knee_finding.rs:99-139) of descending frequencies, in double without contraction; the reference's panics are
+ * AFQ_ERR_BAD_INPUT with its sentence. */
+int64_t afq_gpl_knee(const uint64_t* freq_desc, size_t n);
+/* select_retained_barcodes (cellfilter.rs:740-780) for AFQ_GPL_KNEE / EXPECT / FORCE / UNFILTERED (threshold = arg) over a histogram
+ * with ascending barcodes; writes the retained barcodes ascending (at most cap), returns their number or a negative error. */
+int64_t afq_gpl_select_retained(const uint64_t* bc, const uint64_t* count, size_t n, uint32_t method, uint64_t arg, uint64_t* out, size_t cap);
+/* The five output files from finished tables (all lists ascending by their first column): freq = permit_freq.bin's map,
+ * all_freq (NULL: not written), map = permit_map.bin's pairs, plan = correction_plan.bin's entries; stats[8] in CorrectionStats order. */
+typedef struct afq_gpl_tables {
+    uint32_t barcode_len, neighborhood, frequency; uint32_t filtered;
+    uint64_t conf_num, conf_den, pseudocount;
+    const uint64_t *freq_bc, *freq_count; uint64_t n_freq;
+    const uint64_t *all_bc, *all_count; uint64_t n_all;
+    const uint64_t *map_obs, *map_cor; uint64_t n_map;
+    const uint64_t *plan_obs, *plan_cor; uint64_t n_plan;
+    uint64_t stats[8];
+    uint64_t max_ambig;
+} afq_gpl_tables;
+int afq_gpl_write_outputs(const afq_gpl_opts* opts, const afq_gpl_tables* t);
+
 /* Runs the whole `quant` sub-command.  Returns 0 or a negative AFQ_ERR_* code; message via afq_host_last_error(). */
 int afq_quantify(const afq_quant_opts* opts);
 const char* afq_host_last_error(void);
