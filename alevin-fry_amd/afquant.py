@@ -45,6 +45,7 @@ class WorkerConfig:
     em_init_uniform: bool = False
     bc_bytes: int = 4
     umi_bytes: int = 4
+    bc_split: int = 0  # multi-barcode records of unequal widths: bytes of b0, the first of the two integers in the bc_bytes field (0: one integer)
     umi_len: int = 0  # UMI length in bases if known (RAD file tag ulen); 0 = unknown
     dump_eq: bool = False  # -d: keep each cell's gene-level equivalence classes (QuantResult.eqclasses; -em resolutions)
     num_bootstraps: int = 0  # -b: bootstrap replicates per non-tiny cell (QuantResult.bootstraps; -em resolutions)
@@ -76,6 +77,7 @@ class WorkerConfig:
         c.em_init_uniform = int(self.em_init_uniform)
         c.bc_bytes = self.bc_bytes
         c.umi_bytes = self.umi_bytes
+        c.bc_split = int(self.bc_split)
         c.profile = int(self.profile)
         c.umi_len = int(self.umi_len)
         c.dump_eq = 1 if self.dump_eq else 0

@@ -1248,7 +1248,7 @@ int afq_quantify(const afq_quant_opts* o) {
     } else if (has_aln_tag("type") && has_aln_tag("start_pos") && has_aln_tag("frag_len")) {
         return hfail(AFQ_ERR_UNSUPPORTED, "To process atac-seq data, you should use the \"atac\" sub-command");   // quant.rs:1973-1976
     }
-    uint32_t w_sample = 0, cblen = 0, bc_split = 0;
+    uint32_t w_sample = 0, w_b0 = 0, w_b1 = 0, cblen = 0, bc_split = 0;
     if (multi_bc) {
         if (P.file_tag_vals["num_barcodes"] != 2 || P.read_tags.size() != 3 || P.read_tags[0].name != "b0" || P.read_tags[1].name != "b1" || P.read_tags[2].name != "u")
             return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: only two barcode levels with read tags (b0, b1, u) are supported");
@@ -1257,7 +1257,7 @@ int afq_quantify(const afq_quant_opts* o) {
         if (!w0 || !w1 || w0 > 4 || w1 > 4 || !P.umi_bytes) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: b0 and b1 must be integers of 1, 2 or 4 bytes (u8/u16/u32)");
         // A RAD writer picks the narrowest integer per barcode length (an 8-nt sample barcode is a u16, a 16-nt cell barcode a
         // u32): unequal widths go to the library as a split barcode field, which it rewrites with two dwords (afq_config.bc_split)
-        P.bc_bytes = w0 + w1;
+        P.bc_bytes = w0 + w1; w_b0 = w0; w_b1 = w1;
         if (w0 != w1) { bc_split = w0; w_sample = 4; } else w_sample = w0;
         if (!P.file_tag_vals.count("b1len")) return hfail(AFQ_ERR_BAD_INPUT, "multi-barcode RAD file should have a \"b1len\" file-level tag");
         cblen = (uint32_t)P.file_tag_vals["b1len"];
@@ -1291,7 +1291,17 @@ int afq_quantify(const afq_quant_opts* o) {
         if (nr == 0 || nb < 8 + rec_hdr) return hfail(AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(chunk_off.size()) + " holds no record");   // (quant.rs:756 panics)
         chunk_off.push_back(p); chunk_nb.push_back(nb); chunk_nr.push_back(nr); p += nb;
     }
-    auto cell_key_of = [&](uint64_t raw_bc) -> uint64_t { return multi_bc ? raw_bc >> (8 * w_sample) : raw_bc; };
+    // Two layouts of one multi-barcode pair.  The key the LIBRARY REPORTS holds b0 in its low w_sample bytes and b1 above them
+    // (unequal widths: after the library's rewrite, b1 << 32 | b0).  The BYTES OF THE FILE hold b0 in w_b0 bytes and b1 in the
+    // w_b1 bytes behind them, whatever the widths.  cell_key_of takes a reported key and nothing else; file_cell_key_of reads the
+    // record's barcode field itself, so that no caller shifts one layout by the other's width.
+    auto cell_key_of = [&](uint64_t reported_bc) -> uint64_t { return multi_bc ? reported_bc >> (8 * w_sample) : reported_bc; };
+    auto file_cell_key_of = [&](const uint8_t* bc_field) -> uint64_t {
+        uint64_t v = 0;
+        if (!multi_bc) { std::memcpy(&v, bc_field, P.bc_bytes); return v; }
+        std::memcpy(&v, bc_field + w_b0, w_b1);
+        return v;
+    };
     // --quant-subset (src/quant.rs:1523-1536, 1776): the first record's collate key decides
     size_t subset_size = 0;
     if (o->filter_list) {
@@ -1302,7 +1312,7 @@ int afq_quantify(const afq_quant_opts* o) {
         subset_size = keep.size();
         std::vector<uint64_t> kept, kept_nb;
         std::vector<uint32_t> kept_nr;
-        for (size_t i = 0; i < chunk_off.size(); ++i) { uint64_t bc = 0; std::memcpy(&bc, rad.data() + chunk_off[i] + 8 + 4, P.bc_bytes); if (keep.count(cell_key_of(bc))) { kept.push_back(chunk_off[i]); kept_nb.push_back(chunk_nb[i]); kept_nr.push_back(chunk_nr[i]); } }
+        for (size_t i = 0; i < chunk_off.size(); ++i) { if (keep.count(file_cell_key_of(rad.data() + chunk_off[i] + 8 + 4))) { kept.push_back(chunk_off[i]); kept_nb.push_back(chunk_nb[i]); kept_nr.push_back(chunk_nr[i]); } }
         chunk_off.swap(kept); chunk_nb.swap(kept_nb); chunk_nr.swap(kept_nr);
     }
     // transcript-to-gene map (src/utils.rs:487-662)

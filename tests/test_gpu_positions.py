@@ -222,12 +222,12 @@ def test_set_aln_extra_bytes_states(oracle):
     finally:
         q.close()
     assert_same_result(got, twin)
-    # multi-barcode records of unequal widths (afq_config.bc_split, which WorkerConfig does not carry) with positions
+    # multi-barcode records of unequal widths (afq_config.bc_split) with positions
     import ctypes as C
 
     lib = pkg.load_library()
-    ccfg = cfg_for(s, "cr-like").to_c()
-    ccfg.bc_bytes, ccfg.bc_split = 6, 2
+    ccfg = cfg_for(s, "cr-like", bc_bytes=6, bc_split=2).to_c()
+    assert (ccfg.bc_bytes, ccfg.bc_split) == (6, 2)
     t2g = np.ascontiguousarray(s.tid_to_gid, np.uint32)
     h = C.c_void_p()
     assert lib.afq_create(C.byref(ccfg), t2g.ctypes.data_as(C.POINTER(C.c_uint32)), len(t2g), 0, C.byref(h)) == 0
