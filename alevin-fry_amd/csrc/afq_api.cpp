@@ -432,7 +432,7 @@ P2Small p2_small_layout(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_p
 uint64_t p2_small_bytes(uint64_t n, uint64_t parts, uint64_t tiles, uint64_t n_pug) { return 4 * p2_small_layout(n, parts, tiles, n_pug).words + 64; }
 
 #ifndef AFQ_TAPER_CR
-#define AFQ_TAPER_CR 0.363, 0.606, 0.769, 0.878, 0.951, 1.0, 1.0, 1.0   // (measurement builds override the cr-like taper: eight cumulative shares)
+#define AFQ_TAPER_CR 0.3007, 0.5277, 0.6991, 0.8285, 0.9262, 1.0, 1.0, 1.0   // (measurement builds override the cr-like taper: eight cumulative shares)
 #endif
 // Split the batch into ranges of cells that fit the memory budget, build nothing yet.
 int plan_ranges(afq_ctx* c) {
@@ -511,6 +511,9 @@ int plan_ranges(afq_ctx* c) {
     // (round 11, cr-like: the rows cross on the copy stream back to back from the end of the first range's kernels on, so the step is
     //  the longer of front + kernels(0) + all rows and front + all kernels + the last range's rows; the two meet at a first range of
     //  0.36 of the work: ratio 0.67, six ranges.  10.29-10.33 -> 10.12-10.17 ms against the ratio-0.6 table, profiles/r11_bench.txt)
+    // (round 17, cr-like: the decoder's kernels are 0.5 ms a step shorter, the rows as long as they were, so the two sides meet at a
+    //  smaller first range: 0.30 of the work, ratio 0.755, six ranges.  9.41-9.44 -> 9.22-9.29 ms against the 0.363 table, with 0.333
+    //  in between at 9.32-9.36, profiles/r17_bench.txt)
     static const double kTaperCr[] = {AFQ_TAPER_CR}, kTaperPug[] = {0.40, 0.76, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
     const double* kTaper = pug_res ? kTaperPug : kTaperCr;
     const size_t kTaperN = 8;

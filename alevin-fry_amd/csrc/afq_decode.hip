@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "afq_common.h"
+#include "afq_decode_span.h"
 #include "afq_hooks.h"
 #include "afq_kernels.h"
 #include "afq_prims.h"
@@ -1434,7 +1435,29 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
     };
 
     load_cell(SC ? my_cell : __builtin_amdgcn_readlane(my_cell, 0));
-    if (!SC || slab_a < slab_b) issue_slab_loads((slab_a - sp0) * kSlabWords);
+    // The scattering instance's wave requests its whole span here - every row its slabs will stage, afq_decode_span.h - and the slab
+    // loop holds no load of input rows: with a slab's rows requested a slab ahead, the record loop's first wait for its gathers was a
+    // wait for those rows as well (the counter retires loads in order), one exposed trip to memory a slab.  All waves but the one that
+    // holds the chunk's end take the straight-line loads.
+    constexpr uint32_t kSpanRows = SC ? span_max_rows(kDtileSlabs) : 1;
+    static_assert(!SC || (kSlabWords == kSpanSlabWords && kStage == kSlabWords + kSpanRowWords), "afq_decode_span.h counts these rows");
+    static_assert(!SC || kSpanRows <= 17, "a wave keeps its span in registers: more than four slabs a wave do not fit seven workgroups per CU");
+    [[maybe_unused]] uint32_t SP[kSpanRows];
+    if constexpr (SC) {
+        const uint32_t first = (slab_a - sp0) * kSlabWords, n_mine = slab_b - slab_a;
+        if (span_is_whole(nwords, first, n_mine, kDtileSlabs)) {
+            // (one address, at the span's middle row: every row is an immediate offset from it)
+            const uint32_t* mid = W + (first + (kSpanRows / 2) * kSpanRowWords + lane);
+#pragma unroll
+            for (int r = 0; r < (int)kSpanRows; ++r) SP[r] = mid[(r - (int)(kSpanRows / 2)) * (int)kSpanRowWords];
+        } else {
+#pragma unroll
+            for (uint32_t r = 0; r < kSpanRows; ++r) {
+                const SpanLoad ld = span_load(nwords, first, n_mine, r, lane);
+                SP[r] = ld.load ? W[ld.index] : 0u;
+            }
+        }
+    } else issue_slab_loads((slab_a - sp0) * kSlabWords);
     [[maybe_unused]] TileOut to{};
     if constexpr (SC) {
         to.k1 = in_vgpr(so.keys1 + m.k1_off);
@@ -1447,14 +1470,19 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         to.bc = in_vgpr(bc_out + my_cell);
     }
 
-    bool halo_is_row0 = false;
+    [[maybe_unused]] bool halo_is_row0 = false;
     for (uint32_t slab = slab_a; slab < slab_b; ++slab) {
         const uint32_t s0 = (slab - sp0) * kSlabWords;
-        // a slab that follows one of its own cell finds its first row staged as that slab's halo (the same word, or the same zero
-        // fill past nwords): it was not loaded again, and is not kept in a register over the records either
-        if (halo_is_row0) R[0] = stage[kSlabWords + lane];
+        if constexpr (SC) {   // (the slab's rows are the span's first five)
 #pragma unroll
-        for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = R[r];
+            for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = SP[r];
+        } else {
+            // a slab that follows one of its own cell finds its first row staged as that slab's halo (the same word, or the same zero
+            // fill past nwords): it was not loaded again, and is not kept in a register over the records either
+            if (halo_is_row0) R[0] = stage[kSlabWords + lane];
+#pragma unroll
+            for (int r = 0; r < 5; ++r) stage[r * 64 + lane] = R[r];
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1462,7 +1490,7 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
         // (a scattering tile is slabs of one cell: the next slab, where there is one, is the cell's own)
         const uint32_t next_cell = !SC && has_next ? __builtin_amdgcn_readlane(my_cell, (int)(slab + 1 - slab_a)) : cur_cell;
         const bool same_next = has_next && next_cell == cur_cell;
-        if (same_next) issue_slab_loads(s0 + kSlabWords, 1);
+        if constexpr (!SC) { if (same_next) issue_slab_loads(s0 + kSlabWords, 1); }
 
         const bool triv = TRIVIAL && m.mode == kModeTrivial;  // tiny cells of a trivial run are cr-like (quant.rs:794-938)
         const bool room = nwords >= 2 + HW;
@@ -1667,8 +1695,11 @@ __global__ __launch_bounds__(256, decode_recs_occupancy(BINS)) void k_decode_rec
                 load_cell(next_cell);
                 issue_slab_loads((slab + 1 - sp0) * kSlabWords);
             }
+            halo_is_row0 = same_next;
+        } else {   // the next slab's rows move to the front of the span
+#pragma unroll
+            for (uint32_t r = 0; r + kSpanSlabRows < kSpanRows; ++r) SP[r] = in_vgpr(SP[r + kSpanSlabRows]);   // (in_vgpr: the moves stay in this block, behind the records)
         }
-        halo_is_row0 = same_next;
     }
     flush_chk();
     if constexpr (SC) scatter_tail<BINS>(m, s_keys, &s_stage[0][0], kOwnBase ? s_base_own : &s_stage[0][0] + BINS / 2, s_misc, to);
