@@ -126,3 +126,13 @@ def big_cells(seed):
 
 def workload(seed):
     return tailed(seed) if seed >= 2000 else big_cells(seed)
+
+
+def with_random_orientation(w, seed):
+    """The workload with bit 31 of every alignment word drawn by a seeded coin (tests/ori_cases.py): `quant` never reads the
+    orientation, so the rows are those of the bytes as built."""
+    from ori_cases import reorient
+
+    w.data = reorient(w.data, w.chunk_off, "random", 4, 4, seed=seed)
+    w.what += " random orientation bits"
+    return w

@@ -271,14 +271,8 @@ def _umi_neighbours(u, length):
     return out
 
 
-@pytest.mark.parametrize("usa", [False, True])
-@pytest.mark.parametrize("res", ["parsimony-em", "parsimony-gene-em", "parsimony"])
-def test_classes_of_more_than_64_genes(oracle, res, usa):
-    """A read that hits a large gene family gives a molecule whose gene label has more entries than the device carries in
-    registers (64).  Without an EM such a molecule is dropped like any multi-gene one; with an EM it is a class of the
-    cell and has to come out whole - from every place a molecule is emitted: lone vertices, two-vertex components, the
-    eight-to-a-wave cover (3..8 vertices), the wave cover (9..64), the workgroup cover (> 64) and, in the last cell,
-    the winner-take-all fallback above --large-graph-thresh with its tie sets."""
+def wide_label_cells(usa):
+    """The cells of test_classes_of_more_than_64_genes: (cells, t2g, num_gene_ids, num_rows)."""
     L = 12
     n_genes = 220
     t2g, num_gene_ids, num_rows = synth.make_t2g(n_genes, 2, usa)
@@ -314,6 +308,18 @@ def test_classes_of_more_than_64_genes(oracle, res, usa):
     us = {c, *nb, *_umi_neighbours(nb[0], L), *_umi_neighbours(nb[20], L)}
     reads = [(u, wide1) for u in sorted(us)] + [(c, wide1)] * 5 + [(u, short()) for u in far_umis(150)]
     cells.append((13, reads))
+    return cells, t2g, num_gene_ids, num_rows
+
+
+@pytest.mark.parametrize("usa", [False, True])
+@pytest.mark.parametrize("res", ["parsimony-em", "parsimony-gene-em", "parsimony"])
+def test_classes_of_more_than_64_genes(oracle, res, usa):
+    """A read that hits a large gene family gives a molecule whose gene label has more entries than the device carries in
+    registers (64).  Without an EM such a molecule is dropped like any multi-gene one; with an EM it is a class of the
+    cell and has to come out whole - from every place a molecule is emitted: lone vertices, two-vertex components, the
+    eight-to-a-wave cover (3..8 vertices), the wave cover (9..64), the workgroup cover (> 64) and, in the last cell,
+    the winner-take-all fallback above --large-graph-thresh with its tie sets."""
+    cells, t2g, num_gene_ids, num_rows = wide_label_cells(usa)
     b, off = rad.encode_cells(cells, 4, 4)
     cfg = pkg.WorkerConfig.for_resolution(res, usa_mode=usa, num_genes=num_gene_ids, num_rows=num_rows, small_thresh=0)
     got, want = run_both(oracle, cfg, t2g, b, off)
@@ -474,15 +480,8 @@ def _grid_component(n, t, hi):
     return out
 
 
-@pytest.mark.parametrize("thresh", [0, 60, 8])
-@pytest.mark.parametrize("res,usa", [("parsimony", False), ("parsimony-em", True)])
-def test_component_sizes_at_every_boundary_of_the_flat_build(oracle, res, usa, thresh):
-    """csrc/afq_pugflat.hip sorts a range's components by size into the covers' lists: 2 vertices (k_pc_pairs), 3..4 (a lane each,
-    k_pc_lane4 - the ones with a label of more than four refs go to its eight-lane list), 5..8 (k_pc_tiny8), 9..64 (k_pc_mid, a wave
-    each), more than 64 (the whole cell to the per-cell kernels) and, above --large-graph-thresh, the winner-take-all fallback.
-    One component of every size on both sides of each boundary, alone in a small cell, all of them in one cell, and all of them in a
-    cell of three tiles whose records are shuffled (class first appearance = the tie-break order); --large-graph-thresh at its
-    default, at 60 (the 63..100-vertex components fall back) and at 8."""
+def component_size_cells(usa):
+    """The cells of test_component_sizes_at_every_boundary_of_the_flat_build: (cells, t2g, G)."""
     rng = np.random.default_rng(77)
     sizes = [2, 3, 4, 5, 8, 9, 16, 63, 64, 65, 100]
     comps = [_grid_component(n, 8 * k, (k + 1) << 26 if k % 2 else 0) for k, n in enumerate(sizes)]   # (a transcript block of its own per component: no edges between them)
@@ -496,9 +495,22 @@ def test_component_sizes_at_every_boundary_of_the_flat_build(oracle, res, usa, t
     cells.append((301, recs_of(comps[:9])))           # (no component beyond 64 vertices: the cell stays with the flat build)
     cells.append((302, recs_of(comps, filler=9000)))
     cells.append((303, recs_of(comps[:9], filler=9000)))
-    b, off = rad.encode_cells(cells, 4, 4)
     G = n_t // 2
     t2g = (np.arange(n_t, dtype=np.uint32) // 2 * 2 + (np.arange(n_t, dtype=np.uint32) & 1)) if usa else np.arange(n_t, dtype=np.uint32) // 2
+    return cells, t2g, G
+
+
+@pytest.mark.parametrize("thresh", [0, 60, 8])
+@pytest.mark.parametrize("res,usa", [("parsimony", False), ("parsimony-em", True)])
+def test_component_sizes_at_every_boundary_of_the_flat_build(oracle, res, usa, thresh):
+    """csrc/afq_pugflat.hip sorts a range's components by size into the covers' lists: 2 vertices (k_pc_pairs), 3..4 (a lane each,
+    k_pc_lane4 - the ones with a label of more than four refs go to its eight-lane list), 5..8 (k_pc_tiny8), 9..64 (k_pc_mid, a wave
+    each), more than 64 (the whole cell to the per-cell kernels) and, above --large-graph-thresh, the winner-take-all fallback.
+    One component of every size on both sides of each boundary, alone in a small cell, all of them in one cell, and all of them in a
+    cell of three tiles whose records are shuffled (class first appearance = the tie-break order); --large-graph-thresh at its
+    default, at 60 (the 63..100-vertex components fall back) and at 8."""
+    cells, t2g, G = component_size_cells(usa)
+    b, off = rad.encode_cells(cells, 4, 4)
     kw = dict(large_graph_thresh=thresh) if thresh else {}
     cfg = pkg.WorkerConfig.for_resolution(res, usa_mode=usa, num_genes=2 * G if usa else G, num_rows=3 * G if usa else G, small_thresh=0, **kw)
     got, want = run_both(oracle, cfg, t2g, b, off)
