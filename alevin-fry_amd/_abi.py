@@ -130,6 +130,8 @@ EXPORTS = [
     "afq_gpl_correct",
     "afq_gpl_limits",
     "afq_gpl_table_slot",
+    "afq_collate_rad",
+    "afq_collate_limits",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -158,6 +160,11 @@ class AfqGplHistStats(C.Structure):
 class AfqGplCorrectionStats(C.Structure):
     _fields_ = [("exact_distinct", C.c_uint64), ("exact_reads", C.c_uint64), ("corrected_distinct", C.c_uint64), ("corrected_reads", C.c_uint64),
                 ("ambiguous_distinct", C.c_uint64), ("ambiguous_reads", C.c_uint64), ("not_found_distinct", C.c_uint64), ("not_found_reads", C.c_uint64)]
+
+
+class AfqCollateStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_uncorrected", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_alignments_in", C.c_uint64), ("n_alignments_kept", C.c_uint64), ("n_long_records", C.c_uint64), ("out_bytes", C.c_uint64)]
 
 
 # afq_gpl_hist_rad's expected_ori, afq_gpl_correct's neighborhood / resolution / decisions

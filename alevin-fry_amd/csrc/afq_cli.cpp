@@ -1,4 +1,4 @@
-// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
+// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`, `afquant collate …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
 // reference) and `alevin-fry infer` (src/main.rs:350-365) in front of afq_quantify() / afq_infer_files()
 // (include/afquant_host.h).  Same spellings and defaults; what the reference refuses (--use-eds, -b with a plain
 // resolution, -d with trivial, --summary-stat without -b) is refused here too, with its message.
@@ -25,6 +25,8 @@ static void usage() {
                  "       afquant generate-permit-list -i <input-dir> -d fw|rc|both|either -o <output-dir> (-k | -e N | -f N | -b FILE | -u FILE [-m MINREADS])\n"
                  "       [-t N] [--cell-bc-correction unique|frequency] [--cell-bc-neighborhood hamming-1|substitution-or-shift-1|edit-1]\n"
                  "       [--cell-bc-confidence 0.975|a/b] [--device N] [--fill-bytes BYTES]\n"
+                 "       afquant collate -i <input-dir> -r <rad-dir> [-t N] [--device N]   (one device fill: -m/--max-records, --memory-limit and\n"
+                 "       --collation-mode are accepted and without effect; -c/--compress is not supported)\n"
                  "       afquant infer -c <geqc_counts.mtx> -e <gene_eqclass.txt.gz> -o <output-dir> [--usa] [--quant-subset FILE] [-t N]\n");
 }
 
@@ -140,6 +142,40 @@ int main(int argc, char** argv) {
         const int rc = afq_generate_permit_list(&go);
         if (rc) { std::fprintf(stderr, "afquant generate-permit-list failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         if (corrected == 0) std::fprintf(stderr, "found 0 corrected barcodes; please check the input.\n");
+        return 0;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "collate") == 0) {   // src/main.rs:271-292, 579-610
+        afq_collate_opts co{};
+        co.max_records = 30000000;
+        std::string cmdline;
+        for (int i = 0; i < argc; ++i) { if (i) cmdline += ' '; cmdline += argv[i]; }
+        co.cmdline = cmdline.c_str();
+        auto need2 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-h" || a == "--help") { usage(); return 0; }
+            else if (a == "-i" || a == "--input-dir") co.input_dir = need2(i);
+            else if (a == "-r" || a == "--rad-dir") co.rad_dir = need2(i);
+            else if (a == "-t" || a == "--threads") co.num_threads = (uint32_t)std::atoi(need2(i));
+            else if (a == "-c" || a == "--compress") co.compress = 1;
+            else if (a == "-m" || a == "--max-records") co.max_records = (uint32_t)std::strtoul(need2(i), nullptr, 10);   // one device fill: without effect
+            else if (a == "--memory-limit" || a == "--collation-mode") (void)need2(i);                                   // ... as are these
+            else if (a == "--device") co.device = (uint32_t)std::atoi(need2(i));
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!co.input_dir || !co.rad_dir) {
+            std::fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", co.input_dir ? "" : "  --input-dir <INPUTDIR>\n", co.rad_dir ? "" : "  --rad-dir <RADDIR>\n");
+            usage();
+            return 2;
+        }
+        for (const char* flag : {"-i", "-r"}) {   // clap's pathbuf_directory_exists_validator (main.rs:276-281)
+            const char* dir = flag[1] == 'i' ? co.input_dir : co.rad_dir;
+            FILE* probe = std::fopen(dir, "r");
+            if (!probe) { std::fprintf(stderr, "error: invalid value '%s' for '%s': the directory does not exist\n", dir, flag[1] == 'i' ? "--input-dir <INPUTDIR>" : "--rad-dir <RADDIR>"); return 2; }
+            std::fclose(probe);
+        }
+        const int rc = afq_collate(&co);
+        if (rc) { std::fprintf(stderr, "afquant collate failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         return 0;
     }
     if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "deduplicate") == 0) {   // src/main.rs:942-956, atac/run.rs:128-169

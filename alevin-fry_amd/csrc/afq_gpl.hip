@@ -19,6 +19,7 @@
 #include "afq_common.h"
 #include "afq_kernels.h"
 #include "afq_prims.h"
+#include "afq_rad_walk.h"
 
 namespace afq {
 
@@ -29,35 +30,6 @@ constexpr uint32_t kGplWaves = kGplParseNT / 64;
 constexpr uint32_t kGplTileWords = (3 + kGplParseTile + kGplParseHalo + 3) / 4 + 1;   // (+ the dword an unaligned 4-byte read of the last bytes also touches)
 static_assert(kGplParseHalo >= (4 + 8 + 8) + (4 + 8) * kGplLaneAlns, "the halo holds the widest head and kGplLaneAlns of the widest alignments");
 constexpr uint32_t kGplTileRecs = kGplParseTile / 6 + 1;   // the shortest record: na = 0, a 1-byte barcode, a 1-byte UMI
-
-// dword at byte offset `off` (a multiple of 4 in ADDRESS terms, possibly outside [0, n)) of the input buffer: what lies
-// outside the buffer reads as 0 and is never fetched
-__device__ __forceinline__ uint32_t gpl_ld_dword_in(const uint8_t* bytes, uint64_t n, int64_t off) {
-    if (off >= 0 && (uint64_t)off + 4 <= n) return *reinterpret_cast<const uint32_t*>(bytes + off);
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (off + k >= 0 && (uint64_t)(off + k) < n) v |= (uint32_t)bytes[off + k] << (8 * k);
-    return v;
-}
-// 4 bytes at ANY byte offset g of the buffer (g + 4 <= n: the caller checked), as two aligned dwords
-__device__ __forceinline__ uint32_t gpl_ld_u32(const uint8_t* bytes, uint64_t n, uint64_t g) {
-    const uint32_t sh = (uint32_t)((reinterpret_cast<uintptr_t>(bytes) + g) & 3u);
-    const int64_t base = (int64_t)g - sh;
-    const uint32_t lo = gpl_ld_dword_in(bytes, n, base);
-    if (!sh) return lo;
-    return __builtin_amdgcn_alignbyte(gpl_ld_dword_in(bytes, n, base + 4), lo, sh);
-}
-__device__ __forceinline__ uint32_t gpl_lds32(const uint32_t* t, uint32_t off) {   // 4 bytes at byte offset off of the tile
-    const uint32_t w = off >> 2, sh = off & 3u;
-    const uint32_t lo = t[w];
-    return sh ? __builtin_amdgcn_alignbyte(t[w + 1], lo, sh) : lo;
-}
-__device__ __forceinline__ void gpl_wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// does alignment word w speak for the expected orientation?  (bit 31 set: the read maps forward)
-__device__ __forceinline__ bool gpl_word_fits(uint32_t w, uint32_t ori) { return ori == kGplOriFw ? (w >> 31) != 0 : (w >> 31) == 0; }
 
 // Which record takes which route to its orientation test (cellfilter.rs:1698-1771):
 //   - expected_ori == both: no alignment word is read; every record is compatible, na == 0 included.

@@ -225,7 +225,7 @@ struct RadPrelude {
     std::vector<std::string> ref_names;
     std::vector<TagDesc> file_tags, read_tags, aln_tags;
     std::unordered_map<std::string, uint64_t> file_tag_vals;
-    size_t first_chunk = 0;
+    size_t first_chunk = 0, num_chunks_at = 0;   // (num_chunks_at: where the u64 num_chunks stands)
     uint32_t bc_bytes = 0, umi_bytes = 0;
     std::vector<uint32_t> ref_lengths;   // the ref_lengths file tag (an array of u32), when there is one
     bool have_ref_lengths = false;
@@ -253,6 +253,7 @@ int parse_prelude(const uint8_t* bytes, size_t n, RadPrelude& P, bool want_names
         const uint16_t nl = c.get<uint16_t>();
         if (want_names) P.ref_names.push_back(c.str(nl)); else { if (c.p + nl > c.n) c.ok = false; c.p += nl; }
     }
+    P.num_chunks_at = c.p;
     P.num_chunks = c.get<uint64_t>();
     if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "RAD header truncated");
     if (!read_tag_section(c, P.file_tags) || !read_tag_section(c, P.read_tags) || !read_tag_section(c, P.aln_tags))
@@ -954,6 +955,58 @@ int64_t afq_parse_permit_map(const uint8_t* in, size_t n, uint64_t* observed, ui
     return (int64_t)cnt;
 }
 
+namespace {
+// The correction map of a GPL output directory (sort.rs:450-479, collate.rs:560-571): the plan's global scope if there is a
+// correction_plan.bin - a present but malformed one is an error, and its cell barcode length must be permit_freq.bin's -, else
+// the legacy permit_map.bin, with the reference's warning.
+int load_corrections(const std::string& in, uint64_t bc_len, const char* mismatch, const char* legacy_for, std::vector<uint64_t>& obs, std::vector<uint64_t>& cor) {
+    std::vector<uint8_t> cm;
+    if (file_exists(in + "/correction_plan.bin")) {
+        if (!read_file(in + "/correction_plan.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "could not open correction plan " + in + "/correction_plan.bin");
+        uint32_t cell_len = 0;
+        const int64_t n = afq_parse_correction_plan(cm.data(), cm.size(), nullptr, nullptr, 0, &cell_len);
+        if (n < 0) return (int)n;
+        if (cell_len != bc_len) return hfail(AFQ_ERR_BAD_INPUT, mismatch);
+        obs.resize((size_t)n); cor.resize((size_t)n);
+        afq_parse_correction_plan(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n, nullptr);
+    } else {
+        std::fprintf(stderr, "No correction_plan.bin was found; loading legacy permit_map.bin for %s\n", legacy_for);
+        if (!read_file(in + "/permit_map.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open legacy permit_map.bin file");
+        const int64_t n = afq_parse_permit_map(cm.data(), cm.size(), nullptr, nullptr, 0);
+        if (n < 0) return (int)n;
+        obs.resize((size_t)n); cor.resize((size_t)n);
+        afq_parse_permit_map(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n);
+    }
+    return 0;
+}
+// <rd>/unmapped_bc_count.bin (12-byte pairs: barcode u64, count u32) -> <in>/unmapped_bc_count_collated.bin: the counts of the
+// observed barcodes summed onto their corrected barcodes (atac/collate.rs:247-283; collate.rs:431-480, the legacy layout - libradicl's self-describing one is not read).  missing_ok: no input file
+// is an empty map (collate.rs:440) instead of an error.
+int write_unmapped_collated(const std::string& rd, const std::string& in, const std::vector<uint64_t>& obs, const std::vector<uint64_t>& cor, bool missing_ok) {
+    std::vector<uint8_t> ub;
+    if (!read_file(rd + "/unmapped_bc_count.bin", ub)) {
+        if (!missing_ok || file_exists(rd + "/unmapped_bc_count.bin")) return hfail(AFQ_ERR_BAD_INPUT, "could not open " + rd + "/unmapped_bc_count.bin");
+        ub.clear();
+    }
+    std::unordered_map<uint64_t, uint64_t> cmap;
+    cmap.reserve(obs.size() * 2);
+    for (size_t i = 0; i < obs.size(); ++i) cmap.emplace(obs[i], cor[i]);
+    std::unordered_map<uint64_t, uint32_t> cnt;
+    for (size_t p = 0; p + 12 <= ub.size(); p += 12) {
+        uint64_t k; uint32_t v;
+        std::memcpy(&k, ub.data() + p, 8); std::memcpy(&v, ub.data() + p + 8, 4);
+        auto it = cmap.find(k);
+        if (it != cmap.end()) cnt[it->second] += v;
+    }
+    FilePtr f(std::fopen((in + "/unmapped_bc_count_collated.bin").c_str(), "wb"));
+    if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create serialization file.");
+    const uint64_t n = cnt.size();
+    std::fwrite(&n, 8, 1, f.get());
+    for (auto& kv : cnt) { std::fwrite(&kv.first, 8, 1, f.get()); std::fwrite(&kv.second, 4, 1, f.get()); }
+    return 0;
+}
+}  // namespace
+
 int afq_atac_sort(const afq_atac_sort_opts* o) {
     if (!o || !o->input_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
     if (!o->rad_dir) return hfail(AFQ_ERR_INVALID_ARG, "the RAD directory (-r) is required");
@@ -1019,46 +1072,9 @@ int afq_atac_sort(const afq_atac_sort_opts* o) {
     if (!P.have_ref_lengths || P.ref_lengths.size() != P.ref_count) return hfail(AFQ_ERR_BAD_INPUT, "scATAC RAD: the ref_lengths file tag must be an array of u32 with one entry per reference");
     // ---- the correction map: the plan if there is one, else the legacy map (sort.rs:450-479)
     std::vector<uint64_t> obs, cor;
-    {
-        std::vector<uint8_t> cm;
-        const bool plan = file_exists(in + "/correction_plan.bin");
-        if (plan) {
-            if (!read_file(in + "/correction_plan.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "could not open correction plan " + in + "/correction_plan.bin");
-            uint32_t cell_len = 0;
-            const int64_t n = afq_parse_correction_plan(cm.data(), cm.size(), nullptr, nullptr, 0, &cell_len);
-            if (n < 0) return (int)n;
-            if (cell_len != bc_len) return hfail(AFQ_ERR_BAD_INPUT, "correction plan does not match this ATAC input");
-            obs.resize((size_t)n); cor.resize((size_t)n);
-            afq_parse_correction_plan(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n, nullptr);
-        } else {
-            std::fprintf(stderr, "No correction_plan.bin was found; loading legacy permit_map.bin for ATAC sorting\n");
-            if (!read_file(in + "/permit_map.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open legacy permit_map.bin file");
-            const int64_t n = afq_parse_permit_map(cm.data(), cm.size(), nullptr, nullptr, 0);
-            if (n < 0) return (int)n;
-            obs.resize((size_t)n); cor.resize((size_t)n);
-            afq_parse_permit_map(cm.data(), cm.size(), obs.data(), cor.data(), (size_t)n);
-        }
-    }
+    if (int rc2 = load_corrections(in, bc_len, "correction plan does not match this ATAC input", "ATAC sorting", obs, cor)) return rc2;
     // ---- unmapped_bc_count.bin -> unmapped_bc_count_collated.bin (atac/collate.rs:247-283)
-    {
-        std::vector<uint8_t> ub;
-        if (!read_file(rd + "/unmapped_bc_count.bin", ub)) return hfail(AFQ_ERR_BAD_INPUT, "could not open " + rd + "/unmapped_bc_count.bin");
-        std::unordered_map<uint64_t, uint64_t> cmap;
-        cmap.reserve(obs.size() * 2);
-        for (size_t i = 0; i < obs.size(); ++i) cmap.emplace(obs[i], cor[i]);
-        std::unordered_map<uint64_t, uint32_t> cnt;
-        for (size_t p = 0; p + 12 <= ub.size(); p += 12) {
-            uint64_t k; uint32_t v;
-            std::memcpy(&k, ub.data() + p, 8); std::memcpy(&v, ub.data() + p + 8, 4);
-            auto it = cmap.find(k);
-            if (it != cmap.end()) cnt[it->second] += v;
-        }
-        FilePtr f(std::fopen((in + "/unmapped_bc_count_collated.bin").c_str(), "wb"));
-        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create serialization file.");
-        const uint64_t n = cnt.size();
-        std::fwrite(&n, 8, 1, f.get());
-        for (auto& kv : cnt) { std::fwrite(&kv.first, 8, 1, f.get()); std::fwrite(&kv.second, 4, 1, f.get()); }
-    }
+    if (int rc2 = write_unmapped_collated(rd, in, obs, cor, false)) return rc2;
     // ---- exactly num-chunks chunk headers (sort.rs:670)
     std::vector<uint64_t> chunk_off;
     {
@@ -1147,6 +1163,163 @@ int afq_atac_sort(const afq_atac_sort_opts* o) {
     std::fprintf(stderr, "Number of distinct fragments that have frag length >= 2000 %llu\n", (unsigned long long)st.n_long_fragments);
     std::fprintf(stderr, "Number of position bins that were partitioned again %llu\n", (unsigned long long)st.n_repartitioned_bins);
     if (o->stats_out) *o->stats_out = st;
+    return 0;
+}
+
+// `collate` (src/collate.rs:129-289, 483-643): map.collated.rad with exactly one chunk per cell of permit_freq.bin, in the order
+// (count descending, barcode ascending), every record barcode-corrected and cut to the alignments that fit expected_ori.
+int afq_collate(const afq_collate_opts* o) {
+    if (!o || !o->input_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (!o->rad_dir) return hfail(AFQ_ERR_INVALID_ARG, "the RAD directory (-r) is required");
+    if (o->compress) return hfail(AFQ_ERR_UNSUPPORTED, "compressed output is not supported");
+    const std::string in = o->input_dir, rd = o->rad_dir;
+    // ---- generate_permit_list.json (collate.rs:155-200, 513-520)
+    std::vector<uint8_t> gj;
+    if (!read_file(in + "/generate_permit_list.json", gj)) return hfail(AFQ_ERR_BAD_INPUT, "could not open generate_permit_list.json in \"" + in + "\"");
+    const std::string gjs(gj.begin(), gj.end());
+    auto value_at = [&](const char* key) -> size_t {   // offset of the value of the TOP-LEVEL "key" (gpl_options repeats some names), or npos
+        const std::string k = key;
+        int depth = 0;
+        for (size_t i = 0; i < gjs.size(); ++i) {
+            const char ch = gjs[i];
+            if (ch == '{' || ch == '[') ++depth;
+            else if (ch == '}' || ch == ']') --depth;
+            else if (ch == '"') {
+                size_t e = i + 1;
+                while (e < gjs.size() && gjs[e] != '"') e += gjs[e] == '\\' ? 2 : 1;
+                const size_t after = gjs.find_first_not_of(" \t\r\n", e + 1);
+                if (depth == 1 && after != std::string::npos && gjs[after] == ':' && gjs.compare(i + 1, e - i - 1, k) == 0 && e - i - 1 == k.size())
+                    return gjs.find_first_not_of(" \t\r\n", after + 1);
+                i = e;
+            }
+        }
+        return std::string::npos;
+    };
+    auto is_true = [&](size_t v) { return v != std::string::npos && gjs.compare(v, 4, "true") == 0; };
+    if (value_at("version_str") == std::string::npos)
+        return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
+    if (is_true(value_at("multi_barcode"))) return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode permit lists (multi_barcode: true) are not supported");
+    if (is_true(value_at("velo_mode"))) return hfail(AFQ_ERR_UNSUPPORTED, "collate: velo_mode: true is not supported");
+    uint32_t expected_ori = 0;
+    {
+        const size_t v = value_at("expected_ori");
+        static const char* const kSym[3] = {"\"both\"", "\"fw\"", "\"rc\""};   // (the symbols generate-permit-list writes; `either` is written as both)
+        uint32_t k = 0;
+        while (k < 3 && (v == std::string::npos || gjs.compare(v, std::strlen(kSym[k]), kSym[k]) != 0)) ++k;
+        if (k == 3) return hfail(AFQ_ERR_BAD_INPUT, "could not read strand: generate_permit_list.json: expected_ori must be \"both\", \"fw\" or \"rc\"");
+        expected_ori = k;
+    }
+    // ---- permit_freq.bin: the cells and their order (collate.rs:236-274)
+    std::vector<uint8_t> pf;
+    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 24) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
+    uint64_t pf_ver, bc_len, n_freq;
+    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8); std::memcpy(&n_freq, pf.data() + 16, 8);
+    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
+    if (n_freq != (pf.size() - 24) / 16 || (pf.size() - 24) % 16) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize permit_freq.bin: its length does not match its entry count");
+    if (n_freq == 0) return hfail(AFQ_ERR_BAD_INPUT, "single-barcode permit list contains no output cells");
+    std::vector<std::pair<uint64_t, uint64_t>> freq(n_freq);   // (barcode, count)
+    uint64_t total_to_collate = 0;
+    for (uint64_t i = 0; i < n_freq; ++i) {
+        std::memcpy(&freq[i].first, pf.data() + 24 + 16 * i, 8); std::memcpy(&freq[i].second, pf.data() + 32 + 16 * i, 8);
+        total_to_collate += freq[i].second;
+    }
+    std::sort(freq.begin(), freq.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });   // collate.rs:270-274
+    std::vector<uint64_t> cells(n_freq);
+    for (uint64_t i = 0; i < n_freq; ++i) cells[i] = freq[i].first;
+    // ---- the correction map, the unmapped counts
+    std::vector<uint64_t> obs, cor;
+    if (int rc2 = load_corrections(in, bc_len, "correction plan does not match this input: its cell barcode length is not permit_freq.bin's", "collation", obs, cor)) return rc2;
+    if (int rc2 = write_unmapped_collated(rd, in, obs, cor, true)) return rc2;
+    // ---- map.rad
+    if (!file_exists(rd)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + rd + "\" does not exist");
+    PhaseClock pc;
+    MappedFile mf;
+    if (!mf.open(rd + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open input RAD file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    auto has_tag = [](const std::vector<TagDesc>& v, const char* name) { for (auto& t : v) if (t.name == name) return true; return false; };
+    if (P.file_tag_vals.count("num_barcodes") && P.file_tag_vals["num_barcodes"] > 1)
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode RAD files (num_barcodes > 1) are not supported");
+    if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len"))
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: this is a scATAC RAD file; `atac collate` is not supported (use `atac sort`)");
+    if (has_tag(P.aln_tags, "as") && has_tag(P.aln_tags, "start") && has_tag(P.aln_tags, "end"))
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: long-read RAD records (alignment tags as, start, end) are not supported");
+    if (P.read_tags.size() != 2 || P.read_tags[0].name != "b" || P.read_tags[1].name != "u" || !P.bc_bytes || !P.umi_bytes)
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: the read-level tags must be the integers (b, u)");
+    uint32_t aln_extra = 0;
+    if (P.aln_tags.size() == 2 && P.aln_tags[1].name == "pos") aln_extra = (uint32_t)int_type_bytes(P.aln_tags[1].type);
+    if (P.aln_tags.empty() || P.aln_tags[0].type != 3 || (P.aln_tags.size() == 2 && !aln_extra) || P.aln_tags.size() > 2)
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: the alignment-level tags must be one u32 (ref | orientation), optionally followed by an integer pos");
+    // ---- the chunk table
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < P.num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
+    pc.lap("metadata + maps + chunk table");
+    // ---- the device: one fill
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    const uint64_t span0 = chunk_off.empty() ? P.first_chunk : chunk_off[0];
+    std::vector<uint64_t> rel(chunk_off.size());
+    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    uint8_t* ob = nullptr; uint64_t on = 0, *ooff = nullptr; uint32_t* onrec = nullptr;
+    afq_collate_stats st{};
+    rc = afq_collate_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, P.umi_bytes, expected_ori, 0, obs.data(), cor.data(),
+                         obs.size(), cells.data(), cells.size(), &ob, &on, &ooff, &onrec, &st);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer { void *a, *b, *c; ~Freer() { afq_free(a); afq_free(b); afq_free(c); } } fr{ob, ooff, onrec};
+    pc.lap("device: collate");
+    if (o->stats_out) *o->stats_out = st;
+    if (st.n_kept != total_to_collate)   // collate.rs:615 (nothing was written yet, so no RAD is left behind)
+        return hfail(AFQ_ERR_BAD_INPUT, "expected to collate " + std::to_string(total_to_collate) + " records but retained " + std::to_string(st.n_kept));
+    // ---- map.collated.rad: the input's prelude with num_chunks = the number of cells (collate.rs:544-549), then the chunks
+    const std::string out_path = in + "/map.collated.rad";
+    {
+        FilePtr f(std::fopen(out_path.c_str(), "wb"));
+        bool ok = (bool)f;
+        if (ok) {
+            std::vector<uint8_t> hdr(rad, rad + P.first_chunk);
+            const uint64_t nc = cells.size();
+            std::memcpy(hdr.data() + P.num_chunks_at, &nc, 8);
+            ok = std::fwrite(hdr.data(), 1, hdr.size(), f.get()) == hdr.size();
+            for (uint64_t off = 0; ok && off < on;) {
+                const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
+                ok = std::fwrite(ob + off, 1, len, f.get()) == len;
+                off += len;
+            }
+            ok = ok && std::fflush(f.get()) == 0;
+        }
+        if (!ok) { f.reset(); std::remove(out_path.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + out_path); }
+    }
+    {   // collate.rs:589-597 (collation_mode / memory_budget_bytes describe the reference's engine and are left out)
+        FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
+        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false\n}", json_escape(o->cmdline ? o->cmdline : "").c_str());
+    }
+    pc.lap("map.collated.rad");
+    std::fprintf(stderr, "deserialized correction map of length : %llu\n", (unsigned long long)obs.size());
+    std::fprintf(stderr, "collated %llu of %llu records (%llu orientation consistent, %llu with a barcode that is not in the correction map) into %llu cells\n",
+                 (unsigned long long)st.n_kept, (unsigned long long)st.n_records, (unsigned long long)st.n_compatible, (unsigned long long)st.n_uncorrected,
+                 (unsigned long long)cells.size());
+    std::fprintf(stderr, "kept %llu of %llu alignments; %llu output bytes\n", (unsigned long long)st.n_alignments_kept, (unsigned long long)st.n_alignments_in,
+                 (unsigned long long)st.out_bytes);
     return 0;
 }
 

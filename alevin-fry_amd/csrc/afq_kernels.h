@@ -279,6 +279,35 @@ void launch_gpl_count(hipStream_t s, const SortChunk* chunks, uint32_t n_chunks,
 void launch_gpl_compact(hipStream_t s, const uint64_t* tab_key, const unsigned long long* tab_cnt, uint64_t cap, uint64_t* o_key, uint64_t* o_cnt,
                         uint32_t* n_out);
 void launch_gpl_correct(hipStream_t s, const GplCorrectArgs& a);
+// `collate`: the records of an uncollated RNA RAD, barcode-corrected, one output chunk per cell (afq_collate.hip).  The walk and
+// its limits are the GPL parse's (kGplParseTile, kGplParseHalo, kGplLaneAlns).
+constexpr uint32_t kCollateRadixNT = 256, kCollateRadixItems = 32, kCollateScanItems = 8;
+constexpr uint32_t kCollateRadixBlock = kCollateRadixNT * kCollateRadixItems;   // keys a workgroup of a radix pass takes (256 digit counts each: the fewer workgroups, the shorter the one-workgroup scan of the counts)
+constexpr uint32_t kCollateScanBlock = kCollateRadixNT * kCollateScanItems;     // sorted positions a workgroup of the length scan takes (they sit in registers)
+constexpr uint32_t kErrCollateChunk = 12;   // collate: an output chunk of 4 GiB or more (err_cell: the cell's index)
+struct CollateArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks;
+    uint32_t bc_bytes, umi_bytes, aln_extra, expected_ori;
+    const uint64_t* tab_key; const uint32_t* tab_val; uint32_t tab_mask; uint32_t ones_cell;   // observed barcode -> index of its corrected barcode in `cells`
+    uint32_t n_cells;        // (also the cell word of a record that is dropped: it sorts behind every cell)
+    uint2* rec;              // a slot per record of the chunk table, in input order: (cell, bytes of the record as written)
+    uint64_t* key;           // measure: cell << 32 | slot of every slot
+    uint32_t* chunk_stat;    // measure: [n_chunks][8]: records, compatible, not in the map, kept, alignments in, alignments kept, long records, 0
+    const uint64_t* cells;   // write: [n_cells] the corrected barcodes
+    const uint64_t* dest;    // write: [slot] byte offset of the record in `out`
+    uint8_t* out;
+    DevStatus* st;
+};
+void launch_collate_measure(hipStream_t s, const CollateArgs& a);
+void launch_collate_write(hipStream_t s, const CollateArgs& a);
+// one stable LSD pass over n keys: digit = (key >> shift) & 255; hist holds 256 x ceil(n / kCollateRadixBlock) words (digit-major)
+void launch_collate_radix_pass(hipStream_t s, const uint64_t* src, uint64_t* dst, uint32_t n, uint32_t shift, uint32_t* hist);
+// ex[i] = bytes of the records in front of sorted position i (ex[n]: all of them); dest[slot] = 8 (cell + 1) + ex[i]
+// (block_sum: ceil(n / kCollateScanBlock) words)
+void launch_collate_scan(hipStream_t s, const uint64_t* sorted, const uint2* rec, uint32_t n, uint64_t* block_sum, uint64_t* ex, uint64_t* dest);
+// chunk c: off[c] (off[n_cells]: the end), nrec[c], and its (nbytes, nrec) header into out
+void launch_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, const uint64_t* ex, uint32_t n_cells, uint64_t* off, uint32_t* nrec, uint8_t* out,
+                          DevStatus* st);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

@@ -366,6 +366,46 @@ void afq_gpl_limits(uint32_t out[4]);
 void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity);
 
 /*
+ * `collate`, the device half (src/collate.rs:129-289, 483-643 of the reference): the records of an UNCOLLATED single-barcode RNA
+ * RAD routed by corrected barcode into one chunk per cell.
+ *
+ * `bytes` / `chunk_off` / the record layout / expected_ori are afq_gpl_hist_rad's.  `observed` -> `corrected` is the correction
+ * map (n_corrections entries; one observed barcode may occur twice only with one target); `cells` (n_cells, distinct) are the
+ * output cells IN OUTPUT ORDER, and every corrected barcode must be one of them.
+ *
+ * A record is kept iff it is compatible with expected_ori (afq_gpl_hist_rad's rule, `na == 0` only under both) and its barcode
+ * is an observed key.  It is written with the corrected barcode, its UMI, and ONLY the alignments that fit expected_ori (all of
+ * them under both), in input order, each word untouched (bit 31 stays) with its position bytes; na becomes their number.
+ *
+ * Out (malloc'd; afq_free): out_bytes = the n_cells chunks back to back, each `nbytes u32, nrec u32` + its records, a cell
+ * without a record being a header-only chunk (8, 0); out_chunk_off[n_cells + 1]; out_nrec[n_cells].  Inside a chunk the records
+ * stand in input order (chunk index, then record index): the output is a function of the input alone, byte for byte.
+ *
+ * AFQ_ERR_BAD_INPUT: a chunk outside `bytes` or whose records do not tile it ("chunk i"), a corrected barcode that is no cell, two
+ * targets for one observed barcode, two cells with one barcode.  AFQ_ERR_UNSUPPORTED: 2^32 records or more in one call, more than
+ * 2^32 - 2 cells, 2^30 correction entries or more, an output chunk of 4 GiB or more (the cell is named).  AFQ_ERR_OOM (with the
+ * sizes) when input, output, 32 bytes a record and the tables do not fit the device: one call is one device fill.
+ */
+typedef struct afq_collate_stats {
+    uint64_t n_records;          /* records of the chunks                                                     */
+    uint64_t n_compatible;       /* ... compatible with expected_ori                                          */
+    uint64_t n_uncorrected;      /* ... of those, with a barcode that is not in the map                       */
+    uint64_t n_kept;             /* records written (= n_compatible - n_uncorrected)                          */
+    uint64_t n_alignments_in;    /* alignments of all records                                                 */
+    uint64_t n_alignments_kept;  /* alignments written                                                        */
+    uint64_t n_long_records;     /* records with more than afq_collate_limits()[2] alignments: the whole wave
+                                    handles them out of global memory                                         */
+    uint64_t out_bytes;          /* length of out_bytes                                                       */
+} afq_collate_stats;
+int afq_collate_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                    uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* observed, const uint64_t* corrected,
+                    uint64_t n_corrections, const uint64_t* cells, uint64_t n_cells, uint8_t** out_bytes, uint64_t* out_n_bytes,
+                    uint64_t** out_chunk_off, uint32_t** out_nrec, afq_collate_stats* stats);
+/* out[0] = bytes of a chunk a collate walk stages per trip, out[1] = bytes staged behind them, out[2] = a record with more
+ * alignments than this is a long record (all three are afq_gpl_limits'), out[3] = keys a workgroup of a radix pass takes.  For tests. */
+void afq_collate_limits(uint32_t out[4]);
+
+/*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the
  * number of kernels, or a negative error.  `name[i]` points to static storage.

@@ -87,6 +87,26 @@ typedef struct afq_atac_sort_opts {
 /* Runs the whole `atac sort` sub-command (src/atac/sort.rs:170-895): the coordinate-sorted, de-duplicated BED of an uncollated RAD. */
 int afq_atac_sort(const afq_atac_sort_opts* opts);
 
+/* The options of `alevin-fry collate` (src/main.rs:271-292) for single-barcode RNA RAD files. */
+struct afq_collate_stats;
+typedef struct afq_collate_opts {
+    const char* input_dir;      /* -i : output directory of `generate-permit-list`; map.collated.rad, collate.json and
+                                        unmapped_bc_count_collated.bin are written here                                    */
+    const char* rad_dir;        /* -r : the mapper's directory: map.rad, unmapped_bc_count.bin (optional)                  */
+    uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED): the project has a snappy decoder and no encoder     */
+    uint32_t max_records;       /* -m : accepted, without effect (it sizes the reference's host buffers)                   */
+    uint32_t device;
+    const char* cmdline;        /* optional: goes into collate.json                                                        */
+    struct afq_collate_stats* stats_out;   /* optional */
+} afq_collate_opts;
+/* Runs the whole `collate` sub-command (src/collate.rs:129-289, 483-643) in ONE device fill: one chunk per cell of permit_freq.bin,
+ * in the order (count descending, barcode ascending); records barcode-corrected and cut to the alignments that fit expected_ori;
+ * input order inside a chunk.  ATAC, multi-barcode and long-read preludes, multi_barcode / velo_mode metadata and compressed output
+ * are AFQ_ERR_UNSUPPORTED, named in the message; a kept count other than the sum of permit_freq.bin is the reference's
+ * "expected to collate N records but retained M", and no RAD is left behind. */
+int afq_collate(const afq_collate_opts* opts);
+
 /* The options of `alevin-fry generate-permit-list` (src/main.rs:170-269, 392-577; GenPermitListOpts, src/prog_opts.rs:86-160) for
  * single-barcode RNA RAD files.  Exactly one filter method is given. */
 enum { AFQ_GPL_KNEE = 0, AFQ_GPL_EXPECT = 1, AFQ_GPL_FORCE = 2, AFQ_GPL_VALID_BC = 3, AFQ_GPL_UNFILTERED = 4 };
