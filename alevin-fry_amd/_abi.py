@@ -132,6 +132,8 @@ EXPORTS = [
     "afq_gpl_table_slot",
     "afq_collate_rad",
     "afq_collate_limits",
+    "afq_atac_collate_rad",
+    "afq_atac_collate_limits",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -165,6 +167,11 @@ class AfqGplCorrectionStats(C.Structure):
 class AfqCollateStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_uncorrected", C.c_uint64), ("n_kept", C.c_uint64),
                 ("n_alignments_in", C.c_uint64), ("n_alignments_kept", C.c_uint64), ("n_long_records", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqAtacCollateStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_uncorrected", C.c_uint64),
+                ("n_kept", C.c_uint64), ("n_cells_out", C.c_uint64), ("n_cells_empty", C.c_uint64), ("out_bytes", C.c_uint64)]
 
 
 # afq_gpl_hist_rad's expected_ori, afq_gpl_correct's neighborhood / resolution / decisions

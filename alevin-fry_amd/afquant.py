@@ -318,6 +318,12 @@ def load_library(path: str = LIB_PATH):
     lib.afq_collate_rad.restype = C.c_int
     lib.afq_collate_limits.argtypes = [p(C.c_uint32)]
     lib.afq_collate_limits.restype = None
+    lib.afq_atac_collate_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), p(C.c_uint64),
+                                         C.c_uint64, p(C.c_uint64), C.c_uint64, p(p(C.c_uint8)), p(C.c_uint64), p(C.c_uint64), p(p(C.c_uint64)),
+                                         p(p(C.c_uint32)), p(p(C.c_uint32)), p(_abi.AfqAtacCollateStats)]
+    lib.afq_atac_collate_rad.restype = C.c_int
+    lib.afq_atac_collate_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_atac_collate_limits.restype = None
     lib.afq_free.argtypes = [C.c_void_p]
     lib.afq_free.restype = None
     lib.afq_get_kernel_times.argtypes = [C.c_void_p, p(AfqKernelTime), C.c_uint32]
@@ -365,6 +371,14 @@ def collate_limits():
     out = (C.c_uint32 * 4)()
     load_library().afq_collate_limits(out)
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "radix_block": int(out[3])}
+
+
+def atac_collate_limits():
+    """afq_atac_collate_limits: {"parse_tile", "parse_halo", "aln_bytes", "radix_block"} of `atac collate` - bytes a walk stages per
+    trip, bytes staged behind them, bytes of an alignment, keys a workgroup of a radix pass takes."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_atac_collate_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "aln_bytes": int(out[2]), "radix_block": int(out[3])}
 
 
 def gpl_table_slot(barcode, n_kept, bc_bytes: int = 8):
@@ -683,6 +697,41 @@ class Quantifier:
     def collate_limits():
         """The collate walks' and radix passes' limits (module-level collate_limits)."""
         return collate_limits()
+
+    def atac_collate_rad(self, chunk_bytes, chunk_off, observed, corrected, cells, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0):
+        """afq_atac_collate_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the device),
+        the correction map observed -> corrected and the cells in output order; a dict out: "bytes" (u8: one chunk per cell that kept a
+        record, back to back, headers included), "chunk_off" (u64, n_out + 1), "nrec" (u32 per chunk), "cell" (u32 per chunk: the index
+        into `cells`) and "stats"."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        obs = np.ascontiguousarray(observed, dtype=np.uint64)
+        cor = np.ascontiguousarray(corrected, dtype=np.uint64)
+        cel = np.ascontiguousarray(cells, dtype=np.uint64)
+        if len(obs) != len(cor):
+            raise ValueError("observed and corrected must have one length")
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        o_b, o_n, o_nc, o_off, o_nrec, o_cell, st = C.POINTER(C.c_uint8)(), C.c_uint64(), C.c_uint64(), u64p(), u32p(), u32p(), _abi.AfqAtacCollateStats()
+        self._check(self.lib.afq_atac_collate_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), bc_bytes, on_dev, obs.ctypes.data_as(u64p),
+                                                  cor.ctypes.data_as(u64p), len(obs), cel.ctypes.data_as(u64p), len(cel), C.byref(o_b), C.byref(o_n),
+                                                  C.byref(o_nc), C.byref(o_off), C.byref(o_nrec), C.byref(o_cell), C.byref(st)))
+        n, nc = int(o_n.value), int(o_nc.value)
+        try:
+            mk = lambda p_, k, dt: (np.ctypeslib.as_array(p_, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dt))
+            return {"bytes": mk(o_b, n, np.uint8), "chunk_off": mk(o_off, nc + 1, np.uint64), "nrec": mk(o_nrec, nc, np.uint32),
+                    "cell": mk(o_cell, nc, np.uint32), "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_b, o_off, o_nrec, o_cell):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def atac_collate_limits():
+        """The `atac collate` walks' and radix passes' limits (module-level atac_collate_limits)."""
+        return atac_collate_limits()
 
     def atac_dedup_rad(self, chunk_bytes, chunk_off, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0, copy: bool = True):
         """afq_atac_dedup_rad: collated scATAC chunks in (host bytes, or d_ptr/n_bytes for bytes already on the device),

@@ -60,13 +60,14 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
                                            "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit",
                                            "k_gpl_parse", "k_gpl_count", "k_gpl_compact", "k_gpl_table", "k_gpl_correct",
-                                           "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write"};
+                                           "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write",
+                                           "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -216,6 +217,12 @@ struct CollateBufs {
     std::vector<DevBuf*> all() { return {&chunks, &obs, &val, &tkey, &tval, &cells, &rec, &ka, &kb, &hist, &bsum, &ex, &cstat, &status, &out, &off, &nrec}; }
 };
 
+// afq_atac_collate_rad's
+struct AtacCollateBufs {
+    DevBuf chunks, obs, val, tkey, tval, cells, cellof, ka, kb, hist, first, rank, cstat, status, out, off, nrec, ocell;
+    std::vector<DevBuf*> all() { return {&chunks, &obs, &val, &tkey, &tval, &cells, &cellof, &ka, &kb, &hist, &first, &rank, &cstat, &status, &out, &off, &nrec, &ocell}; }
+};
+
 }  // namespace
 
 struct afq_ctx {
@@ -235,6 +242,7 @@ struct afq_ctx {
     AtacSortBufs asort;
     GplBufs gpl;
     CollateBufs collate;
+    AtacCollateBufs acollate;
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
@@ -1753,6 +1761,7 @@ void afq_destroy(afq_ctx* c) {
     for (DevBuf* b : c->asort.all()) b->release();
     for (DevBuf* b : c->gpl.all()) b->release();
     for (DevBuf* b : c->collate.all()) b->release();
+    for (DevBuf* b : c->acollate.all()) b->release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);
@@ -3222,6 +3231,201 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     if (stats) *stats = S;
     H.release();
     *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
+    return 0;
+}
+
+// `atac collate` on the device (afq_atac_collate.hip): correction table, measure walk, radix placement, cell runs + their scan, chunk
+// heads, write walk.
+void afq_atac_collate_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSortParseTile; out[1] = kSortParseHalo; out[2] = 11; out[3] = kCollateRadixBlock;
+}
+
+int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes, int bytes_on_device,
+                         const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint64_t* cells, uint64_t n_cells64, uint8_t** out_bytes,
+                         uint64_t* out_n_bytes, uint64_t* out_n_chunks, uint64_t** out_chunk_off, uint32_t** out_nrec, uint32_t** out_cell,
+                         afq_atac_collate_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || ((!observed || !corrected) && n_corr) || (!cells && n_cells64) || !out_bytes || !out_n_bytes ||
+        !out_n_chunks || !out_chunk_off || !out_nrec || !out_cell)
+        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    if (n_corr >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: 2^30 or more correction entries");
+    if (n_cells64 > 0xFFFFFFFEull) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: more than 2^32 - 2 cells (" + std::to_string(n_cells64) + ")");
+    const uint32_t n_cells = (uint32_t)n_cells64;
+    const uint32_t R = 4 + bc_bytes + 11;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    // ---- host: corrected barcode -> its index in `cells`; the all-ones key
+    std::vector<uint32_t> val(n_corr);
+    uint32_t ones_cell = kSortNoRank;
+    {
+        std::vector<std::pair<uint64_t, uint32_t>> by_bc(n_cells);
+        for (uint32_t i = 0; i < n_cells; ++i) by_bc[i] = {cells[i], i};
+        std::sort(by_bc.begin(), by_bc.end());
+        for (uint32_t i = 1; i < n_cells; ++i)
+            if (by_bc[i].first == by_bc[i - 1].first)
+                return fail(c, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by_bc[i - 1].second) + " and " + std::to_string(by_bc[i].second) + " carry one barcode (" +
+                            std::to_string(by_bc[i].first) + ")");
+        for (uint64_t i = 0; i < n_corr; ++i) {
+            const auto it = std::lower_bound(by_bc.begin(), by_bc.end(), std::make_pair(corrected[i], 0u));
+            if (it == by_bc.end() || it->first != corrected[i])
+                return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(observed[i]) + " is corrected to " +
+                            std::to_string(corrected[i]) + ", which is not a cell");
+            val[i] = it->second;
+            if (observed[i] == kSortEmptyKey) {
+                if (ones_cell != kSortNoRank && ones_cell != val[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
+                ones_cell = val[i];
+            }
+        }
+    }
+    // ---- chunk table
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
+    std::vector<SortChunk> chunks(n_chunks);
+    uint64_t n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
+    const uint32_t n = (uint32_t)n_slots;
+    const uint64_t cap = sort_table_capacity(n_corr);
+    const uint32_t tab_mask = (uint32_t)(cap - 1);
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ncell1 = (uint64_t)n_cells + 1, ncorr1 = std::max<uint64_t>(n_corr, 1);
+    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock;
+    const uint64_t max_out = std::min<uint64_t>(n_cells, n_slots);   // chunks the output can have
+    // does it fit?  (input + staging, the output - a kept record is never longer than it was, + the heads -, 20 bytes a record of
+    // cells and sort words + the destination that reuses a sort buffer, the digit counts, the tables)
+    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_out = (uint64_t)n_bytes + 8 * max_out + 8, need_rec = s1 * 20 + n_rblocks * 1024,
+                   need_tab = cap * 12 + n_corr * 12 + ncell1 * 16 + (max_out + 1) * 16, need_misc = nc1 * (sizeof(SortChunk) + 32);
+    {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_out + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
+                        std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
+                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->acollate;
+    HipLatch T;
+    auto hip_fail = [&]() {
+        return T.fail(c, "afq_atac_collate_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
+    };
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * ncorr1)); T(B.val.ensure(4 * ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
+    T(B.cells.ensure(8 * ncell1)); T(B.cellof.ensure(4 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks));
+    T(B.first.ensure(4 * ncell1)); T(B.rank.ensure(4 * ncell1)); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
+    if (!T.ok()) return hip_fail();
+    const uint8_t* d_bytes = bytes;
+    if (!bytes_on_device) {
+        T(c->d_bytes_own.ensure(n_bytes + 16));
+        if (!T.ok()) return hip_fail();
+        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
+        d_bytes = c->d_bytes_own.as<uint8_t>();
+    }
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
+    if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    AtacCollateArgs a{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, ones_cell,
+                      n_cells, B.cellof.as<uint32_t>(), B.ka.as<uint64_t>(), B.cstat.as<uint32_t>(), B.cells.as<uint64_t>(), nullptr, nullptr, B.status.as<DevStatus>()};
+    {
+        ScopedTimer t(c, K_ACOLLATE_TABLE, s);
+        launch_sort_table(s, B.obs.as<uint64_t>(), B.val.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_ACOLLATE_MEASURE, s);
+        launch_atac_collate_measure(s, a);
+    }
+    T(hipGetLastError());
+    DevStatus st{};
+    std::vector<uint32_t> cstat(8ull * n_chunks);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
+    hc.lap("atac collate: table + measure");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) {
+        harvest_timers(c);
+        const std::string who = std::to_string(st.err_cell);
+        switch (st.err_code) {
+            case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + who + ": an observed barcode with two different corrected barcodes");
+            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+            default: return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: device status " + std::to_string(st.err_code));
+        }
+    }
+    afq_atac_collate_stats S{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t* q = cstat.data() + 8ull * i;
+        S.n_records += q[0]; S.n_unmapped += q[1]; S.n_multimapped += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4];
+    }
+    // ---- placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies, then the
+    // cells' runs and the scan that numbers the non-empty ones
+    uint64_t* src = B.ka.as<uint64_t>();
+    uint64_t* dst = B.kb.as<uint64_t>();
+    {
+        ScopedTimer t(c, K_ACOLLATE_PLACE, s);
+        for (uint32_t shift = 32; shift < 64 && (n_cells >> (shift - 32)) != 0; shift += 8) {
+            launch_collate_radix_pass(s, src, dst, n, shift, B.hist.as<uint32_t>());
+            std::swap(src, dst);
+        }
+        launch_atac_collate_runs(s, src, n, n_cells, B.first.as<uint32_t>(), B.rank.as<uint32_t>());
+        launch_collate_excl_scan_u32(s, B.rank.as<uint32_t>(), ncell1);
+    }
+    T(hipGetLastError());
+    uint32_t n_out = 0, n_kept_dev = 0;
+    T(hipMemcpyAsync(&n_out, B.rank.as<uint32_t>() + n_cells, 4, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&n_kept_dev, B.first.as<uint32_t>() + n_cells, 4, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    if (!T.ok()) return hip_fail();
+    if (n_kept_dev != S.n_kept || n_out > max_out || (n_out == 0) != (S.n_kept == 0)) {   // (the write's bounds rest on these)
+        harvest_timers(c);
+        return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: the placement holds " + std::to_string(n_kept_dev) + " records in " + std::to_string(n_out) + " cells, the measure kept " +
+                    std::to_string(S.n_kept));
+    }
+    const uint64_t out_total = (uint64_t)R * S.n_kept + 8ull * n_out, o1 = std::max<uint64_t>(out_total, 1), nout1 = (uint64_t)n_out + 1;
+    T(B.out.ensure(o1)); T(B.off.ensure(8 * nout1)); T(B.nrec.ensure(4 * nout1)); T(B.ocell.ensure(4 * nout1));
+    if (!T.ok()) return hip_fail();
+    a.dest = dst; a.out = B.out.as<uint8_t>();   // (dst: the buffer the last pass read is free)
+    {
+        ScopedTimer t(c, K_ACOLLATE_PLACE, s);
+        launch_atac_collate_heads(s, src, n, n_cells, R, B.first.as<uint32_t>(), B.rank.as<uint32_t>(), B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), B.ocell.as<uint32_t>(),
+                                  dst, a.out, B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_ACOLLATE_WRITE, s);
+        if (S.n_kept) launch_atac_collate_write(s, a);
+    }
+    T(hipGetLastError());
+    HostOuts H;
+    uint8_t* ob = (uint8_t*)H.mallocd(o1);
+    uint64_t* ooff = (uint64_t*)H.mallocd(8 * nout1);
+    uint32_t* onrec = (uint32_t*)H.mallocd(4 * nout1);
+    uint32_t* ocell = (uint32_t*)H.mallocd(4 * nout1);
+    if (!ob || !ooff || !onrec || !ocell) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: host allocation failed (" + std::to_string(o1 + 16 * nout1) + " bytes of output)"); }
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(ooff, B.off.p, 8 * nout1, hipMemcpyDeviceToHost, s));
+    if (n_out) { T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(ocell, B.ocell.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); }
+    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
+    harvest_timers(c);
+    hc.lap("atac collate: place + write + D2H");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code == kErrCollateChunk)
+        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: cell " + std::to_string(st.err_cell) + " (barcode " + std::to_string(cells[st.err_cell]) + "): an output chunk of 4 GiB or more");
+    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: device status " + std::to_string(st.err_code) + " in the write");
+    if (ooff[n_out] != out_total) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: the chunks end at " + std::to_string(ooff[n_out]) + " of " + std::to_string(out_total) + " output bytes");
+    S.n_cells_out = n_out; S.n_cells_empty = (uint64_t)n_cells - n_out; S.out_bytes = out_total;
+    if (stats) *stats = S;
+    H.release();
+    *out_bytes = ob; *out_n_bytes = out_total; *out_n_chunks = n_out; *out_chunk_off = ooff; *out_nrec = onrec; *out_cell = ocell;
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`, `afquant collate …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
+// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`, `afquant collate …`, `afquant atac collate …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
 // reference) and `alevin-fry infer` (src/main.rs:350-365) in front of afq_quantify() / afq_infer_files()
 // (include/afquant_host.h).  Same spellings and defaults; what the reference refuses (--use-eds, -b with a plain
 // resolution, -d with trivial, --summary-stat without -b) is refused here too, with its message.
@@ -22,6 +22,7 @@ static void usage() {
                  "resolutions: trivial cr-like cr-like-em parsimony parsimony-em parsimony-gene parsimony-gene-em\n"
                  "       afquant atac deduplicate -i <input-dir> [-t N] [-d fw|rc] [--device N]\n"
                  "       afquant atac sort -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]\n"
+                 "       afquant atac collate -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]   (-m is without effect; -c is not supported)\n"
                  "       afquant generate-permit-list -i <input-dir> -d fw|rc|both|either -o <output-dir> (-k | -e N | -f N | -b FILE | -u FILE [-m MINREADS])\n"
                  "       [-t N] [--cell-bc-correction unique|frequency] [--cell-bc-neighborhood hamming-1|substitution-or-shift-1|edit-1]\n"
                  "       [--cell-bc-confidence 0.975|a/b] [--device N] [--fill-bytes BYTES]\n"
@@ -176,6 +177,39 @@ int main(int argc, char** argv) {
         }
         const int rc = afq_collate(&co);
         if (rc) { std::fprintf(stderr, "afquant collate failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        return 0;
+    }
+    if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "collate") == 0) {   // src/main.rs:905-922
+        afq_atac_collate_opts co{};
+        co.max_records = 30000000;
+        std::string cmdline;
+        for (int i = 0; i < argc; ++i) { if (i) cmdline += ' '; cmdline += argv[i]; }
+        co.cmdline = cmdline.c_str();
+        auto need3 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        for (int i = 3; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-h" || a == "--help") { usage(); return 0; }
+            else if (a == "-i" || a == "--input-dir") co.input_dir = need3(i);
+            else if (a == "-r" || a == "--rad-dir") co.rad_dir = need3(i);
+            else if (a == "-t" || a == "--threads") co.num_threads = (uint32_t)std::atoi(need3(i));
+            else if (a == "-c" || a == "--compress") co.compress = 1;
+            else if (a == "-m" || a == "--max-records") co.max_records = (uint32_t)std::strtoul(need3(i), nullptr, 10);   // one device fill: without effect
+            else if (a == "--device") co.device = (uint32_t)std::atoi(need3(i));
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!co.input_dir || !co.rad_dir) {
+            std::fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", co.input_dir ? "" : "  --input-dir <INPUTDIR>\n", co.rad_dir ? "" : "  --rad-dir <RADDIR>\n");
+            usage();
+            return 2;
+        }
+        for (const char* flag : {"-i", "-r"}) {   // clap's pathbuf_directory_exists_validator (main.rs:907-912)
+            const char* dir = flag[1] == 'i' ? co.input_dir : co.rad_dir;
+            FILE* probe = std::fopen(dir, "r");
+            if (!probe) { std::fprintf(stderr, "error: invalid value '%s' for '%s': the directory does not exist\n", dir, flag[1] == 'i' ? "--input-dir <INPUTDIR>" : "--rad-dir <RADDIR>"); return 2; }
+            std::fclose(probe);
+        }
+        const int rc = afq_atac_collate(&co);
+        if (rc) { std::fprintf(stderr, "afquant atac collate failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         return 0;
     }
     if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "deduplicate") == 0) {   // src/main.rs:942-956, atac/run.rs:128-169

@@ -47,29 +47,6 @@ __device__ __forceinline__ uint32_t collate_find(const CollateArgs& a, uint64_t 
     return kSortNoRank;
 }
 
-// A little-endian byte stream to an address of any alignment.  At most 7 bytes wait in acc; whatever is stored is stored with
-// the widest naturally aligned store that holds only bytes of this stream.
-struct ByteOut {
-    uint8_t* p; uint64_t acc; uint32_t n;
-    __device__ __forceinline__ void step() {   // store 1, 2 or 4 of the waiting bytes (n >= 1; 4 only when n >= 4)
-        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-        if (!mis && n >= 4) { *reinterpret_cast<uint32_t*>(p) = (uint32_t)acc; p += 4; acc >>= 32; n -= 4; }
-        else if (!(mis & 1u) && n >= 2) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)acc; p += 2; acc >>= 16; n -= 2; }
-        else { *p = (uint8_t)acc; p += 1; acc >>= 8; n -= 1; }
-    }
-    __device__ __forceinline__ void put(uint32_t v, uint32_t nb) {   // the low nb (1..4) bytes of v
-        if (nb < 4) v &= (1u << (8 * nb)) - 1u;
-        acc |= (uint64_t)v << (8 * n);
-        n += nb;
-        while (n >= 4) step();
-    }
-    __device__ __forceinline__ void put_field(uint64_t v, uint32_t width) {   // width 1, 2, 4 or 8
-        put((uint32_t)v, width < 4 ? width : 4);
-        if (width == 8) put((uint32_t)(v >> 32), 4);
-    }
-    __device__ __forceinline__ void flush() { while (n) step(); }
-};
-
 // the position bytes (e of them: 0, 1, 2, 4 or 8) behind an alignment word: from the tile, from global memory
 __device__ __forceinline__ void put_extra_lds(ByteOut& w, const uint32_t* tile, uint32_t off, uint32_t e) {
     if (!e) return;
@@ -404,6 +381,11 @@ void launch_collate_radix_pass(hipStream_t s, const uint64_t* src, uint64_t* dst
     AFQ_LAUNCH(k_collate_radix_hist, nb, kCollateRadixNT, s, src, n, shift, hist, nb);
     AFQ_LAUNCH(k_collate_scan1<uint32_t>, 1, kCollateRadixNT, s, hist, 256ull * nb);
     AFQ_LAUNCH(k_collate_radix_scatter, nb, kCollateRadixNT, s, src, dst, n, shift, hist, nb);
+}
+
+void launch_collate_excl_scan_u32(hipStream_t s, uint32_t* v, uint64_t n) {
+    if (!n) return;
+    AFQ_LAUNCH(k_collate_scan1<uint32_t>, 1, kCollateRadixNT, s, v, n);
 }
 
 void launch_collate_scan(hipStream_t s, const uint64_t* sorted, const uint2* rec, uint32_t n, uint64_t* block_sum, uint64_t* ex, uint64_t* dest) {

@@ -1005,6 +1005,25 @@ int write_unmapped_collated(const std::string& rd, const std::string& in, const 
     for (auto& kv : cnt) { std::fwrite(&kv.first, 8, 1, f.get()); std::fwrite(&kv.second, 4, 1, f.get()); }
     return 0;
 }
+// offset of the value of the TOP-LEVEL "key" of a JSON object (gpl_options repeats some names), or npos
+size_t json_top_level_value(const std::string& gjs, const char* key) {
+    const std::string k = key;
+    int depth = 0;
+    for (size_t i = 0; i < gjs.size(); ++i) {
+        const char ch = gjs[i];
+        if (ch == '{' || ch == '[') ++depth;
+        else if (ch == '}' || ch == ']') --depth;
+        else if (ch == '"') {
+            size_t e = i + 1;
+            while (e < gjs.size() && gjs[e] != '"') e += gjs[e] == '\\' ? 2 : 1;
+            const size_t after = gjs.find_first_not_of(" \t\r\n", e + 1);
+            if (depth == 1 && after != std::string::npos && gjs[after] == ':' && gjs.compare(i + 1, e - i - 1, k) == 0 && e - i - 1 == k.size())
+                return gjs.find_first_not_of(" \t\r\n", after + 1);
+            i = e;
+        }
+    }
+    return std::string::npos;
+}
 }  // namespace
 
 int afq_atac_sort(const afq_atac_sort_opts* o) {
@@ -1177,24 +1196,7 @@ int afq_collate(const afq_collate_opts* o) {
     std::vector<uint8_t> gj;
     if (!read_file(in + "/generate_permit_list.json", gj)) return hfail(AFQ_ERR_BAD_INPUT, "could not open generate_permit_list.json in \"" + in + "\"");
     const std::string gjs(gj.begin(), gj.end());
-    auto value_at = [&](const char* key) -> size_t {   // offset of the value of the TOP-LEVEL "key" (gpl_options repeats some names), or npos
-        const std::string k = key;
-        int depth = 0;
-        for (size_t i = 0; i < gjs.size(); ++i) {
-            const char ch = gjs[i];
-            if (ch == '{' || ch == '[') ++depth;
-            else if (ch == '}' || ch == ']') --depth;
-            else if (ch == '"') {
-                size_t e = i + 1;
-                while (e < gjs.size() && gjs[e] != '"') e += gjs[e] == '\\' ? 2 : 1;
-                const size_t after = gjs.find_first_not_of(" \t\r\n", e + 1);
-                if (depth == 1 && after != std::string::npos && gjs[after] == ':' && gjs.compare(i + 1, e - i - 1, k) == 0 && e - i - 1 == k.size())
-                    return gjs.find_first_not_of(" \t\r\n", after + 1);
-                i = e;
-            }
-        }
-        return std::string::npos;
-    };
+    auto value_at = [&](const char* key) { return json_top_level_value(gjs, key); };
     auto is_true = [&](size_t v) { return v != std::string::npos && gjs.compare(v, 4, "true") == 0; };
     if (value_at("version_str") == std::string::npos)
         return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
@@ -1244,7 +1246,7 @@ int afq_collate(const afq_collate_opts* o) {
     if (P.file_tag_vals.count("num_barcodes") && P.file_tag_vals["num_barcodes"] > 1)
         return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode RAD files (num_barcodes > 1) are not supported");
     if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len"))
-        return hfail(AFQ_ERR_UNSUPPORTED, "collate: this is a scATAC RAD file; `atac collate` is not supported (use `atac sort`)");
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: this is a scATAC RAD file; use `atac collate`");
     if (has_tag(P.aln_tags, "as") && has_tag(P.aln_tags, "start") && has_tag(P.aln_tags, "end"))
         return hfail(AFQ_ERR_UNSUPPORTED, "collate: long-read RAD records (alignment tags as, start, end) are not supported");
     if (P.read_tags.size() != 2 || P.read_tags[0].name != "b" || P.read_tags[1].name != "u" || !P.bc_bytes || !P.umi_bytes)
@@ -1320,6 +1322,128 @@ int afq_collate(const afq_collate_opts* o) {
                  (unsigned long long)cells.size());
     std::fprintf(stderr, "kept %llu of %llu alignments; %llu output bytes\n", (unsigned long long)st.n_alignments_kept, (unsigned long long)st.n_alignments_in,
                  (unsigned long long)st.out_bytes);
+    return 0;
+}
+
+// `atac collate` (src/atac/collate.rs, src/main.rs:905-922): map.collated.rad with one chunk per cell of permit_freq.bin that kept a
+// record, in the order (count descending, barcode ascending); a record is kept iff it has one alignment and its barcode is in the
+// correction map.  libradicl's filter (dump_corrected_cb_chunk_to_temp_file_atac) is not among the reference's sources: the rule is
+// restated from collate.rs's own comments (:719-723, :869-892).
+int afq_atac_collate(const afq_atac_collate_opts* o) {
+    if (!o || !o->input_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (!o->rad_dir) return hfail(AFQ_ERR_INVALID_ARG, "the RAD directory (-r) is required");
+    if (o->compress) return hfail(AFQ_ERR_UNSUPPORTED, "compressed output is not supported");
+    const std::string in = o->input_dir, rd = o->rad_dir;
+    // ---- generate_permit_list.json (atac/collate.rs:80-106, 235-245)
+    std::vector<uint8_t> gj;
+    if (!read_file(in + "/generate_permit_list.json", gj)) return hfail(AFQ_ERR_BAD_INPUT, "could not open generate_permit_list.json in \"" + in + "\"");
+    const std::string gjs(gj.begin(), gj.end());
+    if (json_top_level_value(gjs, "version_str") == std::string::npos)
+        return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
+    // ---- permit_freq.bin: the cells and their order (atac/collate.rs:118-158)
+    std::vector<uint8_t> pf;
+    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 24) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
+    uint64_t pf_ver, bc_len, n_freq;
+    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8); std::memcpy(&n_freq, pf.data() + 16, 8);
+    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
+    if (n_freq != (pf.size() - 24) / 16 || (pf.size() - 24) % 16) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize barcode to frequency map.");
+    std::vector<std::pair<uint64_t, uint64_t>> freq(n_freq);   // (barcode, count)
+    for (uint64_t i = 0; i < n_freq; ++i) { std::memcpy(&freq[i].first, pf.data() + 24 + 16 * i, 8); std::memcpy(&freq[i].second, pf.data() + 32 + 16 * i, 8); }
+    std::sort(freq.begin(), freq.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });   // :158
+    std::vector<uint64_t> cells(n_freq);
+    for (uint64_t i = 0; i < n_freq; ++i) cells[i] = freq[i].first;
+    uint64_t num_chunks = 0;
+    {
+        const size_t v = json_top_level_value(gjs, "num-chunks");
+        if (v == std::string::npos) return hfail(AFQ_ERR_BAD_INPUT, "num-chunks key not present");
+        char* e = nullptr;
+        num_chunks = std::strtoull(gjs.c_str() + v, &e, 10);
+        if (e == gjs.c_str() + v) return hfail(AFQ_ERR_BAD_INPUT, "Error parsing num-chunks");
+    }
+    // ---- the correction map (atac/collate.rs:453-495), the unmapped counts (a missing file is an empty map: the library aborts nowhere)
+    std::vector<uint64_t> obs, cor;
+    if (int rc2 = load_corrections(in, bc_len, "correction plan does not match this ATAC input", "ATAC collation", obs, cor)) return rc2;
+    if (int rc2 = write_unmapped_collated(rd, in, obs, cor, true)) return rc2;
+    // ---- map.rad
+    if (!file_exists(rd)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + rd + "\" does not exist");
+    PhaseClock pc;
+    MappedFile mf;
+    if (!mf.open(rd + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open input RAD file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    static const struct { const char* name; uint8_t type; } kAln[4] = {{"ref", 3}, {"type", 1}, {"start_pos", 3}, {"frag_len", 2}};
+    bool atac = P.read_tags.size() == 1 && P.read_tags[0].name == "b" && P.bc_bytes && P.aln_tags.size() == 4;
+    for (size_t i = 0; atac && i < 4; ++i) atac = P.aln_tags[i].name == kAln[i].name && P.aln_tags[i].type == kAln[i].type;
+    if (!atac)
+        return hfail(AFQ_ERR_UNSUPPORTED, "atac collate: this is not a scATAC RAD file (one integer read tag b; alignment tags ref:u32, type:u8, start_pos:u32, frag_len:u16); use `collate`");
+    // ---- exactly num-chunks chunk headers
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
+    pc.lap("metadata + maps + chunk table");
+    // ---- the device: one fill
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    const uint64_t span0 = chunk_off.empty() ? P.first_chunk : chunk_off[0];
+    std::vector<uint64_t> rel(chunk_off.size());
+    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    uint8_t* ob = nullptr; uint64_t on = 0, n_out = 0, *ooff = nullptr; uint32_t *onrec = nullptr, *ocell = nullptr;
+    afq_atac_collate_stats st{};
+    rc = afq_atac_collate_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, 0, obs.data(), cor.data(), obs.size(),
+                              cells.data(), cells.size(), &ob, &on, &n_out, &ooff, &onrec, &ocell, &st);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer { void *a, *b, *c, *d; ~Freer() { afq_free(a); afq_free(b); afq_free(c); afq_free(d); } } fr{ob, ooff, onrec, ocell};
+    pc.lap("device: atac collate");
+    if (o->stats_out) *o->stats_out = st;
+    // ---- map.collated.rad: the input's prelude with num_chunks = the chunks written (atac/collate.rs:896-916), then the chunks
+    const std::string out_path = in + "/map.collated.rad";
+    {
+        FilePtr f(std::fopen(out_path.c_str(), "wb"));
+        bool ok = (bool)f;
+        if (ok) {
+            std::vector<uint8_t> hdr(rad, rad + P.first_chunk);
+            std::memcpy(hdr.data() + P.num_chunks_at, &n_out, 8);
+            ok = std::fwrite(hdr.data(), 1, hdr.size(), f.get()) == hdr.size();
+            for (uint64_t off = 0; ok && off < on;) {
+                const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
+                ok = std::fwrite(ob + off, 1, len, f.get()) == len;
+                off += len;
+            }
+            ok = ok && std::fflush(f.get()) == 0;
+        }
+        if (!ok) { f.reset(); std::remove(out_path.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + out_path); }
+    }
+    {   // atac/collate.rs:337-352
+        FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
+        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false\n}", json_escape(o->cmdline ? o->cmdline : "").c_str());
+    }
+    pc.lap("map.collated.rad");
+    std::fprintf(stderr, "deserialized correction map of length : %llu\n", (unsigned long long)obs.size());
+    std::fprintf(stderr, "collated %llu of %llu records (%llu without a mapping, %llu with more than 1 mapping, %llu with a barcode that is not in the correction map); %llu output bytes\n",
+                 (unsigned long long)st.n_kept, (unsigned long long)st.n_records, (unsigned long long)st.n_unmapped, (unsigned long long)st.n_multimapped,
+                 (unsigned long long)st.n_uncorrected, (unsigned long long)st.out_bytes);
+    std::fprintf(stderr, "writing num output chunks (%llu) to header\n", (unsigned long long)n_out);
+    if (st.n_cells_empty)   // atac/collate.rs:884-892
+        std::fprintf(stderr, "%llu of %llu retained barcodes produced no collated records (every read was unmapped or multi-mapping) and are absent from the output.\n",
+                     (unsigned long long)st.n_cells_empty, (unsigned long long)cells.size());
     return 0;
 }
 

@@ -308,6 +308,32 @@ void launch_collate_scan(hipStream_t s, const uint64_t* sorted, const uint2* rec
 // chunk c: off[c] (off[n_cells]: the end), nrec[c], and its (nbytes, nrec) header into out
 void launch_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, const uint64_t* ex, uint32_t n_cells, uint64_t* off, uint32_t* nrec, uint8_t* out,
                           DevStatus* st);
+// in-place exclusive scan of n words by one workgroup (the radix passes' digit counts; `atac collate`'s non-empty-cell flags)
+void launch_collate_excl_scan_u32(hipStream_t s, uint32_t* v, uint64_t n);
+// `atac collate`: the records of an UNCOLLATED scATAC RAD with exactly one alignment and a barcode of the correction map, barcode-
+// corrected, one output chunk per cell THAT RECEIVED A RECORD (afq_atac_collate.hip).  The walk is k_sort_parse's (kSortParseTile,
+// kSortParseHalo), the placement collate's radix passes; a kept record is R = 4 + bc_bytes + 11 bytes, so the layout needs no length scan.
+struct AtacCollateArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks; uint32_t bc_bytes;
+    const uint64_t* tab_key; const uint32_t* tab_val; uint32_t tab_mask; uint32_t ones_cell;   // observed barcode -> index of its corrected barcode in `cells`
+    uint32_t n_cells;        // (also the cell word of a record that is dropped: it sorts behind every cell)
+    uint32_t* cell_of;       // a slot per record of the chunk table, in input order: the record's cell, n_cells if it is dropped
+    uint64_t* key;           // measure: cell << 32 | slot of every slot
+    uint32_t* chunk_stat;    // measure: [n_chunks][8]: records, na == 0, na > 1, not in the map, kept, 0, 0, 0
+    const uint64_t* cells;   // write: [n_cells] the corrected barcodes
+    const uint64_t* dest;    // write: [slot] byte offset of the record in `out`
+    uint8_t* out;
+    DevStatus* st;
+};
+void launch_atac_collate_measure(hipStream_t s, const AtacCollateArgs& a);
+void launch_atac_collate_write(hipStream_t s, const AtacCollateArgs& a);
+// sorted: the n sort words in (cell, slot) order.  Cell c's run [lo, hi): first[c] = lo (first[n_cells]: the number of kept records),
+// flag[c] = (hi > lo), flag[n_cells] = 0
+void launch_atac_collate_runs(hipStream_t s, const uint64_t* sorted, uint32_t n, uint32_t n_cells, uint32_t* first, uint32_t* flag);
+// rank: the exclusive scan of flag (rank[n_cells] = n_out).  Output chunk j = rank[c] of a non-empty cell c: off[j] = R first[c] + 8 j,
+// nrec[j], cell[j] = c, and its (nbytes, nrec) header into out; dest[slot] = R i + 8 (rank[cell] + 1) for sorted position i
+void launch_atac_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, uint32_t n_cells, uint32_t rec_bytes, const uint32_t* first, const uint32_t* rank,
+                               uint64_t* off, uint32_t* nrec, uint32_t* cell, uint64_t* dest, uint8_t* out, DevStatus* st);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

@@ -1,5 +1,6 @@
 // afq_rad_walk.h — what the wave-per-chunk walks of an uncollated RNA RAD share (k_gpl_parse, afq_gpl.hip; the collate walks,
-// afq_collate.hip): checked loads of the input buffer, unaligned reads of the LDS tile, the wave's LDS fence, the orientation test.
+// afq_collate.hip; the scATAC collate walks, afq_atac_collate.hip): checked loads of the input buffer, unaligned reads of the LDS
+// tile, the wave's LDS fence, the orientation test, and ByteOut, the byte stream both collate write walks store through.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,5 +36,28 @@ __device__ __forceinline__ void gpl_wave_lds_sync() {
 }
 // does alignment word w speak for the expected orientation?  (bit 31 set: the read maps forward)
 __device__ __forceinline__ bool gpl_word_fits(uint32_t w, uint32_t ori) { return ori == kGplOriFw ? (w >> 31) != 0 : (w >> 31) == 0; }
+
+// A little-endian byte stream to an address of any alignment.  At most 7 bytes wait in acc; whatever is stored is stored with
+// the widest naturally aligned store that holds only bytes of this stream.
+struct ByteOut {
+    uint8_t* p; uint64_t acc; uint32_t n;
+    __device__ __forceinline__ void step() {   // store 1, 2 or 4 of the waiting bytes (n >= 1; 4 only when n >= 4)
+        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+        if (!mis && n >= 4) { *reinterpret_cast<uint32_t*>(p) = (uint32_t)acc; p += 4; acc >>= 32; n -= 4; }
+        else if (!(mis & 1u) && n >= 2) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)acc; p += 2; acc >>= 16; n -= 2; }
+        else { *p = (uint8_t)acc; p += 1; acc >>= 8; n -= 1; }
+    }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t nb) {   // the low nb (1..4) bytes of v
+        if (nb < 4) v &= (1u << (8 * nb)) - 1u;
+        acc |= (uint64_t)v << (8 * n);
+        n += nb;
+        while (n >= 4) step();
+    }
+    __device__ __forceinline__ void put_field(uint64_t v, uint32_t width) {   // width 1, 2, 4 or 8
+        put((uint32_t)v, width < 4 ? width : 4);
+        if (width == 8) put((uint32_t)(v >> 32), 4);
+    }
+    __device__ __forceinline__ void flush() { while (n) step(); }
+};
 
 }  // namespace afq

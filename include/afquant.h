@@ -406,6 +406,46 @@ int afq_collate_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const ui
 void afq_collate_limits(uint32_t out[4]);
 
 /*
+ * `atac collate`, the device half (src/atac/collate.rs of the reference): the records of an UNCOLLATED scATAC RAD routed by
+ * corrected barcode into one chunk per cell that receives a record.
+ *
+ * `bytes` / `chunk_off` / bytes_on_device / the record layout (`na u32, barcode (bc_bytes), na x (ref u32, type u8, start_pos u32,
+ * frag_len u16)`) and `observed` -> `corrected` are afq_atac_sort_rad's; `cells` (n_cells, distinct) are the output cells IN OUTPUT
+ * ORDER, and every corrected barcode must be one of them.
+ *
+ * A record is kept iff it has exactly one alignment and its barcode is an observed key: no orientation, map-type or range test
+ * (collate.rs:719-723).  It is written as R = 4 + bc_bytes + 11 bytes: na = 1, the CORRECTED barcode, the 11 alignment bytes as read.
+ *
+ * Out (malloc'd; afq_free): out_bytes = one chunk (`nbytes u32, nrec u32` + its records) per cell that kept a record, in the order
+ * of `cells` - a cell without a kept record is ABSENT; *out_n_chunks of them; out_chunk_off[n_out + 1]; out_nrec[n_out];
+ * out_cell[n_out] = the index into `cells` of output chunk j.  Inside a chunk the records stand in input order (chunk index, then
+ * record index): the output is a function of the input alone, byte for byte and run to run.
+ *
+ * AFQ_ERR_BAD_INPUT: a chunk outside `bytes`; records that do not tile nbytes or do not number nrec ("chunk i": nothing outside
+ * `bytes` is read, the context stays usable); two targets for one observed barcode; a corrected barcode that is no cell; two cells
+ * with one barcode.  AFQ_ERR_UNSUPPORTED: 2^32 records or more, more than 2^32 - 2 cells, 2^30 correction entries or more, an output
+ * chunk of 4 GiB or more (the cell is named).  AFQ_ERR_OOM (with the sizes) when input, output, 20 bytes a record and the tables do
+ * not fit the device: one call is one device fill.
+ */
+typedef struct afq_atac_collate_stats {
+    uint64_t n_records;       /* records of the chunks                                   */
+    uint64_t n_unmapped;      /* ... without an alignment                                */
+    uint64_t n_multimapped;   /* ... with more than one                                  */
+    uint64_t n_uncorrected;   /* ... with one alignment and a barcode not in the map     */
+    uint64_t n_kept;          /* records written                                         */
+    uint64_t n_cells_out;     /* chunks written: cells that kept a record                */
+    uint64_t n_cells_empty;   /* cells that kept none (n_cells - n_cells_out)            */
+    uint64_t out_bytes;       /* length of out_bytes                                     */
+} afq_atac_collate_stats;
+int afq_atac_collate_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                         int bytes_on_device, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corrections, const uint64_t* cells,
+                         uint64_t n_cells, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t* out_n_chunks, uint64_t** out_chunk_off,
+                         uint32_t** out_nrec, uint32_t** out_cell, afq_atac_collate_stats* stats);
+/* out[0] = bytes of a chunk an `atac collate` walk stages per trip, out[1] = bytes staged behind them (both are the `atac sort`
+ * parse's), out[2] = bytes of an alignment (11), out[3] = keys a workgroup of a radix pass takes.  For tests. */
+void afq_atac_collate_limits(uint32_t out[4]);
+
+/*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the
  * number of kernels, or a negative error.  `name[i]` points to static storage.

@@ -107,6 +107,26 @@ typedef struct afq_collate_opts {
  * "expected to collate N records but retained M", and no RAD is left behind. */
 int afq_collate(const afq_collate_opts* opts);
 
+/* The options of `alevin-fry atac collate` (src/main.rs:905-922). */
+struct afq_atac_collate_stats;
+typedef struct afq_atac_collate_opts {
+    const char* input_dir;      /* -i : output directory of `atac generate-permit-list`; map.collated.rad, collate.json and
+                                        unmapped_bc_count_collated.bin are written here                                    */
+    const char* rad_dir;        /* -r : the mapper's directory: map.rad, unmapped_bc_count.bin (optional)                  */
+    uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED): the project has a snappy decoder and no encoder     */
+    uint32_t max_records;       /* -m : accepted, without effect (it sizes the reference's host buffers)                   */
+    uint32_t device;
+    const char* cmdline;        /* optional: goes into collate.json                                                        */
+    struct afq_atac_collate_stats* stats_out;   /* optional */
+} afq_atac_collate_opts;
+/* Runs the whole `atac collate` sub-command (src/atac/collate.rs) in ONE device fill: the first `num-chunks` chunks of map.rad; one
+ * chunk per cell of permit_freq.bin THAT KEPT A RECORD, in the order (count descending, barcode ascending); a record is kept iff it
+ * has one alignment and its barcode is in the correction map; input order inside a chunk; the header's num_chunks is the number of
+ * chunks written.  An RNA prelude and compressed output are AFQ_ERR_UNSUPPORTED.  A missing unmapped_bc_count.bin is an empty map
+ * (the reference panics).  map.collated.rad is written only after the device call succeeded: a failed run leaves none behind. */
+int afq_atac_collate(const afq_atac_collate_opts* opts);
+
 /* The options of `alevin-fry generate-permit-list` (src/main.rs:170-269, 392-577; GenPermitListOpts, src/prog_opts.rs:86-160) for
  * single-barcode RNA RAD files.  Exactly one filter method is given. */
 enum { AFQ_GPL_KNEE = 0, AFQ_GPL_EXPECT = 1, AFQ_GPL_FORCE = 2, AFQ_GPL_VALID_BC = 3, AFQ_GPL_UNFILTERED = 4 };
