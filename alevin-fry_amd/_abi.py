@@ -130,6 +130,8 @@ EXPORTS = [
     "afq_gpl_correct",
     "afq_gpl_limits",
     "afq_gpl_table_slot",
+    "afq_atac_gpl_hist_rad",
+    "afq_atac_gpl_limits",
     "afq_collate_rad",
     "afq_collate_limits",
     "afq_atac_collate_rad",
@@ -162,6 +164,18 @@ class AfqGplHistStats(C.Structure):
 class AfqGplCorrectionStats(C.Structure):
     _fields_ = [("exact_distinct", C.c_uint64), ("exact_reads", C.c_uint64), ("corrected_distinct", C.c_uint64), ("corrected_reads", C.c_uint64),
                 ("ambiguous_distinct", C.c_uint64), ("ambiguous_reads", C.c_uint64), ("not_found_distinct", C.c_uint64), ("not_found_reads", C.c_uint64)]
+
+
+class AfqAtacGplHistStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_binned", C.c_uint64),
+                ("max_ambig", C.c_uint64), ("max_bin", C.c_uint64)]
+
+
+class AfqAtacGplOpts(C.Structure):
+    """afq_atac_gpl_opts of include/afquant_host.h (afq_atac_generate_permit_list)."""
+    _fields_ = [("input_dir", C.c_char_p), ("output_dir", C.c_char_p), ("list_file", C.c_char_p), ("min_reads", C.c_uint64), ("rc", C.c_uint32),
+                ("num_threads", C.c_uint32), ("frequency", C.c_uint32), ("neighborhood", C.c_uint32), ("conf_num", C.c_uint64), ("conf_den", C.c_uint64),
+                ("device", C.c_uint32), ("fill_bytes", C.c_uint64), ("cmdline", C.c_char_p), ("stats_out", C.POINTER(AfqAtacGplHistStats))]
 
 
 class AfqCollateStats(C.Structure):

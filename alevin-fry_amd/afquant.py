@@ -312,6 +312,15 @@ def load_library(path: str = LIB_PATH):
     lib.afq_gpl_limits.restype = None
     lib.afq_gpl_table_slot.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, p(C.c_uint32), p(C.c_uint32)]
     lib.afq_gpl_table_slot.restype = None
+    lib.afq_atac_gpl_hist_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), C.c_uint32,
+                                          C.c_uint32, p(C.c_uint64), p(p(C.c_uint64)), p(p(C.c_uint64)), p(p(C.c_uint64)), p(_abi.AfqAtacGplHistStats)]
+    lib.afq_atac_gpl_hist_rad.restype = C.c_int
+    lib.afq_atac_gpl_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_atac_gpl_limits.restype = None
+    lib.afq_atac_generate_permit_list.argtypes = [p(_abi.AfqAtacGplOpts)]
+    lib.afq_atac_generate_permit_list.restype = C.c_int
+    lib.afq_host_last_error.argtypes = []
+    lib.afq_host_last_error.restype = C.c_char_p
     lib.afq_collate_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                     p(C.c_uint64), p(C.c_uint64), C.c_uint64, p(C.c_uint64), C.c_uint64, p(p(C.c_uint8)), p(C.c_uint64), p(p(C.c_uint64)),
                                     p(p(C.c_uint32)), p(_abi.AfqCollateStats)]
@@ -379,6 +388,35 @@ def atac_collate_limits():
     out = (C.c_uint32 * 4)()
     load_library().afq_atac_collate_limits(out)
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "aln_bytes": int(out[2]), "radix_block": int(out[3])}
+
+
+def atac_gpl_limits():
+    """afq_atac_gpl_limits: {"parse_tile", "parse_halo", "private_bins"} of the `atac generate-permit-list` record pass - bytes a walk
+    stages per trip, bytes staged behind them, bins a workgroup counts privately in LDS (0: the bins are counted in global memory)."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_atac_gpl_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "private_bins": int(out[2])}
+
+
+def atac_generate_permit_list(input_dir, output_dir, list_file, min_reads: int = 10, rc: bool = True, num_threads: int = 8, correction="unique",
+                              neighborhood="hamming-1", confidence=(0, 0), device: int = 0, fill_bytes: int = 0, cmdline: str = ""):
+    """afq_atac_generate_permit_list: the whole `atac generate-permit-list` step from the mapper's directory (map.rad) and an unfiltered
+    barcode list into output_dir (permit_freq.bin, permit_map.bin, correction_plan.bin, bin_recs.bin, bin_lens.bin,
+    generate_permit_list.json).  confidence (0, 0) is the ATAC default 9/10.  Returns the record pass's stats as a dict; raises AfqError."""
+    lib = load_library()
+    st = _abi.AfqAtacGplHistStats()
+    o = _abi.AfqAtacGplOpts()
+    o.input_dir, o.output_dir, o.list_file = os.fsencode(input_dir), os.fsencode(output_dir), os.fsencode(list_file)
+    o.min_reads, o.rc, o.num_threads = int(min_reads), 1 if rc else 0, int(num_threads)
+    o.frequency = _abi.GPL_RESOLUTIONS[correction] if isinstance(correction, str) else int(correction)
+    o.neighborhood = _abi.GPL_NEIGHBORHOODS[neighborhood] if isinstance(neighborhood, str) else int(neighborhood)
+    o.conf_num, o.conf_den = int(confidence[0]), int(confidence[1])
+    o.device, o.fill_bytes, o.cmdline = int(device), int(fill_bytes), cmdline.encode()
+    o.stats_out = C.pointer(st)
+    rc_ = lib.afq_atac_generate_permit_list(C.byref(o))
+    if rc_ != 0:
+        raise AfqError(rc_, (lib.afq_host_last_error() or b"").decode())
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
 
 def gpl_table_slot(barcode, n_kept, bc_bytes: int = 8):
@@ -661,6 +699,36 @@ class Quantifier:
     def gpl_limits():
         """The generate-permit-list parse's limits (module-level gpl_limits)."""
         return gpl_limits()
+
+    def atac_gpl_hist_rad(self, chunk_bytes, chunk_off, bin_base, bc_bytes: int = 4, bin_size: int = 100000, d_ptr: int = 0, n_bytes: int = 0):
+        """afq_atac_gpl_hist_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the device)
+        and bin_base[ref_count + 1] (the first bin of every reference, ascending from 0); (bc, count, bins, stats dict) out: the distinct
+        barcodes of ALL records ascending, their u64 counts, the u64 position bins of the records with one alignment, and the tallies."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        bb = np.ascontiguousarray(bin_base, dtype=np.uint64)
+        if len(bb) < 1:
+            raise ValueError("bin_base holds ref_count + 1 entries")
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p = C.POINTER(C.c_uint64)
+        o_n, o_bc, o_cnt, o_bins, st = C.c_uint64(), u64p(), u64p(), u64p(), _abi.AfqAtacGplHistStats()
+        self._check(self.lib.afq_atac_gpl_hist_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), bc_bytes, on_dev, bb.ctypes.data_as(u64p), len(bb) - 1,
+                                                   int(bin_size), C.byref(o_n), C.byref(o_bc), C.byref(o_cnt), C.byref(o_bins), C.byref(st)))
+        n, nbins = int(o_n.value), int(bb[-1])
+        try:
+            mk = lambda p_, k: (np.ctypeslib.as_array(p_, shape=(k,)).astype(np.uint64, copy=True) if k else np.zeros(0, np.uint64))
+            return mk(o_bc, n), mk(o_cnt, n), mk(o_bins, nbins), {k: int(getattr(st, k)) for k, _ in st._fields_}
+        finally:
+            for q in (o_bc, o_cnt, o_bins):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def atac_gpl_limits():
+        """The `atac generate-permit-list` record pass's limits (module-level atac_gpl_limits)."""
+        return atac_gpl_limits()
 
     def collate_rad(self, chunk_bytes, chunk_off, observed, corrected, cells, bc_bytes: int = 4, umi_bytes: int = 4, expected_ori="both", d_ptr: int = 0,
                     n_bytes: int = 0):

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <condition_variable>
 #include <mutex>
 #include <optional>
@@ -60,14 +61,15 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
                                            "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit",
                                            "k_gpl_parse", "k_gpl_count", "k_gpl_compact", "k_gpl_table", "k_gpl_correct",
                                            "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write",
-                                           "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write"};
+                                           "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write",
+                                           "k_atac_gpl_parse", "k_atac_gpl_bins"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -204,10 +206,11 @@ struct AtacSortBufs {
 // afq_gpl_hist_rad's and afq_gpl_correct's
 struct GplBufs {
     DevBuf chunks, bc, cstat, status, tkey, tcnt, ones, okey, ocnt, nout;            // histogram
+    DevBuf bbase, bins, bins64, bmax;                                                // afq_atac_gpl_hist_rad's position bins
     DevBuf obs, obscnt, ret, retcnt, idx, rkey, rval, dec, tgt, stats, tcount, cstatus;   // correction
     std::vector<DevBuf*> all() {
         return {&chunks, &bc, &cstat, &status, &tkey, &tcnt, &ones, &okey, &ocnt, &nout, &obs, &obscnt, &ret, &retcnt, &idx, &rkey, &rval, &dec, &tgt,
-                &stats, &tcount, &cstatus};
+                &stats, &tcount, &cstatus, &bbase, &bins, &bins64, &bmax};
     }
 };
 
@@ -2802,6 +2805,54 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     return 0;
 }
 
+// The barcode column of a parse (c->gpl.bc; chunk i's first cstat[4 i + 1] slots) through the counting table: the distinct barcodes
+// with their counts, ascending.  afq_gpl_hist_rad's and afq_atac_gpl_hist_rad's.
+static int gpl_count_sorted(afq_ctx* c, const char* who, uint32_t n_chunks, uint64_t n_kept, uint32_t bc_bytes, HipLatch& T, const std::function<int()>& hip_fail,
+                            std::vector<std::pair<uint64_t, uint64_t>>& pairs) {
+    auto& B = c->gpl;
+    hipStream_t s = c->stream;
+    DevStatus st{};
+    const uint64_t cap = gpl_table_capacity(n_kept, bc_bytes);
+    T(B.tkey.ensure(8 * cap)); T(B.tcnt.ensure(8 * cap)); T(B.okey.ensure(4 * cap)); T(B.ocnt.ensure(4 * cap));   // (at most cap / 2 distinct barcodes)
+    if (!T.ok()) return hip_fail();
+    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.tcnt.p, 0, 8 * cap, s));
+    {
+        ScopedTimer t(c, K_GPL_COUNT, s);
+        launch_gpl_count(s, B.chunks.as<SortChunk>(), n_chunks, B.cstat.as<uint32_t>(), B.bc.as<uint64_t>(), B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(),
+                         (uint32_t)(cap - 1), B.ones.as<unsigned long long>(), B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_GPL_COMPACT, s);
+        launch_gpl_compact(s, B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(), cap, B.okey.as<uint64_t>(), B.ocnt.as<uint64_t>(), B.nout.as<uint32_t>());
+    }
+    T(hipGetLastError());
+    uint32_t n_tab = 0;
+    unsigned long long n_ones = 0;
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&n_tab, B.nout.p, 4, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&n_ones, B.ones.p, 8, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, std::string(who) + ": the counting table of " + std::to_string(cap) + " slots ran full (device status " + std::to_string(st.err_code) + ")"); }
+    if (n_tab > cap / 2) return fail(c, AFQ_ERR_HIP, std::string(who) + ": " + std::to_string(n_tab) + " keys in a table of " + std::to_string(cap) + " slots");
+    pairs.assign((size_t)n_tab + (n_ones ? 1 : 0), {0, 0});
+    {
+        std::vector<uint64_t> k(n_tab), n(n_tab);
+        if (n_tab) {
+            T(hipMemcpyAsync(k.data(), B.okey.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
+            T(hipMemcpyAsync(n.data(), B.ocnt.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
+            T(hipStreamSynchronize(s));
+        }
+        harvest_timers(c);
+        if (!T.ok()) return hip_fail();
+        for (uint32_t i = 0; i < n_tab; ++i) pairs[i] = {k[i], n[i]};
+        if (n_ones) pairs[n_tab] = {kSortEmptyKey, (uint64_t)n_ones};
+    }
+    std::sort(pairs.begin(), pairs.end());
+    return 0;
+}
+
 // `generate-permit-list` on the device (afq_gpl.hip): parse + orientation filter, counting table, compaction; the host sorts the
 // distinct barcodes.  And the correction decisions of distinct observed barcodes against a retained set.
 void afq_gpl_limits(uint32_t out[4]) {
@@ -2894,44 +2945,8 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
         S.n_records += cstat[4 * i]; S.n_compatible += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_long_records += cstat[4 * i + 3];
     }
     // ---- count, compact
-    const uint64_t cap = gpl_table_capacity(S.n_compatible, bc_bytes);
-    T(B.tkey.ensure(8 * cap)); T(B.tcnt.ensure(8 * cap)); T(B.okey.ensure(4 * cap)); T(B.ocnt.ensure(4 * cap));   // (at most cap / 2 distinct barcodes)
-    if (!T.ok()) return hip_fail();
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.tcnt.p, 0, 8 * cap, s));
-    {
-        ScopedTimer t(c, K_GPL_COUNT, s);
-        launch_gpl_count(s, B.chunks.as<SortChunk>(), n_chunks, B.cstat.as<uint32_t>(), B.bc.as<uint64_t>(), B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(),
-                         (uint32_t)(cap - 1), B.ones.as<unsigned long long>(), B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_GPL_COMPACT, s);
-        launch_gpl_compact(s, B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(), cap, B.okey.as<uint64_t>(), B.ocnt.as<uint64_t>(), B.nout.as<uint32_t>());
-    }
-    T(hipGetLastError());
-    uint32_t n_tab = 0;
-    unsigned long long n_ones = 0;
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_tab, B.nout.p, 4, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_ones, B.ones.p, 8, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: the counting table of " + std::to_string(cap) + " slots ran full (device status " + std::to_string(st.err_code) + ")"); }
-    if (n_tab > cap / 2) return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: " + std::to_string(n_tab) + " keys in a table of " + std::to_string(cap) + " slots");
-    std::vector<std::pair<uint64_t, uint64_t>> pairs((size_t)n_tab + (n_ones ? 1 : 0));
-    {
-        std::vector<uint64_t> k(n_tab), n(n_tab);
-        if (n_tab) {
-            T(hipMemcpyAsync(k.data(), B.okey.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
-            T(hipMemcpyAsync(n.data(), B.ocnt.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
-            T(hipStreamSynchronize(s));
-        }
-        harvest_timers(c);
-        if (!T.ok()) return hip_fail();
-        for (uint32_t i = 0; i < n_tab; ++i) pairs[i] = {k[i], n[i]};
-        if (n_ones) pairs[n_tab] = {kSortEmptyKey, (uint64_t)n_ones};
-    }
-    std::sort(pairs.begin(), pairs.end());
+    std::vector<std::pair<uint64_t, uint64_t>> pairs;
+    if (int rc = gpl_count_sorted(c, "afq_gpl_hist_rad", n_chunks, S.n_compatible, bc_bytes, T, hip_fail, pairs)) return rc;
     hc.lap("gpl: count + compact + sort");
     uint64_t total = 0;
     for (const auto& pr : pairs) total += pr.second;
@@ -2946,6 +2961,141 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     if (stats) *stats = S;
     H.release();
     *out_n = n_out; *out_bc = obc; *out_count = ocnt;
+    return 0;
+}
+
+// `atac generate-permit-list` on the device (afq_atac_gpl.hip): one walk for the barcode column, the largest na and the position
+// bins; the counting table and its compaction are afq_gpl_hist_rad's.
+void afq_atac_gpl_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSortParseTile; out[1] = kSortParseHalo; out[2] = 0; out[3] = 0;   // ([2]: the bins are counted in global memory, no workgroup holds any)
+}
+
+int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
+                          int bytes_on_device, const uint64_t* bin_base, uint32_t ref_count, uint32_t bin_size, uint64_t* out_n, uint64_t** out_bc,
+                          uint64_t** out_count, uint64_t** out_bins, afq_atac_gpl_hist_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !bin_base || !out_n || !out_bc || !out_count || !out_bins) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
+    if (!bin_size) return fail(c, AFQ_ERR_INVALID_ARG, "bin_size must be at least 1");
+    if (bin_base[0] != 0) return fail(c, AFQ_ERR_INVALID_ARG, "bin_base[0] must be 0");
+    for (uint32_t r = 0; r < ref_count; ++r)
+        if (bin_base[r + 1] < bin_base[r]) return fail(c, AFQ_ERR_INVALID_ARG, "bin_base must ascend (entry " + std::to_string(r + 1) + " is below the one in front)");
+    if (bin_base[ref_count] >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_gpl_hist_rad: 2^31 or more position bins (" + std::to_string(bin_base[ref_count]) + ")");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    const uint32_t n_bins = (uint32_t)bin_base[ref_count];
+    std::vector<uint32_t> bbase(std::max<uint32_t>(ref_count, 1), 0);
+    for (uint32_t r = 0; r < ref_count; ++r) bbase[r] = (uint32_t)bin_base[r];
+    // ---- chunk table
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
+    std::vector<SortChunk> chunks(n_chunks);
+    uint64_t n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    if (n_slots >= (1ull << 30))
+        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);
+    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 24 a slot of the largest table, 12 a bin)
+        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, bc_bytes) * 24,
+                       need_misc = nc1 * (sizeof(SortChunk) + 16) + 12ull * nb1 + 4ull * bbase.size();
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_atac_gpl_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
+                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables and bins > " +
+                        std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->gpl;
+    HipLatch T;
+    auto hip_fail = [&]() { return T.fail(c, "afq_atac_gpl_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_bins) + " bins)"); };
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
+    T(B.ones.ensure(8)); T(B.nout.ensure(4)); T(B.bbase.ensure(4ull * bbase.size())); T(B.bins.ensure(4ull * nb1)); T(B.bins64.ensure(8ull * nb1)); T(B.bmax.ensure(4));
+    if (!T.ok()) return hip_fail();
+    const uint8_t* d_bytes = bytes;
+    if (!bytes_on_device) {
+        T(c->d_bytes_own.ensure(n_bytes + 16));
+        if (!T.ok()) return hip_fail();
+        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
+        d_bytes = c->d_bytes_own.as<uint8_t>();
+    }
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    T(hipMemcpyAsync(B.bbase.p, bbase.data(), 4ull * bbase.size(), hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.ones.p, 0, 8, s));
+    T(hipMemsetAsync(B.nout.p, 0, 4, s));
+    T(hipMemsetAsync(B.bins.p, 0, 4ull * nb1, s));
+    T(hipMemsetAsync(B.bmax.p, 0, 4, s));
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    {
+        ScopedTimer t(c, K_AGPL_PARSE, s);
+        launch_atac_gpl_parse(s, AtacGplParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.bbase.as<uint32_t>(), ref_count, n_bins,
+                                                  bin_size, B.bc.as<uint64_t>(), B.bins.as<uint32_t>(), B.cstat.as<uint32_t>(), B.status.as<DevStatus>()});
+    }
+    {
+        ScopedTimer t(c, K_AGPL_BINS, s);
+        launch_atac_gpl_bins(s, B.bins.as<uint32_t>(), n_bins, B.bins64.as<uint64_t>(), B.bmax.as<uint32_t>());
+    }
+    T(hipGetLastError());
+    DevStatus st{};
+    uint32_t max_bin = 0;
+    std::vector<uint32_t> cstat(4ull * n_chunks);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&max_bin, B.bmax.p, 4, hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
+    hc.lap("atac gpl: parse + bins");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) {
+        harvest_timers(c);
+        const std::string who = std::to_string(st.err_cell);
+        switch (st.err_code) {
+            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+            case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a reference id is not below ref_count");
+            case kErrStartRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a start position's bin is not below the number of bins (" + std::to_string(n_bins) + ")");
+            default: return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: device status " + std::to_string(st.err_code));
+        }
+    }
+    afq_atac_gpl_hist_stats S{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        S.n_unmapped += cstat[4 * i]; S.n_records += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_multimapped += cstat[4 * i + 3];
+    }
+    S.n_binned = S.n_records - S.n_unmapped - S.n_multimapped;
+    S.max_bin = max_bin;
+    if (S.n_records != n_slots)
+        return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: the parse saw " + std::to_string(S.n_records) + " of " + std::to_string(n_slots) + " records");
+    // ---- count, compact
+    std::vector<std::pair<uint64_t, uint64_t>> pairs;
+    if (int rc = gpl_count_sorted(c, "afq_atac_gpl_hist_rad", n_chunks, S.n_records, bc_bytes, T, hip_fail, pairs)) return rc;
+    hc.lap("atac gpl: count + compact + sort");
+    uint64_t total = 0;
+    for (const auto& pr : pairs) total += pr.second;
+    if (total != S.n_records)
+        return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_records) + " records");
+    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    HostOuts H;
+    uint64_t* obc = (uint64_t*)H.mallocd(8 * o1);
+    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
+    uint64_t* obins = n_bins ? (uint64_t*)H.mallocd(8ull * n_bins) : nullptr;
+    if (!obc || !ocnt || (n_bins && !obins))
+        return fail(c, AFQ_ERR_OOM, "afq_atac_gpl_hist_rad: host allocation failed (" + std::to_string(16 * o1 + 8ull * n_bins) + " bytes of histogram and bins)");
+    for (uint64_t i = 0; i < n_out; ++i) { obc[i] = pairs[i].first; ocnt[i] = pairs[i].second; }
+    if (n_bins) {
+        T(hipMemcpyAsync(obins, B.bins64.p, 8ull * n_bins, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (!T.ok()) return hip_fail();
+    }
+    if (stats) *stats = S;
+    H.release();
+    *out_n = n_out; *out_bc = obc; *out_count = ocnt; *out_bins = obins;
     return 0;
 }
 

@@ -93,7 +93,7 @@ constexpr uint32_t kErrLabelHash = 6;    // two different ref lists with the sam
 constexpr uint32_t kErrPugLimit = 7;     // a PUG size limit of the device path was exceeded
 constexpr uint32_t kErrPugPool = 8;      // edge pool exhausted
 constexpr uint32_t kErrInternal = 9;     // a consistency check of the device code failed (a bug, never the input)
-constexpr uint32_t kErrStartRange = 10;  // atac sort: start_pos >= the reference's length
+constexpr uint32_t kErrStartRange = 10;  // atac sort: start_pos >= the reference's length; atac generate-permit-list: the position's bin is past the last bin
 constexpr uint32_t kErrCorrection = 11;  // atac sort: one observed barcode with two corrected ones
 // DevStatus.err_cell of a failure that belongs to the whole range, not to a cell it could name: the range-wide graph build's
 // pool and size limits, and every pool allocation - the pool is one bump allocator per range, and the cell whose request

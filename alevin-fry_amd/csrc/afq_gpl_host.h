@@ -214,9 +214,8 @@ inline int64_t select_retained(const uint64_t* bc, const uint64_t* count, size_t
     return (int64_t)k;
 }
 
-inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::string& err) {
-    if (!o || !t || !o->output_dir) return gfail(err, AFQ_ERR_INVALID_ARG, "null option");
-    const std::string out = o->output_dir;
+// permit_freq.bin, all_freq.bin (when t->all_bc), permit_map.bin and correction_plan.bin into the directory `out` (created if missing)
+inline int write_table_files(const std::string& out, const afq_gpl_tables* t, std::string& err) {
     if (gpl_mkdirs(out)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't create directory path " + out);
     if (!write_freq_file(out + "/permit_freq.bin", t->barcode_len, t->freq_bc, t->freq_count, t->n_freq)) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write permit frequencies");
     if (t->all_bc && !write_freq_file(out + "/all_freq.bin", t->barcode_len, t->all_bc, t->all_count, t->n_all)) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write all_freq.bin");
@@ -249,6 +248,13 @@ inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::st
         for (uint64_t i = 0; i < t->n_plan; ++i) { put64(t->plan_obs[i]); put64(t->plan_cor[i]); }
         if (std::fwrite(b.data(), 1, b.size(), f.get()) != b.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write correction plan");
     }
+    return 0;
+}
+
+inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::string& err) {
+    if (!o || !t || !o->output_dir) return gfail(err, AFQ_ERR_INVALID_ARG, "null option");
+    const std::string out = o->output_dir;
+    if (int rc = write_table_files(out, t, err)) return rc;
     // generate_permit_list.json; gpl_options restates serde's derive of GenPermitListOpts (parity unpinned)
     static const char* const kOriSym[3] = {"both", "fw", "rc"};
     static const char* const kOriEnum[3] = {"Unknown", "Forward", "Reverse"};
@@ -283,6 +289,68 @@ inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::st
     j += "    \"memory_limit\": 536870912,\n    \"tmp_dir\": null\n  },\n";
     j += std::string("  \"resolved_cell_bc_neighborhood\": \"") + kNbh[t->neighborhood ? 1 : 0] + "\",\n";
     j += "  \"resolved_cell_bc_confidence\": \"" + std::to_string(cn) + "/" + std::to_string(cd) + "\",\n";
+    j += "  \"correction_stats\": {\n";
+    for (int i = 0; i < 8; ++i) j += std::string("    \"") + kStat[i] + "\": " + std::to_string(t->stats[i]) + (i < 7 ? ",\n" : "\n");
+    j += "  }\n}";
+    GplFile f(std::fopen((out + "/generate_permit_list.json").c_str(), "w"));
+    if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+    if (std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
+    return 0;
+}
+
+// ---- `atac generate-permit-list` (src/atac/cellfilter.rs)
+// initialize_rec_list (cellfilter.rs:39-54): out[0] = 0, out[r + 1] = out[r] + ceil((f32)len / (f32)bin_size).  The quotient and
+// its ceiling are taken in f32 as the reference takes them: above 2^24 that is not the integer ceiling (200 000 001 / 100 000
+// gives 2000, not 2001).
+inline void atac_bin_lens(const uint32_t* ref_lens, size_t n, uint64_t bin_size, uint64_t* out) {
+    out[0] = 0;
+    for (size_t r = 0; r < n; ++r) {
+        const float q = (float)ref_lens[r] / (float)bin_size;
+        out[r + 1] = out[r] + (uint64_t)std::ceil(q);
+    }
+}
+// needletail::bitkmer::reverse_complement of a k-mer packed first base highest, A C G T = 0 1 2 3
+inline uint64_t reverse_complement(uint64_t v, uint32_t k) {
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < k; ++i) { o = (o << 2) | (3ull - (v & 3ull)); v >>= 2; }
+    return o;
+}
+inline bool write_vec_u64(const std::string& path, const uint64_t* v, uint64_t n) {   // bincode Vec<u64>: the length, then the values
+    GplFile f(std::fopen(path.c_str(), "wb"));
+    if (!f) return false;
+    return std::fwrite(&n, 8, 1, f.get()) == 1 && (!n || std::fwrite(v, 8, n, f.get()) == n);
+}
+// The six files of `atac generate-permit-list`: the four table files, bin_recs.bin / bin_lens.bin, and generate_permit_list.json
+// (process_unfiltered's json!, cellfilter.rs:273-284; gpl_options restates serde's derive of the ATAC GenPermitListOpts, parity
+// unpinned as for RNA).  conf_num / conf_den of `o` are the resolved ones.
+inline int write_atac_outputs(const afq_atac_gpl_opts* o, const afq_gpl_tables* t, const uint64_t* bins, uint64_t n_bins, const uint64_t* bin_lens, uint64_t n_lens,
+                              uint64_t num_chunks, uint64_t max_bin, std::string& err) {
+    if (!o || !t || !o->output_dir) return gfail(err, AFQ_ERR_INVALID_ARG, "null option");
+    const std::string out = o->output_dir;
+    if (int rc = write_table_files(out, t, err)) return rc;
+    if (!write_vec_u64(out + "/bin_recs.bin", bins, n_bins)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize bins recs.");
+    if (!write_vec_u64(out + "/bin_lens.bin", bin_lens, n_lens)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize bins lengths.");
+    static const char* const kNbh[2] = {"hamming-1", "substitution-or-shift-1"};
+    static const char* const kStat[8] = {"exact_distinct", "exact_reads", "corrected_distinct", "corrected_reads", "ambiguous_distinct", "ambiguous_reads", "not_found_distinct", "not_found_reads"};
+    const std::string conf = "{\n      \"numerator\": " + std::to_string(o->conf_num) + ",\n      \"denominator\": " + std::to_string(o->conf_den) + "\n    }";
+    std::string j = "{\n";
+    j += "  \"version_str\": \"0.18.0\",\n";
+    j += "  \"max-ambig-record\": " + std::to_string(t->max_ambig) + ",\n";
+    j += "  \"num-chunks\": " + std::to_string(num_chunks) + ",\n";
+    j += "  \"cmd\": " + gpl_json_str(o->cmdline) + ",\n";
+    j += "  \"permit-list-type\": \"unfiltered\",\n";
+    j += "  \"gpl_options\": {\n";
+    j += "    \"input_dir\": " + gpl_json_str(o->input_dir) + ",\n    \"output_dir\": " + gpl_json_str(o->output_dir) + ",\n";
+    j += "    \"fmeth\": {\n      \"UnfilteredExternalList\": [\n        " + gpl_json_str(o->list_file) + ",\n        " + std::to_string(o->min_reads) + "\n      ]\n    },\n";
+    j += "    \"threads\": " + std::to_string(o->num_threads) + ",\n";
+    j += std::string("    \"rc\": ") + (o->rc ? "true" : "false") + ",\n";
+    j += "    \"cmdline\": " + gpl_json_str(o->cmdline) + ",\n    \"version\": \"0.18.0\",\n";
+    j += std::string("    \"cell_bc_correction\": \"") + (o->frequency ? "frequency" : "unique") + "\",\n";
+    j += std::string("    \"cell_bc_neighborhood\": \"") + kNbh[o->neighborhood ? 1 : 0] + "\",\n";
+    j += "    \"cell_bc_confidence\": " + conf + "\n  },\n";
+    j += "  \"max-rec-in-bin\": " + std::to_string(max_bin) + ",\n";
+    j += std::string("  \"resolved_cell_bc_neighborhood\": \"") + kNbh[t->neighborhood ? 1 : 0] + "\",\n";
+    j += "  \"resolved_cell_bc_confidence\": \"" + std::to_string(o->conf_num) + "/" + std::to_string(o->conf_den) + "\",\n";
     j += "  \"correction_stats\": {\n";
     for (int i = 0; i < 8; ++i) j += std::string("    \"") + kStat[i] + "\": " + std::to_string(t->stats[i]) + (i < 7 ? ",\n" : "\n");
     j += "  }\n}";

@@ -1939,6 +1939,73 @@ int afq_quantify(const afq_quant_opts* o) {
     return 0;
 }
 
+namespace {
+// the text of a barcode list file, plain or gzip (zlib reads both)
+int read_list_text(const char* path, std::string& txt) {
+    gzFile gz = gzopen(path, "rb");
+    if (!gz) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't open input barcode file. (") + path + ")");
+    char buf[1 << 16];
+    int got;
+    while ((got = gzread(gz, buf, sizeof buf)) > 0) txt.append(buf, (size_t)got);
+    gzclose(gz);
+    if (got < 0) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't read line from barcode file. (") + path + ")");
+    return 0;
+}
+// a fill's ascending histogram into the running one, summing a barcode present in both
+void merge_histogram(std::vector<uint64_t>& hbc, std::vector<uint64_t>& hcnt, const uint64_t* bc, const uint64_t* cnt, uint64_t n) {
+    if (hbc.empty()) { hbc.assign(bc, bc + n); hcnt.assign(cnt, cnt + n); return; }
+    std::vector<uint64_t> mb, mc;
+    mb.reserve(hbc.size() + n); mc.reserve(hbc.size() + n);
+    size_t i = 0, j = 0;
+    while (i < hbc.size() || j < n) {
+        if (j >= n || (i < hbc.size() && hbc[i] < bc[j])) { mb.push_back(hbc[i]); mc.push_back(hcnt[i]); ++i; }
+        else if (i >= hbc.size() || bc[j] < hbc[i]) { mb.push_back(bc[j]); mc.push_back(cnt[j]); ++j; }
+        else { mb.push_back(hbc[i]); mc.push_back(hcnt[i] + cnt[j]); ++i; ++j; }
+    }
+    hbc.swap(mb); hcnt.swap(mc);
+}
+// compile_distinct_observed_with_target_counts (barcode_correction.rs:539-603) of the observed histogram against the retained
+// barcodes (both ascending): the plan's entries restricted to permitted targets, permit_freq's map, the eight stats
+struct Freer3 { void *a, *b, *c; ~Freer3() { afq_free(a); afq_free(b); afq_free(c); } };   // three outputs of afq_gpl_correct
+struct GplPlan {
+    std::vector<uint64_t> plan_obs, plan_cor, freq_bc, freq_cnt;
+    std::vector<uint8_t> permitted;   // [retained]: the target has an accepted observation
+    afq_gpl_correction_stats cs{};
+};
+int compile_plan(afq_ctx* ctx, const std::vector<uint64_t>& hbc, const std::vector<uint64_t>& hcnt, const std::vector<uint64_t>& retained,
+                 const std::vector<uint64_t>& ret_cnt, uint32_t cblen, uint32_t nbh, uint32_t frequency, uint64_t conf_num, uint64_t conf_den, GplPlan& out) {
+    afq_gpl_correction_stats& cs = out.cs;
+    std::vector<uint64_t>&plan_obs = out.plan_obs, &plan_cor = out.plan_cor, &freq_bc = out.freq_bc, &freq_cnt = out.freq_cnt;
+    uint8_t* dec = nullptr; uint32_t* tgt = nullptr; uint64_t* tcount = nullptr;
+    int rc = afq_gpl_correct(ctx, hbc.data(), hcnt.data(), hbc.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, frequency, conf_num, conf_den, 1,
+                             &dec, &tgt, &tcount, &cs);
+    if (rc) return hfail(rc, afq_last_error(ctx));
+    Freer3 fr3{dec, tgt, tcount};
+    std::vector<uint8_t> has_obs(retained.size(), 0);
+    std::vector<uint8_t>& permitted = out.permitted;
+    permitted.assign(retained.size(), 0);
+    for (size_t i = 0; i < hbc.size(); ++i) {
+        if (tgt[i] == 0xFFFFFFFFu) continue;
+        permitted[tgt[i]] = 1;   // (the target has an accepted observation: it is in permit_freq)
+        if (dec[i] == 0) has_obs[tgt[i]] = 1;
+    }
+    {   // the observed entries and the identities of never-observed sources, merged in barcode order, restricted to permitted targets
+        size_t r = 0;
+        auto flush_sources = [&](uint64_t below, bool all) {
+            for (; r < retained.size() && (all || retained[r] < below); ++r)
+                if (!has_obs[r]) { ++cs.exact_distinct; if (permitted[r]) { plan_obs.push_back(retained[r]); plan_cor.push_back(retained[r]); } }
+        };
+        for (size_t i = 0; i < hbc.size(); ++i) {
+            flush_sources(hbc[i], false);
+            if (tgt[i] != 0xFFFFFFFFu && permitted[tgt[i]]) { plan_obs.push_back(hbc[i]); plan_cor.push_back(retained[tgt[i]]); }
+        }
+        flush_sources(0, true);
+    }
+    for (size_t r = 0; r < retained.size(); ++r) if (permitted[r]) { freq_bc.push_back(retained[r]); freq_cnt.push_back(tcount[r]); }
+    return 0;
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------
 // `alevin-fry generate-permit-list` (src/cellfilter.rs:369-780, 1686-1830, 2044-2335; src/barcode_correction.rs; src/knee_finding.rs)
 // for single-barcode RNA RAD files: the record pass and the correction decisions run on the device (afq_gpl_hist_rad,
@@ -2005,14 +2072,8 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     // ---- the barcode list of -b / -u (plain text or gzip: zlib reads both)
     std::vector<uint64_t> listed;
     if (o->method == AFQ_GPL_VALID_BC || o->method == AFQ_GPL_UNFILTERED) {
-        gzFile gz = gzopen(o->list_file, "rb");
-        if (!gz) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't open input barcode file. (") + o->list_file + ")");
         std::string txt;
-        char buf[1 << 16];
-        int got;
-        while ((got = gzread(gz, buf, sizeof buf)) > 0) txt.append(buf, (size_t)got);
-        gzclose(gz);
-        if (got < 0) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't read line from barcode file. (") + o->list_file + ")");
+        if (int rc2 = read_list_text(o->list_file, txt)) return rc2;
         uint32_t first_len = 0;
         const int unf = o->method == AFQ_GPL_UNFILTERED;
         const int64_t n = afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), unf, cblen, nullptr, 0, &first_len);
@@ -2071,18 +2132,7 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
         }
         struct Freer { void *a, *b; ~Freer() { afq_free(a); afq_free(b); } } fr{bc, cnt};
         n_records += st.n_records; n_compat += st.n_compatible; max_ambig = std::max(max_ambig, st.max_ambig);
-        if (hbc.empty()) { hbc.assign(bc, bc + n); hcnt.assign(cnt, cnt + n); }
-        else {   // merge two ascending lists, summing a barcode present in both
-            std::vector<uint64_t> mb, mc;
-            mb.reserve(hbc.size() + n); mc.reserve(hbc.size() + n);
-            size_t i = 0, j = 0;
-            while (i < hbc.size() || j < n) {
-                if (j >= n || (i < hbc.size() && hbc[i] < bc[j])) { mb.push_back(hbc[i]); mc.push_back(hcnt[i]); ++i; }
-                else if (i >= hbc.size() || bc[j] < hbc[i]) { mb.push_back(bc[j]); mc.push_back(cnt[j]); ++j; }
-                else { mb.push_back(hbc[i]); mc.push_back(hcnt[i] + cnt[j]); ++i; ++j; }
-            }
-            hbc.swap(mb); hcnt.swap(mc);
-        }
+        merge_histogram(hbc, hcnt, bc, cnt, n);
         c0 = c1;
     }
     std::fprintf(stderr, "observed %llu reads (%llu orientation consistent) in %llu chunks --- max ambiguity read occurs in %llu refs\n", (unsigned long long)n_records,
@@ -2118,34 +2168,11 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     const uint32_t nbh = o->neighborhood >= 0 ? (uint32_t)o->neighborhood : (filtered ? 1u : 0u);   // prog_opts.rs:135-144
     if (o->frequency && nbh == 1)
         std::fprintf(stderr, "cell-barcode Frequency correction is using substitution-or-shift-1. RAD stores no barcode base qualities or indel-error model, so this is an abundance heuristic rather than a calibrated indel posterior.\n");
-    // ---- compile_distinct_observed_with_target_counts (barcode_correction.rs:539-603)
-    uint8_t* dec = nullptr; uint32_t* tgt = nullptr; uint64_t* tcount = nullptr;
-    afq_gpl_correction_stats cs{};
-    rc = afq_gpl_correct(ctx.get(), hbc.data(), hcnt.data(), hbc.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, 1,
-                         &dec, &tgt, &tcount, &cs);
-    if (rc) return hfail(rc, afq_last_error(ctx.get()));
-    struct Freer3 { void *a, *b, *c; ~Freer3() { afq_free(a); afq_free(b); afq_free(c); } } fr3{dec, tgt, tcount};
-    std::vector<uint8_t> has_obs(retained.size(), 0), permitted(retained.size(), 0);
-    std::vector<uint64_t> plan_obs, plan_cor;
-    for (size_t i = 0; i < hbc.size(); ++i) {
-        if (tgt[i] == 0xFFFFFFFFu) continue;
-        permitted[tgt[i]] = 1;   // (the target has an accepted observation: it is in permit_freq)
-        if (dec[i] == 0) has_obs[tgt[i]] = 1;
-    }
-    {   // the observed entries and the identities of never-observed sources, merged in barcode order, restricted to permitted targets
-        size_t r = 0;
-        auto flush_sources = [&](uint64_t below, bool all) {
-            for (; r < retained.size() && (all || retained[r] < below); ++r)
-                if (!has_obs[r]) { ++cs.exact_distinct; if (permitted[r]) { plan_obs.push_back(retained[r]); plan_cor.push_back(retained[r]); } }
-        };
-        for (size_t i = 0; i < hbc.size(); ++i) {
-            flush_sources(hbc[i], false);
-            if (tgt[i] != 0xFFFFFFFFu && permitted[tgt[i]]) { plan_obs.push_back(hbc[i]); plan_cor.push_back(retained[tgt[i]]); }
-        }
-        flush_sources(0, true);
-    }
-    std::vector<uint64_t> freq_bc, freq_cnt;
-    for (size_t r = 0; r < retained.size(); ++r) if (permitted[r]) { freq_bc.push_back(retained[r]); freq_cnt.push_back(tcount[r]); }
+    GplPlan plan;
+    if (int rc2 = compile_plan(ctx.get(), hbc, hcnt, retained, ret_cnt, cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, plan)) return rc2;
+    afq_gpl_correction_stats& cs = plan.cs;
+    std::vector<uint64_t>&plan_obs = plan.plan_obs, &plan_cor = plan.plan_cor, &freq_bc = plan.freq_bc, &freq_cnt = plan.freq_cnt;
+    const std::vector<uint8_t>& permitted = plan.permitted;
     std::fprintf(stderr, "Cell correction: %llu exact reads, %llu corrected, %llu ambiguous, %llu without a candidate\n", (unsigned long long)cs.exact_reads,
                  (unsigned long long)cs.corrected_reads, (unsigned long long)cs.ambiguous_reads, (unsigned long long)cs.not_found_reads);
     // ---- permit_map.bin: the full theoretical neighbourhood (filtered methods), or the observed entries
@@ -2182,6 +2209,173 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     if (rc) return rc;
     std::fprintf(stderr, "total number of distinct corrected barcodes : %llu\n", (unsigned long long)cs.corrected_distinct);
     if (o->corrected_out) *o->corrected_out = cs.corrected_distinct;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// `alevin-fry atac generate-permit-list` (generate_permit_list + process_unfiltered, src/atac/cellfilter.rs:143-599): the record
+// pass runs on the device (afq_atac_gpl_hist_rad), fill by fill, the correction decisions are afq_gpl_correct's; the bins' layout,
+// the listed and retained sets and the files are the host's.  The RNA path's `-u` is the same text but for the orientation
+// filter (there is none here), the reverse complement of the list, and the bins.
+void afq_atac_gpl_bin_lens(const uint32_t* ref_lens, size_t n, uint64_t bin_size, uint64_t* out) {
+    if (out && (ref_lens || !n)) afq::gplhost::atac_bin_lens(ref_lens, n, bin_size, out);
+}
+uint64_t afq_gpl_reverse_complement(uint64_t barcode, uint32_t k) { return afq::gplhost::reverse_complement(barcode, k > 32 ? 32 : k); }
+
+int afq_atac_generate_permit_list(const afq_atac_gpl_opts* o) {
+    if (!o || !o->input_dir || !o->output_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (!o->list_file) return hfail(AFQ_ERR_INVALID_ARG, "atac generate-permit-list needs an unfiltered barcode list file (-u)");
+    if (o->min_reads < 1) return hfail(AFQ_ERR_INVALID_ARG, "min-reads < 1 is not supported, the value " + std::to_string(o->min_reads) + " was provided");
+    if (o->neighborhood > 1) return hfail(AFQ_ERR_INVALID_ARG, "unknown barcode neighbourhood; expected hamming-1 or substitution-or-shift-1");
+    uint64_t conf_num = 9, conf_den = 10;   // Confidence::ATAC
+    if (o->conf_den || o->conf_num) { std::string e; if (int rc = afq::gplhost::confidence_new(o->conf_num, o->conf_den, &conf_num, &conf_den, e)) return hfail(rc, e); }
+    const std::string in = o->input_dir;
+    if (!file_exists(in)) return hfail(AFQ_ERR_BAD_INPUT, "the input rad path \"" + in + "\" does not exist");
+    const uint64_t bin_size = 100000;
+    // ---- the barcode list (populate_unfiltered_barcode_map): read before the RAD file, as the reference reads it
+    std::string txt;
+    if (int rc2 = read_list_text(o->list_file, txt)) return rc2;
+    uint32_t first_len = 0;
+    std::vector<uint64_t> listed;
+    {
+        const int64_t n = afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), 1, 0, nullptr, 0, &first_len);
+        if (n < 0) return (int)n;
+        listed.resize((size_t)n);
+        afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), 1, 0, listed.data(), listed.size(), nullptr);
+        if (o->rc) for (uint64_t& b : listed) b = afq::gplhost::reverse_complement(b, first_len);
+        std::sort(listed.begin(), listed.end());
+        listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
+    }
+    std::fprintf(stderr, "number of unfiltered bcs read = %zu\n", listed.size());
+    MappedFile mf;
+    if (!mf.open(in + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "could not open input rad file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    {
+        bool has_u = false;
+        for (auto& t : P.read_tags) has_u = has_u || t.name == "u";
+        if (has_u) return hfail(AFQ_ERR_UNSUPPORTED, "atac generate-permit-list: this is an RNA RAD file (it has a UMI tag); use generate-permit-list");
+    }
+    if (P.read_tags.size() != 1 || P.read_tags[0].name != "b" || !P.bc_bytes) return hfail(AFQ_ERR_UNSUPPORTED, "scATAC RAD: the read-level tags must be exactly one integer 'b'");
+    static const struct { const char* name; uint8_t type; } kAln[4] = {{"ref", 3}, {"type", 1}, {"start_pos", 3}, {"frag_len", 2}};
+    bool aln_ok = P.aln_tags.size() == 4;
+    for (size_t i = 0; aln_ok && i < 4; ++i) aln_ok = P.aln_tags[i].name == kAln[i].name && P.aln_tags[i].type == kAln[i].type;
+    if (!aln_ok) return hfail(AFQ_ERR_UNSUPPORTED, "scATAC RAD: the alignment-level tags must be ref:u32, type:u8, start_pos:u32, frag_len:u16 (an RNA RAD file goes to generate-permit-list)");
+    if (!P.file_tag_vals.count("cblen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain cblen");
+    const uint32_t cblen = (uint32_t)P.file_tag_vals["cblen"];
+    if (cblen < 1 || cblen > 32) return hfail(AFQ_ERR_BAD_INPUT, "barcode length must be between 1 and 32 (got " + std::to_string(cblen) + ")");
+    if (!P.have_ref_lengths || P.ref_lengths.size() != P.ref_count) return hfail(AFQ_ERR_BAD_INPUT, "scATAC RAD: the ref_lengths file tag must be an array of u32 with one entry per reference");
+    if (P.ref_count >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "atac generate-permit-list: 2^32 or more references");
+    if (first_len != cblen && !listed.empty())
+        std::fprintf(stderr, "The provided permit list had barcodes of length %u, but the mapped reads have barcodes of length %u\n", first_len, cblen);
+    for (uint64_t b : listed) if (cblen < 32 && b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    // ---- the bins (initialize_rec_list)
+    std::vector<uint64_t> bin_lens(P.ref_lengths.size() + 1, 0);
+    afq::gplhost::atac_bin_lens(P.ref_lengths.data(), P.ref_lengths.size(), bin_size, bin_lens.data());
+    const uint64_t n_bins = bin_lens.back();
+    // (the reference panics on this after its record pass, `bins.iter().max().expect("bins should not be empty")`, unless a record
+    // with one alignment has already indexed past the empty bins; refused here before any record is read)
+    if (!n_bins) return hfail(AFQ_ERR_BAD_INPUT, "bins should not be empty (the reference lengths give no position bin)");
+    if (n_bins >= (1ull << 31)) return hfail(AFQ_ERR_UNSUPPORTED, "atac generate-permit-list: 2^31 or more position bins (" + std::to_string(n_bins) + ")");
+    // ---- the chunk table
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < P.num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    // ---- the record pass: one device fill per run of chunks of at most fill_bytes; histograms merged, bins and tallies added
+    const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
+    std::vector<uint64_t> hbc, hcnt, bins(n_bins, 0);
+    afq_atac_gpl_hist_stats tot{};
+    for (size_t c0 = 0; c0 < chunk_off.size();) {
+        size_t c1 = c0;
+        uint64_t nrec_sum = 0;
+        auto chunk_end = [&](size_t i) { uint32_t nb; std::memcpy(&nb, rad + chunk_off[i], 4); return chunk_off[i] + nb; };
+        while (c1 < chunk_off.size()) {
+            uint32_t nr; std::memcpy(&nr, rad + chunk_off[c1] + 4, 4);
+            if (c1 > c0 && (chunk_end(c1) - chunk_off[c0] > fill_bytes || nrec_sum + nr >= (1ull << 30))) break;
+            nrec_sum += nr; ++c1;
+        }
+        const uint64_t base = chunk_off[c0];
+        std::vector<uint64_t> rel(c1 - c0);
+        for (size_t i = c0; i < c1; ++i) rel[i - c0] = chunk_off[i] - base;
+        uint64_t n = 0, *bc = nullptr, *cnt = nullptr, *fb = nullptr;
+        afq_atac_gpl_hist_stats st{};
+        rc = afq_atac_gpl_hist_rad(ctx.get(), rad + base, (size_t)(chunk_end(c1 - 1) - base), rel.data(), (uint32_t)rel.size(), P.bc_bytes, 0, bin_lens.data(),
+                                   (uint32_t)P.ref_count, (uint32_t)bin_size, &n, &bc, &cnt, &fb, &st);
+        if (rc) {
+            std::string m = afq_last_error(ctx.get());
+            if (c0 && m.compare(0, 6, "chunk ") == 0) m += " (chunks of this fill are numbered from chunk " + std::to_string(c0) + " of the file)";
+            return hfail(rc, m);
+        }
+        Freer3 fr{bc, cnt, fb};
+        tot.n_records += st.n_records; tot.n_unmapped += st.n_unmapped; tot.n_multimapped += st.n_multimapped; tot.n_binned += st.n_binned;
+        tot.max_ambig = std::max(tot.max_ambig, st.max_ambig);
+        merge_histogram(hbc, hcnt, bc, cnt, n);
+        for (uint64_t i = 0; i < n_bins; ++i) bins[i] += fb[i];
+        c0 = c1;
+    }
+    tot.max_bin = *std::max_element(bins.begin(), bins.end());
+    if (cblen < 32) for (uint64_t b : hbc) if (b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    auto count_of = [&](uint64_t b) -> uint64_t { auto it = std::lower_bound(hbc.begin(), hbc.end(), b); return it != hbc.end() && *it == b ? hcnt[it - hbc.begin()] : 0; };
+    {   // likely_valid_permit_list over all reads
+        uint64_t unmatched_reads = 0;
+        for (size_t i = 0; i < hbc.size(); ++i) if (!std::binary_search(listed.begin(), listed.end(), hbc[i])) unmatched_reads += hcnt[i];
+        if (tot.n_records > 0) {
+            const double f = (double)unmatched_reads / (double)tot.n_records;
+            if (f < 0.3) std::fprintf(stderr, "The percentage of mapped reads not matching a known barcode exactly is %.3f%%, which is < the warning threshold %.3f%%\n", f * 100.0, 30.0);
+            else std::fprintf(stderr, "Percentage of mapped reads not matching a known barcode exaclty (%g%%) is > the suggested fraction (%g%%)\n", f * 100.0, 30.0);
+        } else std::fprintf(stderr, "Cannot determine (likely) valid permit list if not reads are mapped\n");
+    }
+    std::fprintf(stderr, "observed %llu reads (%llu orientation consistent) in %llu chunks --- max ambiguity read occurs in %llu refs\n", (unsigned long long)tot.n_records,
+                 (unsigned long long)tot.n_records, (unsigned long long)P.num_chunks, (unsigned long long)tot.max_ambig);
+    std::fprintf(stderr, "minimum num reads for barcode pass = %llu\n", (unsigned long long)o->min_reads);
+    std::vector<uint64_t> retained;
+    for (uint64_t b : listed) if (count_of(b) >= o->min_reads) retained.push_back(b);
+    std::vector<uint64_t> ret_cnt(retained.size());
+    for (size_t i = 0; i < retained.size(); ++i) ret_cnt[i] = count_of(retained[i]);
+    const uint32_t nbh = o->neighborhood;
+    if (o->frequency && nbh == 1)
+        std::fprintf(stderr, "ATAC Frequency correction is using substitution-or-shift-1. RAD stores no barcode base qualities or indel-error model, so this is an abundance heuristic rather than a calibrated indel posterior.\n");
+    std::fprintf(stderr, "found %zu cells with non-trivial number of reads by exact barcode match\n", retained.size());
+    GplPlan plan;
+    if (int rc2 = compile_plan(ctx.get(), hbc, hcnt, retained, ret_cnt, cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, plan)) return rc2;
+    const afq_gpl_correction_stats& cs = plan.cs;
+    std::fprintf(stderr, "ATAC cell correction: %llu exact reads, %llu corrected, %llu ambiguous, %llu without a candidate\n", (unsigned long long)cs.exact_reads,
+                 (unsigned long long)cs.corrected_reads, (unsigned long long)cs.ambiguous_reads, (unsigned long long)cs.not_found_reads);
+    afq_gpl_tables T{};
+    T.barcode_len = cblen; T.neighborhood = nbh; T.frequency = o->frequency ? 1 : 0; T.filtered = 0;
+    T.conf_num = conf_num; T.conf_den = conf_den; T.pseudocount = 1;
+    T.freq_bc = plan.freq_bc.data(); T.freq_count = plan.freq_cnt.data(); T.n_freq = plan.freq_bc.size();
+    T.map_obs = plan.plan_obs.data(); T.map_cor = plan.plan_cor.data(); T.n_map = plan.plan_obs.size();   // (the plan's entries, not the theoretical neighbourhood: cellfilter.rs:237-248)
+    T.plan_obs = plan.plan_obs.data(); T.plan_cor = plan.plan_cor.data(); T.n_plan = plan.plan_obs.size();
+    const uint64_t sv[8] = {cs.exact_distinct, cs.exact_reads, cs.corrected_distinct, cs.corrected_reads, cs.ambiguous_distinct, cs.ambiguous_reads, cs.not_found_distinct, cs.not_found_reads};
+    std::memcpy(T.stats, sv, sizeof sv);
+    T.max_ambig = tot.max_ambig;
+    afq_atac_gpl_opts oo = *o;
+    oo.conf_num = conf_num; oo.conf_den = conf_den;
+    {
+        std::string e;
+        if (int rc2 = afq::gplhost::write_atac_outputs(&oo, &T, bins.data(), bins.size(), bin_lens.data(), bin_lens.size(), P.num_chunks, tot.max_bin, e)) return hfail(rc2, e);
+    }
+    std::fprintf(stderr, "total number of distinct corrected barcodes : %llu\n", (unsigned long long)cs.corrected_distinct);
+    if (o->stats_out) *o->stats_out = tot;
     return 0;
 }
 

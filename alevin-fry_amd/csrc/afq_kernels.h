@@ -279,6 +279,20 @@ void launch_gpl_count(hipStream_t s, const SortChunk* chunks, uint32_t n_chunks,
 void launch_gpl_compact(hipStream_t s, const uint64_t* tab_key, const unsigned long long* tab_cnt, uint64_t cap, uint64_t* o_key, uint64_t* o_cnt,
                         uint32_t* n_out);
 void launch_gpl_correct(hipStream_t s, const GplCorrectArgs& a);
+// `atac generate-permit-list`: the barcode of every record of an uncollated scATAC RAD, the largest na and the position-bin
+// histogram of the records with one alignment (afq_atac_gpl.hip).  The walk and its limits are k_sort_parse's (kSortParseTile,
+// kSortParseHalo); the barcode column goes through launch_gpl_count / launch_gpl_compact.
+struct AtacGplParseArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks; uint32_t bc_bytes;
+    const uint32_t* bin_base;   // [ref_count] first bin of a reference
+    uint32_t ref_count, n_bins, bin_size;
+    uint64_t* o_bc;             // a slot per record of the chunk table, in input order
+    uint32_t* bins;             // [n_bins] counters, zeroed by the caller
+    uint32_t* chunk_stat;       // [n_chunks][4]: na == 0, records (0 for a refused chunk), largest na, na > 1
+    DevStatus* st;              // kErrRecordWalk, kErrRefRange, kErrStartRange (here: a bin index not below n_bins); err_cell: the chunk
+};
+void launch_atac_gpl_parse(hipStream_t s, const AtacGplParseArgs& a);
+void launch_atac_gpl_bins(hipStream_t s, const uint32_t* bins, uint32_t n_bins, uint64_t* o_bins, uint32_t* o_max);   // o_bins[i] = bins[i]; *o_max (zeroed by the caller) = the largest
 // `collate`: the records of an uncollated RNA RAD, barcode-corrected, one output chunk per cell (afq_collate.hip).  The walk and
 // its limits are the GPL parse's (kGplParseTile, kGplParseHalo, kGplLaneAlns).
 constexpr uint32_t kCollateRadixNT = 256, kCollateRadixItems = 32, kCollateScanItems = 8;

@@ -366,6 +366,44 @@ void afq_gpl_limits(uint32_t out[4]);
 void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity);
 
 /*
+ * `atac generate-permit-list`, the device half (update_barcode_hist_unfiltered, src/atac/cellfilter.rs:68-103 of the reference): one
+ * walk of an UNCOLLATED scATAC RAD for the barcode histogram, the largest na and the position-bin histogram.
+ *
+ * `bytes` / `chunk_off` / bytes_on_device and the record layout (`na u32, barcode (bc_bytes), na x (ref u32, type u8, start_pos u32,
+ * frag_len u16)`) are afq_atac_sort_rad's.  bin_base[ref_count + 1] ascends from bin_base[0] == 0 (else AFQ_ERR_INVALID_ARG):
+ * reference r owns bins [bin_base[r], bin_base[r + 1]); bin_size >= 1.
+ *
+ * EVERY record counts its barcode, whatever its na, and max_ambig is the largest na over all records.  A record with exactly one
+ * alignment adds 1 to bin bin_base[ref] + start_pos / bin_size.  No position is tested against a reference length - the reference
+ * tests none - so a position past its reference's bins counts in the bins of the NEXT reference.  ref >= ref_count, or a bin index
+ * >= bin_base[ref_count] (where the reference panics on an index), is AFQ_ERR_BAD_INPUT "chunk <i>: ...".
+ *
+ * Out (malloc'd; afq_free): the distinct barcodes, ascending, with their u64 counts; out_bins[bin_base[ref_count]] (NULL without
+ * bins); `stats`.  All counts are integer sums: the output is a function of the input alone, run to run.  The counting table is
+ * afq_gpl_hist_rad's, so afq_gpl_table_slot(barcode, n_records, bc_bytes, ..) describes it.  One call is one fill of the device: a
+ * host with a larger file calls once per part, merges the sorted histograms, adds the bins and sums, takes the largest max_ambig.
+ * Errors: AFQ_ERR_BAD_INPUT "chunk <i>: ..." for a chunk outside the buffer, a head or an alignment list that runs past its chunk,
+ * records that do not tile nbytes or do not number nrec (nothing outside `bytes` is read, the context stays usable);
+ * AFQ_ERR_UNSUPPORTED for 2^30 records or more in one call or 2^31 bins or more; AFQ_ERR_OOM (with the sizes) when input and
+ * tables do not fit the device.
+ */
+typedef struct afq_atac_gpl_hist_stats {
+    uint64_t n_records;      /* records of the chunks (= the sum of the barcode counts)        */
+    uint64_t n_unmapped;     /* ... with na == 0                                              */
+    uint64_t n_multimapped;  /* ... with na > 1                                               */
+    uint64_t n_binned;       /* ... with na == 1 (= the sum of the bins)                      */
+    uint64_t max_ambig;      /* the largest na over ALL records (`max-ambig-record`)          */
+    uint64_t max_bin;        /* the largest bin counter (`max-rec-in-bin`); 0 without bins    */
+} afq_atac_gpl_hist_stats;
+int afq_atac_gpl_hist_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks,
+                          uint32_t bc_bytes, int bytes_on_device, const uint64_t* bin_base /* [ref_count + 1] */, uint32_t ref_count,
+                          uint32_t bin_size, uint64_t* out_n, uint64_t** out_bc, uint64_t** out_count, uint64_t** out_bins,
+                          afq_atac_gpl_hist_stats* stats);
+/* out[0] = bytes of a chunk the walk stages per trip, out[1] = bytes staged behind them (both are the `atac sort` parse's),
+ * out[2] = bins a workgroup counts privately in LDS (0: the bins are counted in global memory), out[3] = 0.  For tests. */
+void afq_atac_gpl_limits(uint32_t out[4]);
+
+/*
  * `collate`, the device half (src/collate.rs:129-289, 483-643 of the reference): the records of an UNCOLLATED single-barcode RNA
  * RAD routed by corrected barcode into one chunk per cell.
  *

@@ -180,6 +180,38 @@ typedef struct afq_gpl_tables {
 } afq_gpl_tables;
 int afq_gpl_write_outputs(const afq_gpl_opts* opts, const afq_gpl_tables* t);
 
+/* The options of `alevin-fry atac generate-permit-list` (src/main.rs; the ATAC GenPermitListOpts, src/atac/prog_opts.rs:11-28). */
+struct afq_atac_gpl_hist_stats;
+typedef struct afq_atac_gpl_opts {
+    const char* input_dir;      /* -i : directory holding the mapper's map.rad                                   */
+    const char* output_dir;     /* -o                                                                            */
+    const char* list_file;      /* -u : unfiltered external permit list, plain or gzip (required: the reference's
+                                        only filter method, atac/cellfilter.rs:158-166)                          */
+    uint64_t min_reads;         /* -m : the reference's CLI default is 10; < 1 is AFQ_ERR_INVALID_ARG with its sentence */
+    uint32_t rc;                /* -d : 1 = rc (the reference's default), 0 = fw                                 */
+    uint32_t num_threads;       /* recorded in the json                                                          */
+    uint32_t frequency;         /* --cell-bc-correction: 0 unique, 1 frequency (pseudocount 1)                   */
+    uint32_t neighborhood;      /* 0 hamming-1 (the ATAC default), 1 substitution-or-shift-1                      */
+    uint64_t conf_num, conf_den;/* 0/0 = Confidence::ATAC = 9/10                                                 */
+    uint32_t device;
+    uint64_t fill_bytes;        /* 0 = 8 GiB; a device fill is a run of whole chunks of at most this many bytes   */
+    const char* cmdline;
+    struct afq_atac_gpl_hist_stats* stats_out;   /* may be NULL */
+} afq_atac_gpl_opts;
+/* Runs the whole sub-command (generate_permit_list + process_unfiltered, src/atac/cellfilter.rs): permit_freq.bin, permit_map.bin
+ * (the plan's entries, NOT the theoretical neighbourhood), correction_plan.bin, bin_recs.bin, bin_lens.bin and
+ * generate_permit_list.json in output_dir, every map in ascending key order.  The record pass runs fill by fill on the device
+ * (afq_atac_gpl_hist_rad), the correction decisions are afq_gpl_correct's.  Listed barcodes are reverse-complemented under rc; the
+ * retained ones are the listed with an exact count >= min_reads.  An RNA prelude is AFQ_ERR_UNSUPPORTED; reference lengths that
+ * give no bin at all are AFQ_ERR_BAD_INPUT "bins should not be empty" (the reference panics with these words).  This is the
+ * library entry point: the command-line word `atac generate-permit-list` is still refused by the CLI. */
+int afq_atac_generate_permit_list(const afq_atac_gpl_opts* opts);
+/* initialize_rec_list (atac/cellfilter.rs:39-54): out[n + 1] with out[0] = 0, out[r + 1] = out[r] + ceil((f32)ref_lens[r] / (f32)bin_size),
+ * quotient and ceiling in f32 as the reference computes them.  For the CPU tests. */
+void afq_atac_gpl_bin_lens(const uint32_t* ref_lens, size_t n, uint64_t bin_size, uint64_t* out);
+/* needletail's reverse_complement of a packed k-mer (k = 1..32).  For the CPU tests. */
+uint64_t afq_gpl_reverse_complement(uint64_t barcode, uint32_t k);
+
 /* Runs the whole `quant` sub-command.  Returns 0 or a negative AFQ_ERR_* code; message via afq_host_last_error(). */
 int afq_quantify(const afq_quant_opts* opts);
 const char* afq_host_last_error(void);
