@@ -132,6 +132,8 @@ EXPORTS = [
     "afq_gpl_table_slot",
     "afq_atac_gpl_hist_rad",
     "afq_atac_gpl_limits",
+    "afq_gpl_multi_hist_rad",
+    "afq_gpl_multi_limits",
     "afq_collate_rad",
     "afq_collate_limits",
     "afq_atac_collate_rad",
@@ -161,6 +163,11 @@ class AfqGplHistStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("max_ambig", C.c_uint64), ("n_long_records", C.c_uint64)]
 
 
+class AfqGplMultiHistStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_routed", C.c_uint64), ("n_unrouted", C.c_uint64),
+                ("n_long_records", C.c_uint64)]
+
+
 class AfqGplCorrectionStats(C.Structure):
     _fields_ = [("exact_distinct", C.c_uint64), ("exact_reads", C.c_uint64), ("corrected_distinct", C.c_uint64), ("corrected_reads", C.c_uint64),
                 ("ambiguous_distinct", C.c_uint64), ("ambiguous_reads", C.c_uint64), ("not_found_distinct", C.c_uint64), ("not_found_reads", C.c_uint64)]
@@ -178,6 +185,15 @@ class AfqAtacGplOpts(C.Structure):
                 ("device", C.c_uint32), ("fill_bytes", C.c_uint64), ("cmdline", C.c_char_p), ("stats_out", C.POINTER(AfqAtacGplHistStats))]
 
 
+class AfqGplMultiOpts(C.Structure):
+    """afq_gpl_multi_opts of include/afquant_host.h (afq_generate_permit_list_multi)."""
+    _fields_ = [("input_dir", C.c_char_p), ("output_dir", C.c_char_p), ("expected_ori", C.c_uint32), ("method", C.c_uint32), ("method_count", C.c_uint64),
+                ("list_file", C.c_char_p), ("min_reads", C.c_uint64), ("frequency", C.c_uint32), ("neighborhood", C.c_int32), ("conf_num", C.c_uint64),
+                ("conf_den", C.c_uint64), ("num_threads", C.c_uint32), ("device", C.c_uint32), ("cmdline", C.c_char_p), ("fill_bytes", C.c_uint64),
+                ("sample_bc_list", C.c_char_p), ("sample_correction", C.c_uint32), ("sample_neighborhood", C.c_uint32), ("sample_conf_num", C.c_uint64),
+                ("sample_conf_den", C.c_uint64), ("sample_bc_ori", C.c_uint32), ("stats_out", C.POINTER(AfqGplMultiHistStats))]
+
+
 class AfqCollateStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_uncorrected", C.c_uint64), ("n_kept", C.c_uint64),
                 ("n_alignments_in", C.c_uint64), ("n_alignments_kept", C.c_uint64), ("n_long_records", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -192,5 +208,8 @@ class AfqAtacCollateStats(C.Structure):
 GPL_ORI = {"both": 0, "either": 0, "fw": 1, "rc": 2}
 GPL_NEIGHBORHOODS = {"hamming-1": 0, "substitution-or-shift-1": 1, "edit-1": 1}
 GPL_RESOLUTIONS = {"unique": 0, "frequency": 1}
+GPL_METHODS = {"knee": 0, "expect": 1, "force": 2, "valid_bc": 3, "unfiltered": 4}                 # AFQ_GPL_*
+GPL_SAMPLE_CORRECTIONS = {"exact": 0, "unique": 1, "frequency": 2, "1-edit": 3}                     # AFQ_GPL_SAMPLE_*
+GPL_SAMPLE_ORI = {"forward": 0, "reverse": 1}
 GPL_EXACT, GPL_CORRECTED, GPL_AMBIGUOUS, GPL_NOT_FOUND = 0, 1, 2, 3
 GPL_NO_TARGET = 0xFFFFFFFF

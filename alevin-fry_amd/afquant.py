@@ -317,6 +317,14 @@ def load_library(path: str = LIB_PATH):
     lib.afq_atac_gpl_hist_rad.restype = C.c_int
     lib.afq_atac_gpl_limits.argtypes = [p(C.c_uint32)]
     lib.afq_atac_gpl_limits.restype = None
+    lib.afq_gpl_multi_hist_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                           p(C.c_uint64), C.c_uint64, p(C.c_uint64), p(p(C.c_uint32)), p(p(C.c_uint64)), p(p(C.c_uint64)),
+                                           p(_abi.AfqGplMultiHistStats)]
+    lib.afq_gpl_multi_hist_rad.restype = C.c_int
+    lib.afq_gpl_multi_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_gpl_multi_limits.restype = None
+    lib.afq_generate_permit_list_multi.argtypes = [p(_abi.AfqGplMultiOpts)]
+    lib.afq_generate_permit_list_multi.restype = C.c_int64
     lib.afq_atac_generate_permit_list.argtypes = [p(_abi.AfqAtacGplOpts)]
     lib.afq_atac_generate_permit_list.restype = C.c_int
     lib.afq_host_last_error.argtypes = []
@@ -390,6 +398,15 @@ def atac_collate_limits():
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "aln_bytes": int(out[2]), "radix_block": int(out[3])}
 
 
+def gpl_multi_limits():
+    """afq_gpl_multi_limits: {"parse_tile", "parse_halo", "lane_alns"} of the multi-barcode generate-permit-list parse - bytes staged per
+    trip, bytes staged behind them, and the number of alignments above which a record is tested by the whole wave.  Tests build their
+    edge shapes from these."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_gpl_multi_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2])}
+
+
 def atac_gpl_limits():
     """afq_atac_gpl_limits: {"parse_tile", "parse_halo", "private_bins"} of the `atac generate-permit-list` record pass - bytes a walk
     stages per trip, bytes staged behind them, bins a workgroup counts privately in LDS (0: the bins are counted in global memory)."""
@@ -417,6 +434,39 @@ def atac_generate_permit_list(input_dir, output_dir, list_file, min_reads: int =
     if rc_ != 0:
         raise AfqError(rc_, (lib.afq_host_last_error() or b"").decode())
     return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def generate_permit_list_multi(input_dir, output_dir, sample_bc_list, method="knee", method_count: int = 0, list_file=None, min_reads: int = 10,
+                               expected_ori="fw", correction="unique", neighborhood=None, confidence=(0, 0), sample_correction="exact",
+                               sample_neighborhood="hamming-1", sample_confidence=(0, 0), sample_bc_ori="forward", num_threads: int = 8, device: int = 0,
+                               fill_bytes: int = 0, cmdline: str = ""):
+    """afq_generate_permit_list_multi: the whole `generate-permit-list` step on a multi-barcode (10x Flex) RAD - the mapper's directory
+    (map.rad) and the sample barcode list in, sample_permit_map.bin, sample_<name>/permit_map.bin / permit_freq.bin, correction_plan.bin,
+    sample_info.json and generate_permit_list.json out.  method: "knee", "expect" / "force" (method_count), "valid_bc" / "unfiltered"
+    (list_file; min_reads with "unfiltered").  sample_correction: "exact", "unique", "frequency" or the deprecated "1-edit".  A
+    confidence of (0, 0) is 39/40; neighborhood None is the multi-barcode default, hamming-1.  Returns {"total_cells": ..., "stats": the
+    record pass's stats}; raises AfqError."""
+    lib = load_library()
+    st = _abi.AfqGplMultiHistStats()
+    o = _abi.AfqGplMultiOpts()
+    o.input_dir, o.output_dir, o.sample_bc_list = os.fsencode(input_dir), os.fsencode(output_dir), os.fsencode(sample_bc_list)
+    o.expected_ori = _abi.GPL_ORI[expected_ori.lower()] if isinstance(expected_ori, str) else int(expected_ori)
+    o.method = _abi.GPL_METHODS[method] if isinstance(method, str) else int(method)
+    o.method_count, o.min_reads = int(method_count), int(min_reads)
+    o.list_file = None if list_file is None else os.fsencode(list_file)
+    o.frequency = _abi.GPL_RESOLUTIONS[correction] if isinstance(correction, str) else int(correction)
+    o.neighborhood = -1 if neighborhood is None else (_abi.GPL_NEIGHBORHOODS[neighborhood] if isinstance(neighborhood, str) else int(neighborhood))
+    o.conf_num, o.conf_den = int(confidence[0]), int(confidence[1])
+    o.sample_correction = _abi.GPL_SAMPLE_CORRECTIONS[sample_correction] if isinstance(sample_correction, str) else int(sample_correction)
+    o.sample_neighborhood = _abi.GPL_NEIGHBORHOODS[sample_neighborhood] if isinstance(sample_neighborhood, str) else int(sample_neighborhood)
+    o.sample_conf_num, o.sample_conf_den = int(sample_confidence[0]), int(sample_confidence[1])
+    o.sample_bc_ori = _abi.GPL_SAMPLE_ORI[sample_bc_ori.lower()] if isinstance(sample_bc_ori, str) else int(sample_bc_ori)
+    o.num_threads, o.device, o.fill_bytes, o.cmdline = int(num_threads), int(device), int(fill_bytes), cmdline.encode()
+    o.stats_out = C.pointer(st)
+    n = lib.afq_generate_permit_list_multi(C.byref(o))
+    if n < 0:
+        raise AfqError(int(n), (lib.afq_host_last_error() or b"").decode())
+    return {"total_cells": int(n), "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
 
 
 def gpl_table_slot(barcode, n_kept, bc_bytes: int = 8):
@@ -699,6 +749,38 @@ class Quantifier:
     def gpl_limits():
         """The generate-permit-list parse's limits (module-level gpl_limits)."""
         return gpl_limits()
+
+    def gpl_multi_hist_rad(self, chunk_bytes, chunk_off, sample_observed, b0_bytes: int = 2, b1_bytes: int = 4, umi_bytes: int = 4, expected_ori="both",
+                           d_ptr: int = 0, n_bytes: int = 0):
+        """afq_gpl_multi_hist_rad: the chunks of an uncollated two-barcode RNA RAD in (host bytes, or d_ptr/n_bytes for bytes already on
+        the device) and the routing entries (packed sample barcodes, ascending, distinct); a dict out: "entry" (u32 index into
+        sample_observed), "cell" (u64) and "count" (u64) of the distinct pairs of the compatible, routed records, ascending by (entry,
+        cell), and "stats" (n_records, n_compatible, n_routed, n_unrouted, n_long_records).  Position bytes: set_aln_extra_bytes."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        ent = np.ascontiguousarray(sample_observed, dtype=np.uint64)
+        ori = _abi.GPL_ORI[expected_ori.lower()] if isinstance(expected_ori, str) else int(expected_ori)
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p = C.POINTER(C.c_uint64)
+        o_n, o_ent, o_cell, o_cnt, st = C.c_uint64(), C.POINTER(C.c_uint32)(), u64p(), u64p(), _abi.AfqGplMultiHistStats()
+        self._check(self.lib.afq_gpl_multi_hist_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), int(b0_bytes), int(b1_bytes), int(umi_bytes), ori, on_dev,
+                                                    ent.ctypes.data_as(u64p), len(ent), C.byref(o_n), C.byref(o_ent), C.byref(o_cell), C.byref(o_cnt), C.byref(st)))
+        n = int(o_n.value)
+        try:
+            mk = lambda p_, dt: (np.ctypeslib.as_array(p_, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt))
+            return {"entry": mk(o_ent, np.uint32), "cell": mk(o_cell, np.uint64), "count": mk(o_cnt, np.uint64),
+                    "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_ent, o_cell, o_cnt):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def gpl_multi_limits():
+        """The multi-barcode generate-permit-list parse's limits (module-level gpl_multi_limits)."""
+        return gpl_multi_limits()
 
     def atac_gpl_hist_rad(self, chunk_bytes, chunk_off, bin_base, bc_bytes: int = 4, bin_size: int = 100000, d_ptr: int = 0, n_bytes: int = 0):
         """afq_atac_gpl_hist_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the device)

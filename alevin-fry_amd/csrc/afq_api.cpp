@@ -24,6 +24,7 @@
 #include "../../include/afquant.h"
 #include "afq_chunk_table.h"
 #include "afq_common.h"
+#include "afq_gpl_host.h"
 #include "afq_hooks.h"
 #include "afq_kernels.h"
 
@@ -61,7 +62,7 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
@@ -69,7 +70,8 @@ const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "
                                            "k_gpl_parse", "k_gpl_count", "k_gpl_compact", "k_gpl_table", "k_gpl_correct",
                                            "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write",
                                            "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write",
-                                           "k_atac_gpl_parse", "k_atac_gpl_bins"};
+                                           "k_atac_gpl_parse", "k_atac_gpl_bins",
+                                           "k_gpl_multi_table", "k_gpl_multi_parse"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -203,7 +205,7 @@ struct AtacSortBufs {
     }
 };
 
-// afq_gpl_hist_rad's and afq_gpl_correct's
+// afq_gpl_hist_rad's and afq_gpl_correct's (afq_gpl_multi_hist_rad keeps its entry list and entry table in the correction's obs, idx, rkey, rval, cstatus)
 struct GplBufs {
     DevBuf chunks, bc, cstat, status, tkey, tcnt, ones, okey, ocnt, nout;            // histogram
     DevBuf bbase, bins, bins64, bmax;                                                // afq_atac_gpl_hist_rad's position bins
@@ -2961,6 +2963,134 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     if (stats) *stats = S;
     H.release();
     *out_n = n_out; *out_bc = obc; *out_count = ocnt;
+    return 0;
+}
+
+// multi-barcode `generate-permit-list` on the device (afq_gpl_multi.hip): entry table, parse + orientation filter + routing; the
+// counting table and its compaction are afq_gpl_hist_rad's, over the keys entry << 32 | b1.
+void afq_gpl_multi_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = 0;
+}
+
+int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes,
+                           uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed,
+                           uint64_t n_entries, uint64_t* out_n, uint32_t** out_entry, uint64_t** out_cell, uint64_t** out_count,
+                           afq_gpl_multi_hist_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || (!sample_observed && n_entries) || !out_n || !out_entry || !out_cell || !out_count)
+        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    {   // widths, orientation, the entry list (afq_gpl_host.h: the CPU suite runs these checks without a device)
+        std::string e;
+        if (int rc = gplhost::multi_check_args(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, n_entries, e)) return fail(c, rc, e);
+    }
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    // ---- chunk table
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
+    std::vector<SortChunk> chunks(n_chunks);
+    uint64_t n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + b0_bytes + b1_bytes + umi_bytes)) return chunk_fault(c, "chunk", i, f);
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    if (n_slots >= (1ull << 30))
+        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_multi_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ne1 = std::max<uint64_t>(n_entries, 1), ecap = sort_table_capacity(n_entries);
+    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 24 a slot of the largest counting table, 12 an entry and 12 a slot of its table)
+        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, 8) * 24 + ne1 * 12 + ecap * 12,
+                       need_misc = nc1 * (sizeof(SortChunk) + 16);
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_gpl_multi_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
+                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables (" +
+                        std::to_string(n_entries) + " routing entries) > " + std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->gpl;
+    HipLatch T;
+    auto hip_fail = [&]() {
+        return T.fail(c, "afq_gpl_multi_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_entries) + " routing entries)");
+    };
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
+    T(B.ones.ensure(8)); T(B.nout.ensure(4));
+    T(B.obs.ensure(8 * ne1)); T(B.idx.ensure(4 * ne1)); T(B.rkey.ensure(8 * ecap)); T(B.rval.ensure(4 * ecap)); T(B.cstatus.ensure(sizeof(DevStatus)));
+    if (!T.ok()) return hip_fail();
+    const uint8_t* d_bytes = bytes;
+    if (!bytes_on_device) {
+        T(c->d_bytes_own.ensure(n_bytes + 16));
+        if (!T.ok()) return hip_fail();
+        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
+        d_bytes = c->d_bytes_own.as<uint8_t>();
+    }
+    std::vector<uint32_t> idx(n_entries);
+    for (uint64_t i = 0; i < n_entries; ++i) idx[i] = (uint32_t)i;
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_entries) {
+        T(hipMemcpyAsync(B.obs.p, sample_observed, 8 * n_entries, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.idx.p, idx.data(), 4 * n_entries, hipMemcpyHostToDevice, s));
+    }
+    T(hipMemsetAsync(B.rkey.p, 0xFF, 8 * ecap, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.cstatus.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.ones.p, 0, 8, s));
+    T(hipMemsetAsync(B.nout.p, 0, 4, s));
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    {
+        ScopedTimer t(c, K_GPLM_TABLE, s);
+        launch_sort_table(s, B.obs.as<uint64_t>(), B.idx.as<uint32_t>(), n_entries, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(ecap - 1), B.cstatus.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_GPLM_PARSE, s);
+        launch_gpl_multi_parse(s, GplMultiParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, b0_bytes, b1_bytes, umi_bytes, c->aln_extra, expected_ori,
+                                                    B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(ecap - 1), B.bc.as<uint64_t>(), B.cstat.as<uint32_t>(),
+                                                    B.status.as<DevStatus>()});
+    }
+    T(hipGetLastError());
+    DevStatus st{}, tst{};
+    std::vector<uint32_t> cstat(4ull * n_chunks);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(&tst, B.cstatus.p, sizeof(tst), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and `sample_observed`: the copies out of them are done by now, too)
+    hc.lap("gpl multi: table + parse");
+    if (!T.ok()) return hip_fail();
+    if (tst.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: entry table status " + std::to_string(tst.err_code) + " at entry " + std::to_string(tst.err_cell)); }
+    if (st.err_code) {
+        harvest_timers(c);
+        if (st.err_code == kErrRecordWalk)
+            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(st.err_cell) + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+        return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: device status " + std::to_string(st.err_code));
+    }
+    afq_gpl_multi_hist_stats S{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        S.n_records += cstat[4 * i]; S.n_routed += cstat[4 * i + 1]; S.n_unrouted += cstat[4 * i + 2]; S.n_long_records += cstat[4 * i + 3];
+    }
+    S.n_compatible = S.n_routed + S.n_unrouted;
+    // ---- count, compact (chunk i's first cstat[4 i + 1] slots hold its keys)
+    std::vector<std::pair<uint64_t, uint64_t>> pairs;
+    if (int rc = gpl_count_sorted(c, "afq_gpl_multi_hist_rad", n_chunks, S.n_routed, 8, T, hip_fail, pairs)) return rc;
+    hc.lap("gpl multi: count + compact + sort");
+    uint64_t total = 0;
+    for (const auto& pr : pairs) total += pr.second;
+    if (total != S.n_routed)
+        return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_routed) + " routed records");
+    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    HostOuts H;
+    uint32_t* oent = (uint32_t*)H.mallocd(4 * o1);
+    uint64_t* ocell = (uint64_t*)H.mallocd(8 * o1);
+    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
+    if (!oent || !ocell || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_gpl_multi_hist_rad: host allocation failed (" + std::to_string(20 * o1) + " bytes of histogram)");
+    for (uint64_t i = 0; i < n_out; ++i) { oent[i] = (uint32_t)(pairs[i].first >> 32); ocell[i] = pairs[i].first & 0xFFFFFFFFull; ocnt[i] = pairs[i].second; }
+    if (stats) *stats = S;
+    H.release();
+    *out_n = n_out; *out_entry = oent; *out_cell = ocell; *out_count = ocnt;
     return 0;
 }
 

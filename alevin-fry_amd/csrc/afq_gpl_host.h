@@ -1,5 +1,6 @@
 // afq_gpl_host.h — the host half of `generate-permit-list` that needs no device: the confidence parser, the barcode-list parser,
-// the knee, the retained-set rules, the neighbourhood a retained barcode generates, and the writers of the five output files.
+// the knee, the retained-set rules, the neighbourhood a retained barcode generates, and the writers of the five output files; for the
+// multi-barcode step the sample list, the sample index (sources that differ from their targets), the routing entries and the plan's scopes.
 // Plain C++, no HIP: afq_host.cpp wraps these into the entry points of include/afquant_host.h, and the CPU suite compiles them on
 // their own (tests/test_gpl_host_cpu.py, under the address and undefined-behaviour sanitizers).  Every function reports through
 // `err` and a negative AFQ_ERR_* code.
@@ -214,6 +215,55 @@ inline int64_t select_retained(const uint64_t* bc, const uint64_t* count, size_t
     return (int64_t)k;
 }
 
+// correction_plan.bin (correction_plan.rs:20-45, 132-161): magic, u16 version, bincode of CorrectionPlan (u64 lengths, u32 enum
+// variants, an Option as a tag byte).  sample_len < 0: a single-barcode plan (no sample length, spec or corrections, one scope
+// without a sample barcode).  Every list arrives in the order write_to sorts it into: corrections by observed barcode, scopes by
+// sample barcode.
+struct PlanSpec { uint32_t barcode_len, neighborhood, frequency; uint64_t conf_num, conf_den, pseudocount; };
+struct PlanScope { bool has_sample; uint64_t sample_barcode; PlanSpec spec; const uint64_t* obs; const uint64_t* cor; uint64_t n; };
+inline std::string plan_bytes(int sample_len, uint32_t cell_len, const PlanSpec* sample_spec, const uint64_t* s_obs, const uint64_t* s_cor, uint64_t n_s,
+                              const std::vector<PlanScope>& scopes) {
+    std::string b("AFCORR\0\0", 8);
+    auto put = [&](const void* p, size_t n) { b.append((const char*)p, n); };
+    auto put8 = [&](uint8_t v) { put(&v, 1); };
+    auto put32 = [&](uint32_t v) { put(&v, 4); };
+    auto put64 = [&](uint64_t v) { put(&v, 8); };
+    auto put_spec = [&](const PlanSpec& sp) {   // barcode_len, neighborhood (0 HammingOne, 1 SubstitutionOrShiftOne), resolution
+        put8((uint8_t)sp.barcode_len); put32(sp.neighborhood);
+        if (sp.frequency) { put32(1); put64(sp.conf_num); put64(sp.conf_den); put64(sp.pseudocount); } else put32(0);
+    };
+    const uint16_t ver = 1;
+    put(&ver, 2);
+    if (sample_len < 0) put8(0); else { put8(1); put8((uint8_t)sample_len); }   // sample_barcode_len
+    put8((uint8_t)cell_len);                                                    // cell_barcode_len
+    if (sample_spec) { put8(1); put_spec(*sample_spec); } else put8(0);         // sample_spec
+    put64(n_s);                                                                 // sample_corrections
+    for (uint64_t i = 0; i < n_s; ++i) { put64(s_obs[i]); put64(s_cor[i]); }
+    put64(scopes.size());                                                       // cell_scopes
+    for (const PlanScope& sc : scopes) {
+        if (sc.has_sample) { put8(1); put64(sc.sample_barcode); } else put8(0);
+        put_spec(sc.spec);
+        put64(sc.n);
+        for (uint64_t i = 0; i < sc.n; ++i) { put64(sc.obs[i]); put64(sc.cor[i]); }
+    }
+    return b;
+}
+inline bool write_plan_file(const std::string& path, int sample_len, uint32_t cell_len, const PlanSpec* sample_spec, const uint64_t* s_obs, const uint64_t* s_cor,
+                            uint64_t n_s, const std::vector<PlanScope>& scopes, uint64_t* n_bytes = nullptr) {
+    GplFile f(std::fopen(path.c_str(), "wb"));
+    if (!f) return false;
+    const std::string b = plan_bytes(sample_len, cell_len, sample_spec, s_obs, s_cor, n_s, scopes);
+    if (n_bytes) *n_bytes = b.size();
+    return std::fwrite(b.data(), 1, b.size(), f.get()) == b.size();
+}
+inline bool write_map_file(const std::string& path, const uint64_t* obs, const uint64_t* cor, uint64_t n) {   // bincode HashMap<u64, u64>
+    GplFile f(std::fopen(path.c_str(), "wb"));
+    if (!f) return false;
+    bool ok = std::fwrite(&n, 8, 1, f.get()) == 1;
+    for (uint64_t i = 0; i < n && ok; ++i) { const uint64_t kv[2] = {obs[i], cor[i]}; ok = std::fwrite(kv, 8, 2, f.get()) == 2; }
+    return ok;
+}
+
 // permit_freq.bin, all_freq.bin (when t->all_bc), permit_map.bin and correction_plan.bin into the directory `out` (created if missing)
 inline int write_table_files(const std::string& out, const afq_gpl_tables* t, std::string& err) {
     if (gpl_mkdirs(out)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't create directory path " + out);
@@ -226,27 +276,11 @@ inline int write_table_files(const std::string& out, const afq_gpl_tables* t, st
         for (uint64_t i = 0; i < t->n_map && ok; ++i) { const uint64_t kv[2] = {t->map_obs[i], t->map_cor[i]}; ok = std::fwrite(kv, 8, 2, f.get()) == 2; }
         if (!ok) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize permit list.");
     }
-    {   // correction_plan.bin (correction_plan.rs:20-45): magic, u16 version, bincode of a plan with one global cell scope
-        GplFile f(std::fopen((out + "/correction_plan.bin").c_str(), "wb"));
-        if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create correction plan");
-        std::string b("AFCORR\0\0", 8);
-        auto put = [&](const void* p, size_t n) { b.append((const char*)p, n); };
-        auto put8 = [&](uint8_t v) { put(&v, 1); };
-        auto put32 = [&](uint32_t v) { put(&v, 4); };
-        auto put64 = [&](uint64_t v) { put(&v, 8); };
-        const uint16_t ver = 1;
-        put(&ver, 2);
-        put8(0);                          // sample_barcode_len: None
-        put8((uint8_t)t->barcode_len);    // cell_barcode_len
-        put8(0);                          // sample_spec: None
-        put64(0);                         // sample_corrections: empty
-        put64(1);                         // cell_scopes: one
-        put8(0);                          // sample_barcode: None
-        put8((uint8_t)t->barcode_len); put32(t->neighborhood);   // spec: barcode_len, neighborhood (0 HammingOne, 1 SubstitutionOrShiftOne)
-        if (t->frequency) { put32(1); put64(t->conf_num); put64(t->conf_den); put64(t->pseudocount); } else put32(0);
-        put64(t->n_plan);
-        for (uint64_t i = 0; i < t->n_plan; ++i) { put64(t->plan_obs[i]); put64(t->plan_cor[i]); }
-        if (std::fwrite(b.data(), 1, b.size(), f.get()) != b.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write correction plan");
+    {   // correction_plan.bin: one global cell scope
+        const PlanSpec spec{t->barcode_len, t->neighborhood, t->frequency, t->conf_num, t->conf_den, t->pseudocount};
+        const std::vector<PlanScope> scopes{PlanScope{false, 0, spec, t->plan_obs, t->plan_cor, t->n_plan}};
+        if (!write_plan_file(out + "/correction_plan.bin", -1, t->barcode_len, nullptr, nullptr, nullptr, 0, scopes))
+            return gfail(err, AFQ_ERR_BAD_INPUT, "could not write correction plan");
     }
     return 0;
 }
@@ -358,6 +392,186 @@ inline int write_atac_outputs(const afq_atac_gpl_opts* o, const afq_gpl_tables* 
     if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create metadata file.");
     if (std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
     return 0;
+}
+
+// ---- multi-barcode `generate-permit-list` (do_generate_permit_list_multi_bc, src/cellfilter.rs:789-1381)
+// the argument checks of afq_gpl_multi_hist_rad that precede device work
+inline int multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* entries, uint64_t n, std::string& err) {
+    if (!entries && n) return gfail(err, AFQ_ERR_INVALID_ARG, "null argument");
+    if (b0_bytes != 1 && b0_bytes != 2 && b0_bytes != 4) return gfail(err, AFQ_ERR_INVALID_ARG, "b0_bytes must be 1, 2 or 4");
+    if (b1_bytes != 1 && b1_bytes != 2 && b1_bytes != 4) return gfail(err, AFQ_ERR_INVALID_ARG, "b1_bytes must be 1, 2 or 4");
+    if (umi_bytes != 1 && umi_bytes != 2 && umi_bytes != 4 && umi_bytes != 8) return gfail(err, AFQ_ERR_INVALID_ARG, "umi_bytes must be 1, 2, 4 or 8");
+    if (expected_ori > 2) return gfail(err, AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
+    if (n > (1ull << 31)) return gfail(err, AFQ_ERR_UNSUPPORTED, "afq_gpl_multi_hist_rad: more than 2^31 routing entries (" + std::to_string(n) + ")");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (i && entries[i] <= entries[i - 1]) return gfail(err, AFQ_ERR_INVALID_ARG, "sample barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
+        if (entries[i] >> (8 * b0_bytes)) return gfail(err, AFQ_ERR_BAD_INPUT, "packed sample barcode " + std::to_string(entries[i]) + " does not fit " + std::to_string(b0_bytes) + " bytes");
+    }
+    return 0;
+}
+
+// load_sample_barcode_list (cellfilter.rs:1405-1569).  rotations ascend by observed barcode; names[i] belongs to canonical[i].
+struct SampleList {
+    std::vector<uint64_t> canonical;                          // in order of first appearance
+    std::vector<std::string> names;
+    std::vector<std::pair<uint64_t, uint64_t>> rotations;     // (observed, canonical)
+    uint32_t barcode_len = 0;
+    size_t sample_of(uint64_t canon) const { return (size_t)(std::find(canonical.begin(), canonical.end(), canon) - canonical.begin()); }
+};
+inline bool gpl_pack_whole(const std::string& seq, uint64_t& v) {   // the whole sequence as one k-mer (BitNuclKmer::new(seq, len, false).next()); the codes of parse_barcode_list
+    if (seq.empty() || seq.size() > 32) return false;
+    v = 0;
+    for (unsigned char ch : seq) {
+        int c;
+        switch (ch) { case 'A': case 'a': c = 0; break; case 'C': case 'c': c = 1; break; case 'G': case 'g': c = 2; break; case 'T': case 't': c = 3; break; default: return false; }
+        v = (v << 2) | (uint64_t)c;
+    }
+    return true;
+}
+inline int parse_sample_list(const std::string& text, bool reverse, SampleList& out, std::string& err) {
+    auto is_ws = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\n' || ch == '\v' || ch == '\f'; };
+    auto rc = [](const std::string& s) {
+        std::string o(s.rbegin(), s.rend());
+        for (char& ch : o) switch (ch) { case 'A': ch = 'T'; break; case 'T': ch = 'A'; break; case 'C': ch = 'G'; break; case 'G': ch = 'C'; break;
+                                         case 'a': ch = 't'; break; case 't': ch = 'a'; break; case 'c': ch = 'g'; break; case 'g': ch = 'c'; break; default: break; }
+        return o;
+    };
+    std::vector<std::pair<uint64_t, uint64_t>>& rot = out.rotations;   // kept sorted by observed
+    size_t len = 0;
+    bool have_len = false;
+    for (size_t p = 0; p < text.size();) {
+        size_t e = text.find('\n', p);
+        if (e == std::string::npos) e = text.size();
+        size_t a = p, b = e;
+        while (a < b && is_ws(text[a])) ++a;
+        while (b > a && is_ws(text[b - 1])) --b;
+        p = e + 1;
+        if (a == b || text[a] == '#') continue;
+        std::vector<std::string> parts;
+        for (size_t q = a;;) { size_t t = text.find('\t', q); if (t == std::string::npos || t >= b) { parts.push_back(text.substr(q, b - q)); break; } parts.push_back(text.substr(q, t - q)); q = t + 1; }
+        std::string obs = parts[0], canon = parts.size() >= 3 ? parts[1] : parts[0], name = parts.size() >= 3 ? parts[2] : parts.size() == 2 ? parts[1] : parts[0];
+        if (obs.size() != canon.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode '" + obs + "' and its canonical barcode '" + canon + "' have different lengths");
+        if (obs.size() < 1 || obs.size() > 32) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode length " + std::to_string(obs.size()) + " is unsupported; expected 1 through 32 bases");
+        if (have_len && len != obs.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode file mixes lengths " + std::to_string(len) + " and " + std::to_string(obs.size()));
+        len = obs.size(); have_len = true;
+        if (reverse) { obs = rc(obs); canon = rc(canon); }
+        uint64_t po = 0, pc = 0;
+        if (!gpl_pack_whole(obs, po)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't pack sample barcode: " + obs);
+        if (!gpl_pack_whole(canon, pc)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't pack sample barcode: " + canon);
+        auto it = std::lower_bound(rot.begin(), rot.end(), std::make_pair(po, (uint64_t)0));
+        if (it != rot.end() && it->first == po) {
+            if (it->second != pc) return gfail(err, AFQ_ERR_BAD_INPUT, "sample construction barcode '" + obs + "' is assigned to conflicting canonical barcodes");
+        } else rot.insert(it, {po, pc});
+        const size_t si = out.sample_of(pc);
+        if (si < out.canonical.size()) {
+            if (out.names[si] != name)
+                return gfail(err, AFQ_ERR_BAD_INPUT, "canonical sample barcode '" + canon + "' is assigned conflicting names '" + out.names[si] + "' and '" + name + "'");
+        } else { out.canonical.push_back(pc); out.names.push_back(name); }
+    }
+    if (!have_len) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode list contains no barcodes");
+    out.barcode_len = (uint32_t)len;
+    return 0;
+}
+
+// for_each_inverse_shift_candidate (barcode_correction.rs:787-817): the sources that would generate `obs` (repeats and obs itself included)
+inline void gpl_push_inverse_shift(uint64_t obs, uint32_t L, std::vector<uint64_t>& out) {
+    for (uint32_t b = 1; b < L; ++b) {
+        const uint64_t lower_mask = gpl_base_mask(b), low_wo = gpl_base_mask(b - 1);
+        const uint64_t ins_fixed = (obs & ~lower_mask) | ((obs & low_wo) << 2);
+        for (uint64_t t = 0; t < 4; ++t) out.push_back(ins_fixed | t);
+        const uint64_t del_fixed = (obs & ~gpl_base_mask(b + 1)) | ((obs >> 2) & low_wo), ob = (obs >> (2 * b)) & 3;
+        for (uint64_t lo = 0; lo < 4; ++lo)
+            for (uint64_t up = 0; up < 4; ++up)
+                if ((lo | up) == ob) out.push_back(del_fixed | (lo << (2 * (b - 1))) | (up << (2 * b)));
+    }
+}
+// CorrectionIndex over sources that differ from their targets (barcode_correction.rs:349-719), for the sample map: a few thousand
+// sources at most, on the host.  (k_gpl_correct, the cell side, assumes identity targets.)
+struct SampleSource { uint64_t source, target, count; };
+enum { kSampleExact = 0, kSampleCorrected = 1, kSampleAmbiguous = 2, kSampleNotFound = 3 };
+struct SampleIndex {
+    uint32_t L = 0; bool shift = false, frequency = false;
+    uint64_t conf_num = 39, conf_den = 40, pseudocount = 1;
+    std::vector<SampleSource> src;   // ascending by source, distinct
+    const SampleSource* find(uint64_t b) const {
+        auto it = std::lower_bound(src.begin(), src.end(), b, [](const SampleSource& s, uint64_t v) { return s.source < v; });
+        return it != src.end() && it->source == b ? &*it : nullptr;
+    }
+    void candidates(uint64_t obs, std::vector<const SampleSource*>& out) const {   // candidate_sources: every retained source once
+        std::vector<uint64_t> c;
+        for (uint32_t pos = 0; pos < L; ++pos) {
+            const uint32_t sh = 2 * pos;
+            const uint64_t base = (obs >> sh) & 3, cleared = obs & ~(3ull << sh);
+            for (uint64_t rep = 0; rep < 4; ++rep) if (rep != base) c.push_back(cleared | (rep << sh));
+        }
+        if (shift) gpl_push_inverse_shift(obs, L, c);
+        std::sort(c.begin(), c.end());
+        c.erase(std::unique(c.begin(), c.end()), c.end());
+        out.clear();
+        for (uint64_t b : c) if (const SampleSource* s = find(b)) out.push_back(s);
+    }
+    uint32_t structural(uint64_t obs, uint64_t& target) const {   // structural_resolution: exact, else unique_neighbor_target
+        if (const SampleSource* s = find(obs)) { target = s->target; return kSampleExact; }
+        std::vector<const SampleSource*> c;
+        candidates(obs, c);
+        if (c.empty()) return kSampleNotFound;
+        for (const SampleSource* s : c) if (s->target != c[0]->target) return kSampleAmbiguous;
+        target = c[0]->target;
+        return kSampleCorrected;
+    }
+    uint32_t resolve(uint64_t obs, uint64_t& target) const {   // resolve (barcode_correction.rs:427-474)
+        if (!frequency) return structural(obs, target);
+        if (const SampleSource* s = find(obs)) { target = s->target; return kSampleExact; }
+        std::vector<const SampleSource*> c;
+        candidates(obs, c);
+        if (c.empty()) return kSampleNotFound;
+        std::vector<std::pair<uint64_t, unsigned __int128>> w;   // (target, weight): a target's aliases sum
+        unsigned __int128 total = 0;
+        for (const SampleSource* s : c) {
+            const unsigned __int128 add = (unsigned __int128)s->count + pseudocount;
+            total += add;
+            auto it = std::find_if(w.begin(), w.end(), [&](const std::pair<uint64_t, unsigned __int128>& x) { return x.first == s->target; });
+            if (it == w.end()) w.push_back({s->target, add}); else it->second += add;
+        }
+        size_t best = 0;   // the greatest (weight, target)
+        for (size_t i = 1; i < w.size(); ++i) if (w[i].second > w[best].second || (w[i].second == w[best].second && w[i].first > w[best].first)) best = i;
+        // winner / total >= num / den  <=>  winner * den >= num * total (weights sum below 2^64 here - the callers' counts are read counts - so both products fit 128 bits)
+        if (w[best].second * conf_den >= (unsigned __int128)conf_num * total) { target = w[best].first; return kSampleCorrected; }
+        return kSampleAmbiguous;
+    }
+    std::vector<uint64_t> theoretical() const {   // theoretical_observations: every source and everything it generates
+        std::vector<uint64_t> o;
+        for (const SampleSource& s : src) { o.push_back(s.source); gpl_push_neighbors(s.source, L, shift, o); }
+        std::sort(o.begin(), o.end());
+        o.erase(std::unique(o.begin(), o.end()), o.end());
+        return o;
+    }
+};
+
+// build_sample_permit_map (cellfilter.rs:1581-1666): what the record pass routes by.  entry ascends; kind 0 = an exact source,
+// 1 = a structurally unique neighbour, 2 = deferred (structurally ambiguous, sample frequency only; target 0).
+struct SampleRouting { std::vector<uint64_t> entry, target; std::vector<uint8_t> kind; };
+inline SampleIndex sample_index(const SampleList& sl, uint32_t sample_correction, uint32_t sample_neighborhood) {
+    SampleIndex ix;
+    ix.L = sl.barcode_len;
+    ix.shift = sample_correction == AFQ_GPL_SAMPLE_ONE_EDIT || (sample_correction != AFQ_GPL_SAMPLE_EXACT && sample_neighborhood == 1);
+    ix.frequency = sample_correction == AFQ_GPL_SAMPLE_FREQUENCY;
+    for (const auto& r : sl.rotations) ix.src.push_back(SampleSource{r.first, r.second, 0});
+    return ix;
+}
+inline void build_sample_routing(const SampleList& sl, uint32_t sample_correction, uint32_t sample_neighborhood, SampleRouting& out) {
+    out = SampleRouting{};
+    if (sample_correction == AFQ_GPL_SAMPLE_EXACT) {
+        for (const auto& r : sl.rotations) { out.entry.push_back(r.first); out.target.push_back(r.second); out.kind.push_back(0); }
+        return;
+    }
+    const SampleIndex ix = sample_index(sl, sample_correction, sample_neighborhood);
+    for (uint64_t b : ix.theoretical()) {
+        uint64_t t = 0;
+        const uint32_t d = ix.structural(b, t);
+        if (d == kSampleExact || d == kSampleCorrected) { out.entry.push_back(b); out.target.push_back(t); out.kind.push_back(d == kSampleExact ? 0 : 1); }
+        else if (d == kSampleAmbiguous && ix.frequency) { out.entry.push_back(b); out.target.push_back(0); out.kind.push_back(2); }
+    }
 }
 
 }  // namespace gplhost

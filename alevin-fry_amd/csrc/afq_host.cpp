@@ -2004,6 +2004,24 @@ int compile_plan(afq_ctx* ctx, const std::vector<uint64_t>& hbc, const std::vect
     for (size_t r = 0; r < retained.size(); ++r) if (permitted[r]) { freq_bc.push_back(retained[r]); freq_cnt.push_back(tcount[r]); }
     return 0;
 }
+// compile_full_neighborhood (barcode_correction.rs:607-610) restricted to permitted targets: permit_map.bin of the filtered methods
+int compile_full_map(afq_ctx* ctx, const std::vector<uint64_t>& retained, const std::vector<uint64_t>& ret_cnt, const std::vector<uint8_t>& permitted, uint32_t cblen,
+                     uint32_t nbh, uint32_t frequency, uint64_t conf_num, uint64_t conf_den, std::vector<uint64_t>& map_obs, std::vector<uint64_t>& map_cor) {
+    std::vector<uint64_t> theo;
+    theo.reserve(retained.size() * (1 + 3ull * cblen + 8));
+    for (uint64_t s : retained) { theo.push_back(s); afq::gplhost::gpl_push_neighbors(s, cblen, nbh == 1, theo); }
+    std::sort(theo.begin(), theo.end());
+    theo.erase(std::unique(theo.begin(), theo.end()), theo.end());
+    const std::vector<uint64_t> zeros(theo.size(), 0);
+    uint8_t* d2 = nullptr; uint32_t* t2 = nullptr; uint64_t* c2 = nullptr;
+    const int rc = afq_gpl_correct(ctx, theo.data(), zeros.data(), theo.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, frequency, conf_num, conf_den, 1,
+                                   &d2, &t2, &c2, nullptr);
+    if (rc) return hfail(rc, afq_last_error(ctx));
+    Freer3 fr4{d2, t2, c2};
+    for (size_t i = 0; i < theo.size(); ++i)
+        if (t2[i] != 0xFFFFFFFFu && permitted[t2[i]]) { map_obs.push_back(theo[i]); map_cor.push_back(retained[t2[i]]); }
+    return 0;
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2178,19 +2196,7 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     // ---- permit_map.bin: the full theoretical neighbourhood (filtered methods), or the observed entries
     std::vector<uint64_t> map_obs, map_cor;
     if (filtered) {
-        std::vector<uint64_t> theo;
-        theo.reserve(retained.size() * (1 + 3ull * cblen + 8));
-        for (uint64_t s : retained) { theo.push_back(s); afq::gplhost::gpl_push_neighbors(s, cblen, nbh == 1, theo); }
-        std::sort(theo.begin(), theo.end());
-        theo.erase(std::unique(theo.begin(), theo.end()), theo.end());
-        const std::vector<uint64_t> zeros(theo.size(), 0);
-        uint8_t* d2 = nullptr; uint32_t* t2 = nullptr; uint64_t* c2 = nullptr;
-        rc = afq_gpl_correct(ctx.get(), theo.data(), zeros.data(), theo.size(), retained.data(), ret_cnt.data(), retained.size(), cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, 1,
-                             &d2, &t2, &c2, nullptr);
-        if (rc) return hfail(rc, afq_last_error(ctx.get()));
-        Freer3 fr4{d2, t2, c2};
-        for (size_t i = 0; i < theo.size(); ++i)
-            if (t2[i] != 0xFFFFFFFFu && permitted[t2[i]]) { map_obs.push_back(theo[i]); map_cor.push_back(retained[t2[i]]); }
+        if (int rc2 = compile_full_map(ctx.get(), retained, ret_cnt, permitted, cblen, nbh, o->frequency ? 1 : 0, conf_num, conf_den, map_obs, map_cor)) return rc2;
     } else { map_obs = plan_obs; map_cor = plan_cor; }
     afq_gpl_tables T{};
     T.barcode_len = cblen; T.neighborhood = nbh; T.frequency = o->frequency ? 1 : 0; T.filtered = filtered ? 1 : 0;
@@ -2210,6 +2216,360 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     std::fprintf(stderr, "total number of distinct corrected barcodes : %llu\n", (unsigned long long)cs.corrected_distinct);
     if (o->corrected_out) *o->corrected_out = cs.corrected_distinct;
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// `alevin-fry generate-permit-list` on a multi-barcode (10x Flex) RAD file (do_generate_permit_list_multi_bc, src/cellfilter.rs:789-1381;
+// compile_multi_sample_cell_output, 193-366; the sample list and its permit map, 1405-1682).  The record pass runs on the device
+// (afq_gpl_multi_hist_rad) over the ROUTING ENTRIES - the exact sources, the structurally unique neighbours and, under sample
+// frequency, the structurally ambiguous barcodes; the host derives everything else from the entry index of a pair: the sample, the
+// exact counts that become the priors, and the replay of the deferred pairs (the reference spools them, correction_spool.rs; here
+// they are rows of the same output).  The cell correction of every sample is the single-barcode path's (afq_gpl_correct).
+int afq_gpl_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed, uint64_t n_entries) {
+    std::string e;
+    const int r = afq::gplhost::multi_check_args(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, n_entries, e);
+    return r ? hfail(r, e) : 0;
+}
+int64_t afq_gpl_multi_routing(const uint8_t* text, size_t n, int reverse, uint32_t sample_correction, uint32_t sample_neighborhood, uint64_t* entry, uint64_t* target,
+                              uint8_t* kind, size_t cap, uint32_t* barcode_len, uint32_t* n_samples) {
+    if (!text && n) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+    if (sample_correction > AFQ_GPL_SAMPLE_ONE_EDIT) return hfail(AFQ_ERR_INVALID_ARG, "unknown sample correction mode");
+    if (sample_neighborhood > 1) return hfail(AFQ_ERR_INVALID_ARG, "unknown barcode neighbourhood; expected hamming-1 or substitution-or-shift-1");
+    afq::gplhost::SampleList sl;
+    std::string e;
+    if (int rc = afq::gplhost::parse_sample_list(std::string((const char*)text, n), reverse != 0, sl, e)) return hfail(rc, e);
+    afq::gplhost::SampleRouting r;
+    afq::gplhost::build_sample_routing(sl, sample_correction, sample_neighborhood, r);
+    for (size_t i = 0; i < r.entry.size() && i < cap; ++i) { if (entry) entry[i] = r.entry[i]; if (target) target[i] = r.target[i]; if (kind) kind[i] = r.kind[i]; }
+    if (barcode_len) *barcode_len = sl.barcode_len;
+    if (n_samples) *n_samples = (uint32_t)sl.canonical.size();
+    return (int64_t)r.entry.size();
+}
+
+namespace {
+// format!("{:?}", path): a quoted string with quotes and backslashes escaped
+void rust_debug_str(const char* s, std::string& o) {
+    o += '"';
+    for (const char* p = s ? s : ""; *p; ++p) { if (*p == '"' || *p == '\\') o.push_back('\\'); o.push_back(*p); }
+    o += '"';
+}
+struct CellCounts { std::vector<uint64_t> bc, cnt; };   // ascending by barcode
+// one entry's cells (ascending) into a sample's two histograms: listed cells feed the retained set, the others only the correction
+void add_cells(const uint64_t* cell, const uint64_t* cnt, size_t n, const std::vector<uint64_t>* whitelist, CellCounts& hist, CellCounts& unmatched) {
+    if (!whitelist) { merge_histogram(hist.bc, hist.cnt, cell, cnt, n); return; }
+    std::vector<uint64_t> ib, ic, ob, oc;
+    for (size_t i = 0; i < n; ++i) {
+        const bool in = std::binary_search(whitelist->begin(), whitelist->end(), cell[i]);
+        (in ? ib : ob).push_back(cell[i]); (in ? ic : oc).push_back(cnt[i]);
+    }
+    if (!ib.empty()) merge_histogram(hist.bc, hist.cnt, ib.data(), ic.data(), ib.size());
+    if (!ob.empty()) merge_histogram(unmatched.bc, unmatched.cnt, ob.data(), oc.data(), ob.size());
+}
+}  // namespace
+
+int64_t afq_generate_permit_list_multi(const afq_gpl_multi_opts* o) {
+    using namespace afq::gplhost;
+    if (!o || !o->input_dir || !o->output_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (o->expected_ori > 2) return hfail(AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
+    if (o->method > AFQ_GPL_UNFILTERED) return hfail(AFQ_ERR_INVALID_ARG, "unknown filter method");
+    if ((o->method == AFQ_GPL_VALID_BC || o->method == AFQ_GPL_UNFILTERED) && !o->list_file) return hfail(AFQ_ERR_INVALID_ARG, "the filter method needs a barcode list file");
+    if (o->method == AFQ_GPL_UNFILTERED && o->min_reads < 1) return hfail(AFQ_ERR_INVALID_ARG, "min-reads < 1 is not supported, the value " + std::to_string(o->min_reads) + " was provided");
+    if (o->neighborhood > 1 || o->sample_neighborhood > 1) return hfail(AFQ_ERR_INVALID_ARG, "unknown barcode neighbourhood; expected hamming-1 or substitution-or-shift-1");
+    if (o->sample_correction > AFQ_GPL_SAMPLE_ONE_EDIT) return hfail(AFQ_ERR_INVALID_ARG, "unknown sample correction mode");
+    if (o->sample_bc_ori > 1) return hfail(AFQ_ERR_INVALID_ARG, "sample_bc_ori must be 0 (forward) or 1 (reverse)");
+    uint64_t conf_num = 39, conf_den = 40, sconf_num = 39, sconf_den = 40;
+    if (o->conf_den || o->conf_num) { std::string e; if (int rc = confidence_new(o->conf_num, o->conf_den, &conf_num, &conf_den, e)) return hfail(rc, e); }
+    if (o->sample_conf_den || o->sample_conf_num) { std::string e; if (int rc = confidence_new(o->sample_conf_num, o->sample_conf_den, &sconf_num, &sconf_den, e)) return hfail(rc, e); }
+    const std::string in = o->input_dir, out = o->output_dir;
+    if (!file_exists(in)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + in + "\" does not exist");
+    MappedFile mf;
+    if (!mf.open(in + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "could not open input rad file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    // ---- the prelude: quant's checks for multi-barcode records (afq_quantify)
+    auto has_tag = [](const std::vector<TagDesc>& v, const char* name) { for (auto& t : v) if (t.name == name) return true; return false; };
+    if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len"))
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode generate-permit-list: this is a scATAC RAD file");
+    if (!P.file_tag_vals.count("num_barcodes") || P.file_tag_vals["num_barcodes"] <= 1)
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode generate-permit-list: this is a single-barcode RAD file (no num_barcodes > 1 file tag); use generate-permit-list");
+    if (has_tag(P.aln_tags, "pos")) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD records with alignment positions (alignment tag pos) are not supported");
+    const uint64_t num_barcodes = P.file_tag_vals["num_barcodes"];
+    if (num_barcodes != 2 || P.read_tags.size() != 3 || P.read_tags[0].name != "b0" || P.read_tags[1].name != "b1" || P.read_tags[2].name != "u")
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: only two barcode levels with read tags (b0, b1, u) are supported");
+    const uint32_t w0 = (uint32_t)int_type_bytes(P.read_tags[0].type), w1 = (uint32_t)int_type_bytes(P.read_tags[1].type), wu = (uint32_t)int_type_bytes(P.read_tags[2].type);
+    if (!w0 || !w1 || w0 > 4 || w1 > 4 || !wu) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: b0 and b1 must be integers of 1, 2 or 4 bytes (u8/u16/u32)");
+    if (P.aln_tags.size() != 1 || P.aln_tags[0].type != 3) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: the alignment-level tags must be one u32 (ref | orientation)");
+    if (!P.file_tag_vals.count("b1len")) return hfail(AFQ_ERR_BAD_INPUT, "multi-barcode RAD file should have a \"b1len\" file-level tag");
+    const uint32_t cblen = (uint32_t)P.file_tag_vals["b1len"];
+    if (cblen < 1 || cblen > 32) return hfail(AFQ_ERR_BAD_INPUT, "barcode length must be between 1 and 32 (got " + std::to_string(cblen) + ")");
+    // ---- the sample list and the routing entries
+    if (!o->sample_bc_list)
+        return hfail(AFQ_ERR_INVALID_ARG, "Multi-barcode RAD file detected (" + std::to_string(num_barcodes) + " barcode levels), but --sample-bc-list was not provided. "
+                     "A known sample barcode list is required for multi-barcode processing.");
+    SampleList sl;
+    {
+        std::vector<uint8_t> raw;
+        if (!read_file(o->sample_bc_list, raw)) return hfail(AFQ_ERR_BAD_INPUT, std::string("couldn't open sample barcode list: ") + o->sample_bc_list);
+        std::string e;
+        if (int rc2 = parse_sample_list(std::string(raw.begin(), raw.end()), o->sample_bc_ori == 1, sl, e)) return hfail(rc2, e);
+    }
+    if (sl.barcode_len > 4 * w0)
+        return hfail(AFQ_ERR_BAD_INPUT, "sample barcodes of " + std::to_string(sl.barcode_len) + " bases do not fit the " + std::to_string(w0) + "-byte b0 field of the records");
+    const bool sample_frequency = o->sample_correction == AFQ_GPL_SAMPLE_FREQUENCY;
+    SampleRouting routing;
+    build_sample_routing(sl, o->sample_correction, o->sample_neighborhood, routing);
+    const size_t n_ent = routing.entry.size(), n_samples = sl.canonical.size();
+    // ---- the -b list, or the -u whitelist that splits every sample's histogram
+    std::vector<uint64_t> listed;
+    if (o->method == AFQ_GPL_VALID_BC || o->method == AFQ_GPL_UNFILTERED) {
+        std::string txt;
+        if (int rc2 = read_list_text(o->list_file, txt)) return rc2;
+        const int unf = o->method == AFQ_GPL_UNFILTERED;
+        const int64_t n = afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), unf, cblen, nullptr, 0, nullptr);
+        if (n < 0) return (int)n;
+        listed.resize((size_t)n);
+        afq_gpl_parse_barcode_list((const uint8_t*)txt.data(), txt.size(), unf, cblen, listed.data(), listed.size(), nullptr);
+        std::sort(listed.begin(), listed.end());
+        listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
+        if (!unf) for (uint64_t b : listed) if (cblen < 32 && b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    }
+    const std::vector<uint64_t>* whitelist = o->method == AFQ_GPL_UNFILTERED ? &listed : nullptr;
+    // ---- the chunk table
+    std::vector<uint64_t> chunk_off;
+    {
+        size_t p = P.first_chunk;
+        for (uint64_t k = 0; k < P.num_chunks; ++k) {
+            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
+            uint32_t nb; std::memcpy(&nb, rad + p, 4);
+            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+            chunk_off.push_back(p); p += nb;
+        }
+    }
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx(raw);
+    // ---- the record pass: one device fill per run of chunks of at most fill_bytes, the sorted outputs merged under the key entry << 32 | cell
+    const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
+    std::vector<uint64_t> pkey, pcnt;
+    afq_gpl_multi_hist_stats S{};
+    for (size_t c0 = 0; c0 < chunk_off.size();) {
+        size_t c1 = c0;
+        uint64_t nrec_sum = 0;
+        auto chunk_end = [&](size_t i) { uint32_t nb; std::memcpy(&nb, rad + chunk_off[i], 4); return chunk_off[i] + nb; };
+        while (c1 < chunk_off.size()) {
+            uint32_t nr; std::memcpy(&nr, rad + chunk_off[c1] + 4, 4);
+            if (c1 > c0 && (chunk_end(c1) - chunk_off[c0] > fill_bytes || nrec_sum + nr >= (1ull << 30))) break;
+            nrec_sum += nr; ++c1;
+        }
+        const uint64_t base = chunk_off[c0];
+        std::vector<uint64_t> rel(c1 - c0);
+        for (size_t i = c0; i < c1; ++i) rel[i - c0] = chunk_off[i] - base;
+        uint64_t n = 0, *cell = nullptr, *cnt = nullptr;
+        uint32_t* ent = nullptr;
+        afq_gpl_multi_hist_stats st{};
+        rc = afq_gpl_multi_hist_rad(ctx.get(), rad + base, (size_t)(chunk_end(c1 - 1) - base), rel.data(), (uint32_t)rel.size(), w0, w1, wu, o->expected_ori, 0,
+                                    routing.entry.data(), n_ent, &n, &ent, &cell, &cnt, &st);
+        if (rc) {
+            std::string m = afq_last_error(ctx.get());
+            if (c0 && m.compare(0, 6, "chunk ") == 0) m += " (chunks of this fill are numbered from chunk " + std::to_string(c0) + " of the file)";
+            return hfail(rc, m);
+        }
+        Freer3 fr{ent, cell, cnt};
+        S.n_records += st.n_records; S.n_compatible += st.n_compatible; S.n_routed += st.n_routed; S.n_unrouted += st.n_unrouted; S.n_long_records += st.n_long_records;
+        std::vector<uint64_t> key(n);
+        for (uint64_t i = 0; i < n; ++i) key[i] = (uint64_t)ent[i] << 32 | cell[i];
+        merge_histogram(pkey, pcnt, key.data(), cnt, n);
+        c0 = c1;
+    }
+    if (o->stats_out) *o->stats_out = S;
+    // ---- per entry: its reads and its run of (cell, count) rows; the immediately routed entries feed their sample
+    std::vector<size_t> run_lo(n_ent + 1, pkey.size());
+    std::vector<uint64_t> entry_reads(n_ent, 0), pcell(pkey.size());
+    {
+        size_t i = 0;
+        for (size_t e = 0; e < n_ent; ++e) {
+            run_lo[e] = i;
+            for (; i < pkey.size() && (pkey[i] >> 32) == e; ++i) { entry_reads[e] += pcnt[i]; pcell[i] = pkey[i] & 0xFFFFFFFFull; }
+        }
+        run_lo[n_ent] = i;
+        if (i != pkey.size()) return hfail(AFQ_ERR_HIP, "afq_generate_permit_list_multi: the record pass returned a pair beyond its " + std::to_string(n_ent) + " routing entries");
+    }
+    if (cblen < 16) for (uint64_t b : pcell) if (b >= (1ull << (2 * cblen))) return hfail(AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(b) + " does not fit declared length " + std::to_string(cblen));
+    std::vector<CellCounts> hist(n_samples), unmatched(n_samples);
+    uint64_t r_exact = 0, r_unique = 0, r_deferred = 0, r_accepted = 0, r_rejected = 0;
+    auto feed = [&](size_t e, uint64_t canon) {
+        const size_t si = sl.sample_of(canon);
+        add_cells(pcell.data() + run_lo[e], pcnt.data() + run_lo[e], run_lo[e + 1] - run_lo[e], whitelist, hist[si], unmatched[si]);
+    };
+    for (size_t e = 0; e < n_ent; ++e) {
+        if (routing.kind[e] == 2) { r_deferred += entry_reads[e]; continue; }
+        (routing.kind[e] == 0 ? r_exact : r_unique) += entry_reads[e];
+        if (entry_reads[e]) feed(e, routing.target[e]);
+    }
+    // ---- the final sample permit map; under frequency the exact counts are the priors and every deferred entry is resolved once
+    std::vector<uint64_t> smap_obs, smap_cor;
+    double replay_s = 0;
+    if (sample_frequency) {
+        SampleIndex ix = sample_index(sl, o->sample_correction, o->sample_neighborhood);
+        ix.conf_num = sconf_num; ix.conf_den = sconf_den; ix.pseudocount = 1;
+        for (size_t e = 0; e < n_ent; ++e)
+            if (routing.kind[e] == 0) {
+                auto it = std::lower_bound(ix.src.begin(), ix.src.end(), routing.entry[e], [](const SampleSource& s, uint64_t v) { return s.source < v; });
+                it->count = entry_reads[e];   // (an exact source is a rotation: it is there)
+            }
+        for (uint64_t b : ix.theoretical()) {   // compile_full_neighborhood
+            uint64_t t = 0;
+            if (ix.resolve(b, t) <= kSampleCorrected) { smap_obs.push_back(b); smap_cor.push_back(t); }
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t e = 0; e < n_ent; ++e) {
+            if (routing.kind[e] != 2 || !entry_reads[e]) continue;
+            uint64_t t = 0;
+            if (ix.resolve(routing.entry[e], t) <= kSampleCorrected) { r_accepted += entry_reads[e]; feed(e, t); } else r_rejected += entry_reads[e];
+        }
+        replay_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        for (size_t e = 0; e < n_ent; ++e) { smap_obs.push_back(routing.entry[e]); smap_cor.push_back(routing.target[e]); }
+    }
+    const uint64_t matched = r_exact + r_unique + r_accepted, unmatched_reads = S.n_unrouted + r_rejected;
+    std::fprintf(stderr, "First pass complete: %llu total reads, %llu matched to samples, %llu unmatched\n", (unsigned long long)S.n_records, (unsigned long long)matched,
+                 (unsigned long long)unmatched_reads);
+    if (gpl_mkdirs(out)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't create output directory " + out);
+    if (!write_map_file(out + "/sample_permit_map.bin", smap_obs.data(), smap_cor.data(), smap_obs.size())) return hfail(AFQ_ERR_BAD_INPUT, "failed to serialize sample permit map");
+    // ---- per sample: the retained set, the correction (on the device), the files
+    const uint32_t nbh = o->neighborhood >= 0 ? (uint32_t)o->neighborhood : 0u;   // resolved_cell_neighborhood(true), prog_opts.rs:135-144
+    const uint32_t freq = o->frequency ? 1u : 0u;
+    if (freq && nbh == 1)
+        std::fprintf(stderr, "cell-barcode Frequency correction is using substitution-or-shift-1. RAD stores no barcode base qualities or indel-error model, so this is an abundance heuristic rather than a calibrated indel posterior.\n");
+    static const char* const kStat[8] = {"exact_distinct", "exact_reads", "corrected_distinct", "corrected_reads", "ambiguous_distinct", "ambiguous_reads", "not_found_distinct", "not_found_reads"};
+    const PlanSpec cspec{cblen, nbh, freq, conf_num, conf_den, 1};
+    std::vector<GplPlan> plans(n_samples);
+    std::vector<std::string> infos(n_samples);
+    uint64_t total_cells = 0;
+    const auto cc0 = std::chrono::steady_clock::now();
+    for (size_t si = 0; si < n_samples; ++si) {
+        const std::string& name = sl.names[si];
+        const std::string sdir = out + "/sample_" + name;
+        if (gpl_mkdirs(sdir)) return hfail(AFQ_ERR_BAD_INPUT, "couldn't create directory path " + sdir);
+        char hex[32];
+        std::snprintf(hex, sizeof hex, "0x%llx", (unsigned long long)sl.canonical[si]);
+        uint64_t num_reads = 0, num_cells = 0, collatable = 0;
+        GplPlan& plan = plans[si];
+        if (!hist[si].bc.empty()) {   // (a sample without a listed read keeps its directory and its entry, and gets no permit files)
+            const CellCounts& h = hist[si];
+            std::vector<uint64_t> retained;
+            if (o->method == AFQ_GPL_VALID_BC) retained = listed;
+            else {
+                const uint32_t m = o->method;
+                const uint64_t arg = m == AFQ_GPL_UNFILTERED ? o->min_reads : o->method_count;
+                const int64_t n = afq_gpl_select_retained(h.bc.data(), h.cnt.data(), h.bc.size(), m, arg, nullptr, 0);
+                if (n < 0) return (int)n;
+                retained.resize((size_t)n);
+                afq_gpl_select_retained(h.bc.data(), h.cnt.data(), h.bc.size(), m, arg, retained.data(), retained.size());
+            }
+            CellCounts obs = h;
+            if (!unmatched[si].bc.empty()) merge_histogram(obs.bc, obs.cnt, unmatched[si].bc.data(), unmatched[si].cnt.data(), unmatched[si].bc.size());
+            std::vector<uint64_t> ret_cnt(retained.size());
+            uint64_t exact_retained = 0;
+            for (size_t i = 0; i < retained.size(); ++i) {
+                auto it = std::lower_bound(obs.bc.begin(), obs.bc.end(), retained[i]);
+                ret_cnt[i] = it != obs.bc.end() && *it == retained[i] ? obs.cnt[it - obs.bc.begin()] : 0;
+                exact_retained += ret_cnt[i];
+            }
+            if (int rc2 = compile_plan(ctx.get(), obs.bc, obs.cnt, retained, ret_cnt, cblen, nbh, freq, conf_num, conf_den, plan)) return rc2;
+            std::vector<uint64_t> map_obs, map_cor;
+            if (o->method != AFQ_GPL_UNFILTERED) {
+                if (int rc2 = compile_full_map(ctx.get(), retained, ret_cnt, plan.permitted, cblen, nbh, freq, conf_num, conf_den, map_obs, map_cor)) return rc2;
+            } else { map_obs = plan.plan_obs; map_cor = plan.plan_cor; }
+            if (!write_map_file(sdir + "/permit_map.bin", map_obs.data(), map_cor.data(), map_obs.size())) return hfail(AFQ_ERR_BAD_INPUT, "failed to serialize permit map");
+            if (!write_freq_file(sdir + "/permit_freq.bin", cblen, plan.freq_bc.data(), plan.freq_cnt.data(), plan.freq_bc.size()))
+                return hfail(AFQ_ERR_BAD_INPUT, "failed to write permit freq for sample '" + name + "'");
+            for (uint64_t v : plan.freq_cnt) collatable += v;
+            num_cells = plan.freq_bc.size();
+            num_reads = o->method == AFQ_GPL_UNFILTERED ? collatable : exact_retained;
+        }
+        total_cells += num_cells;
+        const afq_gpl_correction_stats& cs = plan.cs;
+        const uint64_t sv[8] = {cs.exact_distinct, cs.exact_reads, cs.corrected_distinct, cs.corrected_reads, cs.ambiguous_distinct, cs.ambiguous_reads, cs.not_found_distinct, cs.not_found_reads};
+        std::string j = "    {\n      \"name\": " + gpl_json_str(name.c_str()) + ",\n      \"barcode\": \"" + hex + "\",\n      \"num_reads\": " + std::to_string(num_reads) +
+                        ",\n      \"num_cells\": " + std::to_string(num_cells) + ",\n      \"collatable_reads\": " + std::to_string(collatable) + ",\n      \"cell_correction\": {\n";
+        for (int i = 0; i < 8; ++i) j += std::string("        \"") + kStat[i] + "\": " + std::to_string(sv[i]) + (i < 7 ? ",\n" : "\n");
+        infos[si] = j + "      }\n    }";
+    }
+    const double cell_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - cc0).count();
+    // ---- correction_plan.bin: the sample scope and one cell scope per sample, ascending by canonical barcode
+    std::vector<size_t> order(n_samples);
+    for (size_t i = 0; i < n_samples; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return sl.canonical[a] < sl.canonical[b]; });
+    std::vector<PlanScope> scopes;
+    for (size_t si : order) scopes.push_back(PlanScope{true, sl.canonical[si], cspec, plans[si].plan_obs.data(), plans[si].plan_cor.data(), plans[si].plan_obs.size()});
+    const bool shift_s = o->sample_correction == AFQ_GPL_SAMPLE_ONE_EDIT || o->sample_neighborhood == 1;
+    const PlanSpec sspec{sl.barcode_len, shift_s ? 1u : 0u, sample_frequency ? 1u : 0u, sconf_num, sconf_den, 1};
+    const bool have_sspec = o->sample_correction != AFQ_GPL_SAMPLE_EXACT;
+    uint64_t plan_n = 0;
+    const auto pw0 = std::chrono::steady_clock::now();
+    if (!write_plan_file(out + "/correction_plan.bin", (int)sl.barcode_len, cblen, have_sspec ? &sspec : nullptr, smap_obs.data(), smap_cor.data(), smap_obs.size(), scopes, &plan_n))
+        return hfail(AFQ_ERR_BAD_INPUT, "could not write correction plan");
+    const double plan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - pw0).count();
+    // ---- sample_info.json and generate_permit_list.json (the json! documents of cellfilter.rs:1316-1368)
+    static const char* const kOriSym[3] = {"both", "fw", "rc"};
+    static const char* const kNbh[2] = {"hamming-1", "substitution-or-shift-1"};
+    static const char* const kModeDebug[4] = {"Exact", "Unique", "Frequency", "OneEdit"};
+    static const char* const kModeResolved[4] = {"exact", "unique", "frequency", "unique"};
+    auto common = [&](const char* ind) {
+        std::string j;
+        j += std::string(ind) + "\"cell_bc_correction\": \"" + (freq ? "frequency" : "unique") + "\",\n";
+        j += std::string(ind) + "\"cell_bc_neighborhood\": \"" + kNbh[nbh] + "\",\n";
+        j += std::string(ind) + "\"cell_bc_confidence\": \"" + std::to_string(conf_num) + "/" + std::to_string(conf_den) + "\",\n";
+        j += std::string(ind) + "\"sample_bc_correction\": \"" + kModeResolved[o->sample_correction] + "\",\n";
+        j += std::string(ind) + "\"sample_bc_neighborhood\": " + (have_sspec ? std::string("\"") + kNbh[shift_s ? 1 : 0] + "\"" : std::string("null")) + ",\n";
+        j += std::string(ind) + "\"sample_bc_confidence\": \"" + std::to_string(sconf_num) + "/" + std::to_string(sconf_den) + "\"";
+        return j;
+    };
+    auto dbl = [](double v) { char b[64]; std::snprintf(b, sizeof b, "%.9g", v); std::string s = b; if (s.find_first_of(".e") == std::string::npos) s += ".0"; return s; };
+    {
+        std::string j = "{\n";
+        j += "  \"num_samples\": " + std::to_string(n_samples) + ",\n  \"num_barcodes\": " + std::to_string(num_barcodes) + ",\n  \"total_cells\": " + std::to_string(total_cells) + ",\n";
+        j += "  \"total_reads\": " + std::to_string(S.n_records) + ",\n  \"matched_reads\": " + std::to_string(matched) + ",\n  \"unmatched_reads\": " + std::to_string(unmatched_reads) + ",\n";
+        j += std::string("  \"sample_correction_mode\": \"") + kModeDebug[o->sample_correction] + "\",\n  \"sample_bc_ori\": \"" + (o->sample_bc_ori ? "Reverse" : "Forward") + "\",\n";
+        j += common("  ") + ",\n";
+        j += "  \"cell_correction_seconds\": " + dbl(cell_s) + ",\n  \"correction_plan_bytes\": " + std::to_string(plan_n) + ",\n  \"correction_plan_write_seconds\": " + dbl(plan_s) + ",\n";
+        j += "  \"sample_routing\": {\n    \"exact\": " + std::to_string(r_exact) + ",\n    \"structurally_unique\": " + std::to_string(r_unique) + ",\n    \"immediate_rejected\": " +
+             std::to_string(S.n_unrouted) + ",\n    \"deferred\": " + std::to_string(r_deferred) + ",\n    \"deferred_accepted\": " + std::to_string(r_accepted) +
+             ",\n    \"deferred_rejected\": " + std::to_string(r_rejected) + ",\n    \"spill_runs\": 0,\n    \"spill_pairs_after_run_length_encoding\": 0,\n"
+             "    \"spill_compressed_bytes\": 0,\n    \"spill_uncompressed_bytes\": 0,\n    \"replay_seconds\": " + dbl(replay_s) + "\n  },\n";
+        j += "  \"samples\": [\n";
+        for (size_t si = 0; si < n_samples; ++si) j += infos[si] + (si + 1 < n_samples ? ",\n" : "\n");
+        j += "  ]\n}";
+        GplFile f(std::fopen((out + "/sample_info.json").c_str(), "w"));
+        if (!f || std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return hfail(AFQ_ERR_BAD_INPUT, "cannot write sample_info.json");
+    }
+    {
+        std::string fm;   // format!("{:?}", CellFilterMethod)
+        switch (o->method) {
+            case AFQ_GPL_KNEE: fm = "KneeFinding"; break;
+            case AFQ_GPL_EXPECT: fm = "ExpectCells(" + std::to_string(o->method_count) + ")"; break;
+            case AFQ_GPL_FORCE: fm = "ForceCells(" + std::to_string(o->method_count) + ")"; break;
+            case AFQ_GPL_VALID_BC: fm = "ExplicitList("; rust_debug_str(o->list_file, fm); fm += ")"; break;
+            default: fm = "UnfilteredExternalList("; rust_debug_str(o->list_file, fm); fm += ", " + std::to_string(o->min_reads) + ")"; break;
+        }
+        std::string j = "{\n  \"velo_mode\": false,\n";
+        j += std::string("  \"expected_ori\": \"") + kOriSym[o->expected_ori] + "\",\n  \"version_str\": \"0.18.0\",\n  \"cmd\": " + gpl_json_str(o->cmdline) + ",\n";
+        j += "  \"permit-list-type\": " + gpl_json_str(fm.c_str()) + ",\n  \"multi_barcode\": true,\n  \"num_barcodes\": " + std::to_string(num_barcodes) + ",\n";
+        j += common("  ") + "\n}";
+        GplFile f(std::fopen((out + "/generate_permit_list.json").c_str(), "w"));
+        if (!f || std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return hfail(AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
+    }
+    std::fprintf(stderr, "Multi-barcode permit list generation complete: %zu samples, %llu total cells\n", n_samples, (unsigned long long)total_cells);
+    return (int64_t)total_cells;
 }
 
 // ---------------------------------------------------------------------------

@@ -279,6 +279,18 @@ void launch_gpl_count(hipStream_t s, const SortChunk* chunks, uint32_t n_chunks,
 void launch_gpl_compact(hipStream_t s, const uint64_t* tab_key, const unsigned long long* tab_cnt, uint64_t cap, uint64_t* o_key, uint64_t* o_cnt,
                         uint32_t* n_out);
 void launch_gpl_correct(hipStream_t s, const GplCorrectArgs& a);
+// multi-barcode `generate-permit-list`: the (routing entry, cell barcode) pairs of an uncollated two-barcode RNA RAD
+// (afq_gpl_multi.hip).  The walk and its limits are the GPL parse's; the entry table is launch_sort_table's (no entry is all-ones:
+// a sample barcode has at most 4 bytes); the keys go through launch_gpl_count / launch_gpl_compact.
+struct GplMultiParseArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks;
+    uint32_t b0_bytes, b1_bytes, umi_bytes, aln_extra, expected_ori;
+    const uint64_t* tab_key; const uint32_t* tab_val; uint32_t tab_mask;   // sample barcode -> its index in the entry list
+    uint64_t* o_key;         // a slot per record of the chunk table: entry << 32 | b1 of a chunk's routed records first (chunk_stat[1] of them)
+    uint32_t* chunk_stat;    // [n_chunks][4]: records seen, routed, compatible but unrouted, long records
+    DevStatus* st;
+};
+void launch_gpl_multi_parse(hipStream_t s, const GplMultiParseArgs& a);
 // `atac generate-permit-list`: the barcode of every record of an uncollated scATAC RAD, the largest na and the position-bin
 // histogram of the records with one alignment (afq_atac_gpl.hip).  The walk and its limits are k_sort_parse's (kSortParseTile,
 // kSortParseHalo); the barcode column goes through launch_gpl_count / launch_gpl_compact.

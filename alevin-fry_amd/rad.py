@@ -343,6 +343,27 @@ def encode_chunks(chunks, bc_bytes: int = 4, umi_bytes: int = 4, pos_bytes: int 
     return bytes(out), np.asarray(offs, dtype=np.uint64)
 
 
+def encode_multi_bc_chunks(chunks, b0_bytes: int = 2, b1_bytes: int = 4, umi_bytes: int = 4, pos_bytes: int = 0, pad: int = 0):
+    """chunks of an UNCOLLATED two-barcode (10x Flex) RNA RAD, as multi-barcode generate-permit-list reads them: a list of chunks,
+    each a list of records (b0, b1, umi, [(ref, fw), ...]) - the sample barcode b0 and the cell barcode b1 per record, in the order
+    of the read-tag section (b0, b1, u); alignments, positions and `pad` as encode_chunks.  Returns (bytes, chunk_off[u64])."""
+    out = bytearray(pad)
+    offs = []
+    for recs in chunks:
+        offs.append(len(out))
+        body = bytearray()
+        for b0, b1, umi, alns in recs:
+            body += len(alns).to_bytes(4, "little") + int(b0).to_bytes(b0_bytes, "little") + int(b1).to_bytes(b1_bytes, "little") + int(umi).to_bytes(umi_bytes, "little")
+            if pos_bytes == 0 and len(alns) > 64:
+                a = np.asarray(alns, dtype=np.int64).reshape(-1, 2)
+                body += ((a[:, 0] & 0x7FFFFFFF) | (a[:, 1].astype(bool).astype(np.int64) << 31)).astype("<u4").tobytes()
+                continue
+            for ref, fw in alns:
+                body += ((int(ref) & 0x7FFFFFFF) | (0x80000000 if fw else 0)).to_bytes(4, "little") + bytes(pos_bytes)
+        out += (len(body) + 8).to_bytes(4, "little") + len(recs).to_bytes(4, "little") + body
+    return bytes(out), np.asarray(offs, dtype=np.uint64)
+
+
 NEIGHBORHOOD_TAGS = {"hamming-1": 0, "substitution-or-shift-1": 1}   # BarcodeNeighborhood's variants in declaration order
 
 

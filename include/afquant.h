@@ -366,6 +366,46 @@ void afq_gpl_limits(uint32_t out[4]);
 void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity);
 
 /*
+ * Multi-barcode `generate-permit-list`, the device half (do_generate_permit_list_multi_bc, src/cellfilter.rs:789-1381 of the
+ * reference): the (routing entry, cell barcode) histogram of an UNCOLLATED two-barcode RNA RAD.
+ *
+ * `bytes` / `chunk_off` / bytes_on_device / expected_ori and the compatibility rule are afq_gpl_hist_rad's; a record is `na u32,
+ * b0 (b0_bytes), b1 (b1_bytes), umi (umi_bytes), na x (u32 ref | orientation bit 31, + the position bytes of
+ * afq_set_aln_extra_bytes)`; b0_bytes and b1_bytes are 1, 2 or 4, umi_bytes 1, 2, 4 or 8.  sample_observed[n_entries] are the
+ * routing entries: packed sample barcodes, ascending and distinct (else AFQ_ERR_INVALID_ARG), each fitting b0_bytes (else
+ * AFQ_ERR_BAD_INPUT); n_entries == 0 is legal (every record is then unrouted), more than 2^31 is AFQ_ERR_UNSUPPORTED.
+ *
+ * Every compatible record looks its b0 up among the entries: a hit at index e counts the pair (e, b1), a miss adds to n_unrouted.
+ * What an entry means - an exact source, a corrected neighbour, an alias, a barcode whose decision is deferred - is the host's.
+ *
+ * Out (malloc'd; afq_free): the distinct pairs, ascending by (entry, cell), with their u64 counts, and `stats`.  All counts are
+ * integer sums and the host sorts: the output is a function of the input alone, run to run.  The entry table is afq_atac_sort_rad's
+ * correction table, so afq_atac_sort_table_slot(b0, n_entries, ..) describes it; the counting table is afq_gpl_hist_rad's over the
+ * keys entry << 32 | b1, so afq_gpl_table_slot(key, n_routed, 8, ..) describes it.  One call is one fill of the device: a host with
+ * a larger file calls once per part with the same entries, merges the sorted outputs and sums the stats.
+ * Errors: AFQ_ERR_BAD_INPUT "chunk <i>: ..." for a chunk outside the buffer, a head or an alignment list that runs past its chunk,
+ * records that do not tile nbytes or do not number nrec (nothing outside `bytes` is read, no partial histogram is returned, the
+ * context stays usable); AFQ_ERR_UNSUPPORTED for 2^30 records or more in one call; AFQ_ERR_OOM (with the sizes) when input and
+ * tables do not fit the device.
+ */
+typedef struct afq_gpl_multi_hist_stats {
+    uint64_t n_records;      /* records of the chunks                                                            */
+    uint64_t n_compatible;   /* ... compatible with expected_ori (= n_routed + n_unrouted)                       */
+    uint64_t n_routed;       /* ... whose b0 is a routing entry (= the sum of the counts)                        */
+    uint64_t n_unrouted;     /* ... whose b0 is none                                                             */
+    uint64_t n_long_records; /* records whose alignment words the whole wave tested out of global memory: more than
+                                afq_gpl_multi_limits()[2] alignments, under fw / rc                              */
+} afq_gpl_multi_hist_stats;
+int afq_gpl_multi_hist_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes,
+                           uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed,
+                           uint64_t n_entries, uint64_t* out_n, uint32_t** out_entry, uint64_t** out_cell, uint64_t** out_count,
+                           afq_gpl_multi_hist_stats* stats);
+/* out[0] = bytes of a chunk the multi-barcode GPL parse stages per trip, out[1] = bytes staged behind them (they hold the widest
+ * head, 4 + 4 + 4 + 8, and out[2] of the widest alignments), out[2] = a record with more alignments than this is a long record
+ * (all three are afq_gpl_limits'), out[3] = 0.  For tests. */
+void afq_gpl_multi_limits(uint32_t out[4]);
+
+/*
  * `atac generate-permit-list`, the device half (update_barcode_hist_unfiltered, src/atac/cellfilter.rs:68-103 of the reference): one
  * walk of an UNCOLLATED scATAC RAD for the barcode histogram, the largest na and the position-bin histogram.
  *

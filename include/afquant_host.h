@@ -212,6 +212,57 @@ void afq_atac_gpl_bin_lens(const uint32_t* ref_lens, size_t n, uint64_t bin_size
 /* needletail's reverse_complement of a packed k-mer (k = 1..32).  For the CPU tests. */
 uint64_t afq_gpl_reverse_complement(uint64_t barcode, uint32_t k);
 
+/* The options of `alevin-fry generate-permit-list` on a multi-barcode (10x Flex) RAD file (do_generate_permit_list_multi_bc,
+ * src/cellfilter.rs:789-1381; GenPermitListOpts, src/prog_opts.rs:86-184).  The cell-side fields are afq_gpl_opts'; the cell
+ * neighbourhood's default (-1) is hamming-1 here (resolved_cell_neighborhood(true)). */
+enum { AFQ_GPL_SAMPLE_EXACT = 0, AFQ_GPL_SAMPLE_UNIQUE = 1, AFQ_GPL_SAMPLE_FREQUENCY = 2, AFQ_GPL_SAMPLE_ONE_EDIT = 3 };
+struct afq_gpl_multi_hist_stats;
+typedef struct afq_gpl_multi_opts {
+    const char* input_dir;      /* -i : directory holding the mapper's map.rad                                             */
+    const char* output_dir;     /* -o                                                                                      */
+    uint32_t expected_ori;      /* -d : 0 both / either, 1 fw, 2 rc                                                        */
+    uint32_t method;            /* AFQ_GPL_*: -k, -e N, -f N, -b FILE, -u FILE                                             */
+    uint64_t method_count;      /* N of -e / -f                                                                            */
+    const char* list_file;      /* FILE of -b / -u (with -u: the cell-barcode whitelist that splits every sample's histogram) */
+    uint64_t min_reads;         /* -m (with -u; at least 1)                                                                */
+    uint32_t frequency;         /* --cell-bc-correction frequency (else unique)                                            */
+    int32_t neighborhood;       /* --cell-bc-neighborhood: -1 = hamming-1, 0 hamming-1, 1 substitution-or-shift-1          */
+    uint64_t conf_num, conf_den;/* --cell-bc-confidence; 0/0 = 39/40                                                       */
+    uint32_t num_threads;       /* -t : the device reads the records                                                       */
+    uint32_t device;
+    const char* cmdline;        /* recorded in generate_permit_list.json                                                   */
+    uint64_t fill_bytes;        /* chunk bytes per device fill (0 = 8 GiB); the sorted outputs of several fills are merged */
+    const char* sample_bc_list; /* --sample-bc-list (required): one, two or three tab-separated columns                    */
+    uint32_t sample_correction; /* --sample-bc-correction: AFQ_GPL_SAMPLE_*; ONE_EDIT is the deprecated `1-edit`: unique
+                                   over substitution-or-shift-1, whatever sample_neighborhood says (prog_opts.rs:161-184)  */
+    uint32_t sample_neighborhood;        /* --sample-bc-neighborhood: 0 hamming-1 (the default), 1 substitution-or-shift-1 */
+    uint64_t sample_conf_num, sample_conf_den;   /* --sample-bc-confidence; 0/0 = 39/40                                    */
+    uint32_t sample_bc_ori;     /* --sample-bc-ori: 0 forward, 1 reverse (both columns are reverse-complemented)           */
+    struct afq_gpl_multi_hist_stats* stats_out;   /* optional: the record pass's stats, summed over the fills               */
+} afq_gpl_multi_opts;
+/* Runs the whole step: sample_permit_map.bin, sample_<name>/permit_map.bin and sample_<name>/permit_freq.bin (none for a sample
+ * without a read: it gets its directory and its sample_info entry), correction_plan.bin with a sample scope and one cell scope per
+ * sample, sample_info.json (the reference's keys; the three *_seconds keys and correction_plan_bytes hold what was measured here,
+ * the four spill_* keys are 0: there is no spool) and generate_permit_list.json in output_dir, every map in ascending key order.
+ * The record pass runs fill by fill on the device (afq_gpl_multi_hist_rad) over the routing entries - the exact sources, the
+ * structurally unique neighbours and, under frequency, the structurally ambiguous barcodes, whose pairs the host replays once the
+ * exact counts are known; the cell correction of every sample is afq_gpl_correct's.  Returns total_cells (the sum of the samples'
+ * permitted cells) or a negative AFQ_ERR_* code.  A single-barcode or scATAC prelude, more than two barcode levels and alignment
+ * positions are AFQ_ERR_UNSUPPORTED, named in the message.  This is the library entry point: `afquant generate-permit-list
+ * --sample-*` is still refused by the CLI, and afq_generate_permit_list still refuses a multi-barcode prelude. */
+int64_t afq_generate_permit_list_multi(const afq_gpl_multi_opts* opts);
+/* ---- multi-barcode generate-permit-list pieces for the CPU tests (no GPU needed) ---- */
+/* load_sample_barcode_list (cellfilter.rs:1405-1569) of a file's text, then build_sample_permit_map (1581-1666) under
+ * sample_correction / sample_neighborhood: the routing entries the device call gets.  Returns their number or a negative error (the
+ * reference's sentence in afq_host_last_error()).  Out, each optional and holding `cap` elements: entry[i] ascending, target[i] (the
+ * canonical barcode; 0 for a deferred entry), kind[i] (0 exact source, 1 structurally unique neighbour, 2 deferred: structurally
+ * ambiguous under frequency).  *barcode_len and *n_samples receive the list's barcode length and its number of canonical samples. */
+int64_t afq_gpl_multi_routing(const uint8_t* text, size_t n, int reverse, uint32_t sample_correction, uint32_t sample_neighborhood, uint64_t* entry,
+                              uint64_t* target, uint8_t* kind, size_t cap, uint32_t* barcode_len, uint32_t* n_samples);
+/* The argument checks of afq_gpl_multi_hist_rad that precede device work: widths, expected_ori, entries ascending and distinct
+ * (AFQ_ERR_INVALID_ARG), fitting b0_bytes (AFQ_ERR_BAD_INPUT), at most 2^31 of them (AFQ_ERR_UNSUPPORTED).  0 when they pass. */
+int afq_gpl_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed, uint64_t n_entries);
+
 /* Runs the whole `quant` sub-command.  Returns 0 or a negative AFQ_ERR_* code; message via afq_host_last_error(). */
 int afq_quantify(const afq_quant_opts* opts);
 const char* afq_host_last_error(void);
