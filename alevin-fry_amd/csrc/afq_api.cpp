@@ -1815,6 +1815,53 @@ static int fetch_chunk_headers(afq_ctx* c, const uint8_t* bytes, size_t n_bytes,
     return 0;
 }
 
+// The chunk table of a record pass (the *_rad entry points over an uncollated RAD): every header fetched and checked - `min_rec`
+// is the bytes of a record without alignments -, each chunk with the slot of its first record; n_slots: the records of the call.
+static int build_sort_chunks(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, bool on_device, uint32_t min_rec,
+                             std::vector<SortChunk>& out, uint64_t& n_slots) {
+    std::vector<uint32_t> hdr(2ull * n_chunks);
+    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, on_device, hdr.data(), "chunk")) return rc;
+    std::vector<SortChunk> chunks(n_chunks);
+    n_slots = 0;
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
+        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, min_rec)) return chunk_fault(c, "chunk", i, f);
+        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
+        n_slots += nr;
+    }
+    out.swap(chunks);
+    return 0;
+}
+
+// Host bytes of a record pass to the device (c->d_bytes_own, through staged_h2d); bytes that are there already stay where they
+// are.  *d_bytes: where the kernels read them.  Called behind the entry point's own `ensure`s and before its copies of tables.
+static int stage_rad_bytes(afq_ctx* c, HipLatch& T, const std::function<int()>& hip_fail, const uint8_t* bytes, size_t n_bytes, bool on_device, hipStream_t s,
+                           const uint8_t** d_bytes) {
+    *d_bytes = bytes;
+    if (on_device) return 0;
+    T(c->d_bytes_own.ensure(n_bytes + 16));
+    if (!T.ok()) return hip_fail();
+    if (n_bytes)
+        if (int rc = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1))) return rc;
+    *d_bytes = c->d_bytes_own.as<uint8_t>();
+    return 0;
+}
+
+// A non-zero status word of a record pass's table + parse / measure kernels as the entry point's refusal.  `start_range`: what
+// the caller says of kErrStartRange behind "chunk k: " (`atac sort` and `atac generate-permit-list` mean different things by it);
+// null where the kernels never raise it.
+static int rad_status_fault(afq_ctx* c, const char* who, const DevStatus& st, const char* start_range = nullptr) {
+    harvest_timers(c);
+    const std::string at = std::to_string(st.err_cell);
+    if (st.err_code == kErrStartRange && start_range) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": " + start_range);
+    switch (st.err_code) {
+        case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + at + ": an observed barcode with two different corrected barcodes");
+        case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": the records do not tile the chunk (nbytes / nrec do not match them)");
+        case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": a reference id is not below ref_count");
+        default: return fail(c, AFQ_ERR_HIP, std::string(who) + ": device status " + std::to_string(st.err_code));
+    }
+}
+
 static int submit_host(afq_ctx* c, const ByteSource& src, size_t n_bytes, const uint64_t* chunk_off, const uint32_t* chunk_hdr,
                        uint32_t n_cells, uint64_t first_cell_index) {
     const uint8_t* bytes = src.bytes;
@@ -2563,16 +2610,9 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     bin_base[ref_count] = (uint32_t)n_bins64;
     const uint32_t n_bins = (uint32_t)n_bins64;
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + ")");
     const uint64_t cap = sort_table_capacity(n_corr);
     const uint32_t tab_mask = (uint32_t)(cap - 1);
@@ -2598,13 +2638,8 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     T(B.rbc.ensure(8 * std::max<uint64_t>(uniq.size(), 1))); T(B.bin.ensure(4 * s1)); T(B.key0.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1));
     T(B.status.ensure(sizeof(DevStatus))); T(B.hist.ensure(4ull * nb1)); T(B.cur.ensure(4ull * nb1)); T(B.segs.ensure(sizeof(SortSeg))); T(B.tally.ensure(8));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.rank.p, rank.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
     if (ref_count) T(hipMemcpyAsync(B.rinfo.p, ref_info.data(), 8ull * ref_count, hipMemcpyHostToDevice, s));
@@ -2636,17 +2671,7 @@ int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const ui
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("atac sort: table + parse");
     if (!T.ok()) return hip_fail();
-    if (st.err_code) {
-        harvest_timers(c);
-        const std::string who = std::to_string(st.err_cell);
-        switch (st.err_code) {
-            case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + who + ": an observed barcode with two different corrected barcodes");
-            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-            case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a reference id is not below ref_count");
-            case kErrStartRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a start position is not below its reference's length");
-            default: return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: device status " + std::to_string(st.err_code));
-        }
-    }
+    if (st.err_code) return rad_status_fault(c, "afq_atac_sort_rad", st, "a start position is not below its reference's length");
     afq_atac_sort_stats S{};
     S.n_records = n_slots;
     for (uint32_t i = 0; i < n_chunks; ++i) { S.n_unmapped += cstat[4 * i]; S.n_multimapped += cstat[4 * i + 1]; S.n_uncorrected += cstat[4 * i + 2]; S.n_kept += cstat[4 * i + 3]; }
@@ -2855,6 +2880,29 @@ static int gpl_count_sorted(afq_ctx* c, const char* who, uint32_t n_chunks, uint
     return 0;
 }
 
+// The pairs of gpl_count_sorted count every record the parse put into the barcode column: `expect` of them, which the entry
+// point calls `what`.
+static int gpl_check_total(afq_ctx* c, const char* who, const std::vector<std::pair<uint64_t, uint64_t>>& pairs, uint64_t expect, const char* what) {
+    uint64_t total = 0;
+    for (const auto& pr : pairs) total += pr.second;
+    if (total == expect) return 0;
+    return fail(c, AFQ_ERR_HIP, std::string(who) + ": the table counts " + std::to_string(total) + " of " + std::to_string(expect) + " " + what);
+}
+
+// The pairs as the histogram a single-barcode pass hands over: barcodes and counts in blocks of H; with `obins`, a block for n_bins
+// position bins beside them (`atac generate-permit-list`'s, which fills it).
+static int gpl_hist_out(afq_ctx* c, const char* who, const std::vector<std::pair<uint64_t, uint64_t>>& pairs, HostOuts& H, uint64_t** obc, uint64_t** ocnt,
+                        uint64_t n_bins = 0, uint64_t** obins = nullptr) {
+    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    *obc = (uint64_t*)H.mallocd(8 * o1);
+    *ocnt = (uint64_t*)H.mallocd(8 * o1);
+    if (obins) *obins = n_bins ? (uint64_t*)H.mallocd(8ull * n_bins) : nullptr;
+    if (!*obc || !*ocnt || (n_bins && !*obins))
+        return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(16 * o1 + 8ull * n_bins) + " bytes of histogram" + (obins ? " and bins)" : ")"));
+    for (uint64_t i = 0; i < n_out; ++i) { (*obc)[i] = pairs[i].first; (*ocnt)[i] = pairs[i].second; }
+    return 0;
+}
+
 // `generate-permit-list` on the device (afq_gpl.hip): parse + orientation filter, counting table, compaction; the host sorts the
 // distinct barcodes.  And the correction decisions of distinct observed barcodes against a retained set.
 void afq_gpl_limits(uint32_t out[4]) {
@@ -2881,16 +2929,9 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     HostClock hc;
     hipStream_t s = c->stream;
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes + umi_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes + umi_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 30))
         return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
     const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1);
@@ -2910,13 +2951,8 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
     T(B.ones.ensure(8)); T(B.nout.ensure(4));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
     T(hipMemsetAsync(B.ones.p, 0, 8, s));
@@ -2936,12 +2972,7 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("gpl: parse");
     if (!T.ok()) return hip_fail();
-    if (st.err_code) {
-        harvest_timers(c);
-        if (st.err_code == kErrRecordWalk)
-            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(st.err_cell) + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-        return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: device status " + std::to_string(st.err_code));
-    }
+    if (st.err_code) return rad_status_fault(c, "afq_gpl_hist_rad", st);
     afq_gpl_hist_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         S.n_records += cstat[4 * i]; S.n_compatible += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_long_records += cstat[4 * i + 3];
@@ -2950,19 +2981,13 @@ int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uin
     std::vector<std::pair<uint64_t, uint64_t>> pairs;
     if (int rc = gpl_count_sorted(c, "afq_gpl_hist_rad", n_chunks, S.n_compatible, bc_bytes, T, hip_fail, pairs)) return rc;
     hc.lap("gpl: count + compact + sort");
-    uint64_t total = 0;
-    for (const auto& pr : pairs) total += pr.second;
-    if (total != S.n_compatible)
-        return fail(c, AFQ_ERR_HIP, "afq_gpl_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_compatible) + " compatible records");
-    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    if (int rc = gpl_check_total(c, "afq_gpl_hist_rad", pairs, S.n_compatible, "compatible records")) return rc;
     HostOuts H;
-    uint64_t* obc = (uint64_t*)H.mallocd(8 * o1);
-    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
-    if (!obc || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_gpl_hist_rad: host allocation failed (" + std::to_string(16 * o1) + " bytes of histogram)");
-    for (uint64_t i = 0; i < n_out; ++i) { obc[i] = pairs[i].first; ocnt[i] = pairs[i].second; }
+    uint64_t *obc = nullptr, *ocnt = nullptr;
+    if (int rc = gpl_hist_out(c, "afq_gpl_hist_rad", pairs, H, &obc, &ocnt)) return rc;
     if (stats) *stats = S;
     H.release();
-    *out_n = n_out; *out_bc = obc; *out_count = ocnt;
+    *out_n = pairs.size(); *out_bc = obc; *out_count = ocnt;
     return 0;
 }
 
@@ -2989,16 +3014,9 @@ int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, con
     HostClock hc;
     hipStream_t s = c->stream;
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + b0_bytes + b1_bytes + umi_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + b0_bytes + b1_bytes + umi_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 30))
         return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_multi_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
     const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ne1 = std::max<uint64_t>(n_entries, 1), ecap = sort_table_capacity(n_entries);
@@ -3021,13 +3039,8 @@ int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, con
     T(B.ones.ensure(8)); T(B.nout.ensure(4));
     T(B.obs.ensure(8 * ne1)); T(B.idx.ensure(4 * ne1)); T(B.rkey.ensure(8 * ecap)); T(B.rval.ensure(4 * ecap)); T(B.cstatus.ensure(sizeof(DevStatus)));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     std::vector<uint32_t> idx(n_entries);
     for (uint64_t i = 0; i < n_entries; ++i) idx[i] = (uint32_t)i;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
@@ -3062,12 +3075,7 @@ int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, con
     hc.lap("gpl multi: table + parse");
     if (!T.ok()) return hip_fail();
     if (tst.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: entry table status " + std::to_string(tst.err_code) + " at entry " + std::to_string(tst.err_cell)); }
-    if (st.err_code) {
-        harvest_timers(c);
-        if (st.err_code == kErrRecordWalk)
-            return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(st.err_cell) + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-        return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: device status " + std::to_string(st.err_code));
-    }
+    if (st.err_code) return rad_status_fault(c, "afq_gpl_multi_hist_rad", st);
     afq_gpl_multi_hist_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         S.n_records += cstat[4 * i]; S.n_routed += cstat[4 * i + 1]; S.n_unrouted += cstat[4 * i + 2]; S.n_long_records += cstat[4 * i + 3];
@@ -3077,10 +3085,7 @@ int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, con
     std::vector<std::pair<uint64_t, uint64_t>> pairs;
     if (int rc = gpl_count_sorted(c, "afq_gpl_multi_hist_rad", n_chunks, S.n_routed, 8, T, hip_fail, pairs)) return rc;
     hc.lap("gpl multi: count + compact + sort");
-    uint64_t total = 0;
-    for (const auto& pr : pairs) total += pr.second;
-    if (total != S.n_routed)
-        return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_routed) + " routed records");
+    if (int rc = gpl_check_total(c, "afq_gpl_multi_hist_rad", pairs, S.n_routed, "routed records")) return rc;
     const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
     HostOuts H;
     uint32_t* oent = (uint32_t*)H.mallocd(4 * o1);
@@ -3120,16 +3125,9 @@ int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     std::vector<uint32_t> bbase(std::max<uint32_t>(ref_count, 1), 0);
     for (uint32_t r = 0; r < ref_count; ++r) bbase[r] = (uint32_t)bin_base[r];
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 30))
         return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
     const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);
@@ -3149,13 +3147,8 @@ int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
     T(B.ones.ensure(8)); T(B.nout.ensure(4)); T(B.bbase.ensure(4ull * bbase.size())); T(B.bins.ensure(4ull * nb1)); T(B.bins64.ensure(8ull * nb1)); T(B.bmax.ensure(4));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     T(hipMemcpyAsync(B.bbase.p, bbase.data(), 4ull * bbase.size(), hipMemcpyHostToDevice, s));
     T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
@@ -3184,16 +3177,8 @@ int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("atac gpl: parse + bins");
     if (!T.ok()) return hip_fail();
-    if (st.err_code) {
-        harvest_timers(c);
-        const std::string who = std::to_string(st.err_cell);
-        switch (st.err_code) {
-            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-            case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a reference id is not below ref_count");
-            case kErrStartRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": a start position's bin is not below the number of bins (" + std::to_string(n_bins) + ")");
-            default: return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: device status " + std::to_string(st.err_code));
-        }
-    }
+    if (st.err_code)
+        return rad_status_fault(c, "afq_atac_gpl_hist_rad", st, ("a start position's bin is not below the number of bins (" + std::to_string(n_bins) + ")").c_str());
     afq_atac_gpl_hist_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         S.n_unmapped += cstat[4 * i]; S.n_records += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_multimapped += cstat[4 * i + 3];
@@ -3206,18 +3191,10 @@ int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     std::vector<std::pair<uint64_t, uint64_t>> pairs;
     if (int rc = gpl_count_sorted(c, "afq_atac_gpl_hist_rad", n_chunks, S.n_records, bc_bytes, T, hip_fail, pairs)) return rc;
     hc.lap("atac gpl: count + compact + sort");
-    uint64_t total = 0;
-    for (const auto& pr : pairs) total += pr.second;
-    if (total != S.n_records)
-        return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: the table counts " + std::to_string(total) + " of " + std::to_string(S.n_records) + " records");
-    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
+    if (int rc = gpl_check_total(c, "afq_atac_gpl_hist_rad", pairs, S.n_records, "records")) return rc;
     HostOuts H;
-    uint64_t* obc = (uint64_t*)H.mallocd(8 * o1);
-    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
-    uint64_t* obins = n_bins ? (uint64_t*)H.mallocd(8ull * n_bins) : nullptr;
-    if (!obc || !ocnt || (n_bins && !obins))
-        return fail(c, AFQ_ERR_OOM, "afq_atac_gpl_hist_rad: host allocation failed (" + std::to_string(16 * o1 + 8ull * n_bins) + " bytes of histogram and bins)");
-    for (uint64_t i = 0; i < n_out; ++i) { obc[i] = pairs[i].first; ocnt[i] = pairs[i].second; }
+    uint64_t *obc = nullptr, *ocnt = nullptr, *obins = nullptr;
+    if (int rc = gpl_hist_out(c, "afq_atac_gpl_hist_rad", pairs, H, &obc, &ocnt, n_bins, &obins)) return rc;
     if (n_bins) {
         T(hipMemcpyAsync(obins, B.bins64.p, 8ull * n_bins, hipMemcpyDeviceToHost, s));
         T(hipStreamSynchronize(s));
@@ -3225,7 +3202,7 @@ int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     }
     if (stats) *stats = S;
     H.release();
-    *out_n = n_out; *out_bc = obc; *out_count = ocnt; *out_bins = obins;
+    *out_n = pairs.size(); *out_bc = obc; *out_count = ocnt; *out_bins = obins;
     return 0;
 }
 
@@ -3325,6 +3302,42 @@ int afq_gpl_correct(afq_ctx* c, const uint64_t* observed, const uint64_t* obs_co
     return 0;
 }
 
+// Both collates' host step: val[i] = the index in `cells` of corrected[i]; ones_cell = the cell of the all-ones observed barcode
+// (it cannot be a key of the device's table, whose free slots are all ones), kSortNoRank without one.
+static int collate_cell_index(afq_ctx* c, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint64_t* cells, uint32_t n_cells,
+                              std::vector<uint32_t>& val, uint32_t& ones_cell) {
+    val.assign(n_corr, 0);
+    ones_cell = kSortNoRank;
+    std::vector<std::pair<uint64_t, uint32_t>> by_bc(n_cells);
+    for (uint32_t i = 0; i < n_cells; ++i) by_bc[i] = {cells[i], i};
+    std::sort(by_bc.begin(), by_bc.end());
+    for (uint32_t i = 1; i < n_cells; ++i)
+        if (by_bc[i].first == by_bc[i - 1].first)
+            return fail(c, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by_bc[i - 1].second) + " and " + std::to_string(by_bc[i].second) + " carry one barcode (" +
+                        std::to_string(by_bc[i].first) + ")");
+    for (uint64_t i = 0; i < n_corr; ++i) {
+        const auto it = std::lower_bound(by_bc.begin(), by_bc.end(), std::make_pair(corrected[i], 0u));
+        if (it == by_bc.end() || it->first != corrected[i])
+            return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(observed[i]) + " is corrected to " +
+                        std::to_string(corrected[i]) + ", which is not a cell");
+        val[i] = it->second;
+        if (observed[i] == kSortEmptyKey) {
+            if (ones_cell != kSortNoRank && ones_cell != val[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
+            ones_cell = val[i];
+        }
+    }
+    return 0;
+}
+
+// Both collates' placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies.
+// The sorted words end in `src`; `dst` is the buffer the last pass read, free again.
+static void collate_radix_place(hipStream_t s, uint64_t*& src, uint64_t*& dst, uint32_t n, uint32_t n_cells, uint32_t* hist) {
+    for (uint32_t shift = 32; shift < 64 && (n_cells >> (shift - 32)) != 0; shift += 8) {
+        launch_collate_radix_pass(s, src, dst, n, shift, hist);
+        std::swap(src, dst);
+    }
+}
+
 // `collate` on the device (afq_collate.hip): correction table, measure walk, radix placement, length scan, chunk heads, write walk.
 void afq_collate_limits(uint32_t out[4]) {
     if (!out) return;
@@ -3349,39 +3362,13 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     HostClock hc;
     hipStream_t s = c->stream;
     // ---- host: corrected barcode -> its index in `cells`; the all-ones key
-    std::vector<uint32_t> val(n_corr);
+    std::vector<uint32_t> val;
     uint32_t ones_cell = kSortNoRank;
-    {
-        std::vector<std::pair<uint64_t, uint32_t>> by_bc(n_cells);
-        for (uint32_t i = 0; i < n_cells; ++i) by_bc[i] = {cells[i], i};
-        std::sort(by_bc.begin(), by_bc.end());
-        for (uint32_t i = 1; i < n_cells; ++i)
-            if (by_bc[i].first == by_bc[i - 1].first)
-                return fail(c, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by_bc[i - 1].second) + " and " + std::to_string(by_bc[i].second) + " carry one barcode (" +
-                            std::to_string(by_bc[i].first) + ")");
-        for (uint64_t i = 0; i < n_corr; ++i) {
-            const auto it = std::lower_bound(by_bc.begin(), by_bc.end(), std::make_pair(corrected[i], 0u));
-            if (it == by_bc.end() || it->first != corrected[i])
-                return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(observed[i]) + " is corrected to " +
-                            std::to_string(corrected[i]) + ", which is not a cell");
-            val[i] = it->second;
-            if (observed[i] == kSortEmptyKey) {
-                if (ones_cell != kSortNoRank && ones_cell != val[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
-                ones_cell = val[i];
-            }
-        }
-    }
+    if (int rc = collate_cell_index(c, observed, corrected, n_corr, cells, n_cells, val, ones_cell)) return rc;
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes + umi_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes + umi_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
     const uint32_t n = (uint32_t)n_slots;
     const uint64_t cap = sort_table_capacity(n_corr);
@@ -3409,13 +3396,8 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
     T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
     if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
@@ -3443,15 +3425,7 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("collate: table + measure");
     if (!T.ok()) return hip_fail();
-    if (st.err_code) {
-        harvest_timers(c);
-        const std::string who = std::to_string(st.err_cell);
-        switch (st.err_code) {
-            case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + who + ": an observed barcode with two different corrected barcodes");
-            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-            default: return fail(c, AFQ_ERR_HIP, "afq_collate_rad: device status " + std::to_string(st.err_code));
-        }
-    }
+    if (st.err_code) return rad_status_fault(c, "afq_collate_rad", st);
     afq_collate_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const uint32_t* q = cstat.data() + 8ull * i;
@@ -3462,10 +3436,7 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     uint64_t* dst = B.kb.as<uint64_t>();
     {
         ScopedTimer t(c, K_COLLATE_SORT, s);
-        for (uint32_t shift = 32; shift < 64 && (n_cells >> (shift - 32)) != 0; shift += 8) {
-            launch_collate_radix_pass(s, src, dst, n, shift, B.hist.as<uint32_t>());
-            std::swap(src, dst);
-        }
+        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
     }
     uint64_t kept_bytes = 0;
     {
@@ -3539,39 +3510,13 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     HostClock hc;
     hipStream_t s = c->stream;
     // ---- host: corrected barcode -> its index in `cells`; the all-ones key
-    std::vector<uint32_t> val(n_corr);
+    std::vector<uint32_t> val;
     uint32_t ones_cell = kSortNoRank;
-    {
-        std::vector<std::pair<uint64_t, uint32_t>> by_bc(n_cells);
-        for (uint32_t i = 0; i < n_cells; ++i) by_bc[i] = {cells[i], i};
-        std::sort(by_bc.begin(), by_bc.end());
-        for (uint32_t i = 1; i < n_cells; ++i)
-            if (by_bc[i].first == by_bc[i - 1].first)
-                return fail(c, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by_bc[i - 1].second) + " and " + std::to_string(by_bc[i].second) + " carry one barcode (" +
-                            std::to_string(by_bc[i].first) + ")");
-        for (uint64_t i = 0; i < n_corr; ++i) {
-            const auto it = std::lower_bound(by_bc.begin(), by_bc.end(), std::make_pair(corrected[i], 0u));
-            if (it == by_bc.end() || it->first != corrected[i])
-                return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(observed[i]) + " is corrected to " +
-                            std::to_string(corrected[i]) + ", which is not a cell");
-            val[i] = it->second;
-            if (observed[i] == kSortEmptyKey) {
-                if (ones_cell != kSortNoRank && ones_cell != val[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
-                ones_cell = val[i];
-            }
-        }
-    }
+    if (int rc = collate_cell_index(c, observed, corrected, n_corr, cells, n_cells, val, ones_cell)) return rc;
     // ---- chunk table
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
+    std::vector<SortChunk> chunks;
     uint64_t n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
     if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
     const uint32_t n = (uint32_t)n_slots;
     const uint64_t cap = sort_table_capacity(n_corr);
@@ -3600,13 +3545,8 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     T(B.cells.ensure(8 * ncell1)); T(B.cellof.ensure(4 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks));
     T(B.first.ensure(4 * ncell1)); T(B.rank.ensure(4 * ncell1)); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
     if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = bytes;
-    if (!bytes_on_device) {
-        T(c->d_bytes_own.ensure(n_bytes + 16));
-        if (!T.ok()) return hip_fail();
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
     if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
     if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
@@ -3632,15 +3572,7 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
     hc.lap("atac collate: table + measure");
     if (!T.ok()) return hip_fail();
-    if (st.err_code) {
-        harvest_timers(c);
-        const std::string who = std::to_string(st.err_cell);
-        switch (st.err_code) {
-            case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + who + ": an observed barcode with two different corrected barcodes");
-            case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + who + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-            default: return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: device status " + std::to_string(st.err_code));
-        }
-    }
+    if (st.err_code) return rad_status_fault(c, "afq_atac_collate_rad", st);
     afq_atac_collate_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const uint32_t* q = cstat.data() + 8ull * i;
@@ -3652,10 +3584,7 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     uint64_t* dst = B.kb.as<uint64_t>();
     {
         ScopedTimer t(c, K_ACOLLATE_PLACE, s);
-        for (uint32_t shift = 32; shift < 64 && (n_cells >> (shift - 32)) != 0; shift += 8) {
-            launch_collate_radix_pass(s, src, dst, n, shift, B.hist.as<uint32_t>());
-            std::swap(src, dst);
-        }
+        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
         launch_atac_collate_runs(s, src, n, n_cells, B.first.as<uint32_t>(), B.rank.as<uint32_t>());
         launch_collate_excl_scan_u32(s, B.rank.as<uint32_t>(), ncell1);
     }

@@ -57,13 +57,20 @@ inline int confidence_new(uint64_t num, uint64_t den, uint64_t* onum, uint64_t* 
     return 0;
 }
 inline uint64_t gpl_base_mask(unsigned n) { return n >= 32 ? ~0ull : (1ull << (2 * n)) - 1ull; }
-// for_each_neighbor (barcode_correction.rs:738-782): what a retained source generates
-inline void gpl_push_neighbors(uint64_t bc, uint32_t L, bool shift, std::vector<uint64_t>& out) {
+inline int gpl_base_code(uint8_t ch) {   // A C G T = 0 1 2 3 in either case; -1: no base
+    switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return -1; }
+}
+// the 3 L barcodes one substitution away from bc
+inline void gpl_push_substitutions(uint64_t bc, uint32_t L, std::vector<uint64_t>& out) {
     for (uint32_t pos = 0; pos < L; ++pos) {
         const uint32_t sh = 2 * pos;
         const uint64_t base = (bc >> sh) & 3, cleared = bc & ~(3ull << sh);
         for (uint64_t rep = 0; rep < 4; ++rep) if (rep != base) out.push_back(cleared | (rep << sh));
     }
+}
+// for_each_neighbor (barcode_correction.rs:738-782): what a retained source generates
+inline void gpl_push_neighbors(uint64_t bc, uint32_t L, bool shift, std::vector<uint64_t>& out) {
+    gpl_push_substitutions(bc, L, out);
     if (!shift) return;
     for (uint32_t b = 1; b < L; ++b) {
         const uint64_t lower_mask = (1ull << (2 * b)) - 1, upper = bc & ~lower_mask, lower = bc & lower_mask;
@@ -134,7 +141,6 @@ inline int parse_confidence(const char* text, uint64_t* num, uint64_t* den, std:
 inline int64_t parse_barcode_list(const uint8_t* text, size_t n, int unfiltered, uint32_t barcode_len, uint64_t* out, size_t cap, uint32_t* first_len, std::string& err) {
     if (!text && n) return gfail(err, AFQ_ERR_INVALID_ARG, "null argument");
     if (!unfiltered && (barcode_len < 1 || barcode_len > 32)) return gfail(err, AFQ_ERR_INVALID_ARG, "barcode length must be between 1 and 32");
-    auto code = [](uint8_t ch) -> int { switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return -1; } };
     uint64_t cnt = 0;
     size_t first = 0;
     bool have_first = false;
@@ -155,7 +161,7 @@ inline int64_t parse_barcode_list(const uint8_t* text, size_t n, int unfiltered,
         if (k >= 1 && k <= 32 && len >= k) {
             uint32_t run = 0;
             for (size_t i = 0; i < len; ++i) {
-                const int c = code(text[p + i]);
+                const int c = gpl_base_code(text[p + i]);
                 if (c < 0) { run = 0; v = 0; continue; }
                 v = ((v << 2) | (uint64_t)c) & gpl_base_mask(k);
                 if (++run >= k) { found = true; break; }
@@ -256,8 +262,10 @@ inline bool write_plan_file(const std::string& path, int sample_len, uint32_t ce
     if (n_bytes) *n_bytes = b.size();
     return std::fwrite(b.data(), 1, b.size(), f.get()) == b.size();
 }
-inline bool write_map_file(const std::string& path, const uint64_t* obs, const uint64_t* cor, uint64_t n) {   // bincode HashMap<u64, u64>
+// bincode HashMap<u64, u64>; *created: the file could be opened (for callers that tell that failure from a failed write)
+inline bool write_map_file(const std::string& path, const uint64_t* obs, const uint64_t* cor, uint64_t n, bool* created = nullptr) {
     GplFile f(std::fopen(path.c_str(), "wb"));
+    if (created) *created = (bool)f;
     if (!f) return false;
     bool ok = std::fwrite(&n, 8, 1, f.get()) == 1;
     for (uint64_t i = 0; i < n && ok; ++i) { const uint64_t kv[2] = {obs[i], cor[i]}; ok = std::fwrite(kv, 8, 2, f.get()) == 2; }
@@ -269,19 +277,33 @@ inline int write_table_files(const std::string& out, const afq_gpl_tables* t, st
     if (gpl_mkdirs(out)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't create directory path " + out);
     if (!write_freq_file(out + "/permit_freq.bin", t->barcode_len, t->freq_bc, t->freq_count, t->n_freq)) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write permit frequencies");
     if (t->all_bc && !write_freq_file(out + "/all_freq.bin", t->barcode_len, t->all_bc, t->all_count, t->n_all)) return gfail(err, AFQ_ERR_BAD_INPUT, "could not write all_freq.bin");
-    {
-        GplFile f(std::fopen((out + "/permit_map.bin").c_str(), "wb"));
-        if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create serialization file.");
-        bool ok = std::fwrite(&t->n_map, 8, 1, f.get()) == 1;
-        for (uint64_t i = 0; i < t->n_map && ok; ++i) { const uint64_t kv[2] = {t->map_obs[i], t->map_cor[i]}; ok = std::fwrite(kv, 8, 2, f.get()) == 2; }
-        if (!ok) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize permit list.");
-    }
+    bool created = false;
+    if (!write_map_file(out + "/permit_map.bin", t->map_obs, t->map_cor, t->n_map, &created))
+        return gfail(err, AFQ_ERR_BAD_INPUT, created ? "couldn't serialize permit list." : "could not create serialization file.");
     {   // correction_plan.bin: one global cell scope
         const PlanSpec spec{t->barcode_len, t->neighborhood, t->frequency, t->conf_num, t->conf_den, t->pseudocount};
         const std::vector<PlanScope> scopes{PlanScope{false, 0, spec, t->plan_obs, t->plan_cor, t->n_plan}};
         if (!write_plan_file(out + "/correction_plan.bin", -1, t->barcode_len, nullptr, nullptr, nullptr, 0, scopes))
             return gfail(err, AFQ_ERR_BAD_INPUT, "could not write correction plan");
     }
+    return 0;
+}
+
+// What both generate_permit_list.json writers (RNA, ATAC) share: the neighbourhoods' names, the end of the object - the resolved
+// correction settings (neighbourhood, confidence cn / cd) and correction_stats - and the file itself.
+static const char* const kGplNbh[2] = {"hamming-1", "substitution-or-shift-1"};
+inline std::string gpl_json_tail(const afq_gpl_tables* t, uint64_t cn, uint64_t cd) {
+    static const char* const kStat[8] = {"exact_distinct", "exact_reads", "corrected_distinct", "corrected_reads", "ambiguous_distinct", "ambiguous_reads", "not_found_distinct", "not_found_reads"};
+    std::string j = std::string("  \"resolved_cell_bc_neighborhood\": \"") + kGplNbh[t->neighborhood ? 1 : 0] + "\",\n";
+    j += "  \"resolved_cell_bc_confidence\": \"" + std::to_string(cn) + "/" + std::to_string(cd) + "\",\n";
+    j += "  \"correction_stats\": {\n";
+    for (int i = 0; i < 8; ++i) j += std::string("    \"") + kStat[i] + "\": " + std::to_string(t->stats[i]) + (i < 7 ? ",\n" : "\n");
+    return j + "  }\n}";
+}
+inline int write_gpl_json(const std::string& out, const std::string& j, std::string& err) {
+    GplFile f(std::fopen((out + "/generate_permit_list.json").c_str(), "w"));
+    if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+    if (std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
     return 0;
 }
 
@@ -292,8 +314,6 @@ inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::st
     // generate_permit_list.json; gpl_options restates serde's derive of GenPermitListOpts (parity unpinned)
     static const char* const kOriSym[3] = {"both", "fw", "rc"};
     static const char* const kOriEnum[3] = {"Unknown", "Forward", "Reverse"};
-    static const char* const kNbh[2] = {"hamming-1", "substitution-or-shift-1"};
-    static const char* const kStat[8] = {"exact_distinct", "exact_reads", "corrected_distinct", "corrected_reads", "ambiguous_distinct", "ambiguous_reads", "not_found_distinct", "not_found_reads"};
     const uint32_t ori = o->expected_ori <= 2 ? o->expected_ori : 0;
     const uint64_t cn = o->conf_den ? o->conf_num : 39, cd = o->conf_den ? o->conf_den : 40;
     std::string fm;
@@ -318,18 +338,10 @@ inline int write_outputs(const afq_gpl_opts* o, const afq_gpl_tables* t, std::st
     j += "    \"cmdline\": " + gpl_json_str(o->cmdline) + ",\n    \"version\": \"0.18.0\",\n    \"sample_bc_list\": null,\n    \"sample_names\": null,\n";
     j += "    \"sample_correction_mode\": \"exact\",\n    \"sample_bc_ori\": \"Forward\",\n";
     j += std::string("    \"cell_bc_correction\": \"") + (o->frequency ? "frequency" : "unique") + "\",\n";
-    j += std::string("    \"cell_bc_neighborhood\": ") + (o->neighborhood < 0 ? std::string("null") : std::string("\"") + kNbh[o->neighborhood ? 1 : 0] + "\"") + ",\n";
+    j += std::string("    \"cell_bc_neighborhood\": ") + (o->neighborhood < 0 ? std::string("null") : std::string("\"") + kGplNbh[o->neighborhood ? 1 : 0] + "\"") + ",\n";
     j += "    \"sample_bc_neighborhood\": \"hamming-1\",\n    \"cell_bc_confidence\": " + conf + ",\n    \"sample_bc_confidence\": {\n      \"numerator\": 39,\n      \"denominator\": 40\n    },\n";
     j += "    \"memory_limit\": 536870912,\n    \"tmp_dir\": null\n  },\n";
-    j += std::string("  \"resolved_cell_bc_neighborhood\": \"") + kNbh[t->neighborhood ? 1 : 0] + "\",\n";
-    j += "  \"resolved_cell_bc_confidence\": \"" + std::to_string(cn) + "/" + std::to_string(cd) + "\",\n";
-    j += "  \"correction_stats\": {\n";
-    for (int i = 0; i < 8; ++i) j += std::string("    \"") + kStat[i] + "\": " + std::to_string(t->stats[i]) + (i < 7 ? ",\n" : "\n");
-    j += "  }\n}";
-    GplFile f(std::fopen((out + "/generate_permit_list.json").c_str(), "w"));
-    if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create metadata file.");
-    if (std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
-    return 0;
+    return write_gpl_json(out, j + gpl_json_tail(t, cn, cd), err);
 }
 
 // ---- `atac generate-permit-list` (src/atac/cellfilter.rs)
@@ -364,8 +376,6 @@ inline int write_atac_outputs(const afq_atac_gpl_opts* o, const afq_gpl_tables* 
     if (int rc = write_table_files(out, t, err)) return rc;
     if (!write_vec_u64(out + "/bin_recs.bin", bins, n_bins)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize bins recs.");
     if (!write_vec_u64(out + "/bin_lens.bin", bin_lens, n_lens)) return gfail(err, AFQ_ERR_BAD_INPUT, "couldn't serialize bins lengths.");
-    static const char* const kNbh[2] = {"hamming-1", "substitution-or-shift-1"};
-    static const char* const kStat[8] = {"exact_distinct", "exact_reads", "corrected_distinct", "corrected_reads", "ambiguous_distinct", "ambiguous_reads", "not_found_distinct", "not_found_reads"};
     const std::string conf = "{\n      \"numerator\": " + std::to_string(o->conf_num) + ",\n      \"denominator\": " + std::to_string(o->conf_den) + "\n    }";
     std::string j = "{\n";
     j += "  \"version_str\": \"0.18.0\",\n";
@@ -380,18 +390,10 @@ inline int write_atac_outputs(const afq_atac_gpl_opts* o, const afq_gpl_tables* 
     j += std::string("    \"rc\": ") + (o->rc ? "true" : "false") + ",\n";
     j += "    \"cmdline\": " + gpl_json_str(o->cmdline) + ",\n    \"version\": \"0.18.0\",\n";
     j += std::string("    \"cell_bc_correction\": \"") + (o->frequency ? "frequency" : "unique") + "\",\n";
-    j += std::string("    \"cell_bc_neighborhood\": \"") + kNbh[o->neighborhood ? 1 : 0] + "\",\n";
+    j += std::string("    \"cell_bc_neighborhood\": \"") + kGplNbh[o->neighborhood ? 1 : 0] + "\",\n";
     j += "    \"cell_bc_confidence\": " + conf + "\n  },\n";
     j += "  \"max-rec-in-bin\": " + std::to_string(max_bin) + ",\n";
-    j += std::string("  \"resolved_cell_bc_neighborhood\": \"") + kNbh[t->neighborhood ? 1 : 0] + "\",\n";
-    j += "  \"resolved_cell_bc_confidence\": \"" + std::to_string(o->conf_num) + "/" + std::to_string(o->conf_den) + "\",\n";
-    j += "  \"correction_stats\": {\n";
-    for (int i = 0; i < 8; ++i) j += std::string("    \"") + kStat[i] + "\": " + std::to_string(t->stats[i]) + (i < 7 ? ",\n" : "\n");
-    j += "  }\n}";
-    GplFile f(std::fopen((out + "/generate_permit_list.json").c_str(), "w"));
-    if (!f) return gfail(err, AFQ_ERR_BAD_INPUT, "could not create metadata file.");
-    if (std::fwrite(j.data(), 1, j.size(), f.get()) != j.size()) return gfail(err, AFQ_ERR_BAD_INPUT, "cannot write to generate_permit_list.json file");
-    return 0;
+    return write_gpl_json(out, j + gpl_json_tail(t, o->conf_num, o->conf_den), err);
 }
 
 // ---- multi-barcode `generate-permit-list` (do_generate_permit_list_multi_bc, src/cellfilter.rs:789-1381)
@@ -418,12 +420,12 @@ struct SampleList {
     uint32_t barcode_len = 0;
     size_t sample_of(uint64_t canon) const { return (size_t)(std::find(canonical.begin(), canonical.end(), canon) - canonical.begin()); }
 };
-inline bool gpl_pack_whole(const std::string& seq, uint64_t& v) {   // the whole sequence as one k-mer (BitNuclKmer::new(seq, len, false).next()); the codes of parse_barcode_list
+inline bool gpl_pack_whole(const std::string& seq, uint64_t& v) {   // the whole sequence as one k-mer (BitNuclKmer::new(seq, len, false).next())
     if (seq.empty() || seq.size() > 32) return false;
     v = 0;
     for (unsigned char ch : seq) {
-        int c;
-        switch (ch) { case 'A': case 'a': c = 0; break; case 'C': case 'c': c = 1; break; case 'G': case 'g': c = 2; break; case 'T': case 't': c = 3; break; default: return false; }
+        const int c = gpl_base_code(ch);
+        if (c < 0) return false;
         v = (v << 2) | (uint64_t)c;
     }
     return true;
@@ -499,11 +501,7 @@ struct SampleIndex {
     }
     void candidates(uint64_t obs, std::vector<const SampleSource*>& out) const {   // candidate_sources: every retained source once
         std::vector<uint64_t> c;
-        for (uint32_t pos = 0; pos < L; ++pos) {
-            const uint32_t sh = 2 * pos;
-            const uint64_t base = (obs >> sh) & 3, cleared = obs & ~(3ull << sh);
-            for (uint64_t rep = 0; rep < 4; ++rep) if (rep != base) c.push_back(cleared | (rep << sh));
-        }
+        gpl_push_substitutions(obs, L, c);
         if (shift) gpl_push_inverse_shift(obs, L, c);
         std::sort(c.begin(), c.end());
         c.erase(std::unique(c.begin(), c.end()), c.end());

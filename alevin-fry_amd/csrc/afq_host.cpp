@@ -379,6 +379,26 @@ const ResolutionInfo kRes[] = {
     {"parsimony-gene", "ParsimonyGene", AFQ_RES_PARSIMONY_GENE, true, false},
 };
 
+struct FileCloser { void operator()(FILE* f) const { if (f) std::fclose(f); } };
+using FilePtr = std::unique_ptr<FILE, FileCloser>;
+struct CtxCloser { void operator()(afq_ctx* c) const { if (c) afq_destroy(c); } };
+using CtxPtr = std::unique_ptr<afq_ctx, CtxCloser>;
+
+// The context of a file-level driver that only fills the device with rows or records (nothing is quantified: one gene, one
+// row); aln_extra: the bytes of a position behind every alignment word, 0 without one.
+int open_fill_ctx(uint32_t device, uint32_t aln_extra, CtxPtr& ctx) {
+    afq_config cfg{};
+    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
+    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
+    const uint32_t t2g0 = 0;
+    afq_ctx* raw = nullptr;
+    int rc = afq_create(&cfg, &t2g0, 1, (int)device, &raw);
+    if (rc) return hfail(rc, afq_last_error(nullptr));
+    ctx.reset(raw);
+    if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -571,21 +591,17 @@ int afq_infer_files(const afq_infer_opts* o) {
         ++n_out;
     }
     std::fclose(rows_f);
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* ctx = nullptr;
-    int rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &ctx);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
+    CtxPtr ctx;
+    int rc = open_fill_ctx(o->device, 0, ctx);
+    if (rc) return rc;
     afq_result res{};
-    rc = afq_infer(ctx, lab.data(), lp.data(), (uint32_t)num_eqc, cp.data(), ce.data(), cc.data(), (uint32_t)n_out, (uint32_t)num_genes, o->usa_mode, &res);
-    if (rc) { const std::string m = afq_last_error(ctx); afq_destroy(ctx); return hfail(rc, m); }
+    rc = afq_infer(ctx.get(), lab.data(), lp.data(), (uint32_t)num_eqc, cp.data(), ce.data(), cc.data(), (uint32_t)n_out, (uint32_t)num_genes, o->usa_mode, &res);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
     std::vector<uint64_t> rp(res.cell_ptr, res.cell_ptr + res.n_cells + 1);
     std::vector<uint32_t> cols(res.gene, res.gene + res.nnz);
     std::vector<float> vals(res.val, res.val + res.nnz);
     afq_result_release(&res);
-    afq_destroy(ctx);
+    ctx.reset();
     // (num_cells, num_genes) with num_cells = the subset's size when one is given (infer.rs:141, 175-178)
     if (!write_mtx_file(outd + "/quants_mat.mtx", filter ? keep.size() : n_rows, num_genes, rp, cols.data(), vals.data(), vals.size(), o->num_threads))
         return hfail(AFQ_ERR_BAD_INPUT, "could not write quants_mat.mtx");
@@ -593,11 +609,6 @@ int afq_infer_files(const afq_infer_opts* o) {
 }
 
 // ---- the device side of afq_quantify: one context (+ the -d sibling) per device over a contiguous range of cells ----
-struct FileCloser { void operator()(FILE* f) const { if (f) std::fclose(f); } };
-using FilePtr = std::unique_ptr<FILE, FileCloser>;
-struct CtxCloser { void operator()(afq_ctx* c) const { if (c) afq_destroy(c); } };
-using CtxPtr = std::unique_ptr<afq_ctx, CtxCloser>;
-
 struct DevOut {   // what one device produced for its range of cells, in cell order
     int rc = 0; std::string err;
     std::vector<uint32_t> gene; std::vector<float> val; std::vector<uint64_t> row_end;   // CSR (row_end cumulative within this part)
@@ -810,14 +821,8 @@ int afq_atac_deduplicate(const afq_atac_dedup_opts* o) {
         chunk_off.push_back(p); p += nb;
     }
     pc.lap("map + prelude + chunk table");
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     uint64_t *optr = nullptr, *obc = nullptr; uint32_t *oref = nullptr, *ostart = nullptr; uint16_t *oflen = nullptr, *ocnt = nullptr;
     afq_atac_stats st{};
     const uint64_t span0 = chunk_off.empty() ? 0 : chunk_off[0];
@@ -1005,6 +1010,69 @@ int write_unmapped_collated(const std::string& rd, const std::string& in, const 
     for (auto& kv : cnt) { std::fwrite(&kv.first, 8, 1, f.get()); std::fwrite(&kv.second, 4, 1, f.get()); }
     return 0;
 }
+// The offsets of exactly num_chunks chunks of the mapper's map.rad, hopping the nbytes headers from first_chunk on.
+int walk_chunk_offsets(const uint8_t* rad, size_t rad_n, size_t first_chunk, uint64_t num_chunks, std::vector<uint64_t>& chunk_off) {
+    size_t p = first_chunk;
+    for (uint64_t k = 0; k < num_chunks; ++k) {
+        if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(num_chunks));
+        uint32_t nb; std::memcpy(&nb, rad + p, 4);
+        if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
+        chunk_off.push_back(p); p += nb;
+    }
+    return 0;
+}
+// rel: the chunk offsets counted from span0, as the *_rad entry points take them beside `rad + span0`
+void rebase_chunk_offsets(const std::vector<uint64_t>& chunk_off, uint64_t span0, std::vector<uint64_t>& rel) {
+    rel.resize(chunk_off.size());
+    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+}
+// permit_freq.bin of a GPL output directory (collate.rs:236-274, atac/collate.rs:118-158): its barcode length, and the cells in the
+// order (count descending, barcode ascending); *total: the sum of their counts.  bad_len: what the caller says of a file whose
+// length does not match its entry count.
+int read_permit_cells(const std::string& in, const char* bad_len, uint64_t& bc_len, std::vector<uint64_t>& cells, uint64_t* total = nullptr) {
+    std::vector<uint8_t> pf;
+    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 24) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
+    uint64_t pf_ver, n_freq;
+    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8); std::memcpy(&n_freq, pf.data() + 16, 8);
+    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
+    if (n_freq != (pf.size() - 24) / 16 || (pf.size() - 24) % 16) return hfail(AFQ_ERR_BAD_INPUT, bad_len);
+    std::vector<std::pair<uint64_t, uint64_t>> freq(n_freq);   // (barcode, count)
+    for (uint64_t i = 0; i < n_freq; ++i) {
+        std::memcpy(&freq[i].first, pf.data() + 24 + 16 * i, 8); std::memcpy(&freq[i].second, pf.data() + 32 + 16 * i, 8);
+        if (total) *total += freq[i].second;
+    }
+    std::sort(freq.begin(), freq.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });   // collate.rs:270-274
+    cells.resize(n_freq);
+    for (uint64_t i = 0; i < n_freq; ++i) cells[i] = freq[i].first;
+    return 0;
+}
+// map.collated.rad: the input's prelude with num_chunks = n_chunks_out (collate.rs:544-549, atac/collate.rs:896-916), then the `on`
+// bytes of collated chunks; a file that could not be written whole is removed.
+int write_collated_rad(const std::string& out_path, const uint8_t* rad, const RadPrelude& P, uint64_t n_chunks_out, const uint8_t* ob, uint64_t on) {
+    FilePtr f(std::fopen(out_path.c_str(), "wb"));
+    bool ok = (bool)f;
+    if (ok) {
+        std::vector<uint8_t> hdr(rad, rad + P.first_chunk);
+        std::memcpy(hdr.data() + P.num_chunks_at, &n_chunks_out, 8);
+        ok = std::fwrite(hdr.data(), 1, hdr.size(), f.get()) == hdr.size();
+        for (uint64_t off = 0; ok && off < on;) {
+            const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
+            ok = std::fwrite(ob + off, 1, len, f.get()) == len;
+            off += len;
+        }
+        ok = ok && std::fflush(f.get()) == 0;
+    }
+    if (!ok) { f.reset(); std::remove(out_path.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + out_path); }
+    return 0;
+}
+// collate.json (collate.rs:589-597, atac/collate.rs:337-352; collation_mode / memory_budget_bytes describe the reference's engine
+// and are left out)
+int write_collate_json(const std::string& in, const char* cmdline) {
+    FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
+    if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+    std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false\n}", json_escape(cmdline ? cmdline : "").c_str());
+    return 0;
+}
 // offset of the value of the TOP-LEVEL "key" of a JSON object (gpl_options repeats some names), or npos
 size_t json_top_level_value(const std::string& gjs, const char* key) {
     const std::string k = key;
@@ -1107,18 +1175,12 @@ int afq_atac_sort(const afq_atac_sort_opts* o) {
     }
     if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
     pc.lap("map + prelude + maps + chunk table");
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
     warm.join();
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     const uint64_t span0 = chunk_off.empty() ? 0 : chunk_off[0];
-    std::vector<uint64_t> rel(chunk_off.size());
-    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    std::vector<uint64_t> rel;
+    rebase_chunk_offsets(chunk_off, span0, rel);
     uint64_t n_rows = 0, *obc = nullptr; uint32_t *oref = nullptr, *ostart = nullptr, *ocnt = nullptr; uint16_t* oflen = nullptr;
     afq_atac_sort_stats st{};
     rc = afq_atac_sort_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, 0, obs.data(), cor.data(), obs.size(),
@@ -1212,22 +1274,10 @@ int afq_collate(const afq_collate_opts* o) {
         expected_ori = k;
     }
     // ---- permit_freq.bin: the cells and their order (collate.rs:236-274)
-    std::vector<uint8_t> pf;
-    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 24) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
-    uint64_t pf_ver, bc_len, n_freq;
-    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8); std::memcpy(&n_freq, pf.data() + 16, 8);
-    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
-    if (n_freq != (pf.size() - 24) / 16 || (pf.size() - 24) % 16) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize permit_freq.bin: its length does not match its entry count");
-    if (n_freq == 0) return hfail(AFQ_ERR_BAD_INPUT, "single-barcode permit list contains no output cells");
-    std::vector<std::pair<uint64_t, uint64_t>> freq(n_freq);   // (barcode, count)
-    uint64_t total_to_collate = 0;
-    for (uint64_t i = 0; i < n_freq; ++i) {
-        std::memcpy(&freq[i].first, pf.data() + 24 + 16 * i, 8); std::memcpy(&freq[i].second, pf.data() + 32 + 16 * i, 8);
-        total_to_collate += freq[i].second;
-    }
-    std::sort(freq.begin(), freq.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });   // collate.rs:270-274
-    std::vector<uint64_t> cells(n_freq);
-    for (uint64_t i = 0; i < n_freq; ++i) cells[i] = freq[i].first;
+    std::vector<uint64_t> cells;
+    uint64_t bc_len = 0, total_to_collate = 0;
+    if (int rc2 = read_permit_cells(in, "couldn't deserialize permit_freq.bin: its length does not match its entry count", bc_len, cells, &total_to_collate)) return rc2;
+    if (cells.empty()) return hfail(AFQ_ERR_BAD_INPUT, "single-barcode permit list contains no output cells");
     // ---- the correction map, the unmapped counts
     std::vector<uint64_t> obs, cor;
     if (int rc2 = load_corrections(in, bc_len, "correction plan does not match this input: its cell barcode length is not permit_freq.bin's", "collation", obs, cor)) return rc2;
@@ -1257,30 +1307,15 @@ int afq_collate(const afq_collate_opts* o) {
         return hfail(AFQ_ERR_UNSUPPORTED, "collate: the alignment-level tags must be one u32 (ref | orientation), optionally followed by an integer pos");
     // ---- the chunk table
     std::vector<uint64_t> chunk_off;
-    {
-        size_t p = P.first_chunk;
-        for (uint64_t k = 0; k < P.num_chunks; ++k) {
-            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
-            uint32_t nb; std::memcpy(&nb, rad + p, 4);
-            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
-            chunk_off.push_back(p); p += nb;
-        }
-    }
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, P.num_chunks, chunk_off)) return rc2;
     if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
     pc.lap("metadata + maps + chunk table");
     // ---- the device: one fill
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
-    if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, aln_extra, ctx)) return rc2;
     const uint64_t span0 = chunk_off.empty() ? P.first_chunk : chunk_off[0];
-    std::vector<uint64_t> rel(chunk_off.size());
-    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    std::vector<uint64_t> rel;
+    rebase_chunk_offsets(chunk_off, span0, rel);
     uint8_t* ob = nullptr; uint64_t on = 0, *ooff = nullptr; uint32_t* onrec = nullptr;
     afq_collate_stats st{};
     rc = afq_collate_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, P.umi_bytes, expected_ori, 0, obs.data(), cor.data(),
@@ -1292,29 +1327,8 @@ int afq_collate(const afq_collate_opts* o) {
     if (st.n_kept != total_to_collate)   // collate.rs:615 (nothing was written yet, so no RAD is left behind)
         return hfail(AFQ_ERR_BAD_INPUT, "expected to collate " + std::to_string(total_to_collate) + " records but retained " + std::to_string(st.n_kept));
     // ---- map.collated.rad: the input's prelude with num_chunks = the number of cells (collate.rs:544-549), then the chunks
-    const std::string out_path = in + "/map.collated.rad";
-    {
-        FilePtr f(std::fopen(out_path.c_str(), "wb"));
-        bool ok = (bool)f;
-        if (ok) {
-            std::vector<uint8_t> hdr(rad, rad + P.first_chunk);
-            const uint64_t nc = cells.size();
-            std::memcpy(hdr.data() + P.num_chunks_at, &nc, 8);
-            ok = std::fwrite(hdr.data(), 1, hdr.size(), f.get()) == hdr.size();
-            for (uint64_t off = 0; ok && off < on;) {
-                const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
-                ok = std::fwrite(ob + off, 1, len, f.get()) == len;
-                off += len;
-            }
-            ok = ok && std::fflush(f.get()) == 0;
-        }
-        if (!ok) { f.reset(); std::remove(out_path.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + out_path); }
-    }
-    {   // collate.rs:589-597 (collation_mode / memory_budget_bytes describe the reference's engine and are left out)
-        FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
-        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
-        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false\n}", json_escape(o->cmdline ? o->cmdline : "").c_str());
-    }
+    if (int rc2 = write_collated_rad(in + "/map.collated.rad", rad, P, cells.size(), ob, on)) return rc2;
+    if (int rc2 = write_collate_json(in, o->cmdline)) return rc2;
     pc.lap("map.collated.rad");
     std::fprintf(stderr, "deserialized correction map of length : %llu\n", (unsigned long long)obs.size());
     std::fprintf(stderr, "collated %llu of %llu records (%llu orientation consistent, %llu with a barcode that is not in the correction map) into %llu cells\n",
@@ -1341,17 +1355,9 @@ int afq_atac_collate(const afq_atac_collate_opts* o) {
     if (json_top_level_value(gjs, "version_str") == std::string::npos)
         return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
     // ---- permit_freq.bin: the cells and their order (atac/collate.rs:118-158)
-    std::vector<uint8_t> pf;
-    if (!read_file(in + "/permit_freq.bin", pf) || pf.size() < 24) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read freq file header");
-    uint64_t pf_ver, bc_len, n_freq;
-    std::memcpy(&pf_ver, pf.data(), 8); std::memcpy(&bc_len, pf.data() + 8, 8); std::memcpy(&n_freq, pf.data() + 16, 8);
-    if (pf_ver > 1) return hfail(AFQ_ERR_BAD_INPUT, "The permit_freq.bin file had version " + std::to_string(pf_ver) + ", but this version of alevin-fry requires version 1");
-    if (n_freq != (pf.size() - 24) / 16 || (pf.size() - 24) % 16) return hfail(AFQ_ERR_BAD_INPUT, "couldn't deserialize barcode to frequency map.");
-    std::vector<std::pair<uint64_t, uint64_t>> freq(n_freq);   // (barcode, count)
-    for (uint64_t i = 0; i < n_freq; ++i) { std::memcpy(&freq[i].first, pf.data() + 24 + 16 * i, 8); std::memcpy(&freq[i].second, pf.data() + 32 + 16 * i, 8); }
-    std::sort(freq.begin(), freq.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second > b.second : a.first < b.first; });   // :158
-    std::vector<uint64_t> cells(n_freq);
-    for (uint64_t i = 0; i < n_freq; ++i) cells[i] = freq[i].first;
+    std::vector<uint64_t> cells;
+    uint64_t bc_len = 0;
+    if (int rc2 = read_permit_cells(in, "couldn't deserialize barcode to frequency map.", bc_len, cells)) return rc2;
     uint64_t num_chunks = 0;
     {
         const size_t v = json_top_level_value(gjs, "num-chunks");
@@ -1381,29 +1387,15 @@ int afq_atac_collate(const afq_atac_collate_opts* o) {
         return hfail(AFQ_ERR_UNSUPPORTED, "atac collate: this is not a scATAC RAD file (one integer read tag b; alignment tags ref:u32, type:u8, start_pos:u32, frag_len:u16); use `collate`");
     // ---- exactly num-chunks chunk headers
     std::vector<uint64_t> chunk_off;
-    {
-        size_t p = P.first_chunk;
-        for (uint64_t k = 0; k < num_chunks; ++k) {
-            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(num_chunks));
-            uint32_t nb; std::memcpy(&nb, rad + p, 4);
-            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
-            chunk_off.push_back(p); p += nb;
-        }
-    }
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, num_chunks, chunk_off)) return rc2;
     if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
     pc.lap("metadata + maps + chunk table");
     // ---- the device: one fill
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     const uint64_t span0 = chunk_off.empty() ? P.first_chunk : chunk_off[0];
-    std::vector<uint64_t> rel(chunk_off.size());
-    for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
+    std::vector<uint64_t> rel;
+    rebase_chunk_offsets(chunk_off, span0, rel);
     uint8_t* ob = nullptr; uint64_t on = 0, n_out = 0, *ooff = nullptr; uint32_t *onrec = nullptr, *ocell = nullptr;
     afq_atac_collate_stats st{};
     rc = afq_atac_collate_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, 0, obs.data(), cor.data(), obs.size(),
@@ -1413,28 +1405,8 @@ int afq_atac_collate(const afq_atac_collate_opts* o) {
     pc.lap("device: atac collate");
     if (o->stats_out) *o->stats_out = st;
     // ---- map.collated.rad: the input's prelude with num_chunks = the chunks written (atac/collate.rs:896-916), then the chunks
-    const std::string out_path = in + "/map.collated.rad";
-    {
-        FilePtr f(std::fopen(out_path.c_str(), "wb"));
-        bool ok = (bool)f;
-        if (ok) {
-            std::vector<uint8_t> hdr(rad, rad + P.first_chunk);
-            std::memcpy(hdr.data() + P.num_chunks_at, &n_out, 8);
-            ok = std::fwrite(hdr.data(), 1, hdr.size(), f.get()) == hdr.size();
-            for (uint64_t off = 0; ok && off < on;) {
-                const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
-                ok = std::fwrite(ob + off, 1, len, f.get()) == len;
-                off += len;
-            }
-            ok = ok && std::fflush(f.get()) == 0;
-        }
-        if (!ok) { f.reset(); std::remove(out_path.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + out_path); }
-    }
-    {   // atac/collate.rs:337-352
-        FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
-        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
-        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false\n}", json_escape(o->cmdline ? o->cmdline : "").c_str());
-    }
+    if (int rc2 = write_collated_rad(in + "/map.collated.rad", rad, P, n_out, ob, on)) return rc2;
+    if (int rc2 = write_collate_json(in, o->cmdline)) return rc2;
     pc.lap("map.collated.rad");
     std::fprintf(stderr, "deserialized correction map of length : %llu\n", (unsigned long long)obs.size());
     std::fprintf(stderr, "collated %llu of %llu records (%llu without a mapping, %llu with more than 1 mapping, %llu with a barcode that is not in the correction map); %llu output bytes\n",
@@ -2106,24 +2078,9 @@ int afq_generate_permit_list(const afq_gpl_opts* o) {
     }
     // ---- the chunk table
     std::vector<uint64_t> chunk_off;
-    {
-        size_t p = P.first_chunk;
-        for (uint64_t k = 0; k < P.num_chunks; ++k) {
-            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
-            uint32_t nb; std::memcpy(&nb, rad + p, 4);
-            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
-            chunk_off.push_back(p); p += nb;
-        }
-    }
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
-    if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, P.num_chunks, chunk_off)) return rc2;
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, aln_extra, ctx)) return rc2;
     // ---- the record pass: one device fill per run of chunks of at most fill_bytes, the sorted histograms merged
     const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
     std::vector<uint64_t> hbc, hcnt;
@@ -2339,23 +2296,9 @@ int64_t afq_generate_permit_list_multi(const afq_gpl_multi_opts* o) {
     const std::vector<uint64_t>* whitelist = o->method == AFQ_GPL_UNFILTERED ? &listed : nullptr;
     // ---- the chunk table
     std::vector<uint64_t> chunk_off;
-    {
-        size_t p = P.first_chunk;
-        for (uint64_t k = 0; k < P.num_chunks; ++k) {
-            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
-            uint32_t nb; std::memcpy(&nb, rad + p, 4);
-            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
-            chunk_off.push_back(p); p += nb;
-        }
-    }
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, P.num_chunks, chunk_off)) return rc2;
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     // ---- the record pass: one device fill per run of chunks of at most fill_bytes, the sorted outputs merged under the key entry << 32 | cell
     const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
     std::vector<uint64_t> pkey, pcnt;
@@ -2642,23 +2585,9 @@ int afq_atac_generate_permit_list(const afq_atac_gpl_opts* o) {
     if (n_bins >= (1ull << 31)) return hfail(AFQ_ERR_UNSUPPORTED, "atac generate-permit-list: 2^31 or more position bins (" + std::to_string(n_bins) + ")");
     // ---- the chunk table
     std::vector<uint64_t> chunk_off;
-    {
-        size_t p = P.first_chunk;
-        for (uint64_t k = 0; k < P.num_chunks; ++k) {
-            if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "map.rad ends before chunk " + std::to_string(k) + " of " + std::to_string(P.num_chunks));
-            uint32_t nb; std::memcpy(&nb, rad + p, 4);
-            if (nb < 8 || nb > rad_n - p) return hfail(AFQ_ERR_BAD_INPUT, "corrupt chunk header (chunk " + std::to_string(k) + ")");
-            chunk_off.push_back(p); p += nb;
-        }
-    }
-    afq_config cfg{};
-    cfg.abi_version = AFQ_ABI_VERSION; cfg.resolution = AFQ_RES_CR_LIKE; cfg.num_genes = 1; cfg.num_rows = 1; cfg.small_thresh = 100;
-    cfg.pug_exact_umi = 1; cfg.bc_bytes = 4; cfg.umi_bytes = 4;
-    const uint32_t t2g0 = 0;
-    afq_ctx* raw = nullptr;
-    rc = afq_create(&cfg, &t2g0, 1, (int)o->device, &raw);
-    if (rc) return hfail(rc, afq_last_error(nullptr));
-    CtxPtr ctx(raw);
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, P.num_chunks, chunk_off)) return rc2;
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     // ---- the record pass: one device fill per run of chunks of at most fill_bytes; histograms merged, bins and tallies added
     const uint64_t fill_bytes = o->fill_bytes ? o->fill_bytes : (8ull << 30);
     std::vector<uint64_t> hbc, hcnt, bins(n_bins, 0);

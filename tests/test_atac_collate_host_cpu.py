@@ -36,8 +36,8 @@ PLAN = [(0x11, 0x11), (0x22, 0x22), (0x12, 0x11)]
 A1 = (0, 4, 10, 50)
 
 
-def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=None, rna=False, chunks=None, unmapped=None):
-    """an `atac generate-permit-list` output directory and a mapper directory; -> (input_dir, rad_dir)"""
+def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=None, rna=False, chunks=None, unmapped=None, cut=0):
+    """an `atac generate-permit-list` output directory and a mapper directory (map.rad less its last `cut` bytes); -> (input_dir, rad_dir)"""
     ind, rd = str(tmp_path / "gpl"), str(tmp_path / "map")
     os.makedirs(ind)
     os.makedirs(rd)
@@ -55,7 +55,7 @@ def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=None, rna=False, c
         body, _ = rad.encode_atac_chunks(chunks)
         prelude = rad.rad_prelude_atac(["chr1"], [1000], len(chunks), cblen=L)
     with open(os.path.join(rd, "map.rad"), "wb") as f:
-        f.write(prelude + body)
+        f.write((prelude + body)[:len(prelude) + len(body) - cut])
     if unmapped is not None:
         with open(os.path.join(rd, "unmapped_bc_count.bin"), "wb") as f:
             f.write(b"".join(int(b).to_bytes(8, "little") + int(n).to_bytes(4, "little") for b, n in unmapped))
@@ -137,6 +137,11 @@ def test_an_rna_prelude_is_refused_and_names_collate(lib, tmp_path):
 def test_a_file_with_fewer_chunks_than_num_chunks_is_refused(lib, tmp_path):
     ind, rd = dirs(tmp_path, meta=dict(META, **{"num-chunks": 3}), chunks=[[(0x11, [A1])], [(0x22, [A1])]])
     refused(lib, ind, rd, BAD_INPUT, "map.rad ends before chunk 2 of 3")
+
+
+def test_a_chunk_whose_nbytes_runs_past_the_file_is_refused_by_its_number(lib, tmp_path):
+    ind, rd = dirs(tmp_path, meta=dict(META, **{"num-chunks": 2}), chunks=[[(0x11, [A1])], [(0x22, [A1])]], cut=4)
+    refused(lib, ind, rd, BAD_INPUT, "corrupt chunk header (chunk 1)")
 
 
 def test_the_unmapped_counts_are_written_before_the_prelude_is_read(lib, tmp_path):

@@ -35,8 +35,9 @@ FREQ = [(0x11, 3), (0x22, 5)]
 PLAN = [(0x11, 0x11), (0x22, 0x22), (0x12, 0x11)]
 
 
-def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=PLAN, plan_len=L, atac=False, unmapped=None):
-    """a generate-permit-list output directory and a mapper directory; -> (input_dir, rad_dir)"""
+def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=PLAN, plan_len=L, atac=False, unmapped=None, n_chunks=1, num_chunks=None, cut=0):
+    """a generate-permit-list output directory and a mapper directory; -> (input_dir, rad_dir).  map.rad holds n_chunks chunks of one
+    record, less its last `cut` bytes; its prelude announces num_chunks of them (default: n_chunks)."""
     ind, rd = str(tmp_path / "gpl"), str(tmp_path / "map")
     os.makedirs(ind)
     os.makedirs(rd)
@@ -46,10 +47,11 @@ def dirs(tmp_path, meta=META, freq=FREQ, freq_version=1, plan=PLAN, plan_len=L, 
         f.write(rad.permit_freq_bytes(L, freq, version=freq_version))
     with open(os.path.join(ind, "correction_plan.bin"), "wb") as f:
         f.write(rad.correction_plan_bytes(plan, barcode_len=plan_len))
-    body, _ = rad.encode_chunks([[(0x11, 1, [(1, True)])]])
-    prelude = rad.rad_prelude_atac(["chr1"], [1000], 1) if atac else rad.rad_prelude(["t0", "t1"], 1, L, 12, 4, 4)
+    body, _ = rad.encode_chunks([[(0x11, 1, [(1, True)])]] * n_chunks)
+    num_chunks = n_chunks if num_chunks is None else num_chunks
+    prelude = rad.rad_prelude_atac(["chr1"], [1000], num_chunks) if atac else rad.rad_prelude(["t0", "t1"], num_chunks, L, 12, 4, 4)
     with open(os.path.join(rd, "map.rad"), "wb") as f:
-        f.write(prelude + body)
+        f.write((prelude + body)[:len(prelude) + len(body) - cut])
     if unmapped is not None:
         with open(os.path.join(rd, "unmapped_bc_count.bin"), "wb") as f:
             f.write(b"".join(int(b).to_bytes(8, "little") + int(n).to_bytes(4, "little") for b, n in unmapped))
@@ -118,6 +120,12 @@ def test_permit_list_refusals(lib, tmp_path):
     with open(os.path.join(ind, "permit_map.bin"), "wb") as f:
         f.write(rad.permit_map_bytes(PLAN))
     refused(lib, ind, rd, BAD_INPUT, "correction plan contains trailing data")
+
+
+def test_a_truncated_chunk_table(lib, tmp_path):
+    """the prelude promises three chunks and the file holds two; the last chunk's nbytes runs past the file's end"""
+    refused(lib, *dirs(tmp_path / "a", n_chunks=2, num_chunks=3), BAD_INPUT, "map.rad ends before chunk 2 of 3")
+    refused(lib, *dirs(tmp_path / "b", n_chunks=2, cut=4), BAD_INPUT, "corrupt chunk header (chunk 1)")
 
 
 def test_atac_prelude_is_refused_by_name_after_the_unmapped_counts_were_written(lib, tmp_path):

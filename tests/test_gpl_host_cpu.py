@@ -290,6 +290,27 @@ def test_rad_writers_and_readers_agree():
         rad.read_permit_map(rad.permit_map_bytes(pairs) + b"\0")
 
 
+# ------------------------------------------------------------------------------------------------------------ chunk table
+def refused(lib, tmp_path, code, sentence, num_chunks=2, cut=0):
+    """afq_generate_permit_list on a map.rad of two one-record chunks less its last `cut` bytes, whose prelude announces num_chunks"""
+    os.makedirs(tmp_path / "map")
+    body, _ = rad.encode_chunks([[(0x11, 1, [(1, True)])], [(0x22, 2, [(0, True)])]])
+    blob = rad.rad_prelude(["t0", "t1"], num_chunks, 16, 12, 4, 4) + body
+    (tmp_path / "map" / "map.rad").write_bytes(blob[:len(blob) - cut])
+    lib.afq_generate_permit_list.argtypes = [C.POINTER(GplOpts)]
+    o = GplOpts(input_dir=str(tmp_path / "map").encode(), output_dir=str(tmp_path / "out").encode(), expected_ori=1, method=KNEE, neighborhood=-1)
+    rc = lib.afq_generate_permit_list(C.byref(o))
+    assert rc == code and sentence in err(lib), (rc, err(lib))
+    assert not (tmp_path / "out").exists()
+
+
+def test_a_truncated_chunk_table(lib, tmp_path):
+    """the prelude promises three chunks and the file holds two; the last chunk's nbytes runs past the file's end.  Both are refused
+    before a device is opened."""
+    refused(lib, tmp_path / "a", BAD_INPUT, "map.rad ends before chunk 2 of 3", num_chunks=3)
+    refused(lib, tmp_path / "b", BAD_INPUT, "corrupt chunk header (chunk 1)", cut=4)
+
+
 # ---------------------------------------------------------------------------------------------------------------- sanitizers
 SAN_MAIN = r'''
 #include "afq_gpl_host.h"

@@ -179,6 +179,15 @@ def test_prelude_refusals(tmp_path):
     assert e.code == BAD_INPUT and "does not exist" in str(e)
 
 
+def test_a_truncated_chunk_table(tmp_path):
+    """the prelude promises three chunks and the file holds two; the last chunk's nbytes runs past the file's end"""
+    body, _ = rad.encode_multi_bc_chunks([[(1, 0x11, 1, [(0, True)])], [(1, 0x22, 2, [(0, True)])]])
+    e = multi(tmp_path, write_dir(tmp_path / "three", rad.rad_prelude_multi_bc(["t0"], 3, 8, 16, 12, b_bytes=4, umi_bytes=4, b0_bytes=2), body))
+    assert e.code == BAD_INPUT and "map.rad ends before chunk 2 of 3" in str(e)
+    e = multi(tmp_path, write_dir(tmp_path / "cut", rad.rad_prelude_multi_bc(["t0"], 2, 8, 16, 12, b_bytes=4, umi_bytes=4, b0_bytes=2), body[:-4]))
+    assert e.code == BAD_INPUT and "corrupt chunk header (chunk 1)" in str(e)
+
+
 def test_option_and_list_refusals_precede_the_device(tmp_path):
     good = write_dir(tmp_path / "good", rad.rad_prelude_multi_bc(["t0"], 0, 8, 16, 12, b_bytes=4, umi_bytes=4, b0_bytes=2))
     assert multi(tmp_path, good, method="unfiltered").code == INVALID_ARG                                     # no list file

@@ -155,11 +155,24 @@ def test_malformed_chunks_are_refused_with_their_index(q, kind):
     check(q, C.na_case(), "after " + kind)   # the context serves again afterwards
 
 
+def test_a_record_count_one_too_high_is_refused_by_sentence(q):
+    data, off = pkg.rad.encode_atac_chunks([[(5, [(0, 4, 10, 50)]), (8, [])], [(5, [(0, 4, 20, 50)]), (8, [(0, 4, 30, 50)])]], bc_bytes=4)
+    o1 = int(off[1])
+    bad = data[:o1 + 4] + (3).to_bytes(4, "little") + data[o1 + 8:]   # chunk 1 holds two records and says three
+    with pytest.raises(pkg.AfqError) as e:
+        q.atac_collate_rad(bad, off, [5, 8], [5, 8], [5, 8], bc_bytes=4)
+    assert e.value.code == BAD_INPUT and "chunk 1:" in str(e.value) and "the records do not tile the chunk" in str(e.value), str(e.value)
+
+
 def test_bad_maps_and_cell_lists_are_refused(q):
     c = C.na_case()
     with pytest.raises(pkg.AfqError) as e:
         q.atac_collate_rad(c["data"], c["off"], [5, 8], [5, 99], [5, 9], bc_bytes=4)
     assert e.value.code == BAD_INPUT and "correction entry 1" in str(e.value) and "99" in str(e.value) and "not a cell" in str(e.value)
+    one, off1 = pkg.rad.encode_atac_chunks([[(5, [(0, 4, 10, 50)])]], bc_bytes=4)   # one chunk, one record; cells 1 and 2 are the same barcode
+    with pytest.raises(pkg.AfqError) as e:
+        q.atac_collate_rad(one, off1, [5], [5], [9, 5, 5], bc_bytes=4)
+    assert e.value.code == BAD_INPUT and "cells 1 and 2 carry one barcode (5)" in str(e.value), str(e.value)
     with pytest.raises(pkg.AfqError) as e:
         q.atac_collate_rad(c["data"], c["off"], [5, 8, 5], [5, 8, 8], [5, 8], bc_bytes=4)
     assert e.value.code == BAD_INPUT and "two different corrected barcodes" in str(e.value)

@@ -211,6 +211,13 @@ def test_malformed_chunks_are_refused_with_their_index_and_the_context_stays_usa
     G.same(q.atac_gpl_hist_rad(data, off, [0, 1]), want, "after a chunk outside the buffer")
 
 
+def test_a_record_count_one_too_high_is_refused_by_sentence(q):
+    data, off = rad.encode_atac_chunks([[(1, [A(0, 5)]), (2, [])], [(1, [A(0, 7)]), (2, [A(0, 9)])]])
+    o1 = int(off[1])
+    bad = data[:o1 + 4] + (3).to_bytes(4, "little") + data[o1 + 8:]   # chunk 1 holds two records and says three
+    refused(q, BAD_INPUT, "chunk 1: the records do not tile the chunk", bad, off, [0, 1])
+
+
 # ------------------------------------------------------------------------------------------------------------------- the context
 def test_two_calls_merged_by_hand_equal_one_call(q, lim):
     rl = [250001, 900, 99993]

@@ -157,11 +157,24 @@ def test_malformed_chunks_are_refused_with_their_index(q, lim, kind):
     check(q, lim, C.interleave_case(), oris=["both"])   # the context serves again afterwards
 
 
+def test_a_record_count_one_too_high_is_refused_by_sentence(q):
+    data, off = pkg.rad.encode_chunks([[(7, 1, [(0, True)]), (8, 2, [(1, False)])], [(7, 3, [(0, True), (1, True)]), (8, 4, [(0, False), (1, True)])]])
+    o1 = int(off[1])
+    bad = data[:o1 + 4] + (3).to_bytes(4, "little") + data[o1 + 8:]   # chunk 1 holds two records and says three (three heads would fit it)
+    with pytest.raises(pkg.AfqError) as e:
+        q.collate_rad(bad, off, [7, 8], [7, 8], [7, 8], bc_bytes=4, umi_bytes=4)
+    assert e.value.code == BAD_INPUT and "chunk 1:" in str(e.value) and "the records do not tile the chunk" in str(e.value), str(e.value)
+
+
 def test_bad_corrections_are_refused(q, lim):
     c = C.interleave_case()
     with pytest.raises(pkg.AfqError) as e:
         q.collate_rad(c["data"], c["off"], [7, 8], [7, 99], [7, 9], bc_bytes=4, umi_bytes=4)
     assert e.value.code == BAD_INPUT and "correction entry 1" in str(e.value) and "99" in str(e.value) and "not a cell" in str(e.value)
+    one, off1 = pkg.rad.encode_chunks([[(7, 1, [(0, True)])]])   # one chunk, one record; cells 1 and 2 are the same barcode
+    with pytest.raises(pkg.AfqError) as e:
+        q.collate_rad(one, off1, [7], [7], [9, 7, 7], bc_bytes=4, umi_bytes=4)
+    assert e.value.code == BAD_INPUT and "cells 1 and 2 carry one barcode (7)" in str(e.value), str(e.value)
     with pytest.raises(pkg.AfqError) as e:
         q.collate_rad(c["data"], c["off"], [7, 8, 7], [7, 8, 8], [7, 8], bc_bytes=4, umi_bytes=4)
     assert e.value.code == BAD_INPUT and "two different corrected barcodes" in str(e.value)

@@ -97,6 +97,15 @@ def test_malformed_chunks_are_refused_with_their_index(q, kind):
     check_hist(q, a, oris=["both"])
 
 
+def test_a_record_count_one_too_high_is_refused_by_sentence(q):
+    data, off = pkg.rad.encode_chunks([[(7, 1, [(0, True)]), (8, 2, [(1, False)])], [(7, 3, [(0, True), (1, True)]), (8, 4, [(0, False), (1, True)])]])
+    o1 = int(off[1])
+    bad = data[:o1 + 4] + (3).to_bytes(4, "little") + data[o1 + 8:]   # chunk 1 holds two records and says three (three heads would fit it)
+    with pytest.raises(pkg.AfqError) as e:
+        q.gpl_hist_rad(bad, off, bc_bytes=4, umi_bytes=4)
+    assert e.value.code == BAD_INPUT and "chunk 1:" in str(e.value) and "the records do not tile the chunk" in str(e.value), str(e.value)
+
+
 def test_chunk_table_refusals(q):
     c = G.widths_case(4, 4, 0)
     off = c["off"].copy()

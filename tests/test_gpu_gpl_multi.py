@@ -104,6 +104,15 @@ def test_malformed_chunks_are_refused_with_their_index(q, kind):
     check(q, a, oris=["both"])
 
 
+def test_a_record_count_one_too_high_is_refused_by_sentence(q):
+    data, off = pkg.rad.encode_multi_bc_chunks([[(1, 7, 1, [(0, True)]), (2, 8, 2, [(1, False)])], [(1, 7, 3, [(0, True), (1, True)]), (3, 8, 4, [(0, False), (1, True)])]])
+    o1 = int(off[1])
+    bad = data[:o1 + 4] + (3).to_bytes(4, "little") + data[o1 + 8:]   # chunk 1 holds two records and says three (three heads would fit it)
+    with pytest.raises(pkg.AfqError) as e:
+        q.gpl_multi_hist_rad(bad, off, np.asarray([1, 2], np.uint64), b0_bytes=2, b1_bytes=4, umi_bytes=4)
+    assert e.value.code == BAD_INPUT and "chunk 1:" in str(e.value) and "the records do not tile the chunk" in str(e.value), str(e.value)
+
+
 def test_chunk_table_and_argument_refusals(q):
     c = MC.widths_case(2, 4, 4)
     ent = np.asarray(c["entries"], np.uint64)
