@@ -136,6 +136,8 @@ EXPORTS = [
     "afq_gpl_multi_limits",
     "afq_collate_rad",
     "afq_collate_limits",
+    "afq_collate_multi_rad",
+    "afq_collate_multi_limits",
     "afq_atac_collate_rad",
     "afq_atac_collate_limits",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
@@ -197,6 +199,17 @@ class AfqGplMultiOpts(C.Structure):
 class AfqCollateStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_uncorrected", C.c_uint64), ("n_kept", C.c_uint64),
                 ("n_alignments_in", C.c_uint64), ("n_alignments_kept", C.c_uint64), ("n_long_records", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqCollateMultiStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_compatible", C.c_uint64), ("n_unrouted", C.c_uint64), ("n_uncorrected", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_alignments_in", C.c_uint64), ("n_alignments_kept", C.c_uint64), ("n_long_records", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqCollateMultiOpts(C.Structure):
+    """afq_collate_multi_opts of include/afquant_host.h (afq_collate_multi)."""
+    _fields_ = [("input_dir", C.c_char_p), ("rad_dir", C.c_char_p), ("num_threads", C.c_uint32), ("compress", C.c_uint32), ("max_records", C.c_uint32),
+                ("device", C.c_uint32), ("cmdline", C.c_char_p), ("stats_out", C.POINTER(AfqCollateMultiStats))]
 
 
 class AfqAtacCollateStats(C.Structure):

@@ -335,6 +335,15 @@ def load_library(path: str = LIB_PATH):
     lib.afq_collate_rad.restype = C.c_int
     lib.afq_collate_limits.argtypes = [p(C.c_uint32)]
     lib.afq_collate_limits.restype = None
+    lib.afq_collate_multi_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                          p(C.c_uint64), p(C.c_uint32), C.c_uint64, p(C.c_uint32), p(C.c_uint64), p(C.c_uint64), C.c_uint64, p(C.c_uint32),
+                                          p(C.c_uint64), C.c_uint64, p(C.c_uint32), C.c_uint64, p(p(C.c_uint8)), p(C.c_uint64), p(p(C.c_uint64)),
+                                          p(p(C.c_uint32)), p(_abi.AfqCollateMultiStats)]
+    lib.afq_collate_multi_rad.restype = C.c_int
+    lib.afq_collate_multi_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_collate_multi_limits.restype = None
+    lib.afq_collate_multi.argtypes = [p(_abi.AfqCollateMultiOpts)]
+    lib.afq_collate_multi.restype = C.c_int
     lib.afq_atac_collate_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), p(C.c_uint64),
                                          C.c_uint64, p(C.c_uint64), C.c_uint64, p(p(C.c_uint8)), p(C.c_uint64), p(C.c_uint64), p(p(C.c_uint64)),
                                          p(p(C.c_uint32)), p(p(C.c_uint32)), p(_abi.AfqAtacCollateStats)]
@@ -388,6 +397,29 @@ def collate_limits():
     out = (C.c_uint32 * 4)()
     load_library().afq_collate_limits(out)
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "radix_block": int(out[3])}
+
+
+def collate_multi_limits():
+    """afq_collate_multi_limits: collate_limits' four values for multi-barcode collate (the walks are collate's over another head, the
+    placement is collate's own).  Tests build their edge shapes from these."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_collate_multi_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "radix_block": int(out[3])}
+
+
+def collate_multi(input_dir, rad_dir, device: int = 0, cmdline: str = ""):
+    """afq_collate_multi: multi-barcode `collate` - the output directory of generate_permit_list_multi and the mapper's directory in;
+    map.collated.rad, collation_manifest.bin, collate.json and unmapped_bc_count_collated.bin are written into input_dir.  Returns the
+    device call's stats; raises AfqError."""
+    lib = load_library()
+    st = _abi.AfqCollateMultiStats()
+    o = _abi.AfqCollateMultiOpts()
+    o.input_dir, o.rad_dir, o.device, o.cmdline = os.fsencode(input_dir), os.fsencode(rad_dir), int(device), cmdline.encode()
+    o.stats_out = C.pointer(st)
+    rc = lib.afq_collate_multi(C.byref(o))
+    if rc:
+        raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
 
 def atac_collate_limits():
@@ -847,6 +879,43 @@ class Quantifier:
     def collate_limits():
         """The collate walks' and radix passes' limits (module-level collate_limits)."""
         return collate_limits()
+
+    def collate_multi_rad(self, chunk_bytes, chunk_off, sample_observed, sample_index, corr_sample, corr_observed, corr_corrected, cell_sample, cell_bc,
+                          sample_b0_out, b0_bytes: int = 2, b1_bytes: int = 4, umi_bytes: int = 4, expected_ori="both", d_ptr: int = 0, n_bytes: int = 0):
+        """afq_collate_multi_rad: the chunks of an uncollated two-barcode RNA RAD in (host bytes, or d_ptr/n_bytes for bytes already on the
+        device); the sample table sample_observed -> sample_index, the cell table (corr_sample, corr_observed) -> corr_corrected, the cells
+        (cell_sample, cell_bc) in output order and sample_b0_out, the value written into b0 per sample.  The dict of collate_rad out."""
+        off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+        u64 = lambda v: np.ascontiguousarray(v, dtype=np.uint64)
+        u32 = lambda v: np.ascontiguousarray(v, dtype=np.uint32)
+        so, si, cs, co, cc, ls, lb, b0o = u64(sample_observed), u32(sample_index), u32(corr_sample), u64(corr_observed), u64(corr_corrected), u32(cell_sample), u64(cell_bc), u32(sample_b0_out)
+        if len(so) != len(si) or not (len(cs) == len(co) == len(cc)) or len(ls) != len(lb):
+            raise ValueError("the columns of a table must have one length")
+        ori = _abi.GPL_ORI[expected_ori.lower()] if isinstance(expected_ori, str) else int(expected_ori)
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(chunk_bytes, dtype=np.uint8) if not isinstance(chunk_bytes, np.ndarray) else chunk_bytes)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        o_b, o_n, o_off, o_nrec, st = C.POINTER(C.c_uint8)(), C.c_uint64(), u64p(), u32p(), _abi.AfqCollateMultiStats()
+        self._check(self.lib.afq_collate_multi_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), int(b0_bytes), int(b1_bytes), int(umi_bytes), ori, on_dev,
+                                                   so.ctypes.data_as(u64p), si.ctypes.data_as(u32p), len(so), cs.ctypes.data_as(u32p), co.ctypes.data_as(u64p),
+                                                   cc.ctypes.data_as(u64p), len(cs), ls.ctypes.data_as(u32p), lb.ctypes.data_as(u64p), len(ls),
+                                                   b0o.ctypes.data_as(u32p), len(b0o), C.byref(o_b), C.byref(o_n), C.byref(o_off), C.byref(o_nrec), C.byref(st)))
+        n, nc = int(o_n.value), len(ls)
+        try:
+            mk = lambda p_, k, dt: (np.ctypeslib.as_array(p_, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dt))
+            return {"bytes": mk(o_b, n, np.uint8), "chunk_off": mk(o_off, nc + 1, np.uint64), "nrec": mk(o_nrec, nc, np.uint32),
+                    "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_b, o_off, o_nrec):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def collate_multi_limits():
+        """Multi-barcode collate's limits (module-level collate_multi_limits)."""
+        return collate_multi_limits()
 
     def atac_collate_rad(self, chunk_bytes, chunk_off, observed, corrected, cells, bc_bytes: int = 4, d_ptr: int = 0, n_bytes: int = 0):
         """afq_atac_collate_rad: the chunks of an uncollated scATAC RAD in (host bytes, or d_ptr/n_bytes for bytes already on the device),

@@ -62,7 +62,7 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
@@ -71,7 +71,8 @@ const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "
                                            "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write",
                                            "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write",
                                            "k_atac_gpl_parse", "k_atac_gpl_bins",
-                                           "k_gpl_multi_table", "k_gpl_multi_parse"};
+                                           "k_gpl_multi_table", "k_gpl_multi_parse",
+                                           "k_collate_multi_table", "k_collate_multi_measure", "k_collate_multi_sort", "k_collate_multi_scan", "k_collate_multi_write"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -216,10 +217,13 @@ struct GplBufs {
     }
 };
 
-// afq_collate_rad's
+// afq_collate_rad's, and afq_collate_multi_rad's (its sample entries and their table in sobs, sidx, skey, sval)
 struct CollateBufs {
     DevBuf chunks, obs, val, tkey, tval, cells, rec, ka, kb, hist, bsum, ex, cstat, status, out, off, nrec;
-    std::vector<DevBuf*> all() { return {&chunks, &obs, &val, &tkey, &tval, &cells, &rec, &ka, &kb, &hist, &bsum, &ex, &cstat, &status, &out, &off, &nrec}; }
+    DevBuf sobs, sidx, skey, sval;
+    std::vector<DevBuf*> all() {
+        return {&chunks, &obs, &val, &tkey, &tval, &cells, &rec, &ka, &kb, &hist, &bsum, &ex, &cstat, &status, &out, &off, &nrec, &sobs, &sidx, &skey, &sval};
+    }
 };
 
 // afq_atac_collate_rad's
@@ -3478,6 +3482,165 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
         return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: cell " + std::to_string(st.err_cell) + " (barcode " + std::to_string(cells[st.err_cell]) + "): an output chunk of 4 GiB or more");
     if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_collate_rad: device status " + std::to_string(st.err_code) + " in the write");
     if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, "afq_collate_rad: the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
+    S.out_bytes = out_total;
+    if (stats) *stats = S;
+    H.release();
+    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
+    return 0;
+}
+
+// multi-barcode `collate` on the device (afq_collate_multi.hip): sample table, cell table, measure walk, then collate's radix
+// placement, length scan and chunk heads, write walk.
+void afq_collate_multi_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = kCollateRadixBlock;
+}
+
+int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes, uint32_t b1_bytes,
+                          uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed, const uint32_t* sample_index,
+                          uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed, const uint64_t* corr_corrected, uint64_t n_corr,
+                          const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells64, const uint32_t* sample_b0_out, uint64_t n_samples,
+                          uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off, uint32_t** out_nrec, afq_collate_multi_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !out_bytes || !out_n_bytes || !out_chunk_off || !out_nrec) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    // ---- host: widths, orientation, the three inputs; (sample, corrected barcode) -> its index among the cells (afq_gpl_host.h: the CPU suite runs this without a device)
+    std::vector<uint32_t> val;
+    {
+        std::string e;
+        if (int rc = gplhost::collate_multi_index(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, sample_index, n_sample_entries, corr_sample, corr_observed,
+                                                  corr_corrected, n_corr, cell_sample, cell_bc, n_cells64, sample_b0_out, n_samples, val, e))
+            return fail(c, rc, e);
+    }
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    const uint32_t n_cells = (uint32_t)n_cells64;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    hipStream_t s = c->stream;
+    std::vector<uint64_t> ckey(n_corr), chead(n_cells);
+    for (uint64_t i = 0; i < n_corr; ++i) ckey[i] = (uint64_t)corr_sample[i] << 32 | corr_observed[i];
+    for (uint32_t j = 0; j < n_cells; ++j) chead[j] = (uint64_t)sample_b0_out[cell_sample[j]] << 32 | cell_bc[j];
+    // ---- chunk table
+    std::vector<SortChunk> chunks;
+    uint64_t n_slots = 0;
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + b0_bytes + b1_bytes + umi_bytes, chunks, n_slots)) return rc;
+    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
+    const uint32_t n = (uint32_t)n_slots;
+    const uint64_t cap = sort_table_capacity(n_corr), scap = sort_table_capacity(n_sample_entries);
+    const uint32_t tab_mask = (uint32_t)(cap - 1), stab_mask = (uint32_t)(scap - 1);
+    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ncell1 = (uint64_t)n_cells + 1, ncorr1 = std::max<uint64_t>(n_corr, 1),
+                   nse1 = std::max<uint64_t>(n_sample_entries, 1);
+    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock, n_sblocks = (s1 + kCollateScanBlock - 1) / kCollateScanBlock;
+    // does it fit?  (afq_collate_rad's sum, with the sample entries and their table beside the cell table)
+    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_out = (uint64_t)n_bytes + 8 * ncell1, need_rec = s1 * 32 + 8 + n_rblocks * 1024 + n_sblocks * 8,
+                   need_tab = cap * 12 + n_corr * 12 + scap * 12 + n_sample_entries * 12 + ncell1 * 20, need_misc = nc1 * (sizeof(SortChunk) + 32);
+    {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need_out + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_collate_multi_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
+                        std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
+                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->collate;
+    HipLatch T;
+    auto hip_fail = [&]() {
+        return T.fail(c, "afq_collate_multi_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
+    };
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * ncorr1)); T(B.val.ensure(4 * ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
+    T(B.sobs.ensure(8 * nse1)); T(B.sidx.ensure(4 * nse1)); T(B.skey.ensure(8 * scap)); T(B.sval.ensure(4 * scap));
+    T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
+    T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
+    if (!T.ok()) return hip_fail();
+    const uint8_t* d_bytes = nullptr;
+    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_corr) { T(hipMemcpyAsync(B.obs.p, ckey.data(), 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
+    if (n_sample_entries) {
+        T(hipMemcpyAsync(B.sobs.p, sample_observed, 8 * n_sample_entries, hipMemcpyHostToDevice, s));
+        T(hipMemcpyAsync(B.sidx.p, sample_index, 4 * n_sample_entries, hipMemcpyHostToDevice, s));
+    }
+    if (n_cells) T(hipMemcpyAsync(B.cells.p, chead.data(), 8ull * n_cells, hipMemcpyHostToDevice, s));
+    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
+    T(hipMemsetAsync(B.skey.p, 0xFF, 8 * scap, s));
+    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
+    T(hipMemsetAsync(B.ex.p, 0, 8, s));   // (ex[0]; with no record at all it is also ex[n])
+    if (!T.ok()) return hip_fail();
+    reset_kernel_times(c);
+    CollateMultiArgs a{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, b0_bytes, b1_bytes, umi_bytes, c->aln_extra, expected_ori,
+                       B.skey.as<uint64_t>(), B.sval.as<uint32_t>(), stab_mask, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, n_cells,
+                       B.rec.as<uint2>(), B.ka.as<uint64_t>(), B.cstat.as<uint32_t>(), B.cells.as<uint64_t>(), nullptr, nullptr, B.status.as<DevStatus>()};
+    {
+        ScopedTimer t(c, K_COLLATEM_TABLE, s);
+        launch_sort_table(s, B.sobs.as<uint64_t>(), B.sidx.as<uint32_t>(), n_sample_entries, B.skey.as<uint64_t>(), B.sval.as<uint32_t>(), stab_mask, B.status.as<DevStatus>());
+        launch_sort_table(s, B.obs.as<uint64_t>(), B.val.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_COLLATEM_MEASURE, s);
+        launch_collate_multi_measure(s, a);
+    }
+    T(hipGetLastError());
+    DevStatus st{};
+    std::vector<uint32_t> cstat(8ull * n_chunks);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and the tables: the copies out of them are done by now, too)
+    hc.lap("collate multi: tables + measure");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code) return rad_status_fault(c, "afq_collate_multi_rad", st);
+    afq_collate_multi_stats S{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        const uint32_t* q = cstat.data() + 8ull * i;
+        S.n_records += q[0]; S.n_compatible += q[1]; S.n_unrouted += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4]; S.n_alignments_in += q[5]; S.n_alignments_kept += q[6];
+        S.n_long_records += q[7];
+    }
+    // ---- placement, length scan: collate's
+    uint64_t* src = B.ka.as<uint64_t>();
+    uint64_t* dst = B.kb.as<uint64_t>();
+    {
+        ScopedTimer t(c, K_COLLATEM_SORT, s);
+        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
+    }
+    uint64_t kept_bytes = 0;
+    {
+        ScopedTimer t(c, K_COLLATEM_SCAN, s);
+        launch_collate_scan(s, src, B.rec.as<uint2>(), n, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), dst);   // (dst: the buffer the last pass read is free)
+    }
+    T(hipGetLastError());
+    T(hipMemcpyAsync(&kept_bytes, B.ex.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    if (!T.ok()) return hip_fail();
+    const uint64_t out_total = 8ull * n_cells + kept_bytes, o1 = std::max<uint64_t>(out_total, 1);
+    if (out_total > need_out) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: " + std::to_string(out_total) + " bytes of output from " + std::to_string(n_bytes) + " of input"); }
+    T(B.out.ensure(o1));
+    if (!T.ok()) return hip_fail();
+    a.dest = dst; a.out = B.out.as<uint8_t>();
+    {
+        ScopedTimer t(c, K_COLLATEM_SCAN, s);
+        launch_collate_heads(s, src, n, B.ex.as<uint64_t>(), n_cells, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), a.out, B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, K_COLLATEM_WRITE, s);
+        launch_collate_multi_write(s, a);
+    }
+    T(hipGetLastError());
+    HostOuts H;
+    uint8_t* ob = (uint8_t*)H.mallocd(o1);
+    uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
+    uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
+    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_collate_multi_rad: host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
+    if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
+    harvest_timers(c);
+    hc.lap("collate multi: place + write + D2H");
+    if (!T.ok()) return hip_fail();
+    if (st.err_code == kErrCollateChunk)
+        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: cell " + std::to_string(st.err_cell) + " (sample " + std::to_string(cell_sample[st.err_cell]) + ", barcode " +
+                    std::to_string(cell_bc[st.err_cell]) + "): an output chunk of 4 GiB or more");
+    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: device status " + std::to_string(st.err_code) + " in the write");
+    if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
     S.out_bytes = out_total;
     if (stats) *stats = S;
     H.release();

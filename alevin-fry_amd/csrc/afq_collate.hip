@@ -47,18 +47,6 @@ __device__ __forceinline__ uint32_t collate_find(const CollateArgs& a, uint64_t 
     return kSortNoRank;
 }
 
-// the position bytes (e of them: 0, 1, 2, 4 or 8) behind an alignment word: from the tile, from global memory
-__device__ __forceinline__ void put_extra_lds(ByteOut& w, const uint32_t* tile, uint32_t off, uint32_t e) {
-    if (!e) return;
-    w.put(gpl_lds32(tile, off), e < 4 ? e : 4);
-    if (e == 8) w.put(gpl_lds32(tile, off + 4), 4);
-}
-__device__ __forceinline__ void put_extra_glb(ByteOut& w, const uint8_t* bytes, uint64_t n, uint64_t g, uint32_t e) {
-    if (!e) return;
-    w.put(gpl_ld_u32(bytes, n, g), e < 4 ? e : 4);   // (bytes past the buffer read as 0 and are cut off by put)
-    if (e == 8) w.put(gpl_ld_u32(bytes, n, g + 4), 4);
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
     __shared__ uint32_t s_tile[kWalkWaves][kTileWords];

@@ -1,6 +1,7 @@
 // afq_gpl_host.h — the host half of `generate-permit-list` that needs no device: the confidence parser, the barcode-list parser,
 // the knee, the retained-set rules, the neighbourhood a retained barcode generates, and the writers of the five output files; for the
-// multi-barcode step the sample list, the sample index (sources that differ from their targets), the routing entries and the plan's scopes.
+// multi-barcode step the sample list, the sample index (sources that differ from their targets), the routing entries and the plan's scopes;
+// and the checks of multi-barcode collate's device call that precede device work (collate_multi_index).
 // Plain C++, no HIP: afq_host.cpp wraps these into the entry points of include/afquant_host.h, and the CPU suite compiles them on
 // their own (tests/test_gpl_host_cpu.py, under the address and undefined-behaviour sanitizers).  Every function reports through
 // `err` and a negative AFQ_ERR_* code.
@@ -409,6 +410,70 @@ inline int multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_b
         if (i && entries[i] <= entries[i - 1]) return gfail(err, AFQ_ERR_INVALID_ARG, "sample barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
         if (entries[i] >> (8 * b0_bytes)) return gfail(err, AFQ_ERR_BAD_INPUT, "packed sample barcode " + std::to_string(entries[i]) + " does not fit " + std::to_string(b0_bytes) + " bytes");
     }
+    return 0;
+}
+
+// afq_collate_multi_rad's checks and host step, before any device work: widths, orientation, the three inputs.  val[i] = the index
+// among the cells of (corr_sample[i], corr_corrected[i]).  A sample index is below n_samples <= 2^31 (the cell table's key is
+// sample << 32 | b1 and must not be all ones); sample barcodes and (sample, observed cell barcode) pairs are distinct, as are the cells.
+inline int collate_multi_index(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed,
+                               const uint32_t* sample_index, uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed,
+                               const uint64_t* corr_corrected, uint64_t n_corr, const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells,
+                               const uint32_t* sample_b0_out, uint64_t n_samples, std::vector<uint32_t>& val, std::string& err) {
+    if (((!sample_observed || !sample_index) && n_sample_entries) || ((!corr_sample || !corr_observed || !corr_corrected) && n_corr) ||
+        ((!cell_sample || !cell_bc) && n_cells) || (!sample_b0_out && n_samples))
+        return gfail(err, AFQ_ERR_INVALID_ARG, "null argument");
+    if (b0_bytes != 1 && b0_bytes != 2 && b0_bytes != 4) return gfail(err, AFQ_ERR_INVALID_ARG, "b0_bytes must be 1, 2 or 4");
+    if (b1_bytes != 1 && b1_bytes != 2 && b1_bytes != 4) return gfail(err, AFQ_ERR_INVALID_ARG, "b1_bytes must be 1, 2 or 4");
+    if (umi_bytes != 1 && umi_bytes != 2 && umi_bytes != 4 && umi_bytes != 8) return gfail(err, AFQ_ERR_INVALID_ARG, "umi_bytes must be 1, 2, 4 or 8");
+    if (expected_ori > 2) return gfail(err, AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
+    if (n_samples > (1ull << 31)) return gfail(err, AFQ_ERR_INVALID_ARG, "afq_collate_multi_rad: more than 2^31 samples (" + std::to_string(n_samples) + "): a sample index must be below 2^31");
+    if (n_sample_entries >= (1ull << 30) || n_corr >= (1ull << 30)) return gfail(err, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: 2^30 or more correction entries");
+    if (n_cells > 0xFFFFFFFEull) return gfail(err, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: more than 2^32 - 2 cells (" + std::to_string(n_cells) + ")");
+    const uint64_t top0 = b0_bytes < 4 ? (1ull << (8 * b0_bytes)) : (1ull << 32), top1 = b1_bytes < 4 ? (1ull << (8 * b1_bytes)) : (1ull << 32);
+    auto bad_sample = [&](const char* what, uint64_t i, uint32_t s) {
+        return gfail(err, AFQ_ERR_INVALID_ARG, std::string(what) + " " + std::to_string(i) + ": sample index " + std::to_string(s) + " is not below the " + std::to_string(n_samples) +
+                     " samples (a sample index must be below 2^31)");
+    };
+    for (uint64_t s = 0; s < n_samples; ++s)
+        if (sample_b0_out[s] >= top0) return gfail(err, AFQ_ERR_UNSUPPORTED, "sample " + std::to_string(s) + ": the value " + std::to_string(sample_b0_out[s]) + " written into b0 does not fit " + std::to_string(b0_bytes) + " bytes");
+    {
+        std::vector<uint64_t> so(sample_observed, sample_observed + n_sample_entries);
+        std::sort(so.begin(), so.end());
+        for (uint64_t i = 0; i < n_sample_entries; ++i) {
+            if (sample_index[i] >= n_samples) return bad_sample("sample entry", i, sample_index[i]);
+            if (sample_observed[i] >= top0) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode " + std::to_string(sample_observed[i]) + " does not fit " + std::to_string(b0_bytes) + " bytes");
+            if (i && so[i] == so[i - 1]) return gfail(err, AFQ_ERR_BAD_INPUT, "sample barcode " + std::to_string(so[i]) + " occurs twice among the sample entries");
+        }
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> by(n_cells);   // (sample << 32 | barcode, cell)
+    for (uint64_t j = 0; j < n_cells; ++j) {
+        if (cell_sample[j] >= n_samples) return bad_sample("cell", j, cell_sample[j]);
+        if (cell_bc[j] >= top1) return gfail(err, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(j) + ": barcode " + std::to_string(cell_bc[j]) + " does not fit " + std::to_string(b1_bytes) + " bytes");
+        by[j] = {(uint64_t)cell_sample[j] << 32 | cell_bc[j], (uint32_t)j};
+    }
+    std::sort(by.begin(), by.end());
+    for (uint64_t j = 1; j < n_cells; ++j)
+        if (by[j].first == by[j - 1].first)
+            return gfail(err, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by[j - 1].second) + " and " + std::to_string(by[j].second) + " carry one barcode (" + std::to_string(by[j].first & 0xFFFFFFFFull) +
+                         ") in sample " + std::to_string(by[j].first >> 32));
+    val.assign(n_corr, 0);
+    std::vector<uint64_t> keys(n_corr);
+    for (uint64_t i = 0; i < n_corr; ++i) {
+        if (corr_sample[i] >= n_samples) return bad_sample("correction entry", i, corr_sample[i]);
+        if (corr_observed[i] >= top1) return gfail(err, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(corr_observed[i]) + " does not fit " + std::to_string(b1_bytes) + " bytes");
+        keys[i] = (uint64_t)corr_sample[i] << 32 | corr_observed[i];
+        const uint64_t want = (uint64_t)corr_sample[i] << 32 | (corr_corrected[i] & 0xFFFFFFFFull);
+        const auto it = std::lower_bound(by.begin(), by.end(), std::make_pair(want, 0u));
+        if (corr_corrected[i] >= top1 || it == by.end() || it->first != want)
+            return gfail(err, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(corr_observed[i]) + " of sample " + std::to_string(corr_sample[i]) +
+                         " is corrected to " + std::to_string(corr_corrected[i]) + ", which is not a cell of that sample");
+        val[i] = it->second;
+    }
+    std::sort(keys.begin(), keys.end());
+    for (uint64_t i = 1; i < n_corr; ++i)
+        if (keys[i] == keys[i - 1])
+            return gfail(err, AFQ_ERR_BAD_INPUT, "observed barcode " + std::to_string(keys[i] & 0xFFFFFFFFull) + " occurs twice among the corrections of sample " + std::to_string(keys[i] >> 32));
     return 0;
 }
 

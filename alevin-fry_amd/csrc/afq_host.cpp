@@ -950,6 +950,76 @@ int64_t afq_parse_correction_plan(const uint8_t* in, size_t n, uint64_t* observe
     return (int64_t)n_global;
 }
 
+namespace {
+// a SAMPLE-SCOPED correction plan (what multi-barcode generate-permit-list writes): the sample corrections and, per cell scope
+// that names a sample, the canonical sample barcode and its corrections, in file order
+struct MultiPlanScope { uint64_t sample_barcode; std::vector<uint64_t> obs, cor; };
+struct MultiPlan {
+    uint32_t sample_len = 0, cell_len = 0;
+    std::vector<uint64_t> sample_obs, sample_cor;
+    std::vector<MultiPlanScope> scopes;
+};
+int parse_plan_multi(const uint8_t* in, size_t n, MultiPlan& P) {
+    static const uint8_t kMagic[8] = {'A', 'F', 'C', 'O', 'R', 'R', 0, 0};
+    if (n < 8) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has a truncated header");
+    if (std::memcmp(in, kMagic, 8) != 0) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has invalid magic");
+    Cursor c{in, n};
+    c.p = 8;
+    const uint16_t ver = c.get<uint16_t>();
+    if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "correction plan has a truncated header");
+    if (ver != 1) return hfail(AFQ_ERR_BAD_INPUT, "correction plan uses unsupported format version " + std::to_string(ver) + " (expected 1)");
+    const char* trunc = "could not deserialize correction plan: the file is truncated or malformed";
+    const uint8_t has_sample = c.get<uint8_t>();
+    if (!c.ok || has_sample > 1) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    if (has_sample) P.sample_len = c.get<uint8_t>();
+    P.cell_len = c.get<uint8_t>();
+    const uint8_t has_sspec = c.get<uint8_t>();
+    if (!c.ok || has_sspec > 1 || (has_sspec && !skip_correction_spec(c))) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    auto take = [&](std::vector<uint64_t>& obs, std::vector<uint64_t>& cor) {
+        const size_t at = c.p;
+        uint64_t cnt = 0;
+        if (!take_corrections(c, cnt, nullptr, nullptr, 0, false)) return false;
+        obs.resize((size_t)cnt); cor.resize((size_t)cnt);
+        c.p = at;
+        return take_corrections(c, cnt, obs.data(), cor.data(), (size_t)cnt, true);
+    };
+    if (!take(P.sample_obs, P.sample_cor)) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    const uint64_t n_scopes = c.get<uint64_t>();
+    if (!c.ok || n_scopes > c.n) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+    for (uint64_t i = 0; i < n_scopes; ++i) {
+        const uint8_t has_bc = c.get<uint8_t>();
+        if (!c.ok || has_bc > 1) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+        MultiPlanScope sc{};
+        if (has_bc) sc.sample_barcode = c.get<uint64_t>();
+        if (!skip_correction_spec(c) || !take(sc.obs, sc.cor)) return hfail(AFQ_ERR_BAD_INPUT, trunc);
+        if (has_bc) P.scopes.push_back(std::move(sc));   // (a global scope routes nothing here: collate.rs:1766-1771)
+    }
+    if (c.p != c.n) return hfail(AFQ_ERR_BAD_INPUT, "correction plan contains trailing data");
+    if (!has_sample) return hfail(AFQ_ERR_BAD_INPUT, "correction plan does not match this multi-barcode RAD input: it is not sample-scoped");   // collate.rs:1520-1524
+    return 0;
+}
+}  // namespace
+
+int64_t afq_parse_correction_plan_multi(const uint8_t* in, size_t n, uint64_t* sample_observed, uint64_t* sample_corrected, size_t sample_cap, uint64_t* n_sample,
+                                        uint64_t* scope_barcode, uint64_t* scope_count, size_t scope_cap, uint64_t* n_scopes, uint64_t* cell_observed,
+                                        uint64_t* cell_corrected, size_t cell_cap, uint32_t* sample_barcode_len, uint32_t* cell_barcode_len) {
+    if (!in && n) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+    MultiPlan P;
+    if (int rc = parse_plan_multi(in, n, P)) return rc;
+    for (size_t i = 0; i < P.sample_obs.size() && i < sample_cap; ++i) { if (sample_observed) sample_observed[i] = P.sample_obs[i]; if (sample_corrected) sample_corrected[i] = P.sample_cor[i]; }
+    uint64_t total = 0;
+    for (size_t s = 0; s < P.scopes.size(); ++s) {
+        if (s < scope_cap) { if (scope_barcode) scope_barcode[s] = P.scopes[s].sample_barcode; if (scope_count) scope_count[s] = P.scopes[s].obs.size(); }
+        for (size_t i = 0; i < P.scopes[s].obs.size(); ++i, ++total)
+            if (total < cell_cap) { if (cell_observed) cell_observed[total] = P.scopes[s].obs[i]; if (cell_corrected) cell_corrected[total] = P.scopes[s].cor[i]; }
+    }
+    if (n_sample) *n_sample = P.sample_obs.size();
+    if (n_scopes) *n_scopes = P.scopes.size();
+    if (sample_barcode_len) *sample_barcode_len = P.sample_len;
+    if (cell_barcode_len) *cell_barcode_len = P.cell_len;
+    return (int64_t)total;
+}
+
 int64_t afq_parse_permit_map(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap) {
     if (!in && n) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
     Cursor c{in, n};
@@ -1262,7 +1332,7 @@ int afq_collate(const afq_collate_opts* o) {
     auto is_true = [&](size_t v) { return v != std::string::npos && gjs.compare(v, 4, "true") == 0; };
     if (value_at("version_str") == std::string::npos)
         return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
-    if (is_true(value_at("multi_barcode"))) return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode permit lists (multi_barcode: true) are not supported");
+    if (is_true(value_at("multi_barcode"))) return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode permit lists (multi_barcode: true) are not supported; use afq_collate_multi");
     if (is_true(value_at("velo_mode"))) return hfail(AFQ_ERR_UNSUPPORTED, "collate: velo_mode: true is not supported");
     uint32_t expected_ori = 0;
     {
@@ -1294,7 +1364,7 @@ int afq_collate(const afq_collate_opts* o) {
     if (rc) return rc;
     auto has_tag = [](const std::vector<TagDesc>& v, const char* name) { for (auto& t : v) if (t.name == name) return true; return false; };
     if (P.file_tag_vals.count("num_barcodes") && P.file_tag_vals["num_barcodes"] > 1)
-        return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode RAD files (num_barcodes > 1) are not supported");
+        return hfail(AFQ_ERR_UNSUPPORTED, "collate: multi-barcode RAD files (num_barcodes > 1) are not supported; use afq_collate_multi");
     if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len"))
         return hfail(AFQ_ERR_UNSUPPORTED, "collate: this is a scATAC RAD file; use `atac collate`");
     if (has_tag(P.aln_tags, "as") && has_tag(P.aln_tags, "start") && has_tag(P.aln_tags, "end"))
@@ -1416,6 +1486,290 @@ int afq_atac_collate(const afq_atac_collate_opts* o) {
     if (st.n_cells_empty)   // atac/collate.rs:884-892
         std::fprintf(stderr, "%llu of %llu retained barcodes produced no collated records (every read was unmapped or multi-mapping) and are absent from the output.\n",
                      (unsigned long long)st.n_cells_empty, (unsigned long long)cells.size());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// multi-barcode `collate` (do_collate_multi_bc_fast, src/collate.rs:1415-1920).  libradicl's collate_multi_barcode is not among the
+// reference's sources; where collate.rs leaves a rule to it, the choice is DESIGN.md 3.4h's.
+namespace {
+struct ManifestGroup { uint64_t key; std::string name; uint64_t chunk_start, num_chunks, num_records; };
+// collation_manifest.bin in the layout parse_collation_manifest (below) reads: level names sample, cell; every group is named
+void collation_manifest_bytes(const std::vector<ManifestGroup>& groups, std::vector<uint8_t>& out) {
+    out.clear();
+    auto u64 = [&](uint64_t v) { const uint8_t* p = (const uint8_t*)&v; out.insert(out.end(), p, p + 8); };
+    auto str = [&](const std::string& s) { u64(s.size()); out.insert(out.end(), s.begin(), s.end()); };
+    u64(2); str("sample"); str("cell");
+    u64(groups.size());
+    for (auto& g : groups) { u64(g.key); out.push_back(1); str(g.name); u64(g.chunk_start); u64(g.num_chunks); u64(g.num_records); }
+}
+// a JSON string at js[at] (the opening quote) -> its text; false: not a string, or an escape this reader does not know
+bool json_string_at(const std::string& js, size_t at, std::string& out) {
+    if (at == std::string::npos || at >= js.size() || js[at] != '"') return false;
+    out.clear();
+    for (size_t i = at + 1; i < js.size(); ++i) {
+        const char ch = js[i];
+        if (ch == '"') return true;
+        if (ch != '\\') { out.push_back(ch); continue; }
+        if (++i >= js.size()) return false;
+        switch (js[i]) {
+            case '"': case '\\': case '/': out.push_back(js[i]); break;
+            case 'n': out.push_back('\n'); break;
+            case 't': out.push_back('\t'); break;
+            case 'r': out.push_back('\r'); break;
+            default: return false;
+        }
+    }
+    return false;
+}
+// sample_info.json (collate.rs:1480-1561): num_samples, and name and canonical barcode of every entry of `samples`, in file order
+int read_sample_info(const std::string& path, uint64_t& num_samples, std::vector<std::string>& names, std::vector<uint64_t>& barcodes) {
+    std::vector<uint8_t> raw;
+    if (!read_file(path, raw)) return hfail(AFQ_ERR_BAD_INPUT, "could not open sample_info.json - was generate-permit-list run with --sample-bc-list?");
+    const std::string js(raw.begin(), raw.end());
+    {
+        const size_t v = json_top_level_value(js, "num_samples");
+        char* e = nullptr;
+        if (v != std::string::npos) num_samples = std::strtoull(js.c_str() + v, &e, 10);
+        if (v == std::string::npos || e == js.c_str() + v) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read num_samples from sample_info.json");
+    }
+    const size_t a = json_top_level_value(js, "samples");
+    if (a == std::string::npos || js[a] != '[') return hfail(AFQ_ERR_BAD_INPUT, "couldn't read samples array from sample_info.json");
+    int depth = 0;
+    size_t obj = 0;
+    for (size_t i = a; i < js.size(); ++i) {
+        const char ch = js[i];
+        if (ch == '"') { for (++i; i < js.size() && js[i] != '"'; ++i) if (js[i] == '\\') ++i; continue; }
+        if (ch == '{' || ch == '[') { if (++depth == 2 && ch == '{') obj = i; continue; }
+        if (ch != '}' && ch != ']') continue;
+        if (--depth == 0) break;
+        if (depth != 1 || ch != '}') continue;
+        const std::string o = js.substr(obj, i + 1 - obj);
+        std::string bc = "0x0", nm;   // collate.rs:1551-1560
+        json_string_at(o, json_top_level_value(o, "barcode"), bc);
+        size_t h = 0;
+        while (bc.compare(h, 2, "0x") == 0) h += 2;   // trim_start_matches("0x"): the pattern as often as it leads
+        char* e = nullptr;
+        const std::string hex = bc.substr(h);
+        uint64_t v = hex.empty() ? 0 : std::strtoull(hex.c_str(), &e, 16);
+        if (hex.empty() || !e || *e) v = 0;
+        if (!json_string_at(o, json_top_level_value(o, "name"), nm)) { char hx[32]; std::snprintf(hx, sizeof hx, "%llx", (unsigned long long)v); nm = hx; }
+        names.push_back(nm); barcodes.push_back(v);
+    }
+    if (depth != 0) return hfail(AFQ_ERR_BAD_INPUT, "couldn't read samples array from sample_info.json");
+    return 0;
+}
+}  // namespace
+
+int64_t afq_collation_manifest_bytes(const uint64_t* key, const char* const* name, const uint64_t* chunk_start, const uint64_t* num_chunks, const uint64_t* num_records,
+                                     uint64_t n_groups, uint8_t* out, size_t cap) {
+    if ((!key || !name || !chunk_start || !num_chunks || !num_records) && n_groups) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+    std::vector<ManifestGroup> g;
+    for (uint64_t i = 0; i < n_groups; ++i) {
+        if (!name[i]) return hfail(AFQ_ERR_INVALID_ARG, "null argument");
+        g.push_back(ManifestGroup{key[i], name[i], chunk_start[i], num_chunks[i], num_records[i]});
+    }
+    std::vector<uint8_t> b;
+    collation_manifest_bytes(g, b);
+    if (out && cap >= b.size()) std::memcpy(out, b.data(), b.size());
+    return (int64_t)b.size();
+}
+
+int afq_collate_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed,
+                                 const uint32_t* sample_index, uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed,
+                                 const uint64_t* corr_corrected, uint64_t n_corrections, const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells,
+                                 const uint32_t* sample_b0_out, uint64_t n_samples) {
+    std::string e;
+    std::vector<uint32_t> val;
+    const int r = afq::gplhost::collate_multi_index(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, sample_index, n_sample_entries, corr_sample, corr_observed,
+                                                    corr_corrected, n_corrections, cell_sample, cell_bc, n_cells, sample_b0_out, n_samples, val, e);
+    return r ? hfail(r, e) : 0;
+}
+
+int afq_collate_multi(const afq_collate_multi_opts* o) {
+    if (!o || !o->input_dir) return hfail(AFQ_ERR_INVALID_ARG, "null option");
+    if (!o->rad_dir) return hfail(AFQ_ERR_INVALID_ARG, "the RAD directory (-r) is required");
+    if (o->compress) return hfail(AFQ_ERR_UNSUPPORTED, "compressed output is not supported");
+    const std::string in = o->input_dir, rd = o->rad_dir;
+    // ---- generate_permit_list.json (collate.rs:155-200)
+    std::vector<uint8_t> gj;
+    if (!read_file(in + "/generate_permit_list.json", gj)) return hfail(AFQ_ERR_BAD_INPUT, "could not open generate_permit_list.json in \"" + in + "\"");
+    const std::string gjs(gj.begin(), gj.end());
+    auto value_at = [&](const char* key) { return json_top_level_value(gjs, key); };
+    auto is_true = [&](size_t v) { return v != std::string::npos && gjs.compare(v, 4, "true") == 0; };
+    if (value_at("version_str") == std::string::npos)
+        return hfail(AFQ_ERR_BAD_INPUT, "The generate_permit_list.json file does not contain a version_str field. Please re-run the generate-permit-list step with a newer version of alevin-fry");
+    if (!is_true(value_at("multi_barcode"))) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: this is a single-barcode permit list (no multi_barcode: true); use collate");
+    if (is_true(value_at("velo_mode"))) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: velo_mode: true is not supported");
+    uint32_t expected_ori = 0;
+    {
+        const size_t v = value_at("expected_ori");
+        static const char* const kSym[3] = {"\"both\"", "\"fw\"", "\"rc\""};
+        uint32_t k = 0;
+        while (k < 3 && (v == std::string::npos || gjs.compare(v, std::strlen(kSym[k]), kSym[k]) != 0)) ++k;
+        if (k == 3) return hfail(AFQ_ERR_BAD_INPUT, "could not read strand: generate_permit_list.json: expected_ori must be \"both\", \"fw\" or \"rc\"");
+        expected_ori = k;
+    }
+    // ---- sample_info.json, the cells of every sample (collate.rs:1480-1611)
+    uint64_t num_samples = 0;
+    std::vector<std::string> names;
+    std::vector<uint64_t> canon;
+    if (int rc2 = read_sample_info(in + "/sample_info.json", num_samples, names, canon)) return rc2;
+    const size_t n_plate = names.size();
+    if (n_plate > (1ull << 31)) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: more than 2^31 samples");
+    {
+        std::vector<uint64_t> sorted = canon;
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t i = 1; i < sorted.size(); ++i)
+            if (sorted[i] == sorted[i - 1]) { char hx[32]; std::snprintf(hx, sizeof hx, "0x%llx", (unsigned long long)sorted[i]); return hfail(AFQ_ERR_BAD_INPUT, std::string("sample_info.json lists the sample barcode ") + hx + " twice"); }
+    }
+    std::vector<uint32_t> cell_sample, b0_out(n_plate, 0);
+    std::vector<uint64_t> cell_bc;
+    std::vector<ManifestGroup> groups;
+    std::vector<char> has_cells(n_plate, 0);
+    for (size_t si = 0; si < n_plate; ++si) {
+        const std::string sdir = in + "/sample_" + names[si];
+        if (!file_exists(sdir + "/permit_freq.bin")) continue;   // a sample without a read (collate.rs:1604-1607)
+        std::vector<uint64_t> cells;   // by (count descending, barcode ascending): collate.rs:1611 within a sample
+        uint64_t bc_len = 0, recs = 0;
+        const std::string bad_len = "couldn't deserialize " + sdir + "/permit_freq.bin: its length does not match its entry count";
+        if (int rc2 = read_permit_cells(sdir, bad_len.c_str(), bc_len, cells, &recs)) return rc2;
+        if (cells.empty()) continue;
+        has_cells[si] = 1;
+        b0_out[si] = (uint32_t)groups.size();   // the dense ordinal (collate.rs:1630-1638)
+        groups.push_back(ManifestGroup{canon[si], names[si], (uint64_t)cell_bc.size(), cells.size(), recs});
+        for (uint64_t b : cells) { cell_sample.push_back((uint32_t)si); cell_bc.push_back(b); }
+    }
+    // ---- the plan (collate.rs:1517-1532)
+    if (!file_exists(in + "/correction_plan.bin"))
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: no correction_plan.bin in \"" + in + "\": the reference then corrects cell barcodes on the fly (libradicl's Hamming-1 "
+                     "lookup), which is not restated here; rerun generate-permit-list");
+    MultiPlan plan;
+    {
+        std::vector<uint8_t> cm;
+        if (!read_file(in + "/correction_plan.bin", cm)) return hfail(AFQ_ERR_BAD_INPUT, "could not open correction plan " + in + "/correction_plan.bin");
+        if (int rc2 = parse_plan_multi(cm.data(), cm.size(), plan)) return rc2;
+    }
+    // ---- map.rad: the prelude checks of afq_generate_permit_list_multi
+    if (!file_exists(rd)) return hfail(AFQ_ERR_BAD_INPUT, "the input RAD path \"" + rd + "\" does not exist");
+    PhaseClock pc;
+    MappedFile mf;
+    if (!mf.open(rd + "/map.rad")) return hfail(AFQ_ERR_BAD_INPUT, "couldn't open input RAD file");
+    const uint8_t* rad = mf.p;
+    const size_t rad_n = mf.n;
+    RadPrelude P;
+    int rc = parse_prelude(rad, rad_n, P, false);
+    if (rc) return rc;
+    auto has_tag = [](const std::vector<TagDesc>& v, const char* name) { for (auto& t : v) if (t.name == name) return true; return false; };
+    if (has_tag(P.aln_tags, "start_pos") || has_tag(P.aln_tags, "frag_len")) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: this is a scATAC RAD file; use `atac collate`");
+    if (!P.file_tag_vals.count("num_barcodes") || P.file_tag_vals["num_barcodes"] <= 1)
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: this is a single-barcode RAD file (no num_barcodes > 1 file tag); use collate");
+    if (has_tag(P.aln_tags, "pos")) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD records with alignment positions (alignment tag pos) are not supported");
+    if (P.file_tag_vals["num_barcodes"] != 2 || P.read_tags.size() != 3 || P.read_tags[0].name != "b0" || P.read_tags[1].name != "b1" || P.read_tags[2].name != "u")
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: only two barcode levels with read tags (b0, b1, u) are supported");
+    const uint32_t w0 = (uint32_t)int_type_bytes(P.read_tags[0].type), w1 = (uint32_t)int_type_bytes(P.read_tags[1].type), wu = (uint32_t)int_type_bytes(P.read_tags[2].type);
+    if (!w0 || !w1 || w0 > 4 || w1 > 4 || !wu) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: b0 and b1 must be integers of 1, 2 or 4 bytes (u8/u16/u32)");
+    if (P.aln_tags.size() != 1 || P.aln_tags[0].type != 3) return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode RAD: the alignment-level tags must be one u32 (ref | orientation)");
+    if (!P.file_tag_vals.count("b1len")) return hfail(AFQ_ERR_BAD_INPUT, "multi-barcode RAD file should have a \"b1len\" file-level tag");
+    const uint32_t cblen = (uint32_t)P.file_tag_vals["b1len"];
+    if (cblen < 1 || cblen > 32) return hfail(AFQ_ERR_BAD_INPUT, "barcode length must be between 1 and 32 (got " + std::to_string(cblen) + ")");
+    {   // collate.rs:1495-1515
+        uint32_t sbits = 0;
+        while (num_samples > 1 && sbits < 64 && ((num_samples - 1) >> sbits)) ++sbits;
+        if (sbits + 2 * cblen > 64)
+            return hfail(AFQ_ERR_UNSUPPORTED, "Cannot collate: " + std::to_string(num_samples) + " samples requires " + std::to_string(sbits) + " bits for the sample index, plus " +
+                         std::to_string(2 * cblen) + " bits for " + std::to_string(cblen) + "bp cell barcodes = " + std::to_string(sbits + 2 * cblen) +
+                         " bits total, which exceeds the 64-bit composite key capacity.");
+    }
+    if (plan.cell_len != cblen) return hfail(AFQ_ERR_BAD_INPUT, "correction plan does not match this multi-barcode RAD input");
+    if (!groups.empty() && w0 < 4 && (groups.size() - 1) >> (8 * w0))
+        return hfail(AFQ_ERR_UNSUPPORTED, "multi-barcode collate: the largest sample ordinal (" + std::to_string(groups.size() - 1) + ") does not fit the " + std::to_string(w0) + "-byte b0 field of the records");
+    // ---- the two lookups: observed sample barcode -> plate index (collate.rs:1754-1761); per sample with cells, its scope's corrections
+    const uint64_t top0 = 1ull << (8 * w0), top1 = 1ull << (8 * w1);   // (a key that does not fit its field meets no record)
+    std::vector<std::pair<uint64_t, uint32_t>> plate(n_plate);
+    for (size_t si = 0; si < n_plate; ++si) plate[si] = {canon[si], (uint32_t)si};
+    std::sort(plate.begin(), plate.end());
+    auto plate_of = [&](uint64_t bc) -> int64_t {
+        const auto it = std::lower_bound(plate.begin(), plate.end(), std::make_pair(bc, 0u));
+        return it != plate.end() && it->first == bc ? (int64_t)it->second : -1;
+    };
+    std::vector<uint64_t> s_obs;
+    std::vector<uint32_t> s_idx;
+    for (size_t i = 0; i < plan.sample_obs.size(); ++i) {
+        const int64_t si = plate_of(plan.sample_cor[i]);
+        if (si >= 0 && plan.sample_obs[i] < top0) { s_obs.push_back(plan.sample_obs[i]); s_idx.push_back((uint32_t)si); }
+    }
+    std::vector<uint32_t> c_sample;
+    std::vector<uint64_t> c_obs, c_cor;
+    std::vector<char> scoped(n_plate, 0);
+    for (auto& sc : plan.scopes) {
+        const int64_t si = plate_of(sc.sample_barcode);
+        if (si < 0) continue;
+        scoped[(size_t)si] = 1;
+        for (size_t i = 0; i < sc.obs.size(); ++i)
+            if (sc.obs[i] < top1) { c_sample.push_back((uint32_t)si); c_obs.push_back(sc.obs[i]); c_cor.push_back(sc.cor[i]); }
+    }
+    for (size_t si = 0; si < n_plate; ++si)
+        if (has_cells[si] && !scoped[si]) { char hx[32]; std::snprintf(hx, sizeof hx, "0x%llx", (unsigned long long)canon[si]); return hfail(AFQ_ERR_BAD_INPUT, std::string("correction plan has no cell scope for canonical sample ") + hx); }
+    {   // afq_collate_multi_rad's own checks, before the device is opened: a correction into a barcode that is no cell of its sample is refused here
+        std::string e;
+        std::vector<uint32_t> val;
+        if (int rc2 = afq::gplhost::collate_multi_index(w0, w1, wu, expected_ori, s_obs.data(), s_idx.data(), s_obs.size(), c_sample.data(), c_obs.data(), c_cor.data(), c_obs.size(),
+                                                        cell_sample.data(), cell_bc.data(), cell_bc.size(), b0_out.data(), n_plate, val, e))
+            return hfail(rc2, e);
+    }
+    // ---- the chunk table
+    std::vector<uint64_t> chunk_off;
+    if (int rc2 = walk_chunk_offsets(rad, rad_n, P.first_chunk, P.num_chunks, chunk_off)) return rc2;
+    if (chunk_off.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "2^32 or more chunks");
+    pc.lap("metadata + plan + chunk table");
+    // ---- the device: one fill
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
+    const uint64_t span0 = chunk_off.empty() ? P.first_chunk : chunk_off[0];
+    std::vector<uint64_t> rel;
+    rebase_chunk_offsets(chunk_off, span0, rel);
+    uint8_t* ob = nullptr; uint64_t on = 0, *ooff = nullptr; uint32_t* onrec = nullptr;
+    afq_collate_multi_stats st{};
+    rc = afq_collate_multi_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), w0, w1, wu, expected_ori, 0, s_obs.data(), s_idx.data(), s_obs.size(),
+                               c_sample.data(), c_obs.data(), c_cor.data(), c_obs.size(), cell_sample.data(), cell_bc.data(), cell_bc.size(), b0_out.data(), n_plate, &ob, &on,
+                               &ooff, &onrec, &st);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer { void *a, *b, *c; ~Freer() { afq_free(a); afq_free(b); afq_free(c); } } fr{ob, ooff, onrec};
+    pc.lap("device: collate");
+    if (o->stats_out) *o->stats_out = st;
+    // ---- per sample: the records kept are the sample's collatable reads (nothing was written yet, so no RAD is left behind)
+    for (auto& g : groups) {
+        uint64_t kept = 0;
+        for (uint64_t j = g.chunk_start; j < g.chunk_start + g.num_chunks; ++j) kept += onrec[j];
+        if (kept != g.num_records)
+            return hfail(AFQ_ERR_BAD_INPUT, "sample '" + g.name + "': expected to collate " + std::to_string(g.num_records) + " records but retained " + std::to_string(kept));
+    }
+    // ---- the files
+    if (int rc2 = write_collated_rad(in + "/map.collated.rad", rad, P, cell_bc.size(), ob, on)) return rc2;
+    {
+        std::vector<uint8_t> mb;
+        collation_manifest_bytes(groups, mb);
+        FilePtr f(std::fopen((in + "/collation_manifest.bin").c_str(), "wb"));
+        if (!f || std::fwrite(mb.data(), 1, mb.size(), f.get()) != mb.size()) return hfail(AFQ_ERR_BAD_INPUT, "could not write collation_manifest.bin");
+    }
+    {   // an empty map, in the layout afq_quantify reads (collate.rs:364-381: what the reference writes when it cannot read the input's header)
+        FilePtr f(std::fopen((in + "/unmapped_bc_count_collated.bin").c_str(), "wb"));
+        const uint64_t zero = 0;
+        if (!f || std::fwrite(&zero, 8, 1, f.get()) != 1) return hfail(AFQ_ERR_BAD_INPUT, "could not create serialization file.");
+    }
+    {   // collate.json (collate.rs:1668-1676)
+        FilePtr f(std::fopen((in + "/collate.json").c_str(), "w"));
+        if (!f) return hfail(AFQ_ERR_BAD_INPUT, "could not create metadata file.");
+        std::fprintf(f.get(), "{\n  \"cmd\": \"%s\",\n  \"version_str\": \"0.18.0\",\n  \"compressed_output\": false,\n  \"multi_barcode\": true,\n  \"num_samples\": %llu,\n"
+                     "  \"collation_mode\": \"optimized\",\n  \"memory_budget_bytes\": 0\n}", json_escape(o->cmdline ? o->cmdline : "").c_str(), (unsigned long long)num_samples);
+    }
+    pc.lap("map.collated.rad");
+    std::fprintf(stderr, "collated %llu of %llu records (%llu orientation consistent, %llu with no sample, %llu with a cell barcode that is not in its sample's map) into %llu cells of %llu samples\n",
+                 (unsigned long long)st.n_kept, (unsigned long long)st.n_records, (unsigned long long)st.n_compatible, (unsigned long long)st.n_unrouted,
+                 (unsigned long long)st.n_uncorrected, (unsigned long long)cell_bc.size(), (unsigned long long)groups.size());
+    std::fprintf(stderr, "kept %llu of %llu alignments; %llu output bytes\n", (unsigned long long)st.n_alignments_kept, (unsigned long long)st.n_alignments_in,
+                 (unsigned long long)st.out_bytes);
     return 0;
 }
 

@@ -336,6 +336,26 @@ void launch_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, con
                           DevStatus* st);
 // in-place exclusive scan of n words by one workgroup (the radix passes' digit counts; `atac collate`'s non-empty-cell flags)
 void launch_collate_excl_scan_u32(hipStream_t s, uint32_t* v, uint64_t n);
+// multi-barcode `collate`: the records `na, b0, b1, umi, alignments` of an uncollated two-barcode RNA RAD, routed to a sample by b0 and
+// corrected to a cell of that sample by b1, one output chunk per cell (afq_collate_multi.hip).  The walk and its limits are collate's;
+// both tables are launch_sort_table's (no key is all-ones: b0 and b1 have at most 4 bytes and a sample index is below 2^31); placement,
+// length scan and heads are launch_collate_radix_pass / launch_collate_scan / launch_collate_heads.
+struct CollateMultiArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const SortChunk* chunks; uint32_t n_chunks;
+    uint32_t b0_bytes, b1_bytes, umi_bytes, aln_extra, expected_ori;
+    const uint64_t* stab_key; const uint32_t* stab_val; uint32_t stab_mask;   // observed b0 -> sample index
+    const uint64_t* ctab_key; const uint32_t* ctab_val; uint32_t ctab_mask;   // sample index << 32 | observed b1 -> index of the corrected barcode among the cells
+    uint32_t n_cells;        // (also the cell word of a record that is dropped: it sorts behind every cell)
+    uint2* rec;              // a slot per record of the chunk table, in input order: (cell, bytes of the record as written)
+    uint64_t* key;           // measure: cell << 32 | slot of every slot
+    uint32_t* chunk_stat;    // measure: [n_chunks][8]: records, compatible, unrouted, routed but not in the sample's map, kept, alignments in, alignments kept, long records
+    const uint64_t* cell_head;   // write: [n_cells] the value written into b0 << 32 | the corrected cell barcode
+    const uint64_t* dest;    // write: [slot] byte offset of the record in `out`
+    uint8_t* out;
+    DevStatus* st;
+};
+void launch_collate_multi_measure(hipStream_t s, const CollateMultiArgs& a);
+void launch_collate_multi_write(hipStream_t s, const CollateMultiArgs& a);
 // `atac collate`: the records of an UNCOLLATED scATAC RAD with exactly one alignment and a barcode of the correction map, barcode-
 // corrected, one output chunk per cell THAT RECEIVED A RECORD (afq_atac_collate.hip).  The walk is k_sort_parse's (kSortParseTile,
 // kSortParseHalo), the placement collate's radix passes; a kept record is R = 4 + bc_bytes + 11 bytes, so the layout needs no length scan.

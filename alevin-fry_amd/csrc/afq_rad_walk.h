@@ -1,7 +1,7 @@
 // afq_rad_walk.h — what the wave-per-chunk walks of an uncollated RNA RAD share (k_gpl_parse, afq_gpl.hip; k_gpl_multi_parse,
-// afq_gpl_multi.hip; the collate walks, afq_collate.hip; the scATAC collate walks, afq_atac_collate.hip): checked loads of the input
+// afq_gpl_multi.hip; the collate walks, afq_collate.hip and afq_collate_multi.hip; the scATAC collate walks, afq_atac_collate.hip): checked loads of the input
 // buffer, unaligned reads of the LDS tile, the wave's LDS fence, the orientation test, rad_walk_chunk (the whole GPL walk as a
-// template over what is read of a record's head), and ByteOut, the byte stream both collate write walks store through.
+// template over what is read of a record's head), and ByteOut, the byte stream the collate write walks store through.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -156,5 +156,16 @@ struct ByteOut {
     }
     __device__ __forceinline__ void flush() { while (n) step(); }
 };
+// the position bytes (e of them: 0, 1, 2, 4 or 8) behind an alignment word, into the stream: from the tile, from global memory
+__device__ __forceinline__ void put_extra_lds(ByteOut& w, const uint32_t* tile, uint32_t off, uint32_t e) {
+    if (!e) return;
+    w.put(gpl_lds32(tile, off), e < 4 ? e : 4);
+    if (e == 8) w.put(gpl_lds32(tile, off + 4), 4);
+}
+__device__ __forceinline__ void put_extra_glb(ByteOut& w, const uint8_t* bytes, uint64_t n, uint64_t g, uint32_t e) {
+    if (!e) return;
+    w.put(gpl_ld_u32(bytes, n, g), e < 4 ? e : 4);   // (bytes past the buffer read as 0 and are cut off by put)
+    if (e == 8) w.put(gpl_ld_u32(bytes, n, g + 4), 4);
+}
 
 }  // namespace afq

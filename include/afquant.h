@@ -484,6 +484,51 @@ int afq_collate_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const ui
 void afq_collate_limits(uint32_t out[4]);
 
 /*
+ * multi-barcode `collate`, the device half (do_collate_multi_bc_fast, src/collate.rs:1415-1920 of the reference): the records
+ * `na, b0, b1, umi, alignments` of an UNCOLLATED two-barcode RNA RAD routed to a sample by b0, corrected to a cell of that sample
+ * by b1, and written as one chunk per cell.
+ *
+ * `bytes` / `chunk_off` / the record layout / expected_ori are afq_gpl_multi_hist_rad's; the context's aln_extra counts as there.
+ * Three inputs, all in terms of a SAMPLE INDEX below n_samples (<= 2^31):
+ *   sample table   sample_observed[i] (a b0 value, distinct) -> sample_index[i]                          (n_sample_entries)
+ *   cell table     (corr_sample[i], corr_observed[i]) (distinct pairs) -> corr_corrected[i], which must be a cell of that sample
+ *   cells          (cell_sample[j], cell_bc[j]) (distinct pairs) IN OUTPUT ORDER; sample_b0_out[s] is the value written into b0
+ *                  for a record of sample s and must fit b0_bytes
+ *
+ * A record is kept iff it is compatible with expected_ori (afq_collate_rad's rule), its b0 is a key of the sample table, and its
+ * b1 is an observed key of that sample.  It is written as na' = the number of fitting alignments, b0 = sample_b0_out[sample],
+ * b1 = the corrected cell barcode, the UMI unchanged, and the fitting alignment words untouched in input order.
+ *
+ * Out: as afq_collate_rad - the n_cells chunks back to back (a cell without a record is a header-only chunk), out_chunk_off
+ * [n_cells + 1], out_nrec[n_cells]; inside a chunk the records stand in input order, so the output is a function of the input alone.
+ *
+ * AFQ_ERR_INVALID_ARG: a null pointer, a width that is not 1, 2 or 4 (the UMI: 1, 2, 4 or 8), a bad expected_ori, a sample index
+ * that is not below n_samples, n_samples above 2^31.  AFQ_ERR_BAD_INPUT: a value that does not fit its width, a duplicate key in
+ * either table or among the cells, a correction into a barcode that is no cell of its sample, a chunk whose records do not tile it.
+ * AFQ_ERR_UNSUPPORTED: a sample_b0_out value that does not fit b0_bytes, afq_collate_rad's size limits.  AFQ_ERR_OOM (with the
+ * sizes) when input, output, 32 bytes a record and the tables do not fit the device: one call is one device fill.
+ */
+typedef struct afq_collate_multi_stats {
+    uint64_t n_records;          /* records of the chunks                                                     */
+    uint64_t n_compatible;       /* ... compatible with expected_ori                                          */
+    uint64_t n_unrouted;         /* ... of those, with a b0 that is no key of the sample table                */
+    uint64_t n_uncorrected;      /* ... routed, with a b1 that has no correction in that sample               */
+    uint64_t n_kept;             /* records written (= n_compatible - n_unrouted - n_uncorrected)             */
+    uint64_t n_alignments_in;    /* alignments of all records                                                 */
+    uint64_t n_alignments_kept;  /* alignments written                                                        */
+    uint64_t n_long_records;     /* records with more than afq_collate_multi_limits()[2] alignments           */
+    uint64_t out_bytes;          /* length of out_bytes                                                       */
+} afq_collate_multi_stats;
+int afq_collate_multi_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes,
+                          uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed,
+                          const uint32_t* sample_index, uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed,
+                          const uint64_t* corr_corrected, uint64_t n_corrections, const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells,
+                          const uint32_t* sample_b0_out, uint64_t n_samples, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off,
+                          uint32_t** out_nrec, afq_collate_multi_stats* stats);
+/* afq_collate_limits' four values, for the multi-barcode walks and the shared placement.  For tests. */
+void afq_collate_multi_limits(uint32_t out[4]);
+
+/*
  * `atac collate`, the device half (src/atac/collate.rs of the reference): the records of an UNCOLLATED scATAC RAD routed by
  * corrected barcode into one chunk per cell that receives a record.
  *

@@ -127,6 +127,43 @@ typedef struct afq_atac_collate_opts {
  * (the reference panics).  map.collated.rad is written only after the device call succeeded: a failed run leaves none behind. */
 int afq_atac_collate(const afq_atac_collate_opts* opts);
 
+/* The options of multi-barcode `collate` (src/main.rs:271-292; do_collate_multi_bc_fast, src/collate.rs:1415-1920): afq_collate_opts'
+ * fields, over the output directory of afq_generate_permit_list_multi. */
+struct afq_collate_multi_stats;
+typedef struct afq_collate_multi_opts {
+    const char* input_dir;      /* -i : output directory of multi-barcode `generate-permit-list` (generate_permit_list.json,
+                                        sample_info.json, sample_<name>/permit_freq.bin, correction_plan.bin); map.collated.rad,
+                                        collation_manifest.bin, collate.json and unmapped_bc_count_collated.bin are written here  */
+    const char* rad_dir;        /* -r : the mapper's directory: map.rad                                                     */
+    uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED)                                                     */
+    uint32_t max_records;       /* -m : accepted, without effect                                                          */
+    uint32_t device;
+    const char* cmdline;        /* optional: goes into collate.json                                                        */
+    struct afq_collate_multi_stats* stats_out;   /* optional */
+} afq_collate_multi_opts;
+/* Runs multi-barcode `collate` in ONE device fill: one chunk per (sample, cell) of the samples' permit_freq.bin files, in the order
+ * (position in sample_info.json's samples, count descending, barcode ascending); a record is kept iff it is compatible with
+ * expected_ori, its b0 is an observed key of the plan's sample corrections whose target is a sample of sample_info.json, and its b1
+ * is an observed key of that sample's cell scope; it is written with b0 = the dense ordinal of the sample among the samples that
+ * have cells and b1 = the corrected cell barcode.  collation_manifest.bin holds one group per sample with cells;
+ * unmapped_bc_count_collated.bin is the empty map.  Metadata without multi_barcode: true, velo_mode, a single-barcode or scATAC
+ * prelude, a pos tag, more than two barcode levels, an ordinal that does not fit b0, compressed output and a MISSING
+ * correction_plan.bin are AFQ_ERR_UNSUPPORTED; a plan that is malformed, not sample-scoped or of another cell barcode length, a
+ * sample with cells and no cell scope, and a correction into a barcode that is no cell of its sample are AFQ_ERR_BAD_INPUT.  Per
+ * sample the records kept must number the sum of its permit_freq.bin counts ("expected to collate N records but retained M");
+ * the files are written only after that check, so a failed run leaves none behind. */
+int afq_collate_multi(const afq_collate_multi_opts* opts);
+/* afq_collate_multi_rad's checks that precede device work (include/afquant.h), without a device. */
+int afq_collate_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed,
+                                 const uint32_t* sample_index, uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed,
+                                 const uint64_t* corr_corrected, uint64_t n_corrections, const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells,
+                                 const uint32_t* sample_b0_out, uint64_t n_samples);
+/* collation_manifest.bin as afq_collate_multi writes it and afq_quantify reads it: level names sample, cell; one named group per
+ * entry.  Returns the length; writes when out holds it (out may be NULL to size). */
+int64_t afq_collation_manifest_bytes(const uint64_t* key, const char* const* name, const uint64_t* chunk_start, const uint64_t* num_chunks,
+                                     const uint64_t* num_records, uint64_t n_groups, uint8_t* out, size_t cap);
+
 /* The options of `alevin-fry generate-permit-list` (src/main.rs:170-269, 392-577; GenPermitListOpts, src/prog_opts.rs:86-160) for
  * single-barcode RNA RAD files.  Exactly one filter method is given. */
 enum { AFQ_GPL_KNEE = 0, AFQ_GPL_EXPECT = 1, AFQ_GPL_FORCE = 2, AFQ_GPL_VALID_BC = 3, AFQ_GPL_UNFILTERED = 4 };
@@ -279,6 +316,13 @@ int64_t afq_snappy_frame_decode(const uint8_t* in, size_t n, uint8_t* out, size_
  * cell_barcode_len (may be NULL) receives the plan's barcode length. */
 int64_t afq_parse_correction_plan(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap, uint32_t* cell_barcode_len);
 int64_t afq_parse_permit_map(const uint8_t* in, size_t n, uint64_t* observed, uint64_t* corrected, size_t cap);
+/* A SAMPLE-SCOPED correction_plan.bin (what afq_generate_permit_list_multi writes): the sample corrections (at most sample_cap
+ * written, *n_sample their number), per cell scope that names a sample its canonical sample barcode and the number of its
+ * corrections (scope_cap, *n_scopes), and the scopes' corrections back to back in scope order (cell_cap).  Returns their total
+ * number, or afq_parse_correction_plan's errors; a plan that is NOT sample-scoped is refused.  Every output may be NULL. */
+int64_t afq_parse_correction_plan_multi(const uint8_t* in, size_t n, uint64_t* sample_observed, uint64_t* sample_corrected, size_t sample_cap, uint64_t* n_sample,
+                                        uint64_t* scope_barcode, uint64_t* scope_count, size_t scope_cap, uint64_t* n_scopes, uint64_t* cell_observed,
+                                        uint64_t* cell_corrected, size_t cell_cap, uint32_t* sample_barcode_len, uint32_t* cell_barcode_len);
 /* Parse a RAD prelude; fills the scalars, returns the byte offset of the first chunk or a negative error. */
 typedef struct afq_rad_info {
     uint64_t ref_count, num_chunks, first_chunk_off;
