@@ -169,6 +169,32 @@ def no_alignment_case():
     return planned(MC.no_alignment_case(), seed=3)
 
 
+# ------------------------------------------------------------------------------------------------------------------ routes
+ROUTE_FATES = ("kept", "corrected", "unrouted", "uncorrected")
+
+
+def route_case(lim, pos_bytes=4, b0_bytes=2, b1_bytes=4, umi_bytes=2):
+    """CC.route_case over the head na, b0, b1, umi: every na of CC.route_nas with orientation bits such that all, none, only the word
+    at index 0 / 63 / 64 / last, and all but that word fit; the UMI numbers the records.  Record k takes fate k % 4 of ROUTE_FATES:
+    kept (b0 = 40 is sample 2, b1 = 10 its cell), corrected onto another cell of its sample (b1 = 12 -> 11), unrouted (b0 = 41 has no
+    sample), uncorrected (b1 = 13 has no correction in sample 2).  Three chunks, the middle one a single record; the position bytes
+    are non-zero and differ from alignment to alignment.  Sample 1 has a cell and no record."""
+    recs, k = [], 0
+    for na in CC.route_nas(lim):
+        pats = [[True] * na, [False] * na]
+        for only in sorted({0, 63, 64, na - 1}):
+            if 0 <= only < na:
+                pats.append([j == only for j in range(na)])
+                pats.append([j != only for j in range(na)])
+        for pat in pats:
+            b0, b1 = [(40, 10), (40, 12), (41, 10), (40, 13)][k % 4]
+            recs.append((b0, b1, k, [(100 + j, fw) for j, fw in enumerate(pat)]))
+            k += 1
+    cuts = [0, len(recs) // 3, len(recs) // 3 + 1, len(recs)]
+    chunks = [recs[a:b] for a, b in zip(cuts, cuts[1:])]
+    return case(chunks, {40: 2, 43: 1}, {(2, 10): 10, (2, 11): 11, (2, 12): 11, (1, 10): 10}, [(2, 11), (1, 10), (2, 10)], 3, b0_bytes, b1_bytes, umi_bytes, pos_bytes)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the lookup
 def lookup_case():
     """5 samples, 4-byte fields.  b1 = 0x77 is observed in samples 1 and 4 and corrected to DIFFERENT cells; the barcode 0xC0FFEE is a

@@ -110,6 +110,48 @@ def test_long_cases_hold_a_kept_a_dropped_an_unrouted_and_an_uncorrected_long_re
     assert fw["stats"]["n_long_records"] == 5
 
 
+@pytest.mark.parametrize("pos_bytes", [4, 8])
+def test_the_route_case_stores_position_bytes_beyond_the_first_trip_behind_earlier_fitting_words(lim, pos_bytes):
+    c = C.route_case(lim, pos_bytes)
+    flat = [r for recs in c["chunks"] for r in recs]
+    assert [len(recs) == 1 for recs in c["chunks"]] == [False, True, False] and c["pos_bytes"] == pos_bytes
+    assert {len(r[3]) for r in flat} == set(C.CC.route_nas(lim)) and [r[2] for r in flat] == list(range(len(flat)))
+    first = {}   # the file-wide number of every record's first alignment: the encoder's position bytes count alignments
+    n = 0
+    for r in flat:
+        first[r[2]] = n
+        n += len(r[3])
+    fate = lambda r: C.ROUTE_FATES[r[2] % 4]
+    for f in C.ROUTE_FATES:   # every fate on a long record of each pattern family, and on a record without alignments or with one
+        assert any(fate(r) == f and len(r[3]) > 64 for r in flat) and any(fate(r) == f and len(r[3]) <= 1 for r in flat), f
+    H, A = head(c), 4 + pos_bytes
+    for ori in ("fw", "rc"):
+        w = C.want(c, ori, lim["lane_alns"])
+        st = w["stats"]
+        assert st["n_unrouted"] > 0 and st["n_uncorrected"] > 0 and all(x > 0 for i, x in enumerate(w["nrec"]) if c["cells"][i][0] == 2), (ori, st)
+        assert w["nrec"][c["cells"].index((1, 10))] == 0
+        cell = c["cells"].index((2, 10))
+        by_umi = {int.from_bytes(w["bytes"][s + H - c["umi_bytes"]:s + H], "little"): s for s, _ in C.record_spans(w["bytes"], w["chunk_off"], c)
+                  if w["chunk_off"][cell] <= s < w["chunk_off"][cell + 1]}
+        reached = 0
+        for r in flat:
+            fit = [j for j, (_, fw) in enumerate(r[3]) if fw == (ori == "fw")]
+            if fate(r) != "kept" or len(r[3]) <= 64 or not fit:
+                continue
+            s = by_umi[r[2]]
+            assert int.from_bytes(w["bytes"][s:s + 4], "little") == len(fit)
+            for rank, j in enumerate(fit):
+                word = ((100 + j) | (0x80000000 if r[3][j][1] else 0)).to_bytes(4, "little")
+                at = s + H + A * rank
+                assert w["bytes"][at:at + A] == word + C.CC.position(first[r[2]] + j, pos_bytes), (ori, r[2], j)
+                reached += j >= 64 and rank > 0 and fit[0] < 64   # base > 0 in its trip and rank > 0
+        assert reached >= 2, ori
+    # kept records with 0, 1, na - 1 and na fitting words beyond one trip
+    for ori in ("fw", "rc"):
+        counts = {(len(r[3]), sum(1 for _, fw in r[3] if fw == (ori == "fw"))) for r in flat if r[2] % 4 < 2 and len(r[3]) > 64}
+        assert {k for na, k in counts if na == 129} >= {0, 1, 128, 129}, (ori, counts)
+
+
 def test_records_without_alignments_are_kept_under_both_only(lim):
     c = C.no_alignment_case()
     both, fw, rc = (C.want(c, o)["stats"] for o in C.ORIS)

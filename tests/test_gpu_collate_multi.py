@@ -86,6 +86,14 @@ def test_long_records_kept_dropped_unrouted_and_uncorrected(q, lim, where):
     check(q, lim, C.long_case(where), what=f"long {where}")
 
 
+@pytest.mark.parametrize("pos_bytes", [4, 8])
+def test_every_route_with_position_bytes_and_every_fate(q, lim, pos_bytes):
+    """records of up to 129 alignments WITH position bytes, fitting words before and beyond the first 64-lane trip, kept, corrected,
+    unrouted and uncorrected in turn (tests/test_collate_multi_cases_cpu.py shows the reach)"""
+    out = check(q, lim, C.route_case(lim, pos_bytes), what=f"routes pos {pos_bytes}")
+    assert set(out) == set(C.ORIS) and out["fw"][0]["stats"]["n_long_records"] > 0
+
+
 def test_records_without_alignments(q, lim):
     check(q, lim, C.no_alignment_case(), what="na 0")
 
