@@ -3342,6 +3342,130 @@ static void collate_radix_place(hipStream_t s, uint64_t*& src, uint64_t*& dst, u
     }
 }
 
+// What afq_collate_rad and afq_collate_multi_rad share from the chunk table to the return: collate_plan in front of the entry's
+// uploads, collate_finish behind its measure launch.  The entry fills the first block, the plain data the two differ in, and keeps
+// what is its own: the index step, the uploads (the sample table's sit among the cell table's, and the order of the stream's
+// operations is the entry's), the args struct, the table and measure launches in their brackets, and the sum of its chunk_stat words.
+struct CollateRun {
+    const char* who;                                   // the entry's name in messages
+    int k_sort, k_scan, k_write;                       // timer ids: placement, length scan + heads, write walk
+    const char* lap_measure; const char* lap_write;    // HostClock labels
+    uint32_t head_bytes;                               // a record without alignments
+    uint64_t extra_tab_bytes;                          // device bytes of tables beside the cell table, the correction entries and the cells
+    // collate_plan's
+    std::vector<SortChunk> chunks;
+    uint64_t n_bytes = 0, n_slots = 0, cap = 0, s1 = 0, nc1 = 0, ncell1 = 0, ncorr1 = 0, need_out = 0;
+    uint32_t n = 0, n_chunks = 0, n_cells = 0;
+    HipLatch T;
+    int hip_fail(afq_ctx* c) const {
+        return T.fail(c, who, " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
+    }
+};
+
+// The chunk table, the sizes, the fit check and the buffers both entries use (R.T holds the first failure of an `ensure`: the
+// entry looks at it behind its own).
+static int collate_plan(afq_ctx* c, CollateRun& R, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, bool on_device, uint64_t n_corr,
+                        uint32_t n_cells) {
+    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, on_device, R.head_bytes, R.chunks, R.n_slots)) return rc;
+    const std::string who = R.who;
+    if (R.n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, who + ": 2^32 or more records in one call (" + std::to_string(R.n_slots) + "): fill the device in smaller parts");
+    R.n_bytes = n_bytes; R.n = (uint32_t)R.n_slots; R.n_chunks = n_chunks; R.n_cells = n_cells;
+    R.cap = sort_table_capacity(n_corr);
+    R.s1 = std::max<uint64_t>(R.n_slots, 1); R.nc1 = std::max<uint32_t>(n_chunks, 1); R.ncell1 = (uint64_t)n_cells + 1; R.ncorr1 = std::max<uint64_t>(n_corr, 1);
+    const uint64_t s1 = R.s1, nc1 = R.nc1, ncell1 = R.ncell1, cap = R.cap;
+    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock, n_sblocks = (s1 + kCollateScanBlock - 1) / kCollateScanBlock;
+    // does it fit?  (input + staging, the output - never longer than the input's records + the cells' headers -, 32 bytes a record
+    // of slots, sort words and offsets, the digit counts, the tables)
+    R.need_out = (uint64_t)n_bytes + 8 * ncell1;
+    const uint64_t need_in = on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 32 + 8 + n_rblocks * 1024 + n_sblocks * 8,
+                   need_tab = cap * 12 + n_corr * 12 + R.extra_tab_bytes + ncell1 * 20, need_misc = nc1 * (sizeof(SortChunk) + 32);
+    {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + R.need_out + need_rec + need_tab + need_misc > tot)
+            return fail(c, AFQ_ERR_OOM, who + ": the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
+                        std::to_string(R.need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(R.n_slots) + " records + " +
+                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
+    }
+    auto& B = c->collate;
+    HipLatch& T = R.T;
+    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * R.ncorr1)); T(B.val.ensure(4 * R.ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
+    T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
+    T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
+    return 0;
+}
+
+// Behind the entry's measure launch: status and chunk_stat readback (cstat: [n_chunks][8], the entry's to sum), radix placement,
+// length scan, chunk heads, the entry's write walk (launch_write(dest, out)), the copies back and the closing checks.
+// cell_text(cell) words a cell for the 4 GiB-chunk refusal.
+static int collate_finish(afq_ctx* c, CollateRun& R, HostClock& hc, std::vector<uint32_t>& cstat, const std::function<void(const uint64_t*, uint8_t*)>& launch_write,
+                          const std::function<std::string(uint32_t)>& cell_text, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off, uint32_t** out_nrec) {
+    auto& B = c->collate;
+    HipLatch& T = R.T;
+    hipStream_t s = c->stream;
+    const std::string who = R.who;
+    const uint32_t n = R.n, n_chunks = R.n_chunks, n_cells = R.n_cells;
+    const uint64_t ncell1 = R.ncell1;
+    T(hipGetLastError());
+    DevStatus st{};
+    cstat.assign(8ull * n_chunks, 0);
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and its tables: the copies out of them are done by now, too)
+    hc.lap(R.lap_measure);
+    if (!T.ok()) return R.hip_fail(c);
+    if (st.err_code) return rad_status_fault(c, R.who, st);
+    // ---- placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies
+    uint64_t* src = B.ka.as<uint64_t>();
+    uint64_t* dst = B.kb.as<uint64_t>();
+    {
+        ScopedTimer t(c, R.k_sort, s);
+        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
+    }
+    uint64_t kept_bytes = 0;
+    {
+        ScopedTimer t(c, R.k_scan, s);
+        launch_collate_scan(s, src, B.rec.as<uint2>(), n, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), dst);   // (dst: the buffer the last pass read is free)
+    }
+    T(hipGetLastError());
+    T(hipMemcpyAsync(&kept_bytes, B.ex.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    if (!T.ok()) return R.hip_fail(c);
+    const uint64_t out_total = 8ull * n_cells + kept_bytes, o1 = std::max<uint64_t>(out_total, 1);
+    if (out_total > R.need_out) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, who + ": " + std::to_string(out_total) + " bytes of output from " + std::to_string(R.n_bytes) + " of input"); }
+    T(B.out.ensure(o1));
+    if (!T.ok()) return R.hip_fail(c);
+    {
+        ScopedTimer t(c, R.k_scan, s);
+        launch_collate_heads(s, src, n, B.ex.as<uint64_t>(), n_cells, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), B.out.as<uint8_t>(), B.status.as<DevStatus>());
+    }
+    {
+        ScopedTimer t(c, R.k_write, s);
+        launch_write(dst, B.out.as<uint8_t>());
+    }
+    T(hipGetLastError());
+    HostOuts H;
+    uint8_t* ob = (uint8_t*)H.mallocd(o1);
+    uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
+    uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
+    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, who + ": host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
+    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
+    if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
+    harvest_timers(c);
+    hc.lap(R.lap_write);
+    if (!T.ok()) return R.hip_fail(c);
+    if (st.err_code == kErrCollateChunk)
+        return fail(c, AFQ_ERR_UNSUPPORTED, who + ": cell " + std::to_string(st.err_cell) + " (" + cell_text(st.err_cell) + "): an output chunk of 4 GiB or more");
+    if (st.err_code) return fail(c, AFQ_ERR_HIP, who + ": device status " + std::to_string(st.err_code) + " in the write");
+    if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, who + ": the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
+    H.release();
+    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
+    return 0;
+}
+
 // `collate` on the device (afq_collate.hip): correction table, measure walk, radix placement, length scan, chunk heads, write walk.
 void afq_collate_limits(uint32_t out[4]) {
     if (!out) return;
@@ -3369,40 +3493,18 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
     std::vector<uint32_t> val;
     uint32_t ones_cell = kSortNoRank;
     if (int rc = collate_cell_index(c, observed, corrected, n_corr, cells, n_cells, val, ones_cell)) return rc;
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes + umi_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint32_t n = (uint32_t)n_slots;
-    const uint64_t cap = sort_table_capacity(n_corr);
+    // ---- chunk table, sizes, fit check, buffers
+    CollateRun R{"afq_collate_rad", K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, "collate: table + measure", "collate: place + write + D2H", 4 + bc_bytes + umi_bytes, 0};
+    if (int rc = collate_plan(c, R, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, n_corr, n_cells)) return rc;
+    const uint64_t cap = R.cap;
     const uint32_t tab_mask = (uint32_t)(cap - 1);
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ncell1 = (uint64_t)n_cells + 1, ncorr1 = std::max<uint64_t>(n_corr, 1);
-    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock, n_sblocks = (s1 + kCollateScanBlock - 1) / kCollateScanBlock;
-    // does it fit?  (input + staging, the output - never longer than the input's records + the cells' headers -, 32 bytes a record
-    // of slots, sort words and offsets, the digit counts, the tables)
-    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_out = (uint64_t)n_bytes + 8 * ncell1, need_rec = s1 * 32 + 8 + n_rblocks * 1024 + n_sblocks * 8,
-                   need_tab = cap * 12 + n_corr * 12 + ncell1 * 20, need_misc = nc1 * (sizeof(SortChunk) + 32);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_out + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_collate_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
-                        std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
-    }
     auto& B = c->collate;
-    HipLatch T;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_collate_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
-    };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * ncorr1)); T(B.val.ensure(4 * ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
-    T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
-    T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
+    HipLatch& T = R.T;
+    auto hip_fail = [&]() { return R.hip_fail(c); };
     if (!T.ok()) return hip_fail();
     const uint8_t* d_bytes = nullptr;
     if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, R.chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
     if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
     T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
@@ -3421,80 +3523,23 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
         ScopedTimer t(c, K_COLLATE_MEASURE, s);
         launch_collate_measure(s, a);
     }
-    T(hipGetLastError());
-    DevStatus st{};
-    std::vector<uint32_t> cstat(8ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("collate: table + measure");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return rad_status_fault(c, "afq_collate_rad", st);
+    std::vector<uint32_t> cstat;
+    if (int rc = collate_finish(c, R, hc, cstat, [&](const uint64_t* dest, uint8_t* out) { a.dest = dest; a.out = out; launch_collate_write(s, a); },
+                                [&](uint32_t cell) { return "barcode " + std::to_string(cells[cell]); }, out_bytes, out_n_bytes, out_chunk_off, out_nrec))
+        return rc;
     afq_collate_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const uint32_t* q = cstat.data() + 8ull * i;
         S.n_records += q[0]; S.n_compatible += q[1]; S.n_uncorrected += q[2]; S.n_kept += q[3]; S.n_alignments_in += q[4]; S.n_alignments_kept += q[5]; S.n_long_records += q[6];
     }
-    // ---- placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies
-    uint64_t* src = B.ka.as<uint64_t>();
-    uint64_t* dst = B.kb.as<uint64_t>();
-    {
-        ScopedTimer t(c, K_COLLATE_SORT, s);
-        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
-    }
-    uint64_t kept_bytes = 0;
-    {
-        ScopedTimer t(c, K_COLLATE_SCAN, s);
-        launch_collate_scan(s, src, B.rec.as<uint2>(), n, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), dst);   // (dst: the buffer the last pass read is free)
-    }
-    T(hipGetLastError());
-    T(hipMemcpyAsync(&kept_bytes, B.ex.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return hip_fail();
-    const uint64_t out_total = 8ull * n_cells + kept_bytes, o1 = std::max<uint64_t>(out_total, 1);
-    if (out_total > need_out) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_collate_rad: " + std::to_string(out_total) + " bytes of output from " + std::to_string(n_bytes) + " of input"); }
-    T(B.out.ensure(o1));
-    if (!T.ok()) return hip_fail();
-    a.dest = dst; a.out = B.out.as<uint8_t>();
-    {
-        ScopedTimer t(c, K_COLLATE_SCAN, s);
-        launch_collate_heads(s, src, n, B.ex.as<uint64_t>(), n_cells, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), a.out, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_COLLATE_WRITE, s);
-        launch_collate_write(s, a);
-    }
-    T(hipGetLastError());
-    HostOuts H;
-    uint8_t* ob = (uint8_t*)H.mallocd(o1);
-    uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
-    uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
-    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_collate_rad: host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
-    if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
-    harvest_timers(c);
-    hc.lap("collate: place + write + D2H");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code == kErrCollateChunk)
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: cell " + std::to_string(st.err_cell) + " (barcode " + std::to_string(cells[st.err_cell]) + "): an output chunk of 4 GiB or more");
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_collate_rad: device status " + std::to_string(st.err_code) + " in the write");
-    if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, "afq_collate_rad: the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
-    S.out_bytes = out_total;
+    S.out_bytes = *out_n_bytes;
     if (stats) *stats = S;
-    H.release();
-    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
     return 0;
 }
 
-// multi-barcode `collate` on the device (afq_collate_multi.hip): sample table, cell table, measure walk, then collate's radix
-// placement, length scan and chunk heads, write walk.
-void afq_collate_multi_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = kCollateRadixBlock;
-}
+// multi-barcode `collate` on the device (k_collate_walk over CollateMultiArgs, afq_collate.hip): sample table, cell table, measure
+// walk, then collate's radix placement, length scan and chunk heads, write walk.
+void afq_collate_multi_limits(uint32_t out[4]) { afq_collate_limits(out); }   // (one walk: one set of limits)
 
 int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes, uint32_t b1_bytes,
                           uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed, const uint32_t* sample_index,
@@ -3519,41 +3564,21 @@ int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
     std::vector<uint64_t> ckey(n_corr), chead(n_cells);
     for (uint64_t i = 0; i < n_corr; ++i) ckey[i] = (uint64_t)corr_sample[i] << 32 | corr_observed[i];
     for (uint32_t j = 0; j < n_cells; ++j) chead[j] = (uint64_t)sample_b0_out[cell_sample[j]] << 32 | cell_bc[j];
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + b0_bytes + b1_bytes + umi_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint32_t n = (uint32_t)n_slots;
-    const uint64_t cap = sort_table_capacity(n_corr), scap = sort_table_capacity(n_sample_entries);
+    // ---- chunk table, sizes, fit check, buffers (afq_collate_rad's, with the sample entries and their table beside the cell table)
+    const uint64_t scap = sort_table_capacity(n_sample_entries), nse1 = std::max<uint64_t>(n_sample_entries, 1);
+    CollateRun R{"afq_collate_multi_rad", K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, "collate multi: tables + measure", "collate multi: place + write + D2H",
+                 4 + b0_bytes + b1_bytes + umi_bytes, scap * 12 + n_sample_entries * 12};
+    if (int rc = collate_plan(c, R, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, n_corr, n_cells)) return rc;
+    const uint64_t cap = R.cap;
     const uint32_t tab_mask = (uint32_t)(cap - 1), stab_mask = (uint32_t)(scap - 1);
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ncell1 = (uint64_t)n_cells + 1, ncorr1 = std::max<uint64_t>(n_corr, 1),
-                   nse1 = std::max<uint64_t>(n_sample_entries, 1);
-    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock, n_sblocks = (s1 + kCollateScanBlock - 1) / kCollateScanBlock;
-    // does it fit?  (afq_collate_rad's sum, with the sample entries and their table beside the cell table)
-    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_out = (uint64_t)n_bytes + 8 * ncell1, need_rec = s1 * 32 + 8 + n_rblocks * 1024 + n_sblocks * 8,
-                   need_tab = cap * 12 + n_corr * 12 + scap * 12 + n_sample_entries * 12 + ncell1 * 20, need_misc = nc1 * (sizeof(SortChunk) + 32);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_out + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_collate_multi_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
-                        std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
-    }
     auto& B = c->collate;
-    HipLatch T;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_collate_multi_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
-    };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * ncorr1)); T(B.val.ensure(4 * ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
+    HipLatch& T = R.T;
+    auto hip_fail = [&]() { return R.hip_fail(c); };
     T(B.sobs.ensure(8 * nse1)); T(B.sidx.ensure(4 * nse1)); T(B.skey.ensure(8 * scap)); T(B.sval.ensure(4 * scap));
-    T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
-    T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
     if (!T.ok()) return hip_fail();
     const uint8_t* d_bytes = nullptr;
     if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
+    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, R.chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
     if (n_corr) { T(hipMemcpyAsync(B.obs.p, ckey.data(), 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
     if (n_sample_entries) {
         T(hipMemcpyAsync(B.sobs.p, sample_observed, 8 * n_sample_entries, hipMemcpyHostToDevice, s));
@@ -3578,73 +3603,19 @@ int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
         ScopedTimer t(c, K_COLLATEM_MEASURE, s);
         launch_collate_multi_measure(s, a);
     }
-    T(hipGetLastError());
-    DevStatus st{};
-    std::vector<uint32_t> cstat(8ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and the tables: the copies out of them are done by now, too)
-    hc.lap("collate multi: tables + measure");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return rad_status_fault(c, "afq_collate_multi_rad", st);
+    std::vector<uint32_t> cstat;
+    if (int rc = collate_finish(c, R, hc, cstat, [&](const uint64_t* dest, uint8_t* out) { a.dest = dest; a.out = out; launch_collate_multi_write(s, a); },
+                                [&](uint32_t cell) { return "sample " + std::to_string(cell_sample[cell]) + ", barcode " + std::to_string(cell_bc[cell]); }, out_bytes,
+                                out_n_bytes, out_chunk_off, out_nrec))
+        return rc;
     afq_collate_multi_stats S{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         const uint32_t* q = cstat.data() + 8ull * i;
         S.n_records += q[0]; S.n_compatible += q[1]; S.n_unrouted += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4]; S.n_alignments_in += q[5]; S.n_alignments_kept += q[6];
         S.n_long_records += q[7];
     }
-    // ---- placement, length scan: collate's
-    uint64_t* src = B.ka.as<uint64_t>();
-    uint64_t* dst = B.kb.as<uint64_t>();
-    {
-        ScopedTimer t(c, K_COLLATEM_SORT, s);
-        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
-    }
-    uint64_t kept_bytes = 0;
-    {
-        ScopedTimer t(c, K_COLLATEM_SCAN, s);
-        launch_collate_scan(s, src, B.rec.as<uint2>(), n, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), dst);   // (dst: the buffer the last pass read is free)
-    }
-    T(hipGetLastError());
-    T(hipMemcpyAsync(&kept_bytes, B.ex.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return hip_fail();
-    const uint64_t out_total = 8ull * n_cells + kept_bytes, o1 = std::max<uint64_t>(out_total, 1);
-    if (out_total > need_out) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: " + std::to_string(out_total) + " bytes of output from " + std::to_string(n_bytes) + " of input"); }
-    T(B.out.ensure(o1));
-    if (!T.ok()) return hip_fail();
-    a.dest = dst; a.out = B.out.as<uint8_t>();
-    {
-        ScopedTimer t(c, K_COLLATEM_SCAN, s);
-        launch_collate_heads(s, src, n, B.ex.as<uint64_t>(), n_cells, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), a.out, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_COLLATEM_WRITE, s);
-        launch_collate_multi_write(s, a);
-    }
-    T(hipGetLastError());
-    HostOuts H;
-    uint8_t* ob = (uint8_t*)H.mallocd(o1);
-    uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
-    uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
-    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_collate_multi_rad: host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
-    if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
-    harvest_timers(c);
-    hc.lap("collate multi: place + write + D2H");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code == kErrCollateChunk)
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_multi_rad: cell " + std::to_string(st.err_cell) + " (sample " + std::to_string(cell_sample[st.err_cell]) + ", barcode " +
-                    std::to_string(cell_bc[st.err_cell]) + "): an output chunk of 4 GiB or more");
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: device status " + std::to_string(st.err_code) + " in the write");
-    if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, "afq_collate_multi_rad: the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
-    S.out_bytes = out_total;
+    S.out_bytes = *out_n_bytes;
     if (stats) *stats = S;
-    H.release();
-    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
     return 0;
 }
 

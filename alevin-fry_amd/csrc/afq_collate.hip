@@ -15,10 +15,24 @@
 //     their position bytes at dest[slot].
 // A record with more than kGplLaneAlns alignments is handled by the whole wave out of global memory in both walks.
 //
+// Multi-barcode `collate` (do_collate_multi_bc_fast, src/collate.rs:1415-1920 of the reference) is the same template over another
+// args type: the records are `na, b0, b1, umi, alignments`, routed to a sample by b0, corrected to a cell of that sample by b1, and
+// written with b0 = the sample's ordinal and b1 = the corrected cell barcode.  Five sites of the walk differ, each behind an
+// `if constexpr` on the args type: the head size, the lookup, the counter n_unrouted, the head's barcode fields as written, and the
+// order of the chunk_stat words.  Its lookup has two levels:
+//   - the sample table: observed b0 -> sample index (a few thousand entries at most; it stays in cache).  The lane starts this
+//     probe beside the read of na, before the alignment words are counted, as k_gpl_multi_parse does;
+//   - the cell table: sample << 32 | b1 -> the index of the corrected barcode among the cells.  It depends on the first probe's
+//     result.  b1 has at most 4 bytes and a sample index is below 2^31, so no key is the all-ones free mark (single-barcode keys
+//     can be all-ones: that barcode travels beside the table as ones_cell).
+// Both tables are launch_sort_table's; placement, the length scan and the chunk heads below serve both.
+//
 // Stores.  Two records that are neighbours in the output share an aligned dword and different waves write them.  ByteOut stores
 // only the bytes it was given: byte / short stores up to the first dword boundary and after the last, dwords between; it never
 // reads the output.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "afq_common.h"
 #include "afq_kernels.h"
@@ -31,37 +45,36 @@ namespace {
 
 constexpr int kWalkNT = 256;
 constexpr uint32_t kWalkWaves = kWalkNT / 64;
-constexpr uint32_t kTileWords = (3 + kGplParseTile + kGplParseHalo + 3) / 4 + 1;   // (+ the dword an unaligned 4-byte read of the last bytes also touches)
 static_assert(kGplParseHalo >= (4 + 8 + 8) + (4 + 8) * kGplLaneAlns, "the halo holds the widest head and kGplLaneAlns of the widest alignments");
-constexpr uint32_t kTileRecs = kGplParseTile / 6 + 1;   // the shortest record: na = 0, a 1-byte barcode, a 1-byte UMI
+static_assert(kGplParseHalo >= (4 + 4 + 4 + 8) + (4 + 8) * kGplLaneAlns, "the halo holds the widest head (na, b0, b1, umi) and kGplLaneAlns of the widest alignments");
+static_assert(kRadWalkTileRecs >= kGplParseTile / (4 + 1 + 1 + 1) + 1, "a start slot for every record of a tile of the shortest records");
 
 __device__ __forceinline__ uint32_t collate_find(const CollateArgs& a, uint64_t k) {
     if (k == kSortEmptyKey) return a.ones_cell;
-    uint32_t slot = sort_hash_bc(k) & a.tab_mask;
-    for (uint32_t probe = 0; probe <= a.tab_mask; ++probe) {   // (at most half the slots are taken: an empty one ends the probe)
-        const uint64_t kk = a.tab_key[slot];
-        if (kk == k) return a.tab_val[slot];
-        if (kk == kSortEmptyKey) return kSortNoRank;
-        slot = (slot + 1) & a.tab_mask;
-    }
-    return kSortNoRank;
+    return sort_table_find(a.tab_key, a.tab_val, a.tab_mask, k);
 }
+__device__ __forceinline__ uint32_t collate_head_bytes(const CollateArgs& a) { return 4 + a.bc_bytes + a.umi_bytes; }
+__device__ __forceinline__ uint32_t collate_head_bytes(const CollateMultiArgs& a) { return 4 + a.b0_bytes + a.b1_bytes + a.umi_bytes; }
 
-template <bool WRITE>
-__global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
-    __shared__ uint32_t s_tile[kWalkWaves][kTileWords];
-    __shared__ uint16_t s_start[kWalkWaves][kTileRecs];
+template <bool WRITE, class Args>
+__global__ __launch_bounds__(kWalkNT) void k_collate_walk(Args a) {
+    constexpr bool M = std::is_same_v<Args, CollateMultiArgs>;
+    __shared__ uint32_t s_tile[kWalkWaves][kRadWalkTileWords];
+    __shared__ uint16_t s_start[kWalkWaves][kRadWalkTileRecs];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t chunk = blockIdx.x * kWalkWaves + wave;
     if (chunk >= a.n_chunks) return;   // (no workgroup barrier below: the waves of a block run chunks of different lengths)
     const SortChunk c = a.chunks[chunk];
-    const uint32_t nb = c.nbytes, H = 4 + a.bc_bytes + a.umi_bytes, A = 4 + a.aln_extra;   // the host checked 8 <= nb and chunk_off + nb <= n_bytes
+    const uint32_t nb = c.nbytes, H = collate_head_bytes(a), A = 4 + a.aln_extra;   // the host checked 8 <= nb and chunk_off + nb <= n_bytes
+    [[maybe_unused]] uint32_t m0 = 0, m1 = 0;   // multi: the masks of b0 and b1
+    if constexpr (M) { m0 = a.b0_bytes < 4 ? (1u << (8 * a.b0_bytes)) - 1u : ~0u; m1 = a.b1_bytes < 4 ? (1u << (8 * a.b1_bytes)) - 1u : ~0u; }
     const bool both = a.expected_ori == kGplOriBoth;
     const uint64_t lt = (1ull << lane) - 1ull;
     uint32_t* tile = s_tile[wave];
     uint16_t* starts = s_start[wave];
     uint32_t p = 8, seen = 0;                                          // wave-uniform
     uint32_t n_compat = 0, n_uncorr = 0, n_kept = 0, aln_in = 0, aln_kept = 0, n_long = 0;   // per lane (a chunk is below 4 GiB: no sum wraps)
+    [[maybe_unused]] uint32_t n_unrouted = 0;   // multi: compatible, but b0 names no sample
     bool bad = false;                                                  // uniform: the records do not tile the chunk
     while (p < nb && !bad) {
         // stage [p, p + tile + halo) of the chunk, as aligned dwords
@@ -93,7 +106,9 @@ __global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
             const bool is_long = live && na > kGplLaneAlns;   // its list may end behind the halo: the wave takes it, out of global memory
             if constexpr (!WRITE) {
                 uint32_t nfit = 0;
+                [[maybe_unused]] uint32_t sample = kSortNoRank;
                 if (live) {
+                    if constexpr (M) sample = sort_table_find(a.stab_key, a.stab_val, a.stab_mask, gpl_lds32(tile, o + 4) & m0);   // (its loads fly while the alignment words are read)
                     aln_in += na;
                     n_long += is_long;
                     if (both) nfit = na;
@@ -118,12 +133,22 @@ __global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
                     uint32_t cell = a.n_cells, len = 0;
                     if (both || nfit) {   // compatible (na == 0 only under `both`)
                         ++n_compat;
-                        uint64_t bc = gpl_lds32(tile, o + 4);
-                        if (a.bc_bytes == 8) bc |= (uint64_t)gpl_lds32(tile, o + 8) << 32;
-                        else if (a.bc_bytes < 4) bc &= (1u << (8 * a.bc_bytes)) - 1u;
-                        const uint32_t f = collate_find(a, bc);
-                        if (f == kSortNoRank) ++n_uncorr;
-                        else { cell = f; len = H + A * nfit; ++n_kept; aln_kept += nfit; }   // (len <= the record's own length < 2^32)
+                        if constexpr (M) {
+                            if (sample == kSortNoRank) ++n_unrouted;
+                            else {
+                                const uint32_t b1 = gpl_lds32(tile, o + 4 + a.b0_bytes) & m1;
+                                const uint32_t f = sort_table_find(a.ctab_key, a.ctab_val, a.ctab_mask, (uint64_t)sample << 32 | b1);
+                                if (f == kSortNoRank) ++n_uncorr;
+                                else { cell = f; len = H + A * nfit; ++n_kept; aln_kept += nfit; }   // (len <= the record's own length < 2^32)
+                            }
+                        } else {
+                            uint64_t bc = gpl_lds32(tile, o + 4);
+                            if (a.bc_bytes == 8) bc |= (uint64_t)gpl_lds32(tile, o + 8) << 32;
+                            else if (a.bc_bytes < 4) bc &= (1u << (8 * a.bc_bytes)) - 1u;
+                            const uint32_t f = collate_find(a, bc);
+                            if (f == kSortNoRank) ++n_uncorr;
+                            else { cell = f; len = H + A * nfit; ++n_kept; aln_kept += nfit; }   // (len <= the record's own length < 2^32)
+                        }
                     }
                     a.rec[slot] = make_uint2(cell, len);
                     a.key[slot] = ((uint64_t)cell << 32) | slot;
@@ -139,10 +164,20 @@ __global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
                 const bool kept = cell != a.n_cells;
                 if (kept) {   // the head, and the alignments of a record whose list the halo holds
                     ByteOut w{a.out + d, 0, 0};
-                    w.put(nk, 4);
-                    w.put_field(a.cells[cell], a.bc_bytes);
-                    uint64_t umi = gpl_lds32(tile, o + 4 + a.bc_bytes);
-                    if (a.umi_bytes == 8) umi |= (uint64_t)gpl_lds32(tile, o + 8 + a.bc_bytes) << 32;
+                    uint64_t umi;
+                    if constexpr (M) {   // (each side as it stood as a kernel of its own, the order of load and first put included: the multi write walk's code moves otherwise)
+                        const uint64_t ch = a.cell_head[cell];   // the sample's ordinal << 32 | the corrected cell barcode
+                        w.put(nk, 4);
+                        w.put((uint32_t)(ch >> 32), a.b0_bytes);
+                        w.put((uint32_t)ch, a.b1_bytes);
+                        umi = gpl_lds32(tile, o + 4 + a.b0_bytes + a.b1_bytes);
+                        if (a.umi_bytes == 8) umi |= (uint64_t)gpl_lds32(tile, o + 8 + a.b0_bytes + a.b1_bytes) << 32;
+                    } else {
+                        w.put(nk, 4);
+                        w.put_field(a.cells[cell], a.bc_bytes);
+                        umi = gpl_lds32(tile, o + 4 + a.bc_bytes);
+                        if (a.umi_bytes == 8) umi |= (uint64_t)gpl_lds32(tile, o + 8 + a.bc_bytes) << 32;
+                    }
                     w.put_field(umi, a.umi_bytes);
                     if (!is_long)
                         for (uint32_t j = 0; j < na; ++j) {
@@ -184,12 +219,15 @@ __global__ __launch_bounds__(kWalkNT) void k_collate_walk(CollateArgs a) {
     if (bad && lane == 0) set_err(a.st, kErrRecordWalk, chunk);
     if constexpr (!WRITE) {
         for (int d = 32; d; d >>= 1) {
-            n_compat += __shfl_xor(n_compat, d); n_uncorr += __shfl_xor(n_uncorr, d); n_kept += __shfl_xor(n_kept, d);
+            n_compat += __shfl_xor(n_compat, d);
+            if constexpr (M) n_unrouted += __shfl_xor(n_unrouted, d);
+            n_uncorr += __shfl_xor(n_uncorr, d); n_kept += __shfl_xor(n_kept, d);
             aln_in += __shfl_xor(aln_in, d); aln_kept += __shfl_xor(aln_kept, d); n_long += __shfl_xor(n_long, d);
         }
         if (lane == 0) {
             uint32_t* s = a.chunk_stat + 8ull * chunk;
-            s[0] = seen; s[1] = n_compat; s[2] = n_uncorr; s[3] = n_kept; s[4] = aln_in; s[5] = aln_kept; s[6] = n_long; s[7] = 0;
+            if constexpr (M) { s[0] = seen; s[1] = n_compat; s[2] = n_unrouted; s[3] = n_uncorr; s[4] = n_kept; s[5] = aln_in; s[6] = aln_kept; s[7] = n_long; }
+            else { s[0] = seen; s[1] = n_compat; s[2] = n_uncorr; s[3] = n_kept; s[4] = aln_in; s[5] = aln_kept; s[6] = n_long; s[7] = 0; }
         }
     }
 }
@@ -356,11 +394,19 @@ __global__ __launch_bounds__(256) void k_collate_heads(const uint64_t* __restric
 
 void launch_collate_measure(hipStream_t s, const CollateArgs& a) {
     if (!a.n_chunks) return;
-    AFQ_LAUNCH(k_collate_walk<false>, (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
+    AFQ_LAUNCH((k_collate_walk<false, CollateArgs>), (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
 }
 void launch_collate_write(hipStream_t s, const CollateArgs& a) {
     if (!a.n_chunks) return;
-    AFQ_LAUNCH(k_collate_walk<true>, (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
+    AFQ_LAUNCH((k_collate_walk<true, CollateArgs>), (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
+}
+void launch_collate_multi_measure(hipStream_t s, const CollateMultiArgs& a) {
+    if (!a.n_chunks) return;
+    AFQ_LAUNCH((k_collate_walk<false, CollateMultiArgs>), (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
+}
+void launch_collate_multi_write(hipStream_t s, const CollateMultiArgs& a) {
+    if (!a.n_chunks) return;
+    AFQ_LAUNCH((k_collate_walk<true, CollateMultiArgs>), (a.n_chunks + kWalkWaves - 1) / kWalkWaves, kWalkNT, s, a);
 }
 
 void launch_collate_radix_pass(hipStream_t s, const uint64_t* src, uint64_t* dst, uint32_t n, uint32_t shift, uint32_t* hist) {

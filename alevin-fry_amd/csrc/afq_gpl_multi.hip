@@ -27,16 +27,7 @@ static_assert(kRadWalkTileRecs >= kGplParseTile / (4 + 1 + 1 + 1) + 1, "a start 
 
 struct GplMultiHead { uint32_t entry, b1; };   // what a lane keeps of its record's head: b0's index among the entries (kGplNoTarget: none), b1
 
-__device__ __forceinline__ uint32_t gpl_multi_find(const GplMultiParseArgs& a, uint32_t b0) {
-    uint32_t slot = sort_hash_bc(b0) & a.tab_mask;
-    for (uint32_t probe = 0; probe <= a.tab_mask; ++probe) {   // (at most half the slots are taken: an empty one ends the probe)
-        const uint64_t kk = a.tab_key[slot];
-        if (kk == b0) return a.tab_val[slot];
-        if (kk == kSortEmptyKey) return kGplNoTarget;
-        slot = (slot + 1) & a.tab_mask;
-    }
-    return kGplNoTarget;
-}
+static_assert(kGplNoTarget == kSortNoRank, "sort_table_find's no-entry mark is this pass's");
 
 __global__ __launch_bounds__(kGplMultiNT) void k_gpl_multi_parse(GplMultiParseArgs a) {
     __shared__ uint32_t s_tile[kGplMultiWaves][kRadWalkTileWords];
@@ -51,7 +42,7 @@ __global__ __launch_bounds__(kGplMultiNT) void k_gpl_multi_parse(GplMultiParseAr
     const bool ok = rad_walk_chunk(a.bytes, a.n_bytes, c, 4 + a.b0_bytes + a.b1_bytes + a.umi_bytes, 4 + a.aln_extra, a.expected_ori, s_tile[wave], s_start[wave], lane,
                                    seen, n_long,
                                    [&](uint32_t o) {   // (the probe starts before the orientation test: its loads fly while the alignment words are read)
-        return GplMultiHead{gpl_multi_find(a, gpl_lds32(tile, o + 4) & m0), gpl_lds32(tile, o + 4 + a.b0_bytes) & m1};
+        return GplMultiHead{sort_table_find(a.tab_key, a.tab_val, a.tab_mask, gpl_lds32(tile, o + 4) & m0), gpl_lds32(tile, o + 4 + a.b0_bytes) & m1};
     },
                                    [&](const GplMultiHead& h, uint32_t, bool keep) {
         const bool route = keep && h.entry != kGplNoTarget;

@@ -337,7 +337,7 @@ void launch_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, con
 // in-place exclusive scan of n words by one workgroup (the radix passes' digit counts; `atac collate`'s non-empty-cell flags)
 void launch_collate_excl_scan_u32(hipStream_t s, uint32_t* v, uint64_t n);
 // multi-barcode `collate`: the records `na, b0, b1, umi, alignments` of an uncollated two-barcode RNA RAD, routed to a sample by b0 and
-// corrected to a cell of that sample by b1, one output chunk per cell (afq_collate_multi.hip).  The walk and its limits are collate's;
+// corrected to a cell of that sample by b1, one output chunk per cell (k_collate_walk over these args, afq_collate.hip).  The walk and its limits are collate's;
 // both tables are launch_sort_table's (no key is all-ones: b0 and b1 have at most 4 bytes and a sample index is below 2^31); placement,
 // length scan and heads are launch_collate_radix_pass / launch_collate_scan / launch_collate_heads.
 struct CollateMultiArgs {

@@ -1,7 +1,8 @@
 // afq_rad_walk.h — what the wave-per-chunk walks of an uncollated RNA RAD share (k_gpl_parse, afq_gpl.hip; k_gpl_multi_parse,
-// afq_gpl_multi.hip; the collate walks, afq_collate.hip and afq_collate_multi.hip; the scATAC collate walks, afq_atac_collate.hip): checked loads of the input
-// buffer, unaligned reads of the LDS tile, the wave's LDS fence, the orientation test, rad_walk_chunk (the whole GPL walk as a
-// template over what is read of a record's head), and ByteOut, the byte stream the collate write walks store through.
+// afq_gpl_multi.hip; the collate walks, single- and multi-barcode, afq_collate.hip; the scATAC collate walks, afq_atac_collate.hip): checked loads of the input
+// buffer, unaligned reads of the LDS tile, the wave's LDS fence, the orientation test, sort_table_find (the probe of a
+// launch_sort_table table), rad_walk_chunk (the whole GPL walk as a template over what is read of a record's head), and ByteOut,
+// the byte stream the collate write walks store through.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,18 @@ __device__ __forceinline__ void gpl_wave_lds_sync() {
 }
 // does alignment word w speak for the expected orientation?  (bit 31 set: the read maps forward)
 __device__ __forceinline__ bool gpl_word_fits(uint32_t w, uint32_t ori) { return ori == kGplOriFw ? (w >> 31) != 0 : (w >> 31) == 0; }
+// the open-addressing probe of a launch_sort_table table: key's value, or kSortNoRank when the table has no such key (the key is
+// not the all-ones free mark: a caller whose keys can be all-ones carries that one beside the table)
+__device__ __forceinline__ uint32_t sort_table_find(const uint64_t* __restrict__ tab_key, const uint32_t* __restrict__ tab_val, uint32_t mask, uint64_t key) {
+    uint32_t slot = sort_hash_bc(key) & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe) {   // (at most half the slots are taken: an empty one ends the probe)
+        const uint64_t kk = tab_key[slot];
+        if (kk == key) return tab_val[slot];
+        if (kk == kSortEmptyKey) return kSortNoRank;
+        slot = (slot + 1) & mask;
+    }
+    return kSortNoRank;
+}
 
 // The walk of one mapper chunk by one wave, as k_gpl_parse (afq_gpl.hip) does it, for kernels that want other fields of the head
 // (k_gpl_multi_parse, afq_gpl_multi.hip).  k_gpl_parse keeps its own text of the walk: run through this template it compiled to the
