@@ -1405,6 +1405,10 @@ uint32_t pug_max_blocks() {
 }
 
 uint64_t pug_scratch_words(uint32_t nrec, uint32_t n_ref, bool gene_level) {
+    // k_pug_cell refuses a cell of 2^20 reads or more before it carves its slice: such a cell (the phase kernels take it, up to
+    // 2^22 reads) asks for none.  Sized like the others, a cell of 1.9 M reads and more put the plan's 256 slices above half the
+    // memory budget of a 288 GB device and was refused as out of memory, a million reads below the documented ceiling.
+    if (nrec >= (1u << kVidBits)) return 0;
     const uint64_t R = nrec;
     uint64_t ht_cap = 64;
     while (ht_cap < 2 * R) ht_cap <<= 1;

@@ -89,6 +89,11 @@ def em2_shape(cell, G, usa, min_tier=0):
             else:
                 n = (col + ao,)
             P += any(x in live for x in n)
+    return shape_of_counts(L, P, K, Wc, usa, min_tier)
+
+
+def shape_of_counts(L, P, K, Wc, usa, min_tier=0):
+    """The instance k_em2_setup picks from what it has counted (afq_em2.hip:319-331, 340)."""
     narrow = L + P + 2 <= NARROW_IDS                   # :320
     ids16 = narrow and K < 65535 and Wc <= 65535       # :323
     a, core = lds_all_words(L, P, K, Wc, usa), lds_core_words(L, P, usa)
@@ -302,6 +307,14 @@ def two_entry_em_f64(n, uA, uB, rounds):
         out.append(max(abs(a2 - a) if a2 > 0.01 else 0.0, abs(b2 - b) if b2 > 0.01 else 0.0))
         a, b = a2, b2
     return out
+
+
+def two_entry_em_row_f64(n, uA, uB, rounds):
+    """The same rounds' values: (A, B) after `rounds` rounds."""
+    a, b = (uA + 0.5) * 1e-3, (uB + 0.5) * 1e-3
+    for _ in range(rounds):
+        a, b = uA + n * a / (a + b), uB + n * b / (a + b)
+    return a, b
 
 
 # --- k_boot (afq_em.hip:895-896, 1026, 1111): classes / support entries in LDS up to BOOT_LDS; an entry in more than BOOT_HEAVY
