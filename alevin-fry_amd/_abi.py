@@ -140,6 +140,8 @@ EXPORTS = [
     "afq_collate_multi_limits",
     "afq_atac_collate_rad",
     "afq_atac_collate_limits",
+    "afq_convert_bam_rad",
+    "afq_convert_limits",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -215,6 +217,18 @@ class AfqCollateMultiOpts(C.Structure):
 class AfqAtacCollateStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_uncorrected", C.c_uint64),
                 ("n_kept", C.c_uint64), ("n_cells_out", C.c_uint64), ("n_cells_empty", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqConvertStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_dropped_by_flag", C.c_uint64), ("n_runs", C.c_uint64), ("n_runs_dropped_n", C.c_uint64),
+                ("n_runs_written", C.c_uint64), ("n_alignments_in", C.c_uint64), ("n_alignments_written", C.c_uint64), ("n_long_runs", C.c_uint64),
+                ("n_chunks", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqConvertOpts(C.Structure):
+    """afq_convert_opts of include/afquant_host.h (afq_convert)."""
+    _fields_ = [("bam", C.c_char_p), ("rad_out", C.c_char_p), ("num_threads", C.c_uint32), ("filter_best", C.c_uint32), ("device", C.c_uint32),
+                ("stats_out", C.POINTER(AfqConvertStats))]
 
 
 # afq_gpl_hist_rad's expected_ori, afq_gpl_correct's neighborhood / resolution / decisions

@@ -350,6 +350,17 @@ def load_library(path: str = LIB_PATH):
     lib.afq_atac_collate_rad.restype = C.c_int
     lib.afq_atac_collate_limits.argtypes = [p(C.c_uint32)]
     lib.afq_atac_collate_limits.restype = None
+    lib.afq_convert_bam_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                        p(p(C.c_uint8)), p(C.c_uint64), p(p(C.c_uint64)), p(p(C.c_uint32)), p(C.c_uint64), p(_abi.AfqConvertStats)]
+    lib.afq_convert_bam_rad.restype = C.c_int
+    lib.afq_convert_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_convert_limits.restype = None
+    lib.afq_convert.argtypes = [p(_abi.AfqConvertOpts)]
+    lib.afq_convert.restype = C.c_int
+    lib.afq_convert_prelude_bytes.argtypes = [p(C.c_char_p), C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+    lib.afq_convert_prelude_bytes.restype = C.c_int64
+    lib.afq_view_file.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
+    lib.afq_view_file.restype = C.c_int
     lib.afq_free.argtypes = [C.c_void_p]
     lib.afq_free.restype = None
     lib.afq_get_kernel_times.argtypes = [C.c_void_p, p(AfqKernelTime), C.c_uint32]
@@ -420,6 +431,54 @@ def collate_multi(input_dir, rad_dir, device: int = 0, cmdline: str = ""):
     if rc:
         raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
     return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def convert_limits():
+    """afq_convert_limits: {"parse_tile", "parse_halo", "lane_alns", "scan_block"} of convert - bytes of a span a walk stages per trip,
+    bytes staged behind them, the record count above which the whole wave takes a run, flags a workgroup of the run-number and rank scans takes."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_convert_limits(out)
+    return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "scan_block": int(out[3])}
+
+
+def convert(bam, rad_out, filter_best: bool = False, num_threads: int = 8, device: int = 0):
+    """afq_convert: `convert` - the BAM `bam` (CR / UR tags on its records) as the mapper RAD `rad_out`.  Returns the device call's
+    stats; raises AfqError."""
+    lib = load_library()
+    st = _abi.AfqConvertStats()
+    o = _abi.AfqConvertOpts()
+    o.bam, o.rad_out, o.num_threads, o.filter_best, o.device = os.fsencode(bam), os.fsencode(rad_out), int(num_threads), int(bool(filter_best)), int(device)
+    o.stats_out = C.pointer(st)
+    rc = lib.afq_convert(C.byref(o))
+    if rc:
+        raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def convert_prelude(ref_names, num_chunks: int, cblen: int, ulen: int) -> bytes:
+    """afq_convert_prelude_bytes: the prelude `convert` writes for these reference names, chunk count and lengths."""
+    lib = load_library()
+    names = (C.c_char_p * max(len(ref_names), 1))(*[n.encode() for n in ref_names])
+    n = lib.afq_convert_prelude_bytes(names, len(ref_names), int(num_chunks), int(cblen), int(ulen), None, 0)
+    if n < 0:
+        raise AfqError(int(n), (lib.afq_host_last_error() or b"").decode())
+    buf = (C.c_uint8 * max(int(n), 1))()
+    lib.afq_convert_prelude_bytes(names, len(ref_names), int(num_chunks), int(cblen), int(ulen), buf, int(n))
+    return bytes(buf[: int(n)])
+
+
+def view(rad, header: bool = False) -> str:
+    """afq_view_file: `view` - the records of the RAD file as text, one line per alignment (the reference names first with `header`)."""
+    import tempfile
+
+    lib = load_library()
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "view.txt")
+        rc = lib.afq_view_file(os.fsencode(rad), int(bool(header)), os.fsencode(out))
+        if rc:
+            raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
+        with open(out) as f:
+            return f.read()
 
 
 def atac_collate_limits():
@@ -879,6 +938,34 @@ class Quantifier:
     def collate_limits():
         """The collate walks' and radix passes' limits (module-level collate_limits)."""
         return collate_limits()
+
+    def convert_bam_rad(self, stream, span_off, n_ref: int, bc_bytes: int = 4, umi_bytes: int = 4, filter_best: bool = False, d_ptr: int = 0, n_bytes: int = 0):
+        """afq_convert_bam_rad: the inflated record stream of a BAM in (host bytes, or d_ptr/n_bytes for bytes already on the device) with
+        the table of record starts that cuts it into spans; a dict out: "bytes" (u8: the RAD chunks back to back, headers included),
+        "chunk_off" (u64, n_chunks + 1), "nrec" (u32 per chunk) and "stats"."""
+        off = np.ascontiguousarray(span_off, dtype=np.uint64)
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), n_bytes, 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(stream, dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        u64p = C.POINTER(C.c_uint64)
+        o_b, o_n, o_off, o_nrec, o_nc, st = C.POINTER(C.c_uint8)(), C.c_uint64(), u64p(), C.POINTER(C.c_uint32)(), C.c_uint64(), _abi.AfqConvertStats()
+        self._check(self.lib.afq_convert_bam_rad(self._h, ptr, nb, off.ctypes.data_as(u64p), len(off), int(n_ref), bc_bytes, umi_bytes, int(bool(filter_best)), on_dev,
+                                                 C.byref(o_b), C.byref(o_n), C.byref(o_off), C.byref(o_nrec), C.byref(o_nc), C.byref(st)))
+        n, nc = int(o_n.value), int(o_nc.value)
+        try:
+            mk = lambda p_, k, dt: (np.ctypeslib.as_array(p_, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dt))
+            return {"bytes": mk(o_b, n, np.uint8), "chunk_off": mk(o_off, nc + 1, np.uint64), "nrec": mk(o_nrec, nc, np.uint32),
+                    "stats": {k: int(getattr(st, k)) for k, _ in st._fields_}}
+        finally:
+            for q in (o_b, o_off, o_nrec):
+                self.lib.afq_free(q)
+
+    @staticmethod
+    def convert_limits():
+        """The convert walks' and scans' limits (module-level convert_limits)."""
+        return convert_limits()
 
     def collate_multi_rad(self, chunk_bytes, chunk_off, sample_observed, sample_index, corr_sample, corr_observed, corr_corrected, cell_sample, cell_bc,
                           sample_b0_out, b0_bytes: int = 2, b1_bytes: int = 4, umi_bytes: int = 4, expected_ori="both", d_ptr: int = 0, n_bytes: int = 0):

@@ -1,4 +1,4 @@
-// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`, `afquant collate …`, `afquant atac collate …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
+// afq_cli.cpp — `afquant quant …`, `afquant infer …`, `afquant generate-permit-list …`, `afquant collate …`, `afquant convert …`, `afquant view …`, `afquant atac collate …`: the flag surfaces of `alevin-fry quant` (src/main.rs:294-348 of the
 // reference) and `alevin-fry infer` (src/main.rs:350-365) in front of afq_quantify() / afq_infer_files()
 // (include/afquant_host.h).  Same spellings and defaults; what the reference refuses (--use-eds, -b with a plain
 // resolution, -d with trivial, --summary-stat without -b) is refused here too, with its message.
@@ -28,6 +28,8 @@ static void usage() {
                  "       [--cell-bc-confidence 0.975|a/b] [--device N] [--fill-bytes BYTES]\n"
                  "       afquant collate -i <input-dir> -r <rad-dir> [-t N] [--device N]   (one device fill: -m/--max-records, --memory-limit and\n"
                  "       --collation-mode are accepted and without effect; -c/--compress is not supported)\n"
+                 "       afquant convert -b <file.bam> -o <out.rad> [-t N] [-f] [--device N]   (-f/--filter_best: only a read's best-AS alignments; SAM text is not read)\n"
+                 "       afquant view -r <file.rad> [-H]   (one line per alignment on stdout; -H/--header: the reference names first)\n"
                  "       afquant infer -c <geqc_counts.mtx> -e <gene_eqclass.txt.gz> -o <output-dir> [--usa] [--quant-subset FILE] [-t N]\n");
 }
 
@@ -177,6 +179,44 @@ int main(int argc, char** argv) {
         }
         const int rc = afq_collate(&co);
         if (rc) { std::fprintf(stderr, "afquant collate failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        return 0;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "convert") == 0) {   // bam2rad, src/convert.rs:167-594
+        afq_convert_opts vo{};
+        vo.num_threads = 8;
+        auto need2 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-h" || a == "--help") { usage(); return 0; }
+            else if (a == "-b" || a == "--bam") vo.bam = need2(i);
+            else if (a == "-o" || a == "--output") vo.rad_out = need2(i);
+            else if (a == "-t" || a == "--threads") vo.num_threads = (uint32_t)std::atoi(need2(i));
+            else if (a == "-f" || a == "--filter_best") vo.filter_best = 1;
+            else if (a == "--device") vo.device = (uint32_t)std::atoi(need2(i));
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!vo.bam || !vo.rad_out) {
+            std::fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", vo.bam ? "" : "  --bam <BAM>\n", vo.rad_out ? "" : "  --output <OUTPUT>\n");
+            usage();
+            return 2;
+        }
+        const int rc = afq_convert(&vo);
+        if (rc) { std::fprintf(stderr, "afquant convert failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
+        return 0;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "view") == 0) {   // src/convert.rs:596-709
+        const char* rad = nullptr;
+        int header = 0;
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            if (a == "-h" || a == "--help") { usage(); return 0; }
+            else if (a == "-r" || a == "--rad") { if (i + 1 >= argc) { usage(); return 2; } rad = argv[++i]; }
+            else if (a == "-H" || a == "--header") header = 1;
+            else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+        }
+        if (!rad) { std::fprintf(stderr, "error: the following required arguments were not provided:\n  --rad <RAD>\n"); usage(); return 2; }
+        const int rc = afq_view_file(rad, header, nullptr);
+        if (rc) { std::fprintf(stderr, "afquant view failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         return 0;
     }
     if (argc >= 3 && std::strcmp(argv[1], "atac") == 0 && std::strcmp(argv[2], "collate") == 0) {   // src/main.rs:905-922

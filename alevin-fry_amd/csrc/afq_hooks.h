@@ -11,6 +11,8 @@
 //   AFQ_TEST_ROWS_DELAY_US=n     a range's rows start across the link n microseconds after they were enqueued on the copy stream (a
 //                                host function in front of them): the stand-in for a slow link, under which the next range of the
 //                                slot would compact into row buffers still being read unless it waits for rows_done
+//   AFQ_TEST_CONVERT_SPAN_BYTES=n  afq_convert cuts the record stream into spans of about n bytes instead of 64 KiB: several spans, and
+//                                span starts at chosen records, in a BAM of a few kilobytes (the RAD written does not depend on it)
 // Rounds 1-4 had grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not
 // kept; those alternatives are gone, as are (round 7) the last hooks that selected one and the per-phase clock builds (a
 // measurement build is `make variant DEFS=...` of a scratch copy), and what is left besides the hooks is:

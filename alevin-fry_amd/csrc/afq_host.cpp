@@ -1490,6 +1490,302 @@ int afq_atac_collate(const afq_atac_collate_opts* o) {
 }
 
 // ---------------------------------------------------------------------------
+// `convert` (bam2rad, src/convert.rs:167-594) and `view` (src/convert.rs:596-709).  The container and the BAM header are the
+// host's: BGZF blocks are found by hopping BSIZE of the BC extra field, inflated on threads with zlib's raw inflate, CRC32 and
+// ISIZE verified (SAM/BAM specification, sections 4.1 and 4.2: the record layout rests on that text alone).  The records are
+// the device's (afq_convert_bam_rad).
+namespace {
+struct BgzfBlock { size_t data_off, data_len; uint64_t out_off; uint32_t isize, crc; };
+inline uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+inline uint32_t le32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
+
+int bgzf_plan(const uint8_t* in, size_t n, std::vector<BgzfBlock>& blocks, uint64_t& total) {
+    total = 0;
+    for (size_t p = 0; p < n;) {
+        const std::string at = "BGZF block " + std::to_string(blocks.size()) + ": ";
+        if (n - p < 18) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated: " + std::to_string(n - p) + " bytes where a block header has 18");
+        const uint8_t* h = in + p;
+        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return hfail(AFQ_ERR_BAD_INPUT, at + "bad gzip magic (1f 8b 08 with an extra field is expected)");
+        const size_t xlen = le16(h + 10);
+        if (n - p < 12 + xlen) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated inside the extra field");
+        long bsize = -1;
+        for (size_t e = 12; e + 4 <= 12 + xlen;) {
+            const size_t slen = le16(h + e + 2);
+            if (h[e] == 'B' && h[e + 1] == 'C' && slen == 2 && e + 6 <= 12 + xlen) bsize = (long)le16(h + e + 4);
+            e += 4 + slen;
+        }
+        if (bsize < 0) return hfail(AFQ_ERR_BAD_INPUT, at + "no BC extra field: not a BGZF block");
+        const size_t blk = (size_t)bsize + 1;
+        if (blk < 12 + xlen + 8) return hfail(AFQ_ERR_BAD_INPUT, at + "BSIZE is smaller than the block's own header and trailer");
+        if (n - p < blk) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated: the block has " + std::to_string(blk) + " bytes, the file " + std::to_string(n - p) + " more");
+        BgzfBlock b{p + 12 + xlen, blk - (12 + xlen) - 8, total, le32(h + blk - 4), le32(h + blk - 8)};
+        if (b.isize > 65536) return hfail(AFQ_ERR_BAD_INPUT, at + "ISIZE " + std::to_string(b.isize) + " is above the 65536 bytes of a BGZF block");
+        total += b.isize;
+        blocks.push_back(b);
+        p += blk;
+    }
+    return 0;
+}
+
+int bgzf_inflate(const uint8_t* in, const std::vector<BgzfBlock>& blocks, uint8_t* out, unsigned nthreads) {
+    std::atomic<size_t> next{0};
+    std::mutex mu;
+    size_t bad_at = SIZE_MAX;
+    std::string bad_msg;
+    auto work = [&]() {
+        for (;;) {
+            const size_t i = next.fetch_add(1);
+            if (i >= blocks.size()) return;
+            const BgzfBlock& b = blocks[i];
+            uint8_t none = 0;
+            z_stream zs{};
+            std::string msg;
+            if (inflateInit2(&zs, -15) != Z_OK) msg = "zlib could not be initialised";
+            else {
+                zs.next_in = const_cast<uint8_t*>(in + b.data_off); zs.avail_in = (uInt)b.data_len;
+                zs.next_out = b.isize ? out + b.out_off : &none; zs.avail_out = b.isize ? b.isize : 1;
+                const int rc = inflate(&zs, Z_FINISH);
+                if (rc != Z_STREAM_END) msg = std::string("the deflate stream is corrupt or longer than ISIZE (zlib: ") + (zs.msg ? zs.msg : "no end of stream") + ")";
+                else if (zs.total_out != b.isize) msg = "ISIZE says " + std::to_string(b.isize) + " bytes, the deflate stream holds " + std::to_string(zs.total_out);
+                else if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), b.isize ? out + b.out_off : &none, b.isize) != b.crc) msg = "bad CRC32";
+                inflateEnd(&zs);
+            }
+            if (!msg.empty()) { std::lock_guard<std::mutex> g(mu); if (i < bad_at) { bad_at = i; bad_msg = msg; } }
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nthreads; ++t) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    if (bad_at != SIZE_MAX) return hfail(AFQ_ERR_BAD_INPUT, "BGZF block " + std::to_string(bad_at) + ": " + bad_msg);
+    return 0;
+}
+
+// the CR and UR strings of the record at the stream's start: their lengths are cblen and ulen (convert.rs:263-320)
+int convert_first_lengths(const uint8_t* s, uint64_t n, uint32_t& cblen, uint32_t& ulen) {
+    const std::string at = "record 0: ";
+    if (n < 4) return hfail(AFQ_ERR_BAD_INPUT, at + "the stream ends inside block_size");
+    const uint64_t bs = le32(s);
+    if (bs > n - 4) return hfail(AFQ_ERR_BAD_INPUT, at + "block_size runs past the stream");
+    const uint64_t need = bs >= 32 ? 32 + (uint64_t)s[12] + 4ull * le16(s + 16) + ((uint64_t)le32(s + 20) + 1) / 2 + le32(s + 20) : ~0ull;
+    if (need > bs) return hfail(AFQ_ERR_BAD_INPUT, at + "block_size is too small for the record's fixed fields, name, CIGAR and sequence");
+    const uint8_t* b = s + 4;
+    int have[2] = {0, 0}; bool is_z[2] = {false, false}; uint64_t len[2] = {0, 0};
+    for (uint64_t g = need; g < bs;) {
+        if (bs - g < 3) return hfail(AFQ_ERR_BAD_INPUT, at + "the aux fields do not end at the record's end");
+        const uint8_t t0 = b[g], t1 = b[g + 1], ty = b[g + 2];
+        g += 3;
+        uint64_t sz = 0, zl = 0;
+        switch (ty) {
+            case 'A': case 'c': case 'C': sz = 1; break;
+            case 's': case 'S': sz = 2; break;
+            case 'i': case 'I': case 'f': sz = 4; break;
+            case 'Z': case 'H': { const uint64_t v0 = g; while (g < bs && b[g]) ++g; if (g == bs) return hfail(AFQ_ERR_BAD_INPUT, at + "an aux string without its NUL"); zl = g - v0; ++g; break; }
+            case 'B': {
+                if (bs - g < 5) return hfail(AFQ_ERR_BAD_INPUT, at + "the aux fields do not end at the record's end");
+                const uint8_t sub = b[g];
+                const uint64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                if (!es || (uint64_t)le32(b + g + 1) * es > bs - g - 5) return hfail(AFQ_ERR_BAD_INPUT, at + "a B array of unknown subtype or past the record's end");
+                g += 5 + (uint64_t)le32(b + g + 1) * es;
+                break;
+            }
+            default: return hfail(AFQ_ERR_BAD_INPUT, at + "an aux field of unknown type");
+        }
+        if (sz) { if (bs - g < sz) return hfail(AFQ_ERR_BAD_INPUT, at + "the aux fields do not end at the record's end"); g += sz; }
+        const int w = (t0 == 'C' && t1 == 'R') ? 0 : (t0 == 'U' && t1 == 'R') ? 1 : -1;
+        if (w >= 0 && !have[w]) { have[w] = 1; is_z[w] = ty == 'Z'; len[w] = zl; }
+    }
+    if (!have[0]) return hfail(AFQ_ERR_BAD_INPUT, at + "Input record missing CR tag!");
+    if (!is_z[0]) return hfail(AFQ_ERR_BAD_INPUT, at + "cannot convert non-string (Z) tag into barcode string.");
+    if (!have[1]) return hfail(AFQ_ERR_BAD_INPUT, at + "Input record missing UR tag!");
+    if (!is_z[1]) return hfail(AFQ_ERR_BAD_INPUT, at + "cannot convert non-string (Z) tag into umi string.");
+    if (len[0] < 1 || len[0] > 32) return hfail(AFQ_ERR_BAD_INPUT, at + "cannot encode barcode of length " + std::to_string(len[0]) + ": 1 to 32 bases fit");
+    if (len[1] < 1 || len[1] > 32) return hfail(AFQ_ERR_BAD_INPUT, at + "cannot encode umi of length " + std::to_string(len[1]) + ": 1 to 32 bases fit");
+    cblen = (uint32_t)len[0]; ulen = (uint32_t)len[1];
+    return 0;
+}
+uint32_t convert_width(uint32_t len) { return len <= 4 ? 1 : len <= 8 ? 2 : len <= 16 ? 4 : 8; }   // convert.rs:323-343
+
+// what convert.rs:238-370 writes in front of the chunks
+void convert_prelude(const std::vector<std::string>& names, uint64_t num_chunks, uint32_t cblen, uint32_t ulen, std::vector<uint8_t>& out) {
+    auto put = [&](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
+    auto put16 = [&](uint16_t v) { put(&v, 2); };
+    auto tag = [&](const char* name, uint8_t type) { put16((uint16_t)std::strlen(name)); put(name, std::strlen(name)); put(&type, 1); };
+    auto int_type = [](uint32_t w) -> uint8_t { return w == 1 ? 1 : w == 2 ? 2 : w == 4 ? 3 : 4; };
+    const uint8_t paired = 0;
+    const uint64_t n_ref = names.size();
+    put(&paired, 1); put(&n_ref, 8);
+    for (auto& s : names) { put16((uint16_t)s.size()); put(s.data(), s.size()); }
+    put(&num_chunks, 8);
+    put16(2); tag("cblen", 2); tag("ulen", 2);
+    put16(2); tag("b", int_type(convert_width(cblen))); tag("u", int_type(convert_width(ulen)));
+    put16(1); tag("compressed_ori_refid", 3);
+    put16((uint16_t)cblen); put16((uint16_t)ulen);
+}
+bool ends_with(const std::string& s, const char* e) { const size_t n = std::strlen(e); return s.size() >= n && s.compare(s.size() - n, n, e) == 0; }
+}  // namespace
+
+int64_t afq_convert_prelude_bytes(const char* const* ref_names, uint64_t n_ref, uint64_t num_chunks, uint32_t cblen, uint32_t ulen, uint8_t* out, size_t cap) {
+    if ((!ref_names && n_ref) || cblen < 1 || cblen > 32 || ulen < 1 || ulen > 32) return hfail(AFQ_ERR_INVALID_ARG, "null names, or a length outside 1..32");
+    std::vector<std::string> names;
+    for (uint64_t i = 0; i < n_ref; ++i) names.emplace_back(ref_names[i]);
+    std::vector<uint8_t> b;
+    convert_prelude(names, num_chunks, cblen, ulen, b);
+    if (out) { if (b.size() > cap) return hfail(AFQ_ERR_INVALID_ARG, "output buffer too small"); std::memcpy(out, b.data(), b.size()); }
+    return (int64_t)b.size();
+}
+
+int afq_convert(const afq_convert_opts* o) {
+    if (!o || !o->bam || !o->rad_out) return hfail(AFQ_ERR_INVALID_ARG, "null option: the BAM (-b) and the output RAD (-o) are required");
+    const std::string in = o->bam, outp = o->rad_out;
+    if (ends_with(in, ".sam") || ends_with(in, ".SAM")) return hfail(AFQ_ERR_UNSUPPORTED, "convert: SAM text input is not supported; only BAM is read (convert the file to BAM first)");
+    if (!ends_with(in, ".bam") && !ends_with(in, ".BAM")) return hfail(AFQ_ERR_BAD_INPUT, "unsupported input file format, must end with bam/BAM or sam/SAM");
+    PhaseClock pc;
+    MappedFile mf;
+    if (!mf.open(in)) return hfail(AFQ_ERR_BAD_INPUT, "could not open the input BAM \"" + in + "\"");
+    std::fprintf(stderr, "Bam file size in bytes %llu\n", (unsigned long long)mf.n);
+    // ---- the container
+    std::vector<BgzfBlock> blocks;
+    uint64_t total = 0;
+    if (int rc = bgzf_plan(mf.p, mf.n, blocks, total)) return rc;
+    const unsigned nthreads = o->num_threads > 1 ? o->num_threads - 1 : 1;   // convert.rs:205-210
+    std::fprintf(stderr, "parsing BAM file using %u decompression threads\n", nthreads);
+    std::unique_ptr<uint8_t[]> plain(new (std::nothrow) uint8_t[total + 1]);
+    if (!plain) return hfail(AFQ_ERR_OOM, "convert: " + std::to_string(total) + " bytes for the inflated BAM could not be allocated");
+    if (int rc = bgzf_inflate(mf.p, blocks, plain.get(), nthreads)) return rc;
+    pc.lap("convert: BGZF plan + inflate");
+    // ---- the BAM header: magic, l_text, text, n_ref x (l_name, name, l_ref)
+    Cursor c{plain.get(), (size_t)total};
+    const uint32_t magic = c.get<uint32_t>();
+    if (!c.ok || magic != 0x014d4142u) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad magic (BAM\\1 is expected)");
+    const int32_t l_text = c.get<int32_t>();
+    if (!c.ok || l_text < 0 || (uint64_t)l_text > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: the text runs past the file");
+    c.p += (size_t)l_text;
+    const int32_t n_ref = c.get<int32_t>();
+    if (!c.ok || n_ref < 0) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad reference count");
+    std::vector<std::string> names;
+    for (int32_t i = 0; i < n_ref; ++i) {
+        const int32_t l_name = c.get<int32_t>();
+        if (!c.ok || l_name < 1 || (uint64_t)l_name > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + ": the name runs past the file");
+        std::string nm = c.str((size_t)l_name);
+        nm.resize(std::strlen(nm.c_str()));   // (l_name counts the NUL)
+        if (nm.size() > 0xFFFF) return hfail(AFQ_ERR_UNSUPPORTED, "BAM header: reference " + std::to_string(i) + ": a name of 64 KiB or more does not fit the RAD header");
+        names.push_back(std::move(nm));
+        (void)c.get<int32_t>();   // l_ref
+        if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + " runs past the file");
+    }
+    std::fprintf(stderr, "ref count: %d \n", n_ref);
+    // ---- the first record's lengths, the span table (one hop per record, four bytes read of each)
+    const uint8_t* stream = plain.get() + c.p;
+    const uint64_t sn = total - c.p;
+    if (sn == 0) return hfail(AFQ_ERR_BAD_INPUT, "bam file had no records!");
+    uint32_t cblen = 0, ulen = 0;
+    if (int rc = convert_first_lengths(stream, sn, cblen, ulen)) return rc;
+    const uint64_t span_bytes = (uint64_t)std::max(64L, afq::test_hook_long("CONVERT_SPAN_BYTES", 1L << 16));   // (the hook: several spans in a small file)
+    std::vector<uint64_t> spans;
+    {
+        uint64_t next = 0, idx = 0;
+        for (uint64_t p = 0; p < sn; ++idx) {
+            if (sn - p < 4) return hfail(AFQ_ERR_BAD_INPUT, "record " + std::to_string(idx) + ": the stream ends inside block_size");
+            const uint64_t bs = le32(stream + p);
+            if (bs > sn - p - 4) return hfail(AFQ_ERR_BAD_INPUT, "record " + std::to_string(idx) + ": block_size runs past the stream");
+            if (p >= next) { spans.push_back(p); next = p + span_bytes; }
+            p += 4 + bs;
+        }
+    }
+    if (spans.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "convert: 2^32 or more spans");
+    pc.lap("convert: header + span table");
+    // ---- the device: one fill
+    CtxPtr ctx;
+    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
+    uint8_t* ob = nullptr; uint64_t on = 0, n_chunks = 0, *ooff = nullptr; uint32_t* onrec = nullptr;
+    afq_convert_stats st{};
+    int rc = afq_convert_bam_rad(ctx.get(), stream, sn, spans.data(), (uint32_t)spans.size(), (uint32_t)n_ref, convert_width(cblen), convert_width(ulen), o->filter_best != 0, 0,
+                                 &ob, &on, &ooff, &onrec, &n_chunks, &st);
+    if (rc) return hfail(rc, afq_last_error(ctx.get()));
+    struct Freer { void *a, *b, *c; ~Freer() { afq_free(a); afq_free(b); afq_free(c); } } fr{ob, ooff, onrec};
+    pc.lap("convert: device");
+    if (o->stats_out) *o->stats_out = st;
+    // ---- the RAD: the parent directory is created, an existing file replaced (convert.rs:181-188)
+    const size_t slash = outp.find_last_of('/');
+    if (slash != std::string::npos && slash > 0 && mkdirs_checked(outp.substr(0, slash))) return hfail(AFQ_ERR_BAD_INPUT, "could not create the directory of \"" + outp + "\"");
+    std::remove(outp.c_str());
+    std::vector<uint8_t> pre;
+    convert_prelude(names, n_chunks, cblen, ulen, pre);
+    FilePtr f(std::fopen(outp.c_str(), "wb"));
+    bool ok = (bool)f;
+    if (ok) ok = std::fwrite(pre.data(), 1, pre.size(), f.get()) == pre.size();
+    for (uint64_t off = 0; ok && off < on;) {
+        const size_t len = (size_t)std::min<uint64_t>(on - off, 1ull << 30);
+        ok = std::fwrite(ob + off, 1, len, f.get()) == len;
+        off += len;
+    }
+    ok = ok && std::fflush(f.get()) == 0;
+    if (!ok) { f.reset(); std::remove(outp.c_str()); return hfail(AFQ_ERR_BAD_INPUT, "could not write " + outp); }
+    pc.lap("convert: write");
+    std::fprintf(stderr, "%llu chunks written\n", (unsigned long long)n_chunks);
+    std::fprintf(stderr, "converted %llu records (%llu unmapped or supplementary) in %llu reads: %llu written with %llu of %llu alignments, %llu dropped for two N or more; %llu output bytes\n",
+                 (unsigned long long)st.n_records, (unsigned long long)st.n_dropped_by_flag, (unsigned long long)st.n_runs, (unsigned long long)st.n_runs_written,
+                 (unsigned long long)st.n_alignments_written, (unsigned long long)st.n_alignments_in, (unsigned long long)st.n_runs_dropped_n, (unsigned long long)st.out_bytes);
+    return 0;
+}
+
+int afq_view_file(const char* rad, int print_header, const char* out_path) {
+    if (!rad) return hfail(AFQ_ERR_INVALID_ARG, "null RAD path");
+    MappedFile mf;
+    if (!mf.open(rad)) return hfail(AFQ_ERR_BAD_INPUT, std::string("could not open the RAD file \"") + rad + "\"");
+    RadPrelude P;
+    if (int rc = parse_prelude(mf.p, mf.n, P, true)) return rc;
+    // the b and u read tags must be integers (convert.rs:619-639); the records are read as na, b, u, na x u32
+    const TagDesc* bt = nullptr; const TagDesc* ut = nullptr;
+    for (auto& t : P.read_tags) {
+        if (t.name != "b" && t.name != "u") continue;
+        if (t.type < 1 || t.type > 4) return hfail(AFQ_ERR_UNSUPPORTED, "currently only RAD types 1--4 are supported for 'b' and 'u' tags.");
+        (t.name == "b" ? bt : ut) = &t;
+    }
+    if (!bt) return hfail(AFQ_ERR_BAD_INPUT, "barcode type tag was missing!");
+    if (!ut) return hfail(AFQ_ERR_BAD_INPUT, "umi type tag was missing!");
+    if (!P.file_tag_vals.count("cblen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain cblen");
+    if (!P.file_tag_vals.count("ulen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain ulen");
+    if (P.read_tags.size() != 2 || P.read_tags[0].name != "b" || P.aln_tags.size() != 1 || P.aln_tags[0].type != 3)
+        return hfail(AFQ_ERR_UNSUPPORTED, "view: only records `na, b, u, na x u32` are read (read tags b, u; one u32 alignment tag)");
+    const uint64_t cblen = P.file_tag_vals["cblen"], ulen = P.file_tag_vals["ulen"];
+    if (cblen > 32 || ulen > 32) return hfail(AFQ_ERR_BAD_INPUT, "view: cblen or ulen above 32");
+    FILE* fo = out_path ? std::fopen(out_path, "w") : stdout;
+    if (!fo) return hfail(AFQ_ERR_BAD_INPUT, std::string("could not write \"") + out_path + "\"");
+    struct Closer { FILE* f; bool own; ~Closer() { if (own) std::fclose(f); else std::fflush(f); } } closer{fo, out_path != nullptr};
+    if (print_header)
+        for (size_t i = 0; i < P.ref_names.size(); ++i) std::fprintf(fo, "%zu:%s\n", i, P.ref_names[i].c_str());
+    const uint32_t bw = P.bc_bytes, uw = P.umi_bytes;
+    auto field = [&](size_t at, uint32_t w) { uint64_t v = 0; std::memcpy(&v, mf.p + at, w); return v; };
+    uint64_t id = 0;
+    size_t p = P.first_chunk;
+    for (uint64_t ch = 0; ch < P.num_chunks; ++ch) {
+        const std::string at = "chunk " + std::to_string(ch) + ": ";
+        if (mf.n - p < 8) return hfail(AFQ_ERR_BAD_INPUT, at + "the file ends inside the chunk header");
+        const uint32_t nbytes = le32(mf.p + p), nrec = le32(mf.p + p + 4);
+        if (nbytes < 8 || nbytes > mf.n - p) return hfail(AFQ_ERR_BAD_INPUT, at + "nbytes runs past the file");
+        const size_t end = p + nbytes;
+        size_t q = p + 8;
+        for (uint32_t r = 0; r < nrec; ++r, ++id) {
+            if (end - q < 4 + bw + uw) return hfail(AFQ_ERR_BAD_INPUT, at + "the records do not tile the chunk");
+            const uint32_t na = le32(mf.p + q);
+            if (na > (end - q - 4 - bw - uw) / 4) return hfail(AFQ_ERR_BAD_INPUT, at + "the records do not tile the chunk");
+            const std::string cb = bc_to_string(field(q + 4, bw), (uint32_t)cblen), um = bc_to_string(field(q + 4 + bw, uw), (uint32_t)ulen);
+            q += 4 + bw + uw;
+            for (uint32_t i = 0; i < na; ++i, q += 4) {
+                const uint32_t w = le32(mf.p + q), rid = w & 0x7FFFFFFFu;
+                if (rid >= P.ref_names.size()) return hfail(AFQ_ERR_BAD_INPUT, at + "a reference id is not below ref_count");
+                std::fprintf(fo, "ID:%llu\tHI:%u\tNH:%u\tCB:%s\tUMI:%s\tDIR:%s\t%s\n", (unsigned long long)id, i + 1, na, cb.c_str(), um.c_str(), (w >> 31) ? "true" : "false",
+                             P.ref_names[rid].c_str());
+            }
+        }
+        p = end;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // multi-barcode `collate` (do_collate_multi_bc_fast, src/collate.rs:1415-1920).  libradicl's collate_multi_barcode is not among the
 // reference's sources; where collate.rs leaves a rule to it, the choice is DESIGN.md 3.4h's.
 namespace {

@@ -380,6 +380,59 @@ void launch_atac_collate_runs(hipStream_t s, const uint64_t* sorted, uint32_t n,
 // nrec[j], cell[j] = c, and its (nbytes, nrec) header into out; dest[slot] = R i + 8 (rank[cell] + 1) for sorted position i
 void launch_atac_collate_heads(hipStream_t s, const uint64_t* sorted, uint32_t n, uint32_t n_cells, uint32_t rec_bytes, const uint32_t* first, const uint32_t* rank,
                                uint64_t* off, uint32_t* nrec, uint32_t* cell, uint64_t* dest, uint8_t* out, DevStatus* st);
+// `convert`: the alignment records of a BAM (the inflated stream behind its header) as the chunks of a mapper RAD (afq_convert.hip;
+// bam2rad, src/convert.rs:167-594 of the reference).  A wave walks a host-made span of records (tiles of kGplParseTile bytes and
+// kGplParseHalo behind them, as the RAD walks); the kept records are compacted, cut into runs of one read name, their aux fields
+// scanned, and the runs laid out by launch_collate_scan over the sort words  chunk << 32 | written rank, chunk = rank / 10 001.
+constexpr uint32_t kConvertLaneAlns = 16;           // a run with more records than this is read and written by the whole wave
+constexpr uint32_t kConvertChunkRuns = 10001;       // written runs of an output chunk (convert.rs:473 tests before :551 counts)
+constexpr uint32_t kConvertRecFixed = 36;           // block_size and the fixed fields of a BAM record
+constexpr uint32_t kConvertTileRecs = kGplParseTile / kConvertRecFixed + 1;
+constexpr uint32_t kConvertScanItems = 16, kConvertScanBlock = 256 * kConvertScanItems;   // words a workgroup of the flag scans takes
+// the error word: record index << 8 | code, the smallest wins (atomicMin), so the record named does not depend on the schedule
+constexpr uint32_t kConvErrRecord = 1;     // block_size too small for the record's own fields, or past the span's end; aux that does not tile the record
+constexpr uint32_t kConvErrRef = 2;        // a kept record's refID is not in [0, n_ref)
+constexpr uint32_t kConvErrTagMissing = 3; // a run head without CR or UR
+constexpr uint32_t kConvErrTagType = 4;    // a run head whose CR or UR is not of type Z
+constexpr uint32_t kConvErrBase = 5;       // a base outside ACGTN in the barcode or UMI of a run that is written
+constexpr uint32_t kConvErrScore = 6;      // -f: a record of a written run without an integer AS
+constexpr uint64_t kConvNoErr = ~0ull;
+enum ConvertStat { kConvRunsDroppedN = 0, kConvAlnIn, kConvAlnWritten, kConvLongRuns, kConvStatCount };
+struct ConvertArgs {
+    const uint8_t* bytes; uint64_t n_bytes; const uint64_t* span_off; uint32_t n_spans; uint32_t n_ref;
+    uint32_t bc_bytes, umi_bytes, filter_best;
+    uint32_t* span_cnt;          // count walk: [n_spans][2] records, kept records
+    const uint32_t* span_base;   // fill walk: [n_spans][2] records, kept records in front of the span
+    uint32_t n_kept;
+    uint64_t* rec_off;           // [n_kept] where the kept record's block_size stands
+    uint32_t* rec_idx;           // [n_kept] its index among the records of the file (for the error word)
+    uint32_t* word;              // [n_kept] refID | 0x80000000 when flag 0x10 is clear
+    uint32_t* head;              // [n_kept + 1] heads: 1 where the name differs from the predecessor's, [n_kept] = 0; scanned in place:
+                                 //              runs in front of record k, so k's run is head[k + 1] - 1 and head[n_kept] = n_runs
+    int32_t* score;              // [n_kept] -f: AS, and has_score: was there an integer one
+    uint8_t* has_score;
+    uint32_t n_runs;
+    uint32_t* run_first;         // [n_runs + 1] the run's first kept record ([n_runs] = n_kept)
+    uint64_t* run_bc; uint64_t* run_umi;   // [n_runs] the head's CR and UR, two bits a base
+    uint32_t* run_flag;          // [n_runs + 1] aux: 1 where the run is dropped for two N; runs: 1 where it is written ([n_runs] = 0); scanned in place
+    uint32_t* run_na; int32_t* run_max;    // [n_runs] alignments written, -f: the best AS
+    uint64_t* stat;              // [kConvStatCount]
+    uint64_t* key; uint2* rec;   // [n_written] place: chunk << 32 | rank; (run, bytes of the run as written)
+    const uint64_t* dest;        // [n_written] write: byte offset of the run in out
+    uint32_t n_written;
+    uint8_t* out;
+    unsigned long long* err;     // the error word
+    DevStatus* st;               // kErrCollateChunk from place and the heads
+};
+void launch_convert_count(hipStream_t s, const ConvertArgs& a);
+void launch_convert_fill(hipStream_t s, const ConvertArgs& a);
+void launch_convert_heads(hipStream_t s, const ConvertArgs& a);   // head[] (unscanned)
+// in-place exclusive scan of n words by ceil(n / kConvertScanBlock) workgroups (block_sum: that many words)
+void launch_convert_scan(hipStream_t s, uint32_t* v, uint64_t n, uint32_t* block_sum);
+void launch_convert_aux(hipStream_t s, const ConvertArgs& a);     // behind the scan of head[]: run_first, run_bc, run_umi, run_flag, score
+void launch_convert_runs(hipStream_t s, const ConvertArgs& a);    // run_na, run_max, run_flag := written, stat
+void launch_convert_place(hipStream_t s, const ConvertArgs& a);   // behind the scan of run_flag[]: key, rec
+void launch_convert_write(hipStream_t s, const ConvertArgs& a);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

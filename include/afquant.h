@@ -569,6 +569,47 @@ int afq_atac_collate_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, con
 void afq_atac_collate_limits(uint32_t out[4]);
 
 /*
+ * `convert`, the device half (bam2rad, src/convert.rs:167-594 of the reference): the alignment records of a BAM become the chunks
+ * of a mapper RAD.  `bytes` is the INFLATED record stream behind the BAM header (host memory, or device memory when bytes_on_device);
+ * span_off[n_spans] (host memory) are record starts, span_off[0] == 0, ascending: span i is [span_off[i], span_off[i + 1]), the
+ * last one ends at n_bytes.  n_ref is the BAM header's reference count; bc_bytes / umi_bytes (1, 2, 4 or 8) are the widths of the
+ * RAD's b and u fields.
+ * A record whose flag has 0x4 or 0x800 does not exist for what follows.  The others are cut into runs of consecutive records with
+ * byte-equal names; a run's barcode and UMI are the CR and UR strings of its first record, two bits a base (A0 C1 G2 T3, first base
+ * most significant, one N as A, the low bc_bytes / umi_bytes bytes); a run with two N or more in either is dropped.  Every record
+ * of a run is the alignment word refID | 0x80000000 (the bit when flag 0x10 is clear), in input order; with filter_best only the
+ * records whose integer AS equals the run's largest.  A written run is `na:u32, b, u, na x u32`; 10 001 written runs make a chunk
+ * `nbytes:u32, nrec:u32, records`, the last chunk holds the rest.
+ * Out (malloc'd, freed with afq_free): the chunks back to back, out_chunk_off[n_chunks + 1] (the last entry: out_n_bytes),
+ * out_nrec[n_chunks].  The output is a function of the input alone.
+ * AFQ_ERR_BAD_INPUT "record <index in the stream>: ...": a block_size too small for the record's fixed fields, name, CIGAR and
+ * sequence or past the span's end; aux fields that do not end at the record's end (scanned on run heads, and on every kept record
+ * under filter_best); a kept record's refID outside [0, n_ref); a run head without CR / UR or with one not of type Z; a base outside
+ * ACGTN in a written run; under filter_best a written run's record without an integer AS.  The context stays usable.
+ * AFQ_ERR_UNSUPPORTED: 2^32 records or more, an output chunk of 4 GiB or more.  AFQ_ERR_OOM (with the sizes) when input and about
+ * 120 bytes a kept record do not fit the device: one call is one device fill.  AFQ_ERR_INVALID_ARG: a null pointer, a bad width, a
+ * span table that does not begin at 0, ascend and stay below n_bytes.
+ */
+typedef struct afq_convert_stats {
+    uint64_t n_records;            /* records of the stream                                              */
+    uint64_t n_dropped_by_flag;    /* ... with flag 0x4 or 0x800                                         */
+    uint64_t n_runs;               /* runs of the other records                                          */
+    uint64_t n_runs_dropped_n;     /* ... dropped for two N or more in CR or UR                          */
+    uint64_t n_runs_written;
+    uint64_t n_alignments_in;      /* records of the written runs                                        */
+    uint64_t n_alignments_written; /* ... that were written (all of them without filter_best)            */
+    uint64_t n_long_runs;          /* written runs of more than afq_convert_limits()[2] records: the whole wave takes them */
+    uint64_t n_chunks;
+    uint64_t out_bytes;            /* length of out_bytes                                                */
+} afq_convert_stats;
+int afq_convert_bam_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const uint64_t* span_off, uint32_t n_spans, uint32_t n_ref, uint32_t bc_bytes,
+                        uint32_t umi_bytes, int filter_best, int bytes_on_device, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off,
+                        uint32_t** out_nrec, uint64_t* out_n_chunks, afq_convert_stats* stats);
+/* out[0] = bytes of a span a convert walk stages per trip, out[1] = bytes staged behind them, out[2] = a run with more records
+ * than this is taken by the whole wave, out[3] = flags a workgroup of the run-number and rank scans takes (the layout scan's take half as many).  For tests. */
+void afq_convert_limits(uint32_t out[4]);
+
+/*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the
  * number of kernels, or a negative error.  `name[i]` points to static storage.

@@ -300,6 +300,37 @@ int64_t afq_gpl_multi_routing(const uint8_t* text, size_t n, int reverse, uint32
  * (AFQ_ERR_INVALID_ARG), fitting b0_bytes (AFQ_ERR_BAD_INPUT), at most 2^31 of them (AFQ_ERR_UNSUPPORTED).  0 when they pass. */
 int afq_gpl_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed, uint64_t n_entries);
 
+/* The options of `alevin-fry convert` (src/main.rs, bam2rad of src/convert.rs:167-594). */
+struct afq_convert_stats;
+typedef struct afq_convert_opts {
+    const char* bam;            /* -b : the input; must end in .bam or .BAM (SAM text is not read)                          */
+    const char* rad_out;        /* -o : the RAD file to write; its parent directory is created, an existing file replaced  */
+    uint32_t num_threads;       /* -t : BGZF blocks are inflated on max(1, num_threads - 1) threads (convert.rs:205-210)   */
+    uint32_t filter_best;       /* -f : keep only the alignments of a read whose AS equals the read's best                 */
+    uint32_t device;
+    struct afq_convert_stats* stats_out;   /* optional */
+} afq_convert_opts;
+/* Runs the whole `convert` sub-command in ONE device fill: the BGZF container is inflated on the host (every block's CRC32 and
+ * ISIZE verified; an empty block mid-file and a missing EOF marker are accepted), the BAM header read, the lengths of CR / UR of the
+ * file's first record taken for cblen / ulen, the records handed to afq_convert_bam_rad (include/afquant.h has the record semantics
+ * and their errors), and the prelude (convert.rs:238-370) and chunks written only after the device call succeeded.
+ * AFQ_ERR_UNSUPPORTED: a path ending in .sam / .SAM.  AFQ_ERR_BAD_INPUT: any other ending ("unsupported input file format, must end
+ * with bam/BAM or sam/SAM"), a file that cannot be opened, "BGZF block <i>: ..." for a truncated block, a bad gzip magic, a bad CRC
+ * or ISIZE, a bad BAM header, a file without records, a first record without CR / UR, with one that is not of type Z, or of length
+ * 0 or above 32, "record <i>: ..." for a block_size that runs past the stream; also an output file that cannot be created or
+ * written ("could not write ..."): the library has no code for I/O failures, and its other writers report theirs the same way. */
+int afq_convert(const afq_convert_opts* opts);
+/* The prelude afq_convert writes in front of the chunks (convert.rs:238-370): is_paired = 0, the reference names, num_chunks, the
+ * file tags cblen:u16 and ulen:u16, the read tags b and u (1, 2, 4 or 8 bytes for lengths 1-4, 5-8, 9-16, 17-32), the alignment
+ * tag compressed_ori_refid:u32, the two values.  Returns its length (out may be NULL), or a negative AFQ_ERR_ code.  For tests:
+ * it lets the prelude be compared without a device. */
+int64_t afq_convert_prelude_bytes(const char* const* ref_names, uint64_t n_ref, uint64_t num_chunks, uint32_t cblen, uint32_t ulen, uint8_t* out, size_t cap);
+/* `alevin-fry view` (src/convert.rs:596-709): the records of a RAD file with read tags b and u as text, one line per alignment,
+ * `ID:{id}\tHI:{i+1}\tNH:{n}\tCB:{bases}\tUMI:{bases}\tDIR:{true|false}\t{ref name}`, behind the lines `i:name` of the references when
+ * print_header is set.  out_path NULL writes to stdout.  AFQ_ERR_UNSUPPORTED: a b or u tag that is not an integer of 1-8 bytes.
+ * AFQ_ERR_BAD_INPUT: a missing b / u / cblen / ulen tag, chunks that do not tile the file, a reference id that names no reference. */
+int afq_view_file(const char* rad, int print_header, const char* out_path);
+
 /* Runs the whole `quant` sub-command.  Returns 0 or a negative AFQ_ERR_* code; message via afq_host_last_error(). */
 int afq_quantify(const afq_quant_opts* opts);
 const char* afq_host_last_error(void);
