@@ -142,6 +142,9 @@ EXPORTS = [
     "afq_atac_collate_limits",
     "afq_convert_bam_rad",
     "afq_convert_limits",
+    "afq_snappy_frame_encode",
+    "afq_snappy_limits",
+    "afq_set_collate_compress",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
     "afq_range_pipeline_counts",
@@ -214,15 +217,30 @@ class AfqCollateMultiOpts(C.Structure):
                 ("device", C.c_uint32), ("cmdline", C.c_char_p), ("stats_out", C.POINTER(AfqCollateMultiStats))]
 
 
+class AfqCollateOpts(C.Structure):
+    """afq_collate_opts of include/afquant_host.h (afq_collate, afq_collate_sz)."""
+    _fields_ = AfqCollateMultiOpts._fields_[:-1] + [("stats_out", C.POINTER(AfqCollateStats))]
+
+
 class AfqAtacCollateStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_unmapped", C.c_uint64), ("n_multimapped", C.c_uint64), ("n_uncorrected", C.c_uint64),
                 ("n_kept", C.c_uint64), ("n_cells_out", C.c_uint64), ("n_cells_empty", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqAtacCollateOpts(C.Structure):
+    """afq_atac_collate_opts of include/afquant_host.h (afq_atac_collate, afq_atac_collate_sz)."""
+    _fields_ = AfqCollateMultiOpts._fields_[:-1] + [("stats_out", C.POINTER(AfqAtacCollateStats))]
 
 
 class AfqConvertStats(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_dropped_by_flag", C.c_uint64), ("n_runs", C.c_uint64), ("n_runs_dropped_n", C.c_uint64),
                 ("n_runs_written", C.c_uint64), ("n_alignments_in", C.c_uint64), ("n_alignments_written", C.c_uint64), ("n_long_runs", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class AfqSnappyStats(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_blocks_stored", C.c_uint64),
+                ("n_literal_bytes", C.c_uint64), ("n_copies", C.c_uint64)]
 
 
 class AfqConvertOpts(C.Structure):

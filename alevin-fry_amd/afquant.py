@@ -344,6 +344,13 @@ def load_library(path: str = LIB_PATH):
     lib.afq_collate_multi_limits.restype = None
     lib.afq_collate_multi.argtypes = [p(_abi.AfqCollateMultiOpts)]
     lib.afq_collate_multi.restype = C.c_int
+    # (afq_collate, afq_atac_collate and the three _sz doors: _collate_dirs declares them on function objects of its own)
+    lib.afq_snappy_frame_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, p(p(C.c_uint8)), p(C.c_uint64), p(_abi.AfqSnappyStats)]
+    lib.afq_snappy_frame_encode.restype = C.c_int
+    lib.afq_snappy_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_snappy_limits.restype = None
+    lib.afq_set_collate_compress.argtypes = [C.c_void_p, C.c_int]
+    lib.afq_set_collate_compress.restype = None
     lib.afq_atac_collate_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), p(C.c_uint64),
                                          C.c_uint64, p(C.c_uint64), C.c_uint64, p(p(C.c_uint8)), p(C.c_uint64), p(C.c_uint64), p(p(C.c_uint64)),
                                          p(p(C.c_uint32)), p(p(C.c_uint32)), p(_abi.AfqAtacCollateStats)]
@@ -418,19 +425,47 @@ def collate_multi_limits():
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "radix_block": int(out[3])}
 
 
-def collate_multi(input_dir, rad_dir, device: int = 0, cmdline: str = ""):
-    """afq_collate_multi: multi-barcode `collate` - the output directory of generate_permit_list_multi and the mapper's directory in;
-    map.collated.rad, collation_manifest.bin, collate.json and unmapped_bc_count_collated.bin are written into input_dir.  Returns the
-    device call's stats; raises AfqError."""
+def _collate_dirs(plain, sz, opts_t, stats_t, input_dir, rad_dir, compress, device, cmdline):
     lib = load_library()
-    st = _abi.AfqCollateMultiStats()
-    o = _abi.AfqCollateMultiOpts()
+    st = stats_t()
+    o = opts_t()
     o.input_dir, o.rad_dir, o.device, o.cmdline = os.fsencode(input_dir), os.fsencode(rad_dir), int(device), cmdline.encode()
     o.stats_out = C.pointer(st)
-    rc = lib.afq_collate_multi(C.byref(o))
+    fn = lib[sz if compress else plain]   # (a function object of this call's own: a host may have declared the symbol's prototype over its own struct type)
+    fn.argtypes, fn.restype = [C.POINTER(opts_t)], C.c_int
+    rc = fn(C.byref(o))
     if rc:
         raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
     return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def collate_multi(input_dir, rad_dir, device: int = 0, cmdline: str = "", compress: bool = False):
+    """afq_collate_multi: multi-barcode `collate` - the output directory of generate_permit_list_multi and the mapper's directory in;
+    map.collated.rad, collation_manifest.bin, collate.json and unmapped_bc_count_collated.bin are written into input_dir.  compress:
+    afq_collate_multi_sz - map.collated.rad.sz (snappy frame streams, compressed on the device) in place of map.collated.rad, and
+    collate.json says so.  Returns the device call's stats; raises AfqError."""
+    return _collate_dirs("afq_collate_multi", "afq_collate_multi_sz", _abi.AfqCollateMultiOpts, _abi.AfqCollateMultiStats, input_dir, rad_dir, compress, device, cmdline)
+
+
+def collate(input_dir, rad_dir, compress: bool = False, device: int = 0, cmdline: str = ""):
+    """afq_collate: `collate` - the output directory of generate-permit-list and the mapper's directory in; map.collated.rad,
+    collate.json and unmapped_bc_count_collated.bin are written into input_dir.  compress: afq_collate_sz - map.collated.rad.sz
+    (snappy frame streams, compressed on the device) in place of map.collated.rad, and collate.json says so.  Returns the device
+    call's stats; raises AfqError."""
+    return _collate_dirs("afq_collate", "afq_collate_sz", _abi.AfqCollateOpts, _abi.AfqCollateStats, input_dir, rad_dir, compress, device, cmdline)
+
+
+def atac_collate(input_dir, rad_dir, compress: bool = False, device: int = 0, cmdline: str = ""):
+    """afq_atac_collate: `atac collate`, as collate() for a scATAC RAD (compress: afq_atac_collate_sz)."""
+    return _collate_dirs("afq_atac_collate", "afq_atac_collate_sz", _abi.AfqAtacCollateOpts, _abi.AfqAtacCollateStats, input_dir, rad_dir, compress, device, cmdline)
+
+
+def snappy_limits():
+    """afq_snappy_limits: {"block", "hash_slots", "max_copy", "blocks_per_workgroup"} of the device snappy frame encoder - bytes of
+    input per frame chunk, slots of a chunk's last-position table, the longest single copy element, chunks a workgroup takes."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_snappy_limits(out)
+    return {"block": int(out[0]), "hash_slots": int(out[1]), "max_copy": int(out[2]), "blocks_per_workgroup": int(out[3])}
 
 
 def convert_limits():
@@ -593,6 +628,26 @@ class Quantifier:
     def set_aln_extra_bytes(self, e: int):
         """Width of the position behind every alignment word of the records submitted from now on (0: none)."""
         self._check(self.lib.afq_set_aln_extra_bytes(self._h, int(e)))
+
+    def set_collate_compress(self, on: bool):
+        """afq_set_collate_compress: collate_rad, collate_multi_rad and atac_collate_rad hand "bytes" out as the snappy frame stream of the
+        chunk bytes, compressed on the device; offsets, counts and stats stay in uncompressed coordinates."""
+        self.lib.afq_set_collate_compress(self._h, int(bool(on)))
+
+    def snappy_frame_encode(self, data, d_ptr: int = 0, n_bytes: int = 0):
+        """afq_snappy_frame_encode: the snappy frame stream of `data` (host bytes, or d_ptr/n_bytes for bytes already on the device),
+        compressed on the device.  Returns (bytes, stats)."""
+        if d_ptr:
+            ptr, nb, on_dev = C.c_void_p(d_ptr), int(n_bytes), 1
+        else:
+            b = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+            ptr, nb, on_dev = b.ctypes.data_as(C.c_void_p), b.nbytes, 0
+        o_b, o_n, st = C.POINTER(C.c_uint8)(), C.c_uint64(), _abi.AfqSnappyStats()
+        self._check(self.lib.afq_snappy_frame_encode(self._h, ptr, nb, on_dev, C.byref(o_b), C.byref(o_n), C.byref(st)))
+        try:
+            return C.string_at(o_b, int(o_n.value)), {k: int(getattr(st, k)) for k, _ in st._fields_}
+        finally:
+            self.lib.afq_free(o_b)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -62,7 +62,7 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_CONVERT_WALK, K_CONVERT_RUNS, K_CONVERT_PLACE, K_CONVERT_WRITE, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_CONVERT_WALK, K_CONVERT_RUNS, K_CONVERT_PLACE, K_CONVERT_WRITE, K_SNAPPY_BLOCKS, K_SNAPPY_PACK, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                            "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                            "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
@@ -73,7 +73,8 @@ const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "
                                            "k_atac_gpl_parse", "k_atac_gpl_bins",
                                            "k_gpl_multi_table", "k_gpl_multi_parse",
                                            "k_collate_multi_table", "k_collate_multi_measure", "k_collate_multi_sort", "k_collate_multi_scan", "k_collate_multi_write",
-                                           "k_convert_walk", "k_convert_runs", "k_convert_place", "k_convert_write"};
+                                           "k_convert_walk", "k_convert_runs", "k_convert_place", "k_convert_write",
+                                           "k_snappy_blocks", "k_snappy_pack"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -233,6 +234,12 @@ struct AtacCollateBufs {
     std::vector<DevBuf*> all() { return {&chunks, &obs, &val, &tkey, &tval, &cells, &cellof, &ka, &kb, &hist, &first, &rank, &cstat, &status, &out, &off, &nrec, &ocell}; }
 };
 
+// the snappy frame encoder's (afq_snappy_frame_encode, and the collates' copy down under afq_set_collate_compress)
+struct SnappyBufs {
+    DevBuf in, slots, meta, off, stream;
+    std::vector<DevBuf*> all() { return {&in, &slots, &meta, &off, &stream}; }
+};
+
 // afq_convert_bam_rad's
 struct ConvertBufs {
     DevBuf spans, scnt, sbase, ssum, roff, ridx, word, head, score, has, rfirst, rbc, rumi, rflag, rna, rmax, stat, key, rec, bsum, ex, dest, out, off, nrec, err, status;
@@ -263,6 +270,7 @@ struct afq_ctx {
     CollateBufs collate;
     AtacCollateBufs acollate;
     ConvertBufs convert;
+    SnappyBufs snappy;
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
@@ -292,6 +300,8 @@ struct afq_ctx {
     // afq_set_aln_extra_bytes: every alignment word of a record is followed by a position of this many bytes (0: none).  Such a
     // batch always takes the copy: k_strip_aln writes it without the positions (and with the widened fields)
     uint32_t aln_extra = 0;
+    // afq_set_collate_compress: the three collates hand their chunk bytes out as a snappy frame stream, encoded on the device
+    bool collate_compress = false;
     std::vector<uint64_t> w_off;
     std::vector<uint32_t> w_nbytes;
     uint64_t wide_bytes = 0;
@@ -1783,6 +1793,7 @@ void afq_destroy(afq_ctx* c) {
     for (DevBuf* b : c->collate.all()) b->release();
     for (DevBuf* b : c->acollate.all()) b->release();
     for (DevBuf* b : c->convert.all()) b->release();
+    for (DevBuf* b : c->snappy.all()) b->release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);
@@ -3345,6 +3356,111 @@ static int collate_cell_index(afq_ctx* c, const uint64_t* observed, const uint64
     return 0;
 }
 
+// The snappy frame encoder (afq_snappy.hip).  Device bytes it takes beside n bytes of input that are on the device already: a
+// slot a chunk, 16 bytes of meta and 8 of offset a chunk, and the stream at its bound.
+static uint64_t snappy_device_need(uint64_t n) {
+    const uint64_t nb = snappy_blocks(n);
+    return nb * kSnappySlot + nb * sizeof(SnappyMeta) + (nb + 1) * 8 + snappy_stream_bound(n);
+}
+
+// d_in: n bytes on the device (whatever c->stream holds in front of them is waited for) -> their frame stream as one malloc'd
+// block.  The caller has checked that snappy_device_need(n) fits.
+static int snappy_encode_device(afq_ctx* c, const char* who, const uint8_t* d_in, uint64_t n, uint8_t** out, uint64_t* out_n, afq_snappy_stats* stats) {
+    static const uint8_t kId[10] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};
+    afq_snappy_stats S{};
+    S.n_in = n;
+    const uint64_t nb = snappy_blocks(n);
+    if (nb >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, std::string(who) + ": 2^31 or more snappy frame chunks (" + std::to_string(n) + " bytes)");
+    if (!nb) {
+        uint8_t* ob = (uint8_t*)std::malloc(10);
+        if (!ob) return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (10 bytes of snappy stream)");
+        std::memcpy(ob, kId, 10);
+        S.n_out = 10;
+        if (stats) *stats = S;
+        *out = ob; *out_n = 10;
+        return 0;
+    }
+    auto& Z = c->snappy;
+    hipStream_t s = c->stream;
+    HipLatch T;
+    HostClock hc;
+    const std::string detail = " (snappy encoder, " + std::to_string(n) + " bytes in " + std::to_string(nb) + " frame chunks)";
+    T(Z.slots.ensure(nb * kSnappySlot)); T(Z.meta.ensure(nb * sizeof(SnappyMeta))); T(Z.off.ensure((nb + 1) * 8)); T(Z.stream.ensure(snappy_stream_bound(n)));
+    if (!T.ok()) return T.fail(c, who, detail);
+    hc.lap("snappy: buffers");
+    {
+        ScopedTimer t(c, K_SNAPPY_BLOCKS, s);
+        launch_snappy_blocks(s, d_in, n, nb, Z.slots.as<uint8_t>(), Z.meta.as<SnappyMeta>());
+    }
+    {
+        ScopedTimer t(c, K_SNAPPY_PACK, s);
+        launch_snappy_layout(s, Z.meta.as<SnappyMeta>(), nb, Z.off.as<uint64_t>());
+        launch_snappy_pack(s, d_in, nb, Z.slots.as<uint8_t>(), Z.meta.as<SnappyMeta>(), Z.off.as<uint64_t>(), Z.stream.as<uint8_t>());
+    }
+    T(hipGetLastError());
+    std::vector<SnappyMeta> meta(nb);
+    uint64_t total = 0;
+    T(hipMemcpyAsync(&total, Z.off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s));
+    T(hipMemcpyAsync(meta.data(), Z.meta.p, nb * sizeof(SnappyMeta), hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    hc.lap("snappy: kernels + lengths");
+    if (!T.ok()) { harvest_timers(c); return T.fail(c, who, detail); }
+    if (total < 10 + 8 * nb || total > snappy_stream_bound(n)) {
+        harvest_timers(c);
+        return fail(c, AFQ_ERR_HIP, std::string(who) + ": a snappy stream of " + std::to_string(total) + " bytes from " + std::to_string(n) + " of input");
+    }
+    uint8_t* ob = (uint8_t*)std::malloc(total);
+    if (!ob) { harvest_timers(c); return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(total) + " bytes of snappy stream)"); }
+    hc.lap("snappy: host block");
+    T(hipMemcpyAsync(ob, Z.stream.p, total, hipMemcpyDeviceToHost, s));
+    T(hipStreamSynchronize(s));
+    hc.lap("snappy: stream D2H");
+    harvest_timers(c);
+    if (!T.ok()) { std::free(ob); return T.fail(c, who, detail); }
+    S.n_out = total; S.n_blocks = nb;
+    for (const SnappyMeta& m : meta) {
+        if (m.body & kSnappyStored) ++S.n_blocks_stored;
+        S.n_literal_bytes += m.lit; S.n_copies += m.copies;
+    }
+    if (stats) *stats = S;
+    *out = ob; *out_n = total;
+    return 0;
+}
+
+void afq_snappy_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSnappyBlock; out[1] = kSnappyHashSlots; out[2] = kSnappyMaxCopy; out[3] = kSnappyBlocksPerWg;
+}
+
+int afq_snappy_frame_encode(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, int bytes_on_device, uint8_t** out_bytes, uint64_t* out_n_bytes, afq_snappy_stats* stats) {
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!bytes && n_bytes) || !out_bytes || !out_n_bytes) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes, need = snappy_device_need(n_bytes);
+    {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        if (need_in + need > tot)
+            return fail(c, AFQ_ERR_OOM, "afq_snappy_frame_encode: the input does not fit the device: " + std::to_string(need_in) + " bytes of input + " + std::to_string(need) +
+                        " of slots, stream and tables > " + std::to_string(tot) + " bytes of device memory");
+    }
+    const uint8_t* d_in = bytes;
+    if (!bytes_on_device && n_bytes) {
+        HipLatch T;
+        T(c->snappy.in.ensure(n_bytes));
+        if (T.ok()) T(hipMemcpyAsync(c->snappy.in.p, bytes, n_bytes, hipMemcpyHostToDevice, c->stream));
+        if (!T.ok()) return T.fail(c, "afq_snappy_frame_encode", " (" + std::to_string(n_bytes) + " bytes of input)");
+        d_in = c->snappy.in.as<uint8_t>();
+    }
+    reset_kernel_times(c);
+    return snappy_encode_device(c, "afq_snappy_frame_encode", d_in, n_bytes, out_bytes, out_n_bytes, stats);
+}
+
+void afq_set_collate_compress(afq_ctx* c, int on) {
+    if (c) c->collate_compress = on != 0;
+}
+
 // Both collates' placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies.
 // The sorted words end in `src`; `dst` is the buffer the last pass read, free again.
 static void collate_radix_place(hipStream_t s, uint64_t*& src, uint64_t*& dst, uint32_t n, uint32_t n_cells, uint32_t* hist) {
@@ -3394,10 +3510,12 @@ static int collate_plan(afq_ctx* c, CollateRun& R, const uint8_t* bytes, size_t 
     {
         size_t fr = 0, tot = 0;
         HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + R.need_out + need_rec + need_tab + need_misc > tot)
+        const uint64_t need_sz = c->collate_compress ? snappy_device_need(R.need_out) : 0;   // (the encoder's slots, tables and stream beside the output)
+        if (need_in + R.need_out + need_rec + need_tab + need_misc + need_sz > tot)
             return fail(c, AFQ_ERR_OOM, who + ": the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
                         std::to_string(R.need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(R.n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
+                        std::to_string(need_tab + need_misc) + " of tables" + (need_sz ? " + " + std::to_string(need_sz) + " for the snappy encoder" : std::string()) + " > " +
+                        std::to_string(tot) + " bytes of device memory");
     }
     auto& B = c->collate;
     HipLatch& T = R.T;
@@ -3457,12 +3575,13 @@ static int collate_finish(afq_ctx* c, CollateRun& R, HostClock& hc, std::vector<
     }
     T(hipGetLastError());
     HostOuts H;
-    uint8_t* ob = (uint8_t*)H.mallocd(o1);
+    const bool sz = c->collate_compress;   // the chunk bytes go down as a snappy frame stream, encoded behind the checks below
+    uint8_t* ob = sz ? nullptr : (uint8_t*)H.mallocd(o1);
     uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
     uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
-    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, who + ": host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
+    if ((!sz && !ob) || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, who + ": host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
     T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
+    if (out_total && !sz) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
     T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
     if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
     T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
@@ -3473,8 +3592,13 @@ static int collate_finish(afq_ctx* c, CollateRun& R, HostClock& hc, std::vector<
         return fail(c, AFQ_ERR_UNSUPPORTED, who + ": cell " + std::to_string(st.err_cell) + " (" + cell_text(st.err_cell) + "): an output chunk of 4 GiB or more");
     if (st.err_code) return fail(c, AFQ_ERR_HIP, who + ": device status " + std::to_string(st.err_code) + " in the write");
     if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, who + ": the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
+    uint64_t out_n = out_total;
+    if (sz) {
+        if (int rc = snappy_encode_device(c, R.who, B.out.as<uint8_t>(), out_total, &ob, &out_n, nullptr)) return rc;
+        hc.lap("snappy encode + D2H");
+    }
     H.release();
-    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec;
+    *out_bytes = ob; *out_n_bytes = out_n; *out_chunk_off = ooff; *out_nrec = onrec;
     return 0;
 }
 
@@ -3544,7 +3668,7 @@ int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint
         const uint32_t* q = cstat.data() + 8ull * i;
         S.n_records += q[0]; S.n_compatible += q[1]; S.n_uncorrected += q[2]; S.n_kept += q[3]; S.n_alignments_in += q[4]; S.n_alignments_kept += q[5]; S.n_long_records += q[6];
     }
-    S.out_bytes = *out_n_bytes;
+    S.out_bytes = (*out_chunk_off)[n_cells];   // (uncompressed, also under afq_set_collate_compress)
     if (stats) *stats = S;
     return 0;
 }
@@ -3626,7 +3750,7 @@ int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, cons
         S.n_records += q[0]; S.n_compatible += q[1]; S.n_unrouted += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4]; S.n_alignments_in += q[5]; S.n_alignments_kept += q[6];
         S.n_long_records += q[7];
     }
-    S.out_bytes = *out_n_bytes;
+    S.out_bytes = (*out_chunk_off)[n_cells];   // (uncompressed, also under afq_set_collate_compress)
     if (stats) *stats = S;
     return 0;
 }
@@ -3677,10 +3801,12 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     {
         size_t fr = 0, tot = 0;
         HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_out + need_rec + need_tab + need_misc > tot)
+        const uint64_t need_sz = c->collate_compress ? snappy_device_need(need_out) : 0;   // (the encoder's slots, tables and stream beside the output)
+        if (need_in + need_out + need_rec + need_tab + need_misc + need_sz > tot)
             return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
                         std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables > " + std::to_string(tot) + " bytes of device memory");
+                        std::to_string(need_tab + need_misc) + " of tables" + (need_sz ? " + " + std::to_string(need_sz) + " for the snappy encoder" : std::string()) + " > " +
+                        std::to_string(tot) + " bytes of device memory");
     }
     auto& B = c->acollate;
     HipLatch T;
@@ -3760,13 +3886,14 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     }
     T(hipGetLastError());
     HostOuts H;
-    uint8_t* ob = (uint8_t*)H.mallocd(o1);
+    const bool sz = c->collate_compress;   // the chunk bytes go down as a snappy frame stream, encoded behind the checks below
+    uint8_t* ob = sz ? nullptr : (uint8_t*)H.mallocd(o1);
     uint64_t* ooff = (uint64_t*)H.mallocd(8 * nout1);
     uint32_t* onrec = (uint32_t*)H.mallocd(4 * nout1);
     uint32_t* ocell = (uint32_t*)H.mallocd(4 * nout1);
-    if (!ob || !ooff || !onrec || !ocell) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: host allocation failed (" + std::to_string(o1 + 16 * nout1) + " bytes of output)"); }
+    if ((!sz && !ob) || !ooff || !onrec || !ocell) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: host allocation failed (" + std::to_string(o1 + 16 * nout1) + " bytes of output)"); }
     T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
+    if (out_total && !sz) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
     T(hipMemcpyAsync(ooff, B.off.p, 8 * nout1, hipMemcpyDeviceToHost, s));
     if (n_out) { T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(ocell, B.ocell.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); }
     T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
@@ -3778,9 +3905,14 @@ int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const
     if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: device status " + std::to_string(st.err_code) + " in the write");
     if (ooff[n_out] != out_total) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: the chunks end at " + std::to_string(ooff[n_out]) + " of " + std::to_string(out_total) + " output bytes");
     S.n_cells_out = n_out; S.n_cells_empty = (uint64_t)n_cells - n_out; S.out_bytes = out_total;
+    uint64_t out_n = out_total;
+    if (sz) {
+        if (int rc = snappy_encode_device(c, "afq_atac_collate_rad", B.out.as<uint8_t>(), out_total, &ob, &out_n, nullptr)) return rc;
+        hc.lap("snappy encode + D2H");
+    }
     if (stats) *stats = S;
     H.release();
-    *out_bytes = ob; *out_n_bytes = out_total; *out_n_chunks = n_out; *out_chunk_off = ooff; *out_nrec = onrec; *out_cell = ocell;
+    *out_bytes = ob; *out_n_bytes = out_n; *out_n_chunks = n_out; *out_chunk_off = ooff; *out_nrec = onrec; *out_cell = ocell;
     return 0;
 }
 

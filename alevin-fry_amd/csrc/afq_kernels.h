@@ -433,6 +433,19 @@ void launch_convert_aux(hipStream_t s, const ConvertArgs& a);     // behind the 
 void launch_convert_runs(hipStream_t s, const ConvertArgs& a);    // run_na, run_max, run_flag := written, stat
 void launch_convert_place(hipStream_t s, const ConvertArgs& a);   // behind the scan of run_flag[]: key, rec
 void launch_convert_write(hipStream_t s, const ConvertArgs& a);
+// the snappy frame encoder (afq_snappy.hip): bytes on the device -> stream identifier + one data chunk per kSnappyBlock bytes
+constexpr uint32_t kSnappyBlock = 65536;          // bytes of input per frame chunk (the format's limit)
+constexpr uint32_t kSnappyHashBits = 11, kSnappyHashSlots = 1u << kSnappyHashBits;   // last-position table of a chunk, in LDS
+constexpr uint32_t kSnappyMaxCopy = 64;           // longest single copy element
+constexpr uint32_t kSnappyBlocksPerWg = 1;        // a workgroup is one wave and takes one chunk
+constexpr uint32_t kSnappySlot = (32 + kSnappyBlock + kSnappyBlock / 6 + 15) & ~15u;   // where a chunk's raw block is first written: snappy's own worst case
+constexpr uint32_t kSnappyStored = 0x80000000u;
+struct SnappyMeta { uint32_t body, crc, lit, copies; };   // bytes of the chunk's body (| kSnappyStored: the input's own bytes, type 0x01), masked CRC-32C, literal bytes and copy elements of a raw block
+inline uint64_t snappy_blocks(uint64_t n) { return (n + kSnappyBlock - 1) / kSnappyBlock; }
+inline uint64_t snappy_stream_bound(uint64_t n) { return 10 + n + 8 * snappy_blocks(n); }
+void launch_snappy_blocks(hipStream_t s, const uint8_t* in, uint64_t n, uint64_t n_blocks, uint8_t* slots, SnappyMeta* meta);
+void launch_snappy_layout(hipStream_t s, const SnappyMeta* meta, uint64_t n_blocks, uint64_t* off);   // off[i]: where chunk i's header stands, off[n_blocks]: the stream's length
+void launch_snappy_pack(hipStream_t s, const uint8_t* in, uint64_t n_blocks, const uint8_t* slots, const SnappyMeta* meta, const uint64_t* off, uint8_t* out);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

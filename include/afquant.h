@@ -609,6 +609,31 @@ int afq_convert_bam_rad(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, cons
  * than this is taken by the whole wave, out[3] = flags a workgroup of the run-number and rank scans takes (the layout scan's take half as many).  For tests. */
 void afq_convert_limits(uint32_t out[4]);
 
+/* A snappy frame stream from `bytes`, compressed on the device (afq_snappy.hip): the 10-byte stream identifier, then one data
+ * chunk per afq_snappy_limits()[0] bytes of input, in input order: `type, len24, masked CRC-32C of the uncompressed bytes`
+ * and a raw snappy block (type 0x00), or the bytes themselves (type 0x01) wherever the raw block would not be shorter than
+ * they are.  So n_out <= 10 + n_in + 8 n_blocks; empty input gives the identifier alone.  The stream is a function of the
+ * input alone - the same bytes on every run and after any earlier call on the context - but not the bytes another snappy
+ * encoder would write: no compressor promises that.  Chunks decode independently (no copy reaches across a chunk boundary).
+ * bytes_on_device: `bytes` is a device pointer.  Input, slots (a worst-case raw block a chunk), stream and tables that do
+ * not fit the device are refused with AFQ_ERR_OOM and the sizes before any launch.  out_bytes is malloc'd: afq_free. */
+typedef struct afq_snappy_stats {
+    uint64_t n_in, n_out;                          /* bytes in, bytes of the stream                  */
+    uint64_t n_blocks, n_blocks_stored;            /* frame chunks; of those, written as type 0x01   */
+    uint64_t n_literal_bytes, n_copies;            /* over the compressed chunks                     */
+} afq_snappy_stats;
+int afq_snappy_frame_encode(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, int bytes_on_device, uint8_t** out_bytes, uint64_t* out_n_bytes,
+                            afq_snappy_stats* stats);
+/* out[0] = bytes of input per frame chunk (<= 65536), out[1] = slots of a chunk's last-position table, out[2] = longest single
+ * copy element (<= 64), out[3] = chunks a workgroup takes.  For tests. */
+void afq_snappy_limits(uint32_t out[4]);
+/* on != 0: afq_collate_rad, afq_collate_multi_rad and afq_atac_collate_rad run as they do up to and including their write walk
+ * and then hand out_bytes / out_n_bytes out as the snappy frame stream of the chunk bytes (afq_snappy_frame_encode's, encoded
+ * where the bytes lie, in place of the plain copy down).  out_chunk_off, out_nrec, out_cell and every stats field, out_bytes
+ * included, stay in uncompressed coordinates and equal the plain call's; the refusals and their words are the plain call's,
+ * the memory plan counts the encoder's buffers.  0 (the default): nothing changes. */
+void afq_set_collate_compress(afq_ctx* ctx, int on);
+
 /*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the

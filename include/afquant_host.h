@@ -94,7 +94,7 @@ typedef struct afq_collate_opts {
                                         unmapped_bc_count_collated.bin are written here                                    */
     const char* rad_dir;        /* -r : the mapper's directory: map.rad, unmapped_bc_count.bin (optional)                  */
     uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
-    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED): the project has a snappy decoder and no encoder     */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED) by this entry, ignored by the _sz entry below        */
     uint32_t max_records;       /* -m : accepted, without effect (it sizes the reference's host buffers)                   */
     uint32_t device;
     const char* cmdline;        /* optional: goes into collate.json                                                        */
@@ -106,6 +106,15 @@ typedef struct afq_collate_opts {
  * are AFQ_ERR_UNSUPPORTED, named in the message; a kept count other than the sum of permit_freq.bin is the reference's
  * "expected to collate N records but retained M", and no RAD is left behind. */
 int afq_collate(const afq_collate_opts* opts);
+/* `collate -c` (collate.rs:523-554): afq_collate with compressed output, through a door of its own - afq_collate and the command
+ * line's -c keep answering "compressed output is not supported", word for word, because the tests that pin that refusal are
+ * not changed here; a follow-up that may touch them retires it in one line.  opts->compress is ignored.  Writes
+ * map.collated.rad.sz in place of map.collated.rad: the snappy frame stream of the prelude (num_chunks patched), then the frame
+ * stream of the chunks - two streams back to back, each with its identifier, as the reference's own file is and as
+ * afq_quantify / afq_atac_deduplicate read it - both compressed on the device (afq_snappy_frame_encode; the chunks where the
+ * write walk left them, afq_set_collate_compress); collate.json with "compressed_output": true; unmapped_bc_count_collated.bin
+ * as afq_collate.  Everything else, the refusals and the kept-count check that leaves no file behind included, is afq_collate's. */
+int afq_collate_sz(const afq_collate_opts* opts);
 
 /* The options of `alevin-fry atac collate` (src/main.rs:905-922). */
 struct afq_atac_collate_stats;
@@ -114,7 +123,7 @@ typedef struct afq_atac_collate_opts {
                                         unmapped_bc_count_collated.bin are written here                                    */
     const char* rad_dir;        /* -r : the mapper's directory: map.rad, unmapped_bc_count.bin (optional)                  */
     uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
-    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED): the project has a snappy decoder and no encoder     */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED) by this entry, ignored by the _sz entry below        */
     uint32_t max_records;       /* -m : accepted, without effect (it sizes the reference's host buffers)                   */
     uint32_t device;
     const char* cmdline;        /* optional: goes into collate.json                                                        */
@@ -126,6 +135,9 @@ typedef struct afq_atac_collate_opts {
  * chunks written.  An RNA prelude and compressed output are AFQ_ERR_UNSUPPORTED.  A missing unmapped_bc_count.bin is an empty map
  * (the reference panics).  map.collated.rad is written only after the device call succeeded: a failed run leaves none behind. */
 int afq_atac_collate(const afq_atac_collate_opts* opts);
+/* `atac collate -c`: afq_atac_collate writing map.collated.rad.sz, as afq_collate_sz does for afq_collate (opts->compress is
+ * ignored; afq_atac_collate itself keeps its refusal).  With no record kept the chunk stream is the identifier alone. */
+int afq_atac_collate_sz(const afq_atac_collate_opts* opts);
 
 /* The options of multi-barcode `collate` (src/main.rs:271-292; do_collate_multi_bc_fast, src/collate.rs:1415-1920): afq_collate_opts'
  * fields, over the output directory of afq_generate_permit_list_multi. */
@@ -136,7 +148,7 @@ typedef struct afq_collate_multi_opts {
                                         collation_manifest.bin, collate.json and unmapped_bc_count_collated.bin are written here  */
     const char* rad_dir;        /* -r : the mapper's directory: map.rad                                                     */
     uint32_t num_threads;       /* -t : accepted; the device routes the records                                           */
-    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED)                                                     */
+    uint32_t compress;          /* -c : refused (AFQ_ERR_UNSUPPORTED) by this entry, ignored by the _sz entry below        */
     uint32_t max_records;       /* -m : accepted, without effect                                                          */
     uint32_t device;
     const char* cmdline;        /* optional: goes into collate.json                                                        */
@@ -154,6 +166,10 @@ typedef struct afq_collate_multi_opts {
  * sample the records kept must number the sum of its permit_freq.bin counts ("expected to collate N records but retained M");
  * the files are written only after that check, so a failed run leaves none behind. */
 int afq_collate_multi(const afq_collate_multi_opts* opts);
+/* multi-barcode `collate -c`: afq_collate_multi writing map.collated.rad.sz, as afq_collate_sz does for afq_collate
+ * (opts->compress is ignored; afq_collate_multi itself keeps its refusal).  collate.json's other keys and
+ * collation_manifest.bin - it counts chunks, not bytes - are unchanged. */
+int afq_collate_multi_sz(const afq_collate_multi_opts* opts);
 /* afq_collate_multi_rad's checks that precede device work (include/afquant.h), without a device. */
 int afq_collate_multi_check_args(uint32_t b0_bytes, uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, const uint64_t* sample_observed,
                                  const uint32_t* sample_index, uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed,
