@@ -1,159 +1,17 @@
-// afq_api.cpp — C ABI of include/afquant.h: host planner + stream orchestration.
-//
+// afq_api.cpp — C ABI of include/afquant.h: the context's lifetime and the quant path, host planner + stream orchestration
+// (the other commands' entry points: afq_api_atac / _gpl / _collate / _convert.cpp, over afq_ctx.h and afq_api_rad.cpp).
 // Replaces (reference paths relative to /root/reference):
 //   worker set-up            src/quant.rs:1678-1765   -> afq_create
 //   per-cell loop body       src/quant.rs:733-1322    -> afq_submit / afq_collect
 // No CPU compute path exists here: every count is produced by the gfx950
 // kernels in afq_kernels.hip; a missing device is an error, never a fallback.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <condition_variable>
-#include <mutex>
-#include <optional>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/afquant.h"
-#include "afq_chunk_table.h"
-#include "afq_common.h"
-#include "afq_gpl_host.h"
-#include "afq_hooks.h"
-#include "afq_kernels.h"
+#include "afq_ctx.h"
 
-using namespace afq;
-
-namespace {
-
-thread_local std::string g_create_err;
-
-// AFQ_HOST_TIMING=1 prints where the host side of a batch spends its time (stderr)
-struct HostClock {
-    bool on = std::getenv("AFQ_HOST_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void lap(const char* what) {
-        if (!on) return;
-        auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[afq host] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = n + n / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { e = hipMalloc(&p, n); want = n; }
-        if (e == hipSuccess) cap = want; else p = nullptr;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_CONVERT_WALK, K_CONVERT_RUNS, K_CONVERT_PLACE, K_CONVERT_WRITE, K_SNAPPY_BLOCKS, K_SNAPPY_PACK, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
-                                           "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
-                                           "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
-                                           "k_sort_table", "k_sort_parse", "k_sort_partition", "k_sort_leaf", "k_sort_emit",
-                                           "k_gpl_parse", "k_gpl_count", "k_gpl_compact", "k_gpl_table", "k_gpl_correct",
-                                           "k_collate_table", "k_collate_measure", "k_collate_sort", "k_collate_scan", "k_collate_write",
-                                           "k_atac_collate_table", "k_atac_collate_measure", "k_atac_collate_place", "k_atac_collate_write",
-                                           "k_atac_gpl_parse", "k_atac_gpl_bins",
-                                           "k_gpl_multi_table", "k_gpl_multi_parse",
-                                           "k_collate_multi_table", "k_collate_multi_measure", "k_collate_multi_sort", "k_collate_multi_scan", "k_collate_multi_write",
-                                           "k_convert_walk", "k_convert_runs", "k_convert_place", "k_convert_write",
-                                           "k_snappy_blocks", "k_snappy_pack"};
-
-struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
-
-// Pinned, grow-only host array (D2H lands here directly; handed to the caller zero-copy).
-template <class T>
-struct PinnedVec {
-    T* p = nullptr;
-    size_t n = 0, cap = 0;
-    hipError_t reserve(size_t want) {
-        if (want <= cap) return hipSuccess;
-        size_t nc = std::max(want + want / 4, (size_t)4096);
-        T* q = nullptr;
-        hipError_t e = hipHostMalloc((void**)&q, nc * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        if (n) std::memcpy(q, p, n * sizeof(T));
-        if (p) (void)hipHostFree(p);
-        p = q; cap = nc;
-        return hipSuccess;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = cap = 0; }
-};
-
-struct ResultPool;
-struct HostResult {
-    std::vector<uint64_t> cell_ptr, bc;
-    std::vector<uint32_t> nrec;
-    PinnedVec<uint32_t> gene;
-    PinnedVec<float> val;
-    std::vector<uint8_t> flags;
-    // -d: gene-level equivalence classes per cell (cfg.dump_eq): CSR cell -> classes -> label words
-    std::vector<uint64_t> eq_cell_ptr, eq_label_ptr;
-    std::vector<uint32_t> eq_labels, eq_count;
-    // -b: bootstrap mean / variance per cell, non-zero entries (cfg.num_bootstraps)
-    std::vector<uint64_t> bm_ptr, bv_ptr;
-    std::vector<uint32_t> bm_col, bv_col;
-    std::vector<float> bm_val, bv_val;
-    ResultPool* pool = nullptr;
-    void clear() {
-        cell_ptr.clear(); bc.clear(); nrec.clear(); flags.clear(); gene.n = 0; val.n = 0;
-        eq_cell_ptr.clear(); eq_label_ptr.clear(); eq_labels.clear(); eq_count.clear();
-        bm_ptr.clear(); bv_ptr.clear(); bm_col.clear(); bv_col.clear(); bm_val.clear(); bv_val.clear();
-    }
-};
-
-// Results outlive a collect call (library-owned until afq_result_release), and pinning
-// host memory is slow, so result storage is recycled through a small per-context pool.
-struct ResultPool {
-    std::mutex mu;
-    std::vector<HostResult*> free_list;
-    bool ctx_alive = true;
-    int outstanding = 0;
-};
-
-HostResult* pool_get(ResultPool* P) {
-    std::lock_guard<std::mutex> g(P->mu);
-    HostResult* r;
-    if (!P->free_list.empty()) { r = P->free_list.back(); P->free_list.pop_back(); }
-    else { r = new HostResult(); r->pool = P; }
-    r->clear();
-    ++P->outstanding;
-    return r;
-}
-
-void pool_put(HostResult* r) {
-    ResultPool* P = r->pool;
-    bool destroy_pool = false;
-    {
-        std::lock_guard<std::mutex> g(P->mu);
-        --P->outstanding;
-        if (P->ctx_alive && P->free_list.size() < 2) { P->free_list.push_back(r); r = nullptr; }
-        else destroy_pool = !P->ctx_alive && P->outstanding == 0;
-    }
-    if (r) { r->gene.release(); r->val.release(); delete r; }
-    if (destroy_pool) delete P;
-}
-
-struct Range { uint32_t c0, c1; };
-
-struct RangeState {
+#pragma GCC visibility push(hidden)
+struct RangeState {   // (afq_ctx.h names it: afq_ctx points at its two)
     hipStream_t stream = nullptr;
     DevBuf d_meta, d_keys0, d_keys1, d_cell_nkeys, d_bucket_cnt, d_bucket_cell, d_multi_cells, d_tile_desc, d_src_off, d_slab_ovf, d_ncols,
         d_nnz, d_ovf, d_status, d_bc, d_cell_ptr, d_gene, d_val, d_chk, d_slab_prefix, d_slab_cell, d_cell_bc, d_div, d_lab,
@@ -189,194 +47,39 @@ struct RangeState {
                 &d_bt_mean, &d_bt_var, &d_bt_sptr, &d_bt_ccol, &d_bt_cmean, &d_bt_cvar, &d_em2_off, &d_em2_scratch, &d_em2_tiers, &d_arena, &d_dtile, &d_spill};
     }
 };
-
-// afq_atac_dedup[_rad]'s device buffers, kept between calls (hipMalloc / hipFree of gigabytes is not free)
-struct AtacBufs {
-    DevBuf ref, start, flen, ptr, scr, oref, ostart, oflen, ocnt, on, optr, cref, cstart, cflen, ccnt, flag, cells, bm, cnt, bc, stat, walk, nwalk, status, tally, rstat, runctr;
-    std::vector<DevBuf*> all() {
-        return {&ref, &start, &flen, &ptr, &scr, &oref, &ostart, &oflen, &ocnt, &on, &optr, &cref, &cstart, &cflen, &ccnt, &flag, &cells, &bm, &cnt,
-                &bc, &stat, &walk, &nwalk, &status, &tally, &rstat, &runctr};
-    }
-};
-
-// afq_atac_sort_rad's
-struct AtacSortBufs {
-    DevBuf chunks, obs, rank, tkey, tval, rinfo, bbase, rbc, bin, key0, cstat, status, hist, cur, segs, ka, kb, andor, leaves, ids, on, lout, out, tally;
-    std::vector<DevBuf*> all() {
-        return {&chunks, &obs, &rank, &tkey, &tval, &rinfo, &bbase, &rbc, &bin, &key0, &cstat, &status, &hist, &cur, &segs, &ka, &kb, &andor,
-                &leaves, &ids, &on, &lout, &out, &tally};
-    }
-};
-
-// afq_gpl_hist_rad's and afq_gpl_correct's (afq_gpl_multi_hist_rad keeps its entry list and entry table in the correction's obs, idx, rkey, rval, cstatus)
-struct GplBufs {
-    DevBuf chunks, bc, cstat, status, tkey, tcnt, ones, okey, ocnt, nout;            // histogram
-    DevBuf bbase, bins, bins64, bmax;                                                // afq_atac_gpl_hist_rad's position bins
-    DevBuf obs, obscnt, ret, retcnt, idx, rkey, rval, dec, tgt, stats, tcount, cstatus;   // correction
-    std::vector<DevBuf*> all() {
-        return {&chunks, &bc, &cstat, &status, &tkey, &tcnt, &ones, &okey, &ocnt, &nout, &obs, &obscnt, &ret, &retcnt, &idx, &rkey, &rval, &dec, &tgt,
-                &stats, &tcount, &cstatus, &bbase, &bins, &bins64, &bmax};
-    }
-};
-
-// afq_collate_rad's, and afq_collate_multi_rad's (its sample entries and their table in sobs, sidx, skey, sval)
-struct CollateBufs {
-    DevBuf chunks, obs, val, tkey, tval, cells, rec, ka, kb, hist, bsum, ex, cstat, status, out, off, nrec;
-    DevBuf sobs, sidx, skey, sval;
-    std::vector<DevBuf*> all() {
-        return {&chunks, &obs, &val, &tkey, &tval, &cells, &rec, &ka, &kb, &hist, &bsum, &ex, &cstat, &status, &out, &off, &nrec, &sobs, &sidx, &skey, &sval};
-    }
-};
-
-// afq_atac_collate_rad's
-struct AtacCollateBufs {
-    DevBuf chunks, obs, val, tkey, tval, cells, cellof, ka, kb, hist, first, rank, cstat, status, out, off, nrec, ocell;
-    std::vector<DevBuf*> all() { return {&chunks, &obs, &val, &tkey, &tval, &cells, &cellof, &ka, &kb, &hist, &first, &rank, &cstat, &status, &out, &off, &nrec, &ocell}; }
-};
-
-// the snappy frame encoder's (afq_snappy_frame_encode, and the collates' copy down under afq_set_collate_compress)
-struct SnappyBufs {
-    DevBuf in, slots, meta, off, stream;
-    std::vector<DevBuf*> all() { return {&in, &slots, &meta, &off, &stream}; }
-};
-
-// afq_convert_bam_rad's
-struct ConvertBufs {
-    DevBuf spans, scnt, sbase, ssum, roff, ridx, word, head, score, has, rfirst, rbc, rumi, rflag, rna, rmax, stat, key, rec, bsum, ex, dest, out, off, nrec, err, status;
-    std::vector<DevBuf*> all() {
-        return {&spans, &scnt, &sbase, &ssum, &roff, &ridx, &word, &head, &score, &has, &rfirst, &rbc, &rumi, &rflag, &rna, &rmax, &stat, &key, &rec, &bsum, &ex, &dest,
-                &out, &off, &nrec, &err, &status};
-    }
-};
-
-}  // namespace
-
-struct afq_ctx {
-    afq_config cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint32_t ref_count = 0;
-    std::string err;
-    std::mutex err_mu;   // (the upload thread of afq_submit reports through fail() too)
-    DevBuf d_t2g;
-    // input
-    DevBuf d_bytes_own;
-    const uint8_t* d_bytes = nullptr;
-    size_t n_bytes = 0;
-    DevBuf d_chunk_off, d_hdr;
-    AtacBufs atac;
-    AtacSortBufs asort;
-    GplBufs gpl;
-    CollateBufs collate;
-    AtacCollateBufs acollate;
-    ConvertBufs convert;
-    SnappyBufs snappy;
-    void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
-    hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
-    // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)
-    std::vector<hipEvent_t> h2d_ev;
-    bool h2d_piped = false;
-    std::mutex up_mu;
-    std::condition_variable up_cv;
-    size_t up_enqueued = 0;
-    int up_rc = 0;
-    std::string up_err;
-    // Two sets of per-range device state: while the rows of range i cross PCIe, the kernels of range i+1 run.
-    RangeState rs[2];
-    // The rows cross on a stream of their own, range behind range, and the host does not wait for them until afq_collect
-    // (finish_range; DESIGN.md 3.1 "Round 11").  It never holds a kernel.
-    hipStream_t copy_stream = nullptr;
-    DevBuf d_kick;                   // a few bytes that go up in front of every range's rows (finish_range says why)
-    void* h_kick = nullptr;          // ... out of pinned memory that never changes
-    bool copies_in_flight = false;   // row copies enqueued since the copy stream was last drained
-    bool in_retry = false;           // finish_range is running a range again: the nested ranges take the waiting path
-    uint64_t n_pipe[4] = {0};        // afq_range_pipeline_counts
-    uint64_t last_total = 0;         // rows of the batch collected last: begin_batch sizes the result arrays from it
-    bool all_aligned = true;  // every chunk offset is a multiple of 4
-    // 1/2-byte barcode or UMI fields: the batch is rewritten on the device with 4-byte fields (k_widen) and everything
-    // downstream works on that copy - w_off / w_nbytes are the chunks of the copy, chunk_off / hdr stay the caller's
-    bool widen = false;
-    uint32_t eff_bc = 0, eff_umi = 0;
-    // afq_set_aln_extra_bytes: every alignment word of a record is followed by a position of this many bytes (0: none).  Such a
-    // batch always takes the copy: k_strip_aln writes it without the positions (and with the widened fields)
-    uint32_t aln_extra = 0;
-    // afq_set_collate_compress: the three collates hand their chunk bytes out as a snappy frame stream, encoded on the device
-    bool collate_compress = false;
-    std::vector<uint64_t> w_off;
-    std::vector<uint32_t> w_nbytes;
-    uint64_t wide_bytes = 0;
-    DevBuf d_wide;
-    ResultPool* pool = nullptr;
-    // host planning state
-    std::vector<uint64_t> chunk_off;
-    std::vector<uint32_t> hdr;  // nbytes, nrec per cell
-    std::vector<Range> ranges;
-    size_t next_range = 0;
-    uint64_t first_cell_index = 0;
-    uint32_t n_cells = 0;
-    bool pending = false;
-    HostResult* res = nullptr;
-    // stats / timers
-    afq_batch_stats stats{};
-    uint64_t n_label_rehash = 0;   // ranges decoded again under another label-hash salt (life of the context)
-    uint64_t n_pool_regrow = 0;    // ranges run again with a larger parsimony pool
-    uint64_t n_mono_cells = 0;     // parsimony cells resolved by the one-workgroup kernel (sent there directly, or handed back by the phase kernels)
-    uint64_t n_divert = 0;         // buckets the hash resolve of the last batch handed to the sort path
-    uint64_t n_em_resized = 0;     // ranges whose EM scratch was sized on the host after the device-side plan did not fit
-    uint64_t n_em_inst[6] = {0};   // cells of the last batch per rounds instance of the order-free EM (tiers 0-4), then tier 4 cells with 32-bit ids
-    bool handback_seen = false;    // the phase kernels have handed a cell back to the one-workgroup kernel in some range of this context
-    uint32_t retry_cuts = 0;       // how many times the range being finished has been cut around a failing cell (finish_range)
-    uint32_t retry_halvings = 0, retry_halving_cap = 0;   // ... halved after a range-wide failure, and how often it may be (finish_range)
-    std::vector<TimedLaunch> launches;
-    std::vector<hipEvent_t> event_pool;
-    double k_ms[K_COUNT] = {0};
-    uint32_t k_launches[K_COUNT] = {0};
-};
+#pragma GCC visibility pop
 
 namespace {
 
-int fail(afq_ctx* c, int code, const std::string& msg) {
-    if (c) { std::lock_guard<std::mutex> g(c->err_mu); c->err = msg; } else g_create_err = msg;
-    return code;
-}
-#define HIP_TRY(c, expr)                                                                          \
-    do {                                                                                          \
-        hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess)                                                                    \
-            return fail((c), e__ == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP,              \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                      \
-    } while (0)
-
-// The first error of a run of HIP calls; the calls behind it are skipped (`if (T.ok())`) or made and ignored.
-struct HipLatch {
-    hipError_t e = hipSuccess;
-    void operator()(hipError_t x) { if (e == hipSuccess) e = x; }
-    bool ok() const { return e == hipSuccess; }
-    int fail(afq_ctx* c, const char* who, const std::string& detail = "") const {
-        (void)hipGetLastError();   // (the runtime keeps the error until it is read)
-        return ::fail(c, e == hipErrorOutOfMemory ? AFQ_ERR_OOM : AFQ_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e) + detail);
-    }
-};
-
-void reset_kernel_times(afq_ctx* c) { for (int i = 0; i < K_COUNT; ++i) { c->k_ms[i] = 0; c->k_launches[i] = 0; } }
-
-hipEvent_t get_event(afq_ctx* c) {
-    if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
+HostResult* pool_get(ResultPool* P) {
+    std::lock_guard<std::mutex> g(P->mu);
+    HostResult* r;
+    if (!P->free_list.empty()) { r = P->free_list.back(); P->free_list.pop_back(); }
+    else { r = new HostResult(); r->pool = P; }
+    r->clear();
+    ++P->outstanding;
+    return r;
 }
 
-struct ScopedTimer {
-    afq_ctx* c; int id; hipStream_t s; std::vector<TimedLaunch>* sink; hipEvent_t a = nullptr, b = nullptr;
-    ScopedTimer(afq_ctx* c_, int id_, hipStream_t s_ = nullptr, std::vector<TimedLaunch>* sink_ = nullptr)
-        : c(c_), id(id_), s(s_ ? s_ : c_->stream), sink(sink_ ? sink_ : &c_->launches) {
-        if (c->cfg.profile) { a = get_event(c); b = get_event(c); (void)hipEventRecord(a, s); }
+void pool_put(HostResult* r) {
+    ResultPool* P = r->pool;
+    bool destroy_pool = false;
+    {
+        std::lock_guard<std::mutex> g(P->mu);
+        --P->outstanding;
+        if (P->ctx_alive && P->free_list.size() < 2) { P->free_list.push_back(r); r = nullptr; }
+        else destroy_pool = !P->ctx_alive && P->outstanding == 0;
     }
-    ~ScopedTimer() {
-        if (c->cfg.profile) { (void)hipEventRecord(b, s); sink->push_back({id, a, b}); }
-    }
+    if (r) { r->gene.release(); r->val.release(); delete r; }
+    if (destroy_pool) delete P;
+}
+
+struct RangeSlots {   // `for (auto& rs : range_slots(c))`
+    RangeState* p;
+    RangeState* begin() const { return p; }
+    RangeState* end() const { return p + 2; }
 };
+RangeSlots range_slots(afq_ctx* c) { return {c->rs}; }
 
 // The brackets of a range's kernels.  An event between two kernels of a stream is not free: the timeline of a configs[1] step
 // (profiles/r04_timeline_configs1.txt) shows 10-14 us between two kernels wherever one bracket ended and the next began - two
@@ -409,20 +112,6 @@ struct TimerChain {
     }
     void end() { seg(-1); }
 };
-void recycle_events(afq_ctx* c, const TimedLaunch& t) {
-    if (t.own_a) c->event_pool.push_back(t.a);
-    c->event_pool.push_back(t.b);
-}
-
-void harvest_timers(afq_ctx* c, std::vector<TimedLaunch>* list = nullptr) {
-    if (list) { c->launches.insert(c->launches.end(), list->begin(), list->end()); list->clear(); }
-    for (auto& t : c->launches) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) { c->k_ms[t.id] += ms; c->k_launches[t.id] += 1; }
-        recycle_events(c, t);
-    }
-    c->launches.clear();
-}
 
 uint32_t hdr_bytes(const afq_config& cfg) { return 4 + cfg.bc_bytes + cfg.umi_bytes; }
 
@@ -434,8 +123,6 @@ constexpr uint32_t kSlabCap = 384;
 uint32_t slab_capacity() { const long v = test_hook_long("SLAB_CAP", 0); return v > 0 ? (uint32_t)v : kSlabCap; }
 
 uint32_t bucket_target() { return kBucketTarget; }   // planned mean keys per bucket
-
-bool valid_width(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8; }
 
 // What the device path implements today.  Anything else is refused loudly.
 int check_supported(afq_ctx* c) {
@@ -488,7 +175,7 @@ int plan_ranges(afq_ctx* c) {
     HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
     // buffers already held by this context are reusable
     size_t held = 0;
-    for (auto& rs : c->rs) for (DevBuf* b : rs.all()) held += b->cap;
+    for (auto& rs : range_slots(c)) for (DevBuf* b : rs.all()) held += b->cap;
     const double mem_budget = 0.40 * (double)(free_b + held);  // two range buffer sets are alive at a time
     const uint32_t res = c->cfg.resolution;
     const bool em_res = res == AFQ_RES_CR_LIKE_EM || res == AFQ_RES_PARSIMONY_EM || res == AFQ_RES_PARSIMONY_GENE_EM;
@@ -677,7 +364,7 @@ int ensure_copy_stream(afq_ctx* c) {
 int drain_copies(afq_ctx* c) {
     if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     c->copies_in_flight = false;
-    for (auto& rs : c->rs) rs.rows_pending = false;
+    for (auto& rs : range_slots(c)) rs.rows_pending = false;
     return 0;
 }
 
@@ -1517,6 +1204,8 @@ int finish_range(afq_ctx* c, int slot) {
     return 0;
 }
 
+}  // namespace
+
 // Large pageable (or file-mapped) input -> device: the runtime's own pageable path is one staging thread (~8 GB/s,
 // slower still when every page of a mapped file faults on first touch); here several threads fill pinned pieces
 // while the previous piece is on the wire.  Memory the caller has pinned (hipHostMalloc / hipHostRegister) goes
@@ -1531,6 +1220,7 @@ bool host_ptr_is_pinned(const void* p) {
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return at.type == hipMemoryTypeHost;
 }
+hipStream_t second_stream(afq_ctx* c) { return c->rs[0].stream; }
 unsigned stage_threads() {
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const long forced = test_hook_long("STAGE_THREADS", 0);
@@ -1542,7 +1232,7 @@ struct ByteSource {   // where afq_submit's input comes from: the caller's buffe
     afq_read_fn read = nullptr;
     void* user = nullptr;
 };
-int staged_h2d(afq_ctx* c, uint8_t* dst, const uint8_t* src, size_t n, hipStream_t s, bool pinned, const ByteSource* rd = nullptr, uint64_t rd_off = 0) {
+int staged_h2d(afq_ctx* c, uint8_t* dst, const uint8_t* src, size_t n, hipStream_t s, bool pinned, const ByteSource* rd, uint64_t rd_off) {
     const bool use_reader = rd && rd->read;
     if (!use_reader && (pinned || n < 2 * kStagePiece)) { HIP_TRY(c, hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s)); return 0; }
     for (int i = 0; i < 3; ++i) {
@@ -1605,6 +1295,8 @@ int staged_h2d(afq_ctx* c, uint8_t* dst, const uint8_t* src, size_t n, hipStream
     return rc;
 }
 
+namespace {
+
 // Reset the per-batch state and cut the batch into ranges.
 int begin_batch(afq_ctx* c, uint32_t n_cells, uint64_t first_cell_index) {
     c->n_cells = n_cells;
@@ -1659,10 +1351,10 @@ int run_batch(afq_ctx* c) {
     }
     if (rc) {
         c->pending = false;
-        for (auto& rs : c->rs) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
+        for (auto& rs : range_slots(c)) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
         if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
         c->copies_in_flight = false;
-        for (auto& rs : c->rs) rs.rows_pending = false;
+        for (auto& rs : range_slots(c)) rs.rows_pending = false;
         return rc;
     }
     c->next_range = k;
@@ -1751,6 +1443,7 @@ int afq_create(const afq_config* cfg, const uint32_t* tid_to_gid, uint32_t ref_c
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, AFQ_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= ndev) return fail(nullptr, AFQ_ERR_NO_DEVICE, "device ordinal out of range");
     afq_ctx* c = new afq_ctx();
+    c->rs = new RangeState[2];
     c->cfg = *cfg;
     if (!c->cfg.usa_mode) c->cfg.sa_model = AFQ_SA_WINNER_TAKE_ALL;  // src/quant.rs:1456-1469
     c->device = device;
@@ -1759,7 +1452,7 @@ int afq_create(const afq_config* cfg, const uint32_t* tid_to_gid, uint32_t ref_c
     auto bail = [&](int code, const std::string& m) { g_create_err = m; afq_destroy(c); return code; };
     if (hipSetDevice(device) != hipSuccess) return bail(AFQ_ERR_NO_DEVICE, "hipSetDevice failed");
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(AFQ_ERR_HIP, "hipStreamCreate failed");
-    for (auto& rs : c->rs)
+    for (auto& rs : range_slots(c))
         if (hipStreamCreateWithFlags(&rs.stream, hipStreamNonBlocking) != hipSuccess) return bail(AFQ_ERR_HIP, "hipStreamCreate failed");
     if (c->d_t2g.ensure(4ull * ref_count) != hipSuccess) return bail(AFQ_ERR_OOM, "tid_to_gid allocation failed");
     if (hipMemcpy(c->d_t2g.p, tid_to_gid, 4ull * ref_count, hipMemcpyHostToDevice) != hipSuccess)
@@ -1775,7 +1468,7 @@ void afq_destroy(afq_ctx* c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);   // (before the slots' buffers and the result arrays go)
     harvest_timers(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto& rs : c->rs) {
+    for (auto& rs : range_slots(c)) {
         if (rs.stream) (void)hipStreamSynchronize(rs.stream);
         for (DevBuf* b : rs.all()) b->release();
         rs.h_em2_tiers.release();
@@ -1810,83 +1503,8 @@ void afq_destroy(afq_ctx* c) {
         }
         if (del) delete c->pool;
     }
+    delete[] c->rs;
     delete c;
-}
-
-// The checks of afq_chunk_table.h with the entry points' error texts (`noun`: what the caller's API calls a chunk).
-static int chunk_fault(afq_ctx* c, const char* noun, uint32_t i, ChunkFault f) {
-    static const char* const kWhat[] = {"", ": chunk offset out of range", ": chunk header/size out of range", ": chunk nbytes does not match its records"};
-    return fail(c, AFQ_ERR_BAD_INPUT, std::string(noun) + " " + std::to_string(i) + kWhat[f]);
-}
-static int check_chunk_offsets(afq_ctx* c, const uint64_t* chunk_off, uint32_t n, size_t n_bytes, const char* noun) {
-    const uint32_t bad = first_chunk_outside(chunk_off, n, n_bytes);
-    return bad < n ? chunk_fault(c, noun, bad, kChunkOffset) : 0;
-}
-
-// The `nbytes, nrec` headers of n chunks into hdr[2 * n], from host bytes or gathered off the device (k_gather_headers; `timed`:
-// under a K_GATHER bracket).  No byte is read and nothing is launched before every offset has passed stage A.
-static int fetch_chunk_headers(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n, bool on_device,
-                               uint32_t* hdr, const char* noun = "cell", bool timed = false) {
-    if (int rc = check_chunk_offsets(c, chunk_off, n, n_bytes, noun)) return rc;
-    for (uint32_t i = 0; i < n && !on_device; ++i) std::memcpy(hdr + 2ull * i, bytes + chunk_off[i], 8);
-    if (!on_device || !n) return 0;
-    HIP_TRY(c, c->d_chunk_off.ensure(8ull * n));
-    HIP_TRY(c, c->d_hdr.ensure(8ull * n));
-    HIP_TRY(c, hipMemcpyAsync(c->d_chunk_off.p, chunk_off, 8ull * n, hipMemcpyHostToDevice, c->stream));
-    std::optional<ScopedTimer> t;
-    if (timed) t.emplace(c, K_GATHER);
-    launch_gather_headers(c->stream, bytes, n_bytes, c->d_chunk_off.as<uint64_t>(), n, c->d_hdr.as<uint32_t>());
-    t.reset();
-    HIP_TRY(c, hipMemcpyAsync(hdr, c->d_hdr.p, 8ull * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// The chunk table of a record pass (the *_rad entry points over an uncollated RAD): every header fetched and checked - `min_rec`
-// is the bytes of a record without alignments -, each chunk with the slot of its first record; n_slots: the records of the call.
-static int build_sort_chunks(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, bool on_device, uint32_t min_rec,
-                             std::vector<SortChunk>& out, uint64_t& n_slots) {
-    std::vector<uint32_t> hdr(2ull * n_chunks);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_chunks, on_device, hdr.data(), "chunk")) return rc;
-    std::vector<SortChunk> chunks(n_chunks);
-    n_slots = 0;
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, min_rec)) return chunk_fault(c, "chunk", i, f);
-        chunks[i] = SortChunk{chunk_off[i], n_slots, nb, nr};
-        n_slots += nr;
-    }
-    out.swap(chunks);
-    return 0;
-}
-
-// Host bytes of a record pass to the device (c->d_bytes_own, through staged_h2d); bytes that are there already stay where they
-// are.  *d_bytes: where the kernels read them.  Called behind the entry point's own `ensure`s and before its copies of tables.
-static int stage_rad_bytes(afq_ctx* c, HipLatch& T, const std::function<int()>& hip_fail, const uint8_t* bytes, size_t n_bytes, bool on_device, hipStream_t s,
-                           const uint8_t** d_bytes) {
-    *d_bytes = bytes;
-    if (on_device) return 0;
-    T(c->d_bytes_own.ensure(n_bytes + 16));
-    if (!T.ok()) return hip_fail();
-    if (n_bytes)
-        if (int rc = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1))) return rc;
-    *d_bytes = c->d_bytes_own.as<uint8_t>();
-    return 0;
-}
-
-// A non-zero status word of a record pass's table + parse / measure kernels as the entry point's refusal.  `start_range`: what
-// the caller says of kErrStartRange behind "chunk k: " (`atac sort` and `atac generate-permit-list` mean different things by it);
-// null where the kernels never raise it.
-static int rad_status_fault(afq_ctx* c, const char* who, const DevStatus& st, const char* start_range = nullptr) {
-    harvest_timers(c);
-    const std::string at = std::to_string(st.err_cell);
-    if (st.err_code == kErrStartRange && start_range) return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": " + start_range);
-    switch (st.err_code) {
-        case kErrCorrection: return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + at + ": an observed barcode with two different corrected barcodes");
-        case kErrRecordWalk: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": the records do not tile the chunk (nbytes / nrec do not match them)");
-        case kErrRefRange: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + at + ": a reference id is not below ref_count");
-        default: return fail(c, AFQ_ERR_HIP, std::string(who) + ": device status " + std::to_string(st.err_code));
-    }
 }
 
 static int submit_host(afq_ctx* c, const ByteSource& src, size_t n_bytes, const uint64_t* chunk_off, const uint32_t* chunk_hdr,
@@ -2013,7 +1631,7 @@ int afq_collect(afq_ctx* c, afq_result* out) {
         rc = drain_copies(c);
         hc.lap("collect: wait for rows");
     } else {
-        for (auto& rs : c->rs) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
+        for (auto& rs : range_slots(c)) { if (rs.stream) (void)hipStreamSynchronize(rs.stream); rs.in_flight = false; }
         (void)drain_copies(c);
     }
     if (rc) return rc;
@@ -2150,1982 +1768,6 @@ int afq_infer(afq_ctx* c, const uint32_t* eq_labels, const uint64_t* eq_label_pt
     out->cell_ptr = R->cell_ptr.data(); out->gene = R->gene.p; out->val = R->val.p;
     out->bc = R->bc.data(); out->nrec = R->nrec.data(); out->flags = R->flags.data();
     out->opaque = R;
-    return 0;
-}
-
-// The ATAC entry points hand out gigabytes of results: into pageable malloc memory the D2H runs at a fraction of the link.
-// Their output arrays are pinned instead and recycled through a process-wide pool (afq_free returns them to it).
-namespace {
-struct PinnedPool {
-    std::mutex mu;
-    struct Ent { void* p; size_t cap; bool busy; };
-    std::vector<Ent> ents;
-    void* get(size_t n) {
-        std::lock_guard<std::mutex> g(mu);
-        Ent* best = nullptr;
-        for (auto& e : ents) if (!e.busy && e.cap >= n && (!best || e.cap < best->cap)) best = &e;
-        if (best) { best->busy = true; return best->p; }
-        void* q = nullptr;
-        const size_t cap = n + n / 8 + 4096;
-        if (hipHostMalloc(&q, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        ents.push_back({q, cap, true});
-        return q;
-    }
-    bool put(void* p) {
-        std::lock_guard<std::mutex> g(mu);
-        for (auto& e : ents) if (e.p == p) { e.busy = false; return true; }
-        return false;
-    }
-};
-PinnedPool* pinned_pool() { static PinnedPool* P = new PinnedPool(); return P; }
-// What an ATAC call hands out: arrays from pinned_pool() or malloc, given back (afq_free takes either) unless release()d into the
-// caller's out-parameters on success.  Copies and threads may still be writing into a block when an exit is taken, so before one
-// of these is destroyed or free_all()ed after work was started on its blocks: the filler threads are joined and both streams are
-// synchronised (atac_dedup_piped does that ahead of its first exit), and the pipeline's `runs` and `pin` go back to the pool
-// before a redo falls through to the plain route, which draws on the same pool.
-struct HostOuts {
-    void* p[6] = {};
-    int n = 0;
-    void* keep(void* q) { if (q) p[n++] = q; return q; }
-    void* pinned(size_t bytes) { return keep(pinned_pool()->get(bytes)); }
-    void* mallocd(size_t bytes) { return keep(std::malloc(bytes)); }
-    void free_all() { while (n) afq_free(p[--n]); }
-    void release() { n = 0; }
-    ~HostOuts() { free_all(); }
-};
-}  // namespace
-
-// Shared back half of the two ATAC entry points: de-duplicate the fragments sitting in A.ref/A.start/A.flen (cell i at
-// A.ptr[i], cell_cnt[i] of them when d_cnt is given, else up to A.ptr[i+1]) and hand the distinct ones out as malloc'd arrays.
-static int atac_dedup_device(afq_ctx* c, uint64_t n, uint32_t n_cells, const uint32_t* d_cnt, uint64_t** out_cell_ptr, uint32_t** out_ref,
-                             uint32_t** out_start, uint16_t** out_frag_len, uint16_t** out_count, HostClock& hc, unsigned long long* tally_out = nullptr) {
-    auto& A = c->atac;
-    hipStream_t s = c->stream;
-    const uint64_t n1 = std::max<uint64_t>(n, 1);
-    HipLatch T;
-    T(A.scr.ensure(16 * n1)); T(A.oref.ensure(4 * n1)); T(A.ostart.ensure(4 * n1)); T(A.oflen.ensure(2 * n1));
-    T(A.ocnt.ensure(2 * n1)); T(A.on.ensure(4ull * std::max<uint32_t>(n_cells, 1))); T(A.optr.ensure(8ull * (n_cells + 1)));
-    T(A.flag.ensure(4)); T(A.tally.ensure(16));
-    if (T.ok()) T(hipMemsetAsync(A.flag.p, 0, 4, s));
-    if (T.ok()) T(hipMemsetAsync(A.tally.p, 0, 16, s));
-    // (the tally starts here, not at the compaction: the dedup kernels add the runs whose 16-bit count wrapped to 0 or 1)
-    unsigned long long* const d_tally = tally_out ? A.tally.as<unsigned long long>() : nullptr;
-    std::vector<uint32_t> on(n_cells);
-    uint32_t wide = 0;
-    if (T.ok()) {
-        ScopedTimer t(c, K_ATAC, s);
-        launch_atac_dedup64(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
-                            A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
-                            A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), A.flag.as<uint32_t>(), d_cnt, d_tally);
-        T(hipGetLastError());
-    }
-    if (T.ok()) {
-        T(hipMemcpyAsync(&wide, A.flag.p, 4, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-    }
-    if (T.ok() && wide) {  // a reference id >= 65536: the 16-byte-record kernel (and its tally, not that of the cut keys' runs)
-        T(hipMemsetAsync(A.tally.p, 0, 16, s));
-        ScopedTimer t(c, K_ATAC, s);
-        launch_atac_dedup(s, n_cells, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>(),
-                          A.scr.p, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(),
-                          A.ocnt.as<uint16_t>(), A.on.as<uint32_t>(), d_cnt, d_tally);
-        T(hipGetLastError());
-    }
-    if (T.ok() && n_cells) T(hipMemcpyAsync(on.data(), A.on.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
-    if (T.ok()) T(hipStreamSynchronize(s));
-    hc.lap("atac: kernel");
-    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
-    HostOuts H;
-    uint64_t* optr = (uint64_t*)H.mallocd(8ull * (n_cells + 1));
-    if (!optr) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup: host allocation failed");
-    optr[0] = 0;
-    for (uint32_t i = 0; i < n_cells; ++i) optr[i + 1] = optr[i] + on[i];
-    const uint64_t tot = optr[n_cells], tot1 = std::max<uint64_t>(tot, 1);
-    uint32_t* oref = (uint32_t*)H.pinned(4 * tot1);
-    uint32_t* ostart = (uint32_t*)H.pinned(4 * tot1);
-    uint16_t* oflen = (uint16_t*)H.pinned(2 * tot1);
-    uint16_t* ocnt = (uint16_t*)H.pinned(2 * tot1);
-    if (!oref || !ostart || !oflen || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup: host allocation failed");
-    // dense runs on the device, then straight into the caller's arrays
-    T(A.cref.ensure(4 * tot1)); T(A.cstart.ensure(4 * tot1)); T(A.cflen.ensure(2 * tot1)); T(A.ccnt.ensure(2 * tot1));
-    if (T.ok()) T(hipMemcpyAsync(A.optr.p, optr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    if (T.ok() && tot) {
-        launch_atac_compact(s, n_cells, A.ptr.as<uint64_t>(), A.optr.as<uint64_t>(), A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(),
-                            A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.cref.as<uint32_t>(), A.cstart.as<uint32_t>(),
-                            A.cflen.as<uint16_t>(), A.ccnt.as<uint16_t>(), tally_out ? A.tally.as<unsigned long long>() : nullptr);
-        T(hipGetLastError());
-        T(hipMemcpyAsync(oref, A.cref.p, 4 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ostart, A.cstart.p, 4 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(oflen, A.cflen.p, 2 * tot, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ocnt, A.ccnt.p, 2 * tot, hipMemcpyDeviceToHost, s));
-    }
-    if (T.ok() && tally_out) T(hipMemcpyAsync(tally_out, A.tally.p, 16, hipMemcpyDeviceToHost, s));
-    if (T.ok()) T(hipStreamSynchronize(s));
-    hc.lap("atac: compact + D2H");
-    harvest_timers(c);
-    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
-    H.release();
-    *out_cell_ptr = optr; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_count = ocnt;
-    return 0;
-}
-
-int afq_atac_dedup(afq_ctx* c, const uint32_t* ref, const uint32_t* start, const uint16_t* frag_len,
-                   const uint64_t* cell_ptr, uint32_t n_cells, uint64_t** out_cell_ptr, uint32_t** out_ref,
-                   uint32_t** out_start, uint16_t** out_frag_len, uint16_t** out_count) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if (!cell_ptr || !out_cell_ptr || !out_ref || !out_start || !out_frag_len || !out_count)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t n = cell_ptr[n_cells];
-    if (n && (!ref || !start || !frag_len)) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    for (uint32_t i = 0; i < n_cells; ++i)
-        if (cell_ptr[i + 1] < cell_ptr[i] || cell_ptr[i + 1] - cell_ptr[i] > 0x7FFFFFFFull)
-            return fail(c, AFQ_ERR_INVALID_ARG, "cell_ptr must be non-decreasing");
-    HostClock hc;
-    auto& A = c->atac;
-    hipStream_t s = c->stream;
-    const uint64_t n1 = std::max<uint64_t>(n, 1);
-    HipLatch T;
-    T(A.ref.ensure(4 * n1)); T(A.start.ensure(4 * n1)); T(A.flen.ensure(2 * n1)); T(A.ptr.ensure(8ull * (n_cells + 1)));
-    if (T.ok() && n) {   // (the pinned staging path of afq_submit was measured here too: no faster for these arrays)
-        T(hipMemcpyAsync(A.ref.p, ref, 4 * n, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(A.start.p, start, 4 * n, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(A.flen.p, frag_len, 2 * n, hipMemcpyHostToDevice, s));
-    }
-    if (T.ok()) T(hipMemcpyAsync(A.ptr.p, cell_ptr, 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    if (hc.on) { T(hipStreamSynchronize(s)); hc.lap("atac: alloc + H2D"); }
-    if (!T.ok()) return T.fail(c, "afq_atac_dedup");
-    reset_kernel_times(c);
-    return atac_dedup_device(c, n, n_cells, nullptr, out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc);
-}
-
-namespace {
-// What the two routes of afq_atac_dedup_rad (the eight-range pipeline and the plain one) work on.
-struct AtacRadJob {
-    const uint8_t* d_bytes;
-    size_t n_bytes;
-    uint32_t n_cells, bc_bytes;
-    uint64_t n_rec = 0;
-    std::vector<uint64_t> cap_ptr;   // capacity offsets of the cells' fragments = prefix of nrec
-    DevStatus st{};
-    std::vector<uint32_t> stat;      // per cell: multi-mapped, not a mapped pair
-    unsigned long long tally[2] = {0, 0};
-    uint64_t* obc = nullptr;         // the cells' barcodes (the caller's; owned by afq_atac_dedup_rad until it returns 0)
-    AtacParseArgs parse_args(AtacBufs& A, uint32_t c0, uint32_t c1, uint32_t* nwalk, DevStatus* dst) const {
-        return AtacParseArgs{d_bytes, A.cells.as<AtacCell>() + c0, c1 - c0, bc_bytes, A.bm.as<uint64_t>(), A.ref.as<uint32_t>(), A.start.as<uint32_t>(),
-                             A.flen.as<uint16_t>(), A.cnt.as<uint32_t>() + c0, A.bc.as<uint64_t>() + c0, A.stat.as<uint32_t>() + 2ull * c0,
-                             A.walk.as<uint32_t>() + c0, nwalk, dst, (uint64_t)n_bytes};
-    }
-};
-constexpr int kPipedDone = 0, kPipedRedo = 1;   // (or an AFQ_ERR_ code, all negative)
-}  // namespace
-
-// Big batches go through in eight ranges of cells: the distinct fragments of range r cross PCIe on a second stream while the
-// later ranges are still parsed and sorted.  The rows are the long pole - 12 bytes a row, 1.8 GB for 2*10^8 records, 34 ms at
-// the 52 GB/s the link gives (the e2e leg), against 20 ms for all the kernels - so (round 5) the ref column stays on the device
-// (8 bytes a row cross, 23 ms; the host writes the column from a list of runs, below), and what matters then is how soon the
-// FIRST rows can leave and how few are left when the last kernel ends: the ranges GROW (4, 8, 12, 14, 15, 16, 16, 15 % of the
-// records; four equal ranges kept the link idle for the first quarter of the kernels), the opposite of the cr-like taper,
-// whose rows are short.  Measured and not kept: the parse of range r+1 on a stream of its own next to the sort of range r
-// (the sort's workgroups wait for CUs behind the parse's: 12.7 -> 18.3 ms of sort, 28.6 -> 30.9 ms a step).
-// Returns kPipedDone (the outputs, J.obc, J.stat, J.tally and J.st.n_fallback are filled), kPipedRedo (a reference id >= 65536:
-// nothing is handed out or left allocated, the plain route runs the 16-byte-record kernel) or an error code.
-static int atac_dedup_piped(afq_ctx* c, AtacRadJob& J, uint64_t** out_cell_ptr, uint32_t** out_ref, uint32_t** out_start, uint16_t** out_frag_len,
-                            uint16_t** out_count, HostClock& hc) {
-    auto& A = c->atac;
-    hipStream_t s = c->stream;
-    const uint32_t n_cells = J.n_cells;
-    const uint64_t n1 = std::max<uint64_t>(J.n_rec, 1), nc1 = std::max<uint32_t>(n_cells, 1);
-    constexpr uint32_t kR = 8;
-    static const double kGrow[kR] = {0.04, 0.12, 0.24, 0.38, 0.53, 0.69, 0.85, 1.0};
-    uint32_t cut[kR + 1];
-    cut[0] = 0;
-    for (uint32_t r = 1; r < kR; ++r) {
-        const uint64_t target = (uint64_t)((double)J.n_rec * kGrow[r - 1]);
-        cut[r] = (uint32_t)(std::lower_bound(J.cap_ptr.begin(), J.cap_ptr.begin() + n_cells, target) - J.cap_ptr.begin());
-        if (cut[r] < cut[r - 1]) cut[r] = cut[r - 1];
-    }
-    cut[kR] = n_cells;
-    HipLatch T;
-    T(A.scr.ensure(16 * n1)); T(A.oref.ensure(4 * n1)); T(A.ostart.ensure(4 * n1)); T(A.oflen.ensure(2 * n1)); T(A.ocnt.ensure(2 * n1));
-    T(A.on.ensure(4ull * nc1)); T(A.optr.ensure(8ull * (n_cells + 1))); T(A.flag.ensure(4)); T(A.tally.ensure(16));
-    T(A.cref.ensure(4 * n1)); T(A.cstart.ensure(4 * n1)); T(A.cflen.ensure(2 * n1)); T(A.ccnt.ensure(2 * n1));   // (sized for "nothing is a duplicate")
-    T(A.rstat.ensure(kR * (sizeof(DevStatus) + 16))); T(A.runctr.ensure(4));
-    // The ref column does not cross PCIe: a cell's rows are sorted by ref first, so the column is a few runs per cell - the
-    // compaction kernel lists them (first row, length, ref: 16 bytes a run, written straight into pinned host memory) and
-    // host threads write the column from the list while the other three columns (8 of the 12 bytes of a row) are on the link.
-    // A list that overflows (more than 64 runs per cell on average: thousands of contigs) sends the column itself, as before.
-    const long cap_hook = test_hook_long("ATAC_RUN_CAP", -1);   // (tests: force the overflow)
-    // (at most 2^22 runs = 64 MiB of pinned memory whatever the number of barcodes - an unfiltered sample has a million of them; a
-    //  list that does not fit, or that the host has no pinned memory for, is the overflow case: the column crosses as a copy)
-    uint32_t run_cap = cap_hook >= 0 ? (uint32_t)cap_hook : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1u << 20, 64ull * n_cells), 1u << 22);
-    HostOuts out, tmp;   // the caller's columns; the run list and the pinned block, this function's own
-    uint4* runs = (uint4*)tmp.pinned(16ull * std::max<uint32_t>(run_cap, 1));
-    if (!runs) { run_cap = 0; runs = (uint4*)tmp.pinned(16); }
-    uint32_t* oref = (uint32_t*)out.pinned(4 * n1);
-    uint32_t* ostart = (uint32_t*)out.pinned(4 * n1);
-    uint16_t* oflen = (uint16_t*)out.pinned(2 * n1);
-    uint16_t* ocnt = (uint16_t*)out.pinned(2 * n1);
-    uint64_t* optr = (uint64_t*)out.mallocd(8ull * (n_cells + 1));
-    // (the per-range counts and flags land in PINNED memory: an async copy into pageable memory holds the host until the
-    // stream gets there, and the ranges would be enqueued one at a time)
-    uint8_t* pin = (uint8_t*)tmp.pinned(4ull * nc1 + kR * (sizeof(DevStatus) + 16));
-    if (!oref || !ostart || !oflen || !ocnt || !optr || !runs || !pin) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed");
-    hipStream_t s2 = c->rs[0].stream;
-    DevStatus* d_rst = reinterpret_cast<DevStatus*>(A.rstat.p);
-    uint32_t* d_rnw = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(A.rstat.p) + kR * sizeof(DevStatus));
-    uint32_t* on = reinterpret_cast<uint32_t*>(pin);
-    DevStatus* rst = reinterpret_cast<DevStatus*>(pin + 4ull * nc1);
-    uint32_t* wide = reinterpret_cast<uint32_t*>(pin + 4ull * nc1 + kR * sizeof(DevStatus));
-    volatile uint32_t* snap = wide + kR;   // the run counter as it stood after each range's compaction (the block has four words per range)
-    uint32_t* pin_dev = nullptr;   // the same block as the device sees it
-    T(hipHostGetDevicePointer(reinterpret_cast<void**>(&pin_dev), pin, 0));
-    uint4* runs_dev = nullptr;
-    T(hipHostGetDevicePointer(reinterpret_cast<void**>(&runs_dev), runs, 0));
-    hipEvent_t ev[2 * kR], *const ev2 = ev + kR;   // a range's kernels are done; its run list is complete
-    for (auto& x : ev) x = get_event(c);
-    T(hipMemsetAsync(A.runctr.p, 0, 4, s));
-    // the threads that write the ref column: thread 0 waits for a range's list (the event after its compaction), all fill
-    std::atomic<int> recorded{0}, listed{0}, stop{0};
-    const unsigned nfill = stage_threads();
-    std::vector<std::thread> fillers;
-    if (T.ok()) {
-        for (unsigned t = 0; t < nfill; ++t)
-            fillers.emplace_back([&, t]() {
-                if (t == 0) (void)hipSetDevice(c->device);
-                uint32_t lo = 0;
-                for (uint32_t r = 0; r < kR; ++r) {
-                    if (t == 0) {
-                        while (recorded.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-                        if (hipEventSynchronize(ev2[r]) != hipSuccess) { (void)hipGetLastError(); stop.store(1); return; }
-                        listed.store((int)r + 1, std::memory_order_release);
-                    } else {
-                        while (listed.load(std::memory_order_acquire) <= (int)r) { if (stop.load(std::memory_order_relaxed)) return; std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-                    }
-                    const uint32_t hi = snap[r];
-                    if (hi > run_cap) return;   // this range's column and every later one come as copies
-                    for (uint32_t i = lo + t; i < hi; i += nfill) {
-                        const uint4 q = runs[i];
-                        std::fill_n(oref + (((uint64_t)q.y << 32) | q.x), (size_t)q.z, q.w);
-                    }
-                    lo = hi;
-                }
-            });
-    }
-    T(hipMemsetAsync(A.flag.p, 0, 4, s));
-    T(hipMemsetAsync(A.tally.p, 0, 16, s));
-    T(hipMemsetAsync(A.rstat.p, 0, kR * (sizeof(DevStatus) + 16), s));
-    for (uint32_t r = 0; r < kR && T.ok(); ++r) {
-        const uint32_t c0 = cut[r], nr = cut[r + 1] - c0;
-        { ScopedTimer t(c, K_ATAC_PARSE, s); launch_atac_parse(s, J.parse_args(A, c0, cut[r + 1], d_rnw + r, d_rst + r)); }
-        { ScopedTimer t(c, K_ATAC, s);
-          launch_atac_dedup64(s, nr, A.ref.as<uint32_t>(), A.start.as<uint32_t>(), A.flen.as<uint16_t>(), A.ptr.as<uint64_t>() + c0, A.scr.p,
-                              A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(), A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.on.as<uint32_t>() + c0,
-                              A.flag.as<uint32_t>(), A.cnt.as<uint32_t>() + c0, A.tally.as<unsigned long long>()); }
-        T(hipGetLastError());
-        // (the range's counts, flag and status go to the pinned block by a kernel, not as copies: see k_copy_words3)
-        launch_copy_words3(s, A.on.as<uint32_t>() + c0, nr, pin_dev + c0, A.flag.as<uint32_t>(), 1, pin_dev + (wide - on) + r,
-                           reinterpret_cast<const uint32_t*>(d_rst + r), (uint32_t)(sizeof(DevStatus) / 4), pin_dev + (reinterpret_cast<uint32_t*>(rst + r) - on));
-        T(hipGetLastError());
-        T(hipEventRecord(ev[r], s));
-    }
-    optr[0] = 0;
-    bool redo = false;
-    int bad_rc = 0;
-    uint64_t n_fallback = 0;
-    for (uint32_t r = 0; r < kR && T.ok() && !redo && !bad_rc; ++r) {
-        const uint32_t c0 = cut[r], c1 = cut[r + 1];
-        T(hipEventSynchronize(ev[r]));
-        if (!T.ok()) break;
-        if (wide[r]) { redo = true; break; }
-        if (rst[r].err_code) { bad_rc = fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(c0 + rst[r].err_cell) + ": chunk nbytes does not match its records"); break; }
-        n_fallback += rst[r].n_fallback;
-        for (uint32_t i = c0; i < c1; ++i) optr[i + 1] = optr[i] + on[i];
-        const uint64_t o0 = optr[c0], tot_r = optr[c1] - o0;
-        T(hipMemcpyAsync(A.optr.as<uint64_t>() + c0, optr + c0, 8ull * (c1 - c0 + 1), hipMemcpyHostToDevice, s2));
-        if (tot_r) {
-            launch_atac_compact(s2, c1 - c0, A.ptr.as<uint64_t>() + c0, A.optr.as<uint64_t>() + c0, A.oref.as<uint32_t>(), A.ostart.as<uint32_t>(),
-                                A.oflen.as<uint16_t>(), A.ocnt.as<uint16_t>(), A.cref.as<uint32_t>(), A.cstart.as<uint32_t>(),
-                                A.cflen.as<uint16_t>(), A.ccnt.as<uint16_t>(), A.tally.as<unsigned long long>(), runs_dev, A.runctr.as<uint32_t>(), run_cap);
-            T(hipGetLastError());
-        }
-        launch_copy_words3(s2, A.runctr.as<uint32_t>(), 1, pin_dev + (const_cast<uint32_t*>(snap) - on) + r, nullptr, 0, nullptr, nullptr, 0, nullptr);
-        T(hipGetLastError());
-        T(hipEventRecord(ev2[r], s2));
-        if (T.ok()) recorded.store((int)r + 1, std::memory_order_release);
-        if (tot_r) {
-            T(hipMemcpyAsync(ostart + o0, A.cstart.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
-            T(hipMemcpyAsync(oflen + o0, A.cflen.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
-            T(hipMemcpyAsync(ocnt + o0, A.ccnt.as<uint16_t>() + o0, 2 * tot_r, hipMemcpyDeviceToHost, s2));
-        }
-    }
-    const bool done = T.ok() && !redo && !bad_rc;
-    if (!done) stop.store(1);
-    for (auto& th : fillers) th.join();
-    if (done) {
-        T(hipEventSynchronize(ev2[kR - 1]));   // (every range's count is on the host; the fillers stop at the first list that overflowed)
-        for (uint32_t r = 0; r < kR && T.ok(); ++r)
-            if (snap[r] > run_cap) {
-                const uint64_t o0 = optr[cut[r]], tot_r = optr[cut[r + 1]] - o0;
-                if (tot_r) T(hipMemcpyAsync(oref + o0, A.cref.as<uint32_t>() + o0, 4 * tot_r, hipMemcpyDeviceToHost, s2));
-            }
-        T(hipMemcpyAsync(J.tally, A.tally.p, 16, hipMemcpyDeviceToHost, s2));
-        if (n_cells) T(hipMemcpyAsync(J.stat.data(), A.stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
-        if (n_cells) T(hipMemcpyAsync(J.obc, A.bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s2));
-    }
-    (void)hipStreamSynchronize(s);
-    (void)hipStreamSynchronize(s2);
-    for (auto x : ev) c->event_pool.push_back(x);
-    tmp.free_all();
-    harvest_timers(c);
-    hc.lap("atac: ranges (parse, sort, compact, D2H)");
-    if (bad_rc) return bad_rc;
-    if (!T.ok()) return T.fail(c, "afq_atac_dedup_rad");
-    if (redo) return kPipedRedo;
-    J.st.n_fallback += n_fallback;
-    out.release();
-    *out_cell_ptr = optr; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_count = ocnt;
-    return kPipedDone;
-}
-
-int afq_atac_dedup_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_cells, uint32_t bc_bytes,
-                       int bytes_on_device, uint64_t** out_cell_ptr, uint64_t** out_bc, uint32_t** out_ref, uint32_t** out_start,
-                       uint16_t** out_frag_len, uint16_t** out_count, afq_atac_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_cells) || !out_cell_ptr || !out_bc || !out_ref || !out_start || !out_frag_len || !out_count)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- validate: chunk headers (from the host copy, or gathered off the device), capacity offsets = prefix of nrec
-    std::vector<uint32_t> hdr(2ull * n_cells);
-    if (int rc = fetch_chunk_headers(c, bytes, n_bytes, chunk_off, n_cells, bytes_on_device != 0, hdr.data())) return rc;
-    AtacRadJob J{bytes, n_bytes, n_cells, bc_bytes};
-    std::vector<AtacCell> cells(n_cells);
-    J.cap_ptr.assign((size_t)n_cells + 1, 0);
-    uint64_t bm_words = 0;
-    for (uint32_t i = 0; i < n_cells; ++i) {
-        const uint32_t nb = hdr[2 * i], nr = hdr[2 * i + 1];
-        if (const ChunkFault f = check_chunk_header(chunk_off[i], nb, nr, n_bytes, 4 + bc_bytes)) return chunk_fault(c, "cell", i, f);
-        cells[i] = AtacCell{chunk_off[i], J.n_rec, bm_words, nb, nr};
-        J.cap_ptr[i] = J.n_rec;
-        J.n_rec += nr;
-        bm_words += 4ull * (((uint64_t)nb + 3 + 255) / 256);   // four ballots per group of 256 positions (counted from the dword boundary below the chunk)
-    }
-    J.cap_ptr[n_cells] = J.n_rec;
-    // ---- upload
-    auto& A = c->atac;
-    const uint64_t n1 = std::max<uint64_t>(J.n_rec, 1), nc1 = std::max<uint32_t>(n_cells, 1);
-    HIP_TRY(c, A.ref.ensure(4 * n1)); HIP_TRY(c, A.start.ensure(4 * n1)); HIP_TRY(c, A.flen.ensure(2 * n1)); HIP_TRY(c, A.ptr.ensure(8ull * (n_cells + 1)));
-    HIP_TRY(c, A.cells.ensure(sizeof(AtacCell) * nc1)); HIP_TRY(c, A.bm.ensure(8 * std::max<uint64_t>(bm_words, 1))); HIP_TRY(c, A.cnt.ensure(4ull * nc1));
-    HIP_TRY(c, A.bc.ensure(8ull * nc1)); HIP_TRY(c, A.stat.ensure(8ull * nc1)); HIP_TRY(c, A.walk.ensure(4ull * nc1)); HIP_TRY(c, A.nwalk.ensure(4));
-    HIP_TRY(c, A.status.ensure(sizeof(DevStatus)));
-    if (!bytes_on_device) {
-        HIP_TRY(c, c->d_bytes_own.ensure(n_bytes + 16));
-        if (n_bytes) { int rc2 = staged_h2d(c, (uint8_t*)c->d_bytes_own.p, bytes, n_bytes, s, host_ptr_is_pinned(bytes) && host_ptr_is_pinned(bytes + n_bytes - 1)); if (rc2) return rc2; }
-        J.d_bytes = c->d_bytes_own.as<uint8_t>();
-    }
-    if (n_cells) HIP_TRY(c, hipMemcpyAsync(A.cells.p, cells.data(), sizeof(AtacCell) * n_cells, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(A.ptr.p, J.cap_ptr.data(), 8ull * (n_cells + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(A.nwalk.p, 0, 4, s));
-    HIP_TRY(c, hipMemsetAsync(A.status.p, 0, sizeof(DevStatus), s));
-    if (hc.on) { HIP_TRY(c, hipStreamSynchronize(s)); hc.lap("atac: alloc + H2D"); }
-    reset_kernel_times(c);
-    J.stat.assign(2ull * n_cells, 0);
-    HostOuts H;
-    J.obc = (uint64_t*)H.mallocd(8ull * nc1);
-    if (!J.obc) return fail(c, AFQ_ERR_OOM, "afq_atac_dedup_rad: host allocation failed");
-    // ---- piped (big batches) or plain
-    const size_t pipe_min = (size_t)test_hook_long("ATAC_PIPE_BYTES", 128L << 20);   // (tests: pipeline small inputs too)
-    int route = kPipedRedo;
-    if (n_cells >= 8 && n_bytes >= pipe_min) {
-        route = atac_dedup_piped(c, J, out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc);
-        if (route < 0) return route;
-        if (route == kPipedRedo) reset_kernel_times(c);
-    }
-    if (route == kPipedRedo) {
-        HIP_TRY(c, hipMemsetAsync(A.nwalk.p, 0, 4, s));
-        HIP_TRY(c, hipMemsetAsync(A.status.p, 0, sizeof(DevStatus), s));
-        {
-            ScopedTimer t(c, K_ATAC_PARSE, s);
-            launch_atac_parse(s, J.parse_args(A, 0, n_cells, A.nwalk.as<uint32_t>(), A.status.as<DevStatus>()));
-            HIP_TRY(c, hipGetLastError());
-        }
-        HipLatch T;
-        T(hipMemcpyAsync(&J.st, A.status.p, sizeof(J.st), hipMemcpyDeviceToHost, s));
-        if (T.ok() && n_cells) T(hipMemcpyAsync(J.stat.data(), A.stat.p, 8ull * n_cells, hipMemcpyDeviceToHost, s));
-        if (T.ok() && n_cells) T(hipMemcpyAsync(J.obc, A.bc.p, 8ull * n_cells, hipMemcpyDeviceToHost, s));
-        if (T.ok()) T(hipStreamSynchronize(s));   // the caller keeps ownership of `bytes`: the copy out of them is done by now, too
-        if (!T.ok()) return T.fail(c, "afq_atac_dedup_rad");
-        if (J.st.err_code) return fail(c, AFQ_ERR_BAD_INPUT, "cell " + std::to_string(J.st.err_cell) + ": chunk nbytes does not match its records");
-        int rc = atac_dedup_device(c, J.n_rec, n_cells, A.cnt.as<uint32_t>(), out_cell_ptr, out_ref, out_start, out_frag_len, out_count, hc, J.tally);
-        if (rc) return rc;
-    }
-    // ---- stats
-    H.release();
-    *out_bc = J.obc;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_records = J.n_rec;
-        for (uint32_t i = 0; i < n_cells; ++i) { stats->n_multimapped += J.stat[2 * i]; stats->n_not_mapped_pair += J.stat[2 * i + 1]; }
-        stats->n_distinct = (*out_cell_ptr)[n_cells];
-        stats->n_deduplicated = J.tally[0]; stats->n_long_fragments = J.tally[1];   // (tallied by the compaction kernel)
-        stats->n_fallback_cells = J.st.n_fallback;
-    }
-    return 0;
-}
-
-// `atac sort` on the device (afq_atac_sort.hip): table, parse + correct, partition into position bins, re-partition of the
-// oversize ones, leaves, dense arrays.  The host's part is what needs the whole picture and is small: the ranks of the corrected
-// barcodes, the bins' first ids, and - from the bins' counts - which segments are leaves and which are split again.
-void afq_atac_sort_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kSortBinShift; out[1] = kSortLeafCap; out[2] = kSortRepartAbove; out[3] = kSortParseTile;
-}
-
-void afq_atac_sort_leaf_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kSortSmallLeaf; out[1] = (uint32_t)kSortSmallLeafNT; out[2] = (uint32_t)kSortLeafNT; out[3] = kSortParseHalo;
-}
-
-void afq_atac_sort_table_slot(uint64_t barcode, uint64_t n_corr, uint32_t* home_slot, uint32_t* capacity) {
-    const uint64_t cap = sort_table_capacity(n_corr < (1ull << 30) ? n_corr : (1ull << 30) - 1);   // (afq_atac_sort_rad refuses 2^30 entries and more)
-    if (home_slot) *home_slot = sort_hash_bc(barcode) & (uint32_t)(cap - 1);
-    if (capacity) *capacity = (uint32_t)cap;
-}
-
-int afq_atac_sort_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
-                      int bytes_on_device, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint32_t* ref_lengths,
-                      uint32_t ref_count, uint64_t* out_n, uint32_t** out_ref, uint32_t** out_start, uint16_t** out_frag_len, uint64_t** out_bc,
-                      uint32_t** out_count, afq_atac_sort_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || ((!observed || !corrected) && n_corr) || (!ref_lengths && ref_count) || !out_n || !out_ref ||
-        !out_start || !out_frag_len || !out_bc || !out_count)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    if (n_corr >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^30 or more correction entries");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- host: ranks of the corrected barcodes, the all-ones key, the bins' first ids
-    std::vector<uint64_t> uniq(corrected, corrected + n_corr);
-    std::sort(uniq.begin(), uniq.end());
-    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-    if (uniq.size() >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^31 or more distinct corrected barcodes");
-    std::vector<uint32_t> rank(n_corr);
-    uint32_t ones_rank = kSortNoRank;
-    for (uint64_t i = 0; i < n_corr; ++i) {
-        rank[i] = (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), corrected[i]) - uniq.begin());
-        if (observed[i] == kSortEmptyKey) {
-            if (ones_rank != kSortNoRank && ones_rank != rank[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
-            ones_rank = rank[i];
-        }
-    }
-    std::vector<uint2> ref_info(std::max<uint32_t>(ref_count, 1));
-    std::vector<uint32_t> bin_base((size_t)ref_count + 1, 0);
-    uint64_t n_bins64 = 0;
-    for (uint32_t r = 0; r < ref_count; ++r) {
-        bin_base[r] = (uint32_t)n_bins64;
-        ref_info[r] = make_uint2(ref_lengths[r], (uint32_t)n_bins64);
-        n_bins64 += ((uint64_t)ref_lengths[r] + (1u << kSortBinShift) - 1) >> kSortBinShift;
-        if (n_bins64 >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^31 or more position bins");
-    }
-    bin_base[ref_count] = (uint32_t)n_bins64;
-    const uint32_t n_bins = (uint32_t)n_bins64;
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_sort_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + ")");
-    const uint64_t cap = sort_table_capacity(n_corr);
-    const uint32_t tab_mask = (uint32_t)(cap - 1);
-    // ---- does it fit?  (input + staging, 12 bytes a record of parse output, two key buffers, 22 bytes a row of output, the tables)
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);
-    {
-        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * (12 + 16 + 22), need_tab = cap * 12 + n_corr * 12 + uniq.size() * 8,
-                       need_misc = nc1 * (sizeof(SortChunk) + 16) + (uint64_t)nb1 * 8 + (uint64_t)ref_count * 12;
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
-                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables > " +
-                        std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->asort;
-    HipLatch T;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_atac_sort_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_corr) + " corrections)");
-    };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * std::max<uint64_t>(n_corr, 1))); T(B.rank.ensure(4 * std::max<uint64_t>(n_corr, 1)));
-    T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap)); T(B.rinfo.ensure(8ull * ref_info.size())); T(B.bbase.ensure(4ull * bin_base.size()));
-    T(B.rbc.ensure(8 * std::max<uint64_t>(uniq.size(), 1))); T(B.bin.ensure(4 * s1)); T(B.key0.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1));
-    T(B.status.ensure(sizeof(DevStatus))); T(B.hist.ensure(4ull * nb1)); T(B.cur.ensure(4ull * nb1)); T(B.segs.ensure(sizeof(SortSeg))); T(B.tally.ensure(8));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.rank.p, rank.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
-    if (ref_count) T(hipMemcpyAsync(B.rinfo.p, ref_info.data(), 8ull * ref_count, hipMemcpyHostToDevice, s));
-    T(hipMemcpyAsync(B.bbase.p, bin_base.data(), 4ull * bin_base.size(), hipMemcpyHostToDevice, s));
-    if (!uniq.empty()) T(hipMemcpyAsync(B.rbc.p, uniq.data(), 8 * uniq.size(), hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.hist.p, 0, 4ull * nb1, s));
-    T(hipMemsetAsync(B.tally.p, 0, 8, s));
-    if (hc.on) { T(hipStreamSynchronize(s)); hc.lap("atac sort: alloc + H2D"); }
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    // ---- table, parse
-    {
-        ScopedTimer t(c, K_ASORT_TABLE, s);
-        launch_sort_table(s, B.obs.as<uint64_t>(), B.rank.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_ASORT_PARSE, s);
-        launch_sort_parse(s, SortParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask,
-                                           ones_rank, B.rinfo.as<uint2>(), ref_count, B.bin.as<uint32_t>(), B.key0.as<uint64_t>(), B.cstat.as<uint32_t>(),
-                                           B.status.as<DevStatus>()});
-    }
-    T(hipGetLastError());
-    DevStatus st{};
-    std::vector<uint32_t> cstat(4ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("atac sort: table + parse");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return rad_status_fault(c, "afq_atac_sort_rad", st, "a start position is not below its reference's length");
-    afq_atac_sort_stats S{};
-    S.n_records = n_slots;
-    for (uint32_t i = 0; i < n_chunks; ++i) { S.n_unmapped += cstat[4 * i]; S.n_multimapped += cstat[4 * i + 1]; S.n_uncorrected += cstat[4 * i + 2]; S.n_kept += cstat[4 * i + 3]; }
-    const uint32_t n_kept = (uint32_t)S.n_kept;   // (< 2^32: n_slots is)
-    // ---- level 0: the position bins
-    std::vector<SortLeaf> leaves;
-    struct Big { uint32_t off, cnt, bin; };
-    std::vector<Big> big;
-    if (n_kept) {
-        T(B.ka.ensure(8ull * n_kept));
-        if (!T.ok()) return hip_fail();
-        const SortSeg seg0{0, (uint32_t)n_slots, 0, 0};
-        T(hipMemcpyAsync(B.segs.p, &seg0, sizeof(seg0), hipMemcpyHostToDevice, s));
-        {
-            ScopedTimer t(c, K_ASORT_PART, s);
-            launch_sort_partition(s, B.segs.as<SortSeg>(), 1, (uint32_t)n_slots, B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), n_bins, B.hist.as<uint32_t>(),
-                                  B.cur.as<uint32_t>(), B.ka.as<uint64_t>());
-        }
-        T(hipGetLastError());
-        std::vector<uint32_t> hist(n_bins);
-        T(hipMemcpyAsync(hist.data(), B.hist.p, 4ull * n_bins, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-        uint32_t off = 0;
-        for (uint32_t b = 0; b < n_bins; ++b) {
-            const uint32_t n = hist[b];
-            if (!n) continue;
-            if (n > kSortRepartAbove) { big.push_back(Big{off, n, b}); ++S.n_repartitioned_bins; }
-            else leaves.push_back(SortLeaf{off, n, b, 0});
-            off += n;
-        }
-        if (off != n_kept) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: the bins hold " + std::to_string(off) + " of " + std::to_string(n_kept) + " fragments");
-    }
-    hc.lap("atac sort: partition");
-    // ---- oversize segments: split by the eight highest bits in which their keys differ, until they fit a leaf or are one run
-    uint32_t src_is_b = 0;
-    for (uint32_t level = 0; !big.empty(); ++level) {
-        if (level > 64 / kSortRadixBits) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: a segment survived every key bit");
-        const uint32_t nb_ = (uint32_t)big.size();
-        std::vector<SortSeg> segs(nb_);
-        std::vector<uint64_t> ao(2ull * nb_);
-        uint32_t max_cnt = 0;
-        for (uint32_t i = 0; i < nb_; ++i) { segs[i] = SortSeg{big[i].off, big[i].cnt, i * 256u, 0}; ao[2 * i] = ~0ull; ao[2 * i + 1] = 0; max_cnt = std::max(max_cnt, big[i].cnt); }
-        T(B.segs.ensure(sizeof(SortSeg) * nb_)); T(B.andor.ensure(16ull * nb_)); T(B.hist.ensure(1024ull * nb_)); T(B.cur.ensure(1024ull * nb_)); T(B.kb.ensure(8ull * n_kept));
-        if (!T.ok()) return hip_fail();
-        uint64_t* src = src_is_b ? B.kb.as<uint64_t>() : B.ka.as<uint64_t>();
-        uint64_t* dst = src_is_b ? B.ka.as<uint64_t>() : B.kb.as<uint64_t>();
-        T(hipMemcpyAsync(B.segs.p, segs.data(), sizeof(SortSeg) * nb_, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(B.andor.p, ao.data(), 16ull * nb_, hipMemcpyHostToDevice, s));
-        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_bits(s, B.segs.as<SortSeg>(), nb_, max_cnt, src, B.andor.as<uint64_t>()); }
-        T(hipGetLastError());
-        T(hipMemcpyAsync(ao.data(), B.andor.p, 16ull * nb_, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-        std::vector<Big> split;
-        std::vector<SortSeg> ssegs;
-        max_cnt = 0;
-        for (uint32_t i = 0; i < nb_; ++i) {
-            const uint64_t diff = ao[2 * i] ^ ao[2 * i + 1];
-            if (!diff) { leaves.push_back(SortLeaf{big[i].off, big[i].cnt, big[i].bin, src_is_b | 2u}); continue; }   // one run: no sort
-            const uint32_t top = 63u - (uint32_t)__builtin_clzll(diff);
-            const uint32_t shift = top >= kSortRadixBits - 1 ? top - (kSortRadixBits - 1) : 0u;
-            ssegs.push_back(SortSeg{big[i].off, big[i].cnt, (uint32_t)split.size() * 256u, shift});
-            split.push_back(big[i]);
-            max_cnt = std::max(max_cnt, big[i].cnt);
-        }
-        big.clear();
-        if (split.empty()) break;
-        const uint32_t ns = (uint32_t)split.size();
-        std::vector<uint32_t> hist(256ull * ns);
-        T(hipMemcpyAsync(B.segs.p, ssegs.data(), sizeof(SortSeg) * ns, hipMemcpyHostToDevice, s));
-        T(hipMemsetAsync(B.hist.p, 0, 1024ull * ns, s));
-        { ScopedTimer t(c, K_ASORT_PART, s); launch_sort_partition(s, B.segs.as<SortSeg>(), ns, max_cnt, src, nullptr, 256, B.hist.as<uint32_t>(), B.cur.as<uint32_t>(), dst); }
-        T(hipGetLastError());
-        T(hipMemcpyAsync(hist.data(), B.hist.p, 1024ull * ns, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-        src_is_b ^= 1u;
-        for (uint32_t i = 0; i < ns; ++i) {
-            uint32_t off = split[i].off;
-            for (uint32_t d = 0; d < 256; ++d) {
-                const uint32_t n = hist[256ull * i + d];
-                if (!n) continue;
-                if (n == split[i].cnt) return fail(c, AFQ_ERR_HIP, "afq_atac_sort_rad: a re-partition level did not split its segment");
-                if (n > kSortRepartAbove) big.push_back(Big{off, n, split[i].bin});
-                else leaves.push_back(SortLeaf{off, n, split[i].bin, src_is_b});
-                off += n;
-            }
-        }
-    }
-    hc.lap("atac sort: re-partition");
-    // ---- leaves, in position order
-    std::sort(leaves.begin(), leaves.end(), [](const SortLeaf& a, const SortLeaf& b) { return a.off < b.off; });
-    const uint32_t n_leaves = (uint32_t)leaves.size();
-    std::vector<uint32_t> ids_small, ids_big, on(n_leaves), lout((size_t)n_leaves + 1, 0);
-    for (uint32_t i = 0; i < n_leaves; ++i) ((leaves[i].flags & 2u) || leaves[i].cnt <= kSortSmallLeaf ? ids_small : ids_big).push_back(i);
-    uint64_t n_out = 0;
-    if (n_leaves) {
-        T(B.leaves.ensure(sizeof(SortLeaf) * n_leaves)); T(B.ids.ensure(4ull * n_leaves)); T(B.on.ensure(4ull * n_leaves)); T(B.lout.ensure(4ull * (n_leaves + 1)));
-        if (!T.ok()) return hip_fail();
-        std::vector<uint32_t> ids(ids_small);
-        ids.insert(ids.end(), ids_big.begin(), ids_big.end());
-        T(hipMemcpyAsync(B.leaves.p, leaves.data(), sizeof(SortLeaf) * n_leaves, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(B.ids.p, ids.data(), 4ull * n_leaves, hipMemcpyHostToDevice, s));
-        {   // (the parse's outputs are dead after level 0: the runs' keys and lengths go where they were)
-            ScopedTimer t(c, K_ASORT_LEAF, s);
-            launch_sort_leaves(s, B.leaves.as<SortLeaf>(), B.ids.as<uint32_t>(), (uint32_t)ids_small.size(), B.ids.as<uint32_t>() + ids_small.size(), (uint32_t)ids_big.size(),
-                               B.ka.as<uint64_t>(), B.kb.as<uint64_t>(), B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), B.on.as<uint32_t>());
-        }
-        T(hipGetLastError());
-        T(hipMemcpyAsync(on.data(), B.on.p, 4ull * n_leaves, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-        for (uint32_t i = 0; i < n_leaves; ++i) { n_out += on[i]; lout[i + 1] = (uint32_t)n_out; }
-    }
-    hc.lap("atac sort: leaves");
-    const uint64_t o1 = std::max<uint64_t>(n_out, 1);
-    HostOuts H;
-    uint32_t* oref = (uint32_t*)H.pinned(4 * o1);
-    uint32_t* ostart = (uint32_t*)H.pinned(4 * o1);
-    uint16_t* oflen = (uint16_t*)H.pinned(2 * o1);
-    uint64_t* obc = (uint64_t*)H.pinned(8 * o1);
-    uint32_t* ocnt = (uint32_t*)H.pinned(4 * o1);
-    if (!oref || !ostart || !oflen || !obc || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_atac_sort_rad: host allocation failed (" + std::to_string(22 * o1) + " bytes of rows)");
-    unsigned long long n_long = 0;
-    if (n_out) {
-        // one allocation, the columns behind one another (8-byte column first)
-        T(B.out.ensure(22 * o1 + 64));
-        if (!T.ok()) return hip_fail();
-        uint8_t* b = B.out.as<uint8_t>();
-        uint64_t* dbc = reinterpret_cast<uint64_t*>(b);
-        uint32_t* dref = reinterpret_cast<uint32_t*>(b + 8 * o1);
-        uint32_t* dstart = reinterpret_cast<uint32_t*>(b + 12 * o1);
-        uint32_t* dcnt = reinterpret_cast<uint32_t*>(b + 16 * o1);
-        uint16_t* dflen = reinterpret_cast<uint16_t*>(b + 20 * o1);
-        T(hipMemcpyAsync(B.lout.p, lout.data(), 4ull * (n_leaves + 1), hipMemcpyHostToDevice, s));
-        {
-            ScopedTimer t(c, K_ASORT_EMIT, s);
-            launch_sort_emit(s, B.leaves.as<SortLeaf>(), n_leaves, B.lout.as<uint32_t>(), B.key0.as<uint64_t>(), B.bin.as<uint32_t>(), B.bbase.as<uint32_t>(), ref_count,
-                             B.rbc.as<uint64_t>(), dref, dstart, dflen, dbc, dcnt, B.tally.as<unsigned long long>());
-        }
-        T(hipGetLastError());
-        T(hipMemcpyAsync(oref, dref, 4 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ostart, dstart, 4 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(oflen, dflen, 2 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(obc, dbc, 8 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ocnt, dcnt, 4 * n_out, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(&n_long, B.tally.p, 8, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-    }
-    hc.lap("atac sort: emit + D2H");
-    harvest_timers(c);
-    if (!T.ok()) return hip_fail();
-    S.n_distinct = n_out; S.n_long_fragments = n_long;
-    if (stats) *stats = S;
-    H.release();
-    *out_n = n_out; *out_ref = oref; *out_start = ostart; *out_frag_len = oflen; *out_bc = obc; *out_count = ocnt;
-    return 0;
-}
-
-// The barcode column of a parse (c->gpl.bc; chunk i's first cstat[4 i + 1] slots) through the counting table: the distinct barcodes
-// with their counts, ascending.  afq_gpl_hist_rad's and afq_atac_gpl_hist_rad's.
-static int gpl_count_sorted(afq_ctx* c, const char* who, uint32_t n_chunks, uint64_t n_kept, uint32_t bc_bytes, HipLatch& T, const std::function<int()>& hip_fail,
-                            std::vector<std::pair<uint64_t, uint64_t>>& pairs) {
-    auto& B = c->gpl;
-    hipStream_t s = c->stream;
-    DevStatus st{};
-    const uint64_t cap = gpl_table_capacity(n_kept, bc_bytes);
-    T(B.tkey.ensure(8 * cap)); T(B.tcnt.ensure(8 * cap)); T(B.okey.ensure(4 * cap)); T(B.ocnt.ensure(4 * cap));   // (at most cap / 2 distinct barcodes)
-    if (!T.ok()) return hip_fail();
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.tcnt.p, 0, 8 * cap, s));
-    {
-        ScopedTimer t(c, K_GPL_COUNT, s);
-        launch_gpl_count(s, B.chunks.as<SortChunk>(), n_chunks, B.cstat.as<uint32_t>(), B.bc.as<uint64_t>(), B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(),
-                         (uint32_t)(cap - 1), B.ones.as<unsigned long long>(), B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_GPL_COMPACT, s);
-        launch_gpl_compact(s, B.tkey.as<uint64_t>(), B.tcnt.as<unsigned long long>(), cap, B.okey.as<uint64_t>(), B.ocnt.as<uint64_t>(), B.nout.as<uint32_t>());
-    }
-    T(hipGetLastError());
-    uint32_t n_tab = 0;
-    unsigned long long n_ones = 0;
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_tab, B.nout.p, 4, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_ones, B.ones.p, 8, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, std::string(who) + ": the counting table of " + std::to_string(cap) + " slots ran full (device status " + std::to_string(st.err_code) + ")"); }
-    if (n_tab > cap / 2) return fail(c, AFQ_ERR_HIP, std::string(who) + ": " + std::to_string(n_tab) + " keys in a table of " + std::to_string(cap) + " slots");
-    pairs.assign((size_t)n_tab + (n_ones ? 1 : 0), {0, 0});
-    {
-        std::vector<uint64_t> k(n_tab), n(n_tab);
-        if (n_tab) {
-            T(hipMemcpyAsync(k.data(), B.okey.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
-            T(hipMemcpyAsync(n.data(), B.ocnt.p, 8ull * n_tab, hipMemcpyDeviceToHost, s));
-            T(hipStreamSynchronize(s));
-        }
-        harvest_timers(c);
-        if (!T.ok()) return hip_fail();
-        for (uint32_t i = 0; i < n_tab; ++i) pairs[i] = {k[i], n[i]};
-        if (n_ones) pairs[n_tab] = {kSortEmptyKey, (uint64_t)n_ones};
-    }
-    std::sort(pairs.begin(), pairs.end());
-    return 0;
-}
-
-// The pairs of gpl_count_sorted count every record the parse put into the barcode column: `expect` of them, which the entry
-// point calls `what`.
-static int gpl_check_total(afq_ctx* c, const char* who, const std::vector<std::pair<uint64_t, uint64_t>>& pairs, uint64_t expect, const char* what) {
-    uint64_t total = 0;
-    for (const auto& pr : pairs) total += pr.second;
-    if (total == expect) return 0;
-    return fail(c, AFQ_ERR_HIP, std::string(who) + ": the table counts " + std::to_string(total) + " of " + std::to_string(expect) + " " + what);
-}
-
-// The pairs as the histogram a single-barcode pass hands over: barcodes and counts in blocks of H; with `obins`, a block for n_bins
-// position bins beside them (`atac generate-permit-list`'s, which fills it).
-static int gpl_hist_out(afq_ctx* c, const char* who, const std::vector<std::pair<uint64_t, uint64_t>>& pairs, HostOuts& H, uint64_t** obc, uint64_t** ocnt,
-                        uint64_t n_bins = 0, uint64_t** obins = nullptr) {
-    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
-    *obc = (uint64_t*)H.mallocd(8 * o1);
-    *ocnt = (uint64_t*)H.mallocd(8 * o1);
-    if (obins) *obins = n_bins ? (uint64_t*)H.mallocd(8ull * n_bins) : nullptr;
-    if (!*obc || !*ocnt || (n_bins && !*obins))
-        return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(16 * o1 + 8ull * n_bins) + " bytes of histogram" + (obins ? " and bins)" : ")"));
-    for (uint64_t i = 0; i < n_out; ++i) { (*obc)[i] = pairs[i].first; (*ocnt)[i] = pairs[i].second; }
-    return 0;
-}
-
-// `generate-permit-list` on the device (afq_gpl.hip): parse + orientation filter, counting table, compaction; the host sorts the
-// distinct barcodes.  And the correction decisions of distinct observed barcodes against a retained set.
-void afq_gpl_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = 0;
-}
-
-void afq_gpl_table_slot(uint64_t barcode, uint64_t n_kept, uint32_t bc_bytes, uint32_t* home_slot, uint32_t* capacity) {
-    const uint64_t cap = gpl_table_capacity(n_kept < (1ull << 30) ? n_kept : (1ull << 30) - 1, valid_width(bc_bytes) ? bc_bytes : 8);   // (afq_gpl_hist_rad refuses 2^30 records and more)
-    if (home_slot) *home_slot = sort_hash_bc(barcode) & (uint32_t)(cap - 1);
-    if (capacity) *capacity = (uint32_t)cap;
-}
-
-int afq_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
-                     uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, uint64_t* out_n, uint64_t** out_bc, uint64_t** out_count,
-                     afq_gpl_hist_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !out_n || !out_bc || !out_count) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (!valid_width(umi_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "umi_bytes must be 1, 2, 4 or 8");
-    if (expected_ori > kGplOriRc) return fail(c, AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes + umi_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 30))
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1);
-    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 16 a slot of the largest table, 16 a distinct barcode)
-        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, bc_bytes) * 24,
-                       need_misc = nc1 * (sizeof(SortChunk) + 16);
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_gpl_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
-                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables > " +
-                        std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->gpl;
-    HipLatch T;
-    auto hip_fail = [&]() { return T.fail(c, "afq_gpl_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records)"); };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
-    T(B.ones.ensure(8)); T(B.nout.ensure(4));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.ones.p, 0, 8, s));
-    T(hipMemsetAsync(B.nout.p, 0, 4, s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    {
-        ScopedTimer t(c, K_GPL_PARSE, s);
-        launch_gpl_parse(s, GplParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, umi_bytes, c->aln_extra, expected_ori,
-                                         B.bc.as<uint64_t>(), B.cstat.as<uint32_t>(), B.status.as<DevStatus>()});
-    }
-    T(hipGetLastError());
-    DevStatus st{};
-    std::vector<uint32_t> cstat(4ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("gpl: parse");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return rad_status_fault(c, "afq_gpl_hist_rad", st);
-    afq_gpl_hist_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        S.n_records += cstat[4 * i]; S.n_compatible += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_long_records += cstat[4 * i + 3];
-    }
-    // ---- count, compact
-    std::vector<std::pair<uint64_t, uint64_t>> pairs;
-    if (int rc = gpl_count_sorted(c, "afq_gpl_hist_rad", n_chunks, S.n_compatible, bc_bytes, T, hip_fail, pairs)) return rc;
-    hc.lap("gpl: count + compact + sort");
-    if (int rc = gpl_check_total(c, "afq_gpl_hist_rad", pairs, S.n_compatible, "compatible records")) return rc;
-    HostOuts H;
-    uint64_t *obc = nullptr, *ocnt = nullptr;
-    if (int rc = gpl_hist_out(c, "afq_gpl_hist_rad", pairs, H, &obc, &ocnt)) return rc;
-    if (stats) *stats = S;
-    H.release();
-    *out_n = pairs.size(); *out_bc = obc; *out_count = ocnt;
-    return 0;
-}
-
-// multi-barcode `generate-permit-list` on the device (afq_gpl_multi.hip): entry table, parse + orientation filter + routing; the
-// counting table and its compaction are afq_gpl_hist_rad's, over the keys entry << 32 | b1.
-void afq_gpl_multi_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = 0;
-}
-
-int afq_gpl_multi_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes,
-                           uint32_t b1_bytes, uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed,
-                           uint64_t n_entries, uint64_t* out_n, uint32_t** out_entry, uint64_t** out_cell, uint64_t** out_count,
-                           afq_gpl_multi_hist_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || (!sample_observed && n_entries) || !out_n || !out_entry || !out_cell || !out_count)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    {   // widths, orientation, the entry list (afq_gpl_host.h: the CPU suite runs these checks without a device)
-        std::string e;
-        if (int rc = gplhost::multi_check_args(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, n_entries, e)) return fail(c, rc, e);
-    }
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + b0_bytes + b1_bytes + umi_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 30))
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_multi_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ne1 = std::max<uint64_t>(n_entries, 1), ecap = sort_table_capacity(n_entries);
-    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 24 a slot of the largest counting table, 12 an entry and 12 a slot of its table)
-        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, 8) * 24 + ne1 * 12 + ecap * 12,
-                       need_misc = nc1 * (sizeof(SortChunk) + 16);
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_gpl_multi_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
-                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables (" +
-                        std::to_string(n_entries) + " routing entries) > " + std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->gpl;
-    HipLatch T;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_gpl_multi_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_entries) + " routing entries)");
-    };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
-    T(B.ones.ensure(8)); T(B.nout.ensure(4));
-    T(B.obs.ensure(8 * ne1)); T(B.idx.ensure(4 * ne1)); T(B.rkey.ensure(8 * ecap)); T(B.rval.ensure(4 * ecap)); T(B.cstatus.ensure(sizeof(DevStatus)));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    std::vector<uint32_t> idx(n_entries);
-    for (uint64_t i = 0; i < n_entries; ++i) idx[i] = (uint32_t)i;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_entries) {
-        T(hipMemcpyAsync(B.obs.p, sample_observed, 8 * n_entries, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(B.idx.p, idx.data(), 4 * n_entries, hipMemcpyHostToDevice, s));
-    }
-    T(hipMemsetAsync(B.rkey.p, 0xFF, 8 * ecap, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.cstatus.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.ones.p, 0, 8, s));
-    T(hipMemsetAsync(B.nout.p, 0, 4, s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    {
-        ScopedTimer t(c, K_GPLM_TABLE, s);
-        launch_sort_table(s, B.obs.as<uint64_t>(), B.idx.as<uint32_t>(), n_entries, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(ecap - 1), B.cstatus.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_GPLM_PARSE, s);
-        launch_gpl_multi_parse(s, GplMultiParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, b0_bytes, b1_bytes, umi_bytes, c->aln_extra, expected_ori,
-                                                    B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(ecap - 1), B.bc.as<uint64_t>(), B.cstat.as<uint32_t>(),
-                                                    B.status.as<DevStatus>()});
-    }
-    T(hipGetLastError());
-    DevStatus st{}, tst{};
-    std::vector<uint32_t> cstat(4ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&tst, B.cstatus.p, sizeof(tst), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and `sample_observed`: the copies out of them are done by now, too)
-    hc.lap("gpl multi: table + parse");
-    if (!T.ok()) return hip_fail();
-    if (tst.err_code) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_gpl_multi_hist_rad: entry table status " + std::to_string(tst.err_code) + " at entry " + std::to_string(tst.err_cell)); }
-    if (st.err_code) return rad_status_fault(c, "afq_gpl_multi_hist_rad", st);
-    afq_gpl_multi_hist_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        S.n_records += cstat[4 * i]; S.n_routed += cstat[4 * i + 1]; S.n_unrouted += cstat[4 * i + 2]; S.n_long_records += cstat[4 * i + 3];
-    }
-    S.n_compatible = S.n_routed + S.n_unrouted;
-    // ---- count, compact (chunk i's first cstat[4 i + 1] slots hold its keys)
-    std::vector<std::pair<uint64_t, uint64_t>> pairs;
-    if (int rc = gpl_count_sorted(c, "afq_gpl_multi_hist_rad", n_chunks, S.n_routed, 8, T, hip_fail, pairs)) return rc;
-    hc.lap("gpl multi: count + compact + sort");
-    if (int rc = gpl_check_total(c, "afq_gpl_multi_hist_rad", pairs, S.n_routed, "routed records")) return rc;
-    const uint64_t n_out = pairs.size(), o1 = std::max<uint64_t>(n_out, 1);
-    HostOuts H;
-    uint32_t* oent = (uint32_t*)H.mallocd(4 * o1);
-    uint64_t* ocell = (uint64_t*)H.mallocd(8 * o1);
-    uint64_t* ocnt = (uint64_t*)H.mallocd(8 * o1);
-    if (!oent || !ocell || !ocnt) return fail(c, AFQ_ERR_OOM, "afq_gpl_multi_hist_rad: host allocation failed (" + std::to_string(20 * o1) + " bytes of histogram)");
-    for (uint64_t i = 0; i < n_out; ++i) { oent[i] = (uint32_t)(pairs[i].first >> 32); ocell[i] = pairs[i].first & 0xFFFFFFFFull; ocnt[i] = pairs[i].second; }
-    if (stats) *stats = S;
-    H.release();
-    *out_n = n_out; *out_entry = oent; *out_cell = ocell; *out_count = ocnt;
-    return 0;
-}
-
-// `atac generate-permit-list` on the device (afq_atac_gpl.hip): one walk for the barcode column, the largest na and the position
-// bins; the counting table and its compaction are afq_gpl_hist_rad's.
-void afq_atac_gpl_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kSortParseTile; out[1] = kSortParseHalo; out[2] = 0; out[3] = 0;   // ([2]: the bins are counted in global memory, no workgroup holds any)
-}
-
-int afq_atac_gpl_hist_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes,
-                          int bytes_on_device, const uint64_t* bin_base, uint32_t ref_count, uint32_t bin_size, uint64_t* out_n, uint64_t** out_bc,
-                          uint64_t** out_count, uint64_t** out_bins, afq_atac_gpl_hist_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !bin_base || !out_n || !out_bc || !out_count || !out_bins) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (!bin_size) return fail(c, AFQ_ERR_INVALID_ARG, "bin_size must be at least 1");
-    if (bin_base[0] != 0) return fail(c, AFQ_ERR_INVALID_ARG, "bin_base[0] must be 0");
-    for (uint32_t r = 0; r < ref_count; ++r)
-        if (bin_base[r + 1] < bin_base[r]) return fail(c, AFQ_ERR_INVALID_ARG, "bin_base must ascend (entry " + std::to_string(r + 1) + " is below the one in front)");
-    if (bin_base[ref_count] >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_gpl_hist_rad: 2^31 or more position bins (" + std::to_string(bin_base[ref_count]) + ")");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    const uint32_t n_bins = (uint32_t)bin_base[ref_count];
-    std::vector<uint32_t> bbase(std::max<uint32_t>(ref_count, 1), 0);
-    for (uint32_t r = 0; r < ref_count; ++r) bbase[r] = (uint32_t)bin_base[r];
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 30))
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_gpl_hist_rad: 2^30 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), nb1 = std::max<uint32_t>(n_bins, 1);
-    {   // does it fit?  (input + staging, 8 bytes a record of parse output, 24 a slot of the largest table, 12 a bin)
-        const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 8, need_tab = gpl_table_capacity(n_slots, bc_bytes) * 24,
-                       need_misc = nc1 * (sizeof(SortChunk) + 16) + 12ull * nb1 + 4ull * bbase.size();
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need_rec + need_tab + need_misc > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_atac_gpl_hist_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + " +
-                        std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " + std::to_string(need_tab + need_misc) + " of tables and bins > " +
-                        std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->gpl;
-    HipLatch T;
-    auto hip_fail = [&]() { return T.fail(c, "afq_atac_gpl_hist_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_bins) + " bins)"); };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.bc.ensure(8 * s1)); T(B.cstat.ensure(16ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
-    T(B.ones.ensure(8)); T(B.nout.ensure(4)); T(B.bbase.ensure(4ull * bbase.size())); T(B.bins.ensure(4ull * nb1)); T(B.bins64.ensure(8ull * nb1)); T(B.bmax.ensure(4));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    T(hipMemcpyAsync(B.bbase.p, bbase.data(), 4ull * bbase.size(), hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.ones.p, 0, 8, s));
-    T(hipMemsetAsync(B.nout.p, 0, 4, s));
-    T(hipMemsetAsync(B.bins.p, 0, 4ull * nb1, s));
-    T(hipMemsetAsync(B.bmax.p, 0, 4, s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    {
-        ScopedTimer t(c, K_AGPL_PARSE, s);
-        launch_atac_gpl_parse(s, AtacGplParseArgs{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.bbase.as<uint32_t>(), ref_count, n_bins,
-                                                  bin_size, B.bc.as<uint64_t>(), B.bins.as<uint32_t>(), B.cstat.as<uint32_t>(), B.status.as<DevStatus>()});
-    }
-    {
-        ScopedTimer t(c, K_AGPL_BINS, s);
-        launch_atac_gpl_bins(s, B.bins.as<uint32_t>(), n_bins, B.bins64.as<uint64_t>(), B.bmax.as<uint32_t>());
-    }
-    T(hipGetLastError());
-    DevStatus st{};
-    uint32_t max_bin = 0;
-    std::vector<uint32_t> cstat(4ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&max_bin, B.bmax.p, 4, hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 16ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("atac gpl: parse + bins");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code)
-        return rad_status_fault(c, "afq_atac_gpl_hist_rad", st, ("a start position's bin is not below the number of bins (" + std::to_string(n_bins) + ")").c_str());
-    afq_atac_gpl_hist_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        S.n_unmapped += cstat[4 * i]; S.n_records += cstat[4 * i + 1]; S.max_ambig = std::max<uint64_t>(S.max_ambig, cstat[4 * i + 2]); S.n_multimapped += cstat[4 * i + 3];
-    }
-    S.n_binned = S.n_records - S.n_unmapped - S.n_multimapped;
-    S.max_bin = max_bin;
-    if (S.n_records != n_slots)
-        return fail(c, AFQ_ERR_HIP, "afq_atac_gpl_hist_rad: the parse saw " + std::to_string(S.n_records) + " of " + std::to_string(n_slots) + " records");
-    // ---- count, compact
-    std::vector<std::pair<uint64_t, uint64_t>> pairs;
-    if (int rc = gpl_count_sorted(c, "afq_atac_gpl_hist_rad", n_chunks, S.n_records, bc_bytes, T, hip_fail, pairs)) return rc;
-    hc.lap("atac gpl: count + compact + sort");
-    if (int rc = gpl_check_total(c, "afq_atac_gpl_hist_rad", pairs, S.n_records, "records")) return rc;
-    HostOuts H;
-    uint64_t *obc = nullptr, *ocnt = nullptr, *obins = nullptr;
-    if (int rc = gpl_hist_out(c, "afq_atac_gpl_hist_rad", pairs, H, &obc, &ocnt, n_bins, &obins)) return rc;
-    if (n_bins) {
-        T(hipMemcpyAsync(obins, B.bins64.p, 8ull * n_bins, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-    }
-    if (stats) *stats = S;
-    H.release();
-    *out_n = pairs.size(); *out_bc = obc; *out_count = ocnt; *out_bins = obins;
-    return 0;
-}
-
-int afq_gpl_correct(afq_ctx* c, const uint64_t* observed, const uint64_t* obs_count, uint64_t n_obs, const uint64_t* retained, const uint64_t* ret_count,
-                    uint64_t n_ret, uint32_t barcode_len, uint32_t neighborhood, uint32_t resolution, uint64_t conf_num, uint64_t conf_den,
-                    uint64_t pseudocount, uint8_t** out_decision, uint32_t** out_target, uint64_t** out_target_count, afq_gpl_correction_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if (((!observed || !obs_count) && n_obs) || ((!retained || !ret_count) && n_ret) || !out_decision || !out_target || !out_target_count)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (barcode_len < 1 || barcode_len > 32) return fail(c, AFQ_ERR_INVALID_ARG, "barcode length must be between 1 and 32 (got " + std::to_string(barcode_len) + ")");
-    if (neighborhood > kGplShift) return fail(c, AFQ_ERR_INVALID_ARG, "neighborhood must be 0 (hamming-1) or 1 (substitution-or-shift-1)");
-    if (resolution > kGplFrequency) return fail(c, AFQ_ERR_INVALID_ARG, "resolution must be 0 (unique) or 1 (frequency)");
-    if (resolution == kGplFrequency) {
-        if (conf_den == 0 || conf_num > conf_den)
-            return fail(c, AFQ_ERR_INVALID_ARG, "barcode-correction confidence must be between zero and one (got " + std::to_string(conf_num) + "/" + std::to_string(conf_den) + ")");
-        if (pseudocount == 0) return fail(c, AFQ_ERR_INVALID_ARG, "frequency correction requires a non-zero pseudocount");
-        if (pseudocount >= kGplMaxWeight) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: a pseudocount of 2^55 or more");
-    } else { conf_num = 0; conf_den = 1; pseudocount = 0; }
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    if (n_ret >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: 2^30 or more retained barcodes (" + std::to_string(n_ret) + ")");
-    if (n_obs >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: 2^32 or more observed barcodes in one call (" + std::to_string(n_obs) + ")");
-    const uint64_t fit = barcode_len < 32 ? (1ull << (2 * barcode_len)) : 0;   // (0: every u64 fits)
-    for (uint64_t i = 0; i < n_ret; ++i) {
-        if (i && retained[i] <= retained[i - 1]) return fail(c, AFQ_ERR_INVALID_ARG, "retained barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
-        if (fit && retained[i] >= fit) return fail(c, AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(retained[i]) + " does not fit declared length " + std::to_string(barcode_len));
-        if (resolution == kGplFrequency && ret_count[i] >= kGplMaxWeight - pseudocount)
-            return fail(c, AFQ_ERR_UNSUPPORTED, "afq_gpl_correct: retained barcode " + std::to_string(retained[i]) + " has an exact count + pseudocount of 2^55 or more");
-    }
-    for (uint64_t i = 0; i < n_obs; ++i) {
-        if (i && observed[i] <= observed[i - 1]) return fail(c, AFQ_ERR_INVALID_ARG, "observed barcodes must ascend without duplicates (entry " + std::to_string(i) + ")");
-        if (fit && observed[i] >= fit) return fail(c, AFQ_ERR_BAD_INPUT, "packed barcode " + std::to_string(observed[i]) + " does not fit declared length " + std::to_string(barcode_len));
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const uint64_t cap = sort_table_capacity(n_ret), no1 = std::max<uint64_t>(n_obs, 1), nr1 = std::max<uint64_t>(n_ret, 1);
-    {
-        const uint64_t need = no1 * 21 + nr1 * 28 + cap * 12;
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_gpl_correct: " + std::to_string(need) + " bytes for " + std::to_string(n_obs) + " observed and " + std::to_string(n_ret) +
-                        " retained barcodes > " + std::to_string(tot) + " bytes of device memory");
-    }
-    std::vector<uint32_t> idx(n_ret);
-    uint32_t ones_idx = kGplNoTarget;
-    for (uint64_t i = 0; i < n_ret; ++i) { idx[i] = (uint32_t)i; if (retained[i] == kSortEmptyKey) ones_idx = (uint32_t)i; }
-    auto& B = c->gpl;
-    HipLatch T;
-    auto hip_fail = [&]() { return T.fail(c, "afq_gpl_correct", " (" + std::to_string(n_obs) + " observed, " + std::to_string(n_ret) + " retained barcodes)"); };
-    T(B.obs.ensure(8 * no1)); T(B.obscnt.ensure(8 * no1)); T(B.ret.ensure(8 * nr1)); T(B.retcnt.ensure(8 * nr1)); T(B.idx.ensure(4 * nr1));
-    T(B.rkey.ensure(8 * cap)); T(B.rval.ensure(4 * cap)); T(B.dec.ensure(no1)); T(B.tgt.ensure(4 * no1)); T(B.stats.ensure(64)); T(B.tcount.ensure(8 * nr1));
-    T(B.cstatus.ensure(sizeof(DevStatus)));
-    if (!T.ok()) return hip_fail();
-    if (n_obs) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_obs, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.obscnt.p, obs_count, 8 * n_obs, hipMemcpyHostToDevice, s)); }
-    if (n_ret) {
-        T(hipMemcpyAsync(B.ret.p, retained, 8 * n_ret, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.retcnt.p, ret_count, 8 * n_ret, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(B.idx.p, idx.data(), 4 * n_ret, hipMemcpyHostToDevice, s));
-    }
-    T(hipMemsetAsync(B.rkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.stats.p, 0, 64, s));
-    T(hipMemsetAsync(B.tcount.p, 0, 8 * nr1, s));
-    T(hipMemsetAsync(B.cstatus.p, 0, sizeof(DevStatus), s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    {
-        ScopedTimer t(c, K_GPL_TABLE, s);
-        launch_sort_table(s, B.ret.as<uint64_t>(), B.idx.as<uint32_t>(), n_ret, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(cap - 1), B.cstatus.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_GPL_CORRECT, s);
-        launch_gpl_correct(s, GplCorrectArgs{B.obs.as<uint64_t>(), B.obscnt.as<uint64_t>(), n_obs, B.rkey.as<uint64_t>(), B.rval.as<uint32_t>(), (uint32_t)(cap - 1), ones_idx,
-                                             B.retcnt.as<uint64_t>(), barcode_len, neighborhood, resolution, conf_num, conf_den, pseudocount, B.dec.as<uint8_t>(),
-                                             B.tgt.as<uint32_t>(), B.stats.as<unsigned long long>(), B.tcount.as<unsigned long long>()});
-    }
-    T(hipGetLastError());
-    HostOuts H;
-    uint8_t* odec = (uint8_t*)H.mallocd(no1);
-    uint32_t* otgt = (uint32_t*)H.mallocd(4 * no1);
-    uint64_t* otc = (uint64_t*)H.mallocd(8 * nr1);
-    if (!odec || !otgt || !otc) { (void)hipStreamSynchronize(s); return fail(c, AFQ_ERR_OOM, "afq_gpl_correct: host allocation failed (" + std::to_string(5 * no1 + 8 * nr1) + " bytes of decisions)"); }
-    DevStatus st{};
-    uint64_t cs[8] = {};
-    T(hipMemcpyAsync(&st, B.cstatus.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(cs, B.stats.p, 64, hipMemcpyDeviceToHost, s));
-    if (n_obs) { T(hipMemcpyAsync(odec, B.dec.p, n_obs, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(otgt, B.tgt.p, 4 * n_obs, hipMemcpyDeviceToHost, s)); }
-    T(hipMemcpyAsync(otc, B.tcount.p, 8 * nr1, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
-    harvest_timers(c);
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_gpl_correct: device status " + std::to_string(st.err_code) + " at retained entry " + std::to_string(st.err_cell));
-    if (stats) {
-        stats->exact_distinct = cs[0]; stats->exact_reads = cs[1]; stats->corrected_distinct = cs[2]; stats->corrected_reads = cs[3];
-        stats->ambiguous_distinct = cs[4]; stats->ambiguous_reads = cs[5]; stats->not_found_distinct = cs[6]; stats->not_found_reads = cs[7];
-    }
-    H.release();
-    *out_decision = odec; *out_target = otgt; *out_target_count = otc;
-    return 0;
-}
-
-// Both collates' host step: val[i] = the index in `cells` of corrected[i]; ones_cell = the cell of the all-ones observed barcode
-// (it cannot be a key of the device's table, whose free slots are all ones), kSortNoRank without one.
-static int collate_cell_index(afq_ctx* c, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint64_t* cells, uint32_t n_cells,
-                              std::vector<uint32_t>& val, uint32_t& ones_cell) {
-    val.assign(n_corr, 0);
-    ones_cell = kSortNoRank;
-    std::vector<std::pair<uint64_t, uint32_t>> by_bc(n_cells);
-    for (uint32_t i = 0; i < n_cells; ++i) by_bc[i] = {cells[i], i};
-    std::sort(by_bc.begin(), by_bc.end());
-    for (uint32_t i = 1; i < n_cells; ++i)
-        if (by_bc[i].first == by_bc[i - 1].first)
-            return fail(c, AFQ_ERR_BAD_INPUT, "cells " + std::to_string(by_bc[i - 1].second) + " and " + std::to_string(by_bc[i].second) + " carry one barcode (" +
-                        std::to_string(by_bc[i].first) + ")");
-    for (uint64_t i = 0; i < n_corr; ++i) {
-        const auto it = std::lower_bound(by_bc.begin(), by_bc.end(), std::make_pair(corrected[i], 0u));
-        if (it == by_bc.end() || it->first != corrected[i])
-            return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": observed barcode " + std::to_string(observed[i]) + " is corrected to " +
-                        std::to_string(corrected[i]) + ", which is not a cell");
-        val[i] = it->second;
-        if (observed[i] == kSortEmptyKey) {
-            if (ones_cell != kSortNoRank && ones_cell != val[i]) return fail(c, AFQ_ERR_BAD_INPUT, "correction entry " + std::to_string(i) + ": an observed barcode with two different corrected barcodes");
-            ones_cell = val[i];
-        }
-    }
-    return 0;
-}
-
-// The snappy frame encoder (afq_snappy.hip).  Device bytes it takes beside n bytes of input that are on the device already: a
-// slot a chunk, 16 bytes of meta and 8 of offset a chunk, and the stream at its bound.
-static uint64_t snappy_device_need(uint64_t n) {
-    const uint64_t nb = snappy_blocks(n);
-    return nb * kSnappySlot + nb * sizeof(SnappyMeta) + (nb + 1) * 8 + snappy_stream_bound(n);
-}
-
-// d_in: n bytes on the device (whatever c->stream holds in front of them is waited for) -> their frame stream as one malloc'd
-// block.  The caller has checked that snappy_device_need(n) fits.
-static int snappy_encode_device(afq_ctx* c, const char* who, const uint8_t* d_in, uint64_t n, uint8_t** out, uint64_t* out_n, afq_snappy_stats* stats) {
-    static const uint8_t kId[10] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};
-    afq_snappy_stats S{};
-    S.n_in = n;
-    const uint64_t nb = snappy_blocks(n);
-    if (nb >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, std::string(who) + ": 2^31 or more snappy frame chunks (" + std::to_string(n) + " bytes)");
-    if (!nb) {
-        uint8_t* ob = (uint8_t*)std::malloc(10);
-        if (!ob) return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (10 bytes of snappy stream)");
-        std::memcpy(ob, kId, 10);
-        S.n_out = 10;
-        if (stats) *stats = S;
-        *out = ob; *out_n = 10;
-        return 0;
-    }
-    auto& Z = c->snappy;
-    hipStream_t s = c->stream;
-    HipLatch T;
-    HostClock hc;
-    const std::string detail = " (snappy encoder, " + std::to_string(n) + " bytes in " + std::to_string(nb) + " frame chunks)";
-    T(Z.slots.ensure(nb * kSnappySlot)); T(Z.meta.ensure(nb * sizeof(SnappyMeta))); T(Z.off.ensure((nb + 1) * 8)); T(Z.stream.ensure(snappy_stream_bound(n)));
-    if (!T.ok()) return T.fail(c, who, detail);
-    hc.lap("snappy: buffers");
-    {
-        ScopedTimer t(c, K_SNAPPY_BLOCKS, s);
-        launch_snappy_blocks(s, d_in, n, nb, Z.slots.as<uint8_t>(), Z.meta.as<SnappyMeta>());
-    }
-    {
-        ScopedTimer t(c, K_SNAPPY_PACK, s);
-        launch_snappy_layout(s, Z.meta.as<SnappyMeta>(), nb, Z.off.as<uint64_t>());
-        launch_snappy_pack(s, d_in, nb, Z.slots.as<uint8_t>(), Z.meta.as<SnappyMeta>(), Z.off.as<uint64_t>(), Z.stream.as<uint8_t>());
-    }
-    T(hipGetLastError());
-    std::vector<SnappyMeta> meta(nb);
-    uint64_t total = 0;
-    T(hipMemcpyAsync(&total, Z.off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(meta.data(), Z.meta.p, nb * sizeof(SnappyMeta), hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    hc.lap("snappy: kernels + lengths");
-    if (!T.ok()) { harvest_timers(c); return T.fail(c, who, detail); }
-    if (total < 10 + 8 * nb || total > snappy_stream_bound(n)) {
-        harvest_timers(c);
-        return fail(c, AFQ_ERR_HIP, std::string(who) + ": a snappy stream of " + std::to_string(total) + " bytes from " + std::to_string(n) + " of input");
-    }
-    uint8_t* ob = (uint8_t*)std::malloc(total);
-    if (!ob) { harvest_timers(c); return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(total) + " bytes of snappy stream)"); }
-    hc.lap("snappy: host block");
-    T(hipMemcpyAsync(ob, Z.stream.p, total, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    hc.lap("snappy: stream D2H");
-    harvest_timers(c);
-    if (!T.ok()) { std::free(ob); return T.fail(c, who, detail); }
-    S.n_out = total; S.n_blocks = nb;
-    for (const SnappyMeta& m : meta) {
-        if (m.body & kSnappyStored) ++S.n_blocks_stored;
-        S.n_literal_bytes += m.lit; S.n_copies += m.copies;
-    }
-    if (stats) *stats = S;
-    *out = ob; *out_n = total;
-    return 0;
-}
-
-void afq_snappy_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kSnappyBlock; out[1] = kSnappyHashSlots; out[2] = kSnappyMaxCopy; out[3] = kSnappyBlocksPerWg;
-}
-
-int afq_snappy_frame_encode(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, int bytes_on_device, uint8_t** out_bytes, uint64_t* out_n_bytes, afq_snappy_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || !out_bytes || !out_n_bytes) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes, need = snappy_device_need(n_bytes);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        if (need_in + need > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_snappy_frame_encode: the input does not fit the device: " + std::to_string(need_in) + " bytes of input + " + std::to_string(need) +
-                        " of slots, stream and tables > " + std::to_string(tot) + " bytes of device memory");
-    }
-    const uint8_t* d_in = bytes;
-    if (!bytes_on_device && n_bytes) {
-        HipLatch T;
-        T(c->snappy.in.ensure(n_bytes));
-        if (T.ok()) T(hipMemcpyAsync(c->snappy.in.p, bytes, n_bytes, hipMemcpyHostToDevice, c->stream));
-        if (!T.ok()) return T.fail(c, "afq_snappy_frame_encode", " (" + std::to_string(n_bytes) + " bytes of input)");
-        d_in = c->snappy.in.as<uint8_t>();
-    }
-    reset_kernel_times(c);
-    return snappy_encode_device(c, "afq_snappy_frame_encode", d_in, n_bytes, out_bytes, out_n_bytes, stats);
-}
-
-void afq_set_collate_compress(afq_ctx* c, int on) {
-    if (c) c->collate_compress = on != 0;
-}
-
-// Both collates' placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies.
-// The sorted words end in `src`; `dst` is the buffer the last pass read, free again.
-static void collate_radix_place(hipStream_t s, uint64_t*& src, uint64_t*& dst, uint32_t n, uint32_t n_cells, uint32_t* hist) {
-    for (uint32_t shift = 32; shift < 64 && (n_cells >> (shift - 32)) != 0; shift += 8) {
-        launch_collate_radix_pass(s, src, dst, n, shift, hist);
-        std::swap(src, dst);
-    }
-}
-
-// What afq_collate_rad and afq_collate_multi_rad share from the chunk table to the return: collate_plan in front of the entry's
-// uploads, collate_finish behind its measure launch.  The entry fills the first block, the plain data the two differ in, and keeps
-// what is its own: the index step, the uploads (the sample table's sit among the cell table's, and the order of the stream's
-// operations is the entry's), the args struct, the table and measure launches in their brackets, and the sum of its chunk_stat words.
-struct CollateRun {
-    const char* who;                                   // the entry's name in messages
-    int k_sort, k_scan, k_write;                       // timer ids: placement, length scan + heads, write walk
-    const char* lap_measure; const char* lap_write;    // HostClock labels
-    uint32_t head_bytes;                               // a record without alignments
-    uint64_t extra_tab_bytes;                          // device bytes of tables beside the cell table, the correction entries and the cells
-    // collate_plan's
-    std::vector<SortChunk> chunks;
-    uint64_t n_bytes = 0, n_slots = 0, cap = 0, s1 = 0, nc1 = 0, ncell1 = 0, ncorr1 = 0, need_out = 0;
-    uint32_t n = 0, n_chunks = 0, n_cells = 0;
-    HipLatch T;
-    int hip_fail(afq_ctx* c) const {
-        return T.fail(c, who, " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
-    }
-};
-
-// The chunk table, the sizes, the fit check and the buffers both entries use (R.T holds the first failure of an `ensure`: the
-// entry looks at it behind its own).
-static int collate_plan(afq_ctx* c, CollateRun& R, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, bool on_device, uint64_t n_corr,
-                        uint32_t n_cells) {
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, on_device, R.head_bytes, R.chunks, R.n_slots)) return rc;
-    const std::string who = R.who;
-    if (R.n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, who + ": 2^32 or more records in one call (" + std::to_string(R.n_slots) + "): fill the device in smaller parts");
-    R.n_bytes = n_bytes; R.n = (uint32_t)R.n_slots; R.n_chunks = n_chunks; R.n_cells = n_cells;
-    R.cap = sort_table_capacity(n_corr);
-    R.s1 = std::max<uint64_t>(R.n_slots, 1); R.nc1 = std::max<uint32_t>(n_chunks, 1); R.ncell1 = (uint64_t)n_cells + 1; R.ncorr1 = std::max<uint64_t>(n_corr, 1);
-    const uint64_t s1 = R.s1, nc1 = R.nc1, ncell1 = R.ncell1, cap = R.cap;
-    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock, n_sblocks = (s1 + kCollateScanBlock - 1) / kCollateScanBlock;
-    // does it fit?  (input + staging, the output - never longer than the input's records + the cells' headers -, 32 bytes a record
-    // of slots, sort words and offsets, the digit counts, the tables)
-    R.need_out = (uint64_t)n_bytes + 8 * ncell1;
-    const uint64_t need_in = on_device ? 0 : (uint64_t)n_bytes + 16, need_rec = s1 * 32 + 8 + n_rblocks * 1024 + n_sblocks * 8,
-                   need_tab = cap * 12 + n_corr * 12 + R.extra_tab_bytes + ncell1 * 20, need_misc = nc1 * (sizeof(SortChunk) + 32);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        const uint64_t need_sz = c->collate_compress ? snappy_device_need(R.need_out) : 0;   // (the encoder's slots, tables and stream beside the output)
-        if (need_in + R.need_out + need_rec + need_tab + need_misc + need_sz > tot)
-            return fail(c, AFQ_ERR_OOM, who + ": the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
-                        std::to_string(R.need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(R.n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables" + (need_sz ? " + " + std::to_string(need_sz) + " for the snappy encoder" : std::string()) + " > " +
-                        std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->collate;
-    HipLatch& T = R.T;
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * R.ncorr1)); T(B.val.ensure(4 * R.ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
-    T(B.cells.ensure(8 * ncell1)); T(B.rec.ensure(8 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks)); T(B.bsum.ensure(8 * n_sblocks));
-    T(B.ex.ensure(8 * (s1 + 1))); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus))); T(B.off.ensure(8 * ncell1)); T(B.nrec.ensure(4 * ncell1));
-    return 0;
-}
-
-// Behind the entry's measure launch: status and chunk_stat readback (cstat: [n_chunks][8], the entry's to sum), radix placement,
-// length scan, chunk heads, the entry's write walk (launch_write(dest, out)), the copies back and the closing checks.
-// cell_text(cell) words a cell for the 4 GiB-chunk refusal.
-static int collate_finish(afq_ctx* c, CollateRun& R, HostClock& hc, std::vector<uint32_t>& cstat, const std::function<void(const uint64_t*, uint8_t*)>& launch_write,
-                          const std::function<std::string(uint32_t)>& cell_text, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off, uint32_t** out_nrec) {
-    auto& B = c->collate;
-    HipLatch& T = R.T;
-    hipStream_t s = c->stream;
-    const std::string who = R.who;
-    const uint32_t n = R.n, n_chunks = R.n_chunks, n_cells = R.n_cells;
-    const uint64_t ncell1 = R.ncell1;
-    T(hipGetLastError());
-    DevStatus st{};
-    cstat.assign(8ull * n_chunks, 0);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes` and its tables: the copies out of them are done by now, too)
-    hc.lap(R.lap_measure);
-    if (!T.ok()) return R.hip_fail(c);
-    if (st.err_code) return rad_status_fault(c, R.who, st);
-    // ---- placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies
-    uint64_t* src = B.ka.as<uint64_t>();
-    uint64_t* dst = B.kb.as<uint64_t>();
-    {
-        ScopedTimer t(c, R.k_sort, s);
-        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
-    }
-    uint64_t kept_bytes = 0;
-    {
-        ScopedTimer t(c, R.k_scan, s);
-        launch_collate_scan(s, src, B.rec.as<uint2>(), n, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), dst);   // (dst: the buffer the last pass read is free)
-    }
-    T(hipGetLastError());
-    T(hipMemcpyAsync(&kept_bytes, B.ex.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return R.hip_fail(c);
-    const uint64_t out_total = 8ull * n_cells + kept_bytes, o1 = std::max<uint64_t>(out_total, 1);
-    if (out_total > R.need_out) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, who + ": " + std::to_string(out_total) + " bytes of output from " + std::to_string(R.n_bytes) + " of input"); }
-    T(B.out.ensure(o1));
-    if (!T.ok()) return R.hip_fail(c);
-    {
-        ScopedTimer t(c, R.k_scan, s);
-        launch_collate_heads(s, src, n, B.ex.as<uint64_t>(), n_cells, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), B.out.as<uint8_t>(), B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, R.k_write, s);
-        launch_write(dst, B.out.as<uint8_t>());
-    }
-    T(hipGetLastError());
-    HostOuts H;
-    const bool sz = c->collate_compress;   // the chunk bytes go down as a snappy frame stream, encoded behind the checks below
-    uint8_t* ob = sz ? nullptr : (uint8_t*)H.mallocd(o1);
-    uint64_t* ooff = (uint64_t*)H.mallocd(8 * ncell1);
-    uint32_t* onrec = (uint32_t*)H.mallocd(4 * ncell1);
-    if ((!sz && !ob) || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, who + ": host allocation failed (" + std::to_string(o1 + 12 * ncell1) + " bytes of output)"); }
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total && !sz) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(ooff, B.off.p, 8 * ncell1, hipMemcpyDeviceToHost, s));
-    if (n_cells) T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_cells, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
-    harvest_timers(c);
-    hc.lap(R.lap_write);
-    if (!T.ok()) return R.hip_fail(c);
-    if (st.err_code == kErrCollateChunk)
-        return fail(c, AFQ_ERR_UNSUPPORTED, who + ": cell " + std::to_string(st.err_cell) + " (" + cell_text(st.err_cell) + "): an output chunk of 4 GiB or more");
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, who + ": device status " + std::to_string(st.err_code) + " in the write");
-    if (ooff[n_cells] != out_total) return fail(c, AFQ_ERR_HIP, who + ": the chunks end at " + std::to_string(ooff[n_cells]) + " of " + std::to_string(out_total) + " output bytes");
-    uint64_t out_n = out_total;
-    if (sz) {
-        if (int rc = snappy_encode_device(c, R.who, B.out.as<uint8_t>(), out_total, &ob, &out_n, nullptr)) return rc;
-        hc.lap("snappy encode + D2H");
-    }
-    H.release();
-    *out_bytes = ob; *out_n_bytes = out_n; *out_chunk_off = ooff; *out_nrec = onrec;
-    return 0;
-}
-
-// `collate` on the device (afq_collate.hip): correction table, measure walk, radix placement, length scan, chunk heads, write walk.
-void afq_collate_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kGplLaneAlns; out[3] = kCollateRadixBlock;
-}
-
-int afq_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes, uint32_t umi_bytes,
-                    uint32_t expected_ori, int bytes_on_device, const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint64_t* cells,
-                    uint64_t n_cells64, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off, uint32_t** out_nrec, afq_collate_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || ((!observed || !corrected) && n_corr) || (!cells && n_cells64) || !out_bytes || !out_n_bytes ||
-        !out_chunk_off || !out_nrec)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (!valid_width(umi_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "umi_bytes must be 1, 2, 4 or 8");
-    if (expected_ori > kGplOriRc) return fail(c, AFQ_ERR_INVALID_ARG, "expected_ori must be 0 (both), 1 (fw) or 2 (rc)");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    if (n_corr >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: 2^30 or more correction entries");
-    if (n_cells64 > 0xFFFFFFFEull) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_collate_rad: more than 2^32 - 2 cells (" + std::to_string(n_cells64) + ")");
-    const uint32_t n_cells = (uint32_t)n_cells64;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- host: corrected barcode -> its index in `cells`; the all-ones key
-    std::vector<uint32_t> val;
-    uint32_t ones_cell = kSortNoRank;
-    if (int rc = collate_cell_index(c, observed, corrected, n_corr, cells, n_cells, val, ones_cell)) return rc;
-    // ---- chunk table, sizes, fit check, buffers
-    CollateRun R{"afq_collate_rad", K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, "collate: table + measure", "collate: place + write + D2H", 4 + bc_bytes + umi_bytes, 0};
-    if (int rc = collate_plan(c, R, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, n_corr, n_cells)) return rc;
-    const uint64_t cap = R.cap;
-    const uint32_t tab_mask = (uint32_t)(cap - 1);
-    auto& B = c->collate;
-    HipLatch& T = R.T;
-    auto hip_fail = [&]() { return R.hip_fail(c); };
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, R.chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
-    if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.ex.p, 0, 8, s));   // (ex[0]; with no record at all it is also ex[n])
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    CollateArgs a{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, umi_bytes, c->aln_extra, expected_ori, B.tkey.as<uint64_t>(),
-                  B.tval.as<uint32_t>(), tab_mask, ones_cell, n_cells, B.rec.as<uint2>(), B.ka.as<uint64_t>(), B.cstat.as<uint32_t>(), B.cells.as<uint64_t>(),
-                  nullptr, nullptr, B.status.as<DevStatus>()};
-    {
-        ScopedTimer t(c, K_COLLATE_TABLE, s);
-        launch_sort_table(s, B.obs.as<uint64_t>(), B.val.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_COLLATE_MEASURE, s);
-        launch_collate_measure(s, a);
-    }
-    std::vector<uint32_t> cstat;
-    if (int rc = collate_finish(c, R, hc, cstat, [&](const uint64_t* dest, uint8_t* out) { a.dest = dest; a.out = out; launch_collate_write(s, a); },
-                                [&](uint32_t cell) { return "barcode " + std::to_string(cells[cell]); }, out_bytes, out_n_bytes, out_chunk_off, out_nrec))
-        return rc;
-    afq_collate_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t* q = cstat.data() + 8ull * i;
-        S.n_records += q[0]; S.n_compatible += q[1]; S.n_uncorrected += q[2]; S.n_kept += q[3]; S.n_alignments_in += q[4]; S.n_alignments_kept += q[5]; S.n_long_records += q[6];
-    }
-    S.out_bytes = (*out_chunk_off)[n_cells];   // (uncompressed, also under afq_set_collate_compress)
-    if (stats) *stats = S;
-    return 0;
-}
-
-// multi-barcode `collate` on the device (k_collate_walk over CollateMultiArgs, afq_collate.hip): sample table, cell table, measure
-// walk, then collate's radix placement, length scan and chunk heads, write walk.
-void afq_collate_multi_limits(uint32_t out[4]) { afq_collate_limits(out); }   // (one walk: one set of limits)
-
-int afq_collate_multi_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t b0_bytes, uint32_t b1_bytes,
-                          uint32_t umi_bytes, uint32_t expected_ori, int bytes_on_device, const uint64_t* sample_observed, const uint32_t* sample_index,
-                          uint64_t n_sample_entries, const uint32_t* corr_sample, const uint64_t* corr_observed, const uint64_t* corr_corrected, uint64_t n_corr,
-                          const uint32_t* cell_sample, const uint64_t* cell_bc, uint64_t n_cells64, const uint32_t* sample_b0_out, uint64_t n_samples,
-                          uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off, uint32_t** out_nrec, afq_collate_multi_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || !out_bytes || !out_n_bytes || !out_chunk_off || !out_nrec) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    // ---- host: widths, orientation, the three inputs; (sample, corrected barcode) -> its index among the cells (afq_gpl_host.h: the CPU suite runs this without a device)
-    std::vector<uint32_t> val;
-    {
-        std::string e;
-        if (int rc = gplhost::collate_multi_index(b0_bytes, b1_bytes, umi_bytes, expected_ori, sample_observed, sample_index, n_sample_entries, corr_sample, corr_observed,
-                                                  corr_corrected, n_corr, cell_sample, cell_bc, n_cells64, sample_b0_out, n_samples, val, e))
-            return fail(c, rc, e);
-    }
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    const uint32_t n_cells = (uint32_t)n_cells64;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    std::vector<uint64_t> ckey(n_corr), chead(n_cells);
-    for (uint64_t i = 0; i < n_corr; ++i) ckey[i] = (uint64_t)corr_sample[i] << 32 | corr_observed[i];
-    for (uint32_t j = 0; j < n_cells; ++j) chead[j] = (uint64_t)sample_b0_out[cell_sample[j]] << 32 | cell_bc[j];
-    // ---- chunk table, sizes, fit check, buffers (afq_collate_rad's, with the sample entries and their table beside the cell table)
-    const uint64_t scap = sort_table_capacity(n_sample_entries), nse1 = std::max<uint64_t>(n_sample_entries, 1);
-    CollateRun R{"afq_collate_multi_rad", K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, "collate multi: tables + measure", "collate multi: place + write + D2H",
-                 4 + b0_bytes + b1_bytes + umi_bytes, scap * 12 + n_sample_entries * 12};
-    if (int rc = collate_plan(c, R, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, n_corr, n_cells)) return rc;
-    const uint64_t cap = R.cap;
-    const uint32_t tab_mask = (uint32_t)(cap - 1), stab_mask = (uint32_t)(scap - 1);
-    auto& B = c->collate;
-    HipLatch& T = R.T;
-    auto hip_fail = [&]() { return R.hip_fail(c); };
-    T(B.sobs.ensure(8 * nse1)); T(B.sidx.ensure(4 * nse1)); T(B.skey.ensure(8 * scap)); T(B.sval.ensure(4 * scap));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, R.chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_corr) { T(hipMemcpyAsync(B.obs.p, ckey.data(), 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
-    if (n_sample_entries) {
-        T(hipMemcpyAsync(B.sobs.p, sample_observed, 8 * n_sample_entries, hipMemcpyHostToDevice, s));
-        T(hipMemcpyAsync(B.sidx.p, sample_index, 4 * n_sample_entries, hipMemcpyHostToDevice, s));
-    }
-    if (n_cells) T(hipMemcpyAsync(B.cells.p, chead.data(), 8ull * n_cells, hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.skey.p, 0xFF, 8 * scap, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    T(hipMemsetAsync(B.ex.p, 0, 8, s));   // (ex[0]; with no record at all it is also ex[n])
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    CollateMultiArgs a{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, b0_bytes, b1_bytes, umi_bytes, c->aln_extra, expected_ori,
-                       B.skey.as<uint64_t>(), B.sval.as<uint32_t>(), stab_mask, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, n_cells,
-                       B.rec.as<uint2>(), B.ka.as<uint64_t>(), B.cstat.as<uint32_t>(), B.cells.as<uint64_t>(), nullptr, nullptr, B.status.as<DevStatus>()};
-    {
-        ScopedTimer t(c, K_COLLATEM_TABLE, s);
-        launch_sort_table(s, B.sobs.as<uint64_t>(), B.sidx.as<uint32_t>(), n_sample_entries, B.skey.as<uint64_t>(), B.sval.as<uint32_t>(), stab_mask, B.status.as<DevStatus>());
-        launch_sort_table(s, B.obs.as<uint64_t>(), B.val.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_COLLATEM_MEASURE, s);
-        launch_collate_multi_measure(s, a);
-    }
-    std::vector<uint32_t> cstat;
-    if (int rc = collate_finish(c, R, hc, cstat, [&](const uint64_t* dest, uint8_t* out) { a.dest = dest; a.out = out; launch_collate_multi_write(s, a); },
-                                [&](uint32_t cell) { return "sample " + std::to_string(cell_sample[cell]) + ", barcode " + std::to_string(cell_bc[cell]); }, out_bytes,
-                                out_n_bytes, out_chunk_off, out_nrec))
-        return rc;
-    afq_collate_multi_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t* q = cstat.data() + 8ull * i;
-        S.n_records += q[0]; S.n_compatible += q[1]; S.n_unrouted += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4]; S.n_alignments_in += q[5]; S.n_alignments_kept += q[6];
-        S.n_long_records += q[7];
-    }
-    S.out_bytes = (*out_chunk_off)[n_cells];   // (uncompressed, also under afq_set_collate_compress)
-    if (stats) *stats = S;
-    return 0;
-}
-
-// `atac collate` on the device (afq_atac_collate.hip): correction table, measure walk, radix placement, cell runs + their scan, chunk
-// heads, write walk.
-void afq_atac_collate_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kSortParseTile; out[1] = kSortParseHalo; out[2] = 11; out[3] = kCollateRadixBlock;
-}
-
-int afq_atac_collate_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* chunk_off, uint32_t n_chunks, uint32_t bc_bytes, int bytes_on_device,
-                         const uint64_t* observed, const uint64_t* corrected, uint64_t n_corr, const uint64_t* cells, uint64_t n_cells64, uint8_t** out_bytes,
-                         uint64_t* out_n_bytes, uint64_t* out_n_chunks, uint64_t** out_chunk_off, uint32_t** out_nrec, uint32_t** out_cell,
-                         afq_atac_collate_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!chunk_off && n_chunks) || ((!observed || !corrected) && n_corr) || (!cells && n_cells64) || !out_bytes || !out_n_bytes ||
-        !out_n_chunks || !out_chunk_off || !out_nrec || !out_cell)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes must be 1, 2, 4 or 8");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    if (n_corr >= (1ull << 30)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: 2^30 or more correction entries");
-    if (n_cells64 > 0xFFFFFFFEull) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: more than 2^32 - 2 cells (" + std::to_string(n_cells64) + ")");
-    const uint32_t n_cells = (uint32_t)n_cells64;
-    const uint32_t R = 4 + bc_bytes + 11;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    // ---- host: corrected barcode -> its index in `cells`; the all-ones key
-    std::vector<uint32_t> val;
-    uint32_t ones_cell = kSortNoRank;
-    if (int rc = collate_cell_index(c, observed, corrected, n_corr, cells, n_cells, val, ones_cell)) return rc;
-    // ---- chunk table
-    std::vector<SortChunk> chunks;
-    uint64_t n_slots = 0;
-    if (int rc = build_sort_chunks(c, bytes, n_bytes, chunk_off, n_chunks, bytes_on_device != 0, 4 + bc_bytes, chunks, n_slots)) return rc;
-    if (n_slots >= (1ull << 32)) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: 2^32 or more records in one call (" + std::to_string(n_slots) + "): fill the device in smaller parts");
-    const uint32_t n = (uint32_t)n_slots;
-    const uint64_t cap = sort_table_capacity(n_corr);
-    const uint32_t tab_mask = (uint32_t)(cap - 1);
-    const uint64_t s1 = std::max<uint64_t>(n_slots, 1), nc1 = std::max<uint32_t>(n_chunks, 1), ncell1 = (uint64_t)n_cells + 1, ncorr1 = std::max<uint64_t>(n_corr, 1);
-    const uint64_t n_rblocks = (s1 + kCollateRadixBlock - 1) / kCollateRadixBlock;
-    const uint64_t max_out = std::min<uint64_t>(n_cells, n_slots);   // chunks the output can have
-    // does it fit?  (input + staging, the output - a kept record is never longer than it was, + the heads -, 20 bytes a record of
-    // cells and sort words + the destination that reuses a sort buffer, the digit counts, the tables)
-    const uint64_t need_in = bytes_on_device ? 0 : (uint64_t)n_bytes + 16, need_out = (uint64_t)n_bytes + 8 * max_out + 8, need_rec = s1 * 20 + n_rblocks * 1024,
-                   need_tab = cap * 12 + n_corr * 12 + ncell1 * 16 + (max_out + 1) * 16, need_misc = nc1 * (sizeof(SortChunk) + 32);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-        const uint64_t need_sz = c->collate_compress ? snappy_device_need(need_out) : 0;   // (the encoder's slots, tables and stream beside the output)
-        if (need_in + need_out + need_rec + need_tab + need_misc + need_sz > tot)
-            return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
-                        std::to_string(need_out) + " of output + " + std::to_string(need_rec) + " for " + std::to_string(n_slots) + " records + " +
-                        std::to_string(need_tab + need_misc) + " of tables" + (need_sz ? " + " + std::to_string(need_sz) + " for the snappy encoder" : std::string()) + " > " +
-                        std::to_string(tot) + " bytes of device memory");
-    }
-    auto& B = c->acollate;
-    HipLatch T;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_atac_collate_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_slots) + " records, " + std::to_string(n_cells) + " cells)");
-    };
-    T(B.chunks.ensure(sizeof(SortChunk) * nc1)); T(B.obs.ensure(8 * ncorr1)); T(B.val.ensure(4 * ncorr1)); T(B.tkey.ensure(8 * cap)); T(B.tval.ensure(4 * cap));
-    T(B.cells.ensure(8 * ncell1)); T(B.cellof.ensure(4 * s1)); T(B.ka.ensure(8 * s1)); T(B.kb.ensure(8 * s1)); T(B.hist.ensure(1024 * n_rblocks));
-    T(B.first.ensure(4 * ncell1)); T(B.rank.ensure(4 * ncell1)); T(B.cstat.ensure(32ull * nc1)); T(B.status.ensure(sizeof(DevStatus)));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_chunks) T(hipMemcpyAsync(B.chunks.p, chunks.data(), sizeof(SortChunk) * n_chunks, hipMemcpyHostToDevice, s));
-    if (n_corr) { T(hipMemcpyAsync(B.obs.p, observed, 8 * n_corr, hipMemcpyHostToDevice, s)); T(hipMemcpyAsync(B.val.p, val.data(), 4 * n_corr, hipMemcpyHostToDevice, s)); }
-    if (n_cells) T(hipMemcpyAsync(B.cells.p, cells, 8ull * n_cells, hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.tkey.p, 0xFF, 8 * cap, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    AtacCollateArgs a{d_bytes, (uint64_t)n_bytes, B.chunks.as<SortChunk>(), n_chunks, bc_bytes, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, ones_cell,
-                      n_cells, B.cellof.as<uint32_t>(), B.ka.as<uint64_t>(), B.cstat.as<uint32_t>(), B.cells.as<uint64_t>(), nullptr, nullptr, B.status.as<DevStatus>()};
-    {
-        ScopedTimer t(c, K_ACOLLATE_TABLE, s);
-        launch_sort_table(s, B.obs.as<uint64_t>(), B.val.as<uint32_t>(), n_corr, B.tkey.as<uint64_t>(), B.tval.as<uint32_t>(), tab_mask, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_ACOLLATE_MEASURE, s);
-        launch_atac_collate_measure(s, a);
-    }
-    T(hipGetLastError());
-    DevStatus st{};
-    std::vector<uint32_t> cstat(8ull * n_chunks);
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (n_chunks) T(hipMemcpyAsync(cstat.data(), B.cstat.p, 32ull * n_chunks, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("atac collate: table + measure");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code) return rad_status_fault(c, "afq_atac_collate_rad", st);
-    afq_atac_collate_stats S{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        const uint32_t* q = cstat.data() + 8ull * i;
-        S.n_records += q[0]; S.n_unmapped += q[1]; S.n_multimapped += q[2]; S.n_uncorrected += q[3]; S.n_kept += q[4];
-    }
-    // ---- placement: stable LSD passes over the bytes of the cell word that n_cells (the dropped records' word) occupies, then the
-    // cells' runs and the scan that numbers the non-empty ones
-    uint64_t* src = B.ka.as<uint64_t>();
-    uint64_t* dst = B.kb.as<uint64_t>();
-    {
-        ScopedTimer t(c, K_ACOLLATE_PLACE, s);
-        collate_radix_place(s, src, dst, n, n_cells, B.hist.as<uint32_t>());
-        launch_atac_collate_runs(s, src, n, n_cells, B.first.as<uint32_t>(), B.rank.as<uint32_t>());
-        launch_collate_excl_scan_u32(s, B.rank.as<uint32_t>(), ncell1);
-    }
-    T(hipGetLastError());
-    uint32_t n_out = 0, n_kept_dev = 0;
-    T(hipMemcpyAsync(&n_out, B.rank.as<uint32_t>() + n_cells, 4, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_kept_dev, B.first.as<uint32_t>() + n_cells, 4, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    if (!T.ok()) return hip_fail();
-    if (n_kept_dev != S.n_kept || n_out > max_out || (n_out == 0) != (S.n_kept == 0)) {   // (the write's bounds rest on these)
-        harvest_timers(c);
-        return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: the placement holds " + std::to_string(n_kept_dev) + " records in " + std::to_string(n_out) + " cells, the measure kept " +
-                    std::to_string(S.n_kept));
-    }
-    const uint64_t out_total = (uint64_t)R * S.n_kept + 8ull * n_out, o1 = std::max<uint64_t>(out_total, 1), nout1 = (uint64_t)n_out + 1;
-    T(B.out.ensure(o1)); T(B.off.ensure(8 * nout1)); T(B.nrec.ensure(4 * nout1)); T(B.ocell.ensure(4 * nout1));
-    if (!T.ok()) return hip_fail();
-    a.dest = dst; a.out = B.out.as<uint8_t>();   // (dst: the buffer the last pass read is free)
-    {
-        ScopedTimer t(c, K_ACOLLATE_PLACE, s);
-        launch_atac_collate_heads(s, src, n, n_cells, R, B.first.as<uint32_t>(), B.rank.as<uint32_t>(), B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), B.ocell.as<uint32_t>(),
-                                  dst, a.out, B.status.as<DevStatus>());
-    }
-    {
-        ScopedTimer t(c, K_ACOLLATE_WRITE, s);
-        if (S.n_kept) launch_atac_collate_write(s, a);
-    }
-    T(hipGetLastError());
-    HostOuts H;
-    const bool sz = c->collate_compress;   // the chunk bytes go down as a snappy frame stream, encoded behind the checks below
-    uint8_t* ob = sz ? nullptr : (uint8_t*)H.mallocd(o1);
-    uint64_t* ooff = (uint64_t*)H.mallocd(8 * nout1);
-    uint32_t* onrec = (uint32_t*)H.mallocd(4 * nout1);
-    uint32_t* ocell = (uint32_t*)H.mallocd(4 * nout1);
-    if ((!sz && !ob) || !ooff || !onrec || !ocell) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_atac_collate_rad: host allocation failed (" + std::to_string(o1 + 16 * nout1) + " bytes of output)"); }
-    T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-    if (out_total && !sz) T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(ooff, B.off.p, 8 * nout1, hipMemcpyDeviceToHost, s));
-    if (n_out) { T(hipMemcpyAsync(onrec, B.nrec.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(ocell, B.ocell.p, 4ull * n_out, hipMemcpyDeviceToHost, s)); }
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into H's blocks)
-    harvest_timers(c);
-    hc.lap("atac collate: place + write + D2H");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code == kErrCollateChunk)
-        return fail(c, AFQ_ERR_UNSUPPORTED, "afq_atac_collate_rad: cell " + std::to_string(st.err_cell) + " (barcode " + std::to_string(cells[st.err_cell]) + "): an output chunk of 4 GiB or more");
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: device status " + std::to_string(st.err_code) + " in the write");
-    if (ooff[n_out] != out_total) return fail(c, AFQ_ERR_HIP, "afq_atac_collate_rad: the chunks end at " + std::to_string(ooff[n_out]) + " of " + std::to_string(out_total) + " output bytes");
-    S.n_cells_out = n_out; S.n_cells_empty = (uint64_t)n_cells - n_out; S.out_bytes = out_total;
-    uint64_t out_n = out_total;
-    if (sz) {
-        if (int rc = snappy_encode_device(c, "afq_atac_collate_rad", B.out.as<uint8_t>(), out_total, &ob, &out_n, nullptr)) return rc;
-        hc.lap("snappy encode + D2H");
-    }
-    if (stats) *stats = S;
-    H.release();
-    *out_bytes = ob; *out_n_bytes = out_n; *out_n_chunks = n_out; *out_chunk_off = ooff; *out_nrec = onrec; *out_cell = ocell;
-    return 0;
-}
-
-void afq_convert_limits(uint32_t out[4]) {
-    if (!out) return;
-    out[0] = kGplParseTile; out[1] = kGplParseHalo; out[2] = kConvertLaneAlns; out[3] = kConvertScanBlock;   // (the layout scan's workgroups take kCollateScanBlock, half of that)
-}
-
-// the error word of the convert kernels (record index << 8 | code) as the entry point's refusal
-static int convert_fault(afq_ctx* c, unsigned long long e) {
-    harvest_timers(c);
-    const std::string at = "record " + std::to_string(e >> 8) + ": ";
-    switch ((uint32_t)(e & 0xFF)) {
-        case kConvErrRecord: return fail(c, AFQ_ERR_BAD_INPUT, at + "malformed record: block_size is too small for the record's fixed fields, name, CIGAR and sequence, or runs past the stream, or the aux fields do not end at the record's end");
-        case kConvErrRef: return fail(c, AFQ_ERR_BAD_INPUT, at + "the reference id is negative or not below the BAM header's reference count");
-        case kConvErrTagMissing: return fail(c, AFQ_ERR_BAD_INPUT, at + "Input record missing CR or UR tag!");
-        case kConvErrTagType: return fail(c, AFQ_ERR_BAD_INPUT, at + "cannot convert non-string (Z) tag into barcode or umi string.");
-        case kConvErrBase: return fail(c, AFQ_ERR_BAD_INPUT, at + "unknown nucleotide in the CR or UR string (only A, C, G, T and N are coded)");
-        case kConvErrScore: return fail(c, AFQ_ERR_BAD_INPUT, at + "NO SCORE: --filter_best needs an integer AS tag on every record of a read that is written");
-        default: return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: device error word " + std::to_string(e));
-    }
-}
-
-int afq_convert_bam_rad(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, const uint64_t* span_off, uint32_t n_spans, uint32_t n_ref, uint32_t bc_bytes,
-                        uint32_t umi_bytes, int filter_best, int bytes_on_device, uint8_t** out_bytes, uint64_t* out_n_bytes, uint64_t** out_chunk_off,
-                        uint32_t** out_nrec, uint64_t* out_n_chunks, afq_convert_stats* stats) {
-    if (!c) return AFQ_ERR_INVALID_ARG;
-    if ((!bytes && n_bytes) || (!span_off && n_spans) || !out_bytes || !out_n_bytes || !out_chunk_off || !out_nrec || !out_n_chunks)
-        return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
-    if (!valid_width(bc_bytes) || !valid_width(umi_bytes)) return fail(c, AFQ_ERR_INVALID_ARG, "bc_bytes and umi_bytes must be 1, 2, 4 or 8");
-    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
-    if ((n_spans == 0) != (n_bytes == 0)) return fail(c, AFQ_ERR_INVALID_ARG, "afq_convert_bam_rad: a record stream needs a span table, and a span table a record stream");
-    for (uint32_t i = 0; i < n_spans; ++i)   // (the walks read [span_off[i], span_off[i + 1]) and nothing else)
-        if ((i == 0 && span_off[0] != 0) || (i && span_off[i] <= span_off[i - 1]) || span_off[i] >= n_bytes)
-            return fail(c, AFQ_ERR_INVALID_ARG, "afq_convert_bam_rad: span " + std::to_string(i) + ": the span table must begin at 0, ascend and stay below n_bytes");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HostClock hc;
-    hipStream_t s = c->stream;
-    size_t fr = 0, tot = 0;
-    HIP_TRY(c, hipMemGetInfo(&fr, &tot));
-    const uint64_t ns1 = std::max<uint32_t>(n_spans, 1), need_in = (bytes_on_device ? 0 : (uint64_t)n_bytes + 16) + ns1 * 24;
-    if (need_in > tot)
-        return fail(c, AFQ_ERR_OOM, "afq_convert_bam_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input, staging and span table > " +
-                    std::to_string(tot) + " bytes of device memory");
-    auto& B = c->convert;
-    HipLatch T;
-    uint64_t n_rec = 0, n_kept64 = 0;
-    auto hip_fail = [&]() {
-        return T.fail(c, "afq_convert_bam_rad", " (" + std::to_string(n_bytes) + " input bytes, " + std::to_string(n_spans) + " spans, " + std::to_string(n_rec) + " records)");
-    };
-    T(B.spans.ensure(8 * ns1)); T(B.scnt.ensure(8 * ns1)); T(B.sbase.ensure(8 * ns1)); T(B.err.ensure(8)); T(B.stat.ensure(8 * kConvStatCount)); T(B.status.ensure(sizeof(DevStatus)));
-    if (!T.ok()) return hip_fail();
-    const uint8_t* d_bytes = nullptr;
-    if (int rc = stage_rad_bytes(c, T, hip_fail, bytes, n_bytes, bytes_on_device != 0, s, &d_bytes)) return rc;
-    if (n_spans) T(hipMemcpyAsync(B.spans.p, span_off, 8ull * n_spans, hipMemcpyHostToDevice, s));
-    T(hipMemsetAsync(B.err.p, 0xFF, 8, s));
-    T(hipMemsetAsync(B.stat.p, 0, 8 * kConvStatCount, s));
-    T(hipMemsetAsync(B.status.p, 0, sizeof(DevStatus), s));
-    if (!T.ok()) return hip_fail();
-    reset_kernel_times(c);
-    ConvertArgs a{};
-    a.bytes = d_bytes; a.n_bytes = n_bytes; a.span_off = B.spans.as<uint64_t>(); a.n_spans = n_spans; a.n_ref = n_ref;
-    a.bc_bytes = bc_bytes; a.umi_bytes = umi_bytes; a.filter_best = filter_best != 0;
-    a.span_cnt = B.scnt.as<uint32_t>(); a.span_base = B.sbase.as<uint32_t>(); a.stat = B.stat.as<uint64_t>();
-    a.err = B.err.as<unsigned long long>(); a.st = B.status.as<DevStatus>();
-    // ---- the count walk; the host sums the spans' counts (a few words a span) into the bases of the fill walk
-    {
-        ScopedTimer t(c, K_CONVERT_WALK, s);
-        launch_convert_count(s, a);
-    }
-    T(hipGetLastError());
-    std::vector<uint32_t> cnt(2ull * n_spans), base(2ull * n_spans);
-    if (n_spans) T(hipMemcpyAsync(cnt.data(), B.scnt.p, 8ull * n_spans, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));   // (the caller keeps `bytes`: the copy out of them is done by now, too)
-    hc.lap("convert: H2D + count walk");
-    if (!T.ok()) return hip_fail();
-    for (uint32_t i = 0; i < n_spans; ++i) {
-        base[2ull * i] = (uint32_t)n_rec; base[2ull * i + 1] = (uint32_t)n_kept64;   // (read only below 2^32: checked next)
-        n_rec += cnt[2ull * i]; n_kept64 += cnt[2ull * i + 1];
-    }
-    if (n_rec >= (1ull << 32)) { harvest_timers(c); return fail(c, AFQ_ERR_UNSUPPORTED, "afq_convert_bam_rad: 2^32 or more records in one call (" + std::to_string(n_rec) + "): convert the file in parts"); }
-    const uint32_t n_kept = (uint32_t)n_kept64;
-    afq_convert_stats S{};
-    unsigned long long e = kConvNoErr;
-    uint32_t n_runs = 0, n_written = 0;
-    uint64_t n_chunks = 0, out_total = 0;
-    const uint64_t k1 = (uint64_t)n_kept + 1;
-    // does the rest fit?  A kept record: 25 bytes of offset, index, word, head flag, score; as a run of its own 36 more (first,
-    // barcode, UMI, flag, na, best score), 32 of placement (sort word, length, scan, destination) and its 4 + 8 + 8 + 4 output bytes
-    {
-        const uint64_t need_rec = k1 * (25 + 36 + 32 + 24) + 8 * (k1 / kConvertChunkRuns + 2) * 3;
-        if (need_in + need_rec > tot) {
-            harvest_timers(c);
-            return fail(c, AFQ_ERR_OOM, "afq_convert_bam_rad: the input does not fit the device: " + std::to_string(need_in) + " bytes of input and staging + up to " +
-                        std::to_string(need_rec) + " for " + std::to_string(n_kept) + " kept records > " + std::to_string(tot) + " bytes of device memory");
-        }
-    }
-    T(B.roff.ensure(8 * k1)); T(B.ridx.ensure(4 * k1)); T(B.word.ensure(4 * k1)); T(B.head.ensure(4 * k1)); T(B.score.ensure(4 * k1)); T(B.has.ensure(k1));
-    T(B.ssum.ensure(4 * ((k1 + kConvertScanBlock - 1) / kConvertScanBlock)));   // (the runs number at most n_kept: it serves both flag scans)
-    if (!T.ok()) return hip_fail();
-    a.n_kept = n_kept; a.rec_off = B.roff.as<uint64_t>(); a.rec_idx = B.ridx.as<uint32_t>(); a.word = B.word.as<uint32_t>(); a.head = B.head.as<uint32_t>();
-    a.score = B.score.as<int32_t>(); a.has_score = B.has.as<uint8_t>();
-    // ---- the fill walk (it raises the walk's errors: only now is a record's index in the file known), the names, the run numbers
-    if (n_spans) T(hipMemcpyAsync(B.sbase.p, base.data(), 8ull * n_spans, hipMemcpyHostToDevice, s));
-    {
-        ScopedTimer t(c, K_CONVERT_WALK, s);
-        launch_convert_fill(s, a);
-    }
-    {
-        ScopedTimer t(c, K_CONVERT_RUNS, s);
-        launch_convert_heads(s, a);
-        launch_convert_scan(s, a.head, k1, B.ssum.as<uint32_t>());
-    }
-    T(hipGetLastError());
-    T(hipMemcpyAsync(&e, B.err.p, 8, hipMemcpyDeviceToHost, s));
-    T(hipMemcpyAsync(&n_runs, a.head + n_kept, 4, hipMemcpyDeviceToHost, s));
-    T(hipStreamSynchronize(s));
-    hc.lap("convert: fill walk + names");
-    if (!T.ok()) return hip_fail();
-    if (e != kConvNoErr) return convert_fault(c, e);
-    if (n_runs > n_kept || (n_runs == 0) != (n_kept == 0)) { harvest_timers(c); return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: " + std::to_string(n_runs) + " runs of " + std::to_string(n_kept) + " records"); }
-    if (n_kept) {
-        // ---- the aux fields, the runs' best scores, the ranks of the written runs
-        const uint64_t r1 = (uint64_t)n_runs + 1;
-        T(B.rfirst.ensure(4 * r1)); T(B.rbc.ensure(8 * r1)); T(B.rumi.ensure(8 * r1)); T(B.rflag.ensure(4 * r1)); T(B.rna.ensure(4 * r1)); T(B.rmax.ensure(4 * r1));
-        if (!T.ok()) return hip_fail();
-        a.n_runs = n_runs; a.run_first = B.rfirst.as<uint32_t>(); a.run_bc = B.rbc.as<uint64_t>(); a.run_umi = B.rumi.as<uint64_t>(); a.run_flag = B.rflag.as<uint32_t>();
-        a.run_na = B.rna.as<uint32_t>(); a.run_max = B.rmax.as<int32_t>();
-        {
-            ScopedTimer t(c, K_CONVERT_RUNS, s);
-            launch_convert_aux(s, a);
-            launch_convert_runs(s, a);
-            launch_convert_scan(s, a.run_flag, r1, B.ssum.as<uint32_t>());
-        }
-        T(hipGetLastError());
-        uint64_t dstat[kConvStatCount] = {};
-        T(hipMemcpyAsync(&e, B.err.p, 8, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(&n_written, a.run_flag + n_runs, 4, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(dstat, B.stat.p, sizeof dstat, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        hc.lap("convert: aux + runs");
-        if (!T.ok()) return hip_fail();
-        if (e != kConvNoErr) return convert_fault(c, e);
-        S.n_runs_dropped_n = dstat[kConvRunsDroppedN]; S.n_alignments_in = dstat[kConvAlnIn]; S.n_alignments_written = dstat[kConvAlnWritten]; S.n_long_runs = dstat[kConvLongRuns];
-        if (n_written > n_runs || n_written + S.n_runs_dropped_n != n_runs) {   // (the placement's bounds rest on these)
-            harvest_timers(c);
-            return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: " + std::to_string(n_written) + " written and " + std::to_string(S.n_runs_dropped_n) + " dropped runs of " + std::to_string(n_runs));
-        }
-    }
-    n_chunks = ((uint64_t)n_written + kConvertChunkRuns - 1) / kConvertChunkRuns;
-    const uint64_t nc1 = n_chunks + 1;
-    if (n_written) {
-        // ---- the layout: the scan of the runs' lengths in written order, 8 bytes in front of every 10 001st
-        const uint64_t w1 = (uint64_t)n_written + 1, n_sblocks = (w1 + kCollateScanBlock - 1) / kCollateScanBlock;
-        T(B.key.ensure(8 * w1)); T(B.rec.ensure(8 * w1)); T(B.bsum.ensure(8 * n_sblocks)); T(B.ex.ensure(8 * w1)); T(B.dest.ensure(8 * w1));
-        if (!T.ok()) return hip_fail();
-        a.n_written = n_written; a.key = B.key.as<uint64_t>(); a.rec = B.rec.as<uint2>(); a.dest = B.dest.as<uint64_t>();
-        {
-            ScopedTimer t(c, K_CONVERT_PLACE, s);
-            launch_convert_place(s, a);
-            launch_collate_scan(s, a.key, a.rec, n_written, B.bsum.as<uint64_t>(), B.ex.as<uint64_t>(), B.dest.as<uint64_t>());
-        }
-        T(hipGetLastError());
-        uint64_t rec_bytes = 0;
-        T(hipMemcpyAsync(&rec_bytes, B.ex.as<uint64_t>() + n_written, 8, hipMemcpyDeviceToHost, s));
-        T(hipStreamSynchronize(s));
-        if (!T.ok()) return hip_fail();
-        const uint64_t H = 4 + bc_bytes + umi_bytes;
-        if (rec_bytes > H * n_written + 4 * S.n_alignments_written) {   // (equal, unless a run alone is 4 GiB: the status word says so below)
-            harvest_timers(c);
-            return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: the layout holds " + std::to_string(rec_bytes) + " bytes of runs, the runs " + std::to_string(H * n_written + 4 * S.n_alignments_written));
-        }
-        out_total = rec_bytes + 8 * n_chunks;
-    }
-    const uint64_t o1 = std::max<uint64_t>(out_total, 1);
-    T(B.out.ensure(o1)); T(B.off.ensure(8 * nc1)); T(B.nrec.ensure(4 * nc1));
-    if (!T.ok()) return hip_fail();
-    a.out = B.out.as<uint8_t>();
-    if (n_written) {
-        {
-            ScopedTimer t(c, K_CONVERT_PLACE, s);
-            launch_collate_heads(s, a.key, n_written, B.ex.as<uint64_t>(), (uint32_t)n_chunks, B.off.as<uint64_t>(), B.nrec.as<uint32_t>(), a.out, a.st);
-        }
-        {
-            ScopedTimer t(c, K_CONVERT_WRITE, s);
-            launch_convert_write(s, a);
-        }
-        T(hipGetLastError());
-    }
-    HostOuts Hs;
-    uint8_t* ob = (uint8_t*)Hs.mallocd(o1);
-    uint64_t* ooff = (uint64_t*)Hs.mallocd(8 * nc1);
-    uint32_t* onrec = (uint32_t*)Hs.mallocd(4 * nc1);
-    if (!ob || !ooff || !onrec) { (void)hipStreamSynchronize(s); harvest_timers(c); return fail(c, AFQ_ERR_OOM, "afq_convert_bam_rad: host allocation failed (" + std::to_string(o1 + 12 * nc1) + " bytes of output)"); }
-    DevStatus st{};
-    ooff[0] = 0;
-    if (n_written) {
-        T(hipMemcpyAsync(&st, B.status.p, sizeof(st), hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ob, B.out.p, out_total, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(ooff, B.off.p, 8 * nc1, hipMemcpyDeviceToHost, s));
-        T(hipMemcpyAsync(onrec, B.nrec.p, 4 * n_chunks, hipMemcpyDeviceToHost, s));
-    }
-    T(hipStreamSynchronize(s));   // (before any exit below: the copies write into Hs's blocks)
-    harvest_timers(c);
-    hc.lap("convert: place + write + D2H");
-    if (!T.ok()) return hip_fail();
-    if (st.err_code == kErrCollateChunk) return fail(c, AFQ_ERR_UNSUPPORTED, "afq_convert_bam_rad: output chunk " + std::to_string(st.err_cell) + ": an output chunk of 4 GiB or more");
-    if (st.err_code) return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: device status " + std::to_string(st.err_code) + " in the write");
-    if (ooff[n_chunks] != out_total) return fail(c, AFQ_ERR_HIP, "afq_convert_bam_rad: the chunks end at " + std::to_string(ooff[n_chunks]) + " of " + std::to_string(out_total) + " output bytes");
-    S.n_records = n_rec; S.n_dropped_by_flag = n_rec - n_kept; S.n_runs = n_runs; S.n_runs_written = n_written; S.n_chunks = n_chunks; S.out_bytes = out_total;
-    if (stats) *stats = S;
-    Hs.release();
-    *out_bytes = ob; *out_n_bytes = out_total; *out_chunk_off = ooff; *out_nrec = onrec; *out_n_chunks = n_chunks;
     return 0;
 }
 
