@@ -144,6 +144,9 @@ EXPORTS = [
     "afq_convert_limits",
     "afq_snappy_frame_encode",
     "afq_snappy_limits",
+    "afq_snappy_frame_decode_device",
+    "afq_snappy_decode_limits",
+    "afq_collated_chunk_table",
     "afq_set_collate_compress",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",

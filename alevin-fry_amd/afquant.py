@@ -349,6 +349,13 @@ def load_library(path: str = LIB_PATH):
     lib.afq_snappy_frame_encode.restype = C.c_int
     lib.afq_snappy_limits.argtypes = [p(C.c_uint32)]
     lib.afq_snappy_limits.restype = None
+    lib.afq_snappy_frame_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, p(p(C.c_uint8)), p(C.c_uint64), p(_abi.AfqSnappyStats)]
+    lib.afq_snappy_frame_decode_device.restype = C.c_int
+    lib.afq_collated_chunk_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, p(p(C.c_uint64)), p(p(C.c_uint32)), p(p(C.c_uint32)),
+                                             p(p(C.c_uint64)), p(C.c_uint64)]
+    lib.afq_collated_chunk_table.restype = C.c_int
+    lib.afq_snappy_decode_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_snappy_decode_limits.restype = None
     lib.afq_set_collate_compress.argtypes = [C.c_void_p, C.c_int]
     lib.afq_set_collate_compress.restype = None
     lib.afq_atac_collate_rad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, p(C.c_uint64), C.c_uint32, C.c_uint32, C.c_int, p(C.c_uint64), p(C.c_uint64),
@@ -466,6 +473,14 @@ def snappy_limits():
     out = (C.c_uint32 * 4)()
     load_library().afq_snappy_limits(out)
     return {"block": int(out[0]), "hash_slots": int(out[1]), "max_copy": int(out[2]), "blocks_per_workgroup": int(out[3])}
+
+
+def snappy_decode_limits():
+    """afq_snappy_decode_limits: {"window", "threads", "piece_chunks", "lds_bytes"} of the device snappy frame decoder - bytes of a chunk's
+    body staged per trip, threads of a workgroup (it takes one data chunk), data chunks of one launch at the most, LDS bytes of a workgroup."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_snappy_decode_limits(out)
+    return {"window": int(out[0]), "threads": int(out[1]), "piece_chunks": int(out[2]), "lds_bytes": int(out[3])}
 
 
 def convert_limits():
@@ -718,6 +733,35 @@ class Quantifier:
     def quant_chunks(self, chunk_bytes, chunk_off, first_cell_index: int = 0) -> QuantResult:
         self.submit(chunk_bytes, chunk_off, first_cell_index)
         return self.collect()
+
+    def snappy_frame_decode(self, stream, shift: int = 0, on_device: bool = False):
+        """afq_snappy_frame_decode_device: the bytes of the snappy frame stream `stream` (host bytes), decoded on the device.  Returns
+        (bytes, stats); with on_device (device pointer, n_bytes, stats) instead - decoded byte x lies at pointer + shift + x, and the
+        memory is the context's, valid until the next decode on it or close()."""
+        b = np.ascontiguousarray(np.frombuffer(stream, dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream)
+        o_b, o_n, st = C.POINTER(C.c_uint8)(), C.c_uint64(), _abi.AfqSnappyStats()
+        self._check(self.lib.afq_snappy_frame_decode_device(self._h, b.ctypes.data_as(C.c_void_p), b.nbytes, int(shift), 1 if on_device else 0, C.byref(o_b),
+                                                            C.byref(o_n), C.byref(st)))
+        stats = {k: int(getattr(st, k)) for k, _ in st._fields_}
+        if on_device:
+            return C.cast(o_b, C.c_void_p).value or 0, int(o_n.value), stats
+        try:
+            return C.string_at(o_b, int(o_n.value)), stats
+        finally:
+            self.lib.afq_free(o_b)
+
+    def collated_chunk_table(self, d_ptr: int, n_bytes: int, first_chunk: int = 0, rec_hdr_bytes: int = 0):
+        """afq_collated_chunk_table: the chunk table of the collated record stream of n_bytes at device pointer d_ptr, hopped on the
+        device from first_chunk.  Returns (off, nbytes, nrec, first_bc) as arrays, one entry a chunk."""
+        o_off, o_nb, o_nr, o_bc, o_n = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        self._check(self.lib.afq_collated_chunk_table(self._h, C.c_void_p(d_ptr), int(n_bytes), int(first_chunk), int(rec_hdr_bytes), C.byref(o_off), C.byref(o_nb),
+                                                      C.byref(o_nr), C.byref(o_bc), C.byref(o_n)))
+        try:
+            n = int(o_n.value)
+            return tuple(np.ctypeslib.as_array(a, shape=(n,)).copy() if n else np.zeros(0, t) for a, t in ((o_off, np.uint64), (o_nb, np.uint32), (o_nr, np.uint32), (o_bc, np.uint64)))
+        finally:
+            for a in (o_off, o_nb, o_nr, o_bc):
+                self.lib.afq_free(a)
 
     def kernel_times(self):
         buf = (AfqKernelTime * 64)()

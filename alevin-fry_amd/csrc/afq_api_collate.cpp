@@ -1,8 +1,10 @@
-// afq_api_collate.cpp — the snappy frame encoder's host side and the three collates with their limits.
+// afq_api_collate.cpp — the snappy frame encoder's and decoder's host side and the three collates with their limits.
 #include <functional>
 
 #include "afq_ctx.h"
 #include "afq_gpl_host.h"
+#include "afq_snappy_elem.h"
+#include "afq_snappy_plan.h"
 
 // Both collates' host step: val[i] = the index in `cells` of corrected[i]; ones_cell = the cell of the all-ones observed barcode
 // (it cannot be a key of the device's table, whose free slots are all ones), kSortNoRank without one.
@@ -130,6 +132,217 @@ int afq_snappy_frame_encode(afq_ctx* c, const uint8_t* bytes, size_t n_bytes, in
     }
     reset_kernel_times(c);
     return snappy_encode_device(c, "afq_snappy_frame_encode", d_in, n_bytes, out_bytes, out_n_bytes, stats);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the decoder
+void afq_snappy_decode_limits(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSnappyDecWindow; out[1] = kSnappyDecThreads; out[2] = kSnappyDecPieceChunks; out[3] = kSnappyDecLds;
+}
+
+static const char* snappy_code_words(uint32_t code) {
+    switch (code) {
+        case kSnappyLiteralPastBody: return "a literal runs past the block";
+        case kSnappyOffsetZero: return "a copy from offset 0";
+        case kSnappyOffsetPastStart: return "a copy from in front of the chunk";
+        case kSnappyOutputPastUlen: return "more bytes than declared";
+        case kSnappyTagCutOff: return "an element cut off";
+        case kSnappyOutputShort: return "fewer bytes than declared";
+        case kSnappyLengthDisagrees: return "the block's length is not the planned one";
+        default: return "";
+    }
+}
+
+// The compressed bytes of a piece - at most kSnappyDecPieceChunks data chunks within kSnappyDecPieceBytes of stream - cross
+// into one of two device buffers on c->stream while the launch of the piece in front reads the other on the second stream.
+// A piece is sized so that staged_h2d takes it through the context's pinned staging and its filler threads (it does so from
+// 64 MiB on; a full piece of compressible records is some 150 MB, one of stored chunks 128 MiB); what is shorter - a small
+// stream, a stream's last piece - goes up as one plain copy, as everywhere in the library.
+static constexpr uint64_t kSnappyDecPieceBytes = 128ull << 20;   // (a chunk holds less than 2^24)
+int afq_snappy_frame_decode_device(afq_ctx* c, const uint8_t* stream, size_t n, uint32_t shift, int out_on_device, uint8_t** out, uint64_t* out_n, afq_snappy_stats* stats) {
+    static const char* who = "afq_snappy_frame_decode_device";
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!stream && n) || !out || !out_n || shift > 3) return fail(c, AFQ_ERR_INVALID_ARG, !out || !out_n || (!stream && n) ? "null argument" : "shift is 0..3");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    std::vector<SnappyChunk> chunks;
+    uint64_t total = 0;
+    {
+        std::string err;
+        if (!snappy_frame_plan(stream, n, chunks, total, err)) return fail(c, AFQ_ERR_BAD_INPUT, err);
+    }
+    const uint64_t nc = chunks.size();
+    if (nc >= (1ull << 31)) return fail(c, AFQ_ERR_UNSUPPORTED, std::string(who) + ": 2^31 or more snappy frame chunks");
+    // the pieces: [first[k], first[k + 1]) of the chunks, their bytes [lo, hi) of the stream
+    struct Piece { uint64_t c0, c1, lo, hi; };
+    std::vector<Piece> pieces;
+    std::vector<SnappyDecChunk> plan(nc);
+    uint64_t piece_max = 0;
+    for (uint64_t i = 0; i < nc;) {
+        Piece P{i, i, chunks[i].in_off, chunks[i].in_off};
+        while (P.c1 < nc && P.c1 - P.c0 < kSnappyDecPieceChunks && (P.c1 == P.c0 || chunks[P.c1].in_off + chunks[P.c1].in_len - P.lo <= kSnappyDecPieceBytes)) {
+            const SnappyChunk& k = chunks[P.c1];
+            plan[P.c1] = SnappyDecChunk{(uint64_t)k.in_off - P.lo, k.out_off, (uint32_t)k.in_len, (uint32_t)k.ulen, k.crc, k.compressed ? 1u : 0u};
+            P.hi = k.in_off + k.in_len;
+            ++P.c1;
+        }
+        piece_max = std::max(piece_max, P.hi - P.lo);
+        pieces.push_back(P);
+        i = P.c1;
+    }
+    hc.lap("sz decode: plan");
+    const uint64_t n_buf = pieces.size() > 1 ? 2 : 1;
+    const uint64_t need_in = n_buf * piece_max, need_plan = nc * sizeof(SnappyDecChunk) + 64, need_out = (uint64_t)shift + total + 16;
+    auto& Z = c->snappy;
+    {   // what the decoder has to allocate beyond what it holds from an earlier call, against what the device has free
+        auto more = [](const DevBuf& b, uint64_t want) -> uint64_t { return want > b.cap ? want : 0; };
+        uint64_t alloc = more(Z.dec_plan, need_plan) + more(Z.dec_out, need_out) + more(Z.dec_stat, 5 * 8);
+        for (uint64_t b = 0; b < n_buf && nc; ++b) alloc += more(Z.dec_in[b], piece_max);
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        uint64_t room = fr;
+        if (const long hook = test_hook_long("SNAPPY_DEC_ROOM_BYTES", -1); hook >= 0) room = std::min<uint64_t>(room, (uint64_t)hook);
+        if (alloc > room)
+            return fail(c, AFQ_ERR_OOM, std::string(who) + ": the stream does not fit the device: " + std::to_string(need_in) + " bytes of compressed pieces + " +
+                        std::to_string(need_plan) + " of plan + " + std::to_string(need_out) + " of decoded bytes, " + std::to_string(alloc) + " of them still to allocate > " +
+                        std::to_string(room) + " bytes free of " + std::to_string(tot) + " of device memory");
+    }
+    const std::string detail = " (snappy decoder, " + std::to_string(n) + " bytes in " + std::to_string(nc) + " data chunks, " + std::to_string(total) + " decoded)";
+    HipLatch T;
+    T(Z.dec_out.ensure(need_out)); T(Z.dec_plan.ensure(need_plan)); T(Z.dec_stat.ensure(5 * 8));
+    for (uint64_t b = 0; b < n_buf && nc; ++b) T(Z.dec_in[b].ensure(piece_max));
+    if (!T.ok()) return T.fail(c, who, detail);
+    hipStream_t up = c->stream, ks = second_stream(c);
+    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_plan = nullptr;
+    for (int b = 0; b < 2; ++b) { T(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming)); T(hipEventCreateWithFlags(&ev_done[b], hipEventDisableTiming)); }
+    T(hipEventCreateWithFlags(&ev_plan, hipEventDisableTiming));
+    auto drop_events = [&] {
+        for (int b = 0; b < 2; ++b) { if (ev_up[b]) (void)hipEventDestroy(ev_up[b]); if (ev_done[b]) (void)hipEventDestroy(ev_done[b]); }
+        if (ev_plan) (void)hipEventDestroy(ev_plan);
+    };
+    uint64_t h_stat[5] = {~0ull, 0, 0, 0, 0};   // the status word, then chunks, stored chunks, literal bytes, copy elements
+    int rc = 0;
+    if (T.ok()) {
+        reset_kernel_times(c);
+        T(hipMemcpyAsync(Z.dec_stat.p, h_stat, sizeof h_stat, hipMemcpyHostToDevice, up));
+        if (nc) T(hipMemcpyAsync(Z.dec_plan.p, plan.data(), nc * sizeof(SnappyDecChunk), hipMemcpyHostToDevice, up));
+        if (shift) T(hipMemsetAsync(Z.dec_out.p, 0, 4, up));   // what stands around the decoded bytes is zero, as around a batch that submit_host landed
+        T(hipMemsetAsync(Z.dec_out.as<uint8_t>() + shift + total, 0, 16, up));
+        T(hipEventRecord(ev_plan, up));
+        T(hipStreamWaitEvent(ks, ev_plan, 0));
+        uint8_t* d_dst = Z.dec_out.as<uint8_t>() + shift;
+        for (size_t k = 0; k < pieces.size() && T.ok() && !rc; ++k) {
+            const Piece& P = pieces[k];
+            const int b = (int)(k & 1);
+            if (k >= 2) T(hipStreamWaitEvent(up, ev_done[b], 0));   // the launch that read this buffer last
+            const uint8_t* src = stream + P.lo;
+            const size_t len = (size_t)(P.hi - P.lo);
+            if (len) rc = staged_h2d(c, Z.dec_in[b].as<uint8_t>(), src, len, up, host_ptr_is_pinned(src) && host_ptr_is_pinned(src + len - 1));
+            if (rc) break;
+            T(hipEventRecord(ev_up[b], up));
+            T(hipStreamWaitEvent(ks, ev_up[b], 0));
+            {
+                ScopedTimer t(c, K_SNAPPY_DECODE, ks);
+                launch_snappy_decode(ks, Z.dec_in[b].as<uint8_t>(), Z.dec_plan.as<SnappyDecChunk>() + P.c0, (uint32_t)(P.c1 - P.c0), P.c0, d_dst, Z.dec_stat.as<uint64_t>(),
+                                     Z.dec_stat.as<uint64_t>() + 1);
+            }
+            T(hipGetLastError());
+            T(hipEventRecord(ev_done[b], ks));
+        }
+        T(hipMemcpyAsync(h_stat, Z.dec_stat.p, sizeof h_stat, hipMemcpyDeviceToHost, ks));
+        T(hipStreamSynchronize(up));
+        T(hipStreamSynchronize(ks));
+        harvest_timers(c);
+    }
+    drop_events();
+    hc.lap("sz decode: upload + kernels");
+    if (rc) return rc;
+    if (!T.ok()) return T.fail(c, who, detail);
+    if (h_stat[0] != ~0ull) {
+        const uint32_t code = (uint32_t)(h_stat[0] & 0xff);
+        const std::string at = "chunk " + std::to_string(h_stat[0] >> 8);
+        if (code == kSnappyCrcMismatch) return fail(c, AFQ_ERR_BAD_INPUT, "snappy CRC mismatch (" + at + ")");
+        return fail(c, AFQ_ERR_BAD_INPUT, "corrupt snappy block (" + at + ": " + snappy_code_words(code) + ")");
+    }
+    if (h_stat[1] != nc) return fail(c, AFQ_ERR_HIP, std::string(who) + ": " + std::to_string(h_stat[1]) + " of " + std::to_string(nc) + " chunks decoded" + detail);
+    if (out_on_device) *out = Z.dec_out.as<uint8_t>();
+    else {
+        uint8_t* ob = (uint8_t*)std::malloc(total ? total : 1);
+        if (!ob) return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(total) + " decoded bytes)");
+        if (total) {
+            T(hipMemcpyAsync(ob, Z.dec_out.as<uint8_t>() + shift, total, hipMemcpyDeviceToHost, ks));
+            T(hipStreamSynchronize(ks));
+        }
+        if (!T.ok()) { std::free(ob); return T.fail(c, who, detail); }
+        hc.lap("sz decode: bytes D2H");
+        *out = ob;
+    }
+    *out_n = total;
+    if (stats) {
+        afq_snappy_stats S{};
+        S.n_in = n; S.n_out = total; S.n_blocks = h_stat[1]; S.n_blocks_stored = h_stat[2]; S.n_literal_bytes = h_stat[3]; S.n_copies = h_stat[4];
+        *stats = S;
+    }
+    return 0;
+}
+
+// The chunk table of a collated record stream on the device.  The hop counts every chunk and writes those that the buffers hold:
+// a first guess of a chunk per 4 KiB, and a second launch with room for all where the stream has more.
+int afq_collated_chunk_table(afq_ctx* c, const uint8_t* d_bytes, uint64_t n, uint64_t first_chunk, uint32_t rec_hdr_bytes, uint64_t** out_off, uint32_t** out_nbytes,
+                             uint32_t** out_nrec, uint64_t** out_first_bc, uint64_t* out_n_chunks) {
+    static const char* who = "afq_collated_chunk_table";
+    if (!c) return AFQ_ERR_INVALID_ARG;
+    if ((!d_bytes && n) || !out_off || !out_nbytes || !out_nrec || !out_first_bc || !out_n_chunks) return fail(c, AFQ_ERR_INVALID_ARG, "null argument");
+    if (c->pending) return fail(c, AFQ_ERR_STATE, "a quant batch is pending on this context");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HostClock hc;
+    auto& Z = c->snappy;
+    hipStream_t s = c->stream;
+    uint64_t cap = std::max<uint64_t>(4096, n / 4096), h_stat[2] = {0, 0};
+    reset_kernel_times(c);
+    for (int pass = 0; pass < 2; ++pass) {
+        HipLatch T;
+        T(Z.ct_off.ensure(cap * 8)); T(Z.ct_nb.ensure(cap * 4)); T(Z.ct_nr.ensure(cap * 4)); T(Z.ct_bc.ensure(cap * 8)); T(Z.ct_stat.ensure(16));
+        if (T.ok()) {
+            ScopedTimer t(c, K_CHUNK_TABLE, s);
+            launch_collated_chunk_table(s, d_bytes, n, first_chunk, rec_hdr_bytes, cap, Z.ct_off.as<uint64_t>(), Z.ct_nb.as<uint32_t>(), Z.ct_nr.as<uint32_t>(),
+                                        Z.ct_bc.as<uint64_t>(), Z.ct_stat.as<uint64_t>());
+        }
+        T(hipGetLastError());
+        T(hipMemcpyAsync(h_stat, Z.ct_stat.p, 16, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        harvest_timers(c);
+        if (!T.ok()) return T.fail(c, who, " (" + std::to_string(n) + " bytes, room for " + std::to_string(cap) + " chunks)");
+        if (h_stat[1] != kChunkTableOk || h_stat[0] <= cap) break;
+        cap = h_stat[0];
+    }
+    hc.lap("chunk table: hop");
+    switch (h_stat[1]) {   // the host hop's sentences (afq_quantify)
+        case kChunkTableOk: break;
+        case kChunkTableTrailing: return fail(c, AFQ_ERR_BAD_INPUT, "trailing bytes after the last chunk");
+        case kChunkTableCorrupt: return fail(c, AFQ_ERR_BAD_INPUT, "corrupt chunk header");
+        case kChunkTableNoRecord: return fail(c, AFQ_ERR_BAD_INPUT, "chunk " + std::to_string(h_stat[0]) + " holds no record");
+        default: return fail(c, AFQ_ERR_HIP, std::string(who) + ": unknown status " + std::to_string(h_stat[1]));
+    }
+    const uint64_t nc = h_stat[0];
+    if (nc > cap) return fail(c, AFQ_ERR_HIP, std::string(who) + ": " + std::to_string(nc) + " chunks on the second hop, " + std::to_string(cap) + " on the first");
+    uint64_t* o_off = (uint64_t*)std::malloc(std::max<uint64_t>(1, nc) * 8);
+    uint32_t* o_nb = (uint32_t*)std::malloc(std::max<uint64_t>(1, nc) * 4);
+    uint32_t* o_nr = (uint32_t*)std::malloc(std::max<uint64_t>(1, nc) * 4);
+    uint64_t* o_bc = (uint64_t*)std::malloc(std::max<uint64_t>(1, nc) * 8);
+    auto drop = [&] { std::free(o_off); std::free(o_nb); std::free(o_nr); std::free(o_bc); };
+    if (!o_off || !o_nb || !o_nr || !o_bc) { drop(); return fail(c, AFQ_ERR_OOM, std::string(who) + ": host allocation failed (" + std::to_string(nc) + " chunks)"); }
+    if (nc) {
+        HipLatch T;
+        T(hipMemcpyAsync(o_off, Z.ct_off.p, nc * 8, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(o_nb, Z.ct_nb.p, nc * 4, hipMemcpyDeviceToHost, s));
+        T(hipMemcpyAsync(o_nr, Z.ct_nr.p, nc * 4, hipMemcpyDeviceToHost, s)); T(hipMemcpyAsync(o_bc, Z.ct_bc.p, nc * 8, hipMemcpyDeviceToHost, s));
+        T(hipStreamSynchronize(s));
+        if (!T.ok()) { drop(); return T.fail(c, who, " (" + std::to_string(nc) + " chunks)"); }
+    }
+    hc.lap("chunk table: D2H");
+    *out_off = o_off; *out_nbytes = o_nb; *out_nrec = o_nr; *out_first_bc = o_bc; *out_n_chunks = nc;
+    return 0;
 }
 
 void afq_set_collate_compress(afq_ctx* c, int on) {

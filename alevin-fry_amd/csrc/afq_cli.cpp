@@ -18,9 +18,9 @@ static void usage() {
                  "usage: afquant quant -i <input-dir> -m <tg-map> -o <output-dir> -r <resolution>\n"
                  "       [-t <threads>] [--small-thresh N] [--umi-edit-dist 0|1] [--large-graph-thresh N]\n"
                  "       [--quant-subset FILE] [--init-uniform] [--use-mtx] [-d] [-b N] [--device N | --devices 0,1,...]\n"
-                 "       [--summary-stat] [--boot-seed S] [--sa-model winner-take-all|prefer-ambig]\n"
+                 "       [--summary-stat] [--boot-seed S] [--sa-model winner-take-all|prefer-ambig] [--sz-on-device]\n"
                  "resolutions: trivial cr-like cr-like-em parsimony parsimony-em parsimony-gene parsimony-gene-em\n"
-                 "       afquant atac deduplicate -i <input-dir> [-t N] [-d fw|rc] [--device N]\n"
+                 "       afquant atac deduplicate -i <input-dir> [-t N] [-d fw|rc] [--device N] [--sz-on-device]\n"
                  "       afquant atac sort -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]\n"
                  "       afquant atac collate -i <input-dir> -r <rad-dir> [-t N] [-c] [-m N] [--device N]   (-m is without effect; -c is not supported)\n"
                  "       afquant generate-permit-list -i <input-dir> -d fw|rc|both|either -o <output-dir> (-k | -e N | -f N | -b FILE | -u FILE [-m MINREADS])\n"
@@ -267,6 +267,7 @@ int main(int argc, char** argv) {
                 else { std::fprintf(stderr, "invalid barcode orientation %s\n", v.c_str()); return 2; }
             }
             else if (a == "--device") ao.device = (uint32_t)std::atoi(need3(i));
+            else if (a == "--sz-on-device") ao.sz_on_device = 1;
             else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
         }
         if (!ao.input_dir) { usage(); return 2; }
@@ -334,6 +335,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--multi-sample-output") (void)need(i);
         else if (a == "--device") o.device = (uint32_t)std::atoi(need(i));
+        else if (a == "--sz-on-device") o.sz_on_device = 1;
         else if (a == "--devices") {   // comma list of HIP device ordinals: cells are range-partitioned over them
             for (const char* p = need(i); *p;) { char* e; const long v = std::strtol(p, &e, 10); if (e == p) { std::fprintf(stderr, "--devices wants a comma list of integers\n"); return 2; } devs.push_back((int32_t)v); p = *e == ',' ? e + 1 : e; if (*e && *e != ',') { std::fprintf(stderr, "--devices wants a comma list of integers\n"); return 2; } }
         }

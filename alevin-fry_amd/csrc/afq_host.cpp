@@ -43,6 +43,7 @@
 #include "../../include/afquant_host.h"
 #include "afq_gpl_host.h"
 #include "afq_hooks.h"
+#include "afq_snappy_plan.h"
 
 namespace {
 
@@ -113,13 +114,6 @@ uint32_t crc32c(const uint8_t* p, size_t n) {
 }
 uint32_t mask_crc(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }
 
-// uncompressed length of a raw snappy block (leading uvarint); returns false on a malformed prefix
-bool snappy_raw_length(const uint8_t* in, size_t n, uint64_t& ulen, size_t& hdr) {
-    ulen = 0; int shift = 0; size_t p = 0;
-    for (;;) { if (p >= n || shift > 35) return false; const uint8_t b = in[p++]; ulen |= (uint64_t)(b & 0x7F) << shift; if (!(b & 0x80)) break; shift += 7; }
-    hdr = p;
-    return true;
-}
 // raw snappy block -> exactly ulen bytes at dst
 bool snappy_raw_decompress_into(const uint8_t* in, size_t n, uint8_t* dst, uint64_t ulen) {
     uint64_t declared; size_t p;
@@ -148,38 +142,7 @@ bool snappy_raw_decompress_into(const uint8_t* in, size_t n, uint8_t* dst, uint6
     return w == ulen;
 }
 
-// Snappy frame format.  The data chunks of a frame are independent (<= 64 KiB of output each), so the stream is
-// planned in one cheap pass over the chunk headers and decoded by several threads.
-struct SnappyChunk { size_t in_off, in_len; uint64_t out_off, ulen; uint32_t crc; bool compressed; };
-bool snappy_frame_plan(const uint8_t* in, size_t n, std::vector<SnappyChunk>& chunks, uint64_t& total, std::string& err) {
-    size_t p = 0;
-    total = 0;
-    bool first = true;
-    while (p < n) {
-        if (p + 4 > n) { err = "truncated snappy frame header"; return false; }
-        if (first && in[p] != 0xff) { err = "snappy stream does not start with its stream identifier"; return false; }   // as snap::read::FrameDecoder
-        first = false;
-        const uint8_t type = in[p];
-        const size_t len = in[p + 1] | ((size_t)in[p + 2] << 8) | ((size_t)in[p + 3] << 16);
-        p += 4;
-        if (p + len > n) { err = "truncated snappy frame chunk"; return false; }
-        if (type == 0xff) { if (len != 6 || std::memcmp(in + p, "sNaPpY", 6) != 0) { err = "bad snappy stream identifier"; return false; } }
-        else if (type == 0x00 || type == 0x01) {
-            if (len < 4) { err = "snappy chunk too short"; return false; }
-            SnappyChunk c;
-            c.crc = in[p] | ((uint32_t)in[p + 1] << 8) | ((uint32_t)in[p + 2] << 16) | ((uint32_t)in[p + 3] << 24);
-            c.in_off = p + 4; c.in_len = len - 4; c.out_off = total; c.compressed = type == 0x00;
-            if (c.compressed) { size_t h; if (!snappy_raw_length(in + c.in_off, c.in_len, c.ulen, h)) { err = "corrupt snappy block"; return false; } }
-            else c.ulen = c.in_len;
-            if (c.ulen > 65536) { err = "snappy chunk larger than the frame format's 65536-byte limit"; return false; }
-            total += c.ulen;
-            chunks.push_back(c);
-        } else if (type >= 0x02 && type <= 0x7f) { err = "unskippable reserved snappy chunk"; return false; }
-        // 0x80..0xfe: skippable / padding
-        p += len;
-    }
-    return true;
-}
+// (the plan of a frame stream - SnappyChunk, snappy_frame_plan - is afq_snappy_plan.h's, shared with the device decoder)
 bool snappy_frame_run(const uint8_t* in, const std::vector<SnappyChunk>& chunks, uint8_t* out, unsigned nthreads, std::string& err) {
     nthreads = std::max(1u, std::min<unsigned>(nthreads, 64u));
     if (chunks.size() < 64) nthreads = 1;
@@ -214,8 +177,9 @@ bool snappy_frame_decode(const uint8_t* in, size_t n, std::vector<uint8_t>& out,
 // RAD prelude
 struct Cursor {
     const uint8_t* b; size_t n, p = 0; bool ok = true;
-    template <class T> T get() { T v{}; if (p + sizeof(T) > n) { ok = false; return v; } std::memcpy(&v, b + p, sizeof(T)); p += sizeof(T); return v; }
-    std::string str(size_t len) { if (p + len > n) { ok = false; return {}; } std::string s((const char*)b + p, len); p += len; return s; }
+    bool ran_out = false;   // what failed was a read past the n bytes (as opposed to bytes that are there and wrong)
+    template <class T> T get() { T v{}; if (p + sizeof(T) > n) { ok = false; ran_out = true; return v; } std::memcpy(&v, b + p, sizeof(T)); p += sizeof(T); return v; }
+    std::string str(size_t len) { if (p + len > n) { ok = false; ran_out = true; return {}; } std::string s((const char*)b + p, len); p += len; return s; }
 };
 struct TagDesc { std::string name; uint8_t type = 0, len_type = 0, elem_type = 0; };
 size_t int_type_bytes(uint8_t t) { return t == 1 ? 1 : t == 2 ? 2 : t == 3 ? 4 : t == 4 ? 8 : 0; }
@@ -226,6 +190,7 @@ struct RadPrelude {
     std::vector<TagDesc> file_tags, read_tags, aln_tags;
     std::unordered_map<std::string, uint64_t> file_tag_vals;
     size_t first_chunk = 0, num_chunks_at = 0;   // (num_chunks_at: where the u64 num_chunks stands)
+    bool ran_out = false;   // parse_prelude failed because the bytes ended (a longer prefix of the file may parse), not because of what they hold
     uint32_t bc_bytes = 0, umi_bytes = 0;
     std::vector<uint32_t> ref_lengths;   // the ref_lengths file tag (an array of u32), when there is one
     bool have_ref_lengths = false;
@@ -248,16 +213,18 @@ int parse_prelude(const uint8_t* bytes, size_t n, RadPrelude& P, bool want_names
     Cursor c{bytes, n};
     P.is_paired = c.get<uint8_t>() != 0;
     P.ref_count = c.get<uint64_t>();
-    if (!c.ok || P.ref_count > n) return hfail(AFQ_ERR_BAD_INPUT, "RAD header: bad ref_count");
+    if (!c.ok || P.ref_count > n) { P.ran_out = true; return hfail(AFQ_ERR_BAD_INPUT, "RAD header: bad ref_count"); }   // (a count above the bytes at hand: sz_prelude holds it against the file's length)
     for (uint64_t i = 0; i < P.ref_count && c.ok; ++i) {
         const uint16_t nl = c.get<uint16_t>();
-        if (want_names) P.ref_names.push_back(c.str(nl)); else { if (c.p + nl > c.n) c.ok = false; c.p += nl; }
+        if (want_names) P.ref_names.push_back(c.str(nl)); else { if (c.p + nl > c.n) { c.ok = false; c.ran_out = true; } c.p += nl; }
     }
     P.num_chunks_at = c.p;
     P.num_chunks = c.get<uint64_t>();
-    if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "RAD header truncated");
-    if (!read_tag_section(c, P.file_tags) || !read_tag_section(c, P.read_tags) || !read_tag_section(c, P.aln_tags))
+    if (!c.ok) { P.ran_out = c.ran_out; return hfail(AFQ_ERR_BAD_INPUT, "RAD header truncated"); }
+    if (!read_tag_section(c, P.file_tags) || !read_tag_section(c, P.read_tags) || !read_tag_section(c, P.aln_tags)) {
+        P.ran_out = c.ran_out;
         return hfail(AFQ_ERR_BAD_INPUT, "RAD tag sections truncated");
+    }
     for (auto& t : P.file_tags) {  // values of the file-level tags follow, in declaration order
         uint64_t v = 0;
         switch (t.type) {
@@ -271,7 +238,8 @@ int parse_prelude(const uint8_t* bytes, size_t n, RadPrelude& P, bool want_names
                 uint64_t len = 0;
                 switch (t.len_type) { case 1: len = c.get<uint8_t>(); break; case 2: len = c.get<uint16_t>(); break; case 3: len = c.get<uint32_t>(); break; case 4: len = c.get<uint64_t>(); break; default: c.ok = false; }
                 const size_t eb = t.elem_type == 5 ? 4 : t.elem_type == 6 ? 8 : t.elem_type == 0 ? 1 : int_type_bytes(t.elem_type);
-                if (!eb || c.p + len * eb > c.n) c.ok = false;
+                if (!eb) c.ok = false;
+                else if (c.p + len * eb > c.n) { c.ok = false; c.ran_out = true; }
                 else {
                     if (t.name == "ref_lengths" && t.elem_type == 3) { P.ref_lengths.resize((size_t)len); if (len) std::memcpy(P.ref_lengths.data(), c.b + c.p, (size_t)len * 4); P.have_ref_lengths = true; }
                     c.p += len * eb;
@@ -283,7 +251,7 @@ int parse_prelude(const uint8_t* bytes, size_t n, RadPrelude& P, bool want_names
         }
         P.file_tag_vals[t.name] = v;
     }
-    if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "RAD file-tag values truncated or of unknown type");
+    if (!c.ok) { P.ran_out = c.ran_out; return hfail(AFQ_ERR_BAD_INPUT, "RAD file-tag values truncated or of unknown type"); }
     P.first_chunk = c.p;
     for (auto& t : P.read_tags) {
         if (t.name == "b") P.bc_bytes = (uint32_t)int_type_bytes(t.type);
@@ -396,6 +364,53 @@ int open_fill_ctx(uint32_t device, uint32_t aln_extra, CtxPtr& ctx) {
     if (rc) return hfail(rc, afq_last_error(nullptr));
     ctx.reset(raw);
     if (aln_extra) { rc = afq_set_aln_extra_bytes(ctx.get(), aln_extra); if (rc) return hfail(rc, afq_last_error(ctx.get())); }
+    return 0;
+}
+
+// ---- map.collated.rad.sz decoded on the device (sz_on_device of afq_quantify and afq_atac_deduplicate): the decoded file never
+// exists on the host.  The prelude comes from as many leading frame chunks as it needs, decoded here; the rest is the device's.
+// The leading data chunks of the planned stream `z`, decoded by the host decoder until parse_prelude succeeds on them: one
+// chunk, then twice as many as the time before (a prelude with many reference names is longer than a chunk).  A prelude that
+// does not parse with the whole file decoded is the file's fault, and its sentence is returned.  More chunks are decoded only
+// where the parse ran out of bytes that the file (`total` decoded bytes) can still supply: a prelude that is wrong in the bytes
+// at hand, or asks for more than the whole file holds, is refused with what has been decoded.
+int sz_prelude(const uint8_t* z, const std::vector<SnappyChunk>& chunks, uint64_t total, std::vector<uint8_t>& head, RadPrelude& P, bool want_names) {
+    size_t have = 0, want = 1;
+    for (;;) {
+        want = std::min(want, chunks.size());
+        if (want > have) {
+            const std::vector<SnappyChunk> sub(chunks.begin() + have, chunks.begin() + want);
+            head.resize((size_t)(sub.back().out_off + sub.back().ulen));
+            std::string err;
+            if (!snappy_frame_run(z, sub, head.data(), 1, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+            have = want;
+        }
+        RadPrelude Q;
+        const int rc = parse_prelude(head.data(), head.size(), Q, want_names);
+        if (!rc) { P = std::move(Q); return 0; }
+        if (have == chunks.size() || !Q.ran_out || Q.ref_count > total) return rc;
+        want = 2 * have;
+    }
+}
+// The decoded stream on the device and its chunk table.  The bytes are the context's: valid while it lives and decodes nothing else.
+struct SzResident {
+    const uint8_t* d_rad = nullptr;   // device memory: byte x of the decoded stream lies at d_rad[x]; the first chunk is dword-aligned
+    uint64_t n = 0;
+    std::vector<uint64_t> chunk_off, chunk_nb, first_bc;   // first_bc: the 8 bytes at chunk + 12, the first record's barcode field
+    std::vector<uint32_t> chunk_nr;
+};
+int sz_decode_resident(afq_ctx* ctx, const uint8_t* z, size_t zn, uint64_t first_chunk, uint32_t rec_hdr, SzResident& R, PhaseClock& pc) {
+    const uint32_t shift = (uint32_t)((4 - first_chunk % 4) % 4);   // the chunks land as submit_host lands them
+    uint8_t* d = nullptr;
+    if (int rc = afq_snappy_frame_decode_device(ctx, z, zn, shift, 1, &d, &R.n, nullptr))
+        return hfail(rc, std::string("map.collated.rad.sz: ") + afq_last_error(ctx));
+    R.d_rad = d + shift;
+    pc.lap("sz: upload + decode");
+    uint64_t *off = nullptr, *bc = nullptr, nc = 0; uint32_t *nb = nullptr, *nr = nullptr;
+    if (int rc = afq_collated_chunk_table(ctx, R.d_rad, R.n, first_chunk, rec_hdr, &off, &nb, &nr, &bc, &nc)) return hfail(rc, afq_last_error(ctx));
+    R.chunk_off.assign(off, off + nc); R.chunk_nb.assign(nb, nb + nc); R.chunk_nr.assign(nr, nr + nc); R.first_bc.assign(bc, bc + nc);
+    afq_free(off); afq_free(nb); afq_free(nr); afq_free(bc);
+    pc.lap("sz: chunk table");
     return 0;
 }
 
@@ -677,7 +692,7 @@ struct DevStat { double busy_s = 0; uint64_t bytes = 0, cells = 0; uint32_t batc
 // reference's workers do with chunks (quant.rs:1553-1575, 1678-1765); the rows of batch b go to parts[b], so the gather in
 // batch order is the gather in cell order whatever device took which batch.
 static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, uint32_t aln_extra, const std::vector<uint32_t>& t2g, int device, bool bind_numa,
-                             const uint8_t* rad, int rad_fd, const std::vector<uint64_t>& chunk_off, const std::vector<uint64_t>& chunk_nb,
+                             const uint8_t* rad, int rad_fd, const uint8_t* d_rad, const std::vector<uint64_t>& chunk_off, const std::vector<uint64_t>& chunk_nb,
                              const std::vector<uint32_t>& chunk_nr, const std::vector<std::pair<size_t, size_t>>& batches, std::atomic<size_t>& next,
                              std::atomic<int>& stop, bool want_eq, bool res_is_em, std::vector<DevOut>& parts, DevStat& stat) {
     auto now = []() { return std::chrono::steady_clock::now(); };
@@ -711,8 +726,12 @@ static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, u
         std::vector<uint64_t> rel(c1 - c0);
         for (size_t k = c0; k < c1; ++k) rel[k - c0] = chunk_off[k] - span0;
         const uint64_t span1 = chunk_off[c1 - 1] + chunk_nb[c1 - 1];   // with --quant-subset the span also covers chunks that were filtered out
+        // the decoded file lies on the device (sz_on_device): the span as it lies there, from the dword boundary below it
+        const uint32_t mis = d_rad ? (uint32_t)(reinterpret_cast<uintptr_t>(d_rad + span0) & 3u) : 0u;
+        if (mis) for (auto& r : rel) r += mis;
         auto ta = now();
-        if (rad_fd >= 0) {   // an uncompressed file: the library pulls the bytes itself (pread into its staging)
+        if (d_rad) rc = afq_submit_device(ctx.get(), d_rad + span0 - mis, (size_t)(span1 - span0) + mis, rel.data(), (uint32_t)(c1 - c0), c0);
+        else if (rad_fd >= 0) {   // an uncompressed file: the library pulls the bytes itself (pread into its staging)
             FileSource fs{rad_fd, span0};
             std::vector<uint32_t> hdr(2 * (c1 - c0));
             for (size_t k = c0; k < c1; ++k) { hdr[2 * (k - c0)] = (uint32_t)chunk_nb[k]; hdr[2 * (k - c0) + 1] = chunk_nr[k]; }
@@ -739,7 +758,8 @@ static void run_device_worker(const afq_config& cfg, const afq_config* cfg_eq, u
             afq_result res_eq{};
             afq_eqclasses ec{};
             if (ctx_eq) {
-                rc = afq_submit(ctx_eq.get(), rad + span0, (size_t)(span1 - span0), rel.data(), (uint32_t)(c1 - c0), c0);
+                if (d_rad) rc = afq_submit_device(ctx_eq.get(), d_rad + span0 - mis, (size_t)(span1 - span0) + mis, rel.data(), (uint32_t)(c1 - c0), c0);
+                else rc = afq_submit(ctx_eq.get(), rad + span0, (size_t)(span1 - span0), rel.data(), (uint32_t)(c1 - c0), c0);
                 if (!rc) rc = afq_collect(ctx_eq.get(), &res_eq);
                 if (rc) { out.rc = rc; out.err = afq_last_error(ctx_eq.get()); stat.rc = rc; stat.err = out.err; stop = 1; afq_result_release(&res); return; }
             }
@@ -792,18 +812,25 @@ int afq_atac_deduplicate(const afq_atac_dedup_opts* o) {
     std::unique_ptr<uint8_t[]> rad_buf;
     uint64_t rad_buf_n = 0;
     const unsigned nthreads = o->num_threads ? o->num_threads : std::max(1u, std::thread::hardware_concurrency());
+    const bool resident = compressed && o->sz_on_device;
+    if (o->sz_on_device && !compressed) std::fprintf(stderr, "--sz-on-device: map.collated.rad is not compressed; the option is ignored\n");
+    std::vector<SnappyChunk> sz_chunks;
+    std::vector<uint8_t> sz_head;
     if (compressed) {
         std::string err;
-        std::vector<SnappyChunk> chunks;
-        if (!snappy_frame_plan(mf.p, mf.n, chunks, rad_buf_n, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
-        rad_buf.reset(new (std::nothrow) uint8_t[rad_buf_n ? rad_buf_n : 1]);
-        if (!rad_buf) return hfail(AFQ_ERR_OOM, "map.collated.rad.sz: not enough host memory for the decompressed file");
-        if (!snappy_frame_run(mf.p, chunks, rad_buf.get(), nthreads, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        if (!snappy_frame_plan(mf.p, mf.n, sz_chunks, rad_buf_n, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        if (!resident) {
+            rad_buf.reset(new (std::nothrow) uint8_t[rad_buf_n ? rad_buf_n : 1]);
+            if (!rad_buf) return hfail(AFQ_ERR_OOM, "map.collated.rad.sz: not enough host memory for the decompressed file");
+            if (!snappy_frame_run(mf.p, sz_chunks, rad_buf.get(), nthreads, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        }
     }
-    const uint8_t* rad = compressed ? rad_buf.get() : mf.p;
+    const uint8_t* rad = compressed ? rad_buf.get() : mf.p;   // (resident: null - the decoded bytes lie on the device alone)
     const size_t rad_n = compressed ? (size_t)rad_buf_n : mf.n;
     RadPrelude P;
-    int rc = parse_prelude(rad, rad_n, P, true);
+    int rc = 0;
+    if (resident) { rc = sz_prelude(mf.p, sz_chunks, rad_buf_n, sz_head, P, true); pc.lap("sz: prelude chunks"); }
+    else rc = parse_prelude(rad, rad_n, P, true);
     if (rc) return rc;
     // AtacSeqReadRecord: read tag b; alignment tags ref:u32, type:u8, start_pos:u32, frag_len:u16 (tests/atac_integration.rs:110-121)
     if (P.read_tags.size() != 1 || P.read_tags[0].name != "b" || !P.bc_bytes) return hfail(AFQ_ERR_UNSUPPORTED, "scATAC RAD: the read-level tags must be exactly one integer 'b'");
@@ -814,6 +841,13 @@ int afq_atac_deduplicate(const afq_atac_dedup_opts* o) {
     if (!P.file_tag_vals.count("cblen")) return hfail(AFQ_ERR_BAD_INPUT, "tag map must contain cblen");
     const uint32_t cblen = (uint32_t)P.file_tag_vals["cblen"];
     std::vector<uint64_t> chunk_off;
+    CtxPtr ctx;
+    SzResident Z;
+    if (resident) {   // decode and hop on the device; this hop asks nothing of a chunk's records
+        if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
+        if (int rc2 = sz_decode_resident(ctx.get(), mf.p, mf.n, P.first_chunk, 0, Z, pc)) return rc2;
+        chunk_off.swap(Z.chunk_off);
+    } else
     for (size_t p = P.first_chunk; p < rad_n;) {
         if (p + 8 > rad_n) return hfail(AFQ_ERR_BAD_INPUT, "trailing bytes after the last chunk");
         uint32_t nb; std::memcpy(&nb, rad + p, 4);
@@ -821,14 +855,13 @@ int afq_atac_deduplicate(const afq_atac_dedup_opts* o) {
         chunk_off.push_back(p); p += nb;
     }
     pc.lap("map + prelude + chunk table");
-    CtxPtr ctx;
-    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
+    if (!ctx) { if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2; }
     uint64_t *optr = nullptr, *obc = nullptr; uint32_t *oref = nullptr, *ostart = nullptr; uint16_t *oflen = nullptr, *ocnt = nullptr;
     afq_atac_stats st{};
     const uint64_t span0 = chunk_off.empty() ? 0 : chunk_off[0];
     std::vector<uint64_t> rel(chunk_off.size());
     for (size_t i = 0; i < chunk_off.size(); ++i) rel[i] = chunk_off[i] - span0;
-    rc = afq_atac_dedup_rad(ctx.get(), rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, 0, &optr, &obc, &oref, &ostart, &oflen, &ocnt, &st);
+    rc = afq_atac_dedup_rad(ctx.get(), resident ? Z.d_rad + span0 : rad + span0, rad_n - span0, rel.data(), (uint32_t)chunk_off.size(), P.bc_bytes, resident ? 1 : 0, &optr, &obc, &oref, &ostart, &oflen, &ocnt, &st);
     if (rc) return hfail(rc, afq_last_error(ctx.get()));
     struct Freer { uint64_t* a; uint64_t* b; uint32_t* c2; uint32_t* d; uint16_t* e; uint16_t* f; ~Freer() { afq_free(a); afq_free(b); afq_free(c2); afq_free(d); afq_free(e); afq_free(f); } } fr{optr, obc, oref, ostart, oflen, ocnt};
     pc.lap("device: parse + dedup");
@@ -2168,24 +2201,34 @@ int afq_quantify(const afq_quant_opts* o) {
     { size_t k = cjs.find("\"compressed_output\""); if (k != std::string::npos) { size_t v = cjs.find_first_not_of(" \t\r\n:", k + 19); compressed = v != std::string::npos && cjs.compare(v, 4, "true") == 0; } }
     PhaseClock pc;
     // the HIP runtime takes a few hundred ms to come up: let it do so while the prelude and the tg-map are parsed
-    std::thread warm([dev = (int)(o->devices && o->n_devices ? o->devices[0] : (int)o->device)]() { afq_device_warmup(dev); });
+    const int first_device = o->devices && o->n_devices ? (int)o->devices[0] : (int)o->device;   // the one device of a one-device run: the workers', the warm-up's, the resident decode's
+    std::thread warm([dev = first_device]() { afq_device_warmup(dev); });
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } warm_join{warm};
     MappedFile mf;
     if (!mf.open(in + (compressed ? "/map.collated.rad.sz" : "/map.collated.rad"))) return hfail(AFQ_ERR_BAD_INPUT, "could not read the collated RAD file");
     std::unique_ptr<uint8_t[]> rad_buf;   // (not a vector: no point zero-filling gigabytes that are about to be overwritten)
     uint64_t rad_buf_n = 0;
+    // sz_on_device: the decoded file exists on the device alone - the prelude from the leading frame chunks here, the chunk table
+    // from the device's hop further down, the workers' spans from where the decoder left them
+    const bool resident = compressed && o->sz_on_device;
+    if (o->sz_on_device && o->devices && o->n_devices > 1) return hfail(AFQ_ERR_UNSUPPORTED, "--sz-on-device takes one device");
+    if (o->sz_on_device && !compressed) std::fprintf(stderr, "--sz-on-device: map.collated.rad is not compressed; the option is ignored\n");
+    std::vector<SnappyChunk> sz_chunks;
+    std::vector<uint8_t> sz_head;
     if (compressed) {
         std::string err;
-        std::vector<SnappyChunk> chunks;
-        if (!snappy_frame_plan(mf.p, mf.n, chunks, rad_buf_n, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
-        rad_buf.reset(new (std::nothrow) uint8_t[rad_buf_n ? rad_buf_n : 1]);
-        if (!rad_buf) return hfail(AFQ_ERR_OOM, "map.collated.rad.sz: not enough host memory for the decompressed file");
-        if (!snappy_frame_run(mf.p, chunks, rad_buf.get(), o->num_threads ? o->num_threads : std::max(1u, std::thread::hardware_concurrency()), err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        if (!snappy_frame_plan(mf.p, mf.n, sz_chunks, rad_buf_n, err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        if (!resident) {
+            rad_buf.reset(new (std::nothrow) uint8_t[rad_buf_n ? rad_buf_n : 1]);
+            if (!rad_buf) return hfail(AFQ_ERR_OOM, "map.collated.rad.sz: not enough host memory for the decompressed file");
+            if (!snappy_frame_run(mf.p, sz_chunks, rad_buf.get(), o->num_threads ? o->num_threads : std::max(1u, std::thread::hardware_concurrency()), err)) return hfail(AFQ_ERR_BAD_INPUT, "map.collated.rad.sz: " + err);
+        }
     }
     struct { const uint8_t* p; size_t n; const uint8_t* data() const { return p; } size_t size() const { return n; } } rad{compressed ? rad_buf.get() : mf.p, compressed ? (size_t)rad_buf_n : mf.n};
-    pc.lap(compressed ? "map + snappy decode" : "map the RAD file");
     RadPrelude P;
-    int rc = parse_prelude(rad.data(), rad.size(), P, true);
+    int rc = 0;
+    if (resident) { rc = sz_prelude(mf.p, sz_chunks, rad_buf_n, sz_head, P, true); pc.lap("sz: prelude chunks"); }
+    else { pc.lap(compressed ? "map + snappy decode" : "map the RAD file"); rc = parse_prelude(rad.data(), rad.size(), P, true); }
     if (rc) return rc;
     // Record layout.  Single-barcode scRNA: read tags (b, u).  Multi-barcode (10x Flex; KnownRecordType::RnaShortMultiBC,
     // src/utils.rs:313-340): file tag num_barcodes = 2, read tags (b0, b1, u) - after collation b0 is the integer sample
@@ -2248,6 +2291,14 @@ int afq_quantify(const afq_quant_opts* o) {
     const uint32_t rec_hdr = 4 + P.bc_bytes + P.umi_bytes;
     std::vector<uint64_t> chunk_off, chunk_nb;
     std::vector<uint32_t> chunk_nr;
+    CtxPtr sz_ctx;    // resident: the context that decoded the file and holds its bytes until the workers are done
+    SzResident Z;
+    if (resident) {
+        if (warm.joinable()) warm.join();
+        if (int rc2 = open_fill_ctx((uint32_t)first_device, 0, sz_ctx)) return rc2;   // (the workers' device: `--devices 1` names it, not `--device`)
+        if (int rc2 = sz_decode_resident(sz_ctx.get(), mf.p, mf.n, P.first_chunk, rec_hdr, Z, pc)) return rc2;
+        chunk_off.swap(Z.chunk_off); chunk_nb.swap(Z.chunk_nb); chunk_nr.swap(Z.chunk_nr);
+    } else
     for (size_t p = P.first_chunk; p < rad.size();) {
         if (p + 8 > rad.size()) return hfail(AFQ_ERR_BAD_INPUT, "trailing bytes after the last chunk");
         uint32_t nb, nr; std::memcpy(&nb, rad.data() + p, 4); std::memcpy(&nr, rad.data() + p + 4, 4);
@@ -2276,7 +2327,8 @@ int afq_quantify(const afq_quant_opts* o) {
         subset_size = keep.size();
         std::vector<uint64_t> kept, kept_nb;
         std::vector<uint32_t> kept_nr;
-        for (size_t i = 0; i < chunk_off.size(); ++i) { if (keep.count(file_cell_key_of(rad.data() + chunk_off[i] + 8 + 4))) { kept.push_back(chunk_off[i]); kept_nb.push_back(chunk_nb[i]); kept_nr.push_back(chunk_nr[i]); } }
+        // (resident: the first record's barcode field as the device's hop read it)
+        for (size_t i = 0; i < chunk_off.size(); ++i) { if (keep.count(file_cell_key_of(resident ? reinterpret_cast<const uint8_t*>(&Z.first_bc[i]) : rad.data() + chunk_off[i] + 8 + 4))) { kept.push_back(chunk_off[i]); kept_nb.push_back(chunk_nb[i]); kept_nr.push_back(chunk_nr[i]); } }
         chunk_off.swap(kept); chunk_nb.swap(kept_nb); chunk_nr.swap(kept_nr);
     }
     // transcript-to-gene map (src/utils.rs:487-662)
@@ -2366,6 +2418,7 @@ int afq_quantify(const afq_quant_opts* o) {
     pc.lap("(wait for the HIP runtime)");
     std::vector<int> devices;
     if (o->devices && o->n_devices) devices.assign(o->devices, o->devices + o->n_devices); else devices.push_back((int)o->device);
+    if (resident && devices[0] != first_device) return hfail(AFQ_ERR_STATE, "--sz-on-device: the decoded file lies on device " + std::to_string(first_device) + ", the workers run on device " + std::to_string(devices[0]));
     if (devices.size() > chunk_off.size() && !chunk_off.empty()) devices.resize(chunk_off.size());
     // The queue: contiguous batches of cells in file order (largest cells first, collate.rs:272-274).  One device: as large
     // as memory allows (batch_bytes).  Several: about eight batches per device, so that the devices finish together whatever
@@ -2391,7 +2444,7 @@ int afq_quantify(const afq_quant_opts* o) {
         std::atomic<size_t> next{0};
         std::atomic<int> stop{0};
         auto work = [&](size_t d) {
-            run_device_worker(cfg, cfg_eq.dump_eq ? &cfg_eq : nullptr, aln_extra, t2g, devices[d], devices.size() > 1, rad.data(), compressed ? -1 : mf.fd, chunk_off, chunk_nb, chunk_nr,
+            run_device_worker(cfg, cfg_eq.dump_eq ? &cfg_eq : nullptr, aln_extra, t2g, devices[d], devices.size() > 1, rad.data(), compressed ? -1 : mf.fd, resident ? Z.d_rad : nullptr, chunk_off, chunk_nb, chunk_nr,
                               batches, next, stop, o->dump_eq != 0, res_is_em, parts, dstat[d]);
         };
         if (devices.size() == 1) work(0);

@@ -446,6 +446,25 @@ inline uint64_t snappy_stream_bound(uint64_t n) { return 10 + n + 8 * snappy_blo
 void launch_snappy_blocks(hipStream_t s, const uint8_t* in, uint64_t n, uint64_t n_blocks, uint8_t* slots, SnappyMeta* meta);
 void launch_snappy_layout(hipStream_t s, const SnappyMeta* meta, uint64_t n_blocks, uint64_t* off);   // off[i]: where chunk i's header stands, off[n_blocks]: the stream's length
 void launch_snappy_pack(hipStream_t s, const uint8_t* in, uint64_t n_blocks, const uint8_t* slots, const SnappyMeta* meta, const uint64_t* off, uint8_t* out);
+
+// the snappy frame decoder (afq_snappy.hip): a frame stream on the device and the host's plan of it -> its bytes on the device
+constexpr uint32_t kSnappyDecThreads = 64;         // a workgroup is one wave and takes one data chunk
+constexpr uint32_t kSnappyDecWindow = 8192;        // bytes of a chunk's body staged in LDS per trip to memory
+constexpr uint32_t kSnappyDecPieceChunks = 4096;   // data chunks of one launch at the most (a piece of the stream; afq_snappy_frame_decode_device)
+constexpr uint32_t kSnappyDecLds = (kSnappyBlock + 16) + (kSnappyDecWindow + 32) + 1024;   // staged output, window, CRC table: two workgroups share a CU's 160 KiB
+struct SnappyDecChunk { uint64_t in_off, out_off; uint32_t in_len, ulen, crc, compressed; };   // in_off from the launch's `in`, out_off from its `dst`
+// status: min over the refused chunks of (first_index + chunk) << 8 | SnappyDecodeCode (afq_snappy_elem.h); stats[4]: chunks,
+// stored chunks, literal bytes, copy elements - of the chunks that decoded
+void launch_snappy_decode(hipStream_t s, const uint8_t* in, const SnappyDecChunk* plan, uint32_t n_chunks, uint64_t first_index, uint8_t* dst, uint64_t* status, uint64_t* stats);
+
+// the chunk table of a collated record stream on the device (afq_snappy.hip, k_collated_chunk_table): one wave hops the headers
+constexpr uint32_t kChunkTableTile = 16384, kChunkTableShort = 1024, kChunkTableHalo = 24;   // bytes of the stream staged per trip; a header at the tile's last byte and the 8 bytes at + 12 lie in the halo
+constexpr uint32_t kChunkTableWords = (3 + kChunkTableTile + kChunkTableHalo + 3) / 4 + 1;
+enum ChunkTableCode : uint32_t { kChunkTableOk = 0, kChunkTableTrailing, kChunkTableCorrupt, kChunkTableNoRecord };
+// stat[0]: chunks hopped (entries are written for the first `cap`), stat[1]: ChunkTableCode - on a refusal stat[0] is the chunk it is about.
+// rec_hdr: bytes of a record's head (a chunk must hold one record at least), 0: no such check
+void launch_collated_chunk_table(hipStream_t s, const uint8_t* bytes, uint64_t n, uint64_t first_chunk, uint32_t rec_hdr, uint64_t cap, uint64_t* off, uint32_t* nbytes,
+                                 uint32_t* nrec, uint64_t* first_bc, uint64_t* stat);
 void warm_code_object();
 void launch_resolve(hipStream_t s, const ResolveArgs& a);
 void launch_resolve_big(hipStream_t s, const ResolveArgs& a);

@@ -20,11 +20,14 @@
 //   - k_snappy_layout: one workgroup scans 8 + body bytes over the chunks, 10 in front: where every chunk header stands.
 //   - k_snappy_pack: a workgroup per chunk writes the header and copies the body (slot or input) to its place - any residue of
 //     the destination, 16-byte stores between a bytewise head and tail.
+// And the way back, k_snappy_decode (below, with its own account): a planned frame stream on the device -> its bytes.
 #include <hip/hip_runtime.h>
 
 #include "afq_common.h"
 #include "afq_kernels.h"
 #include "afq_prims.h"
+#include "afq_rad_walk.h"
+#include "afq_snappy_elem.h"
 
 namespace afq {
 
@@ -65,6 +68,34 @@ __device__ __forceinline__ uint32_t ld4(const uint8_t* p) {
     uint32_t w;
     __builtin_memcpy(&w, p, 4);
     return w;
+}
+
+// the bytewise CRC table, 256 words, filled by one wave
+__device__ __forceinline__ void crc_table_fill(uint32_t* s_tab, uint32_t lane) {
+    for (uint32_t i = lane; i < 256; i += 64) {
+        uint32_t c = i;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
+        s_tab[i] = c;
+    }
+}
+// The masked CRC-32C of src[0, n) by one wave: lane l takes the slice [l sl, (l + 1) sl) (sl a multiple of 4, 64 sl >= n), the
+// slices combine by the linearity of the register.  full: n = kSnappyBlock and sl = kSliceFull, the shifts are constants.
+__device__ __forceinline__ uint32_t wave_masked_crc(const uint8_t* src, uint32_t n, uint32_t sl, bool full, const uint32_t* s_tab, uint32_t lane) {
+    const uint32_t b = min(n, lane * sl), e = min(n, b + sl);
+    uint32_t st = lane == 0 ? 0xFFFFFFFFu : 0u;
+    uint32_t p = b;
+    for (; p + 4 <= e; p += 4) {
+        st ^= ld4(src + p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st = s_tab[st & 255u] ^ (st >> 8);
+    }
+    for (; p < e; ++p) st = s_tab[(st ^ src[p]) & 255u] ^ (st >> 8);
+    st = gf_mul(st, full ? c_shift.v[63 - lane] : gf_pow_x8(n - e));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) st ^= __shfl_xor(st, d);
+    const uint32_t crc = ~st;
+    return ((crc >> 15) | (crc << 17)) + 0xa282ead8u;
 }
 
 __device__ __forceinline__ uint32_t literal_size(uint32_t len) { return len == 0 ? 0 : len + (len <= 60 ? 1 : len <= 256 ? 2 : 3); }
@@ -124,32 +155,10 @@ __global__ __launch_bounds__(64) void k_snappy_blocks(const uint8_t* __restrict_
     const uint64_t left = n_total - at;
     const uint32_t n = left < kSnappyBlock ? (uint32_t)left : kSnappyBlock;   // 1..kSnappyBlock
     // ---- CRC-32C of the chunk
-    for (uint32_t i = lane; i < 256; i += 64) {
-        uint32_t c = i;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
-        s_tab[i] = c;
-    }
+    crc_table_fill(s_tab, lane);
     __syncthreads();
-    uint32_t masked_crc;
-    {
-        const bool full = n == kSnappyBlock;
-        const uint32_t sl = full ? kSliceFull : (((n + 63) / 64 + 3) & ~3u);
-        const uint32_t b = min(n, lane * sl), e = min(n, b + sl);
-        uint32_t st = lane == 0 ? 0xFFFFFFFFu : 0u;
-        uint32_t p = b;
-        for (; p + 4 <= e; p += 4) {
-            st ^= ld4(src + p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) st = s_tab[st & 255u] ^ (st >> 8);
-        }
-        for (; p < e; ++p) st = s_tab[(st ^ src[p]) & 255u] ^ (st >> 8);
-        st = gf_mul(st, full ? c_shift.v[63 - lane] : gf_pow_x8(n - e));
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) st ^= __shfl_xor(st, d);
-        const uint32_t crc = ~st;
-        masked_crc = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;
-    }
+    const bool full = n == kSnappyBlock;
+    const uint32_t masked_crc = wave_masked_crc(src, n, full ? kSliceFull : (((n + 63) / 64 + 3) & ~3u), full, s_tab, lane);
     // ---- the raw block
     __syncthreads();
     for (uint32_t i = lane; i < kSnappyHashSlots; i += 64) s_tab[i] = 0;   // 0: no position; else position + 1
@@ -261,6 +270,196 @@ __global__ __launch_bounds__(kPackNT) void k_snappy_pack(const uint8_t* __restri
     if (t < len - done) d[done + t] = s[done + t];
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the decoder
+// k_snappy_decode: ONE WAVE per data chunk of a planned frame stream (the plan is the host's walk over the chunk headers,
+// afq_snappy_plan.h).  The chunk's output is built in LDS and its body is read through an LDS window, so no element waits for
+// global memory: a copy element reads LDS, never bytes this kernel has written to memory.  The element loop is the wave's: the
+// 8 bytes at the element go from the window into scalar registers in one trip, the parser runs on them (afq_snappy_elem.h -
+// nothing moves that the parser has not validated against in_len and ulen), the lanes move the element's bytes while the next
+// element's 8 bytes are on their way.  Then the masked CRC-32C of the staged bytes by slices (the encoder's code), and the write-out to
+// any residue of the destination, 16-byte stores between a bytewise head and tail: the output is staged at the destination's
+// own residue, so both sides of a 16-byte move are aligned.  A chunk that is refused writes nothing and enters
+// `index << 8 | code` into the status word by atomicMin: the lowest bad chunk is named whatever the schedule.
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// body[at, at + n) into the window, at the residue of its address: 16-byte loads between a bytewise head and tail, none of them
+// outside the n bytes.  Returns where body[at] stands.
+__device__ __forceinline__ const uint8_t* window_fill(uint4* s_in, const uint8_t* g, uint32_t n, uint32_t lane) {
+    __syncthreads();   // the reads of what the window held
+    uint8_t* sw = (uint8_t*)s_in + ((uintptr_t)g & 15);
+    const uint32_t head = min(n, (uint32_t)((16 - ((uintptr_t)g & 15)) & 15));
+    if (lane < head) sw[lane] = g[lane];
+    const uint32_t nvec = (n - head) / 16;
+    for (uint32_t k = lane; k < nvec; k += kSnappyDecThreads) *(uint4*)(sw + head + 16 * k) = *(const uint4*)(g + head + 16ull * k);
+    const uint32_t done = head + 16 * nvec;
+    if (lane < n - done) sw[done + lane] = g[done + lane];
+    __syncthreads();
+    return sw;
+}
+
+__global__ __launch_bounds__(kSnappyDecThreads) void k_snappy_decode(const uint8_t* __restrict__ in, const SnappyDecChunk* __restrict__ plan, uint64_t first_index,
+                                                                     uint8_t* __restrict__ dst, unsigned long long* __restrict__ status, unsigned long long* __restrict__ stats) {
+    __shared__ uint4 s_out[(kSnappyBlock + 16) / 16];
+    __shared__ uint4 s_in[(kSnappyDecWindow + 32) / 16];   // (+ the residue of the body's address, + the words load8 touches behind the window)
+    __shared__ uint32_t s_tab[256];
+    static_assert(sizeof(s_out) + sizeof(s_in) + sizeof(s_tab) == kSnappyDecLds, "afq_snappy_decode_limits reports the workgroup's LDS");
+    const uint32_t lane = threadIdx.x;
+    const SnappyDecChunk c = plan[blockIdx.x];
+    const uint8_t* body = in + c.in_off;
+    uint8_t* d = dst + c.out_off;
+    const uint32_t in_len = uni(c.in_len), ulen = uni(c.ulen);
+    uint8_t* so = (uint8_t*)s_out + ((uintptr_t)d & 15);   // so[i] is output byte i
+    crc_table_fill(s_tab, lane);
+    uint32_t code = kSnappyOk, n_lit = 0, n_cp = 0;
+    // the window holds body[wbase, wend) at sw
+    uint32_t wbase = 0, wend = 0;
+    const uint8_t* sw = (const uint8_t*)s_in;
+    auto stage = [&](uint32_t at) {   // at < in_len
+        const uint32_t n = min(kSnappyDecWindow, in_len - at);
+        sw = window_fill(s_in, body + at, n, lane);
+        wbase = at; wend = at + n;
+    };
+    // 8 bytes of the body from p on in one trip (aligned words of the window; what lies behind wend is not looked at)
+    auto load8 = [&](uint32_t p) -> uint64_t {
+        const uint32_t o = (uint32_t)(sw - (const uint8_t*)s_in) + (p - wbase);
+        const uint32_t* t = (const uint32_t*)s_in;
+        const uint32_t x = o >> 2, sh = o & 3u;
+        const uint32_t w0 = t[x], w1 = t[x + 1], w2 = t[x + 2];
+        const uint32_t lo = sh ? __builtin_amdgcn_alignbyte(w1, w0, sh) : w0, hi = sh ? __builtin_amdgcn_alignbyte(w2, w1, sh) : w1;
+        return (uint64_t)uni(lo) | (uint64_t)uni(hi) << 32;   // into scalar registers: the parser then runs on the scalar unit
+    };
+    if (ulen > kSnappyBlock) code = kSnappyLengthDisagrees;
+    else if (!c.compressed) {
+        if (in_len != ulen) code = kSnappyLengthDisagrees;
+        else
+            for (uint32_t at = 0; at < in_len; at += kSnappyDecWindow) {
+                stage(at);
+                for (uint32_t i = lane; i < wend - wbase; i += kSnappyDecThreads) so[at + i] = sw[i];
+            }
+    } else {
+        uint32_t p = 0, w = 0;
+        uint64_t declared = 0, hdr = 0;   // hdr: the 8 bytes at p; the parser asks for at most 5 of them, all below in_len
+        if (in_len) {
+            stage(0);
+            hdr = load8(0);
+            p = uni(snappy_elem_length([&](uint32_t i) -> uint32_t { return (uint32_t)(hdr >> (8 * i)) & 255u; }, in_len, declared));
+        }
+        if (!p || declared != ulen) code = kSnappyLengthDisagrees;
+        bool have = false;   // hdr holds the bytes at p
+        while (!code && p < in_len) {
+            if (!have) {
+                const uint32_t need = min(kSnappyElemMaxHeader, in_len - p);
+                if (p < wbase || p + need > wend) stage(p);
+                hdr = load8(p);
+            }
+            const SnappyElem e = snappy_elem_parse([&](uint32_t i) -> uint32_t { return (uint32_t)(hdr >> (8 * (i - p))) & 255u; }, in_len, p, w, ulen);
+            code = uni(e.code);
+            if (code) break;
+            const uint32_t len = uni(e.len), next = uni(e.next), is_copy = uni(e.copy);
+            // the next element's header, read while this element's bytes move (the window's bytes do not change under a restage)
+            have = false;
+            uint64_t nhdr = 0;
+            if (next < in_len) {
+                const uint32_t need = min(kSnappyElemMaxHeader, in_len - next);
+                if (next >= wbase && next + need <= wend) { nhdr = load8(next); have = true; }
+            }
+            if (!is_copy) {
+                const uint32_t src0 = uni(e.src);
+                for (uint32_t done = 0; done < len;) {   // [src0, src0 + len) lies in the body, [w, w + len) below ulen
+                    const uint32_t src = src0 + done;
+                    if (src < wbase || src >= wend) stage(src);
+                    const uint32_t k = min(len - done, wend - src);
+                    for (uint32_t i = lane; i < k; i += kSnappyDecThreads) so[w + done + i] = sw[src - wbase + i];
+                    done += k;
+                }
+                n_lit += len;
+            } else {
+                const uint32_t off = uni(e.off);   // 1 <= off <= w, len <= 64, w + len <= ulen
+                if (lane < len) {
+                    // off < len: the run-length case, lane i reads i mod off.  lane and off are below 64: (lane + 0.5) / off is
+                    // at least 1 / 128 from an integer, far more than the reciprocal's error, so the quotient is exact
+                    const uint32_t i = off < len ? lane - off * (uint32_t)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)off)) : lane;
+                    const uint8_t v = so[w - off + i];
+                    so[w + lane] = v;
+                }
+                ++n_cp;
+            }
+            w += len;
+            p = next;
+            hdr = nhdr;
+            gpl_wave_lds_sync();   // one wave: its LDS operations complete in order; this keeps the compiler to that order
+        }
+        if (!code && w != ulen) code = kSnappyOutputShort;
+    }
+    __syncthreads();
+    if (!code) {
+        uint32_t sl = ((ulen + 63) / 64 + 3) & ~3u;
+        if (!(sl & 4u)) sl += 4;   // an odd number of words from slice to slice: the lanes' reads spread over the banks
+        if (wave_masked_crc(so, ulen, sl, false, s_tab, lane) != c.crc) code = kSnappyCrcMismatch;
+    }
+    if (code) {
+        if (lane == 0) atomicMin(status, (unsigned long long)(first_index + blockIdx.x) << 8 | code);
+        return;
+    }
+    const uint32_t head = min(ulen, (uint32_t)((16 - ((uintptr_t)d & 15)) & 15));
+    if (lane < head) d[lane] = so[lane];
+    const uint32_t nvec = (ulen - head) / 16;
+    for (uint32_t k = lane; k < nvec; k += kSnappyDecThreads) *(uint4*)(d + head + 16 * k) = *(const uint4*)(so + head + 16 * k);
+    const uint32_t done = head + 16 * nvec;
+    if (lane < ulen - done) d[done + lane] = so[done + lane];
+    if (lane < 4) atomicAdd(&stats[lane], (unsigned long long)(lane == 0 ? 1u : lane == 1 ? (c.compressed ? 0u : 1u) : lane == 2 ? n_lit : n_cp));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the chunk table
+// k_collated_chunk_table: the chunk table of a collated record stream that lies on the device (the decoder's output), as the
+// host's hop over the `nbytes, nrec` headers finds it.  The hop is serial by nature - a header says where the next one stands -
+// so ONE WAVE makes it, through LDS tiles: a tile is staged with aligned, bounded loads (what lies outside the buffer reads as
+// 0 and is never fetched), the headers inside it are hopped in LDS, wave-uniform; a chunk that ends behind the tile costs one
+// jump to its end, and the tile behind a jump is a short one (kChunkTableShort: a large cell costs a header's worth of loads,
+// not a tile's), the whole tile again once headers keep falling into it.  Lane 0 writes offset, nbytes, nrec and the 8 bytes at chunk + 12 (the first record's barcode field) for
+// the chunks below `cap`; the hop counts on past it, so that the host can come back with room for all.  It ends at the first
+// refusal - the host hop's, in its order - and says which and at which chunk.
+__global__ __launch_bounds__(64) void k_collated_chunk_table(const uint8_t* __restrict__ bytes, uint64_t n, uint64_t first_chunk, uint32_t rec_hdr, uint64_t cap,
+                                                             uint64_t* __restrict__ off, uint32_t* __restrict__ nbytes, uint32_t* __restrict__ nrec,
+                                                             uint64_t* __restrict__ first_bc, uint64_t* __restrict__ stat) {
+    __shared__ uint32_t tile[kChunkTableWords];
+    const uint32_t lane = threadIdx.x;
+    uint64_t p = first_chunk, k = 0;
+    uint32_t code = kChunkTableOk;
+    uint32_t span = kChunkTableTile;   // bytes of this trip's tile: all of it while headers keep falling into it, a short one behind a jump
+    while (p < n && !code) {
+        const uint32_t al = (uint32_t)((reinterpret_cast<uintptr_t>(bytes) + p) & 3u);
+        const uint32_t words = (3 + span + kChunkTableHalo + 3) / 4 + 1;
+        const int64_t base = (int64_t)p - al;
+        if (base >= 0 && (uint64_t)base + 4ull * words <= n) {   // the tile lies inside the buffer: loads without a test each, many in flight
+#pragma unroll 8
+            for (uint32_t i = lane; i < words; i += 64) tile[i] = *reinterpret_cast<const uint32_t*>(bytes + base + 4ull * i);
+        } else
+            for (uint32_t i = lane; i < words; i += 64) tile[i] = gpl_ld_dword_in(bytes, n, base + 4ll * i);
+        gpl_wave_lds_sync();
+        uint32_t q = 0;   // the header at p + q: its 8 bytes and the 8 at + 12 lie in the tile or its halo
+        bool jumped = false;
+        while (q < span && p + q < n) {
+            const uint64_t a = p + q;
+            if (n - a < 8) { code = kChunkTableTrailing; break; }
+            const uint32_t nb = uni(gpl_lds32(tile, al + q)), nr = uni(gpl_lds32(tile, al + q + 4));
+            if (nb < 8 || nb > n - a) { code = kChunkTableCorrupt; break; }
+            if (rec_hdr && (nr == 0 || nb < 8 + rec_hdr)) { code = kChunkTableNoRecord; break; }
+            if (lane == 0 && k < cap) {
+                off[k] = a; nbytes[k] = nb; nrec[k] = nr;
+                first_bc[k] = (uint64_t)gpl_lds32(tile, al + q + 12) | (uint64_t)gpl_lds32(tile, al + q + 16) << 32;
+            }
+            ++k;
+            if (nb >= span - q) { p = a + nb; jumped = true; break; }   // the next header is not in this tile
+            q += nb;
+        }
+        if (!jumped) p += q;
+        span = jumped ? kChunkTableShort : kChunkTableTile;
+        gpl_wave_lds_sync();   // (the next trip overwrites the tile)
+    }
+    if (lane == 0) { stat[0] = k; stat[1] = code; }   // (a refusal: k is the index of the chunk it is about)
+}
+
 }  // namespace
 
 void launch_snappy_blocks(hipStream_t s, const uint8_t* in, uint64_t n, uint64_t n_blocks, uint8_t* slots, SnappyMeta* meta) {
@@ -271,6 +470,14 @@ void launch_snappy_layout(hipStream_t s, const SnappyMeta* meta, uint64_t n_bloc
 }
 void launch_snappy_pack(hipStream_t s, const uint8_t* in, uint64_t n_blocks, const uint8_t* slots, const SnappyMeta* meta, const uint64_t* off, uint8_t* out) {
     if (n_blocks) AFQ_LAUNCH(k_snappy_pack, (uint32_t)n_blocks, kPackNT, s, in, slots, meta, off, out);
+}
+
+void launch_snappy_decode(hipStream_t s, const uint8_t* in, const SnappyDecChunk* plan, uint32_t n_chunks, uint64_t first_index, uint8_t* dst, uint64_t* status, uint64_t* stats) {
+    if (n_chunks) AFQ_LAUNCH(k_snappy_decode, n_chunks, kSnappyDecThreads, s, in, plan, first_index, dst, (unsigned long long*)status, (unsigned long long*)stats);
+}
+void launch_collated_chunk_table(hipStream_t s, const uint8_t* bytes, uint64_t n, uint64_t first_chunk, uint32_t rec_hdr, uint64_t cap, uint64_t* off, uint32_t* nbytes,
+                                 uint32_t* nrec, uint64_t* first_bc, uint64_t* stat) {
+    AFQ_LAUNCH(k_collated_chunk_table, 1, 64, s, bytes, n, first_chunk, rec_hdr, cap, off, nbytes, nrec, first_bc, stat);
 }
 
 }  // namespace afq

@@ -627,6 +627,32 @@ int afq_snappy_frame_encode(afq_ctx* ctx, const uint8_t* bytes, size_t n_bytes, 
 /* out[0] = bytes of input per frame chunk (<= 65536), out[1] = slots of a chunk's last-position table, out[2] = longest single
  * copy element (<= 64), out[3] = chunks a workgroup takes.  For tests. */
 void afq_snappy_limits(uint32_t out[4]);
+/* The way back: the bytes of a snappy frame stream, decoded on the device (afq_snappy.hip, k_snappy_decode: one workgroup per
+ * data chunk, the chunk built in LDS, its masked CRC-32C checked there).  `stream` is host memory; the host plans it by its
+ * chunk headers and it crosses in pieces of whole chunks - at most afq_snappy_decode_limits()[2] data chunks, one launch a
+ * piece, never more than two pieces of compressed bytes on the device.  shift (0..3): decoded byte x lies at (*out)[shift + x]
+ * of the device buffer, whose base is 4-byte aligned at least.
+ * out_on_device = 0: *out is malloc'd host memory holding the *out_n decoded bytes (afq_free).
+ * out_on_device = 1: *out is device memory of the context, valid until the next decode on it or afq_destroy.
+ * What the decoder has to allocate and the device does not have free is AFQ_ERR_OOM with the sizes before any allocation or launch.  A stream the plan refuses, a corrupt block and
+ * a CRC mismatch are AFQ_ERR_BAD_INPUT with the host decoder's sentence ("corrupt snappy block", "snappy CRC mismatch", ...)
+ * followed by "(chunk N ...)", N the lowest data chunk that is refused; nothing out of range is read or written for any body,
+ * and the context serves again.  stats: n_in = n, n_out = *out_n, the rest as the encoder's over the stream's chunks. */
+int afq_snappy_frame_decode_device(afq_ctx* ctx, const uint8_t* stream, size_t n, uint32_t shift, int out_on_device, uint8_t** out, uint64_t* out_n,
+                                   afq_snappy_stats* stats);
+/* out[0] = bytes of a chunk's body staged per trip, out[1] = threads of a workgroup (one data chunk each), out[2] = data chunks
+ * of a launch at the most, out[3] = LDS bytes of a workgroup.  For tests. */
+void afq_snappy_decode_limits(uint32_t out[4]);
+/* The chunk table of a collated record stream that lies on the device (such as afq_snappy_frame_decode_device's output):
+ * d_bytes is a device pointer of any alignment to n bytes, the first chunk's header stands at first_chunk, every chunk begins
+ * with `nbytes:u32, nrec:u32` and the next one stands nbytes further.  One wave hops the headers (k_collated_chunk_table).
+ * Outputs, malloc'd (afq_free), one entry a chunk: its offset, nbytes, nrec, and the 8 bytes at offset + 12 - the first record's
+ * barcode field - little-endian, bytes behind the buffer's end as 0.  rec_hdr_bytes: the bytes of a record's head (na, barcode,
+ * UMI); a chunk must hold one record at least; 0: that is not asked.  Refusals, AFQ_ERR_BAD_INPUT, at the first chunk they hold
+ * for, with the sentences of afq_quantify's hop: "trailing bytes after the last chunk", "corrupt chunk header", "chunk N holds
+ * no record". */
+int afq_collated_chunk_table(afq_ctx* ctx, const uint8_t* d_bytes, uint64_t n, uint64_t first_chunk, uint32_t rec_hdr_bytes, uint64_t** off, uint32_t** nbytes,
+                             uint32_t** nrec, uint64_t** first_bc, uint64_t* n_chunks);
 /* on != 0: afq_collate_rad, afq_collate_multi_rad and afq_atac_collate_rad run as they do up to and including their write walk
  * and then hand out_bytes / out_n_bytes out as the snappy frame stream of the chunk bytes (afq_snappy_frame_encode's, encoded
  * where the bytes lie, in place of the plain copy down).  out_chunk_off, out_nrec, out_cell and every stats field, out_bytes

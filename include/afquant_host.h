@@ -41,7 +41,10 @@ typedef struct afq_quant_opts {
                                    per device over a contiguous, byte-balanced range of cells; rows are gathered in cell order, so
                                    the output does not depend on the device count                                          */
     uint32_t n_devices;
-    uint32_t reserved;
+    uint32_t sz_on_device;      /* --sz-on-device : map.collated.rad.sz is decoded on the device (afq_snappy_frame_decode_device) and stays there -
+                                   the prelude comes from its leading frame chunks, the chunk table from afq_collated_chunk_table, the
+                                   batches are submitted where the decoder left them.  One device only (several: AFQ_ERR_UNSUPPORTED);
+                                   ignored with a log line when the directory is not compressed.  0: the file is decoded on the host   */
 } afq_quant_opts;
 
 /* The CLI-visible options of `alevin-fry infer` (src/main.rs:350-365). */
@@ -65,7 +68,7 @@ typedef struct afq_atac_dedup_opts {
     uint32_t num_threads;       /* -t : BED formatting / snappy threads (0 = all cores)                                   */
     uint32_t rev;               /* -d/--permit-bc-ori rc (the CLI default) : barcodes are written reverse-complemented    */
     uint32_t device;
-    uint32_t reserved;
+    uint32_t sz_on_device;      /* --sz-on-device : as afq_quant_opts.sz_on_device                                        */
     struct afq_atac_stats* stats_out; /* optional: the counters the reference logs (deduplicate.rs:285-308)               */
 } afq_atac_dedup_opts;
 /* Runs the whole `atac deduplicate` sub-command (src/atac/deduplicate.rs:68-309) on the device: <input_dir>/map.bed. */
