@@ -11,7 +11,10 @@ the input such a kernel would see, and tests/test_far_offset_cases_cpu.py shows 
 
 A record layout is (fields, A): fields = [(name, width), ...] behind the 4-byte na, A = the bytes of one alignment.  A FAMILY (below)
 binds a layout to the family's existing case builders and judge; it adds no judge of its own - `from_bytes` only decodes bytes back
-into the structures the family's judge takes."""
+into the structures the family's judge takes.
+
+Below the families: `chunk_table_placement` (a collated stream for afq_collated_chunk_table) and `bam_placement` (a BAM record stream for
+afq_convert_bam_rad), built on the same buffer size with their own decoys; each section says how."""
 import numpy as np
 
 import atac_collate_cases as AC
@@ -475,3 +478,198 @@ def placements(fam, lim):
                     hit += 1
         assert hit, (fam.name, layout, "applies to no case")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ the chunk table
+# afq_collated_chunk_table hops a collated stream that lies on the device.  The stream here: CT_FIRST bytes of prelude, two chunks
+# of about 2^31 bytes each whose bodies are the buffer's zeros, thirty small chunks up to a header that stands at `at` - one of
+# CT_HEADERS_AT, all around byte 2^32 - and some three hundred chunks behind it, one longer than the hop's tile, the last one of 15
+# bytes: its 8 bytes at + 12 run past the stream's end, behind which CT_GUARD bytes of 0xff stand in the buffer (never the hop's to
+# read).  DECOYS: 2^32 below every byte at or behind 2^32 of a chunk's nbytes, nrec and 8 bytes at + 12 stands the byte of another
+# nbytes (+ 4), nrec (+ 1) and barcode (every bit flipped); they lie in the prelude and the first large chunk's body, which the hop
+# does not look at.  A hop that drops the high half of an address reads them: chunk_table_view(truncated=True).
+CT_FIRST = 37
+CT_HEADERS_AT = (FAR - 20, FAR - 15, FAR - 8, FAR - 4, FAR - 1)   # (the chunk at FAR - 20 is one of 20 bytes: the next header stands at FAR)
+CT_WHERE = {FAR - 20: ("nbytes", 0), FAR - 15: ("first_bc", 3), FAR - 8: ("record", 0), FAR - 4: ("nrec", 0), FAR - 1: ("nbytes", 1)}
+CT_BIG = (1 << 31) + 12345
+CT_GUARD = 16
+
+
+def chunk_table_placement(at, tile, no_record=False):
+    """-> dict: pieces (for a zeroed buffer of N_BYTES), n (the stream's bytes), off / nbytes (every chunk's, Python ints), k_at (the
+    index of the chunk at `at`), n_whole (the stream's bytes without its last, 15-byte chunk).  no_record: chunk k_at + 2, which
+    lies behind byte 2^32, says nrec = 0."""
+    import chunk_table_cases as T
+
+    rng = np.random.default_rng(int(FAR - at))
+    front = [int(x) for x in rng.integers(20, 900, 30)]
+    back = [20 if at == FAR - 20 else 333] + [int(x) for x in rng.integers(20, 900, 300)] + [15]
+    back[150] = tile + 777
+    small0 = at - sum(front)
+    sizes = [CT_BIG, small0 - CT_FIRST - CT_BIG] + front + back
+    off = _from(sizes, CT_FIRST)
+    k_at, n = 2 + len(front), off[-1] + sizes[-1]
+    assert off[k_at] == at and off[2] == small0 and (1 << 30) < sizes[1] < FAR and n + CT_GUARD + 3 <= N_BYTES
+    nrec = [1, 1] + [nb & 7 or 1 for nb in sizes[2:]]
+    if no_record:
+        assert off[k_at + 2] > FAR
+        nrec[k_at + 2] = 0
+    chunks = [T.chunk(nb, nr, rng) for nb, nr in zip(sizes[2:], nrec[2:])]
+    far = b"".join(chunks)
+    head = lambda nb, nr: int(nb).to_bytes(4, "little") + int(nr).to_bytes(4, "little")
+    low = bytearray(n - FAR)
+    low[:CT_FIRST] = rng.integers(0, 256, CT_FIRST, dtype=np.uint8).tobytes()
+    for p, ch, nb, nr in zip(off[2:], chunks, sizes[2:], nrec[2:]):
+        fields = head(nb + 4, nr + 1) + ch[8:12] + bytes(x ^ 0xFF for x in ch[12:20])
+        for j in list(range(8)) + list(range(12, len(fields))):
+            if p + j >= FAR:
+                low[p + j - FAR] = fields[j]
+    low[CT_FIRST:CT_FIRST + 8] = head(sizes[0], 1)
+    pieces = [(0, bytes(low)), (off[1], head(sizes[1], 1)), (small0, far), (n, b"\xff" * CT_GUARD)]
+    return {"pieces": pieces, "n": n, "off": off, "nbytes": sizes, "nrec": nrec, "k_at": k_at, "n_whole": off[-1], "at": at}
+
+
+def chunk_table_view(pl, n=None, truncated=False):
+    """the stream's first n bytes (all of them by default) as the hop reads them - chunk_table_cases.host_hop takes it"""
+    import chunk_table_cases as T
+
+    return T.Sparse(pl["n"] if n is None else n, pl["pieces"], wrap=FAR if truncated else None)
+
+
+def chunk_table_where(pl):
+    """(field, byte within it) of byte 2^32: nbytes, nrec, "record" (the 4 bytes behind the header), first_bc or "body" """
+    c = max(i for i, o in enumerate(pl["off"]) if o <= FAR)
+    j = FAR - pl["off"][c]
+    assert j < pl["nbytes"][c]
+    for name, a, b in (("nbytes", 0, 4), ("nrec", 4, 8), ("record", 8, 12), ("first_bc", 12, 20)):
+        if a <= j < b:
+            return name, j - a
+    return "body", j - 20
+
+
+# ------------------------------------------------------------------------------------------------------------------ convert
+# afq_convert_bam_rad walks every byte of an inflated BAM record stream, so what lies between the low records and the records at byte
+# 2^32 are records too: two FILLERS, unmapped (flag 0x4, dropped by the walk), every other fixed field zero, block_size about 2^31,
+# each in a span of its own; only their 36 fixed bytes are written, their bodies are the buffer's zeros and are never parsed.  The
+# stream: a pad (one unmapped record), the DECOYS, [one more low record], filler, filler, the high records.  Decoy j stands exactly
+# 2^32 below high record j and has its sizes; every character of its name and every base of its CR and UR is another one, its refID is
+# the next one, its AS has the low bit flipped.  The decoys are records of the stream like any other (the judge states them too): a
+# kernel that drops the high half of an offset reads a decoy where it owes a high record and writes the decoy's run twice.
+BAM_N_REF, BAM_BW, BAM_UW = 7, 4, 4
+BAM_PLACEMENTS = ("block_size", "l_read_name", "flag", "name", "CR", "UR", "AS", "start-on", "run-across")
+_BASE = str.maketrans("ACGTN", "CGTAC")
+
+
+def bam_filler_bytes(block_size):
+    import struct
+
+    return struct.pack("<I", block_size) + struct.pack("<iiBBHHHIiii", 0, 0, 0, 0, 0, 0, 0x4, 0, 0, 0, 0)
+
+
+def bam_decoy(r):
+    aux = []
+    for t, ty, v in r.get("aux", []):
+        if t in ("CR", "UR") and ty == "Z":
+            v = v.translate(_BASE)
+        elif t == "AS" and ty in "cCsSiI":
+            v ^= 1
+        aux.append((t, ty, v))
+    return dict(r, name="".join(chr(ord(ch) ^ 1) for ch in r["name"]), ref=(r.get("ref", 0) + 1) % BAM_N_REF, aux=aux)
+
+
+def bam_high_records(lim):
+    """the records that stand around byte 2^32: the runs of bam_cases' `names`, `scores`, `aux` and `n_and_lengths` (every one with an
+    integer AS, so that every placement runs with and without filter_best) -> (records, the index of the target: a run's head with CR,
+    UR and a 4-byte AS)"""
+    import bam_cases as B
+
+    by_name = {c["name"]: c for c in B.name_cases() + B.device_cases(lim)}
+    recs = [r for name in ("names", "scores", "aux", "n_and_lengths") for r in by_name[name]["records"]]
+    t = next(i for i, r in enumerate(recs) if r["name"] == "tied")
+    return recs, t
+
+
+def bam_field_at(r, k):
+    """the field of record r (its bytes: block_size first) that byte k lies in: a fixed field's name, "name", or (tag, "tag" / "value")"""
+    import bam_cases as B
+
+    fixed = (("block_size", 4), ("refID", 4), ("pos", 4), ("l_read_name", 1), ("mapq", 1), ("bin", 2), ("n_cigar_op", 2), ("flag", 2), ("l_seq", 4), ("next_refID", 4),
+             ("next_pos", 4), ("tlen", 4))
+    at = 0
+    for name, w in fixed:
+        if k < at + w:
+            return name
+        at += w
+    if k < at + len(r["name"]) + 1:
+        return "name"
+    at += len(r["name"]) + 1 + 4 * len(r.get("cigar", [])) + (r.get("seq_len", 0) + 1) // 2 + r.get("seq_len", 0)
+    assert k >= at, "the placements aim at no CIGAR or sequence"
+    for f in r.get("aux", []):
+        n = len(B.aux_bytes([f]))
+        if k < at + n:
+            return f[0], "tag" if k < at + 3 else "value"
+        at += n
+    return "tail"
+
+
+def bam_offset_of(r, field):
+    """the first byte, from the record's first, of a fixed field, of the name, or of an aux tag's value"""
+    import bam_cases as B
+
+    n = len(B.record_bytes(r))
+    return next(k for k in range(n) if bam_field_at(r, k) in (field, (field, "value")))
+
+
+def bam_placement(where, lim, tail=None):
+    """-> dict: pieces, n_bytes, span_off, records (the judge's list, the fillers as small unmapped records), high0 (the index of the
+    first high record), offs (every record's offset), target (the index of the record that byte 2^32 lies in), decoyed (the indices of
+    the high records that have a decoy 2^32 below).  tail: a record put behind the last high record (the refusals')."""
+    import bam_cases as B
+
+    high, t = bam_high_records(lim)
+    low_extra = []
+    if where == "run-across":   # a run of three with distinct scores: its head the last low record, the others the first high ones
+        run = [B.rec("across", ref=i + 2, score=s, flag=0x10 * (i & 1)) for i, s in enumerate((3, 9, 9))]
+        low_extra, high, t = run[:1], run[1:] + high, 0
+    high = high + ([tail] if tail is not None else [])
+    hb = [B.record_bytes(r) for r in high]
+    within = {"block_size": 2, "l_read_name": bam_offset_of(high[t], "l_read_name"), "flag": bam_offset_of(high[t], "flag"), "name": bam_offset_of(high[t], "name") + 2,
+              "CR": bam_offset_of(high[t], "CR") + 5, "UR": bam_offset_of(high[t], "UR") + 5, "AS": bam_offset_of(high[t], "AS") + 2, "start-on": 0, "run-across": -5}[where]
+    h_off = _around([len(b) for b in hb], t, FAR - within)
+    # the low side: a pad up to the first decoy, the decoys 2^32 below their high records
+    j0 = next(j for j, o in enumerate(h_off) if o == FAR or o - FAR >= 64)   # (the pad is a record: bam_cases.filler makes none below 54 bytes)
+    n_dec = len(high) - j0 - (tail is not None)   # (the refusals' record has no decoy: the lowest record in error is the one named)
+    decoys = [bam_decoy(r) for r in high[j0:j0 + n_dec]]
+    assert [len(B.record_bytes(d)) for d in decoys] == [len(b) for b in hb[j0:j0 + n_dec]]
+    pad = [B.filler(h_off[j0] - FAR, name="pad")] if h_off[j0] > FAR else []
+    low = pad + decoys + low_extra
+    lb = [B.record_bytes(r) for r in low]
+    low_end, high_end = sum(len(b) for b in lb), h_off[-1] + len(hb[-1])
+    f1, f2 = low_end, low_end + 36 + CT_BIG
+    sizes = [len(b) for b in lb] + [f2 - f1, h_off[0] - f2] + [len(b) for b in hb]
+    offs = _from(sizes, 0)
+    high0 = len(low) + 2
+    assert offs[high0:] == h_off and all(offs[len(pad) + j] == h_off[j0 + j] - FAR for j in range(len(decoys))) and high_end + 16 + 3 <= N_BYTES
+    unmapped = dict(name="", flag=0x4)
+    pieces = [(0, b"".join(lb)), (f1, bam_filler_bytes(f2 - f1 - 4)), (f2, bam_filler_bytes(h_off[0] - f2 - 4)), (h_off[0], b"".join(hb))]
+    span_off = sorted({0, f1, f2, h_off[0]} | {o for o in h_off[7::7]} | ({FAR} if where == "start-on" else set()))
+    return {"where": where, "pieces": pieces, "n_bytes": high_end, "span_off": span_off, "records": low + [unmapped, unmapped] + high, "high0": high0, "offs": offs,
+            "target": high0 + t, "decoyed": list(range(high0 + j0, high0 + j0 + n_dec)), "n_pad": len(pad), "fillers": (high0 - 2, high0 - 1)}
+
+
+def bam_truncated_records(pl):
+    """the record list a kernel states that reads every record at its offset mod 2^32: the decoys where the decoyed high records stand"""
+    recs = list(pl["records"])
+    for j, i in enumerate(pl["decoyed"]):
+        recs[i] = pl["records"][pl["n_pad"] + j]
+    return recs
+
+
+def bam_refusals(lim):
+    """(name, placement, record index named): a record behind byte 2^32 whose aux fields overrun its end; a last record whose block_size
+    reaches past the span's end.  Both are refused through the error word; neither makes a kernel read outside [0, n_bytes)."""
+    import bam_cases as B
+
+    a = bam_placement("block_size", lim, tail=dict(B.rec("overrun", ref=1, score=1), raw_tail=b"XY"))
+    b = bam_placement("block_size", lim, tail=dict(B.rec("past", ref=1, score=1), block_size=4000))
+    return [("aux past the record's end", a, len(a["records"]) - 1), ("block_size past the span's end", b, len(b["records"]) - 1)]

@@ -221,3 +221,115 @@ def judge_chunk(c):
         return True, sj.crc32c(sj.raw_decode(c.body))
     except sj.SnappyJudgeError:
         return False, None
+
+
+# ------------------------------------------------------------------------------------------------ output at and across byte 2^32
+# A stream whose decoded bytes cross byte 2^32 (tests/test_gpu_snappy_decode.py decodes it, tests/test_snappy_far_stream_cpu.py
+# holds its plan): a first chunk, a LOW GROUP of small mixed chunks, some 65 535 chunks of 65 536 zero bytes (one frame, repeated),
+# a shorter chunk of zeros that brings the output to where the FAR GROUP must begin, and the far group - forty small mixed chunks,
+# one of them (the STRADDLER, larger) begins `before` bytes in front of byte 2^32.  The far chunks behind the straddler are the
+# low group's twins: low chunk j lies exactly 2^32 below far chunk j + 1 behind the straddler, has its length and other bytes, and
+# the first chunk (random bytes) lies 2^32 below the straddler's bytes from byte 2^32 on.  A decoder that drops the high half of an
+# out_off therefore writes over the low group, and what is read back of [0, 2^21) differs from what the stream says.
+FAR = 1 << 32
+FAR_LOW, FAR_GROUP, FAR_STRADDLER = 10, 40, 5   # chunks of the low group, of the far group, the straddler's place in the far group
+FAR_STREAMS = {   # name: (the straddler of a seed, its elements' output lengths as (kind, n), `before`)
+    "in a literal": (lambda seed: compressed([("lit", rnd(4097, seed))]), [("lit", 4097)], 1003),
+    "in a copy": (lambda seed: compressed(run_elems(4097, seed, 29)), [("lit", 29)] + [("copy", 64)] * 63 + [("copy", 36)], 2048),
+    "start on": (lambda seed: stored(rnd(4097, seed)), [("stored", 4097)], 0),
+}
+
+
+def mixed_kinds(seed=0):
+    """forty compressed chunks of run elements (1 .. 40 bytes, periods 1 .. 5) and five stored ones (0 .. 4 bytes)"""
+    return [compressed(run_elems(1 + k, seed + k, 1 + k % 5)) for k in range(40)] + [stored(rnd(k, seed + k)) for k in range(5)]
+
+
+def zeros_chunk(n):
+    """n >= 1 zero bytes: one literal of a byte, then copies from 1 back, 64 at a time"""
+    return compressed([("lit", b"\0")] + [("copy", 2, 1, min(64, n - 1 - a)) for a in range(0, n - 1, 64)])
+
+
+class FarStream:
+    """runs: [(group, DataChunk, count)] in stream order; first[r] / out_off[r]: the index and output offset of run r's first chunk"""
+
+    def __init__(self, name):
+        make, self.straddler_elems, self.before = FAR_STREAMS[name]
+        self.name = name
+        far_kinds, low_kinds = mixed_kinds(0), mixed_kinds(1000)
+        far = [far_kinds[(7 * j) % len(far_kinds)] for j in range(FAR_GROUP)]
+        far[FAR_STRADDLER] = make(77)
+        low = [low_kinds[(7 * j) % len(low_kinds)] for j in range(FAR_STRADDLER + 1, FAR_STRADDLER + 1 + FAR_LOW)]
+        first = stored(rnd(len(far[FAR_STRADDLER].data) - self.before, 78))
+        self.filler = zeros_chunk(65536)
+        front = len(first.data) + sum(len(c.data) for c in low)
+        gap = FAR - self.before - sum(len(c.data) for c in far[:FAR_STRADDLER]) - front
+        self.n_fillers, short = divmod(gap, 65536)
+        self.runs = [("first", first, 1)] + [("low", c, 1) for c in low] + [("filler", self.filler, self.n_fillers)]
+        self.runs += [("short filler", zeros_chunk(short), 1)] if short else []
+        self.runs += [("far", c, 1) for c in far]
+        self.first, self.out_off, i, o = [], [], 0, 0
+        for _, c, count in self.runs:
+            self.first.append(i), self.out_off.append(o)
+            i, o = i + count, o + count * len(c.data)
+        self.n_chunks, self.total = i, o
+
+    def stream(self, crc_flip=None):
+        """the stream's bytes; crc_flip = (chunk index, bit): that chunk's CRC with the bit flipped"""
+        parts = [sj.STREAM_ID]
+        for (_, c, count), i in zip(self.runs, self.first):
+            if crc_flip is not None and crc_flip[0] == i:
+                assert count == 1
+                c = DataChunk(c.compressed, c.body, c.data, crc_xor=1 << crc_flip[1])
+            parts.append(c.frame() * count)
+        return b"".join(parts)
+
+    def group(self, name):
+        """[(chunk index, out_off, chunk)] of the single chunks of a group"""
+        return [(i, o, c) for (g, c, count), i, o in zip(self.runs, self.first, self.out_off) if g == name and count == 1]
+
+    def straddler(self):
+        return self.group("far")[FAR_STRADDLER]
+
+    def elem_at(self, byte):
+        """(kind, first output byte, length) of the straddler's element that produces output byte `byte` of the straddler"""
+        at = 0
+        for kind, n in self.straddler_elems:
+            if at <= byte < at + n:
+                return kind, at, n
+            at += n
+        raise ValueError(byte)
+
+    def window(self, a, b, truncated=False):
+        """bytes [a, b) of the output as the stream says them, zeros behind `total`.  truncated: as a decoder leaves them that writes
+        every chunk, in stream order, at out_off mod 2^32 (the model of a dropped high half; a window of it is sparse, like this one)."""
+        out = bytearray(b - a)
+        for (_, c, count), o in zip(self.runs, self.out_off):
+            u = len(c.data)
+            if not u:
+                continue
+            if count > 1:   # the fillers end below 2^32, truncated or not: only those that touch the window are visited
+                assert o + count * u <= FAR
+                starts = [o + k * u for k in range(max(0, (a - o) // u), min(count, -(-(b - o) // u)))]
+            else:
+                starts = [o % FAR if truncated else o]
+            for s in starts:
+                x, y = max(a, s), min(b, s + u)
+                if x < y:
+                    out[x - a:y - a] = c.data[x - s:y - s]
+        return bytes(out)
+
+    def tallies(self):
+        """n_blocks, n_blocks_stored, n_literal_bytes, n_copies: the judge's tallies of each distinct chunk times how often it occurs"""
+        t, seen = dict(n_blocks=0, n_blocks_stored=0, n_literal_bytes=0, n_copies=0), {}
+        for _, c, count in self.runs:
+            if id(c) not in seen:
+                s = sj.decode(sj.STREAM_ID + c.frame())
+                assert s.data == c.data and s.n_chunks == 1
+                seen[id(c)] = s
+            s = seen[id(c)]
+            t["n_blocks"] += count
+            t["n_blocks_stored"] += count * s.n_stored
+            t["n_literal_bytes"] += count * s.literal_bytes
+            t["n_copies"] += count * s.copies
+        return t

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from chunk_table_cases import chunk, host_hop   # (one copy, shared with tests/test_gpu_far_offsets.py)
 from util import pkg
 
 pytestmark = pytest.mark.gpu
@@ -22,29 +23,6 @@ def q():
     qq = pkg.Quantifier(cfg, np.zeros(1, np.uint32), device=0)
     yield qq
     qq.close()
-
-
-def host_hop(b, first_chunk, rec_hdr):
-    """afq_quantify's hop: (off, nbytes, nrec, first_bc), or the sentence it refuses with"""
-    n, p = len(b), first_chunk
-    off, nbs, nrs, bcs = [], [], [], []
-    while p < n:
-        if p + 8 > n:
-            return "trailing bytes after the last chunk"
-        nb, nr = int.from_bytes(b[p:p + 4], "little"), int.from_bytes(b[p + 4:p + 8], "little")
-        if nb < 8 or p + nb > n:
-            return "corrupt chunk header"
-        if rec_hdr and (nr == 0 or nb < 8 + rec_hdr):
-            return f"chunk {len(off)} holds no record"
-        off.append(p), nbs.append(nb), nrs.append(nr)
-        bcs.append(int.from_bytes(b[p + 12:p + 20].ljust(8, b"\0"), "little"))
-        p += nb
-    return np.array(off, np.uint64), np.array(nbs, np.uint32), np.array(nrs, np.uint32), np.array(bcs, np.uint64)
-
-
-def chunk(nb, nr, rng):
-    assert nb >= 8
-    return int(nb).to_bytes(4, "little") + int(nr).to_bytes(4, "little") + rng.integers(0, 256, nb - 8, dtype=np.uint8).tobytes()
 
 
 def device_table(q, b, first_chunk, rec_hdr, shift):

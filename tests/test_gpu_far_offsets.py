@@ -1,7 +1,9 @@
 """GPU tests of 64-bit chunk offsets: the eight record passes and the quant decoders read chunks that lie at and across byte 2^32 of
 one device buffer (tests/far_offset_cases.py places them; tests/test_far_offset_cases_cpu.py shows where byte 2^32 falls and that
 the decoys at offset - 2^32 give a kernel that truncates an offset a wrong answer).  The chunks' contents are those of the families'
-existing cases, so every result is compared exactly with the family's existing judge on the original case.
+existing cases, so every result is compared exactly with the family's existing judge on the original case.  The same holds for the
+chunk-table hop over a collated stream and for the convert walk over a BAM record stream, each with its headers or records around
+byte 2^32, its decoys 2^32 lower and its existing judge (chunk_table_cases.host_hop, convert_judge.stated).
 
 One buffer of 2^32 + 2^21 zero bytes serves the whole module; a test writes its pieces, runs, and zeroes them again."""
 import contextlib
@@ -204,3 +206,102 @@ def test_widened_and_stripped_cells_far_in_the_buffer(buf, bw, uw, e, umi_len):
     want, gots = compact_then_far(buf, cfg, s.tid_to_gid, bp, op, bw, uw, e)
     for got in [want] + gots:
         _judge_device(got, cells, js, f"{bw}/{uw}/{e}")
+
+
+# ------------------------------------------------------------------------------------------------------------------ the chunk table
+def test_chunk_table_past_4_gib(buf, q):
+    """afq_collated_chunk_table over a stream of 2^32 and some 170 KB bytes (F.chunk_table_placement): a header at each of
+    F.CT_HEADERS_AT and on byte 2^32, three hundred chunks behind it, decoys 2^32 below; the table is chunk_table_cases.host_hop's
+    over the sparse pieces, and so are the three refusals, whose chunks lie behind byte 2^32"""
+    import chunk_table_cases as T
+
+    tile, wants = T.hop_tile(), {}
+
+    def hop(pl, d_ptr, n, rec_hdr, what):
+        key = (pl["at"], pl["nrec"][pl["k_at"] + 2], n, rec_hdr)
+        if key not in wants:
+            wants[key] = T.host_hop(F.chunk_table_view(pl, n), F.CT_FIRST, rec_hdr)
+        want = wants[key]
+        if isinstance(want, str):
+            with pytest.raises(pkg.AfqError) as e:
+                q.collated_chunk_table(d_ptr, n, F.CT_FIRST, rec_hdr)
+            assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and str(e.value).endswith(": " + want), (what, str(e.value), want)
+        else:
+            got = q.collated_chunk_table(d_ptr, n, F.CT_FIRST, rec_hdr)
+            for g, w, name in zip(got, want, ("off", "nbytes", "nrec", "first_bc")):
+                assert g.dtype == w.dtype and np.array_equal(g, w), (what, name)
+        return want
+
+    tables = refusals = 0
+    for at in F.CT_HEADERS_AT:
+        pl, nr = F.chunk_table_placement(at, tile), F.chunk_table_placement(at, tile, no_record=True)
+        n_chunks, K = len(pl["off"]), nr["k_at"] + 2
+        assert F.chunk_table_where(pl) == F.CT_WHERE[at] and nr["off"][K] > F.FAR and sum(1 for o in pl["off"] if o >= F.FAR) > 300
+        for al in ALS:
+            what = f"header at 2^32 - {F.FAR - at} / base + {al}"
+            with placed(buf, pl["pieces"], al) as (d_ptr, _):
+                for n, rec_hdr, k in ((pl["n"], 6, n_chunks), (pl["n"], 0, n_chunks), (pl["n_whole"], 12, n_chunks - 1)):
+                    w = hop(pl, d_ptr, n, rec_hdr, what)
+                    assert len(w[0]) == k and int(w[0][-1]) > F.FAR
+                    tables += 1
+                for rec_hdr in (12, 0):
+                    assert hop(pl, d_ptr, pl["n_whole"] + 5, rec_hdr, what) == "trailing bytes after the last chunk"
+                    assert hop(pl, d_ptr, pl["n"] - 1, rec_hdr, what) == "corrupt chunk header"
+                    refusals += 2
+                assert hop(pl, d_ptr, pl["n"], 12, what) == f"chunk {n_chunks - 1} holds no record"
+                refusals += 1
+            with placed(buf, nr["pieces"], al) as (d_ptr, _):
+                assert hop(nr, d_ptr, nr["n_whole"], 12, what) == f"chunk {K} holds no record"
+                assert len(hop(nr, d_ptr, nr["n_whole"], 0, what)[0]) == n_chunks - 1
+                assert len(hop(nr, d_ptr, nr["n"], 0, what)[0]) == n_chunks   # the context serves again
+                refusals, tables = refusals + 1, tables + 2
+    assert tables == len(F.CT_HEADERS_AT) * len(ALS) * 5 == 50 and refusals == len(F.CT_HEADERS_AT) * len(ALS) * 6 == 60
+
+
+# ------------------------------------------------------------------------------------------------------------------ convert
+def _convert(q, pl, fb, d_ptr):
+    return q.convert_bam_rad(None, pl["span_off"], n_ref=F.BAM_N_REF, bc_bytes=F.BAM_BW, umi_bytes=F.BAM_UW, filter_best=fb, d_ptr=d_ptr, n_bytes=pl["n_bytes"])
+
+
+def test_convert_reads_records_at_and_across_byte_two_to_the_32(buf, q):
+    """afq_convert_bam_rad over a record stream of 2^32 and a few thousand bytes (F.bam_placement): byte 2^32 in a record's block_size,
+    l_read_name, flag, name, CR, UR and AS, a record and a span on it, a run whose head lies 4 GiB in front of its other records; the
+    decoys 2^32 below.  Judged by convert_judge.stated on the same records, with test_gpu_convert's `same`.  Then the two refusals
+    behind byte 2^32, each naming its record, and a placement again."""
+    import convert_judge as J
+    from test_gpu_convert import same
+
+    lim = pkg.convert_limits()
+    compared = 0
+    for where in F.BAM_PLACEMENTS:
+        pl = F.bam_placement(where, lim)
+        wants = {fb: J.stated(pl["records"], fb, n_ref=F.BAM_N_REF, lane_alns=lim["lane_alns"], bw=F.BAM_BW, uw=F.BAM_UW) for fb in (False, True)}
+        assert wants[False]["stats"]["n_records"] == len(pl["records"]) and wants[False]["stats"]["n_dropped_by_flag"] >= 2 and pl["n_bytes"] > F.FAR
+        for al in ALS:
+            with placed(buf, pl["pieces"], al) as (d_ptr, _):
+                for fb in (False, True):
+                    same(_convert(q, pl, fb, d_ptr), wants[fb], f"convert / {where} / base + {al} / filter_best={fb}")
+                    compared += 1
+    assert compared == len(F.BAM_PLACEMENTS) * len(ALS) * 2 == 36
+    refused = 0
+    for what, pl, index in F.bam_refusals(lim):
+        assert pl["offs"][index] > F.FAR
+        for al in ALS:
+            with placed(buf, pl["pieces"], al) as (d_ptr, _):
+                with pytest.raises(pkg.AfqError) as e:
+                    _convert(q, pl, False, d_ptr)
+                assert e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and f"record {index}:" in str(e.value), (what, al, str(e.value))
+                refused += 1
+        c = _names_case()
+        got = q.convert_bam_rad(c[0], c[1], n_ref=F.BAM_N_REF, bc_bytes=F.BAM_BW, umi_bytes=F.BAM_UW)   # the context serves a small case
+        same(got, c[2], f"names behind {what}")
+    assert refused == 2 * len(ALS)
+
+
+def _names_case():
+    """bam_cases' `names` case from host bytes: (stream, span table, what the judge states)"""
+    import bam_cases as B
+    import convert_judge as J
+
+    c = B.name_cases()[0]
+    return B.stream_of(c)[0], B.span_table(c), J.stated(c["records"], False, n_ref=F.BAM_N_REF, lane_alns=pkg.convert_limits()["lane_alns"])

@@ -120,7 +120,7 @@ def test_more_chunks_than_a_launch_takes(q, hip):
     """pieces of the stream: piece_chunks + 5 and 2 piece_chunks + 1 data chunks cross in two and three launches, through both
     buffers and back into the first; a bad chunk in the last piece is named by its index in the stream"""
     pc = pkg.afquant.snappy_decode_limits()["piece_chunks"]
-    kinds = [ss.compressed(ss.run_elems(1 + k, k, 1 + k % 5)) for k in range(40)] + [ss.stored(ss.rnd(k, k)) for k in range(5)]
+    kinds = ss.mixed_kinds()
     for n in (pc + 5, 2 * pc + 1):
         case = ss.Case(f"{n} chunks", [kinds[(7 * k) % len(kinds)] for k in range(n)])
         decode_every_way(q, hip, case.stream, case.data, what=case.name, shifts=(0, 3))
@@ -129,6 +129,66 @@ def test_more_chunks_than_a_launch_takes(q, hip):
     with pytest.raises(pkg.AfqError) as e:
         q.snappy_frame_decode(case.stream)
     assert f"corrupt snappy block (chunk {2 * pc + 3}: a copy from offset 0)" in str(e.value), str(e.value)
+
+
+@pytest.mark.parametrize("name", sorted(ss.FAR_STREAMS))
+def test_output_offsets_past_4_gib(hip, name):
+    """ss.FarStream: 4 GiB and a little of output, mostly chunks of 65 536 zeros, in more than 16 pieces; a chunk begins `before`
+    bytes in front of byte 2^32 (inside a literal, inside a copy's destination, or on it), the far chunks behind it have twins of
+    other bytes 2^32 lower (tests/test_snappy_far_stream_cpu.py).  Read back: the low 2 MiB with the twins, the MiB in front of byte
+    2^32 to the end, the 16 cleared bytes behind, sixteen MiB of the zeros between, then every byte of the fillers in 256 MiB pieces.
+    Then a far chunk's CRC with a bit flipped.  Prints each decode's and each sweep's wall time."""
+    import time
+
+    FAR = ss.FAR
+    fs = ss.FarStream(name)
+    stream = fs.stream()
+    pc = pkg.afquant.snappy_decode_limits()["piece_chunks"]
+    si, so, sc = fs.straddler()
+    far, low = fs.group("far"), fs.group("low")
+    assert fs.n_chunks > 16 * pc and 150e6 < len(stream) < 300e6 and FAR < fs.total < FAR + (1 << 20)
+    assert so == FAR - fs.before and so <= FAR < so + len(sc.data) and (fs.before == 0) == (name == "start on") and (fs.before % 16 != 0 or name != "in a literal")
+    assert name != "in a copy" or fs.elem_at(fs.before)[0] == "copy" and fs.elem_at(fs.before)[1] < fs.before
+    assert far[ss.FAR_STRADDLER] == (si, so, sc) and all(i > 1 << 16 for i, _, _ in far) and low[0][:2] == (1, len(sc.data) - fs.before)
+    assert all(fo - FAR == lo and len(fc.data) == len(lc.data) and (fc.data != lc.data or not fc.data) for (_, lo, lc), (_, fo, fc) in zip(low, far[ss.FAR_STRADDLER + 1:]))
+    stats = dict(fs.tallies(), n_in=len(stream), n_out=fs.total)
+    windows = [(0, 1 << 21), (FAR - (1 << 20), fs.total + 16)] + [((2 * k + 1) << 27, ((2 * k + 1) << 27) + (1 << 20)) for k in range(16)]
+    wants = [fs.window(a, b) for a, b in windows]
+    assert wants[1][-16:] == bytes(16) and all(w == bytes(1 << 20) for w in wants[2:]) and wants[0] != fs.window(0, 1 << 21, truncated=True)
+    small = ss.VALID[-1]
+    q = pkg.Quantifier(pkg.WorkerConfig.for_resolution("cr-like", num_genes=1, num_rows=1), np.zeros(1, np.uint32), device=0)   # its 4 GiB end with the test
+    try:
+        compared = 0
+        for shift in (0, 3):
+            t0 = time.perf_counter()
+            ptr, n, st = q.snappy_frame_decode(stream, shift=shift, on_device=True)
+            print("%s, shift %d: %d bytes decoded in %.2f s" % (name, shift, n, time.perf_counter() - t0))
+            assert n == fs.total and st == stats and ptr % 4 == 0, (name, shift, n, st, stats)
+            for (a, b), want in zip(windows, wants):
+                assert read_back(hip, ptr + shift + a, b - a) == want, (name, shift, "bytes [%d, %d)" % (a, b))
+                compared += 1
+            # the sweep: every byte between the low 2 MiB and the MiB in front of byte 2^32 is a filler's zero
+            t0, room, swept = time.perf_counter(), C.create_string_buffer(1 << 28), 0
+            for a in range(0, FAR, 1 << 28):
+                a, b = max(a, 1 << 21), min(a + (1 << 28), FAR - (1 << 20))
+                assert hip.hipMemcpy(room, C.c_void_p(ptr + shift + a), b - a, 2) == 0
+                assert not np.frombuffer(room, np.uint8, b - a).any(), (name, shift, "a byte of the fillers in [%d, %d)" % (a, b))
+                swept += b - a
+            assert swept == FAR - (1 << 21) - (1 << 20)
+            print("%s, shift %d: %d bytes swept in %.2f s" % (name, shift, swept, time.perf_counter() - t0))
+            del room
+        assert compared == 2 * len(windows) == 36
+        del stream
+        bi = far[ss.FAR_STRADDLER + 3][0]
+        bad = fs.stream(crc_flip=(bi, 9))
+        t0 = time.perf_counter()
+        with pytest.raises(pkg.AfqError) as e:
+            q.snappy_frame_decode(bad, shift=1, on_device=True)
+        print("%s, a CRC bit of chunk %d: refused in %.2f s" % (name, bi, time.perf_counter() - t0))
+        assert bi > 1 << 16 and e.value.code == pkg._abi.AFQ_ERR_BAD_INPUT and f"snappy CRC mismatch (chunk {bi})" in str(e.value), str(e.value)
+        decode_every_way(q, hip, small.stream, small.data, what=f"{small.name} behind the refusal", shifts=(1,))
+    finally:
+        q.close()
 
 
 @pytest.mark.parametrize("fill", ["zeros", "random", "rad"])
