@@ -147,6 +147,8 @@ EXPORTS = [
     "afq_snappy_frame_decode_device",
     "afq_snappy_decode_limits",
     "afq_collated_chunk_table",
+    "afq_bgzf_inflate_device",
+    "afq_inflate_limits",
     "afq_set_collate_compress",
     "afq_device_warmup", "afq_device_pci_bus_id", "afq_label_rehash_count", "afq_pool_regrow_count", "afq_em_resize_count", "afq_mono_cell_count", "afq_resolve_divert_count",
     "afq_em_instance_counts",
@@ -244,6 +246,14 @@ class AfqConvertStats(C.Structure):
 class AfqSnappyStats(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_blocks_stored", C.c_uint64),
                 ("n_literal_bytes", C.c_uint64), ("n_copies", C.c_uint64)]
+
+
+class AfqInflateStats(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_blocks_empty", C.c_uint64), ("n_stored", C.c_uint64),
+                ("n_fixed", C.c_uint64), ("n_dynamic", C.c_uint64), ("n_literals", C.c_uint64), ("n_copies", C.c_uint64)]
+
+
+AFQ_CONVERT_INFLATE_ON_DEVICE = 1
 
 
 class AfqConvertOpts(C.Structure):

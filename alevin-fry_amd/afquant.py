@@ -371,6 +371,12 @@ def load_library(path: str = LIB_PATH):
     lib.afq_convert_limits.restype = None
     lib.afq_convert.argtypes = [p(_abi.AfqConvertOpts)]
     lib.afq_convert.restype = C.c_int
+    lib.afq_convert_with.argtypes = [p(_abi.AfqConvertOpts), C.c_uint32]
+    lib.afq_convert_with.restype = C.c_int
+    lib.afq_bgzf_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, p(p(C.c_uint8)), p(C.c_uint64), p(_abi.AfqInflateStats)]
+    lib.afq_bgzf_inflate_device.restype = C.c_int
+    lib.afq_inflate_limits.argtypes = [p(C.c_uint32)]
+    lib.afq_inflate_limits.restype = None
     lib.afq_convert_prelude_bytes.argtypes = [p(C.c_char_p), C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
     lib.afq_convert_prelude_bytes.restype = C.c_int64
     lib.afq_view_file.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
@@ -483,6 +489,14 @@ def snappy_decode_limits():
     return {"window": int(out[0]), "threads": int(out[1]), "piece_chunks": int(out[2]), "lds_bytes": int(out[3])}
 
 
+def inflate_limits():
+    """afq_inflate_limits: {"threads", "piece_blocks", "lds_bytes", "blocks_per_workgroup"} of the device BGZF inflater - threads of a
+    workgroup, BGZF blocks of one launch at the most, LDS bytes of a workgroup, blocks a workgroup takes."""
+    out = (C.c_uint32 * 4)()
+    load_library().afq_inflate_limits(out)
+    return {"threads": int(out[0]), "piece_blocks": int(out[1]), "lds_bytes": int(out[2]), "blocks_per_workgroup": int(out[3])}
+
+
 def convert_limits():
     """afq_convert_limits: {"parse_tile", "parse_halo", "lane_alns", "scan_block"} of convert - bytes of a span a walk stages per trip,
     bytes staged behind them, the record count above which the whole wave takes a run, flags a workgroup of the run-number and rank scans takes."""
@@ -491,15 +505,16 @@ def convert_limits():
     return {"parse_tile": int(out[0]), "parse_halo": int(out[1]), "lane_alns": int(out[2]), "scan_block": int(out[3])}
 
 
-def convert(bam, rad_out, filter_best: bool = False, num_threads: int = 8, device: int = 0):
-    """afq_convert: `convert` - the BAM `bam` (CR / UR tags on its records) as the mapper RAD `rad_out`.  Returns the device call's
-    stats; raises AfqError."""
+def convert(bam, rad_out, filter_best: bool = False, num_threads: int = 8, device: int = 0, inflate_on_device: bool = False):
+    """afq_convert_with: `convert` - the BAM `bam` (CR / UR tags on its records) as the mapper RAD `rad_out`.  inflate_on_device: the
+    BGZF blocks are inflated on the device (`--inflate-on-device`) instead of on host threads; the file written and the stats do
+    not depend on it.  Returns the device call's stats; raises AfqError."""
     lib = load_library()
     st = _abi.AfqConvertStats()
     o = _abi.AfqConvertOpts()
     o.bam, o.rad_out, o.num_threads, o.filter_best, o.device = os.fsencode(bam), os.fsencode(rad_out), int(num_threads), int(bool(filter_best)), int(device)
     o.stats_out = C.pointer(st)
-    rc = lib.afq_convert(C.byref(o))
+    rc = lib.afq_convert_with(C.byref(o), _abi.AFQ_CONVERT_INFLATE_ON_DEVICE if inflate_on_device else 0)
     if rc:
         raise AfqError(int(rc), (lib.afq_host_last_error() or b"").decode())
     return {k: int(getattr(st, k)) for k, _ in st._fields_}
@@ -745,6 +760,22 @@ class Quantifier:
         stats = {k: int(getattr(st, k)) for k, _ in st._fields_}
         if on_device:
             return C.cast(o_b, C.c_void_p).value or 0, int(o_n.value), stats
+        try:
+            return C.string_at(o_b, int(o_n.value)), stats
+        finally:
+            self.lib.afq_free(o_b)
+
+    def bgzf_inflate(self, data, shift: int = 0, on_device: bool = False):
+        """afq_bgzf_inflate_device: the bytes of the BGZF file `data` (host bytes), inflated on the device.  Returns (bytes, stats);
+        with on_device ((device pointer, n_bytes), stats) instead - inflated byte x lies at pointer + shift + x, the pointer is
+        16-byte aligned, and the memory is the context's, valid until the next inflate on it or close()."""
+        b = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+        o_b, o_n, st = C.POINTER(C.c_uint8)(), C.c_uint64(), _abi.AfqInflateStats()
+        self._check(self.lib.afq_bgzf_inflate_device(self._h, b.ctypes.data_as(C.c_void_p), b.nbytes, int(shift), 1 if on_device else 0, C.byref(o_b), C.byref(o_n),
+                                                     C.byref(st)))
+        stats = {k: int(getattr(st, k)) for k, _ in st._fields_}
+        if on_device:
+            return (C.cast(o_b, C.c_void_p).value or 0, int(o_n.value)), stats
         try:
             return C.string_at(o_b, int(o_n.value)), stats
         finally:

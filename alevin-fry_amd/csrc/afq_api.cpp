@@ -1487,6 +1487,7 @@ void afq_destroy(afq_ctx* c) {
     for (DevBuf* b : c->acollate.all()) b->release();
     for (DevBuf* b : c->convert.all()) b->release();
     for (DevBuf* b : c->snappy.all()) b->release();
+    for (DevBuf* b : c->inflate.all()) b->release();
     for (auto& p : c->stage) if (p) (void)hipHostFree(p);
     for (auto& ev : c->stage_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->h2d_ev) if (ev) (void)hipEventDestroy(ev);

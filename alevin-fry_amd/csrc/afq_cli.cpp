@@ -28,7 +28,8 @@ static void usage() {
                  "       [--cell-bc-confidence 0.975|a/b] [--device N] [--fill-bytes BYTES]\n"
                  "       afquant collate -i <input-dir> -r <rad-dir> [-t N] [--device N]   (one device fill: -m/--max-records, --memory-limit and\n"
                  "       --collation-mode are accepted and without effect; -c/--compress is not supported)\n"
-                 "       afquant convert -b <file.bam> -o <out.rad> [-t N] [-f] [--device N]   (-f/--filter_best: only a read's best-AS alignments; SAM text is not read)\n"
+                 "       afquant convert -b <file.bam> -o <out.rad> [-t N] [-f] [--device N] [--inflate-on-device]   (-f/--filter_best: only a read's best-AS alignments; SAM text is not read;\n"
+                 "       --inflate-on-device: the BGZF blocks are inflated on the device instead of on -t host threads)\n"
                  "       afquant view -r <file.rad> [-H]   (one line per alignment on stdout; -H/--header: the reference names first)\n"
                  "       afquant infer -c <geqc_counts.mtx> -e <gene_eqclass.txt.gz> -o <output-dir> [--usa] [--quant-subset FILE] [-t N]\n");
 }
@@ -184,6 +185,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && std::strcmp(argv[1], "convert") == 0) {   // bam2rad, src/convert.rs:167-594
         afq_convert_opts vo{};
         vo.num_threads = 8;
+        uint32_t vflags = 0;
         auto need2 = [&](int& i) -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         for (int i = 2; i < argc; ++i) {
             const std::string a = argv[i];
@@ -193,6 +195,7 @@ int main(int argc, char** argv) {
             else if (a == "-t" || a == "--threads") vo.num_threads = (uint32_t)std::atoi(need2(i));
             else if (a == "-f" || a == "--filter_best") vo.filter_best = 1;
             else if (a == "--device") vo.device = (uint32_t)std::atoi(need2(i));
+            else if (a == "--inflate-on-device") vflags |= AFQ_CONVERT_INFLATE_ON_DEVICE;
             else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
         }
         if (!vo.bam || !vo.rad_out) {
@@ -200,7 +203,7 @@ int main(int argc, char** argv) {
             usage();
             return 2;
         }
-        const int rc = afq_convert(&vo);
+        const int rc = afq_convert_with(&vo, vflags);
         if (rc) { std::fprintf(stderr, "afquant convert failed (%d): %s\n", rc, afq_host_last_error()); return 1; }
         return 0;
     }

@@ -54,7 +54,7 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_CONVERT_WALK, K_CONVERT_RUNS, K_CONVERT_PLACE, K_CONVERT_WRITE, K_SNAPPY_BLOCKS, K_SNAPPY_PACK, K_SNAPPY_DECODE, K_CHUNK_TABLE, K_COUNT };
+enum KernelId { K_GATHER = 0, K_DECODE_PAR, K_DECODE, K_SCATTER, K_RESOLVE, K_RESOLVE_BIG, K_PUG, K_CELL_HIST, K_EM, K_BOOT, K_COMPACT, K_ATAC, K_ATAC_PARSE, K_FIX_SLABS, K_P2_SPLIT, K_P2_PART, K_P2_SEARCH, K_P2_LONE, K_P2_GRAPH, K_ASORT_TABLE, K_ASORT_PARSE, K_ASORT_PART, K_ASORT_LEAF, K_ASORT_EMIT, K_GPL_PARSE, K_GPL_COUNT, K_GPL_COMPACT, K_GPL_TABLE, K_GPL_CORRECT, K_COLLATE_TABLE, K_COLLATE_MEASURE, K_COLLATE_SORT, K_COLLATE_SCAN, K_COLLATE_WRITE, K_ACOLLATE_TABLE, K_ACOLLATE_MEASURE, K_ACOLLATE_PLACE, K_ACOLLATE_WRITE, K_AGPL_PARSE, K_AGPL_BINS, K_GPLM_TABLE, K_GPLM_PARSE, K_COLLATEM_TABLE, K_COLLATEM_MEASURE, K_COLLATEM_SORT, K_COLLATEM_SCAN, K_COLLATEM_WRITE, K_CONVERT_WALK, K_CONVERT_RUNS, K_CONVERT_PLACE, K_CONVERT_WRITE, K_SNAPPY_BLOCKS, K_SNAPPY_PACK, K_SNAPPY_DECODE, K_CHUNK_TABLE, K_BGZF_INFLATE, K_COUNT };
 inline constexpr const char* kKernelNames[K_COUNT] = {"k_gather_headers", "k_decode_par", "k_decode", "k_scatter",
                                                       "k_resolve", "k_resolve_big", "k_pug_cell", "k_cell_hist", "k_em", "k_boot", "k_compact", "k_atac_dedup", "k_atac_parse", "k_fix_slabs",
                                                       "k_p2_split", "k_p2_part", "k_p2_search", "k_p2_lone", "k_p2_graph",
@@ -66,7 +66,7 @@ inline constexpr const char* kKernelNames[K_COUNT] = {"k_gather_headers", "k_dec
                                                       "k_gpl_multi_table", "k_gpl_multi_parse",
                                                       "k_collate_multi_table", "k_collate_multi_measure", "k_collate_multi_sort", "k_collate_multi_scan", "k_collate_multi_write",
                                                       "k_convert_walk", "k_convert_runs", "k_convert_place", "k_convert_write",
-                                                      "k_snappy_blocks", "k_snappy_pack", "k_snappy_decode", "k_collated_chunk_table"};
+                                                      "k_snappy_blocks", "k_snappy_pack", "k_snappy_decode", "k_collated_chunk_table", "k_bgzf_inflate"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; bool own_a = true; };   // own_a false: a is the b of the bracket in front (TimerChain) - it goes back to the event pool once
 
@@ -177,6 +177,12 @@ struct SnappyBufs {
     std::vector<DevBuf*> all() { return {&in, &slots, &meta, &off, &stream, &dec_in[0], &dec_in[1], &dec_plan, &dec_stat, &dec_out, &ct_off, &ct_nb, &ct_nr, &ct_bc, &ct_stat}; }
 };
 
+// afq_bgzf_inflate_device's: two pieces of compressed blocks, the plan, status + tallies, the inflated bytes
+struct InflateBufs {
+    DevBuf in[2], plan, stat, out;
+    std::vector<DevBuf*> all() { return {&in[0], &in[1], &plan, &stat, &out}; }
+};
+
 // afq_convert_bam_rad's
 struct ConvertBufs {
     DevBuf spans, scnt, sbase, ssum, roff, ridx, word, head, score, has, rfirst, rbc, rumi, rflag, rna, rmax, stat, key, rec, bsum, ex, dest, out, off, nrec, err, status;
@@ -206,6 +212,7 @@ struct afq_ctx {
     AtacCollateBufs acollate;
     ConvertBufs convert;
     SnappyBufs snappy;
+    InflateBufs inflate;
     void* stage[3] = {nullptr, nullptr, nullptr};          // pinned staging for large host->device input copies
     hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
     // afq_submit: the input crosses PCIe range by range while earlier ranges already run (h2d_ev[i] = range i's bytes landed)

@@ -15,6 +15,7 @@
 //                                span starts at chosen records, in a BAM of a few kilobytes (the RAD written does not depend on it)
 //   AFQ_TEST_SNAPPY_DEC_ROOM_BYTES=n  afq_snappy_frame_decode_device answers as a device with at most n bytes free would: its AFQ_ERR_OOM
 //                                with the sizes, before any allocation or launch - on a test box that always has room
+//   AFQ_TEST_INFLATE_ROOM_BYTES=n  afq_bgzf_inflate_device answers likewise: AFQ_ERR_OOM with the sizes for what it still has to allocate
 // Rounds 1-4 had grown 36 getenv() sites, two thirds of them measurement switches whose alternative had been measured and not
 // kept; those alternatives are gone, as are (round 7) the last hooks that selected one and the per-phase clock builds (a
 // measurement build is `make variant DEFS=...` of a scratch copy), and what is left besides the hooks is:

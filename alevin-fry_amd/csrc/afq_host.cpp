@@ -41,6 +41,7 @@
 
 #include "../../include/afquant.h"
 #include "../../include/afquant_host.h"
+#include "afq_bgzf_plan.h"
 #include "afq_gpl_host.h"
 #include "afq_hooks.h"
 #include "afq_snappy_plan.h"
@@ -1561,36 +1562,13 @@ static int atac_collate_run(const afq_atac_collate_opts* o, bool sz) {
 // ISIZE verified (SAM/BAM specification, sections 4.1 and 4.2: the record layout rests on that text alone).  The records are
 // the device's (afq_convert_bam_rad).
 namespace {
-struct BgzfBlock { size_t data_off, data_len; uint64_t out_off; uint32_t isize, crc; };
 inline uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 inline uint32_t le32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 
+// the plan of afq_bgzf_plan.h with its refusal as this file's
 int bgzf_plan(const uint8_t* in, size_t n, std::vector<BgzfBlock>& blocks, uint64_t& total) {
-    total = 0;
-    for (size_t p = 0; p < n;) {
-        const std::string at = "BGZF block " + std::to_string(blocks.size()) + ": ";
-        if (n - p < 18) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated: " + std::to_string(n - p) + " bytes where a block header has 18");
-        const uint8_t* h = in + p;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return hfail(AFQ_ERR_BAD_INPUT, at + "bad gzip magic (1f 8b 08 with an extra field is expected)");
-        const size_t xlen = le16(h + 10);
-        if (n - p < 12 + xlen) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated inside the extra field");
-        long bsize = -1;
-        for (size_t e = 12; e + 4 <= 12 + xlen;) {
-            const size_t slen = le16(h + e + 2);
-            if (h[e] == 'B' && h[e + 1] == 'C' && slen == 2 && e + 6 <= 12 + xlen) bsize = (long)le16(h + e + 4);
-            e += 4 + slen;
-        }
-        if (bsize < 0) return hfail(AFQ_ERR_BAD_INPUT, at + "no BC extra field: not a BGZF block");
-        const size_t blk = (size_t)bsize + 1;
-        if (blk < 12 + xlen + 8) return hfail(AFQ_ERR_BAD_INPUT, at + "BSIZE is smaller than the block's own header and trailer");
-        if (n - p < blk) return hfail(AFQ_ERR_BAD_INPUT, at + "truncated: the block has " + std::to_string(blk) + " bytes, the file " + std::to_string(n - p) + " more");
-        BgzfBlock b{p + 12 + xlen, blk - (12 + xlen) - 8, total, le32(h + blk - 4), le32(h + blk - 8)};
-        if (b.isize > 65536) return hfail(AFQ_ERR_BAD_INPUT, at + "ISIZE " + std::to_string(b.isize) + " is above the 65536 bytes of a BGZF block");
-        total += b.isize;
-        blocks.push_back(b);
-        p += blk;
-    }
-    return 0;
+    std::string err;
+    return ::bgzf_plan(in, n, blocks, total, err) ? 0 : hfail(AFQ_ERR_BAD_INPUT, err);
 }
 
 int bgzf_inflate(const uint8_t* in, const std::vector<BgzfBlock>& blocks, uint8_t* out, unsigned nthreads) {
@@ -1701,8 +1679,39 @@ int64_t afq_convert_prelude_bytes(const char* const* ref_names, uint64_t n_ref, 
     return (int64_t)b.size();
 }
 
-int afq_convert(const afq_convert_opts* o) {
+namespace {
+// the BAM header at p[0, n): magic, l_text, text, n_ref x (l_name, name, l_ref) -> the names and where the records begin
+int convert_bam_header(const uint8_t* p, size_t n, std::vector<std::string>& names, int32_t& n_ref, size_t& hdr_len) {
+    names.clear();
+    Cursor c{p, n};
+    const uint32_t magic = c.get<uint32_t>();
+    if (!c.ok || magic != 0x014d4142u) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad magic (BAM\\1 is expected)");
+    const int32_t l_text = c.get<int32_t>();
+    if (!c.ok || l_text < 0 || (uint64_t)l_text > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: the text runs past the file");
+    c.p += (size_t)l_text;
+    n_ref = c.get<int32_t>();
+    if (!c.ok || n_ref < 0) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad reference count");
+    for (int32_t i = 0; i < n_ref; ++i) {
+        const int32_t l_name = c.get<int32_t>();
+        if (!c.ok || l_name < 1 || (uint64_t)l_name > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + ": the name runs past the file");
+        std::string nm = c.str((size_t)l_name);
+        nm.resize(std::strlen(nm.c_str()));   // (l_name counts the NUL)
+        if (nm.size() > 0xFFFF) return hfail(AFQ_ERR_UNSUPPORTED, "BAM header: reference " + std::to_string(i) + ": a name of 64 KiB or more does not fit the RAD header");
+        names.push_back(std::move(nm));
+        (void)c.get<int32_t>();   // l_ref
+        if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + " runs past the file");
+    }
+    hdr_len = c.p;
+    return 0;
+}
+}  // namespace
+
+int afq_convert(const afq_convert_opts* o) { return afq_convert_with(o, 0); }
+
+int afq_convert_with(const afq_convert_opts* o, uint32_t flags) {
+    if (flags & ~AFQ_CONVERT_INFLATE_ON_DEVICE) return hfail(AFQ_ERR_INVALID_ARG, "afq_convert_with: unknown flag bits (AFQ_CONVERT_INFLATE_ON_DEVICE is the one there is)");
     if (!o || !o->bam || !o->rad_out) return hfail(AFQ_ERR_INVALID_ARG, "null option: the BAM (-b) and the output RAD (-o) are required");
+    const bool on_device = (flags & AFQ_CONVERT_INFLATE_ON_DEVICE) != 0;
     const std::string in = o->bam, outp = o->rad_out;
     if (ends_with(in, ".sam") || ends_with(in, ".SAM")) return hfail(AFQ_ERR_UNSUPPORTED, "convert: SAM text input is not supported; only BAM is read (convert the file to BAM first)");
     if (!ends_with(in, ".bam") && !ends_with(in, ".BAM")) return hfail(AFQ_ERR_BAD_INPUT, "unsupported input file format, must end with bam/BAM or sam/SAM");
@@ -1714,36 +1723,60 @@ int afq_convert(const afq_convert_opts* o) {
     std::vector<BgzfBlock> blocks;
     uint64_t total = 0;
     if (int rc = bgzf_plan(mf.p, mf.n, blocks, total)) return rc;
-    const unsigned nthreads = o->num_threads > 1 ? o->num_threads - 1 : 1;   // convert.rs:205-210
-    std::fprintf(stderr, "parsing BAM file using %u decompression threads\n", nthreads);
-    std::unique_ptr<uint8_t[]> plain(new (std::nothrow) uint8_t[total + 1]);
-    if (!plain) return hfail(AFQ_ERR_OOM, "convert: " + std::to_string(total) + " bytes for the inflated BAM could not be allocated");
-    if (int rc = bgzf_inflate(mf.p, blocks, plain.get(), nthreads)) return rc;
-    pc.lap("convert: BGZF plan + inflate");
-    // ---- the BAM header: magic, l_text, text, n_ref x (l_name, name, l_ref)
-    Cursor c{plain.get(), (size_t)total};
-    const uint32_t magic = c.get<uint32_t>();
-    if (!c.ok || magic != 0x014d4142u) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad magic (BAM\\1 is expected)");
-    const int32_t l_text = c.get<int32_t>();
-    if (!c.ok || l_text < 0 || (uint64_t)l_text > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: the text runs past the file");
-    c.p += (size_t)l_text;
-    const int32_t n_ref = c.get<int32_t>();
-    if (!c.ok || n_ref < 0) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: bad reference count");
+    std::unique_ptr<uint8_t[]> plain;   // the closed door: the inflated file; the open one: the record stream, copied back
     std::vector<std::string> names;
-    for (int32_t i = 0; i < n_ref; ++i) {
-        const int32_t l_name = c.get<int32_t>();
-        if (!c.ok || l_name < 1 || (uint64_t)l_name > c.n - c.p) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + ": the name runs past the file");
-        std::string nm = c.str((size_t)l_name);
-        nm.resize(std::strlen(nm.c_str()));   // (l_name counts the NUL)
-        if (nm.size() > 0xFFFF) return hfail(AFQ_ERR_UNSUPPORTED, "BAM header: reference " + std::to_string(i) + ": a name of 64 KiB or more does not fit the RAD header");
-        names.push_back(std::move(nm));
-        (void)c.get<int32_t>();   // l_ref
-        if (!c.ok) return hfail(AFQ_ERR_BAD_INPUT, "BAM header: reference " + std::to_string(i) + " runs past the file");
+    int32_t n_ref = 0;
+    size_t hdr_len = 0;
+    CtxPtr ctx;
+    const uint8_t* d_stream = nullptr;   // the open door: the record stream on the device
+    if (!on_device) {
+        const unsigned nthreads = o->num_threads > 1 ? o->num_threads - 1 : 1;   // convert.rs:205-210
+        std::fprintf(stderr, "parsing BAM file using %u decompression threads\n", nthreads);
+        plain.reset(new (std::nothrow) uint8_t[total + 1]);
+        if (!plain) return hfail(AFQ_ERR_OOM, "convert: " + std::to_string(total) + " bytes for the inflated BAM could not be allocated");
+        if (int rc = bgzf_inflate(mf.p, blocks, plain.get(), nthreads)) return rc;
+        pc.lap("convert: BGZF plan + inflate");
+        if (int rc = convert_bam_header(plain.get(), (size_t)total, names, n_ref, hdr_len)) return rc;
+    } else {
+        // The leading blocks are inflated here until the BAM header is whole - one block, then twice as many as the time before -
+        // for the header's length: the device lays the file down so that the first record stands at a 16-byte-aligned address.
+        // A header that does not parse with every block inflated is the file's fault; its sentence waits behind the device's
+        // verdict on the blocks, as it does behind the host inflate's.
+        std::fprintf(stderr, "parsing BAM file with the BGZF blocks inflated on the device\n");
+        pc.lap("convert: BGZF plan");
+        if (int rc = open_fill_ctx(o->device, 0, ctx)) return rc;
+        std::vector<uint8_t> head;
+        int hdr_rc = 0;
+        std::string hdr_err;
+        for (size_t have = 0, want = 1;; want = 2 * have) {
+            want = std::min(want, blocks.size());
+            if (want > have) {
+                const std::vector<BgzfBlock> sub(blocks.begin(), blocks.begin() + want);
+                head.assign((size_t)(sub.back().out_off + sub.back().isize) + 1, 0);
+                if (int rc = bgzf_inflate(mf.p, sub, head.data(), 1)) return rc;
+                head.pop_back();
+                have = want;
+            }
+            hdr_rc = convert_bam_header(head.data(), head.size(), names, n_ref, hdr_len);
+            if (!hdr_rc || have == blocks.size()) break;
+        }
+        if (hdr_rc) { hdr_err = g_herr; hdr_len = 0; }
+        const uint32_t shift = (uint32_t)((16 - hdr_len % 16) % 16);
+        uint8_t* d = nullptr;
+        uint64_t dn = 0;
+        if (int rc = afq_bgzf_inflate_device(ctx.get(), mf.p, mf.n, shift, 1, &d, &dn, nullptr)) return hfail(rc, afq_last_error(ctx.get()));
+        pc.lap("convert: device inflate");
+        if (hdr_rc) return hfail(hdr_rc, hdr_err);
+        d_stream = d + shift + hdr_len;
+        const uint64_t rest = total - hdr_len;
+        plain.reset(new (std::nothrow) uint8_t[hdr_len + rest + 1]);
+        if (!plain) return hfail(AFQ_ERR_OOM, "convert: " + std::to_string(total) + " bytes for the inflated BAM could not be allocated");
+        if (int rc = afq_bgzf_resident_to_host(ctx.get(), shift, hdr_len, plain.get() + hdr_len, rest)) return hfail(rc, afq_last_error(ctx.get()));
     }
     std::fprintf(stderr, "ref count: %d \n", n_ref);
     // ---- the first record's lengths, the span table (one hop per record, four bytes read of each)
-    const uint8_t* stream = plain.get() + c.p;
-    const uint64_t sn = total - c.p;
+    const uint8_t* stream = plain.get() + hdr_len;
+    const uint64_t sn = total - hdr_len;
     if (sn == 0) return hfail(AFQ_ERR_BAD_INPUT, "bam file had no records!");
     uint32_t cblen = 0, ulen = 0;
     if (int rc = convert_first_lengths(stream, sn, cblen, ulen)) return rc;
@@ -1760,14 +1793,14 @@ int afq_convert(const afq_convert_opts* o) {
         }
     }
     if (spans.size() >= (1ull << 32)) return hfail(AFQ_ERR_UNSUPPORTED, "convert: 2^32 or more spans");
-    pc.lap("convert: header + span table");
+    pc.lap(on_device ? "convert: stream D2H + span table" : "convert: header + span table");
     // ---- the device: one fill
-    CtxPtr ctx;
-    if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
+    if (!on_device)
+        if (int rc2 = open_fill_ctx(o->device, 0, ctx)) return rc2;
     uint8_t* ob = nullptr; uint64_t on = 0, n_chunks = 0, *ooff = nullptr; uint32_t* onrec = nullptr;
     afq_convert_stats st{};
-    int rc = afq_convert_bam_rad(ctx.get(), stream, sn, spans.data(), (uint32_t)spans.size(), (uint32_t)n_ref, convert_width(cblen), convert_width(ulen), o->filter_best != 0, 0,
-                                 &ob, &on, &ooff, &onrec, &n_chunks, &st);
+    int rc = afq_convert_bam_rad(ctx.get(), on_device ? d_stream : stream, sn, spans.data(), (uint32_t)spans.size(), (uint32_t)n_ref, convert_width(cblen), convert_width(ulen),
+                                 o->filter_best != 0, on_device ? 1 : 0, &ob, &on, &ooff, &onrec, &n_chunks, &st);
     if (rc) return hfail(rc, afq_last_error(ctx.get()));
     struct Freer { void *a, *b, *c; ~Freer() { afq_free(a); afq_free(b); afq_free(c); } } fr{ob, ooff, onrec};
     pc.lap("convert: device");

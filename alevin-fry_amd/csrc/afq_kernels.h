@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "afq_common.h"
+#include "afq_inflate_elem.h"
 
 // the scattering decoder's tile: slabs per wave (four waves a tile) and the keys its LDS stage holds (measurement builds override them)
 #ifndef AFQ_DTILE_SLABS
@@ -456,6 +457,18 @@ struct SnappyDecChunk { uint64_t in_off, out_off; uint32_t in_len, ulen, crc, co
 // status: min over the refused chunks of (first_index + chunk) << 8 | SnappyDecodeCode (afq_snappy_elem.h); stats[4]: chunks,
 // stored chunks, literal bytes, copy elements - of the chunks that decoded
 void launch_snappy_decode(hipStream_t s, const uint8_t* in, const SnappyDecChunk* plan, uint32_t n_chunks, uint64_t first_index, uint8_t* dst, uint64_t* status, uint64_t* stats);
+
+// the BGZF inflater (afq_inflate.hip): the blocks of a BGZF file on the device and the host's plan of them -> their bytes on the device
+constexpr uint32_t kInflateThreads = 64;          // a workgroup is one wave and takes one BGZF block
+constexpr uint32_t kInflateBlocksPerWg = 1;
+constexpr uint32_t kInflateWindow = 8192;         // bytes of a block's payload staged in LDS per trip to memory
+constexpr uint32_t kInflatePieceBlocks = 4096;    // BGZF blocks of one launch at the most (a piece of the file; afq_bgzf_inflate_device)
+constexpr uint32_t kInflateLds = (kInflateMaxOut + 16) + (kInflateWindow + 32) + 1024 + (uint32_t)sizeof(InflateTables);   // staged output, window, CRC table, decode tables: two workgroups share a CU's 160 KiB
+struct BgzfDecBlock { uint64_t in_off, out_off; uint32_t in_len, isize, crc, pad; };   // in_off from the launch's `in`, out_off from its `dst`
+// status[0]: min over the refused blocks of (first_index + block) << 8 | InflateCode (afq_inflate_elem.h); status[1]: min over the
+// blocks that ended short of ISIZE of (first_index + block) << 32 | bytes produced; stats[7]: blocks, blocks of ISIZE 0, stored,
+// fixed and dynamic deflate blocks, literals, copies - of the blocks that decoded
+void launch_bgzf_inflate(hipStream_t s, const uint8_t* in, const BgzfDecBlock* plan, uint32_t n_blocks, uint64_t first_index, uint8_t* dst, uint64_t* status, uint64_t* stats);
 
 // the chunk table of a collated record stream on the device (afq_snappy.hip, k_collated_chunk_table): one wave hops the headers
 constexpr uint32_t kChunkTableTile = 16384, kChunkTableShort = 1024, kChunkTableHalo = 24;   // bytes of the stream staged per trip; a header at the tile's last byte and the 8 bytes at + 12 lie in the halo

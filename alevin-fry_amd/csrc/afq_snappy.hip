@@ -23,6 +23,7 @@
 // And the way back, k_snappy_decode (below, with its own account): a planned frame stream on the device -> its bytes.
 #include <hip/hip_runtime.h>
 
+#include "afq_block_codec.h"
 #include "afq_common.h"
 #include "afq_kernels.h"
 #include "afq_prims.h"
@@ -33,68 +34,22 @@ namespace afq {
 
 namespace {
 
-constexpr uint32_t kCrcPoly = 0x82F63B78u;     // CRC-32C, reflected
 constexpr uint32_t kSliceFull = kSnappyBlock / 64;
 static_assert(kSnappyBlock <= 65536 && kSliceFull % 4 == 0, "a frame chunk holds at most 65536 bytes; a full chunk's slices are whole words");
 static_assert(kSnappySlot >= 32 + kSnappyBlock + kSnappyBlock / 6 && kSnappySlot % 16 == 0, "a slot holds snappy's worst case");
 
-// a b modulo the polynomial; bit 31 is x^0 (the register's bit order)
-__host__ __device__ constexpr uint32_t gf_mul(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        if (a & m) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ kCrcPoly : b >> 1;
-    }
-    return p;
-}
-// x^(8 n): what n zero bytes do to the register
-__host__ __device__ constexpr uint32_t gf_pow_x8(uint32_t n) {
-    uint32_t r = 0x80000000u, b = 0x00800000u;
-    for (; n; n >>= 1) {
-        if (n & 1u) r = gf_mul(r, b);
-        b = gf_mul(b, b);
-    }
-    return r;
-}
 struct ShiftTab { uint32_t v[64]; };
 constexpr ShiftTab make_shift_tab() {
     ShiftTab t{};
-    for (uint32_t k = 0; k < 64; ++k) t.v[k] = gf_pow_x8(k * kSliceFull);
+    for (uint32_t k = 0; k < 64; ++k) t.v[k] = gf_pow_x8<kCrc32cPoly>(k * kSliceFull);
     return t;
 }
 __constant__ ShiftTab c_shift = make_shift_tab();   // [k]: k full slices behind a lane's
 
-__device__ __forceinline__ uint32_t ld4(const uint8_t* p) {
-    uint32_t w;
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
-
-// the bytewise CRC table, 256 words, filled by one wave
-__device__ __forceinline__ void crc_table_fill(uint32_t* s_tab, uint32_t lane) {
-    for (uint32_t i = lane; i < 256; i += 64) {
-        uint32_t c = i;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
-        s_tab[i] = c;
-    }
-}
-// The masked CRC-32C of src[0, n) by one wave: lane l takes the slice [l sl, (l + 1) sl) (sl a multiple of 4, 64 sl >= n), the
-// slices combine by the linearity of the register.  full: n = kSnappyBlock and sl = kSliceFull, the shifts are constants.
+// The masked CRC-32C of src[0, n) by one wave (wave_crc of afq_block_codec.h).  full: n = kSnappyBlock and sl = kSliceFull, the
+// shifts are constants.
 __device__ __forceinline__ uint32_t wave_masked_crc(const uint8_t* src, uint32_t n, uint32_t sl, bool full, const uint32_t* s_tab, uint32_t lane) {
-    const uint32_t b = min(n, lane * sl), e = min(n, b + sl);
-    uint32_t st = lane == 0 ? 0xFFFFFFFFu : 0u;
-    uint32_t p = b;
-    for (; p + 4 <= e; p += 4) {
-        st ^= ld4(src + p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) st = s_tab[st & 255u] ^ (st >> 8);
-    }
-    for (; p < e; ++p) st = s_tab[(st ^ src[p]) & 255u] ^ (st >> 8);
-    st = gf_mul(st, full ? c_shift.v[63 - lane] : gf_pow_x8(n - e));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) st ^= __shfl_xor(st, d);
-    const uint32_t crc = ~st;
+    const uint32_t crc = wave_crc<kCrc32cPoly>(src, n, sl, full ? c_shift.v : nullptr, s_tab, lane);
     return ((crc >> 15) | (crc << 17)) + 0xa282ead8u;
 }
 
@@ -155,7 +110,7 @@ __global__ __launch_bounds__(64) void k_snappy_blocks(const uint8_t* __restrict_
     const uint64_t left = n_total - at;
     const uint32_t n = left < kSnappyBlock ? (uint32_t)left : kSnappyBlock;   // 1..kSnappyBlock
     // ---- CRC-32C of the chunk
-    crc_table_fill(s_tab, lane);
+    crc_table_fill<kCrc32cPoly>(s_tab, lane);
     __syncthreads();
     const bool full = n == kSnappyBlock;
     const uint32_t masked_crc = wave_masked_crc(src, n, full ? kSliceFull : (((n + 63) / 64 + 3) & ~3u), full, s_tab, lane);
@@ -280,23 +235,6 @@ __global__ __launch_bounds__(kPackNT) void k_snappy_pack(const uint8_t* __restri
 // any residue of the destination, 16-byte stores between a bytewise head and tail: the output is staged at the destination's
 // own residue, so both sides of a 16-byte move are aligned.  A chunk that is refused writes nothing and enters
 // `index << 8 | code` into the status word by atomicMin: the lowest bad chunk is named whatever the schedule.
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// body[at, at + n) into the window, at the residue of its address: 16-byte loads between a bytewise head and tail, none of them
-// outside the n bytes.  Returns where body[at] stands.
-__device__ __forceinline__ const uint8_t* window_fill(uint4* s_in, const uint8_t* g, uint32_t n, uint32_t lane) {
-    __syncthreads();   // the reads of what the window held
-    uint8_t* sw = (uint8_t*)s_in + ((uintptr_t)g & 15);
-    const uint32_t head = min(n, (uint32_t)((16 - ((uintptr_t)g & 15)) & 15));
-    if (lane < head) sw[lane] = g[lane];
-    const uint32_t nvec = (n - head) / 16;
-    for (uint32_t k = lane; k < nvec; k += kSnappyDecThreads) *(uint4*)(sw + head + 16 * k) = *(const uint4*)(g + head + 16ull * k);
-    const uint32_t done = head + 16 * nvec;
-    if (lane < n - done) sw[done + lane] = g[done + lane];
-    __syncthreads();
-    return sw;
-}
-
 __global__ __launch_bounds__(kSnappyDecThreads) void k_snappy_decode(const uint8_t* __restrict__ in, const SnappyDecChunk* __restrict__ plan, uint64_t first_index,
                                                                      uint8_t* __restrict__ dst, unsigned long long* __restrict__ status, unsigned long long* __restrict__ stats) {
     __shared__ uint4 s_out[(kSnappyBlock + 16) / 16];
@@ -309,14 +247,14 @@ __global__ __launch_bounds__(kSnappyDecThreads) void k_snappy_decode(const uint8
     uint8_t* d = dst + c.out_off;
     const uint32_t in_len = uni(c.in_len), ulen = uni(c.ulen);
     uint8_t* so = (uint8_t*)s_out + ((uintptr_t)d & 15);   // so[i] is output byte i
-    crc_table_fill(s_tab, lane);
+    crc_table_fill<kCrc32cPoly>(s_tab, lane);
     uint32_t code = kSnappyOk, n_lit = 0, n_cp = 0;
     // the window holds body[wbase, wend) at sw
     uint32_t wbase = 0, wend = 0;
     const uint8_t* sw = (const uint8_t*)s_in;
     auto stage = [&](uint32_t at) {   // at < in_len
         const uint32_t n = min(kSnappyDecWindow, in_len - at);
-        sw = window_fill(s_in, body + at, n, lane);
+        sw = window_fill(s_in, body + at, n, lane, kSnappyDecThreads);
         wbase = at; wend = at + n;
     };
     // 8 bytes of the body from p on in one trip (aligned words of the window; what lies behind wend is not looked at)
@@ -393,20 +331,13 @@ __global__ __launch_bounds__(kSnappyDecThreads) void k_snappy_decode(const uint8
     }
     __syncthreads();
     if (!code) {
-        uint32_t sl = ((ulen + 63) / 64 + 3) & ~3u;
-        if (!(sl & 4u)) sl += 4;   // an odd number of words from slice to slice: the lanes' reads spread over the banks
-        if (wave_masked_crc(so, ulen, sl, false, s_tab, lane) != c.crc) code = kSnappyCrcMismatch;
+        if (wave_masked_crc(so, ulen, crc_slice_lds(ulen), false, s_tab, lane) != c.crc) code = kSnappyCrcMismatch;
     }
     if (code) {
         if (lane == 0) atomicMin(status, (unsigned long long)(first_index + blockIdx.x) << 8 | code);
         return;
     }
-    const uint32_t head = min(ulen, (uint32_t)((16 - ((uintptr_t)d & 15)) & 15));
-    if (lane < head) d[lane] = so[lane];
-    const uint32_t nvec = (ulen - head) / 16;
-    for (uint32_t k = lane; k < nvec; k += kSnappyDecThreads) *(uint4*)(d + head + 16 * k) = *(const uint4*)(so + head + 16 * k);
-    const uint32_t done = head + 16 * nvec;
-    if (lane < ulen - done) d[done + lane] = so[done + lane];
+    staged_write_out(d, so, ulen, lane, kSnappyDecThreads);
     if (lane < 4) atomicAdd(&stats[lane], (unsigned long long)(lane == 0 ? 1u : lane == 1 ? (c.compressed ? 0u : 1u) : lane == 2 ? n_lit : n_cp));
 }
 

@@ -660,6 +660,32 @@ int afq_collated_chunk_table(afq_ctx* ctx, const uint8_t* d_bytes, uint64_t n, u
  * the memory plan counts the encoder's buffers.  0 (the default): nothing changes. */
 void afq_set_collate_compress(afq_ctx* ctx, int on);
 
+/* The bytes of a BGZF file (SAM/BAM specification 4.1: gzip members of at most 64 KiB with a BC extra field), inflated on the
+ * device (afq_inflate.hip, k_bgzf_inflate: one workgroup per BGZF block, the block built in LDS from a raw deflate stream of
+ * stored, fixed and dynamic blocks, its CRC-32 and ISIZE checked there).  `file` is host memory; the host plans it by its block
+ * headers (the plan of afq_convert) and it crosses in pieces of whole blocks - at most afq_inflate_limits()[1] blocks, one launch
+ * a piece, never more than two pieces of compressed bytes on the device.  shift (0..15): inflated byte x lies at
+ * (*out)[shift + x] of the device buffer, whose base is 16-byte aligned.  Bytes behind a payload's final deflate block are
+ * accepted, as zlib accepts them.
+ * out_on_device = 0: *out is malloc'd host memory holding the *out_n inflated bytes (afq_free).
+ * out_on_device = 1: *out is device memory of the context, valid until the next inflate on it or afq_destroy.
+ * Compressed pieces, plan, status and inflated bytes that the inflater has to allocate and the device does not have free are
+ * AFQ_ERR_OOM with the sizes before any allocation or launch.  A file the plan refuses is AFQ_ERR_BAD_INPUT with afq_convert's
+ * sentence; so is a bad block: "BGZF block N: ", N the lowest block that is refused, and "bad CRC32", "ISIZE says I bytes, the
+ * deflate stream holds P", or "the deflate stream is corrupt or longer than ISIZE (...)" with what the parser found; nothing out
+ * of range is read or written for any payload, a refused block writes nothing, and the context serves again. */
+typedef struct afq_inflate_stats {
+    uint64_t n_in, n_out;                   /* bytes of the file, bytes inflated               */
+    uint64_t n_blocks, n_blocks_empty;      /* BGZF blocks; of those with ISIZE 0              */
+    uint64_t n_stored, n_fixed, n_dynamic;  /* deflate blocks by type                          */
+    uint64_t n_literals, n_copies;          /* over fixed and dynamic blocks                   */
+} afq_inflate_stats;
+int afq_bgzf_inflate_device(afq_ctx* ctx, const uint8_t* file, size_t n, uint32_t shift, int out_on_device, uint8_t** out, uint64_t* out_n,
+                            afq_inflate_stats* stats);
+/* out[0] = threads of a workgroup, out[1] = BGZF blocks of a launch at the most, out[2] = LDS bytes of a workgroup, out[3] =
+ * blocks a workgroup takes.  For tests. */
+void afq_inflate_limits(uint32_t out[4]);
+
 /*
  * Kernel timing of the last collected batch (HIP events on the context's own
  * stream; only when cfg.profile != 0).  Fills up to `cap` entries; returns the

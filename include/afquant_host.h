@@ -329,8 +329,8 @@ typedef struct afq_convert_opts {
     uint32_t device;
     struct afq_convert_stats* stats_out;   /* optional */
 } afq_convert_opts;
-/* Runs the whole `convert` sub-command in ONE device fill: the BGZF container is inflated on the host (every block's CRC32 and
- * ISIZE verified; an empty block mid-file and a missing EOF marker are accepted), the BAM header read, the lengths of CR / UR of the
+/* Runs the whole `convert` sub-command in ONE device fill: the BGZF container is inflated on the host - or, through afq_convert_with
+ * below, on the device - (every block's CRC32 and ISIZE verified; an empty block mid-file and a missing EOF marker are accepted), the BAM header read, the lengths of CR / UR of the
  * file's first record taken for cblen / ulen, the records handed to afq_convert_bam_rad (include/afquant.h has the record semantics
  * and their errors), and the prelude (convert.rs:238-370) and chunks written only after the device call succeeded.
  * AFQ_ERR_UNSUPPORTED: a path ending in .sam / .SAM.  AFQ_ERR_BAD_INPUT: any other ending ("unsupported input file format, must end
@@ -339,6 +339,17 @@ typedef struct afq_convert_opts {
  * 0 or above 32, "record <i>: ..." for a block_size that runs past the stream; also an output file that cannot be created or
  * written ("could not write ..."): the library has no code for I/O failures, and its other writers report theirs the same way. */
 int afq_convert(const afq_convert_opts* opts);
+/* afq_convert with flags: afq_convert(o) is afq_convert_with(o, 0); unknown flag bits are AFQ_ERR_INVALID_ARG.
+ * AFQ_CONVERT_INFLATE_ON_DEVICE (`convert --inflate-on-device`): the BGZF blocks are inflated on the device
+ * (afq_bgzf_inflate_device of include/afquant.h) and the inflated bytes never cross from host to device.  The host plans the
+ * blocks, inflates only the leading ones with zlib until the BAM header is whole, and has the device lay the file down so that
+ * the first record stands at a 16-byte-aligned address; the record stream comes back once, for the first record's lengths and
+ * the span table, and afq_convert_bam_rad runs on the resident stream.  The RAD file, the stats and the stderr lines are
+ * afq_convert's, except that the line about decompression threads says that the device inflates; a bad block is named with
+ * afq_convert's words where they do not come from zlib ("bad CRC32", "ISIZE says ..."), otherwise with "the deflate stream is
+ * corrupt or longer than ISIZE (<what the device's parser found>)". */
+#define AFQ_CONVERT_INFLATE_ON_DEVICE 1u
+int afq_convert_with(const afq_convert_opts* opts, uint32_t flags);
 /* The prelude afq_convert writes in front of the chunks (convert.rs:238-370): is_paired = 0, the reference names, num_chunks, the
  * file tags cblen:u16 and ulen:u16, the read tags b and u (1, 2, 4 or 8 bytes for lengths 1-4, 5-8, 9-16, 17-32), the alignment
  * tag compressed_ori_refid:u32, the two values.  Returns its length (out may be NULL), or a negative AFQ_ERR_ code.  For tests:
